@@ -15,7 +15,7 @@ config's GLOBAL batch (cfg1 256, cfg2 1024, cfg3 512, cfg4 2048) is split contig
 (``parallel.shard_bounds``), so ``--config cfg2 --scaling strong --gpus 8`` is BASELINE configs[2] to the letter.
 Clips shard embarrassingly over the batch and the path has no exchange step, so ``value`` has NO data-path collective:
 every rank keeps its (B_r,F,T') features on its own GPU, exactly where a data-parallel classifier consumes them.  At N > 1
-the same run then times the K steps again WITH north_star's "trivial gather" of the outputs, one per step on a side stream,
+a ``--full`` run then times the K steps again WITH north_star's "trivial gather" of the outputs, one per step on a side stream,
 overlapped with the next step's kernels, in two collective modes by default (``--gather-mode collective``) and a third on request
 (``--gather-mode all``: it maps peer memory across processes -- kept out of the default run so that a first contact with an 8-GPU node
 cannot lose the whole line to an experiment):
@@ -31,6 +31,8 @@ complete when it returns); the copy mode is a transport experiment without that 
 (``ms_per_step`` with the gather minus without) are under ``gather.modes`` ("frames/s with and without the gather").
 
     python bench.py                                  # N = 1, cfg1
+    python bench.py --full                           # + the longer region, rooflines, CPU baseline
+    python bench.py --dump-outputs DIR               # + the last timed step's features as DIR/features.npy
     python bench.py --gpus 8 --steps 20 --warmup 5    # self-launches one rank per GPU (torch.distributed.run, free port)
     python bench.py --config cfg2 --scaling strong --gpus 8
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -40,7 +42,12 @@ Before the W warm-up steps the same step runs ``--spinup-steps`` times (default:
 untimed, reported in the line as ``spinup_steps``): a fresh process starts at idle clocks and K timed steps of 0.3 ms would
 otherwise be over before the GPU's power state has settled.  The timed region is exactly K steps between the barriers.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+A plain run sets up, spins up, warms up, times the K steps and prints the line (``value``, ``ms_per_step`` and the workload);
+``--dump-outputs DIR`` also writes the features the last timed step returned (``dump_outputs``: same arguments, same inputs
+and parameters, so two builds compare output for output).  ``--full`` adds everything else the line can carry: the 25x longer
+region (``ms_per_step_long``), the rooflines (their own profiled runs), the CPU baseline and, at N > 1, the gather passes.
+
+Prints ONE JSON line on rank 0 (contract in the task statement); with ``--full`` it carries these extra objects:
   roofline     -- dominant kernel of THIS config (leaf_fft_wg_kernel; leaf_fft_wg4k_kernel at cfg2).  The fused path is
                   bound by fp32 VALU issue, not by HBM: ``bound`` = "valu_fp32", ``achieved`` = fp32 flops the
                   kernel EXECUTES per launch / its HIP-event time, ``peak`` = 157.3 TFLOP/s, ``frac`` = achieved / peak
@@ -49,7 +56,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
                   the reference's direct-form flops to the executed ones is reported separately
                   (``algorithmic_speedup_vs_direct_form``), as are the PMC-derived figures of the committed rocprofv3
                   passes of this config (``traffic``, ``traffic_source``, ``traffic_ratio``, ``valu_issue_frac_pmc``).
-  roofline_hbm -- the HBM view BASELINE.json's metric names: algorithmic bytes per step / step time vs 8 TB/s.
+  roofline_hbm -- the HBM view BASELINE.json's metric names: algorithmic bytes per step / step time vs 8 TB/s (from
+                  the timed steps alone: in a plain run's line too).
   cpu_baseline -- the CPU oracle (torch CPU port of the reference graph) timed on this host's cores on a
                   bounded sample of the same workload (rank 0, N = 1 only), plus BASELINE configs[0] (batch 4) at cfg1.
 """
@@ -127,6 +135,12 @@ def main():
                          "without them and every rank exits")
     ap.add_argument("--compute-reserve-cus", type=int, default=0,
                     help="CUs left free in the pass that defines `value` (0: the compute kernels fill the chip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the 25x longer region, the rooflines, the CPU baseline and, "
+                         "at N > 1, the gather passes (a plain run times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the features the last timed step returned as DIR/<name>.npy (float32; a fixed sample of clips "
+                         "beyond 64 MB)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -213,7 +227,7 @@ def main():
         rel = (B * T * F) / (256 * 16000 * 40) * (2.0 if SR > 16000 else 1.0)
         args.spinup_steps = max(20, min(800, int(800 / max(rel, 1e-3))))
 
-    do_gather = use_dist and not args.no_gather
+    do_gather = use_dist and not args.no_gather and args.full
     comm_stream = torch.cuda.Stream(device=dev) if do_gather else None
     comm_done = [None, None]
     gathered = [torch.empty(global_batch, F, TP, device=dev, dtype=out_dtype) for _ in range(2)] if do_gather else None
@@ -262,6 +276,8 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
+    last_out = [None]
+
     def timed_pass(gather, algo, steps=None):
         steps = args.steps if steps is None else steps
         """W warm-up + exactly K timed steps between barriers; returns (max over ranks, min over ranks) of the elapsed time."""
@@ -275,8 +291,10 @@ def main():
             step(i, gather)
         sync()                                      # barrier + synchronize: every rank starts its K steps together
         t0 = time.perf_counter()
-        for i in range(steps):
+        for i in range(steps - 1):
             step(i, gather)
+        if steps > 0:
+            last_out[0] = step(steps - 1, gather)   # what the caller of the last timed step receives (--dump-outputs)
         if comm_stream is not None:
             comm_stream.synchronize()
         torch.cuda.synchronize(dev)
@@ -407,11 +425,15 @@ def main():
             step(i, False)
         torch.cuda.synchronize(dev)
         elapsed, elapsed_min, elapsed_closed = timed_pass(False, algo_compute)
-        # the same bracket around a region 25 x as long (untimed as far as `value` goes): says how much of `value` is the
-        # shortness of a K-step region (`ms_per_step_long`, `long_steps` in the line)
-        long_steps = max(args.steps, min(25 * args.steps, int(1.0 / max(elapsed / args.steps, 1e-6))))
-        elapsed_long = timed_pass(False, algo_compute, long_steps)[0]
-        model._algo = algo_compute
+        dumped = dump_outputs(args.dump_outputs, last_out[0], rank, world) if args.dump_outputs else None
+        last_out[0] = None
+        long_steps = elapsed_long = None
+        if args.full:
+            # the same bracket around a region 25 x as long (untimed as far as `value` goes): says how much of `value` is the
+            # shortness of a K-step region (`ms_per_step_long`, `long_steps` in the line)
+            long_steps = max(args.steps, min(25 * args.steps, int(1.0 / max(elapsed / args.steps, 1e-6))))
+            elapsed_long = timed_pass(False, algo_compute, long_steps)[0]
+            model._algo = algo_compute
     frames_per_step = global_batch * TP
     value = frames_per_step * args.steps / elapsed
     step_ms = elapsed / args.steps * 1e3
@@ -495,34 +517,36 @@ def main():
             r["frac_of_practical_roof"] = round(r["frac"] / practical["frac_of_peak"], 4)
         return r
 
-    with torch.no_grad():
-        if algo in (_native.ALGO_FFT, _native.ALGO_FFT_WG):
-            plan = _native.fft_plan_info(B, T, F, K, hop)
-            kname = (("leaf_fft_wg4k_kernel" if plan and plan["fft_n"] == 4096 else "leaf_fft_wg_kernel")
-                     if algo == _native.ALGO_FFT_WG else "leaf_fft_kernel")
-            roofline = roofline_of(algo, algo_name, kname, "valu_fp32",
-                                   "fp32 VALU issue (64 FLOP/clk/SIMD = 157.3 TF); overlap-save FFT kernel, no MFMA.  `frac` is "
-                                   "measured here at full clock; `valu_issue_frac_pmc` and `traffic` come from the committed "
-                                   "rocprofv3 counter passes, which run the chip ~10 % slower -- two views, not factors of one number",
-                                   main=True)
-            # the comparison kernels only at the metric's own config (the direct-form kernel takes 10-100x longer elsewhere)
-            other = None if args.config != "cfg1" else {"fft_per_wave_kernel": roofline_of(_native.ALGO_FFT, "fft", "leaf_fft_kernel", "valu_fp32",
-                                                        "round-1 kernel: one wave per (block, filter group), 2 waves/SIMD"),
-                     "mfma_kernel": roofline_of(_native.ALGO_MFMA, "mfma", "leaf_fused_kernel", "mfma",
-                                                "fp32 MFMA roof (same 157.3 TF); direct Hermitian-GEMM kernel")}
-            if other and algo == _native.ALGO_FFT:
-                other.pop("fft_per_wave_kernel")
-        else:
-            roofline = roofline_of(_native.ALGO_MFMA, "mfma", "leaf_fused_kernel", "mfma",
-                                   "fp32 MFMA roof; direct Hermitian-GEMM kernel", main=True)
-            other = None
+    roofline = other = None
+    if args.full:
+        with torch.no_grad():
+            if algo in (_native.ALGO_FFT, _native.ALGO_FFT_WG):
+                plan = _native.fft_plan_info(B, T, F, K, hop)
+                kname = (("leaf_fft_wg4k_kernel" if plan and plan["fft_n"] == 4096 else "leaf_fft_wg_kernel")
+                         if algo == _native.ALGO_FFT_WG else "leaf_fft_kernel")
+                roofline = roofline_of(algo, algo_name, kname, "valu_fp32",
+                                       "fp32 VALU issue (64 FLOP/clk/SIMD = 157.3 TF); overlap-save FFT kernel, no MFMA.  `frac` is "
+                                       "measured here at full clock; `valu_issue_frac_pmc` and `traffic` come from the committed "
+                                       "rocprofv3 counter passes, which run the chip ~10 % slower -- two views, not factors of one number",
+                                       main=True)
+                # the comparison kernels only at the metric's own config (the direct-form kernel takes 10-100x longer elsewhere)
+                other = None if args.config != "cfg1" else {"fft_per_wave_kernel": roofline_of(_native.ALGO_FFT, "fft", "leaf_fft_kernel", "valu_fp32",
+                                                            "round-1 kernel: one wave per (block, filter group), 2 waves/SIMD"),
+                         "mfma_kernel": roofline_of(_native.ALGO_MFMA, "mfma", "leaf_fused_kernel", "mfma",
+                                                    "fp32 MFMA roof (same 157.3 TF); direct Hermitian-GEMM kernel")}
+                if other and algo == _native.ALGO_FFT:
+                    other.pop("fft_per_wave_kernel")
+            else:
+                roofline = roofline_of(_native.ALGO_MFMA, "mfma", "leaf_fused_kernel", "mfma",
+                                       "fp32 MFMA roof; direct Hermitian-GEMM kernel", main=True)
+                other = None
     hbm_gbps = bytes_per_frame * frames_rank / (step_ms * 1e-3) / 1e9
     roofline_hbm = {"bound": "hbm", "achieved": round(hbm_gbps, 2), "peak": PEAK_HBM_GBPS, "unit": "GB/s",
                     "frac": round(hbm_gbps / PEAK_HBM_GBPS, 6), "algorithmic_bytes_per_frame": bytes_per_frame,
                     "note": "per GPU, whole step; the fused path is VALU-issue-bound, see DESIGN.md"}
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_baseline = time_cpu_baseline(model, x, F, SR, use_pcen, TP, with_cfg0=(args.config == "cfg1"))
 
     line = None
@@ -532,7 +556,8 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(step_ms, 4),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "spinup_steps": args.spinup_steps,
-            "long_steps": long_steps, "ms_per_step_long": round(elapsed_long / long_steps * 1e3, 4),
+            "full": args.full,
+            "long_steps": long_steps, "ms_per_step_long": round(elapsed_long / long_steps * 1e3, 4) if long_steps else None,
             "timed_call": "Leaf.forward (nn.Module call under torch.no_grad(), output allocated per call)",
             "config": {"workload": f"BASELINE configs[{cfg['index']}]: {cfg['what']}, "
                                    + (f"batch {B} x {seconds:g} s clips per GPU" if args.scaling == "weak" else
@@ -560,6 +585,8 @@ def main():
                           "own synchronize after step K, MAX over ranks (all_reduce, outside the timed region)")
         if args.compute_reserve_cus:
             line["config"]["reserved_cus"] = args.compute_reserve_cus
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
 
     # ---- the "trivial gather" passes (N > 1): after the line exists, under a watchdog.  A transport that raises is contained by
     # guarded_gather_pass; one that HANGS is not, so a timer bounds the whole phase: on expiry rank 0 prints the line it already
@@ -630,6 +657,35 @@ def main():
         t_exit.start()
         dist.destroy_process_group()
         t_exit.cancel()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, out, rank, world):
+    """--dump-outputs: the (B, F, T') features the last timed step returned, as float32 (bf16 I/O widens exactly) in
+    DIR/features.npy (rank r > 0: features_rank<r>.npy).  Above 64 MB in all (split evenly over the ranks) a fixed, seeded
+    sample of whole clips is written instead, in clip order, and their indices beside it (features_clips[_rank<r>].npy,
+    float64).  Returns {name: shape} of what was written."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    feats = out.detach()
+    budget = DUMP_LIMIT_BYTES // max(1, world)
+    written = {}
+    if feats.numel() * 4 > budget:
+        per_clip = feats[0].numel() * 4
+        n = max(1, budget // per_clip)
+        clips = torch.randperm(feats.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values
+        feats = feats[clips.to(feats.device)]
+        if feats.numel() * 4 > budget:                   # one clip alone is over the limit: its first frames
+            feats = feats[..., :max(1, budget // (4 * feats.shape[1]))]
+        np.save(os.path.join(directory, f"features_clips{suffix}.npy"), clips.double().numpy())
+        written[f"features_clips{suffix}"] = list(clips.shape)
+    arr = feats.float().cpu().numpy()
+    np.save(os.path.join(directory, f"features{suffix}.npy"), arr)
+    written[f"features{suffix}"] = list(arr.shape)
+    return written
 
 
 def band_task_plan(classes):

@@ -296,7 +296,7 @@ def test_bench_self_launches_multi_rank_from_a_plain_shell():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                          "--spinup-steps", "10", "--gather-mode", "all"], capture_output=True, text=True, env=env, timeout=900, cwd=repo)
+                          "--spinup-steps", "10", "--gather-mode", "all", "--full"], capture_output=True, text=True, env=env, timeout=900, cwd=repo)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -434,7 +434,7 @@ def test_bench_rccl_branches_run_at_world_size_one():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LEAF_BENCH_FORCE_DIST="1", LEAF_BENCH_BACKEND="nccl", HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "5", "--warmup", "2", "--spinup-steps", "10",
-                          "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900, cwd=repo)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=900, cwd=repo)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["config"]["backend"].startswith("nccl") and line["config"]["backend_world_size"] == 1
@@ -703,7 +703,7 @@ def test_bench_runs_every_baseline_config_multi_rank(config, scaling, extra):
         launch = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                   "--master-port", str(port), os.path.join(repo, "bench.py")]
     res = subprocess.run(launch + ["--config", config, "--scaling", scaling, "--gpus", "2",
-                                   "--steps", "3", "--warmup", "1", "--spinup-steps", "2", "--gather-mode", "rccl"] + extra,
+                                   "--steps", "3", "--warmup", "1", "--spinup-steps", "2", "--gather-mode", "rccl", "--full"] + extra,
                          capture_output=True, text=True, env=env, timeout=900, cwd=repo)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -747,7 +747,7 @@ def test_bench_eight_rank_dry_run_of_the_configs_that_name_eight_gpus(config, cl
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--config", config, "--scaling", "strong", "--gpus", "8",
-                          "--steps", "2", "--warmup", "1", "--spinup-steps", "2", "--gather-mode", "rccl"],
+                          "--steps", "2", "--warmup", "1", "--spinup-steps", "2", "--gather-mode", "rccl", "--full"],
                          capture_output=True, text=True, env=env, timeout=1500, cwd=repo)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -782,7 +782,7 @@ def test_bench_survives_a_failed_gather(who):
     else:
         env["LEAF_BENCH_FAIL_GATHER"] = who
     res = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--spinup-steps", "5"] + extra, capture_output=True, text=True, env=env, timeout=900, cwd=repo)
+                          "--spinup-steps", "5", "--full"] + extra, capture_output=True, text=True, env=env, timeout=900, cwd=repo)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -809,7 +809,7 @@ def test_bench_value_does_not_need_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LEAF_BENCH_FORCE_DIST="1", LEAF_BENCH_BACKEND="nccl", LEAF_BENCH_FAIL_NCCL_INIT="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "3", "--warmup", "1", "--spinup-steps", "5",
-                          "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900, cwd=repo)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=900, cwd=repo)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]
@@ -817,6 +817,48 @@ def test_bench_value_does_not_need_rccl():
     assert line["value"] > 0 and "value_with_gather" not in line and "gloo" in line["config"]["backend"]
     notes = line["gather"]["notes"]
     assert any("rccl communicator: not created" in n for n in notes) and any("no transport" in n for n in notes), notes
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) is the headline alone: the line has the contract's fields and `steps` timed steps, none
+    of the --full measurements; --dump-outputs writes the features of the last timed step, the same from run to run whatever the
+    step count (seeded inputs and parameters), and they are what Leaf.forward returns for those inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = {}
+    for steps in (3, 7):
+        out_dir = tmp_path / f"k{steps}"
+        res = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                              "--spinup-steps", "5", "--dump-outputs", str(out_dir)],
+                             capture_output=True, text=True, env=env, timeout=600, cwd=repo)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, res.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+        assert line["steps"] == steps and line["warmup"] == 2 and line["full"] is False and line["higher_is_better"] is True
+        assert abs(line["value"] - 256 * 100 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-3
+        assert line["roofline"] is None and line["roofline_other_algo"] is None and line["cpu_baseline"] is None
+        assert line["long_steps"] is None and "gather" not in line
+        assert line["dumped_outputs"]["arrays"] == {"features": [256, 40, 100]}
+        assert sorted(os.listdir(out_dir)) == ["features.npy"]
+        dumps[steps] = np.load(out_dir / "features.npy")
+        assert dumps[steps].dtype == np.float32 and np.isfinite(dumps[steps]).all()
+    assert np.array_equal(dumps[3], dumps[7])
+    # the same inputs and parameters in this process (bench.py's seeds), through the module call the bench times
+    torch.manual_seed(0)
+    m = L.Leaf().eval().to(DEV)
+    gen = torch.Generator(device=DEV).manual_seed(1000)
+    x = 2 * torch.rand(256, 1, 16000, device=DEV, generator=gen) - 1
+    with torch.no_grad():
+        want = m(x)
+    assert rel_err(torch.from_numpy(dumps[7]), want.cpu()) < 1e-6
 
 
 @pytest.mark.gpu

@@ -333,6 +333,33 @@ def test_bench_configs_are_the_baseline_configs():
     assert bench.PEAK_FP32_VALU_TFLOPS == 157.3 and bench.PEAK_HBM_GBPS == 8000.0
 
 
+def test_bench_dump_outputs_writes_float32_and_samples_clips_past_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (dump_outputs): the features as float32 .npy (bf16 widened exactly); past the size limit a fixed,
+    seeded sample of whole clips in clip order, with their indices beside them; rank r > 0 writes its own names."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_for_dump_test", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+    feats = torch.randn(10, 4, 6, generator=torch.Generator().manual_seed(3)).to(torch.bfloat16)
+    assert bench.dump_outputs(str(tmp_path / "all"), feats, 0, 1) == {"features": [10, 4, 6]}
+    got = np.load(tmp_path / "all" / "features.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, feats.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * 4 * 6 * 4 * 2)           # three clips per rank at world size 2
+    picks = []
+    for _ in range(2):
+        d = tmp_path / f"sample{len(picks)}"
+        assert bench.dump_outputs(str(d), feats, 1, 2) == {"features_clips_rank1": [3], "features_rank1": [3, 4, 6]}
+        idx = np.load(d / "features_clips_rank1.npy")
+        assert idx.dtype == np.float64 and list(idx) == sorted(set(idx)) and 0 <= idx.min() and idx.max() < 10
+        assert np.array_equal(np.load(d / "features_rank1.npy"), feats.float().numpy()[idx.astype(np.int64)])
+        picks.append(list(idx))
+    assert picks[0] == picks[1]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 3 * 4)                   # less than one clip: its first frames
+    assert bench.dump_outputs(str(tmp_path / "one"), feats, 0, 1) == {"features_clips": [1], "features": [1, 4, 3]}
+
+
 def test_notes_switch_table_is_current():
     """NOTES.md's last section lists every compile-time switch of the HIP sources with its default (tools/list_switches.py):
     regenerated here and compared, so that a new -DLEAF_* handle or a changed default cannot go undocumented."""

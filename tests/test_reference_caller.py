@@ -1,7 +1,12 @@
 """The reference's OWN caller on top of the product (SURVEY 8b "who calls it").
 
-Container-only: `/root/reference` does not exist on the GPU box, so everything here skips there (like the regeneration of the
-golden fixtures).  Nothing of the reference is copied: its `models.classifier.Classifier` (models/classifier.py:7-18) and its
+Everywhere: tests/golden/reference_caller_cfgs.json holds what the reference's Classifier produced for every shipped cfg (the cfg's
+`frontend` / `audio_config` sections, its `features.*` keys and shapes, and its features checkpoint: data only, written by
+`python tests/test_reference_caller.py --write-fixture` where the reference tree exists).  The product's `get_frontend` (what
+models/classifier.py:11 calls, through the import-path shim) is held to those records and loads that checkpoint strictly.
+
+Where the reference tree exists, the same test also runs the reference's own caller live and checks the records against it.
+Nothing of the reference is copied: its `models.classifier.Classifier` (models/classifier.py:7-18) and its
 shipped `cfgs/**/*.cfg` are imported / read where they lie, in FRESH interpreters (`-B`: no bytecode into the read-only tree)
 whose `sys.path` puts this repo AHEAD of the reference, so `from leaf_pytorch import get_frontend` (models/classifier.py:3)
 resolves to the import-path shim `leaf_pytorch/` of this repo and `models.*` to the reference.
@@ -19,13 +24,12 @@ import sys
 import tempfile
 
 import pytest
+import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFERENCE = os.environ.get("LEAF_REFERENCE", "/root/reference")
 CFGS = sorted(glob.glob(os.path.join(REFERENCE, "cfgs", "**", "*.cfg"), recursive=True))
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "models")),
-                                reason="the reference tree only exists in the build container")
+FIXTURE = os.path.join(REPO, "tests", "golden", "reference_caller_cfgs.json")
 
 SEVEN = ["features._complex_conv._kernel", "features._pooling.weights", "features._pooling._bias", "features._compression.alpha",
          "features._compression.delta", "features._compression.root", "features._compression.ema._weights"]
@@ -73,7 +77,7 @@ for path in cfgs:
            "feature_shapes": {k: list(v.shape) for k, v in sd.items() if k.startswith("features.")},
            "n_filters": int(fe._complex_conv._filters), "kernel_size": int(fe._complex_conv._kernel_size),
            "use_legacy_complex": bool(fe._complex_conv.use_legacy_complex), "n_model_keys": sum(1 for k in sd if k.startswith("model.")),
-           "frontend_cfg": cfg["frontend"]}
+           "frontend_cfg": cfg["frontend"], "audio_config": cfg.get("audio_config", {})}
     sd_path = os.path.join(sd_dir, name.replace(os.sep, "__") + "." + mode + ".pt")
     other = os.path.join(sd_dir, name.replace(os.sep, "__") + "." + ("reference" if mode == "product" else "product") + ".pt")
     if os.path.exists(other):
@@ -98,7 +102,9 @@ def run_child(mode, tmp, cfgs):
     return json.load(open(out))
 
 
-def test_reference_classifier_builds_on_the_product_for_every_shipped_cfg():
+def check_live_reference():
+    """The reference's Classifier on the reference's Leaf and on the product, checkpoints across both ways; returns the
+    reference's records (what the fixture stores)."""
     assert len(CFGS) >= 14, CFGS
     with tempfile.TemporaryDirectory() as tmp:
         ref = run_child("reference", tmp, CFGS)          # the reference's Classifier on the reference's Leaf: checkpoints to load
@@ -124,3 +130,76 @@ def test_reference_classifier_builds_on_the_product_for_every_shipped_cfg():
         b = back["cfgs"][name]
         assert b["strict_load_of_the_other"] == "<All keys matched successfully>" and b["round_trip_equal"], (name, b)
     assert saw_64, "no shipped cfg with n_filters: 64 was exercised (the AudioSet cfgs)"
+    return ref["cfgs"]
+
+
+def reference_records(tmp):
+    """The reference's Classifier on the reference's Leaf, every shipped cfg: its records plus its features checkpoint."""
+    ref = run_child("reference", tmp, CFGS)
+    recs = {}
+    for name, r in ref["cfgs"].items():
+        sd = torch.load(os.path.join(tmp, name.replace(os.sep, "__") + ".reference.pt"))["model_state_dict"]
+        recs[name] = dict(r, features_state_dict={k: {"dtype": str(v.dtype).replace("torch.", ""), "shape": list(v.shape),
+                                                      "values": v.flatten().tolist()}
+                                                  for k, v in sd.items() if k.startswith("features.")})
+    return recs
+
+
+STRUCTURE = ("features_class", "feature_keys", "feature_shapes", "n_filters", "kernel_size", "use_legacy_complex", "n_model_keys",
+             "frontend_cfg", "audio_config")
+
+
+def test_reference_classifier_builds_on_the_product_for_every_shipped_cfg():
+    import contextlib
+    import io
+    import leaf_pytorch                                           # the import-path shim models/classifier.py:3 resolves to
+    from leaf_pytorch_amd.frontend import Leaf
+    recs = json.load(open(FIXTURE))["cfgs"]
+    assert len(recs) >= 14, sorted(recs)
+    saw_64 = False
+    for name, r in recs.items():
+        assert r["features_class"] == "leaf_pytorch.frontend.Leaf", name
+        with contextlib.redirect_stdout(io.StringIO()):
+            torch.manual_seed(0)
+            fe = leaf_pytorch.get_frontend({"frontend": r["frontend_cfg"], "audio_config": r["audio_config"]})
+        assert type(fe) is Leaf, (name, type(fe))
+        sd = {"features." + k: v for k, v in fe.state_dict().items()}
+        assert list(sd) == r["feature_keys"] == SEVEN, (name, list(sd))
+        assert {k: list(v.shape) for k, v in sd.items()} == r["feature_shapes"], name
+        fc = r["frontend_cfg"]
+        want_f = 40 if fc.get("default_args", False) else int(fc.get("n_filters", 40))
+        assert fe._complex_conv._filters == r["n_filters"] == want_f and fe._complex_conv._kernel_size == r["kernel_size"] == 401, name
+        assert bool(fe._complex_conv.use_legacy_complex) == r["use_legacy_complex"] == bool(fc.get("use_legacy_complex", False)), name
+        assert r["n_model_keys"] > 0, name
+        saw_64 = saw_64 or want_f == 64
+        # the reference's checkpoint (train.py:33-49's format, its features part) loads strictly and comes back bit for bit ...
+        ref_sd = {k: torch.tensor(e["values"], dtype=getattr(torch, e["dtype"])).reshape(e["shape"])
+                  for k, e in r["features_state_dict"].items()}
+        assert list(ref_sd) == SEVEN, name
+        missing_unexpected = fe.load_state_dict({k[len("features."):]: v for k, v in ref_sd.items()}, strict=True)
+        assert str(missing_unexpected) == "<All keys matched successfully>", (name, missing_unexpected)
+        back = fe.state_dict()
+        assert all(torch.equal(back[k[len("features."):]], v) and back[k[len("features."):]].dtype == v.dtype
+                   for k, v in ref_sd.items()), name
+        # ... and the product's own checkpoint has the keys, shapes and dtypes the reference's strict load asks for
+        assert {k: (list(v.shape), v.dtype) for k, v in sd.items()} == {k: (list(v.shape), v.dtype) for k, v in ref_sd.items()}, name
+    assert saw_64, "no shipped cfg with n_filters: 64 was exercised (the AudioSet cfgs)"
+    if os.path.isdir(os.path.join(REFERENCE, "models")):
+        live = check_live_reference()
+        assert set(live) == set(recs), (sorted(live), sorted(recs))
+        for name, r in live.items():
+            assert {k: r[k] for k in STRUCTURE} == {k: recs[name][k] for k in STRUCTURE}, name
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] != ["--write-fixture"]:
+        sys.exit("usage: python tests/test_reference_caller.py --write-fixture   (where the reference tree exists)")
+    assert CFGS, f"no cfgs under {REFERENCE}"
+    with tempfile.TemporaryDirectory() as tmp:
+        recs = reference_records(tmp)
+    with open(FIXTURE, "w") as fh:
+        json.dump({"what": "the reference's models.classifier.Classifier on the reference's Leaf, torch.manual_seed(0), per shipped cfg "
+                           "(path under cfgs/): records and the features.* part of its state_dict",
+                   "cfgs": {k: recs[k] for k in sorted(recs)}}, fh, indent=1, sort_keys=False)
+        fh.write("\n")
+    print(f"wrote {FIXTURE}: {len(recs)} cfgs")

@@ -28,7 +28,7 @@ def jl(name):
 def block():
     out = []
     pmc = j("pmc_summary.json")["configs"]
-    out.append("**Bench lines** (`python bench.py --config cfgK --steps 50 --warmup 10`, N = 1; `bench_cfgK_n1.json`) and the PMC passes of "
+    out.append("**Bench lines** (`python bench.py --config cfgK --steps 50 --warmup 10 --full`, N = 1; `bench_cfgK_n1.json`) and the PMC passes of "
                "the same workloads (`pmc_summary.json`):\n")
     out.append("| config | workload per GPU | ms / step | frames/s | dominant kernel | kernel ms | tasks per block (2048 / 8×256 / 4×512) | executed GFLOP | "
                "`frac` | of practical roof | VALU issue (PMC) | HBM traffic / algorithmic | CPU oracle frames/s (threads) |")

@@ -9,11 +9,11 @@ export TMPDIR=/tmp
 rm -rf "$D"; mkdir -p "$D"
 timeout 1200 python -m pytest tests -m gpu -q 2>&1 | tail -5 > "$D/pytest_gpu.log"; cat "$D/pytest_gpu.log"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee "$D/smoke.log"
-timeout 600 python bench.py --steps 50 --warmup 10 2>/dev/null | tail -1 > "$D/bench_n1.json"; cut -c1-600 "$D/bench_n1.json"
-timeout 600 python bench.py --gpus 2 --steps 20 --warmup 5 2>/dev/null | tail -1 > "$D/bench_n2_dryrun_1gpu_gloo.json"; cut -c1-200 "$D/bench_n2_dryrun_1gpu_gloo.json"
+timeout 600 python bench.py --steps 50 --warmup 10 --full 2>/dev/null | tail -1 > "$D/bench_n1.json"; cut -c1-600 "$D/bench_n1.json"
+timeout 600 python bench.py --gpus 2 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > "$D/bench_n2_dryrun_1gpu_gloo.json"; cut -c1-200 "$D/bench_n2_dryrun_1gpu_gloo.json"
 # the RCCL branches on the one GPU there is: a one-rank process group, all three gather modes (round 3)
-LEAF_BENCH_FORCE_DIST=1 timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 > "$D/bench_n1_rccl_world1.json"; cut -c1-200 "$D/bench_n1_rccl_world1.json"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/stats" -o bench -- python bench.py --steps 50 --warmup 10 --no-cpu-baseline > "$D/bench_under_rocprof.log" 2>&1
+LEAF_BENCH_FORCE_DIST=1 timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --full 2>/dev/null | tail -1 > "$D/bench_n1_rccl_world1.json"; cut -c1-200 "$D/bench_n1_rccl_world1.json"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/stats" -o bench -- python bench.py --steps 50 --warmup 10 --no-cpu-baseline --full > "$D/bench_under_rocprof.log" 2>&1
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "sq GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_WAVE_CYCLES SQ_INSTS_LDS SQ_WAIT_ANY SQ_LDS_BANK_CONFLICT"; do
     set -- $pass; name=$1; shift
     timeout 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$D/pmc_$name" -o w -- python tools/profile_workload.py > /dev/null 2>&1

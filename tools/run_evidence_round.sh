@@ -27,14 +27,14 @@ import json, sys
 d = json.loads(sys.stdin.read()); d['from'] = 'profiles/$ROUND/ubench_valu.txt'
 json.dump(d, open('profiles/valu_roof.json', 'w')); json.dump(d, open('$D/valu_roof.json', 'w')); print('valu roof', d['frac_of_peak'])"
 for c in cfg1 cfg2 cfg3 cfg4; do
-    timeout 600 python bench.py --config $c --steps 50 --warmup 10 2>/dev/null | tail -1 > "$D/bench_${c}_n1.json"; cut -c1-260 "$D/bench_${c}_n1.json"
+    timeout 600 python bench.py --config $c --steps 50 --warmup 10 --full 2>/dev/null | tail -1 > "$D/bench_${c}_n1.json"; cut -c1-260 "$D/bench_${c}_n1.json"
 done
-timeout 600 python bench.py --gpus 2 --steps 20 --warmup 5 2>/dev/null | tail -1 > "$D/bench_cfg1_n2_dryrun_1gpu_gloo.json"
-timeout 600 python bench.py --config cfg2 --scaling strong --gpus 2 --steps 5 --warmup 2 2>/dev/null | tail -1 > "$D/bench_cfg2_strong_n2_dryrun_1gpu_gloo.json"
-LEAF_BENCH_FORCE_DIST=1 timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | tail -1 > "$D/bench_cfg1_n1_rccl_world1.json"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/stats" -o bench -- python bench.py --steps 50 --warmup 10 --no-cpu-baseline > "$D/bench_under_rocprof.log" 2>&1
+timeout 600 python bench.py --gpus 2 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > "$D/bench_cfg1_n2_dryrun_1gpu_gloo.json"
+timeout 600 python bench.py --config cfg2 --scaling strong --gpus 2 --steps 5 --warmup 2 --full 2>/dev/null | tail -1 > "$D/bench_cfg2_strong_n2_dryrun_1gpu_gloo.json"
+LEAF_BENCH_FORCE_DIST=1 timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --full 2>/dev/null | tail -1 > "$D/bench_cfg1_n1_rccl_world1.json"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/stats" -o bench -- python bench.py --steps 50 --warmup 10 --no-cpu-baseline --full > "$D/bench_under_rocprof.log" 2>&1
 cp "$D"/stats/*/bench_kernel_stats.csv "$D/bench_kernel_stats.csv" 2>/dev/null || cp "$D/stats/bench_kernel_stats.csv" "$D/bench_kernel_stats.csv"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/stats2" -o bench -- python bench.py --config cfg2 --steps 30 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$D/stats2" -o bench -- python bench.py --config cfg2 --steps 30 --warmup 5 --no-cpu-baseline --full > /dev/null 2>&1
 cp "$D"/stats2/*/bench_kernel_stats.csv "$D/bench_cfg2_kernel_stats.csv" 2>/dev/null || cp "$D/stats2/bench_kernel_stats.csv" "$D/bench_cfg2_kernel_stats.csv"
 timeout 600 python tools/check_band.py 2>&1 | grep -v amdgpu.ids > "$D/band_check.txt"; tail -12 "$D/band_check.txt"
 timeout 600 python tools/check_band4k.py 2>&1 | grep -v amdgpu.ids > "$D/band4k_check.txt"; tail -6 "$D/band4k_check.txt"
