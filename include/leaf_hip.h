@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define LEAF_ABI_VERSION 5
+#define LEAF_ABI_VERSION 6
 
 typedef enum leaf_status {
     LEAF_OK = 0,
@@ -53,14 +53,17 @@ typedef enum leaf_status {
     LEAF_ERR_LAUNCH = -5,         /* HIP reported a launch failure (hipGetLastError != 0)   */
     LEAF_ERR_NO_DEVICE = -6,      /* no usable gfx950 device                                */
     LEAF_ERR_ALIGNMENT = -7,      /* a buffer is not 4-byte aligned                         */
-    LEAF_ERR_UNSUPPORTED = -8     /* valid arguments, unsupported combination: bfloat16 I/O with a backward
-                                     (leaf_forward_save_f32) or with the staged kernels; LEAF_FLAG_PEAKNORM with
+    LEAF_ERR_UNSUPPORTED = -8     /* valid arguments, unsupported combination: bfloat16 I/O with the staged FORWARD
+                                     kernels (the backward takes it on every path, ABI 6); LEAF_FLAG_PEAKNORM with
                                      leaf_forward_save_f32 / leaf_forward_prepared_f32 or off the overlap-save paths */
 } leaf_status;
 
 /* flags */
 #define LEAF_FLAG_PCEN   0x1   /* apply PCEN (requires alpha, delta, root, ema_w)                */
-#define LEAF_FLAG_LOG1P  0x2   /* extension (not in the reference): out = log1p(pooled), PCEN off */
+#define LEAF_FLAG_LOG1P  0x2   /* extension (not in the reference): out = log1p(max(pooled, 1e-5)), PCEN off (ignored with
+                                  LEAF_FLAG_PCEN).  ABI 6: leaf_forward_save_f32 and leaf_backward_f32 honour it too -- the
+                                  backward divides grad_out by 1 + pooled above the floor where it reads it (no extra
+                                  launch, no extra workspace) */
 #define LEAF_FLAG_BWD_STAGED 0x8 /* leaf_backward_f32 only: force the staged (one-lane-per-output) kernels */
 #define LEAF_FLAG_BWD_MFMA 0x10 /* leaf_backward_f32 only: force the fused MFMA backward (skip the overlap-save FFT one) */
 #define LEAF_FLAG_BWD_FULL_TRANSFORMS 0x40 /* leaf_backward_f32 only (ABI 4): no band-limited filter tasks in the backward -- by default the
@@ -81,8 +84,13 @@ typedef enum leaf_status {
                                   waveform ever being written: one read-only pre-pass finds each clip's scale s, and because the
                                   path is linear up to |.|^2, s^2 multiplies the pooled energies where the bias is added
                                   (pooling.py:41).  Equal to leaf_peak_normalize_f32 + forward up to fp32 rounding (~1e-7). */
-#define LEAF_FLAG_IO_BF16 0x4  /* extension (BASELINE configs[4]): x and out are bfloat16 buffers (2 bytes per element),
-                                  arithmetic stays fp32; fused path only */
+#define LEAF_FLAG_IO_BF16 0x4  /* extension (BASELINE configs[4]): x and out are bfloat16 buffers (2 bytes per element, 2-byte
+                                  aligned), arithmetic stays fp32; fused forward paths only.  ABI 6, training: leaf_forward_save_f32
+                                  takes it (pooled_raw stays fp32), and in leaf_backward_f32 x, grad_out and g_x are bfloat16
+                                  (g_x rounded to nearest even) while parameters, their gradients and pooled_raw stay fp32.  The
+                                  overlap-save backwards widen x in their loads (no fp32 copy: the workspace does not grow); the
+                                  MFMA and the staged backward take one widening pass into the workspace, which
+                                  leaf_backward_workspace_bytes accounts for when given the flag */
 
 /* algorithm selector for the fused path */
 #define LEAF_ALGO_AUTO   0     /* _FFT_SMALL for a handful of clips of a LEAF geometry; else the FFT kernels when their plan fits and K >= 224 or the geometry has a static instance, else MFMA, else staged */
@@ -258,6 +266,8 @@ int leaf_band_classes_f32(const float* kernel, const float* pool_w, const float*
  * LEAF_FLAG_BWD_STAGED or a geometry neither covers: staged one-lane-per-output kernels.  Workspace =
  * leaf_backward_workspace_bytes for the SAME flags and need_dx = (g_x != NULL): sized for the path that will actually
  * run (a few MB for the overlap-save backward; the staged path materialises dL/dy, B*T*2F floats).
+ * ABI 6: LEAF_FLAG_LOG1P (PCEN off) and LEAF_FLAG_IO_BF16 (x, grad_out, g_x bfloat16 behind the float pointers) as described
+ * at the flags; x, grad_out and g_x must be 4-byte (bfloat16: 2-byte) aligned, else LEAF_ERR_ALIGNMENT.
  */
 size_t leaf_backward_workspace_bytes(int B, int T, int F, int K, int hop, int flags, int need_dx);
 int leaf_backward_f32(const float* x, int B, int T,

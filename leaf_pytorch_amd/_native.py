@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libleaf_hip.so")
 SRC_PATH = os.path.join(_PKG_DIR, "csrc", "leaf_kernels.hip")
 INCLUDE_DIR = os.path.join(_REPO_DIR, "include")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 ALGO_AUTO, ALGO_STAGED, ALGO_MFMA, ALGO_FFT, ALGO_FFT_WG, ALGO_FFT_SMALL = 0, 1, 2, 3, 4, 5
 
 
@@ -356,20 +356,29 @@ def leaf_forward(x: torch.Tensor, kernel, pool_w, pool_b, alpha, delta, root, em
 def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, grad_out: torch.Tensor,
                   pcen: bool = True, need_dx: bool = False, staged: bool = False,
                   pooled_raw: Optional[torch.Tensor] = None, mfma: bool = False, full_transforms: bool = False,
-                  strict_band_classes: bool = False):
+                  strict_band_classes: bool = False, log1p: bool = False):
     """Gradients of the forward w.r.t. (kernel, pool_w, pool_b, alpha, delta, root, ema_w[, x]).  Wraps leaf_backward_f32.
     ``staged`` / ``mfma`` force the staged kernels / the fused MFMA backward (default: the overlap-save backward where
-    it applies, else MFMA, else staged)."""
+    it applies, else MFMA, else staged).  ``log1p``: the backward of the log1p-compressed forward (PCEN off; ignored with
+    PCEN on, as in the forward).  A bfloat16 ``x`` selects bfloat16 I/O: ``grad_out`` is bfloat16 too and dL/dx comes back
+    in bfloat16; the parameter gradients and ``pooled_raw`` are float32."""
     lib = load()
     require_hip(x, "leaf_backward")
     dev = x.device
-    x2 = _dev_f32(x[:, 0, :] if x.dim() == 3 else x, "x", dev)
+    x2 = x[:, 0, :] if x.dim() == 3 else x
+    io_bf16 = x2.dtype == torch.bfloat16
+    x2 = x2.detach().contiguous() if io_bf16 else _dev_f32(x2, "x", dev)
     B, T = x2.shape
     F = kernel.shape[0]
     kernel = _dev_f32(kernel, "kernel", dev)
     pw = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
     pb = _dev_f32(pool_b, "pool_b", dev)
-    go = _dev_f32(grad_out, "grad_out", dev)
+    if io_bf16:
+        if grad_out.dtype != torch.bfloat16 or grad_out.device != dev:
+            raise RuntimeError(f"grad_out must be bfloat16 on {dev} when x is bfloat16, got {grad_out.dtype} on {grad_out.device}")
+        go = grad_out.detach().contiguous()
+    else:
+        go = _dev_f32(grad_out, "grad_out", dev)
     TP = lib.leaf_num_frames(T, K, hop)
     if tuple(go.shape) != (B, F, TP):
         raise RuntimeError(f"grad_out has shape {tuple(go.shape)}, expected {(B, F, TP)}")
@@ -393,14 +402,15 @@ def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, 
         for b0, b1 in batch_slices(B, T):
             g = leaf_backward(x2[b0:b1], kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, go[b0:b1], pcen=pcen, need_dx=need_dx,
                               staged=staged, pooled_raw=None if pooled_raw is None else pooled_raw[b0:b1], mfma=mfma,
-                              full_transforms=full_transforms, strict_band_classes=strict_band_classes)
+                              full_transforms=full_transforms, strict_band_classes=strict_band_classes, log1p=log1p)
             if need_dx:
                 g_x[b0:b1].copy_(g[7])
             total = list(g[:7]) if total is None else [None if a is None else a.add_(b) for a, b in zip(total, g[:7])]
         return (*total, g_x)
     flags = ((FLAG_PCEN if pcen else 0) | (FLAG_BWD_STAGED if staged else 0) | (FLAG_BWD_MFMA if mfma else 0) |
              (FLAG_BWD_FULL_TRANSFORMS if full_transforms else 0) |   # full_transforms: no band-limited filter tasks in the backward
-             (FLAG_BWD_STRICT_BAND_CLASSES if strict_band_classes else 0))
+             (FLAG_BWD_STRICT_BAND_CLASSES if strict_band_classes else 0) |
+             (FLAG_LOG1P if log1p and not pcen else 0) | (FLAG_IO_BF16 if io_bf16 else 0))
     with torch.cuda.device(dev):
         # sized for the path these flags select (a few MB for the overlap-save backward, not the staged path's dL/dy)
         ws = workspace(lib.leaf_backward_workspace_bytes(B, T, F, K, hop, flags, int(need_dx)), dev)

@@ -76,7 +76,7 @@ def _register_python_side() -> None:
         return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)))
 
     @torch.library.register_fake("leaf_amd::forward_train")
-    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo):
+    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p=False):
         shape = (x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop))
         return x.new_empty(shape), x.new_empty(shape, dtype=torch.float32)
 
@@ -86,12 +86,13 @@ def _register_python_side() -> None:
         pc = F if alpha is not None else 0
         e = lambda *s: kernel.new_empty(s)
         return [torch.empty_like(kernel), torch.empty_like(pool_w), torch.empty_like(pool_b), e(pc), e(pc), e(pc), e(pc),
-                torch.empty_like(x) if need_dx else e(0)]
+                torch.empty_like(x) if need_dx else e(0)]            # (g_x in the dtype of x: bfloat16 for bfloat16 I/O)
 
     def setup_context(ctx, inputs, output):
-        x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo = inputs
+        x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p = inputs
         _, raw = output
         ctx.pcen = alpha is not None
+        ctx.log1p = bool(log1p) and not ctx.pcen                 # (ignored with PCEN on, as in the forward)
         ctx.geom = (K, hop)
         ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)     # Leaf.full_transforms(): no band tasks in the backward either
         ctx.strict = bool(algo & _native.ALGO_STRICT_BAND_CLASSES)
@@ -106,9 +107,10 @@ def _register_python_side() -> None:
         gk, gpw, gpb, ga, gd, gr, gw, gx = torch.ops.leaf_amd.backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop,
                                                                      grad_out.contiguous(), raw, need_dx,
                                                                      (_native.FLAG_BWD_FULL_TRANSFORMS if ctx.full else 0) |
-                                                                     (_native.FLAG_BWD_STRICT_BAND_CLASSES if ctx.strict else 0))
+                                                                     (_native.FLAG_BWD_STRICT_BAND_CLASSES if ctx.strict else 0) |
+                                                                     (_native.FLAG_LOG1P if ctx.log1p else 0))
         pc = (ga, gd, gr, gw) if ctx.pcen else (None,) * 4
-        return (gx if need_dx else None, gk, gpw, gpb, *pc, None, None, None)
+        return (gx if need_dx else None, gk, gpw, gpb, *pc, None, None, None, None)
 
     torch.library.register_autograd("leaf_amd::forward_train", backward, setup_context=setup_context)
     from . import _second_order
@@ -121,5 +123,5 @@ def forward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: i
 
 
 def forward_train(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int,
-                  algo: int = _native.ALGO_AUTO) -> torch.Tensor:
-    return torch.ops.leaf_amd.forward_train(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo)[0]
+                  algo: int = _native.ALGO_AUTO, log1p: bool = False) -> torch.Tensor:
+    return torch.ops.leaf_amd.forward_train(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p)[0]

@@ -24,6 +24,7 @@ import math
 import torch
 
 FLOOR_POOLED = 1e-5        # frontend.py:86: torch.maximum(outputs, 1e-5)
+FLAG_LOG1P = 0x2           # include/leaf_hip.h: LEAF_FLAG_LOG1P, carried in leaf_amd::backward's `flags`
 PCEN_FLOOR = 1e-12         # frontend.py:65-69: the floor Leaf constructs its PCENLayer with
 
 
@@ -77,12 +78,17 @@ def setup_context(ctx, inputs, output):
     ctx.pcen = alpha is not None
     ctx.geom = (K, hop)
     ctx.need_dx = bool(need_dx)
+    ctx.log1p = bool(flags & FLAG_LOG1P) and not ctx.pcen       # the log1p-compressed forward (PCEN off): log1p on top of the composite
+    ctx.io_bf16 = x.dtype == torch.bfloat16
     ctx.save_for_backward(x, kernel, pool_w, pool_b, grad_out, *([alpha, delta, root, ema_w] if ctx.pcen else []))
 
 
 def backward(ctx, grads):
     """Cotangents ``grads`` on (g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w, g_x) -> gradients on the op's inputs."""
     K, hop = ctx.geom
+    if getattr(ctx, "io_bf16", False):
+        raise RuntimeError("gradients of gradients through Leaf are float32 only: second order with bfloat16 I/O is not supported "
+                           "(feed float32 waveforms for create_graph=True)")
     saved = ctx.saved_tensors
     x, kernel, pool_w, pool_b, grad_out = saved[:5]
     with torch.enable_grad():
@@ -90,6 +96,8 @@ def backward(ctx, grads):
         go = grad_out.detach().requires_grad_(True)
         pc = leaves[4:] if ctx.pcen else [None] * 4
         out = composite_forward(leaves[0], leaves[1], leaves[2], leaves[3], *pc, K, hop)
+        if getattr(ctx, "log1p", False):
+            out = torch.log1p(out)
         wrt = leaves[1:] + ([leaves[0]] if ctx.need_dx else [])                 # the op's output order: parameters, then x
         vs = [grads[i] for i in range(3)] + ([grads[i] for i in range(3, 7)] if ctx.pcen else []) + ([grads[7]] if ctx.need_dx else [])
         G = torch.autograd.grad(out, wrt, go, create_graph=True, allow_unused=True)

@@ -22,4 +22,13 @@ const void* leaf_inst_fft_blk_bwd_dx(int sk) {
     return reinterpret_cast<const void*>(fn);
 }
 
+const void* leaf_inst_fft_blk_bwd_dx_bf16(int sk) {
+    using K = void (*)(const FftParams);
+    K fn = nullptr;
+    if (sk == 401) fn = leaf_fft_blk_bwd_dx_kernel<401, 160, true>;
+    else if (sk == 801) fn = leaf_fft_blk_bwd_dx_kernel<801, 320, true>;
+    else if (sk == 201) fn = leaf_fft_blk_bwd_dx_kernel<201, 80, true>;
+    return reinterpret_cast<const void*>(fn);
+}
+
 unsigned leaf_layout_fft_wg_bwd() { return leaf_layout_hash_fft(); }                // parameter-struct layout this unit was compiled with (leaf_inst.hpp)

@@ -19,9 +19,11 @@ namespace {
 
 // One lane per (b,f) row.  raw = pooled before the floor.  Forward EMA is recomputed into `ema`, then the
 // reverse-time sweep produces g_pre (grad w.r.t. raw) and the row's contributions to d alpha, d delta, d root,
-// d ema_w in rowsum[row][4].  mode bit0: PCEN on; bit4 (16): no pooled floor (the stand-alone PCENLayer backward).
+// d ema_w in rowsum[row][4].  mode bit0: PCEN on; bit1 (2): log1p compression behind the floor (PCEN off only: the forward's
+// extension, out = log1p(max(raw, 1e-5)), so d out / d raw = 1 / (1 + raw) above the floor -- a division, not a reciprocal);
+// bit2 (4): gout is bfloat16 (LEAF_FLAG_IO_BF16); bit4 (16): no pooled floor (the stand-alone PCENLayer backward).
 #ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
-__global__ void pcen_bwd_rows_kernel(const float* __restrict__ raw, const float* __restrict__ gout, int BF, int F, int TP,
+__global__ void pcen_bwd_rows_kernel(const float* __restrict__ raw, const void* __restrict__ gout, int BF, int F, int TP,
                                      const float* __restrict__ alpha, const float* __restrict__ delta,
                                      const float* __restrict__ root, const float* __restrict__ ema_w, float floor_,
                                      int mode, float* __restrict__ ema, float* __restrict__ gpre,
@@ -30,7 +32,8 @@ __global__ void pcen_bwd_rows_kernel(const float* __restrict__ raw, const float*
     const int row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= BF) return;
     const float* r = raw + (size_t)row * TP;
-    const float* go = gout + (size_t)row * TP;
+    const int gbf = mode & 4;
+    const size_t go0 = (size_t)row * TP;
     float* gp = gpre + (size_t)row * TP;
     const int f = row % F;
     // fused backward: also a [B][TP][FP] copy with filters in tap-column order
@@ -39,7 +42,8 @@ __global__ void pcen_bwd_rows_kernel(const float* __restrict__ raw, const float*
     auto fl = [&](float v) { return nofloor ? v : fmaxf(v, kPooledFloor); };
     if (!(mode & 1)) {
         for (int m = 0; m < TP; ++m) {
-            const float v = (nofloor || r[m] > kPooledFloor) ? go[m] : 0.0f;
+            const float g = io_load(gout, go0 + m, gbf);
+            const float v = (nofloor || r[m] > kPooledFloor) ? ((mode & 2) ? g / (1.0f + r[m]) : g) : 0.0f;
             gp[m] = v;
             if (gc) gc[(size_t)m * FP] = v;
         }
@@ -66,7 +70,7 @@ __global__ void pcen_bwd_rows_kernel(const float* __restrict__ raw, const float*
         const float u = powf(Mf, a);
         const float v = p / u + d;
         const float vr = powf(v, rho);
-        const float g = go[m];
+        const float g = io_load(gout, go0 + m, gbf);
         const float dv = rho * vr / v * g;
         s_d += dv - rho * d_rho / d * g;
         s_rho += (vr * logf(v) - d_rho * ln_d) * g;
@@ -103,7 +107,7 @@ __global__ void pcen_bwd_rows_kernel(const float* __restrict__ raw, const float*
 #endif
 constexpr int kScanRegChunks = 4;
 #ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
-__global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restrict__ raw, const float* __restrict__ gout, int BF,
+__global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restrict__ raw, const void* __restrict__ gout, int BF,
                                                             int F, int TP, const float* __restrict__ alpha,
                                                             const float* __restrict__ delta, const float* __restrict__ root,
                                                             const float* __restrict__ ema_w, float floor_, int mode,
@@ -116,14 +120,16 @@ __global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restr
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= BF) return;
     const float* r = raw + (size_t)row * TP;
-    const float* go = gout + (size_t)row * TP;
+    const int gbf = mode & 4;                        // grad_out is bfloat16 (widened in the load)
+    const size_t go0 = (size_t)row * TP;
     float* gp = gpre + (size_t)row * TP;
     const int f = row % F;
     float* gc = gcols ? gcols + (size_t)(row / F) * TP * FP + col_of[f] : nullptr;
     if (!(mode & 1)) {
         float sg = 0.0f;
         for (int m = lane; m < TP; m += 64) {
-            const float v = r[m] > kPooledFloor ? go[m] : 0.0f;
+            const float g = io_load(gout, go0 + m, gbf);
+            const float v = r[m] > kPooledFloor ? ((mode & 2) ? g / (1.0f + r[m]) : g) : 0.0f;       // log1p: d log1p(p) / d p
             gp[m] = v;
             sg += v;
             if (gc) gc[(size_t)m * FP] = v;
@@ -232,7 +238,7 @@ __global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restr
                     l2v = logf(v) * 1.4426950408889634f;
                     vr = powf(v, rho);
                 }
-                const float g = go[m];
+                const float g = io_load(gout, go0 + m, gbf);
                 const float dv = rho * vr / v * g;
                 s_d += dv - rho * d_rho / d * g;
                 s_rho += (vr * (l2v * 0.6931471805599453f) - d_rho * ln_d) * g;
@@ -582,7 +588,7 @@ __global__ void dkernel_kernel(const float* __restrict__ part, const float* __re
 // dx[b,i] = sum_c sum_j taps[c][j] * dy[b,c,i - j + padL]
 #ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
 __global__ void dx_kernel(const float* __restrict__ dy, const float* __restrict__ taps, int T, int C, int K, int padL,
-                          float* __restrict__ dx) {
+                          void* __restrict__ dx, int out_bf16 = 0) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
     if (i >= T) return;
@@ -593,7 +599,15 @@ __global__ void dx_kernel(const float* __restrict__ dy, const float* __restrict_
         const int j0 = max(0, i + padL - (T - 1)), j1 = min(K, i + padL + 1);
         for (int j = j0; j < j1; ++j) acc = fmaf(w[j], d[i + padL - j], acc);
     }
-    dx[(size_t)b * T + i] = acc;
+    io_store(dx, (size_t)b * T + i, out_bf16, acc);
+}
+#endif
+
+// bfloat16 waveform -> fp32 copy in the workspace, for the backward families that read x as fp32 only (MFMA, staged)
+#ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
+__global__ void bf16_widen_kernel(const unsigned short* __restrict__ src, size_t n, float* __restrict__ dst) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = bf16_widen(src[i]);
 }
 #endif
 

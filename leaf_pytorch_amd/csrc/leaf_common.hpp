@@ -16,6 +16,21 @@ typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-by
 constexpr float kPooledFloor = 1e-5f;    // frontend.py:84
 // frontend.py:84 is torch.maximum(pooled, 1e-5): NaN propagates (fmaxf would return the floor instead).
 __device__ __forceinline__ float pooled_floor(float v) { return v < kPooledFloor ? kPooledFloor : v; }
+// bfloat16 I/O (LEAF_FLAG_IO_BF16): widening is exact (the 16 bits are the float's upper half); narrowing rounds to nearest even,
+// NaN to the quiet NaN torch's conversion gives.  Arithmetic stays fp32 everywhere.
+__device__ __forceinline__ float bf16_widen(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
+__device__ __forceinline__ unsigned short bf16_round(float v) {
+    const unsigned u = __float_as_uint(v);
+    return v != v ? (unsigned short)0x7fc0u : (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+// element i of an I/O buffer that holds fp32 or (bf16 != 0) bfloat16
+__device__ __forceinline__ float io_load(const void* p, size_t i, int bf16) {
+    return bf16 ? bf16_widen(static_cast<const unsigned short*>(p)[i]) : static_cast<const float*>(p)[i];
+}
+__device__ __forceinline__ void io_store(void* p, size_t i, int bf16, float v) {
+    if (bf16) static_cast<unsigned short*>(p)[i] = bf16_round(v);
+    else static_cast<float*>(p)[i] = v;
+}
 // Compile-time tuning knobs (tools/ablate.py builds variants of this file with -D...; the product uses the defaults)
 #ifndef LEAF_WAVES_PER_WG
 #define LEAF_WAVES_PER_WG 8

@@ -577,12 +577,24 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
                 const int n_c = c * LS;
                 float are[32], aim[32];
                 const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
+                const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
+                if (p.io_bf16) {                                          // bf16 waveform, widened in the load (as the forward, leaf_fft_wg.hpp)
 #pragma unroll
-                for (int r = 0; r < 32; ++r) {
-                    const int i = 64 * r + lane;
-                    const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
-                    are[r] = (n >= 0 && n < p.T) ? xb[n] : 0.0f;
-                    aim[r] = 0.0f;
+                    for (int r = 0; r < 32; ++r) {
+                        const int i = 64 * r + lane;
+                        const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
+                        const unsigned v = xh[min(max(n, 0), p.T - 1)];
+                        are[r] = (n >= 0 && n < p.T) ? __uint_as_float(v << 16) : 0.0f;
+                        aim[r] = 0.0f;
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 32; ++r) {
+                        const int i = 64 * r + lane;
+                        const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
+                        are[r] = (n >= 0 && n < p.T) ? xb[n] : 0.0f;
+                        aim[r] = 0.0f;
+                    }
                 }
                 fft2048w<HALF>(are, aim, scr, scr_lds, twl, twh, lane);
                 wg_wait_ge(&q[9 + slot], gen);                            // the slot's previous occupant has been released
@@ -691,7 +703,9 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
 // ---- backward WITH dL/dx: one wave per block (see the header comment).  Blocks are dealt to the persistent waves by
 // striding; per block: forward transform -> A' into wave-private LDS; for every filter wg_bwd_filter<.., DX = 1> (which
 // adds R_f g into the 64 accumulator registers); then dL/da' = Re(FFT(conj G)), un-rotated into dxblk.
-template <int SK, int SHOP>
+// BF16: the instance for a bfloat16 waveform (LEAF_FLAG_IO_BF16), widened in the load; the fp32 instance carries no trace of it (this
+// kernel sits at the register limit)
+template <int SK, int SHOP, bool BF16 = false>
 __global__ __launch_bounds__(kBlkBwdWaves * 64, 2) void leaf_fft_blk_bwd_dx_kernel(const FftParams p) {
     constexpr int SCRF = kWgScrHalfFloats;
     constexpr int GU = fft_wg_bwd_row_floats(SK);
@@ -721,12 +735,24 @@ __global__ __launch_bounds__(kBlkBwdWaves * 64, 2) void leaf_fft_blk_bwd_dx_kern
         {
             float are[32], aim[32];
             const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
+            const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
+            if constexpr (BF16) {
 #pragma unroll
-            for (int r = 0; r < 32; ++r) {
-                const int i = 64 * r + lane;
-                const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
-                are[r] = (n >= 0 && n < p.T) ? xb[n] : 0.0f;
-                aim[r] = 0.0f;
+                for (int r = 0; r < 32; ++r) {
+                    const int i = 64 * r + lane;
+                    const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
+                    const unsigned v = xh[min(max(n, 0), p.T - 1)];
+                    are[r] = (n >= 0 && n < p.T) ? __uint_as_float(v << 16) : 0.0f;
+                    aim[r] = 0.0f;
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 32; ++r) {
+                    const int i = 64 * r + lane;
+                    const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
+                    are[r] = (n >= 0 && n < p.T) ? xb[n] : 0.0f;
+                    aim[r] = 0.0f;
+                }
             }
             fft2048w<true>(are, aim, scr, scr_lds, twl, twh, lane);
 #pragma unroll
@@ -774,7 +800,8 @@ __global__ __launch_bounds__(kBlkBwdWaves * 64, 2) void leaf_fft_blk_bwd_dx_kern
 
 // dL/dx from the per-block input gradients: x[n] belongs to the NB-sample windows (NB = 2048 or 4096) of the blocks c with
 // 0 <= n - c L + padL < NB (at most three), each with nfq partials (one per filter group); summed in a fixed order.
-#ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
+// BF16: dx is a bfloat16 buffer (LEAF_FLAG_IO_BF16), the sums rounded to nearest even in the store.
+template <bool BF16 = false>
 __global__ void fft_dx_gather_kernel(const float* __restrict__ dxblk, int T, int nblk, int nfq, int L, int padL,
                                      float* __restrict__ dx, int NB = kFftN) {
     // four consecutive samples per thread (a quarter of the waves, four loads in flight each); per sample the same blocks in the
@@ -797,8 +824,10 @@ __global__ void fft_dx_gather_kernel(const float* __restrict__ dxblk, int T, int
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-        if (n0 + k < T) dx[(size_t)b * T + n0 + k] = acc[k];
+        if (n0 + k < T) {
+            if constexpr (BF16) reinterpret_cast<unsigned short*>(dx)[(size_t)b * T + n0 + k] = bf16_round(acc[k]);
+            else dx[(size_t)b * T + n0 + k] = acc[k];
+        }
 }
-#endif
 
 }  // namespace

@@ -659,7 +659,7 @@ const char* leaf_status_string(int status) {
         case LEAF_ERR_LAUNCH: return "HIP kernel launch failed";
         case LEAF_ERR_NO_DEVICE: return "no usable gfx950 device";
         case LEAF_ERR_ALIGNMENT: return "buffer not 4-byte aligned";
-        case LEAF_ERR_UNSUPPORTED: return "combination not supported (bfloat16 I/O has no backward / no staged path: use float32 buffers; LEAF_FLAG_PEAKNORM needs an overlap-save path)";
+        case LEAF_ERR_UNSUPPORTED: return "combination not supported (bfloat16 I/O has no staged forward: use float32 buffers; LEAF_FLAG_PEAKNORM needs an overlap-save path and has no backward)";
     }
     return "unknown status";
 }
@@ -1322,7 +1322,6 @@ int leaf_forward_save_f32(const float* x, int B, int T, const float* kernel, con
                           int flags, int algo, float* out, float* pooled_raw, void* workspace, size_t workspace_bytes,
                           void* stream) {
     if (!pooled_raw) return LEAF_ERR_NULL_POINTER;
-    if (flags & LEAF_FLAG_IO_BF16) return LEAF_ERR_UNSUPPORTED;          // the backward is fp32-only
     // forward-only: pooled_raw would be that of the normalised clips while leaf_backward_f32 differentiates against x
     if (flags & LEAF_FLAG_PEAKNORM) return LEAF_ERR_UNSUPPORTED;
     return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out, workspace,
@@ -1517,7 +1516,7 @@ inline int wg_bwd_sixteenths(int K, int hop, bool dx) {
     if (!band_geometry_ok(K, hop) || !LEAF_BAND_BWD || !tl_bwd_band_possible) return 20;
     return dx ? (LEAF_BAND_BWD_DX ? LEAF_WG_BWD_DX_BAND_SIXTEENTHS : 20) : LEAF_WG_BWD_BAND_SIXTEENTHS;
 }
-FftWgBwdLaunch pick_fft_wg_bwd_kernel(int K, int hop, bool dx, long long blocks = 0) {
+FftWgBwdLaunch pick_fft_wg_bwd_kernel(int K, int hop, bool dx, long long blocks = 0, bool io_bf16 = false) {
     if (LEAF_FFT_FORCE_GENERIC) return {nullptr, 0, 0};
     if (dx) {
         if (!(fft_static_geometry(K, hop) && (K & 1))) return {nullptr, 0, 0};
@@ -1526,7 +1525,7 @@ FftWgBwdLaunch pick_fft_wg_bwd_kernel(int K, int hop, bool dx, long long blocks 
             fft_wg_bwd_dx_lds_bytes(12, K) <= (size_t)kMaxLds)
             return {as_fft_kernel(leaf_inst_fft_wg_bwd_dx(K)), 12, fft_wg_bwd_dx_lds_bytes(12, K), true};
         // below that: one wave per block, G in registers (leaf_fft_blk_bwd_dx_kernel)
-        return {as_fft_kernel(leaf_inst_fft_blk_bwd_dx(K)), kBlkBwdWaves, fft_blk_bwd_lds_bytes(K)};
+        return {as_fft_kernel(io_bf16 ? leaf_inst_fft_blk_bwd_dx_bf16(K) : leaf_inst_fft_blk_bwd_dx(K)), kBlkBwdWaves, fft_blk_bwd_lds_bytes(K)};
     }
     if (fft_static_geometry(K, hop) && (K & 1)) return {as_fft_kernel(leaf_inst_fft_wg_bwd(K)), 12, fft_wg_bwd_lds_bytes(12, K)};
     return {nullptr, 0, 0};
@@ -1703,24 +1702,36 @@ static BwdPath bwd_path(int B, int T, int F, int K, int hop, int flags, bool nee
     }
     return BWD_PATH_STAGED;
 }
-
-size_t leaf_backward_workspace_bytes(int B, int T, int F, int K, int hop, int flags, int need_dx) {
-    if (check_shape(B, T, F, K, hop) != LEAF_OK) return 0;
-    switch (bwd_path(B, T, F, K, hop, flags, need_dx != 0)) {
-        case BWD_PATH_FFT: return fft_bwd_layout(make_fft_plan(B, T, F, K, hop), B, F, need_dx != 0).total * 4;
-        case BWD_PATH_FFT4K: return fft4k_bwd_layout(make_fft4k_bwd_plan(B, T, F, K, hop, need_dx != 0), B, F).total * 4;
+static size_t bwd_own_workspace_floats(BwdPath path, int B, int T, int F, int K, int hop, bool need_dx) {
+    switch (path) {
+        case BWD_PATH_FFT: return fft_bwd_layout(make_fft_plan(B, T, F, K, hop), B, F, need_dx).total;
+        case BWD_PATH_FFT4K: return fft4k_bwd_layout(make_fft4k_bwd_plan(B, T, F, K, hop, need_dx), B, F).total;
         case BWD_PATH_MFMA: {
             const FusedPlan pl = make_plan(B, T, F, K, hop);
-            return bwd_layout(pl, make_bwd_plan(pl, T), B, T, F, num_cus()).total * 4;
+            return bwd_layout(pl, make_bwd_plan(pl, T), B, T, F, num_cus()).total;
         }
         default: break;
     }
     const int TP = (T - 1) / hop + 1;
-    const size_t fl = align_up((size_t)2 * F * K, 64) * 2 /* taps, dtaps unused slot */ + align_up((size_t)F * K, 64) * 2 +
-                      align_up((size_t)B * 2 * F * T, 64) + align_up((size_t)B * F * T, 64) +
-                      align_up((size_t)B * F * TP, 64) * 3 + align_up((size_t)B * F * 4, 64) +
-                      align_up((size_t)B * 2 * F * K, 64);
-    return fl * 4;
+    return align_up((size_t)2 * F * K, 64) * 2 /* taps, dtaps unused slot */ + align_up((size_t)F * K, 64) * 2 +
+           align_up((size_t)B * 2 * F * T, 64) + align_up((size_t)B * F * T, 64) +
+           align_up((size_t)B * F * TP, 64) * 3 + align_up((size_t)B * F * 4, 64) +
+           align_up((size_t)B * 2 * F * K, 64);
+}
+
+// LEAF_FLAG_IO_BF16: the static-geometry overlap-save backwards (K = 401 / 160, 801 / 320, 201 / 80) and the 4096-sample plans read
+// the bf16 waveform directly (nothing added); the run-time-geometry kernels of the 2048-sample plan, the MFMA and the staged backward
+// read fp32 only and get a widened copy of x behind their own layout
+static size_t bwd_x32_floats(BwdPath path, int B, int T, int K, int hop, int flags) {
+    if (!(flags & LEAF_FLAG_IO_BF16) || path == BWD_PATH_FFT4K) return 0;
+    if (path == BWD_PATH_FFT && fft_static_geometry(K, hop) && (K & 1) && !LEAF_FFT_FORCE_GENERIC) return 0;
+    return align_up((size_t)B * T, 64);
+}
+
+size_t leaf_backward_workspace_bytes(int B, int T, int F, int K, int hop, int flags, int need_dx) {
+    if (check_shape(B, T, F, K, hop) != LEAF_OK) return 0;
+    const BwdPath path = bwd_path(B, T, F, K, hop, flags, need_dx != 0);
+    return (bwd_own_workspace_floats(path, B, T, F, K, hop, need_dx != 0) + bwd_x32_floats(path, B, T, K, hop, flags)) * 4;
 }
 
 int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
@@ -1728,6 +1739,7 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
                       int flags, const float* grad_out, const float* pooled_raw, float* g_kernel, float* g_pool_w,
                       float* g_pool_b, float* g_alpha, float* g_delta, float* g_root, float* g_ema_w, float* g_x,
                       void* workspace, size_t workspace_bytes, void* stream) {
+    // LEAF_FLAG_IO_BF16: x, grad_out and g_x are bfloat16 buffers behind the float pointers (as in the forward); everything else fp32
     if (empty_batch(B, T, F, K, hop)) {
         // the sum over zero clips: every parameter gradient is exactly zero (what autograd returns for the reference)
         if (!g_kernel || !g_pool_w || !g_pool_b) return LEAF_ERR_NULL_POINTER;
@@ -1748,14 +1760,33 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
     int rc = check_shape(B, T, F, K, hop);
     if (rc != LEAF_OK) return rc;
     if (2 * F > 65535 || B > 65535) return LEAF_ERR_BAD_SHAPE;
+    const bool io_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;
+    {
+        const uintptr_t io_mask = io_bf16 ? 1u : 3u;
+        if ((reinterpret_cast<uintptr_t>(x) & io_mask) || (reinterpret_cast<uintptr_t>(grad_out) & io_mask) ||
+            (reinterpret_cast<uintptr_t>(g_x) & io_mask) || misaligned(workspace))
+            return LEAF_ERR_ALIGNMENT;
+    }
     const BwdPath path = bwd_path(B, T, F, K, hop, flags, g_x != nullptr);
     if (!workspace || workspace_bytes < leaf_backward_workspace_bytes(B, T, F, K, hop, flags, g_x != nullptr))
         return LEAF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int TP = (T - 1) / hop + 1;
     const int padL = K / 2 + K % 2 - 1;
-    const int mode = use_pcen ? 1 : 0;
+    // first-stage mode (pcen_bwd_scan_kernel): bit0 PCEN, bit1 log1p compression (PCEN off only, as in the forward), bit2 bf16 grad_out;
+    // param_reduce_kernel reads bit0 alone
+    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (io_bf16 ? 4 : 0);
     float* ws = static_cast<float*>(workspace);
+    bool x_bf16 = io_bf16;                                   // what the kernels below read x as
+    if (float* x32 = bwd_x32_floats(path, B, T, K, hop, flags) ? ws + bwd_own_workspace_floats(path, B, T, F, K, hop, g_x != nullptr) : nullptr) {
+        // these families read fp32: one widening pass into the workspace's tail, then the fp32 path
+        const size_t n = (size_t)B * T;
+        hipLaunchKernelGGL(bf16_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                           reinterpret_cast<const unsigned short*>(x), n, x32);
+        LEAF_LAUNCH_CHECK();
+        x = x32;
+        x_bf16 = false;
+    }
     if (path == BWD_PATH_FFT4K) {
         // ---- overlap-save backward on 4096-sample blocks: long odd windows, parameter gradients
         const Fft4kBwdPlan bp = make_fft4k_bwd_plan(B, T, F, K, hop, g_x != nullptr);
@@ -1789,7 +1820,7 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
         hipLaunchKernelGGL(iota_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, col_of, F);
         LEAF_LAUNCH_CHECK();
         FftParams q{};
-        q.x = x; q.io_bf16 = 0; q.H = reinterpret_cast<const float2*>(tab3); q.Gz = Grow; q.part = part;
+        q.x = x; q.io_bf16 = x_bf16 ? 1 : 0; q.H = reinterpret_cast<const float2*>(tab3); q.Gz = Grow; q.part = part;
         q.B = B; q.T = T; q.TP = bp.TP; q.F = F; q.K = K; q.hop = hop; q.padL = bp.padL; q.L = bp.L; q.nblk = bp.nblk;
         q.nslot = 2; q.GZ = bp.RG;
         q.lone = reinterpret_cast<const float*>(Wt);                      // (read by the static forward kernel when it recomputes below)
@@ -1832,7 +1863,7 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
         hipLaunchKernelGGL(kb, grid, dim3(bp.nw * 64), blds, st, q);
         LEAF_LAUNCH_CHECK();
         if (bp.dx) {
-            hipLaunchKernelGGL(fft_dx_gather_kernel, dim3(ceil_div(T, 1024), B), dim3(256), 0, st, ws + L.dxblk, T, bp.nblk, 1, bp.L,
+            hipLaunchKernelGGL(io_bf16 ? fft_dx_gather_kernel<true> : fft_dx_gather_kernel<false>, dim3(ceil_div(T, 1024), B), dim3(256), 0, st, ws + L.dxblk, T, bp.nblk, 1, bp.L,
                                bp.padL, g_x, kFft4N);
             LEAF_LAUNCH_CHECK();
         }
@@ -1890,7 +1921,7 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
             }
             LEAF_LAUNCH_CHECK();
             FftParams q{};
-            q.x = x; q.io_bf16 = 0; q.H = reinterpret_cast<const float2*>(R3); q.Gz = Gz; q.part = part;
+            q.x = x; q.io_bf16 = x_bf16 ? 1 : 0; q.H = reinterpret_cast<const float2*>(R3); q.Gz = Gz; q.part = part;
             q.lone = (K & 1) ? nullptr : ws + L.lone;
             q.B = B; q.T = T; q.TP = fp.TP; q.F = F; q.K = K; q.hop = hop; q.padL = fp.padL;
             q.L = fp.L; q.nblk = fp.nblk; q.GZ = fp.GZ; q.nslot = fp.nslot; q.g_bufs = fp.g_bufs; q.NT = fp.NT; q.fq = fp.fq; q.nfq = fp.nfq;
@@ -1917,7 +1948,7 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
             q.gpre = gpre; q.pool_w = pool_w; q.dkpart = dkpart; q.dwpart = dwpart; q.part = nullptr;
             if (fft_wg_bwd_use(fp, B, K, hop, g_x != nullptr)) {
                 // workgroup-per-block backward; with g_x the per-block input gradients go to dxblk and are gathered below
-                FftWgBwdLaunch wl = pick_fft_wg_bwd_kernel(K, hop, g_x != nullptr, (long long)B * fp.nblk);
+                FftWgBwdLaunch wl = pick_fft_wg_bwd_kernel(K, hop, g_x != nullptr, (long long)B * fp.nblk, x_bf16);
                 q.part = g_x ? ws + L.dxblk : nullptr;
                 if (band_bwd) {
                     band.lds_off = (int)(wl.lds / 4);
@@ -1930,8 +1961,8 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
                 hipLaunchKernelGGL(wl.fn, dim3(std::max(1, std::min(wgs, num_cus()))), dim3(wl.nw * 64), wl.lds, st, q);
                 LEAF_LAUNCH_CHECK();
                 if (g_x) {
-                    hipLaunchKernelGGL(fft_dx_gather_kernel, dim3(ceil_div(T, 1024), B), dim3(256), 0, st, ws + L.dxblk, T, fp.nblk,
-                                       wl.block_dx ? 1 : fp.nfq, fp.L, fp.padL, g_x);
+                    hipLaunchKernelGGL(io_bf16 ? fft_dx_gather_kernel<true> : fft_dx_gather_kernel<false>, dim3(ceil_div(T, 1024), B), dim3(256), 0, st, ws + L.dxblk, T, fp.nblk,
+                                       wl.block_dx ? 1 : fp.nfq, fp.L, fp.padL, g_x, kFftN);
                     LEAF_LAUNCH_CHECK();
                 }
             } else if (g_x && pick_fft_wgg_bwd_dx_kernel(fp, B, K, hop).fn) {
@@ -1941,8 +1972,8 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wl.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl.lds);
                 hipLaunchKernelGGL(wl.fn, dim3(std::max(1, std::min(B * fp.nblk, num_cus()))), dim3(wl.nw * 64), wl.lds, st, q);
                 LEAF_LAUNCH_CHECK();
-                hipLaunchKernelGGL(fft_dx_gather_kernel, dim3(ceil_div(T, 1024), B), dim3(256), 0, st, ws + L.dxblk, T, fp.nblk, 1, fp.L,
-                                   fp.padL, g_x);
+                hipLaunchKernelGGL(io_bf16 ? fft_dx_gather_kernel<true> : fft_dx_gather_kernel<false>, dim3(ceil_div(T, 1024), B), dim3(256), 0, st, ws + L.dxblk, T, fp.nblk, 1, fp.L,
+                                   fp.padL, g_x, kFftN);
                 LEAF_LAUNCH_CHECK();
             } else if (g_x) {
                 return LEAF_ERR_BAD_ALGO;                                 // bwd_path() admits the FFT path only with a dL/dx kernel
@@ -2077,7 +2108,7 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
     hipLaunchKernelGGL(dkernel_kernel, dim3(F), dim3(256), 0, st, tpart, taps, kernel, B, F, K, gabor_bounds(K), g_kernel);
     LEAF_LAUNCH_CHECK();
     if (g_x) {
-        hipLaunchKernelGGL(dx_kernel, dim3(ceil_div(T, 256), B), dim3(256), 0, st, y, taps, T, 2 * F, K, padL, g_x);
+        hipLaunchKernelGGL(dx_kernel, dim3(ceil_div(T, 256), B), dim3(256), 0, st, y, taps, T, 2 * F, K, padL, g_x, io_bf16 ? 1 : 0);
         LEAF_LAUNCH_CHECK();
     }
     return LEAF_OK;

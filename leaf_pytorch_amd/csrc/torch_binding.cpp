@@ -144,33 +144,45 @@ Tensor op_forward(const Tensor& x, const Tensor& kernel, const Tensor& pool_w, c
 // leaf_amd::forward_train -- the same, additionally returning the pre-floor pooled tensor the backward consumes
 std::tuple<Tensor, Tensor> op_forward_train(const Tensor& x, const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b,
                                             const OptTensor& alpha, const OptTensor& delta, const OptTensor& root,
-                                            const OptTensor& ema_w, int64_t K, int64_t hop, int64_t algo) {
+                                            const OptTensor& ema_w, int64_t K, int64_t hop, int64_t algo, bool log1p) {
     const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
     Tensor raw;
-    Tensor out = forward_impl(x, p, K, hop, false, algo, &raw);
+    Tensor out = forward_impl(x, p, K, hop, log1p, algo, &raw);
     return {out, raw};
 }
 
 // leaf_amd::backward -- what autograd derives for frontend.py:78-89: (g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root,
-// g_ema_w, g_x); the PCEN entries are empty tensors without PCEN, g_x is empty unless need_dx.
+// g_ema_w, g_x); the PCEN entries are empty tensors without PCEN, g_x is empty unless need_dx.  `flags` are C-ABI flags
+// (LEAF_FLAG_BWD_*, and LEAF_FLAG_LOG1P for the backward of the log1p-compressed forward); LEAF_FLAG_PCEN and
+// LEAF_FLAG_IO_BF16 follow from the tensors.  bfloat16 x: grad_out is bfloat16 too, g_x comes back in bfloat16, the
+// parameter gradients and pooled_raw are float32.
 std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b,
                                 const OptTensor& alpha, const OptTensor& delta, const OptTensor& root, const OptTensor& ema_w,
                                 int64_t K, int64_t hop, const Tensor& grad_out, const OptTensor& pooled_raw, bool need_dx,
                                 int64_t flags) {
     Tensor x2 = waveform_2d(x);
-    TORCH_CHECK(x2.scalar_type() == at::kFloat, "the backward is float32 only, got ", x2.scalar_type());
+    const bool io_bf16 = x2.scalar_type() == at::kBFloat16;
+    TORCH_CHECK(io_bf16 || x2.scalar_type() == at::kFloat, "x must be float32 (or bfloat16 for the bf16-I/O extension), got ",
+                x2.scalar_type());
     const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
     TORCH_CHECK(x2.size(1) < (int64_t(1) << 31), "a clip of ", x2.size(1), " samples is beyond the C ABI's 32-bit sample index");
     const int64_t B = x2.size(0);
     const int T = (int)x2.size(1), F = (int)p.kernel.size(0);
     const int TP = leaf_num_frames(T, (int)K, (int)hop);
-    Tensor go = dev_f32(grad_out, "grad_out", x2.device());
+    Tensor go;
+    if (io_bf16) {
+        TORCH_CHECK(grad_out.device() == x2.device(), "grad_out is on ", grad_out.device(), ", expected ", x2.device());
+        TORCH_CHECK(grad_out.scalar_type() == at::kBFloat16, "grad_out must be bfloat16 when x is bfloat16, got ", grad_out.scalar_type());
+        go = grad_out.contiguous();
+    } else {
+        go = dev_f32(grad_out, "grad_out", x2.device());
+    }
     TORCH_CHECK(go.dim() == 3 && go.size(0) == B && go.size(1) == F && go.size(2) == TP, "grad_out has shape ", go.sizes(),
                 ", expected (", B, ",", F, ",", TP, ")");
     OptTensor raw = dev_f32(pooled_raw, "pooled_raw", x2.device());
     c10::hip::HIPGuardMasqueradingAsCUDA guard(x2.device());
     auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x2.device().index());
-    auto opt = x2.options();
+    auto opt = x2.options().dtype(at::kFloat);                // parameter gradients are float32 whatever the I/O type
     Tensor gk = at::empty_like(p.kernel), gpw = at::empty_like(p.pool_w), gpb = at::empty_like(p.pool_b);
     Tensor ga = at::empty({p.pcen ? F : 0}, opt), gd = at::empty({p.pcen ? F : 0}, opt), gr = at::empty({p.pcen ? F : 0}, opt),
            gw = at::empty({p.pcen ? F : 0}, opt);
@@ -179,7 +191,11 @@ std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Ten
         for (Tensor* g : {&gk, &gpw, &gpb, &ga, &gd, &gr, &gw}) g->zero_();
         return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw, need_dx ? gx.reshape(x.sizes()) : gx};
     }
-    const int fl = (int)flags | (p.pcen ? LEAF_FLAG_PCEN : 0);
+    const int fl = ((int)flags & ~(LEAF_FLAG_PCEN | LEAF_FLAG_IO_BF16)) | (p.pcen ? LEAF_FLAG_PCEN : 0) | (io_bf16 ? LEAF_FLAG_IO_BF16 : 0);
+    const size_t io = io_bf16 ? 2 : 4;
+    auto io_at = [io](const Tensor& t, size_t elems) {      // element offset into a float32 / bfloat16 I/O tensor, as the C ABI's float pointer
+        return reinterpret_cast<float*>(static_cast<char*>(t.data_ptr()) + elems * io);
+    };
     // B * T >= 2^31: slices of whole clips as in the forward; the parameter gradients of the slices are added in slice order
     // (a fixed order: the step stays bit-reproducible), dL/dx is written slice by slice
     const BatchSlices sl = batch_slices(B, T);
@@ -197,13 +213,13 @@ std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Ten
         const bool first = b0 == 0;
         Tensor &k_ = first ? gk : tk, &pw_ = first ? gpw : tpw, &pb_ = first ? gpb : tpb, &a_ = first ? ga : ta, &d_ = first ? gd : td,
                &r_ = first ? gr : tr, &w_ = first ? gw : tw;
-        const int rc = leaf_backward_f32(fptr(x2) + (size_t)b0 * T, nb, T, fptr(p.kernel), fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha),
+        const int rc = leaf_backward_f32(io_at(x2, (size_t)b0 * T), nb, T, fptr(p.kernel), fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha),
                                          fptr(p.delta), fptr(p.root), fptr(p.ema_w), F, (int)K, (int)hop, fl,
-                                         fptr(go) + (size_t)b0 * F * TP, raw ? fptr(raw) + (size_t)b0 * F * TP : nullptr,
+                                         io_at(go, (size_t)b0 * F * TP), raw ? fptr(raw) + (size_t)b0 * F * TP : nullptr,
                                          k_.data_ptr<float>(), pw_.data_ptr<float>(), pb_.data_ptr<float>(),
                                          p.pcen ? a_.data_ptr<float>() : nullptr, p.pcen ? d_.data_ptr<float>() : nullptr,
                                          p.pcen ? r_.data_ptr<float>() : nullptr, p.pcen ? w_.data_ptr<float>() : nullptr,
-                                         need_dx ? gx.data_ptr<float>() + (size_t)b0 * T : nullptr, ws.data_ptr(), (size_t)ws.numel(),
+                                         need_dx ? io_at(gx, (size_t)b0 * T) : nullptr, ws.data_ptr(), (size_t)ws.numel(),
                                          stream.stream());
         check_status(rc, "leaf_backward_f32");
         if (!first) {
@@ -220,7 +236,7 @@ TORCH_LIBRARY(leaf_amd, m) {
     m.def("forward(Tensor x, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, Tensor? root, "
           "Tensor? ema_w, int K, int hop, bool log1p, int algo) -> Tensor");
     m.def("forward_train(Tensor x, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, Tensor? root, "
-          "Tensor? ema_w, int K, int hop, int algo) -> (Tensor, Tensor)");
+          "Tensor? ema_w, int K, int hop, int algo, bool log1p=False) -> (Tensor, Tensor)");
     m.def("backward(Tensor x, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, Tensor? root, "
           "Tensor? ema_w, int K, int hop, Tensor grad_out, Tensor? pooled_raw, bool need_dx, int flags) -> Tensor[]");
 }

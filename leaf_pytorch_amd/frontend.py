@@ -29,12 +29,13 @@ class _LeafForward(torch.autograd.Function):
     """Forward = fused HIP path (leaf_forward_f32); backward = leaf_backward_f32 (recomputes on device)."""
 
     @staticmethod
-    def forward(ctx, x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen, algo):
+    def forward(ctx, x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen, algo, log1p=False):
         if algo & _native.OPT_PEAKNORM:
             # leaf_forward_save_f32 would hand the backward a pooled tensor of the NORMALISED clips next to the raw x
             raise RuntimeError("the folded PeakNormalization prologue is forward-only (no backward through it)")
         out, raw = _native.leaf_forward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen=pcen,
-                                        algo=algo, save_raw=True)
+                                        log1p=log1p, algo=algo, save_raw=True)
+        ctx.log1p = bool(log1p) and not pcen
         ctx.save_for_backward(x, kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if pcen else []))
         ctx.geom = (K, hop, pcen)
         ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)      # Leaf.full_transforms(): the backward keeps them too
@@ -51,10 +52,11 @@ class _LeafForward(torch.autograd.Function):
         need_dx = ctx.needs_input_grad[0]
         gk, gpw, gpb, ga, gd, gr, gw, gx = _native.leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop,
                                                                  grad_out, pcen=pcen, need_dx=need_dx, pooled_raw=raw,
-                                                                 full_transforms=ctx.full, strict_band_classes=ctx.strict)
+                                                                 full_transforms=ctx.full, strict_band_classes=ctx.strict,
+                                                                 log1p=ctx.log1p)
         if gx is not None:
             gx = gx.reshape(x.shape)
-        return gx, gk, gpw, gpb, ga, gd, gr, gw, None, None, None, None
+        return gx, gk, gpw, gpb, ga, gd, gr, gw, None, None, None, None, None
 
 
 class Leaf(nn.Module):
@@ -90,6 +92,7 @@ class Leaf(nn.Module):
         self._tables = None
         self._tables_key = None
         self._fuse_peaknorm = False          # not part of the reference surface: see fuse_peak_normalization()
+        self._log1p = False                  # not part of the reference surface: see log_compression()
 
     def full_transforms(self, enable: bool = True) -> "Leaf":
         """Not part of the reference surface: switch the band-limited filter tasks off for this module -- every filter on the
@@ -98,6 +101,17 @@ class Leaf(nn.Module):
         oracle in the forward and ~1e-5 of the full-transform gradients; this is the opt-out for a caller who wants the
         formulation without the approximation, at ~1.8x the time of the 16 kHz forward."""
         self._algo = (self._algo | _native.ALGO_FULL_TRANSFORMS) if enable else (self._algo & ~_native.ALGO_FULL_TRANSFORMS)
+        return self
+
+    def log_compression(self, enable: bool = True) -> "Leaf":
+        """Not part of the reference surface: log compression in place of PCEN -- ``forward(x)`` returns
+        ``log1p(max(pooled, 1e-5))`` (the LEAF paper's ablation without PCEN; LEAF_FLAG_LOG1P), computed where the fused
+        kernels finalize a frame, and the backward applies ``1 / (1 + pooled)`` where it reads ``grad_out``: no extra pass over
+        the features in either direction.  Needs ``pcen_compression=False`` (``ValueError`` otherwise).  Adds no parameter and
+        no buffer: ``state_dict`` keys stay those of the reference, so its checkpoints still load strictly."""
+        if enable and self._compression is not None:
+            raise ValueError("log_compression() needs a Leaf built with pcen_compression=False (PCEN is the compression of this module)")
+        self._log1p = bool(enable)
         return self
 
     def fuse_peak_normalization(self, enable: bool = True) -> "Leaf":
@@ -157,6 +171,7 @@ class Leaf(nn.Module):
         if c is not None and c._floor != 1e-12:
             raise NotImplementedError("fused path is specialised for the PCEN floor Leaf constructs (1e-12)")
         args = (x, *params, self._complex_conv._kernel_size, self._pooling.strides, c is not None, algo)
+        log1p = self._log1p and c is None
         needs_grad = params_need_grad or (torch.is_grad_enabled() and x.requires_grad)
         if needs_grad and (algo & _native.OPT_PEAKNORM):
             raise RuntimeError("Leaf.forward: the folded PeakNormalization prologue is forward-only")   # unreachable by design
@@ -164,13 +179,11 @@ class Leaf(nn.Module):
             # dispatcher ops (csrc/torch_binding.cpp): traceable by torch.compile / export, one hop per eager call
             _ops.load()
             if needs_grad:
-                if x.dtype == torch.bfloat16:
-                    raise RuntimeError("Leaf.forward: the backward is float32 only -- bfloat16 I/O is an inference extension")
-                return _ops.forward_train(*args[:10], algo=args[11])
+                return _ops.forward_train(*args[:10], algo=args[11], log1p=log1p)
             if not (self._cache_tables and not torch.compiler.is_compiling()):
-                return _ops.forward(*args[:10], algo=args[11])
+                return _ops.forward(*args[:10], log1p=log1p, algo=args[11])
         if needs_grad:
-            return _LeafForward.apply(*args)
+            return _LeafForward.apply(*args, log1p)
         if self._cache_tables and self._algo in (_native.ALGO_AUTO, _native.ALGO_FFT):
             K, hop = args[8], args[9]
             B, T, F = x.shape[0], x.shape[-1], args[1].shape[0]
@@ -183,6 +196,6 @@ class Leaf(nn.Module):
                 tables = self._prepared_tables()
                 if tables is not None:
                     return _native.leaf_forward_prepared(x, tables, args[3], args[4], args[5], args[6], args[7],
-                                                         args[1].shape[0], K, hop, pcen=args[10])
-        return _native.leaf_forward(*args[:8], args[8], args[9], pcen=args[10], algo=args[11] & ~_native.OPT_PEAKNORM,
+                                                         args[1].shape[0], K, hop, pcen=args[10], log1p=log1p)
+        return _native.leaf_forward(*args[:8], args[8], args[9], pcen=args[10], log1p=log1p, algo=args[11] & ~_native.OPT_PEAKNORM,
                                     peak_normalize=bool(args[11] & _native.OPT_PEAKNORM))

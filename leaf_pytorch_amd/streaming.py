@@ -31,7 +31,7 @@ class LeafStream:
         self.lead = -(-2 * self.pad_l // self.hop)                        # frames of lead-in
         # ... and holds every sample up to m' hop + 2 (K - 1 - pad_l)
         self.reach = 2 * (self.K - 1 - self.pad_l)
-        self.log1p = log1p
+        self.log1p = bool(log1p) or bool(getattr(leaf, "_log1p", False))   # the module's log_compression() switch, or asked for here
         # (B, L): the samples still needed, from a whole number of hops before the next frame to emit.  At the start of a
         # stream the buffer begins at the recording's first sample -- the reference zero-pads the ENERGY in front of a clip
         # (frontend.py:15-19 then pooling.py:41), not the waveform, so the first frames must see the true clip start --

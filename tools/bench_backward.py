@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Time forward and forward+backward of Leaf (parameters require grad) on one GPU.
-   usage: bench_backward.py [B [n_filters sample_rate seconds [nodx]]]   (default 256 clips of the default 40 f / 16 kHz / 1 s;
-   nodx skips the dL/dx timing -- staged kernels, hundreds of ms, for geometries without a fused dL/dx)"""
+   usage: bench_backward.py [--no-pcen | --log1p] [--bf16] [--interleave V1,V2,..] [B [n_filters sample_rate seconds [nodx]]]
+   (default 256 clips of the default 40 f / 16 kHz / 1 s, PCEN on, float32;
+   nodx skips the dL/dx timing -- staged kernels, hundreds of ms, for geometries without a fused dL/dx)
+   --no-pcen: PCEN off (BASELINE configs[3] without compression); --log1p: PCEN off with Leaf.log_compression() (configs[3]);
+   --bf16: bfloat16 waveform, features, grad_out and dL/dx (configs[4]).
+   --interleave pcen,off,log1p,pcen+bf16,...: instead of the line above, the training step (grad_out resident; with "+dx": incl. dL/dx)
+   of each named variant timed in turn, round after round, in this one process: median, min and max of the rounds per variant, so that
+   two variants are compared under the same clocks and the spread of each is on the page."""
 import os
 import sys
 
@@ -11,13 +17,29 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from leaf_pytorch_amd import Leaf  # noqa: E402
 
 dev = torch.device("cuda:0")
+OPTS = {a for a in sys.argv[1:] if a in ("--no-pcen", "--log1p", "--bf16")}
+INTERLEAVE = None
+if "--interleave" in sys.argv:
+    i = sys.argv.index("--interleave")
+    INTERLEAVE = sys.argv[i + 1].split(",")
+    del sys.argv[i:i + 2]
+sys.argv = [a for a in sys.argv if a not in OPTS]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 F = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 SR = int(sys.argv[3]) if len(sys.argv) > 3 else 16000
 SECS = float(sys.argv[4]) if len(sys.argv) > 4 else 1.0
 torch.manual_seed(0)
-m = Leaf(n_filters=F, sample_rate=SR).to(dev)
+
+
+def make(pcen=True, log1p=False):
+    mod = Leaf(n_filters=F, sample_rate=SR, pcen_compression=pcen and not log1p)
+    return (mod.log_compression() if log1p else mod).to(dev)
+
+
+m = make(pcen="--no-pcen" not in OPTS, log1p="--log1p" in OPTS)
 x = 2 * torch.rand(B, 1, int(SR * SECS), device=dev) - 1
+if "--bf16" in OPTS:
+    x = x.to(torch.bfloat16)
 
 
 def timed(fn, n=20):
@@ -84,6 +106,38 @@ def graphed(fn_step):
 
 
 NODX = len(sys.argv) > 5 and sys.argv[5] == "nodx"
+if INTERLEAVE:
+    import statistics
+    steps = {}
+    for name in INTERLEAVE:
+        parts = name.split("+")
+        mod = make(pcen=parts[0] == "pcen", log1p=parts[0] == "log1p")
+        xv = (x.to(torch.bfloat16) if "bf16" in parts else x.float()).clone().requires_grad_("dx" in parts)
+        with torch.no_grad():
+            gv = torch.randn_like(mod(xv))
+
+        def step(mod=mod, xv=xv, gv=gv):
+            mod.zero_grad(set_to_none=True)
+            xv.grad = None
+            torch.autograd.backward(mod(xv), gv)
+        steps[name] = step
+    res = {name: [] for name in steps}
+    for rnd in range(9):
+        for name, step in steps.items():
+            for _ in range(5):
+                step()
+            torch.cuda.synchronize()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(20):
+                step()
+            e.record(); e.synchronize()
+            if rnd:                                # (the first round warms the clocks and the allocator)
+                res[name].append(s.elapsed_time(e) / 20)
+    for name, r in res.items():
+        print(f"B={B} F={F} sr={SR} {SECS:g}s {name:14s} forward+backward (grad_out resident) median {statistics.median(r):.4f} ms   "
+              f"min {min(r):.4f}   max {max(r):.4f}   spread {max(r) - min(r):.4f}")
+    sys.exit(0)
 print(f"B={B} F={F} sr={SR} {SECS:g}s: forward {timed(fwd):.3f} ms   forward+backward {timed(fwd_bwd):.3f} ms   "
       f"(grad_out resident: {timed(fwd_bwd_resident):.3f} ms)   "
       + ("" if NODX else f"forward+backward incl. dL/dx {timed(fwd_bwd_dx):.3f} ms")
