@@ -52,10 +52,12 @@ typedef enum leaf_status {
     LEAF_ERR_BAD_ALGO = -4,       /* unknown / inapplicable algorithm selector              */
     LEAF_ERR_LAUNCH = -5,         /* HIP reported a launch failure (hipGetLastError != 0)   */
     LEAF_ERR_NO_DEVICE = -6,      /* no usable gfx950 device                                */
-    LEAF_ERR_ALIGNMENT = -7,      /* a buffer is not 4-byte aligned                         */
+    LEAF_ERR_ALIGNMENT = -7,      /* a buffer is not 4-byte aligned (bfloat16 / 16-bit PCM buffers: 2-byte) */
     LEAF_ERR_UNSUPPORTED = -8     /* valid arguments, unsupported combination: bfloat16 I/O with the staged FORWARD
                                      kernels (the backward takes it on every path, ABI 6); LEAF_FLAG_PEAKNORM with
-                                     leaf_forward_save_f32 / leaf_forward_prepared_f32 or off the overlap-save paths */
+                                     leaf_forward_save_f32 / leaf_forward_prepared_f32 or off the overlap-save paths;
+                                     LEAF_FLAG_X_PCM16 with the staged FORWARD kernels, together with LEAF_FLAG_IO_BF16, or
+                                     with g_x != NULL (an integer input has no gradient) */
 } leaf_status;
 
 /* flags */
@@ -91,6 +93,21 @@ typedef enum leaf_status {
                                   overlap-save backwards widen x in their loads (no fp32 copy: the workspace does not grow); the
                                   MFMA and the staged backward take one widening pass into the workspace, which
                                   leaf_backward_workspace_bytes accounts for when given the flag */
+#define LEAF_FLAG_X_PCM16 0x100 /* extension (additive: the ABI version stays 6): x is an int16_t [B][T] buffer behind the const
+                                  float*, 2-byte aligned (an odd address: LEAF_ERR_ALIGNMENT), and each sample means v / 32768 --
+                                  exact in fp32, so the results carry the bits of the float32 call on float(v) / 32768.  Everything
+                                  else stays float32: out, pooled_raw, grad_out, the parameters and their gradients.  Honoured by
+                                  leaf_forward_f32, _save_f32, _prepared_f32, _profiled_f32, leaf_backward_f32 and
+                                  leaf_backward_workspace_bytes.  Every fused forward path converts in its loads (sign-extending
+                                  16-bit load, int -> float, * 2^-15); LEAF_ALGO_STAGED, explicit or what AUTO resolves to, answers
+                                  LEAF_ERR_UNSUPPORTED (leaf_workspace_bytes takes no flags, so that path cannot get a widened copy).
+                                  Backward: the static overlap-save kernels and the 4096-sample plans read int16 directly; the
+                                  run-time-geometry 2048-sample kernels, the MFMA and the staged backward read one widened fp32 copy
+                                  in the workspace, reported by leaf_backward_workspace_bytes exactly where it is for bfloat16.
+                                  g_x must be NULL (an integer input has no gradient) and LEAF_FLAG_IO_BF16 must be clear (int16
+                                  in with bfloat16 out is not built): LEAF_ERR_UNSUPPORTED, answered before the workspace check
+                                  and before any launch.  LEAF_FLAG_PEAKNORM with it is valid on every entry point and path: no
+                                  |v / 32768| exceeds 1, so every clip's scale is 1 and the peak pre-pass is skipped. */
 
 /* algorithm selector for the fused path */
 #define LEAF_ALGO_AUTO   0     /* _FFT_SMALL for a handful of clips of a LEAF geometry; else the FFT kernels when their plan fits and K >= 224 or the geometry has a static instance, else MFMA, else staged */
@@ -268,6 +285,7 @@ int leaf_band_classes_f32(const float* kernel, const float* pool_w, const float*
  * run (a few MB for the overlap-save backward; the staged path materialises dL/dy, B*T*2F floats).
  * ABI 6: LEAF_FLAG_LOG1P (PCEN off) and LEAF_FLAG_IO_BF16 (x, grad_out, g_x bfloat16 behind the float pointers) as described
  * at the flags; x, grad_out and g_x must be 4-byte (bfloat16: 2-byte) aligned, else LEAF_ERR_ALIGNMENT.
+ * LEAF_FLAG_X_PCM16: x alone is int16 (2-byte aligned), grad_out stays float32, g_x must be NULL (LEAF_ERR_UNSUPPORTED).
  */
 size_t leaf_backward_workspace_bytes(int B, int T, int F, int K, int hop, int flags, int need_dx);
 int leaf_backward_f32(const float* x, int B, int T,
@@ -373,7 +391,7 @@ int leaf_pcen_backward_f32(const float* p, const float* grad_out, int B, int F, 
 size_t leaf_fft_tables_bytes(int F, int K, int hop);
 int leaf_fft_prepare_tables_f32(const float* kernel /*[F][2]*/, const float* pool_w /*[F]*/, int F, int K, int hop,
                                 void* tables, size_t tables_bytes, void* stream);
-/* x is float32, or bfloat16 with LEAF_FLAG_IO_BF16 (then out is bfloat16 too); workspace >= leaf_workspace_bytes(...,
+/* x is float32, bfloat16 with LEAF_FLAG_IO_BF16 (then out is bfloat16 too) or int16 with LEAF_FLAG_X_PCM16 (out stays float32); workspace >= leaf_workspace_bytes(...,
  * LEAF_ALGO_FFT). */
 int leaf_forward_prepared_f32(const float* x, int B, int T, const void* tables, size_t tables_bytes,
                               const float* pool_b, const float* alpha, const float* delta, const float* root,

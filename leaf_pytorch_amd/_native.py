@@ -30,6 +30,7 @@ def algo_reserve_cus(k: int) -> int:
 
 
 FLAG_PCEN, FLAG_LOG1P, FLAG_IO_BF16, FLAG_BWD_STAGED, FLAG_BWD_MFMA, FLAG_PEAKNORM, FLAG_BWD_FULL_TRANSFORMS = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
+FLAG_X_PCM16 = 0x100           # x is int16 PCM (a sample v means v / 32768); everything else stays float32
 FLAG_BWD_STRICT_BAND_CLASSES = 0x80   # leaf_backward_f32: the backward's band classes by round 5's rule alone (default: the forward's bias-aware decision)
 ALGO_STREAM_FINALIZE = 1 << 25   # LEAF_ALGO_STREAM_FINALIZE: per-frame sums in an LDS ring, finalized as the blocks complete
 ALGO_FULL_TRANSFORMS = 1 << 26   # LEAF_ALGO_FULL_TRANSFORMS: no band-limited filter tasks (every filter on 2048-point transforms)
@@ -215,6 +216,16 @@ def _dev_f32(t: torch.Tensor, name: str, device: torch.device) -> torch.Tensor:
     return t.detach().contiguous()
 
 
+def _dev_x(x2: torch.Tensor, device: torch.device):
+    """The waveform buffer of a call and its I/O flags: float32 (0), bfloat16 (FLAG_IO_BF16: the features come back in bfloat16
+    too) or int16 PCM (FLAG_X_PCM16: a sample v means v / 32768, the features are float32)."""
+    if x2.dtype == torch.bfloat16 or x2.dtype == torch.int16:
+        if x2.device != device:
+            raise RuntimeError(f"x is on {x2.device}, expected {device}")
+        return x2.detach().contiguous(), (FLAG_IO_BF16 if x2.dtype == torch.bfloat16 else FLAG_X_PCM16)
+    return _dev_f32(x2, "x", device), 0
+
+
 def require_hip(x: torch.Tensor, who: str) -> None:
     if x.device.type != "cuda":
         raise RuntimeError(
@@ -276,10 +287,22 @@ def batch_slices(B: int, T: int):
     return [(b0, min(B, b0 + per)) for b0 in range(0, B, per)]
 
 
+def _pcm16_lands_on_staged(lib, x2: torch.Tensor, F: int, K: int, hop: int, algo: int) -> bool:
+    """Whether one C-ABI forward call on the int16 batch ``x2`` runs the staged kernels (the explicit selector, or what AUTO resolves to)."""
+    B, T = x2.shape
+    if B == 0 or B * T >= (1 << 31):
+        return False
+    sel = algo & 0xff
+    if sel == ALGO_AUTO:
+        with torch.cuda.device(x2.device):
+            sel = lib.leaf_auto_algo(B, T, F, K, hop)
+    return sel == ALGO_STAGED
+
+
 def leaf_forward(x: torch.Tensor, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int,
                  pcen: bool = True, log1p: bool = False, algo: int = ALGO_AUTO,
                  out: Optional[torch.Tensor] = None, save_raw: bool = False, peak_normalize: bool = False):
-    """x (B,1,T) or (B,T) float32 on a HIP device -> (B,F,T').  Wraps leaf_forward_f32 (leaf_forward_save_f32 when
+    """x (B,1,T) or (B,T) float32 (bfloat16, or int16 PCM: a sample v means v / 32768) on a HIP device -> (B,F,T').  Wraps leaf_forward_f32 (leaf_forward_save_f32 when
     ``save_raw``: then returns (out, pooled_raw) for the backward)."""
     lib = load()
     require_hip(x, "leaf_forward")
@@ -292,14 +315,20 @@ def leaf_forward(x: torch.Tensor, kernel, pool_w, pool_b, alpha, delta, root, em
     else:
         raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
     dev = x.device
-    io_bf16 = x2.dtype == torch.bfloat16           # extension: bf16 waveform in, bf16 features out, fp32 arithmetic
-    x2 = x2.detach().contiguous() if io_bf16 else _dev_f32(x2, "x", dev)
+    # extensions: bf16 waveform in, bf16 features out; int16 PCM waveform in (v / 32768), float32 features out; fp32 arithmetic
+    x2, flags = _dev_x(x2, dev)
+    io_bf16 = flags == FLAG_IO_BF16
     B, T = x2.shape
     F = kernel.shape[0]
     kernel = _dev_f32(kernel, "kernel", dev)
     pool_w = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
     pool_b = _dev_f32(pool_b, "pool_b", dev)
-    flags = FLAG_IO_BF16 if io_bf16 else 0
+    if flags == FLAG_X_PCM16:
+        peak_normalize = False                     # |v / 32768| <= 1: nothing to normalise for int16, and nothing is launched
+        # the staged forward reads float32 only (LEAF_ERR_UNSUPPORTED from the C ABI): where the call lands on it, convert here
+        # -- the same values, v / 32768 exactly -- and run the float path (a batch beyond one C-ABI call: slice by slice, below)
+        if _pcm16_lands_on_staged(lib, x2, F, K, hop, algo):
+            x2, flags = x2.float().mul_(2.0 ** -15), 0
     if peak_normalize:
         flags |= FLAG_PEAKNORM                     # forward of the peak-normalised clips, the scale folded into the finalize
     if pcen:
@@ -315,13 +344,13 @@ def leaf_forward(x: torch.Tensor, kernel, pool_w, pool_b, alpha, delta, root, em
         raise RuntimeError(f"bad shape B={B} T={T} K={K} hop={hop}")
     if out is not None and (out.dtype != (torch.bfloat16 if io_bf16 else torch.float32) or not out.is_contiguous()
                             or tuple(out.shape) != (B, F, TP) or out.device != dev):
-        raise RuntimeError(f"out must be a contiguous {(B, F, TP)} tensor on {dev} matching the input dtype (float32 or bfloat16)")
+        raise RuntimeError(f"out must be a contiguous {(B, F, TP)} tensor on {dev} matching the input dtype (float32; bfloat16 for bfloat16 x)")
     if (algo & 0xff) not in (ALGO_AUTO, ALGO_STAGED, ALGO_MFMA, ALGO_FFT, ALGO_FFT_WG, ALGO_FFT_SMALL):
         raise RuntimeError(f"unknown algorithm selector {algo & 0xff}")
     if B == 0:
         # the empty batch: (0, F, T') like the reference (frontend.py:78-89 -> convolution.py:97); nothing is launched
         # (`out`, the selector and the flags are validated above, and a caller-supplied `out` is what comes back)
-        if save_raw and peak_normalize:
+        if save_raw and (flags & FLAG_PEAKNORM):
             raise RuntimeError("the folded PeakNormalization prologue is forward-only")
         empty = out if out is not None else torch.empty((0, F, TP), dtype=torch.bfloat16 if io_bf16 else torch.float32, device=dev)
         return (empty, torch.empty((0, F, TP), dtype=torch.float32, device=dev)) if save_raw else empty
@@ -361,13 +390,16 @@ def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, 
     ``staged`` / ``mfma`` force the staged kernels / the fused MFMA backward (default: the overlap-save backward where
     it applies, else MFMA, else staged).  ``log1p``: the backward of the log1p-compressed forward (PCEN off; ignored with
     PCEN on, as in the forward).  A bfloat16 ``x`` selects bfloat16 I/O: ``grad_out`` is bfloat16 too and dL/dx comes back
-    in bfloat16; the parameter gradients and ``pooled_raw`` are float32."""
+    in bfloat16; the parameter gradients and ``pooled_raw`` are float32.  An int16 ``x`` (PCM, v / 32768) keeps ``grad_out`` float32
+    and has no dL/dx (``need_dx=True`` raises)."""
     lib = load()
     require_hip(x, "leaf_backward")
     dev = x.device
     x2 = x[:, 0, :] if x.dim() == 3 else x
-    io_bf16 = x2.dtype == torch.bfloat16
-    x2 = x2.detach().contiguous() if io_bf16 else _dev_f32(x2, "x", dev)
+    x2, io_flags = _dev_x(x2, dev)
+    io_bf16 = io_flags == FLAG_IO_BF16
+    if io_flags == FLAG_X_PCM16 and need_dx:
+        raise RuntimeError("an int16 (PCM) input has no gradient: need_dx=True needs a float32 or bfloat16 x")
     B, T = x2.shape
     F = kernel.shape[0]
     kernel = _dev_f32(kernel, "kernel", dev)
@@ -410,7 +442,7 @@ def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, 
     flags = ((FLAG_PCEN if pcen else 0) | (FLAG_BWD_STAGED if staged else 0) | (FLAG_BWD_MFMA if mfma else 0) |
              (FLAG_BWD_FULL_TRANSFORMS if full_transforms else 0) |   # full_transforms: no band-limited filter tasks in the backward
              (FLAG_BWD_STRICT_BAND_CLASSES if strict_band_classes else 0) |
-             (FLAG_LOG1P if log1p and not pcen else 0) | (FLAG_IO_BF16 if io_bf16 else 0))
+             (FLAG_LOG1P if log1p and not pcen else 0) | io_flags)
     with torch.cuda.device(dev):
         # sized for the path these flags select (a few MB for the overlap-save backward, not the staged path's dL/dy)
         ws = workspace(lib.leaf_backward_workspace_bytes(B, T, F, K, hop, flags, int(need_dx)), dev)
@@ -426,19 +458,18 @@ def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, 
 def leaf_forward_profiled(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, pcen: bool = True,
                           algo: int = ALGO_AUTO, log1p: bool = False):
     """Measurement call: returns (out, [taps_ms, fused_ms, finalize_ms]) from HIP events on the current stream.  Same flags
-    as ``leaf_forward`` (PCEN on / off, log1p, bfloat16 I/O when ``x`` is bfloat16), so every BASELINE config can be timed."""
+    as ``leaf_forward`` (PCEN on / off, log1p, bfloat16 I/O when ``x`` is bfloat16, PCM input when it is int16), so every BASELINE config can be timed."""
     lib = load()
     require_hip(x, "leaf_forward_profiled")
     dev = x.device
     x2 = x[:, 0, :] if x.dim() == 3 else x
-    io_bf16 = x2.dtype == torch.bfloat16
-    x2 = x2.detach().contiguous() if io_bf16 else _dev_f32(x2, "x", dev)
+    x2, flags = _dev_x(x2, dev)
+    io_bf16 = flags == FLAG_IO_BF16
     B, T = x2.shape
     F = kernel.shape[0]
     kernel = _dev_f32(kernel, "kernel", dev)
     pool_w = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
     pool_b = _dev_f32(pool_b, "pool_b", dev)
-    flags = FLAG_IO_BF16 if io_bf16 else 0
     if pcen:
         flags |= FLAG_PCEN
         alpha, delta, root, ema_w = (_dev_f32(t, "pcen param", dev) for t in (alpha, delta, root, ema_w))
@@ -730,11 +761,10 @@ def leaf_forward_prepared(x: torch.Tensor, tables: torch.Tensor, pool_b, alpha, 
     else:
         raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
     dev = x.device
-    io_bf16 = x2.dtype == torch.bfloat16
-    x2 = x2.detach().contiguous() if io_bf16 else _dev_f32(x2, "x", dev)
+    x2, flags = _dev_x(x2, dev)
+    io_bf16 = flags == FLAG_IO_BF16
     B, T = x2.shape
     pool_b = _dev_f32(pool_b, "pool_b", dev)
-    flags = FLAG_IO_BF16 if io_bf16 else 0
     if pcen:
         flags |= FLAG_PCEN
         alpha, delta, root, ema_w = (_dev_f32(t, "pcen param", dev) for t in (alpha, delta, root, ema_w))

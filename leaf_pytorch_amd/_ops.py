@@ -70,15 +70,20 @@ def _frames(T: int, K: int, hop: int) -> int:
     return (T + pad_l + pad_r - K) // hop + 1
 
 
+def _out_dtype(x: torch.Tensor) -> torch.dtype:
+    """Feature dtype for a waveform: bfloat16 clips give bfloat16 features, int16 PCM (like float32) gives float32."""
+    return torch.bfloat16 if x.dtype == torch.bfloat16 else torch.float32
+
+
 def _register_python_side() -> None:
     @torch.library.register_fake("leaf_amd::forward")
     def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo):
-        return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)))
+        return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)), dtype=_out_dtype(x))
 
     @torch.library.register_fake("leaf_amd::forward_train")
     def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p=False):
         shape = (x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop))
-        return x.new_empty(shape), x.new_empty(shape, dtype=torch.float32)
+        return x.new_empty(shape, dtype=_out_dtype(x)), x.new_empty(shape, dtype=torch.float32)
 
     @torch.library.register_fake("leaf_amd::backward")
     def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out, pooled_raw, need_dx, flags):

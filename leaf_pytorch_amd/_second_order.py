@@ -80,6 +80,7 @@ def setup_context(ctx, inputs, output):
     ctx.need_dx = bool(need_dx)
     ctx.log1p = bool(flags & FLAG_LOG1P) and not ctx.pcen       # the log1p-compressed forward (PCEN off): log1p on top of the composite
     ctx.io_bf16 = x.dtype == torch.bfloat16
+    ctx.x_pcm16 = x.dtype == torch.int16
     ctx.save_for_backward(x, kernel, pool_w, pool_b, grad_out, *([alpha, delta, root, ema_w] if ctx.pcen else []))
 
 
@@ -89,6 +90,9 @@ def backward(ctx, grads):
     if getattr(ctx, "io_bf16", False):
         raise RuntimeError("gradients of gradients through Leaf are float32 only: second order with bfloat16 I/O is not supported "
                            "(feed float32 waveforms for create_graph=True)")
+    if getattr(ctx, "x_pcm16", False):
+        raise RuntimeError("gradients of gradients through Leaf are float32 only: second order with an int16 (PCM) waveform is not "
+                           "supported (feed x.float() / 32768 for create_graph=True)")
     saved = ctx.saved_tensors
     x, kernel, pool_w, pool_b, grad_out = saved[:5]
     with torch.enable_grad():

@@ -32,7 +32,7 @@ __global__ void pcen_bwd_rows_kernel(const float* __restrict__ raw, const void* 
     const int row = blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= BF) return;
     const float* r = raw + (size_t)row * TP;
-    const int gbf = mode & 4;
+    const int gbf = (mode & 4) ? kSampleBf16 : kSampleF32;
     const size_t go0 = (size_t)row * TP;
     float* gp = gpre + (size_t)row * TP;
     const int f = row % F;
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restr
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= BF) return;
     const float* r = raw + (size_t)row * TP;
-    const int gbf = mode & 4;                        // grad_out is bfloat16 (widened in the load)
+    const int gbf = (mode & 4) ? kSampleBf16 : kSampleF32;                        // grad_out is bfloat16 (widened in the load)
     const size_t go0 = (size_t)row * TP;
     float* gp = gpre + (size_t)row * TP;
     const int f = row % F;
@@ -603,11 +603,12 @@ __global__ void dx_kernel(const float* __restrict__ dy, const float* __restrict_
 }
 #endif
 
-// bfloat16 waveform -> fp32 copy in the workspace, for the backward families that read x as fp32 only (MFMA, staged)
+// 16-bit waveform (bfloat16 or PCM, `st`: kSampleBf16 / kSamplePcm16) -> fp32 copy in the workspace, for the backward families that
+// read x as fp32 only (run-time-geometry 2048-sample kernels, MFMA, staged)
 #ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
-__global__ void bf16_widen_kernel(const unsigned short* __restrict__ src, size_t n, float* __restrict__ dst) {
+__global__ void x16_widen_kernel(const unsigned short* __restrict__ src, int st, size_t n, float* __restrict__ dst) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = bf16_widen(src[i]);
+    if (i < n) dst[i] = st == kSamplePcm16 ? pcm16_widen((short)src[i]) : bf16_widen(src[i]);
 }
 #endif
 

@@ -23,9 +23,16 @@ __device__ __forceinline__ unsigned short bf16_round(float v) {
     const unsigned u = __float_as_uint(v);
     return v != v ? (unsigned short)0x7fc0u : (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
-// element i of an I/O buffer that holds fp32 or (bf16 != 0) bfloat16
-__device__ __forceinline__ float io_load(const void* p, size_t i, int bf16) {
-    return bf16 ? bf16_widen(static_cast<const unsigned short*>(p)[i]) : static_cast<const float*>(p)[i];
+// Sample type of a waveform buffer, carried in the parameter structs' `io_bf16` field (the name predates 16-bit PCM): 0 fp32,
+// 1 bfloat16 (LEAF_FLAG_IO_BF16), 2 16-bit PCM (LEAF_FLAG_X_PCM16).  A PCM sample v means v / 32768: the int -> float conversion and
+// the scaling by a power of two are both exact, so the result is bit for bit what a caller's float(v) / 32768 holds.
+constexpr int kSampleF32 = 0, kSampleBf16 = 1, kSamplePcm16 = 2;
+__device__ __forceinline__ float pcm16_widen(short v) { return (float)(int)v * 0x1p-15f; }
+// element i of an I/O buffer of sample type `st` (one of the three codes above, nothing else: a mode bit is mapped by the caller)
+__device__ __forceinline__ float io_load(const void* p, size_t i, int st) {
+    if (st == kSampleBf16) return bf16_widen(static_cast<const unsigned short*>(p)[i]);
+    if (st == kSamplePcm16) return pcm16_widen(static_cast<const short*>(p)[i]);
+    return static_cast<const float*>(p)[i];
 }
 __device__ __forceinline__ void io_store(void* p, size_t i, int bf16, float v) {
     if (bf16) static_cast<unsigned short*>(p)[i] = bf16_round(v);

@@ -250,12 +250,15 @@ __device__ __forceinline__ void block_rows8(const void* x, size_t clip, int io_b
     auto pin8 = [&]() {
         asm volatile("" : "+v"(xa[0]), "+v"(xa[1]), "+v"(xa[2]), "+v"(xa[3]), "+v"(xa[4]), "+v"(xa[5]), "+v"(xa[6]), "+v"(xa[7]));
     };
-    // the four variants (sample type x interior / edge) are whole loops under wave-uniform branches: eight loads in flight
+    // the four variants (sample width x interior / edge) are whole loops under wave-uniform branches: eight loads in flight; the
+    // two 16-bit types (io_bf16: kSampleBf16 / kSamplePcm16) share theirs, the conversion chosen by a wave-uniform select
+    const bool pcm = io_bf16 == kSamplePcm16;
+    auto widen16 = [&](unsigned short v) { return pcm ? pcm16_widen((short)v) : __uint_as_float((unsigned)v << 16); };
     if (interior) {
         const int n0 = nb + lane + ofs;
         if (io_bf16) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) xa[j] = __uint_as_float((unsigned)xh[n0 + 64 * row(j)] << 16);
+            for (int j = 0; j < 8; ++j) xa[j] = widen16(xh[n0 + 64 * row(j)]);
         } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j) xa[j] = xb[n0 + 64 * row(j)];
@@ -267,7 +270,7 @@ __device__ __forceinline__ void block_rows8(const void* x, size_t clip, int io_b
         for (int j = 0; j < 8; ++j) nc[j] = min(max(nb + 64 * row(j) + lane + ofs, 0), T - 1);
         if (io_bf16) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) xa[j] = __uint_as_float((unsigned)xh[nc[j]] << 16);
+            for (int j = 0; j < 8; ++j) xa[j] = widen16(xh[nc[j]]);
         } else {
 #pragma unroll
             for (int j = 0; j < 8; ++j) xa[j] = xb[nc[j]];
@@ -567,8 +570,8 @@ struct BandParams {
 };
 
 struct FftParams {
-    const void* x;         // [B][T] fp32, or bf16 when io_bf16
-    int io_bf16;
+    const void* x;         // [B][T] fp32, bf16 or 16-bit PCM by io_bf16
+    int io_bf16;           // sample type of x: kSampleF32 / kSampleBf16 / kSamplePcm16 (leaf_common.hpp)
     const float2* H;       // [F][2048] complex spectra, or (real-spectrum kernels, odd K) [F][2048] floats
     const float* Gz;       // [F][GZ]
     float* part;           // [B][F][nslot][TP]: slot s = s-th block the frame's window meets (2, or 3 when K - 1 > L)
@@ -712,13 +715,17 @@ __global__ __launch_bounds__(kFftWaves * 64, 2) void leaf_fft_kernel(const FftPa
             const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
             // bf16 input: every lane always loads (index clamped into the clip, value zeroed outside it), so that the 32
             // 2-byte loads are in flight together instead of one exec-masked load at a time (-9 % on 10 s clips)
+            // 16-bit PCM shares the loop (this kernel sits at the register limit: a third loop put the fp32 path into scratch): the
+            // conversion is chosen per sample by a wave-uniform select between the shift and sign-extend / convert / scale
             if (p.io_bf16) {
+                const bool pcm = p.io_bf16 == kSamplePcm16;
 #pragma unroll
                 for (int r = 0; r < 32; ++r) {
                     const int i = 64 * r + lane;                         // RS: block rotated left by padL samples
                     const int n = n_c - p.padL + (RS ? ((i + p.rot) & (kFftN - 1)) : i);
                     const unsigned v = xh[min(max(n, 0), p.T - 1)];
-                    are[r] = (n >= 0 && n < p.T) ? __uint_as_float(v << 16) : 0.0f;
+                    const float w = pcm ? pcm16_widen((short)v) : __uint_as_float(v << 16);
+                    are[r] = (n >= 0 && n < p.T) ? w : 0.0f;
                     aim[r] = 0.0f;
                 }
             } else {

@@ -42,8 +42,8 @@ constexpr int kSmallRing = 10;                   // most block spectra resident 
 constexpr int kSmallMaxBlocks = 2 * kSmallRing;  // clips up to two passes long take this kernel
 
 struct SmallParams {
-    const void* x;          // [B][T] fp32, or bf16 when io_bf16
-    int io_bf16;
+    const void* x;          // [B][T] fp32, bf16 or 16-bit PCM by io_bf16
+    int io_bf16;            // sample type of x: kSampleF32 / kSampleBf16 / kSamplePcm16 (leaf_common.hpp)
     const float* kernel;    // [F][2] (mu, sigma), unclamped
     const float* pool_w;    // [F]
     GaborBounds bd;
@@ -157,12 +157,14 @@ __global__ __launch_bounds__((SPLIT ? kSmallSplitWaves : kSmallWaves) * 64, SPLI
     auto load_block = [&](int c, int lane_) {                             // block c, rotated left by padL samples
         const int n_c = c * LS;
         if (p.io_bf16) {
+            const bool pcm = p.io_bf16 == kSamplePcm16;     // 16-bit PCM shares the loop: a wave-uniform select of the conversion
 #pragma unroll
             for (int r = 0; r < 32; ++r) {
                 const int i = 64 * r + lane_;
                 const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
                 const unsigned v = xh[min(max(n, 0), p.T - 1)];
-                zre[r] = (n >= 0 && n < p.T) ? __uint_as_float(v << 16) : 0.0f;
+                const float w = pcm ? pcm16_widen((short)v) : __uint_as_float(v << 16);
+                zre[r] = (n >= 0 && n < p.T) ? w : 0.0f;
                 zim[r] = 0.0f;
             }
         } else {

@@ -1103,12 +1103,14 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
                 const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
                 const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
                 if (p.io_bf16) {
+                    const bool pcm = p.io_bf16 == kSamplePcm16;     // 16-bit PCM shares the loop: a wave-uniform select of the conversion
 #pragma unroll
                     for (int r = 0; r < 32; ++r) {
                         const int i = 64 * r + lane;                      // block rotated left by padL samples
                         const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
                         const unsigned v = xh[min(max(n, 0), p.T - 1)];
-                        are[r] = (n >= 0 && n < p.T) ? __uint_as_float(v << 16) : 0.0f;
+                        const float w = pcm ? pcm16_widen((short)v) : __uint_as_float(v << 16);
+                        are[r] = (n >= 0 && n < p.T) ? w : 0.0f;
                         aim[r] = 0.0f;
                     }
                 } else {

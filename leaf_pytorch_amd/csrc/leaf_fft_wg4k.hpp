@@ -446,11 +446,13 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
                 const int n_c = c * LS;
                 const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
                 const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
+                const bool pcm = p.io_bf16 == kSamplePcm16;                // 16-bit PCM: the bf16 load, another conversion (wave-uniform select)
                 auto sample = [&](int i) -> float {                       // rotated block a'[i] = xz[n_c - padL + ((i + padL) mod 4096)]
                     const int n = n_c - PADL + ((i + PADL) & (kFft4N - 1));
                     if (p.io_bf16) {
                         const unsigned v = xh[min(max(n, 0), p.T - 1)];
-                        return (n >= 0 && n < p.T) ? __uint_as_float(v << 16) : 0.0f;
+                        const float w = pcm ? pcm16_widen((short)v) : __uint_as_float(v << 16);
+                        return (n >= 0 && n < p.T) ? w : 0.0f;
                     }
                     return (n >= 0 && n < p.T) ? xb[n] : 0.0f;
                 };

@@ -578,13 +578,15 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
                 float are[32], aim[32];
                 const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
                 const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
-                if (p.io_bf16) {                                          // bf16 waveform, widened in the load (as the forward, leaf_fft_wg.hpp)
+                if (p.io_bf16) {                                          // 16-bit waveform, widened in the load (as the forward, leaf_fft_wg.hpp)
+                    const bool pcm = p.io_bf16 == kSamplePcm16;     // 16-bit PCM shares the loop: a wave-uniform select of the conversion
 #pragma unroll
                     for (int r = 0; r < 32; ++r) {
                         const int i = 64 * r + lane;
                         const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
                         const unsigned v = xh[min(max(n, 0), p.T - 1)];
-                        are[r] = (n >= 0 && n < p.T) ? __uint_as_float(v << 16) : 0.0f;
+                        const float w = pcm ? pcm16_widen((short)v) : __uint_as_float(v << 16);
+                        are[r] = (n >= 0 && n < p.T) ? w : 0.0f;
                         aim[r] = 0.0f;
                     }
                 } else {
@@ -704,7 +706,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
 // striding; per block: forward transform -> A' into wave-private LDS; for every filter wg_bwd_filter<.., DX = 1> (which
 // adds R_f g into the 64 accumulator registers); then dL/da' = Re(FFT(conj G)), un-rotated into dxblk.
 // BF16: the instance for a bfloat16 waveform (LEAF_FLAG_IO_BF16), widened in the load; the fp32 instance carries no trace of it (this
-// kernel sits at the register limit)
+// kernel sits at the register limit).  There is no 16-bit PCM instance: an integer waveform has no gradient, so dL/dx is refused.
 template <int SK, int SHOP, bool BF16 = false>
 __global__ __launch_bounds__(kBlkBwdWaves * 64, 2) void leaf_fft_blk_bwd_dx_kernel(const FftParams p) {
     constexpr int SCRF = kWgScrHalfFloats;

@@ -98,8 +98,8 @@ __global__ __launch_bounds__(256) void fused_prep_kernel(const float* __restrict
 #endif
 
 struct FusedParams {
-    const void* x;         // [B][T] fp32, or bf16 when io_bf16
-    int io_bf16;
+    const void* x;         // [B][T] fp32, bf16 or 16-bit PCM by io_bf16
+    int io_bf16;           // sample type of x: kSampleF32 / kSampleBf16 / kSamplePcm16 (leaf_common.hpp)
     const float* W;        // [R][2*FP] half-support tap table (columns in perm order)
     const float* G;        // [FP][GJ] pooling windows (columns in perm order), zero for j >= K
     const int* tile_ks;    // [FP/16]
@@ -300,6 +300,7 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kWavesPerWG / 4) void leaf_fused_
         } else if (!(kAblate & 2)) {
             const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
             const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
+            const bool pcm = p.io_bf16 == kSamplePcm16;  // 16-bit PCM: the bf16 load, another conversion (wave-uniform select)
             const int n0 = n_blk - p.HP + p.xshift;
             for (int i0 = lane; i0 < p.XS; i0 += 4 * 64) {
                 float v[4];
@@ -308,7 +309,7 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kWavesPerWG / 4) void leaf_fused_
                     const int i = i0 + 64 * j, n = n0 + i;
                     const bool ok = i < p.XS && n >= 0 && n < p.T;
                     if (p.io_bf16)
-                        v[j] = ok ? __uint_as_float((unsigned)xh[n] << 16) : 0.0f;
+                        v[j] = ok ? (pcm ? pcm16_widen((short)xh[n]) : __uint_as_float((unsigned)xh[n] << 16)) : 0.0f;
                     else
                         v[j] = ok ? xb[n] : 0.0f;
                 }

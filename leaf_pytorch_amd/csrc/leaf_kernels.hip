@@ -581,6 +581,10 @@ int auto_algo(int B, int T, int F, int K, int hop, bool allow_small = true) {
 }
 
 inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
+// sample type of the waveform buffer (leaf_common.hpp kSample*), the value the kernels' `io_bf16` field carries
+inline int x_sample_type(int flags) {
+    return (flags & LEAF_FLAG_IO_BF16) ? kSampleBf16 : (flags & LEAF_FLAG_X_PCM16) ? kSamplePcm16 : kSampleF32;
+}
 
 // Every inst_*.hip was compiled with the parameter-struct layouts this unit has (the handles are opaque, a per-unit
 // macro divergence would otherwise be a silent parameter mismatch at launch).  Checked once; a mismatch fails every entry
@@ -658,8 +662,8 @@ const char* leaf_status_string(int status) {
         case LEAF_ERR_BAD_ALGO: return "unknown or inapplicable algorithm selector";
         case LEAF_ERR_LAUNCH: return "HIP kernel launch failed";
         case LEAF_ERR_NO_DEVICE: return "no usable gfx950 device";
-        case LEAF_ERR_ALIGNMENT: return "buffer not 4-byte aligned";
-        case LEAF_ERR_UNSUPPORTED: return "combination not supported (bfloat16 I/O has no staged forward: use float32 buffers; LEAF_FLAG_PEAKNORM needs an overlap-save path and has no backward)";
+        case LEAF_ERR_ALIGNMENT: return "buffer not 4-byte aligned (2-byte for bfloat16 and 16-bit PCM buffers)";
+        case LEAF_ERR_UNSUPPORTED: return "combination not supported (bfloat16 I/O and 16-bit PCM input (LEAF_FLAG_X_PCM16) have no staged forward: use float32 buffers; LEAF_FLAG_X_PCM16 excludes LEAF_FLAG_IO_BF16 and has no dL/dx (g_x must be NULL); LEAF_FLAG_PEAKNORM needs an overlap-save path and has no backward)";
     }
     return "unknown status";
 }
@@ -939,7 +943,7 @@ int leaf_pcen_backward_f32(const float* p, const float* grad_out, int B, int F, 
 
 // The overlap-save forward: (tables) -> main kernel -> finalize.  With tables_ready the tables were produced earlier by
 // leaf_fft_prepare_tables_f32 from the same parameters (inference with frozen parameters) and the prep launch is skipped.
-static int fft_forward(const FftPlan& fp, const void* x, bool io_bf16, int B, int T, const float* kernel, const float* pool_w,
+static int fft_forward(const FftPlan& fp, const void* x, int xtype, int B, int T, const float* kernel, const float* pool_w,
                        const float* pool_b, const float* alpha, const float* delta, const float* root, const float* ema_w,
                        int F, int K, int hop, int mode, void* out, float* tables, float* part, bool tables_ready,
                        hipStream_t st, hipEvent_t* ev, float* pooled_raw, bool use_wg, const float* clip_scale2 = nullptr,
@@ -983,8 +987,10 @@ static int fft_forward(const FftPlan& fp, const void* x, bool io_bf16, int B, in
             static const bool spec0_off = [] { const char* e = tools_env("LEAF_SPEC0"); return e && atoi(e) == 0; }();   // tools only: A/B
             const int main_grid = std::max(1, std::min(B * fp.nblk, num_cus()));
             size_t prep_dyn = 0;
-            if (LEAF_WG_SPEC0 && !spec0_off && !tables_ready && main_grid <= kMaxCusForSpec0 && wl.nw <= 12) {
-                ba.x = x; ba.io_bf16 = io_bf16 ? 1 : 0; ba.B = B; ba.nblk = fp.nblk; ba.G = main_grid;
+            // (16-bit PCM: the table launch reads fp32 and bf16 only -- a third sample type in its first-block loads cost the fp32 path
+            // 0.9 us of the table launch at cfg1 -- so the main kernel transforms its first blocks itself: the same bits)
+            if (LEAF_WG_SPEC0 && !spec0_off && !tables_ready && main_grid <= kMaxCusForSpec0 && wl.nw <= 12 && xtype != kSamplePcm16) {
+                ba.x = x; ba.io_bf16 = xtype; ba.B = B; ba.nblk = fp.nblk; ba.G = main_grid;
                 ba.spec0 = reinterpret_cast<float2*>(dyn + bl.spec0);
                 spec0 = ba.spec0;
                 prep_dyn = (size_t)(kPrepWaves - 1) * kWgScrFloats * 4;
@@ -1004,7 +1010,7 @@ static int fft_forward(const FftPlan& fp, const void* x, bool io_bf16, int B, in
     }
     if (ev) (void)hipEventRecord(ev[1], st);
     FftParams q{};
-    q.x = x; q.io_bf16 = io_bf16 ? 1 : 0; q.H = H; q.Gz = Gz; q.part = part;
+    q.x = x; q.io_bf16 = xtype; q.H = H; q.Gz = Gz; q.part = part;
     q.B = B; q.T = T; q.TP = fp.TP; q.F = F; q.K = K; q.hop = hop; q.padL = fp.padL;
     q.L = fp.L; q.nblk = fp.nblk; q.GZ = fp.GZ; q.nslot = fp.nslot; q.g_bufs = fp.g_bufs; q.NT = fp.NT; q.fq = fp.fq; q.nfq = fp.nfq;
     q.scr_floats = fp.scr_floats;
@@ -1109,7 +1115,8 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
         if (sel != LEAF_ALGO_AUTO && sel != LEAF_ALGO_STAGED && sel != LEAF_ALGO_MFMA && sel != LEAF_ALGO_FFT && sel != LEAF_ALGO_FFT_WG &&
             sel != LEAF_ALGO_FFT_SMALL)
             return LEAF_ERR_BAD_ALGO;
-        if ((flags & LEAF_FLAG_IO_BF16) && sel == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
+        if ((flags & LEAF_FLAG_X_PCM16) && (flags & LEAF_FLAG_IO_BF16)) return LEAF_ERR_UNSUPPORTED;   // int16 in with bfloat16 out: not built
+        if ((flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16)) && sel == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
         if (B == 0 && !inst_layouts_ok()) return LEAF_ERR_LAUNCH;
     }
     if (empty_batch(B, T, F, K, hop)) return LEAF_OK;
@@ -1120,7 +1127,8 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
     if (rc != LEAF_OK) return rc;
     {
         const uintptr_t io_mask = (flags & LEAF_FLAG_IO_BF16) ? 1u : 3u;
-        if ((reinterpret_cast<uintptr_t>(x) & io_mask) || (reinterpret_cast<uintptr_t>(out) & io_mask) || misaligned(workspace))
+        const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;       // 16-bit PCM: x alone is a 2-byte buffer
+        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & io_mask) || misaligned(workspace))
             return LEAF_ERR_ALIGNMENT;
     }
     const int tuning_desync = ((algo >> 8) & 0xff) - 1;      // LEAF_ALGO_TUNE_DESYNC(n); -1 = automatic
@@ -1131,10 +1139,13 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
         return LEAF_ERR_BAD_ALGO;
     const FusedPlan pl = make_plan(B, T, F, K, hop);
     const bool io_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;
-    if (io_bf16 && algo == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;             // bf16 I/O is a fused-path feature
+    const int xtype = x_sample_type(flags);                                           // what the kernels read x as; out follows io_bf16 alone
+    if (xtype != kSampleF32 && algo == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED; // 16-bit input is a fused-path feature
     if (algo == LEAF_ALGO_MFMA && !pl.ok) return LEAF_ERR_BAD_ALGO;
     if (algo == LEAF_ALGO_AUTO) algo = auto_algo(B, T, F, K, hop);
-    if (io_bf16 && algo == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
+    if (xtype != kSampleF32 && algo == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
+    // a PCM sample means v / 32768, so no clip's peak exceeds 1: peak normalisation is the identity (no pre-pass, every scale 1)
+    if (xtype == kSamplePcm16) flags &= ~LEAF_FLAG_PEAKNORM;
     const size_t need = leaf_workspace_bytes(B, T, F, K, hop, algo);
     if (!workspace || workspace_bytes < need) return LEAF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -1147,7 +1158,7 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
     if (flags & LEAF_FLAG_PEAKNORM) {
         if (algo != LEAF_ALGO_FFT && algo != LEAF_ALGO_FFT_WG && algo != LEAF_ALGO_FFT_SMALL) return LEAF_ERR_UNSUPPORTED;
         clip_scale2 = ws + need / 4 - align_up((size_t)B, 64);
-        hipLaunchKernelGGL(peak_scale2_kernel, dim3(B), dim3(1024), 0, st, x, io_bf16 ? 1 : 0, T, clip_scale2);
+        hipLaunchKernelGGL(peak_scale2_kernel, dim3(B), dim3(1024), 0, st, x, xtype, T, clip_scale2);
         LEAF_LAUNCH_CHECK();
     }
 
@@ -1159,7 +1170,7 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
         const SmallKernel kfn = reinterpret_cast<SmallKernel>(const_cast<void*>(leaf_inst_fft_small(K, sp.split)));
         if (!kfn) return LEAF_ERR_BAD_ALGO;
         SmallParams q{};
-        q.x = x; q.io_bf16 = io_bf16 ? 1 : 0; q.kernel = kernel; q.pool_w = pool_w; q.bd = gabor_bounds(K);
+        q.x = x; q.io_bf16 = xtype; q.kernel = kernel; q.pool_w = pool_w; q.bd = gabor_bounds(K);
         q.B = B; q.T = T; q.TP = sp.TP; q.F = F; q.nblk = sp.nblk; q.ring = sp.split ? kSmallSplitRing : sp.ring;
         q.fin = FinParams{nullptr, F, sp.TP, SlotGeom{fft_block_len(K, hop, true), K / 2 + K % 2 - 1, K, hop, T, 2}, pool_b, alpha, delta,
                           root, ema_w, 1e-12f, mode, out, pooled_raw, clip_scale2};
@@ -1213,7 +1224,7 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
             LEAF_LAUNCH_CHECK();
             if (ev) (void)hipEventRecord(ev[1], st);
             FftParams q{};
-            q.x = x; q.io_bf16 = io_bf16 ? 1 : 0; q.H = reinterpret_cast<const float2*>(tab); q.Gz = Grow; q.part = part;
+            q.x = x; q.io_bf16 = xtype; q.H = reinterpret_cast<const float2*>(tab); q.Gz = Grow; q.part = part;
             q.B = B; q.T = T; q.TP = f4.TP; q.F = F; q.K = K; q.hop = hop; q.padL = f4.padL; q.L = f4.L; q.nblk = f4.nblk;
             q.nslot = f4.nslot; q.GZ = f4.RG; q.NT = f4.generic ? fft_wgg4k_frame_floats(K, hop) : 0;
             q.lone = reinterpret_cast<const float*>(Wt);                  // (static 32 kHz kernel: the shared twiddle table travels in `lone`)
@@ -1249,7 +1260,7 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
         if (!fp.ok) return LEAF_ERR_BAD_ALGO;
         float* tables = ws;                                        // [spectra | pooling rows | col_of], then the partials
         float* part = ws + fft_table_floats(fp, F);
-        return fft_forward(fp, x, io_bf16, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, mode, out,
+        return fft_forward(fp, x, xtype, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, mode, out,
                            tables, part, /*tables_ready=*/false, st, ev, pooled_raw, algo == LEAF_ALGO_FFT_WG, clip_scale2);
     }
 
@@ -1268,7 +1279,7 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
         LEAF_LAUNCH_CHECK();
         if (ev) (void)hipEventRecord(ev[1], st);
         FusedParams prm = base_fused_params(pl, B, T, F, K, hop, tuning_desync);
-        prm.x = x; prm.io_bf16 = io_bf16 ? 1 : 0; prm.W = W; prm.G = G; prm.tile_ks = tile_ks; prm.part = part;
+        prm.x = x; prm.io_bf16 = xtype; prm.W = W; prm.G = G; prm.tile_ks = tile_ks; prm.part = part;
 #if LEAF_TRACE
         prm.trace = reinterpret_cast<unsigned long long*>(part + align_up(pl.part_floats, 64));
 #endif
@@ -1323,7 +1334,8 @@ int leaf_forward_save_f32(const float* x, int B, int T, const float* kernel, con
                           void* stream) {
     if (!pooled_raw) return LEAF_ERR_NULL_POINTER;
     // forward-only: pooled_raw would be that of the normalised clips while leaf_backward_f32 differentiates against x
-    if (flags & LEAF_FLAG_PEAKNORM) return LEAF_ERR_UNSUPPORTED;
+    // (16-bit PCM: normalisation is the identity, so the flag is accepted and changes nothing)
+    if ((flags & LEAF_FLAG_PEAKNORM) && !(flags & LEAF_FLAG_X_PCM16)) return LEAF_ERR_UNSUPPORTED;
     return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out, workspace,
                         workspace_bytes, stream, nullptr, pooled_raw);
 }
@@ -1441,7 +1453,9 @@ int leaf_band_classes_f32(const float* kernel, const float* pool_w, const float*
 int leaf_forward_prepared_f32(const float* x, int B, int T, const void* tables, size_t tables_bytes, const float* pool_b,
                               const float* alpha, const float* delta, const float* root, const float* ema_w, int F, int K,
                               int hop, int flags, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (flags & LEAF_FLAG_PEAKNORM) return LEAF_ERR_UNSUPPORTED;         // no scale pre-pass on the prepared-tables path
+    if ((flags & LEAF_FLAG_X_PCM16) && (flags & LEAF_FLAG_IO_BF16)) return LEAF_ERR_UNSUPPORTED;
+    // no scale pre-pass on the prepared-tables path (16-bit PCM needs none: every clip's scale is 1)
+    if ((flags & LEAF_FLAG_PEAKNORM) && !(flags & LEAF_FLAG_X_PCM16)) return LEAF_ERR_UNSUPPORTED;
     if (empty_batch(B, T, F, K, hop)) return LEAF_OK;
     if (!x || !tables || !pool_b || !out) return LEAF_ERR_NULL_POINTER;
     const bool use_pcen = (flags & LEAF_FLAG_PCEN) != 0;
@@ -1453,7 +1467,8 @@ int leaf_forward_prepared_f32(const float* x, int B, int T, const void* tables, 
     if (tables_bytes < leaf_fft_tables_bytes(F, K, hop)) return LEAF_ERR_WORKSPACE;
     const bool io_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;
     const uintptr_t io_mask = io_bf16 ? 1u : 3u;
-    if ((reinterpret_cast<uintptr_t>(x) & io_mask) || (reinterpret_cast<uintptr_t>(out) & io_mask) || misaligned(workspace) ||
+    const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;
+    if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & io_mask) || misaligned(workspace) ||
         misaligned(tables))
         return LEAF_ERR_ALIGNMENT;
     if (!workspace || workspace_bytes < (align_up(fp.part_floats, 64) + (LEAF_TRACE ? 16 * 64 * 2 : 0)) * 4) return LEAF_ERR_WORKSPACE;
@@ -1462,7 +1477,7 @@ int leaf_forward_prepared_f32(const float* x, int B, int T, const void* tables, 
     // workspace has the room (it has when sized by leaf_workspace_bytes as documented); otherwise full transforms
     const size_t part_end = align_up(fp.part_floats, 64) + (LEAF_TRACE ? 16 * 64 * 2 : 0);
     float* band_scratch = fp.band_dyn && workspace_bytes >= (part_end + fp.band_dyn) * 4 ? static_cast<float*>(workspace) + part_end : nullptr;
-    return fft_forward(fp, x, io_bf16, B, T, nullptr, nullptr, pool_b, alpha, delta, root, ema_w, F, K, hop, mode, out,
+    return fft_forward(fp, x, x_sample_type(flags), B, T, nullptr, nullptr, pool_b, alpha, delta, root, ema_w, F, K, hop, mode, out,
                        static_cast<float*>(const_cast<void*>(tables)), static_cast<float*>(workspace), /*tables_ready=*/true,
                        (hipStream_t)stream, nullptr, nullptr,
                        auto_algo(B, T, F, K, hop, /*allow_small=*/false) == LEAF_ALGO_FFT_WG,   // the workgroup kernel from the batch AUTO takes it at
@@ -1719,11 +1734,11 @@ static size_t bwd_own_workspace_floats(BwdPath path, int B, int T, int F, int K,
            align_up((size_t)B * 2 * F * K, 64);
 }
 
-// LEAF_FLAG_IO_BF16: the static-geometry overlap-save backwards (K = 401 / 160, 801 / 320, 201 / 80) and the 4096-sample plans read
-// the bf16 waveform directly (nothing added); the run-time-geometry kernels of the 2048-sample plan, the MFMA and the staged backward
+// LEAF_FLAG_IO_BF16 / LEAF_FLAG_X_PCM16 (a 16-bit waveform): the static-geometry overlap-save backwards (K = 401 / 160, 801 / 320, 201 / 80) and the 4096-sample plans read
+// the 16-bit waveform directly (nothing added); the run-time-geometry kernels of the 2048-sample plan, the MFMA and the staged backward
 // read fp32 only and get a widened copy of x behind their own layout
 static size_t bwd_x32_floats(BwdPath path, int B, int T, int K, int hop, int flags) {
-    if (!(flags & LEAF_FLAG_IO_BF16) || path == BWD_PATH_FFT4K) return 0;
+    if (!(flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16)) || path == BWD_PATH_FFT4K) return 0;
     if (path == BWD_PATH_FFT && fft_static_geometry(K, hop) && (K & 1) && !LEAF_FFT_FORCE_GENERIC) return 0;
     return align_up((size_t)B * T, 64);
 }
@@ -1740,6 +1755,8 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
                       float* g_pool_b, float* g_alpha, float* g_delta, float* g_root, float* g_ema_w, float* g_x,
                       void* workspace, size_t workspace_bytes, void* stream) {
     // LEAF_FLAG_IO_BF16: x, grad_out and g_x are bfloat16 buffers behind the float pointers (as in the forward); everything else fp32
+    // LEAF_FLAG_X_PCM16: x alone is a 16-bit PCM buffer (v / 32768); an integer input has no gradient, so g_x must be NULL
+    if ((flags & LEAF_FLAG_X_PCM16) && ((flags & LEAF_FLAG_IO_BF16) || g_x)) return LEAF_ERR_UNSUPPORTED;
     if (empty_batch(B, T, F, K, hop)) {
         // the sum over zero clips: every parameter gradient is exactly zero (what autograd returns for the reference)
         if (!g_kernel || !g_pool_w || !g_pool_b) return LEAF_ERR_NULL_POINTER;
@@ -1763,7 +1780,8 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
     const bool io_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;
     {
         const uintptr_t io_mask = io_bf16 ? 1u : 3u;
-        if ((reinterpret_cast<uintptr_t>(x) & io_mask) || (reinterpret_cast<uintptr_t>(grad_out) & io_mask) ||
+        const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;
+        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(grad_out) & io_mask) ||
             (reinterpret_cast<uintptr_t>(g_x) & io_mask) || misaligned(workspace))
             return LEAF_ERR_ALIGNMENT;
     }
@@ -1777,15 +1795,15 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
     // param_reduce_kernel reads bit0 alone
     const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (io_bf16 ? 4 : 0);
     float* ws = static_cast<float*>(workspace);
-    bool x_bf16 = io_bf16;                                   // what the kernels below read x as
+    int xtype = x_sample_type(flags);                        // what the kernels below read x as
     if (float* x32 = bwd_x32_floats(path, B, T, K, hop, flags) ? ws + bwd_own_workspace_floats(path, B, T, F, K, hop, g_x != nullptr) : nullptr) {
         // these families read fp32: one widening pass into the workspace's tail, then the fp32 path
         const size_t n = (size_t)B * T;
-        hipLaunchKernelGGL(bf16_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                           reinterpret_cast<const unsigned short*>(x), n, x32);
+        hipLaunchKernelGGL(x16_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                           reinterpret_cast<const unsigned short*>(x), xtype, n, x32);
         LEAF_LAUNCH_CHECK();
         x = x32;
-        x_bf16 = false;
+        xtype = kSampleF32;
     }
     if (path == BWD_PATH_FFT4K) {
         // ---- overlap-save backward on 4096-sample blocks: long odd windows, parameter gradients
@@ -1820,7 +1838,7 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
         hipLaunchKernelGGL(iota_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, col_of, F);
         LEAF_LAUNCH_CHECK();
         FftParams q{};
-        q.x = x; q.io_bf16 = x_bf16 ? 1 : 0; q.H = reinterpret_cast<const float2*>(tab3); q.Gz = Grow; q.part = part;
+        q.x = x; q.io_bf16 = xtype; q.H = reinterpret_cast<const float2*>(tab3); q.Gz = Grow; q.part = part;
         q.B = B; q.T = T; q.TP = bp.TP; q.F = F; q.K = K; q.hop = hop; q.padL = bp.padL; q.L = bp.L; q.nblk = bp.nblk;
         q.nslot = 2; q.GZ = bp.RG;
         q.lone = reinterpret_cast<const float*>(Wt);                      // (read by the static forward kernel when it recomputes below)
@@ -1921,7 +1939,7 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
             }
             LEAF_LAUNCH_CHECK();
             FftParams q{};
-            q.x = x; q.io_bf16 = x_bf16 ? 1 : 0; q.H = reinterpret_cast<const float2*>(R3); q.Gz = Gz; q.part = part;
+            q.x = x; q.io_bf16 = xtype; q.H = reinterpret_cast<const float2*>(R3); q.Gz = Gz; q.part = part;
             q.lone = (K & 1) ? nullptr : ws + L.lone;
             q.B = B; q.T = T; q.TP = fp.TP; q.F = F; q.K = K; q.hop = hop; q.padL = fp.padL;
             q.L = fp.L; q.nblk = fp.nblk; q.GZ = fp.GZ; q.nslot = fp.nslot; q.g_bufs = fp.g_bufs; q.NT = fp.NT; q.fq = fp.fq; q.nfq = fp.nfq;
@@ -1948,7 +1966,7 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
             q.gpre = gpre; q.pool_w = pool_w; q.dkpart = dkpart; q.dwpart = dwpart; q.part = nullptr;
             if (fft_wg_bwd_use(fp, B, K, hop, g_x != nullptr)) {
                 // workgroup-per-block backward; with g_x the per-block input gradients go to dxblk and are gathered below
-                FftWgBwdLaunch wl = pick_fft_wg_bwd_kernel(K, hop, g_x != nullptr, (long long)B * fp.nblk, x_bf16);
+                FftWgBwdLaunch wl = pick_fft_wg_bwd_kernel(K, hop, g_x != nullptr, (long long)B * fp.nblk, xtype == kSampleBf16);
                 q.part = g_x ? ws + L.dxblk : nullptr;
                 if (band_bwd) {
                     band.lds_off = (int)(wl.lds / 4);

@@ -101,15 +101,18 @@ __global__ __launch_bounds__(1024) void peak_normalize_kernel(const float* __res
 }
 
 // LEAF_FLAG_PEAKNORM: the per-clip scale of the transform above without the copy -- scale2[b] = s_b^2, s_b = 1 / peak when
-// the clip's peak |x| exceeds 1, else 1 (what the overlap-save finalize multiplies the pooled energies by).  x fp32 or bf16.
+// the clip's peak |x| exceeds 1, else 1 (what the overlap-save finalize multiplies the pooled energies by).  x fp32, bf16 or 16-bit PCM (io_bf16: the sample type).
 #ifndef LEAF_INST_TU
 __global__ __launch_bounds__(1024) void peak_scale2_kernel(const void* __restrict__ x_, int io_bf16, int T, float* __restrict__ scale2) {
     __shared__ float red[16];
     const int b = blockIdx.x, tid = threadIdx.x;
     float m = 0.0f;
-    if (io_bf16) {
+    if (io_bf16 == kSampleBf16) {
         const unsigned short* xb = static_cast<const unsigned short*>(x_) + (size_t)b * T;
         for (int i = tid; i < T; i += 1024) m = fmaxf(m, fabsf(__uint_as_float((unsigned)xb[i] << 16)));
+    } else if (io_bf16 == kSamplePcm16) {                 // |v / 32768| <= 1: the scale comes out as 1 (the library skips this launch)
+        const short* xb = static_cast<const short*>(x_) + (size_t)b * T;
+        for (int i = tid; i < T; i += 1024) m = fmaxf(m, fabsf(pcm16_widen(xb[i])));
     } else {
         const float* xb = static_cast<const float*>(x_) + (size_t)b * T;
         for (int i = tid; i < T; i += 1024) m = fmaxf(m, fabsf(xb[i]));

@@ -77,30 +77,42 @@ Params gather(const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b, 
 Tensor forward_impl(const Tensor& x, const Params& p, int64_t K, int64_t hop, bool log1p, int64_t algo, Tensor* raw) {
     Tensor x2 = waveform_2d(x);
     const bool io_bf16 = x2.scalar_type() == at::kBFloat16;
-    TORCH_CHECK(io_bf16 || x2.scalar_type() == at::kFloat, "x must be float32 (or bfloat16 for the bf16-I/O extension), got ",
-                x2.scalar_type());
+    const bool pcm16 = x2.scalar_type() == at::kShort;        // 16-bit PCM in (a sample v means v / 32768), float32 out
+    TORCH_CHECK(io_bf16 || pcm16 || x2.scalar_type() == at::kFloat,
+                "x must be float32 (or bfloat16 for the bf16-I/O extension, or int16 PCM), got ", x2.scalar_type());
     TORCH_CHECK(x2.size(1) < (int64_t(1) << 31), "a clip of ", x2.size(1), " samples is beyond the C ABI's 32-bit sample index");
     const int64_t B = x2.size(0);
     const int T = (int)x2.size(1), F = (int)p.kernel.size(0);
     const int TP = leaf_num_frames(T, (int)K, (int)hop);
     TORCH_CHECK(TP >= 1 && F >= 1, "bad shape B=", B, " T=", T, " F=", F, " K=", K, " hop=", hop);
+    const auto out_opt = pcm16 ? x2.options().dtype(at::kFloat) : x2.options();
     if (B == 0) {
         // the empty batch: the reference returns (0, F, T') (frontend.py:78-89 -> convolution.py:97); nothing is launched
         if (raw) *raw = at::empty({0, F, TP}, x2.options().dtype(at::kFloat));
-        return at::empty({0, F, TP}, x2.options());
+        return at::empty({0, F, TP}, out_opt);
     }
-    int flags = (io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (p.pcen ? LEAF_FLAG_PCEN : (log1p ? LEAF_FLAG_LOG1P : 0));
+    int flags = (io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (pcm16 ? LEAF_FLAG_X_PCM16 : 0) | (p.pcen ? LEAF_FLAG_PCEN : (log1p ? LEAF_FLAG_LOG1P : 0));
     // call options travelling in the upper bits of the op's `algo` argument (the schema stays as it is): bit 24 = the
     // PeakNormalization prologue folded into the forward (LEAF_FLAG_PEAKNORM; inference only)
     constexpr int64_t kOptPeakNorm = int64_t(1) << 24;
     if (algo & kOptPeakNorm) {
         TORCH_CHECK(!raw, "the fused PeakNormalization prologue is forward-only");
-        flags |= LEAF_FLAG_PEAKNORM;
+        if (!pcm16) flags |= LEAF_FLAG_PEAKNORM;                // (|v / 32768| <= 1: nothing to normalise, nothing launched)
         algo &= ~kOptPeakNorm;
     }
     c10::hip::HIPGuardMasqueradingAsCUDA guard(x2.device());
     auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x2.device().index());
-    Tensor out = at::empty({B, F, TP}, x2.options());
+    bool pcm16_staged = false;
+    if (pcm16) {
+        // the staged forward reads float32 only (LEAF_ERR_UNSUPPORTED from the C ABI): where the call lands on it, each slice is
+        // converted below -- the same values, v / 32768 exactly -- and runs the float path
+        int sel = (int)(algo & 0xff);
+        if (sel == LEAF_ALGO_AUTO) sel = leaf_auto_algo((int)std::min<int64_t>(B, batch_slices(B, T).per_call), T, F, (int)K, (int)hop);
+        pcm16_staged = sel == LEAF_ALGO_STAGED;
+        if (pcm16_staged) flags &= ~LEAF_FLAG_X_PCM16;
+    }
+    const bool x16 = (flags & LEAF_FLAG_X_PCM16) != 0;
+    Tensor out = at::empty({B, F, TP}, out_opt);
     if (raw) *raw = at::empty({B, F, TP}, x2.options().dtype(at::kFloat));
     // The C ABI indexes the samples of ONE call with 32 bits and refuses B * T >= 2^31 (LEAF_ERR_BAD_SHAPE); the reference's
     // conv1d takes any batch (frontend.py:78-89).  Clips are independent, so a larger batch goes through in balanced slices of
@@ -112,10 +124,13 @@ Tensor forward_impl(const Tensor& x, const Params& p, int64_t K, int64_t hop, bo
     Tensor ws = at::empty({(int64_t)std::max<size_t>({leaf_workspace_bytes((int)sl.per_call, T, F, (int)K, (int)hop, (int)algo),
                                                       leaf_workspace_bytes(last, T, F, (int)K, (int)hop, (int)algo), size_t(4)})},
                           x2.options().dtype(at::kByte));
-    const size_t io = io_bf16 ? 2 : 4;
+    const size_t io = io_bf16 ? 2 : 4, xio = x16 ? 2 : io;
     for (int64_t b0 = 0; b0 < B; b0 += sl.per_call) {
         const int nb = (int)std::min<int64_t>(sl.per_call, B - b0);
-        const float* xin = reinterpret_cast<const float*>(static_cast<const char*>(x2.data_ptr()) + (size_t)b0 * T * io);
+        Tensor xs;                                              // one slice of an int16 batch as float32, for the staged forward
+        if (pcm16_staged) xs = x2.narrow(0, b0, nb).to(at::kFloat).mul_(1.0 / 32768.0);
+        const float* xin = pcm16_staged ? xs.data_ptr<float>()
+                                        : reinterpret_cast<const float*>(static_cast<const char*>(x2.data_ptr()) + (size_t)b0 * T * xio);
         float* o = reinterpret_cast<float*>(static_cast<char*>(out.data_ptr()) + (size_t)b0 * F * TP * io);
         int rc;
         if (raw) {
@@ -154,16 +169,18 @@ std::tuple<Tensor, Tensor> op_forward_train(const Tensor& x, const Tensor& kerne
 // leaf_amd::backward -- what autograd derives for frontend.py:78-89: (g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root,
 // g_ema_w, g_x); the PCEN entries are empty tensors without PCEN, g_x is empty unless need_dx.  `flags` are C-ABI flags
 // (LEAF_FLAG_BWD_*, and LEAF_FLAG_LOG1P for the backward of the log1p-compressed forward); LEAF_FLAG_PCEN and
-// LEAF_FLAG_IO_BF16 follow from the tensors.  bfloat16 x: grad_out is bfloat16 too, g_x comes back in bfloat16, the
-// parameter gradients and pooled_raw are float32.
+// LEAF_FLAG_IO_BF16 / LEAF_FLAG_X_PCM16 follow from the tensors.  bfloat16 x: grad_out is bfloat16 too, g_x comes back in
+// bfloat16, the parameter gradients and pooled_raw are float32.  int16 x (PCM): grad_out float32, need_dx refused.
 std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b,
                                 const OptTensor& alpha, const OptTensor& delta, const OptTensor& root, const OptTensor& ema_w,
                                 int64_t K, int64_t hop, const Tensor& grad_out, const OptTensor& pooled_raw, bool need_dx,
                                 int64_t flags) {
     Tensor x2 = waveform_2d(x);
     const bool io_bf16 = x2.scalar_type() == at::kBFloat16;
-    TORCH_CHECK(io_bf16 || x2.scalar_type() == at::kFloat, "x must be float32 (or bfloat16 for the bf16-I/O extension), got ",
-                x2.scalar_type());
+    const bool pcm16 = x2.scalar_type() == at::kShort;
+    TORCH_CHECK(io_bf16 || pcm16 || x2.scalar_type() == at::kFloat,
+                "x must be float32 (or bfloat16 for the bf16-I/O extension, or int16 PCM), got ", x2.scalar_type());
+    TORCH_CHECK(!(pcm16 && need_dx), "an int16 (PCM) input has no gradient: need_dx needs a float32 or bfloat16 x");
     const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
     TORCH_CHECK(x2.size(1) < (int64_t(1) << 31), "a clip of ", x2.size(1), " samples is beyond the C ABI's 32-bit sample index");
     const int64_t B = x2.size(0);
@@ -191,10 +208,11 @@ std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Ten
         for (Tensor* g : {&gk, &gpw, &gpb, &ga, &gd, &gr, &gw}) g->zero_();
         return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw, need_dx ? gx.reshape(x.sizes()) : gx};
     }
-    const int fl = ((int)flags & ~(LEAF_FLAG_PCEN | LEAF_FLAG_IO_BF16)) | (p.pcen ? LEAF_FLAG_PCEN : 0) | (io_bf16 ? LEAF_FLAG_IO_BF16 : 0);
+    const int fl = ((int)flags & ~(LEAF_FLAG_PCEN | LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16)) | (p.pcen ? LEAF_FLAG_PCEN : 0) |
+                   (io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (pcm16 ? LEAF_FLAG_X_PCM16 : 0);
     const size_t io = io_bf16 ? 2 : 4;
-    auto io_at = [io](const Tensor& t, size_t elems) {      // element offset into a float32 / bfloat16 I/O tensor, as the C ABI's float pointer
-        return reinterpret_cast<float*>(static_cast<char*>(t.data_ptr()) + elems * io);
+    auto io_at = [io](const Tensor& t, size_t elems) {      // element offset into a float32 / bfloat16 / int16 I/O tensor, as the C ABI's float pointer
+        return reinterpret_cast<float*>(static_cast<char*>(t.data_ptr()) + elems * (t.scalar_type() == at::kShort ? 2 : io));
     };
     // B * T >= 2^31: slices of whole clips as in the forward; the parameter gradients of the slices are added in slice order
     // (a fixed order: the step stays bit-reproducible), dL/dx is written slice by slice

@@ -143,6 +143,10 @@ class Leaf(nn.Module):
         return self._tables
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """(B,1,T) float32 -> (B,F,T') float32, as the reference.  Not part of the reference surface: a bfloat16 ``x`` gives
+        bfloat16 features, and an int16 ``x`` is 16-bit PCM -- a sample v means v / 32768, converted inside the kernels' loads --
+        and gives the float32 features of ``x.float() / 32768`` bit for bit, on every path (inference, ``cache_tables()``,
+        training of the parameters, ``log_compression()``, ``full_transforms()``); it has no gradient of its own."""
         _native.require_hip(x, "Leaf.forward")
         algo = self._algo
         c = self._compression
@@ -152,7 +156,8 @@ class Leaf(nn.Module):
         # from the tensors actually handed to the kernel, not self.parameters(): nn.DataParallel replicas hold plain
         # (non-leaf) tensors, for which parameters() is empty
         params_need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params)
-        if self._fuse_peaknorm:
+        # an int16 waveform (16-bit PCM: a sample v means v / 32768) lies in [-1, 1) by construction: nothing to normalise
+        if self._fuse_peaknorm and x.dtype != torch.int16:
             K_, hop_ = self._complex_conv._kernel_size, self._pooling.strides
             # the folded prologue is forward-only: the same condition that sends the call to the training path below
             fused_ok = (not (params_need_grad or (torch.is_grad_enabled() and x.requires_grad))

@@ -61,10 +61,17 @@ class LeafStream:
 
     @torch.no_grad()
     def step(self, chunk: torch.Tensor) -> torch.Tensor:
-        """chunk (B,1,Tc) or (B,Tc) float32 on the device -> the frames that became final, (B,F,n) with n >= 0."""
+        """chunk (B,1,Tc) or (B,Tc) on the device -> the frames that became final, (B,F,n) float32 with n >= 0.  Chunks are float32
+        (every other type but int16 is widened with ``.float()``, as before), or int16 for 16-bit PCM (a sample v means v / 32768): then the history buffer stays
+        int16 and the int16 forward runs on it.  A stream keeps the type of its first chunk: a change in mid-stream raises."""
+        pcm = chunk.dtype == torch.int16
+        if self.buf is not None and pcm != (self.buf.dtype == torch.int16):
+            raise RuntimeError(f"LeafStream.step: this stream holds {'int16 PCM' if self.buf.dtype == torch.int16 else 'float32'} "
+                               f"samples and got a {chunk.dtype} chunk: one sample type per stream (flush() ends it)")
         _native.require_hip(chunk, "LeafStream.step")
         x2 = chunk[:, 0, :] if chunk.dim() == 3 else chunk
-        self.buf = x2.float() if self.buf is None else torch.cat([self.buf, x2.to(self.buf.dtype)], dim=1)
+        x2 = x2 if pcm else x2.float()
+        self.buf = x2 if self.buf is None else torch.cat([self.buf, x2], dim=1)
         last = (self.buf.shape[1] - 1 - self.reach) // self.hop           # last frame whose receptive field is complete
         if last < self.next:
             return chunk.new_empty((x2.shape[0], self.F, 0), dtype=torch.float32)
@@ -84,7 +91,7 @@ class LeafStream:
         if self.buf is None:
             return torch.empty((0, self.F, 0), device="cuda")
         last = (self.buf.shape[1] - 1) // self.hop                        # frames of a clip of this length: floor((T - 1) / hop) + 1
-        out = self._emit(self.next, last) if last >= self.next else self.buf.new_empty((self.buf.shape[0], self.F, 0))
+        out = self._emit(self.next, last) if last >= self.next else self.buf.new_empty((self.buf.shape[0], self.F, 0), dtype=torch.float32)
         self.buf = self.state = None
         self.next = 0
         self.started = False

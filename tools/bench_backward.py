@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Time forward and forward+backward of Leaf (parameters require grad) on one GPU.
-   usage: bench_backward.py [--no-pcen | --log1p] [--bf16] [--interleave V1,V2,..] [B [n_filters sample_rate seconds [nodx]]]
+   usage: bench_backward.py [--no-pcen | --log1p] [--bf16 | --pcm16] [--interleave V1,V2,..] [B [n_filters sample_rate seconds [nodx]]]
    (default 256 clips of the default 40 f / 16 kHz / 1 s, PCEN on, float32;
    nodx skips the dL/dx timing -- staged kernels, hundreds of ms, for geometries without a fused dL/dx)
    --no-pcen: PCEN off (BASELINE configs[3] without compression); --log1p: PCEN off with Leaf.log_compression() (configs[3]);
    --bf16: bfloat16 waveform, features, grad_out and dL/dx (configs[4]).
-   --interleave pcen,off,log1p,pcen+bf16,...: instead of the line above, the training step (grad_out resident; with "+dx": incl. dL/dx)
+   --pcm16: int16 waveform (16-bit PCM, a sample v means v / 32768), float32 features and grad_out, no dL/dx.
+   --interleave pcen,off,log1p,pcen+bf16,pcen+pcm16,pcen+pcm16cast,...: ("+pcm16cast": the int16 clips converted by the caller,
+   x.float().mul_(2**-15), inside the timed step, then the float32 call; "+fwd": the no-grad forward alone instead of the step) instead of the line above, the training step (grad_out resident; with "+dx": incl. dL/dx)
    of each named variant timed in turn, round after round, in this one process: median, min and max of the rounds per variant, so that
    two variants are compared under the same clocks and the spread of each is on the page."""
 import os
@@ -17,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from leaf_pytorch_amd import Leaf  # noqa: E402
 
 dev = torch.device("cuda:0")
-OPTS = {a for a in sys.argv[1:] if a in ("--no-pcen", "--log1p", "--bf16")}
+OPTS = {a for a in sys.argv[1:] if a in ("--no-pcen", "--log1p", "--bf16", "--pcm16")}
 INTERLEAVE = None
 if "--interleave" in sys.argv:
     i = sys.argv.index("--interleave")
@@ -40,6 +42,9 @@ m = make(pcen="--no-pcen" not in OPTS, log1p="--log1p" in OPTS)
 x = 2 * torch.rand(B, 1, int(SR * SECS), device=dev) - 1
 if "--bf16" in OPTS:
     x = x.to(torch.bfloat16)
+x16 = torch.round(x.float() * 32767).to(torch.int16)          # the same clips as 16-bit PCM
+if "--pcm16" in OPTS:
+    x = x16
 
 
 def timed(fn, n=20):
@@ -80,7 +85,7 @@ def fwd_bwd_resident():
     torch.autograd.backward(m(x), go)
 
 
-xg = x.clone().requires_grad_(True)
+xg = x.clone().requires_grad_(True) if x.is_floating_point() else None
 
 
 def fwd_bwd_dx():
@@ -105,21 +110,27 @@ def graphed(fn_step):
     return g.replay
 
 
-NODX = len(sys.argv) > 5 and sys.argv[5] == "nodx"
+NODX = (len(sys.argv) > 5 and sys.argv[5] == "nodx") or xg is None          # (an integer waveform has no gradient)
 if INTERLEAVE:
     import statistics
     steps = {}
     for name in INTERLEAVE:
         parts = name.split("+")
         mod = make(pcen=parts[0] == "pcen", log1p=parts[0] == "log1p")
-        xv = (x.to(torch.bfloat16) if "bf16" in parts else x.float()).clone().requires_grad_("dx" in parts)
+        pcm, cast = "pcm16" in parts, "pcm16cast" in parts
+        xv = x16.clone() if pcm or cast else (x.to(torch.bfloat16) if "bf16" in parts else x.float()).clone().requires_grad_("dx" in parts)
         with torch.no_grad():
             gv = torch.randn_like(mod(xv))
 
-        def step(mod=mod, xv=xv, gv=gv):
+        def step(mod=mod, xv=xv, gv=gv, cast=cast, fwd_only="fwd" in parts):
+            xin = xv.float().mul_(2.0 ** -15) if cast else xv
+            if fwd_only:
+                with torch.no_grad():
+                    mod(xin)
+                return
             mod.zero_grad(set_to_none=True)
             xv.grad = None
-            torch.autograd.backward(mod(xv), gv)
+            torch.autograd.backward(mod(xin), gv)
         steps[name] = step
     res = {name: [] for name in steps}
     for rnd in range(9):
@@ -135,7 +146,7 @@ if INTERLEAVE:
             if rnd:                                # (the first round warms the clocks and the allocator)
                 res[name].append(s.elapsed_time(e) / 20)
     for name, r in res.items():
-        print(f"B={B} F={F} sr={SR} {SECS:g}s {name:14s} forward+backward (grad_out resident) median {statistics.median(r):.4f} ms   "
+        print(f"B={B} F={F} sr={SR} {SECS:g}s {name:18s} {'forward (no grad)' if '+fwd' in name else 'forward+backward (grad_out resident)'} median {statistics.median(r):.4f} ms   "
               f"min {min(r):.4f}   max {max(r):.4f}   spread {max(r) - min(r):.4f}")
     sys.exit(0)
 print(f"B={B} F={F} sr={SR} {SECS:g}s: forward {timed(fwd):.3f} ms   forward+backward {timed(fwd_bwd):.3f} ms   "
