@@ -23,6 +23,17 @@
  *     their own -- kernels of one call hand data to each other through it (partial sums, tables, the seam slots of the
  *     one-launch kernel's two halves), and a second call writing the same bytes would be read as the first call's.  Calls on ONE
  *     stream may share a workspace (they execute in order).
+ *   - ALIGNMENT.  `workspace` and `tables`: 16 bytes -- the kernels read their regions (each a multiple of 256 bytes behind
+ *     the base) as float2 / float4 / int4 rows, with 16-byte direct-to-LDS loads and, at the seam of the one-launch kernel,
+ *     64-bit atomics (hipMalloc and every framework allocator give 256 bytes or more).  Every other buffer is reached one
+ *     element at a time and needs its element's alignment: 4 bytes for float32 / int32 (x, out, pooled_raw, grad_out, g_x, the
+ *     parameters, their gradients, every stage input and output, `classes`, the stream state), 2 bytes where a flag makes the
+ *     buffer bfloat16 or int16.  Anything below is answered with LEAF_ERR_ALIGNMENT before the workspace check and before any
+ *     launch (NULL for an optional argument passes).
+ *   - EXACT SIZES.  A call writes nothing outside the buffers it is given at the sizes this header states, the workspace at
+ *     exactly the bytes its size query answers; it reads no workspace byte it has not written itself (the workspace may hold
+ *     anything on entry, a previous call's leftovers included) and writes -- never accumulates into -- every element of its
+ *     outputs (tests/test_gpu_abi_memory.py).
  *   - return value: LEAF_OK (0) or a negative leaf_status code.  Never throws, never aborts.
  *   - B = 0 is the EMPTY BATCH, not an error (the reference returns a (0, F, T') tensor: frontend.py:78-89 ->
  *     convolution.py:97): leaf_forward_f32 / _save_f32 / _prepared_f32 / _profiled_f32 return LEAF_OK without a launch
@@ -52,7 +63,9 @@ typedef enum leaf_status {
     LEAF_ERR_BAD_ALGO = -4,       /* unknown / inapplicable algorithm selector              */
     LEAF_ERR_LAUNCH = -5,         /* HIP reported a launch failure (hipGetLastError != 0)   */
     LEAF_ERR_NO_DEVICE = -6,      /* no usable gfx950 device                                */
-    LEAF_ERR_ALIGNMENT = -7,      /* a buffer is not 4-byte aligned (bfloat16 / 16-bit PCM buffers: 2-byte) */
+    LEAF_ERR_ALIGNMENT = -7,      /* a buffer is below its alignment: workspace / tables 16-byte, float32 buffers 4-byte, bfloat16 /
+                                     16-bit PCM buffers 2-byte (ALIGNMENT under Conventions); answered before the workspace check
+                                     and before any launch */
     LEAF_ERR_UNSUPPORTED = -8     /* valid arguments, unsupported combination: bfloat16 I/O with the staged FORWARD
                                      kernels (the backward takes it on every path, ABI 6); LEAF_FLAG_PEAKNORM with
                                      leaf_forward_save_f32 / leaf_forward_prepared_f32 or off the overlap-save paths;
@@ -284,7 +297,7 @@ int leaf_band_classes_f32(const float* kernel, const float* pool_w, const float*
  * leaf_backward_workspace_bytes for the SAME flags and need_dx = (g_x != NULL): sized for the path that will actually
  * run (a few MB for the overlap-save backward; the staged path materialises dL/dy, B*T*2F floats).
  * ABI 6: LEAF_FLAG_LOG1P (PCEN off) and LEAF_FLAG_IO_BF16 (x, grad_out, g_x bfloat16 behind the float pointers) as described
- * at the flags; x, grad_out and g_x must be 4-byte (bfloat16: 2-byte) aligned, else LEAF_ERR_ALIGNMENT.
+ * at the flags; x, grad_out and g_x must be 4-byte (bfloat16: 2-byte) aligned, the workspace 16-byte, else LEAF_ERR_ALIGNMENT.
  * LEAF_FLAG_X_PCM16: x alone is int16 (2-byte aligned), grad_out stays float32, g_x must be NULL (LEAF_ERR_UNSUPPORTED).
  */
 size_t leaf_backward_workspace_bytes(int B, int T, int F, int K, int hop, int flags, int need_dx);

@@ -581,6 +581,12 @@ int auto_algo(int B, int T, int F, int K, int hop, bool allow_small = true) {
 }
 
 inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
+// float32 / int32 buffers the kernels reach with one-element accesses only (parameters, their gradients, pooled_raw, stage
+// inputs and outputs): 4-byte aligned; NULL (an optional argument left out) passes
+template <class... P> inline bool any_misaligned(const P*... p) { return (misaligned(p) || ...); }
+// `workspace` and `tables`: the kernels read their regions (each a multiple of 256 bytes behind the base) with 8- and 16-byte
+// accesses -- float2 / float4 / int4 rows, 16-byte direct-to-LDS loads, the 64-bit seam tickets: 16-byte aligned
+inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 // sample type of the waveform buffer (leaf_common.hpp kSample*), the value the kernels' `io_bf16` field carries
 inline int x_sample_type(int flags) {
     return (flags & LEAF_FLAG_IO_BF16) ? kSampleBf16 : (flags & LEAF_FLAG_X_PCM16) ? kSamplePcm16 : kSampleF32;
@@ -662,7 +668,7 @@ const char* leaf_status_string(int status) {
         case LEAF_ERR_BAD_ALGO: return "unknown or inapplicable algorithm selector";
         case LEAF_ERR_LAUNCH: return "HIP kernel launch failed";
         case LEAF_ERR_NO_DEVICE: return "no usable gfx950 device";
-        case LEAF_ERR_ALIGNMENT: return "buffer not 4-byte aligned (2-byte for bfloat16 and 16-bit PCM buffers)";
+        case LEAF_ERR_ALIGNMENT: return "buffer not 4-byte aligned (2-byte for bfloat16 and 16-bit PCM buffers; 16-byte for workspace and tables)";
         case LEAF_ERR_UNSUPPORTED: return "combination not supported (bfloat16 I/O and 16-bit PCM input (LEAF_FLAG_X_PCM16) have no staged forward: use float32 buffers; LEAF_FLAG_X_PCM16 excludes LEAF_FLAG_IO_BF16 and has no dL/dx (g_x must be NULL); LEAF_FLAG_PEAKNORM needs an overlap-save path and has no backward)";
     }
     return "unknown status";
@@ -727,6 +733,7 @@ size_t leaf_workspace_bytes(int B, int T, int F, int K, int hop, int algo) {
 int leaf_gabor_taps_f32(const float* kernel, int F, int K, float* taps, void* stream) {
     if (!kernel || !taps) return LEAF_ERR_NULL_POINTER;
     if (F < 1 || K < 1) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(kernel, taps)) return LEAF_ERR_ALIGNMENT;
     hipLaunchKernelGGL(taps_direct_kernel, dim3(ceil_div(F * K, 256)), dim3(256), 0, (hipStream_t)stream, kernel, F, K,
                        gabor_bounds(K), taps);
     LEAF_LAUNCH_CHECK();
@@ -736,6 +743,7 @@ int leaf_gabor_taps_f32(const float* kernel, int F, int K, float* taps, void* st
 int leaf_lowpass_window_f32(const float* pool_w, int F, int K, float* window, void* stream) {
     if (!pool_w || !window) return LEAF_ERR_NULL_POINTER;
     if (F < 1 || K < 1) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(pool_w, window)) return LEAF_ERR_ALIGNMENT;
     hipLaunchKernelGGL(lowpass_window_kernel, dim3(ceil_div(F * K, 256)), dim3(256), 0, (hipStream_t)stream, pool_w, F, K,
                        window);
     LEAF_LAUNCH_CHECK();
@@ -746,6 +754,7 @@ int leaf_gabor_conv_f32(const float* x, int B, int T, const float* kernel, int F
                         size_t workspace_bytes, void* stream) {
     if (!x || !kernel || !y) return LEAF_ERR_NULL_POINTER;
     if (check_shape(B, T, F, K, 1) != LEAF_OK || 2 * F > 65535 || B > 65535) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(x, kernel, y) || misaligned16(workspace)) return LEAF_ERR_ALIGNMENT;
     if (!workspace || workspace_bytes < (size_t)2 * F * K * 4) return LEAF_ERR_WORKSPACE;
     float* taps = static_cast<float*>(workspace);
     int rc = leaf_gabor_taps_f32(kernel, F, K, taps, stream);
@@ -760,6 +769,7 @@ int leaf_gabor_conv_f32(const float* x, int B, int T, const float* kernel, int F
 int leaf_squared_modulus_f32(const float* y, int B, int F, int T, float* e, void* stream) {
     if (!y || !e) return LEAF_ERR_NULL_POINTER;
     if (B < 1 || F < 1 || T < 1) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(y, e)) return LEAF_ERR_ALIGNMENT;
     const size_t n = (size_t)B * F * T;
     hipLaunchKernelGGL(sqmod_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y,
                        (size_t)B * F, T, e);
@@ -771,6 +781,7 @@ int leaf_gaussian_lowpass_f32(const float* e, int B, int F, int T, const float* 
                               int hop, float* pooled, void* workspace, size_t workspace_bytes, void* stream) {
     if (!e || !pool_w || !pooled) return LEAF_ERR_NULL_POINTER;
     if (check_shape(B, T, F, K, hop) != LEAF_OK || F > 65535 || B > 65535) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(e, pool_w, pool_b, pooled) || misaligned16(workspace)) return LEAF_ERR_ALIGNMENT;
     if (!workspace || workspace_bytes < (size_t)F * K * 4) return LEAF_ERR_WORKSPACE;
     float* g = static_cast<float*>(workspace);
     int rc = leaf_lowpass_window_f32(pool_w, F, K, g, stream);
@@ -786,6 +797,7 @@ int leaf_gaussian_lowpass_f32(const float* e, int B, int F, int T, const float* 
 int leaf_ema_f32(const float* p, int B, int F, int TP, const float* ema_w, float* ema, void* stream) {
     if (!p || !ema_w || !ema) return LEAF_ERR_NULL_POINTER;
     if (B < 1 || F < 1 || TP < 1) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(p, ema_w, ema)) return LEAF_ERR_ALIGNMENT;
     hipLaunchKernelGGL(pcen_rows_kernel, dim3(ceil_div(B * F, 64)), dim3(64), 0, (hipStream_t)stream, p, B * F, F, TP,
                        (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ema_w, 0.0f, 0, ema);
     LEAF_LAUNCH_CHECK();
@@ -796,6 +808,7 @@ int leaf_pcen_f32(const float* p, int B, int F, int TP, const float* alpha, cons
                   const float* ema_w, float floor_, float* out, void* stream) {
     if (!p || !alpha || !delta || !root || !ema_w || !out) return LEAF_ERR_NULL_POINTER;
     if (B < 1 || F < 1 || TP < 1) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(p, alpha, delta, root, ema_w, out)) return LEAF_ERR_ALIGNMENT;
     hipLaunchKernelGGL(pcen_rows_kernel, dim3(ceil_div(B * F, 64)), dim3(64), 0, (hipStream_t)stream, p, B * F, F, TP,
                        alpha, delta, root, ema_w, floor_, 1, out);
     LEAF_LAUNCH_CHECK();
@@ -808,6 +821,7 @@ int leaf_pcen_stream_f32(const float* p, int B, int F, int n, const float* alpha
     if (!p || !out) return LEAF_ERR_NULL_POINTER;
     if (alpha && (!delta || !root || !ema_w)) return LEAF_ERR_NULL_POINTER;
     if (B < 1 || F < 1 || n < 1) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(p, alpha, delta, root, ema_w, ema_in, ema_out, out)) return LEAF_ERR_ALIGNMENT;
     FinParams q{};
     q.F = F; q.TP = n; q.alpha = alpha; q.delta = delta; q.root = root; q.ema_w = ema_w; q.floor_ = floor_;
     q.mode = alpha ? 1 : (log1p_ ? 2 : 0);
@@ -837,6 +851,7 @@ int leaf_gabor_conv_backward_f32(const float* x, int B, int T, const float* kern
                                  float* g_kernel, float* g_x, void* workspace, size_t workspace_bytes, void* stream) {
     if (!x || !kernel || !grad_y) return LEAF_ERR_NULL_POINTER;
     if (check_shape(B, T, F, K, 1) != LEAF_OK || 2 * F > 65535 || B > 65535) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(x, kernel, grad_y, g_kernel, g_x) || misaligned16(workspace)) return LEAF_ERR_ALIGNMENT;
     if (!workspace || workspace_bytes < leaf_stage_backward_workspace_bytes(LEAF_STAGE_GABOR_CONV, B, T, F, K, 1))
         return LEAF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -862,6 +877,7 @@ int leaf_gabor_conv_backward_f32(const float* x, int B, int T, const float* kern
 int leaf_squared_modulus_backward_f32(const float* y, const float* grad_e, int B, int F, int T, float* grad_y, void* stream) {
     if (!y || !grad_e || !grad_y) return LEAF_ERR_NULL_POINTER;
     if (B < 1 || F < 1 || T < 1) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(y, grad_e, grad_y)) return LEAF_ERR_ALIGNMENT;
     const size_t n = (size_t)B * F * T;
     hipLaunchKernelGGL(sqmod_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, grad_e,
                        (size_t)B * F, T, grad_y);
@@ -874,6 +890,7 @@ int leaf_gaussian_lowpass_backward_f32(const float* e, const float* grad_pooled,
                                        size_t workspace_bytes, void* stream) {
     if (!e || !grad_pooled || !pool_w) return LEAF_ERR_NULL_POINTER;
     if (check_shape(B, T, F, K, hop) != LEAF_OK || F > 65535 || B > 65535) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(e, grad_pooled, pool_w, g_e, g_pool_w, g_pool_b) || misaligned16(workspace)) return LEAF_ERR_ALIGNMENT;
     if (!workspace || workspace_bytes < leaf_stage_backward_workspace_bytes(LEAF_STAGE_LOWPASS, B, T, F, K, hop))
         return LEAF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -906,6 +923,7 @@ int leaf_ema_backward_f32(const float* p, const float* grad_ema, int B, int F, i
                           float* g_ema_w, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !grad_ema || !ema_w || !g_p || !g_ema_w) return LEAF_ERR_NULL_POINTER;
     if (B < 1 || F < 1 || TP < 1) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(p, grad_ema, ema_w, g_p, g_ema_w) || misaligned16(workspace)) return LEAF_ERR_ALIGNMENT;
     if (!workspace || workspace_bytes < leaf_stage_backward_workspace_bytes(LEAF_STAGE_EMA, B, TP, F, 1, 1))
         return LEAF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -927,6 +945,8 @@ int leaf_pcen_backward_f32(const float* p, const float* grad_out, int B, int F, 
     if (!p || !grad_out || !alpha || !delta || !root || !ema_w || !g_p || !g_alpha || !g_delta || !g_root || !g_ema_w)
         return LEAF_ERR_NULL_POINTER;
     if (B < 1 || F < 1 || TP < 1) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(p, grad_out, alpha, delta, root, ema_w, g_p, g_alpha, g_delta, g_root, g_ema_w) || misaligned16(workspace))
+        return LEAF_ERR_ALIGNMENT;
     if (!workspace || workspace_bytes < leaf_stage_backward_workspace_bytes(LEAF_STAGE_PCEN, B, TP, F, 1, 1))
         return LEAF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -1099,6 +1119,7 @@ static int fft_forward(const FftPlan& fp, const void* x, int xtype, int B, int T
 int leaf_peak_normalize_f32(const float* x, int B, int T, float* out, void* stream) {
     if (!x || !out) return LEAF_ERR_NULL_POINTER;
     if (B < 1 || T < 1) return LEAF_ERR_BAD_SHAPE;
+    if (any_misaligned(x, out)) return LEAF_ERR_ALIGNMENT;
     hipLaunchKernelGGL(peak_normalize_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, x, T, out);
     LEAF_LAUNCH_CHECK();
     return LEAF_OK;
@@ -1128,7 +1149,8 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
     {
         const uintptr_t io_mask = (flags & LEAF_FLAG_IO_BF16) ? 1u : 3u;
         const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;       // 16-bit PCM: x alone is a 2-byte buffer
-        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & io_mask) || misaligned(workspace))
+        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & io_mask) || misaligned16(workspace) ||
+            any_misaligned(kernel, pool_w, pool_b, alpha, delta, root, ema_w, pooled_raw))
             return LEAF_ERR_ALIGNMENT;
     }
     const int tuning_desync = ((algo >> 8) & 0xff) - 1;      // LEAF_ALGO_TUNE_DESYNC(n); -1 = automatic
@@ -1383,8 +1405,8 @@ int leaf_fft_prepare_tables_f32(const float* kernel, const float* pool_w, int F,
     if (!kernel || !pool_w || !tables) return LEAF_ERR_NULL_POINTER;
     const size_t need = leaf_fft_tables_bytes(F, K, hop);
     if (need == 0) return LEAF_ERR_BAD_ALGO;
+    if (misaligned16(tables) || any_misaligned(kernel, pool_w)) return LEAF_ERR_ALIGNMENT;
     if (tables_bytes < need) return LEAF_ERR_WORKSPACE;
-    if (misaligned(tables)) return LEAF_ERR_ALIGNMENT;
     const FftPlan fp = make_fft_plan(1, std::max(K, 2 * kFftN), F, K, hop);
     float* t = static_cast<float*>(tables);
     float* Gz = t + align_up(fp.h_floats, 64);
@@ -1414,8 +1436,8 @@ int leaf_band_classes_f32(const float* kernel, const float* pool_w, const float*
         // the 4096-sample plan (K = 801 / hop = 320): one class, decided by fft4k_prep_kernel; classes[f] = 512 or 4096
         const Fft4kPlan f4 = make_fft4k_plan(1, 2 * kFft4N, F, K, hop);
         if (f4.ok && !f4.generic && f4.band_floats) {
+            if (misaligned16(workspace) || any_misaligned(kernel, pool_w, pool_b, classes)) return LEAF_ERR_ALIGNMENT;
             if (!workspace || workspace_bytes < fft4k_workspace_floats(f4, 1) * 4) return LEAF_ERR_WORKSPACE;
-            if (misaligned(workspace) || misaligned(classes)) return LEAF_ERR_ALIGNMENT;
             float* tab = static_cast<float*>(workspace);
             float* Grow = tab + align_up(f4.tab_floats, 64);
             float* bt = Grow + align_up(f4.grow_floats, 64) + align_up(f4.part_floats, 64);
@@ -1433,8 +1455,8 @@ int leaf_band_classes_f32(const float* kernel, const float* pool_w, const float*
     const BandLayout bl = band_layout(F, K, hop);
     if (!bl.stat) return LEAF_ERR_UNSUPPORTED;               // no band tasks for this geometry: every filter on full transforms
     const size_t need = leaf_fft_tables_bytes(F, K, hop);
+    if (misaligned16(workspace) || any_misaligned(kernel, pool_w, pool_b, classes)) return LEAF_ERR_ALIGNMENT;
     if (!workspace || need == 0 || workspace_bytes < need) return LEAF_ERR_WORKSPACE;
-    if (misaligned(workspace) || misaligned(classes)) return LEAF_ERR_ALIGNMENT;
     const FftPlan fp = make_fft_plan(1, std::max(K, 2 * kFftN), F, K, hop);
     float* t = static_cast<float*>(workspace);
     float* Gz = t + align_up(fp.h_floats, 64);
@@ -1468,8 +1490,8 @@ int leaf_forward_prepared_f32(const float* x, int B, int T, const void* tables, 
     const bool io_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;
     const uintptr_t io_mask = io_bf16 ? 1u : 3u;
     const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;
-    if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & io_mask) || misaligned(workspace) ||
-        misaligned(tables))
+    if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & io_mask) || misaligned16(workspace) ||
+        misaligned16(tables) || any_misaligned(pool_b, alpha, delta, root, ema_w))
         return LEAF_ERR_ALIGNMENT;
     if (!workspace || workspace_bytes < (align_up(fp.part_floats, 64) + (LEAF_TRACE ? 16 * 64 * 2 : 0)) * 4) return LEAF_ERR_WORKSPACE;
     const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (io_bf16 ? 4 : 0);
@@ -1782,7 +1804,9 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
         const uintptr_t io_mask = io_bf16 ? 1u : 3u;
         const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;
         if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(grad_out) & io_mask) ||
-            (reinterpret_cast<uintptr_t>(g_x) & io_mask) || misaligned(workspace))
+            (reinterpret_cast<uintptr_t>(g_x) & io_mask) || misaligned16(workspace) ||
+            any_misaligned(kernel, pool_w, pool_b, alpha, delta, root, ema_w, pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta,
+                           g_root, g_ema_w))
             return LEAF_ERR_ALIGNMENT;
     }
     const BwdPath path = bwd_path(B, T, F, K, hop, flags, g_x != nullptr);
