@@ -311,6 +311,50 @@ int leaf_backward_f32(const float* x, int B, int T,
                       float* g_x, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Waveform mixup in front of the frontend (the reference's training loop, utilities/data/mixup.py:17-24 with train.py:237-243),
+ * additive to ABI 6.  Per clip b, with the partner clip p = mix_perm[b] and the weight lam = mix_lam[b], a mixed sample is
+ *     om = 1 - lam;   x'[b][n] = (x[b][n] * lam) + (x[p][n] * om)
+ * in fp32 with three separately rounded operations (no fused multiply-add): bit for bit the reference's expression.  x is float32,
+ * or int16 with LEAF_FLAG_X_PCM16 (the sample v means v / 32768, which is exact).  mix_perm [B] int32 and mix_lam [B] float32 are
+ * device buffers, 4-byte aligned; an entry of mix_perm outside [0, B) is clamped into it on the device (a wrong partner, never a read
+ * out of bounds).  Every *_mix_* entry computes exactly what its plain counterpart computes on x'.
+ *
+ * leaf_mixup_f32: x' itself, out [B][T] float32, one pass (read two clips, write one).  flags: 0 or LEAF_FLAG_X_PCM16.
+ *
+ * leaf_forward_mix_f32 / leaf_forward_save_mix_f32 / leaf_backward_mix_f32: leaf_forward_f32 / leaf_forward_save_f32 /
+ * leaf_backward_f32 on x', arguments as there plus the two buffers after x.  The static-geometry overlap-save kernels (FFT_SMALL,
+ * FFT and FFT_WG at 401/160, 201/80 and 801/320, and the matching per-wave and workgroup backwards) and the 4096-sample plans,
+ * forward and backward, mix inside their loads: x' never exists in memory and an int16 batch stays int16 through a training step.
+ * Every other selector and path (run-time-geometry kernels of the 2048-sample plan, MFMA, staged) first writes x' behind its own
+ * workspace with the kernel of leaf_mixup_f32 and continues on it; the queries below include that copy where it is needed.  Workspace: leaf_forward_mix_workspace_bytes for the same selector,
+ * leaf_backward_mix_workspace_bytes for the same flags.  LEAF_ERR_UNSUPPORTED: LEAF_FLAG_IO_BF16 (the mix is defined in fp32),
+ * LEAF_FLAG_PEAKNORM (the normalisation would have to follow the mix) and g_x != NULL (dL/dx would be a scatter over mix_perm, and
+ * x is data here).  B == 0 is the empty batch as everywhere; mix_perm and mix_lam may then be NULL.
+ */
+int leaf_mixup_f32(const void* x, int B, int T, const int* mix_perm /*[B]*/, const float* mix_lam /*[B]*/, int flags,
+                   float* out, void* stream);
+size_t leaf_forward_mix_workspace_bytes(int B, int T, int F, int K, int hop, int algo);
+int leaf_forward_mix_f32(const void* x, const int* mix_perm /*[B]*/, const float* mix_lam /*[B]*/, int B, int T,
+                         const float* kernel, const float* pool_w, const float* pool_b,
+                         const float* alpha, const float* delta, const float* root, const float* ema_w,
+                         int F, int K, int hop, int flags, int algo,
+                         float* out, void* workspace, size_t workspace_bytes, void* stream);
+int leaf_forward_save_mix_f32(const void* x, const int* mix_perm /*[B]*/, const float* mix_lam /*[B]*/, int B, int T,
+                              const float* kernel, const float* pool_w, const float* pool_b,
+                              const float* alpha, const float* delta, const float* root, const float* ema_w,
+                              int F, int K, int hop, int flags, int algo,
+                              float* out, float* pooled_raw, void* workspace, size_t workspace_bytes, void* stream);
+size_t leaf_backward_mix_workspace_bytes(int B, int T, int F, int K, int hop, int flags);
+int leaf_backward_mix_f32(const void* x, const int* mix_perm /*[B]*/, const float* mix_lam /*[B]*/, int B, int T,
+                          const float* kernel, const float* pool_w, const float* pool_b,
+                          const float* alpha, const float* delta, const float* root, const float* ema_w,
+                          int F, int K, int hop, int flags, const float* grad_out,
+                          const float* pooled_raw /* from leaf_forward_save_mix_f32, or NULL = recompute */,
+                          float* g_kernel, float* g_pool_w, float* g_pool_b,
+                          float* g_alpha, float* g_delta, float* g_root, float* g_ema_w,
+                          float* g_x /* must be NULL */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Stage entry points (each is one reference module's forward; they are what the sub-modules of
  * leaf_pytorch_amd.Leaf call when used on their own, and what the parity tests probe).
  */

@@ -95,6 +95,16 @@ _SIGNATURES = {
     "leaf_forward_prepared_f32": (ctypes.c_int, [_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
                                   + [_f32p] * 5 + [ctypes.c_int] * 4
                                   + [_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # waveform mixup: x, mix_perm, mix_lam in front of the plain entries' arguments
+    "leaf_mixup_f32": (ctypes.c_int, [_f32p, ctypes.c_int, ctypes.c_int, _f32p, _f32p, ctypes.c_int, _f32p, ctypes.c_void_p]),
+    "leaf_forward_mix_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "leaf_forward_mix_f32": (ctypes.c_int, [_f32p] * 3 + [ctypes.c_int, ctypes.c_int] + [_f32p] * 7 + [ctypes.c_int] * 5
+                             + [_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "leaf_forward_save_mix_f32": (ctypes.c_int, [_f32p] * 3 + [ctypes.c_int, ctypes.c_int] + [_f32p] * 7 + [ctypes.c_int] * 5
+                                  + [_f32p, _f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "leaf_backward_mix_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "leaf_backward_mix_f32": (ctypes.c_int, [_f32p] * 3 + [ctypes.c_int, ctypes.c_int] + [_f32p] * 7 + [ctypes.c_int] * 4 + [_f32p] * 10
+                              + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -453,6 +463,155 @@ def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, 
                                    _ptr(ws), ws.numel(), stream_ptr(dev))
     check(rc, "leaf_backward_f32")
     return g_kernel, g_pw.reshape(pool_w.shape), g_pb, g_pc[0], g_pc[1], g_pc[2], g_pc[3], g_x
+
+
+def mix_args(perm, lam, B: int, device: torch.device):
+    """The two mixup buffers of a call, as the C ABI reads them: ``perm`` (any integer tensor or sequence of length B) as int32 and
+    ``lam`` (length B) as float32, both on ``device``.  A ``perm`` that arrives on the CPU is validated there: an index outside
+    [0, B) raises ValueError before anything is launched (a device-side ``perm`` is clamped by the kernels instead: checking it
+    would be a synchronisation per step)."""
+    if not isinstance(perm, torch.Tensor):
+        perm = torch.as_tensor(perm)
+    if perm.dtype.is_floating_point or perm.dtype.is_complex or perm.dtype == torch.bool:
+        raise TypeError(f"perm must be an integer tensor or sequence, got {perm.dtype}")
+    perm = perm.reshape(-1)
+    if perm.numel() != B:
+        raise ValueError(f"perm has {perm.numel()} entries, expected one per clip ({B})")
+    if perm.device.type == "cpu" and B and (int(perm.min()) < 0 or int(perm.max()) >= B):
+        raise ValueError(f"perm holds an index outside [0, {B})")
+    if not isinstance(lam, torch.Tensor):
+        lam = torch.as_tensor(lam, dtype=torch.float32)
+    lam = lam.reshape(-1)
+    if lam.numel() != B:
+        raise ValueError(f"lam has {lam.numel()} entries, expected one per clip ({B})")
+    if lam.dtype != torch.float32:
+        raise RuntimeError(f"lam must be float32, got {lam.dtype}")
+    return (perm.detach().to(device=device, dtype=torch.int32).contiguous(), lam.detach().to(device=device).contiguous())
+
+
+def _mix_x(x: torch.Tensor, who: str) -> torch.Tensor:
+    require_hip(x, who)
+    if x.dim() == 3 and x.shape[1] == 1:
+        x2 = x[:, 0, :]
+    elif x.dim() == 2:
+        x2 = x
+    else:
+        raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
+    if x2.dtype not in (torch.float32, torch.int16):
+        raise RuntimeError(f"{who}: the mix is defined in float32 on a float32 or int16 (PCM) waveform, got {x2.dtype}")
+    return x2.detach().contiguous()
+
+
+def mixup(x: torch.Tensor, perm, lam) -> torch.Tensor:
+    """The mixed waveform itself (leaf_mixup_f32): x (B,1,T) or (B,T), float32 or int16 PCM (v / 32768) ->
+    float32 of the same shape, ``x * lam + x[perm] * (1 - lam)`` per clip with separately rounded fp32 operations."""
+    lib = load()
+    x2 = _mix_x(x, "mixup")
+    B, T = x2.shape
+    dev = x2.device
+    perm, lam = mix_args(perm, lam, B, dev)
+    out = torch.empty((B, T), dtype=torch.float32, device=dev)
+    if B * T >= (1 << 31):
+        raise RuntimeError("mixup: a batch beyond one C-ABI call (B * T >= 2^31) cannot be mixed across its slices")
+    if B and T:
+        with torch.cuda.device(dev):
+            check(lib.leaf_mixup_f32(_ptr(x2), B, T, _ptr(perm), _ptr(lam), FLAG_X_PCM16 if x2.dtype == torch.int16 else 0, _ptr(out),
+                                     stream_ptr(dev)), "leaf_mixup_f32")
+    return out.reshape(x.shape)
+
+
+def leaf_forward_mix(x: torch.Tensor, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int,
+                     pcen: bool = True, log1p: bool = False, algo: int = ALGO_AUTO, save_raw: bool = False):
+    """``leaf_forward`` of the mixed batch ``x * lam + x[perm] * (1 - lam)`` without materialising it where the kernels mix in their
+    loads (leaf_forward_mix_f32 / leaf_forward_save_mix_f32).  x float32 or int16 PCM; bfloat16 raises."""
+    lib = load()
+    x2 = _mix_x(x, "leaf_forward_mix")
+    dev = x2.device
+    B, T = x2.shape
+    perm, lam = mix_args(perm, lam, B, dev)
+    flags = FLAG_X_PCM16 if x2.dtype == torch.int16 else 0
+    F = kernel.shape[0]
+    kernel = _dev_f32(kernel, "kernel", dev)
+    pool_w = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
+    pool_b = _dev_f32(pool_b, "pool_b", dev)
+    if pcen:
+        flags |= FLAG_PCEN
+        alpha, delta, root, ema_w = (_dev_f32(t, n, dev) for t, n in
+                                     ((alpha, "alpha"), (delta, "delta"), (root, "root"), (ema_w, "ema_w")))
+    else:
+        alpha = delta = root = ema_w = None
+        if log1p:
+            flags |= FLAG_LOG1P
+    TP = lib.leaf_num_frames(T, K, hop)
+    if TP < 1:
+        raise RuntimeError(f"bad shape B={B} T={T} K={K} hop={hop}")
+    if (algo & 0xff) not in (ALGO_AUTO, ALGO_STAGED, ALGO_MFMA, ALGO_FFT, ALGO_FFT_WG, ALGO_FFT_SMALL):
+        raise RuntimeError(f"unknown algorithm selector {algo & 0xff}")
+    out = torch.empty((B, F, TP), dtype=torch.float32, device=dev)
+    raw = torch.empty((B, F, TP), dtype=torch.float32, device=dev) if save_raw else None
+    if B == 0:
+        return (out, raw) if save_raw else out
+    if B * T >= (1 << 31):
+        raise RuntimeError("leaf_forward_mix: a batch beyond one C-ABI call (B * T >= 2^31) cannot be mixed across its slices")
+    with torch.cuda.device(dev):
+        ws = workspace(lib.leaf_forward_mix_workspace_bytes(B, T, F, K, hop, algo), dev)
+        if save_raw:
+            rc = lib.leaf_forward_save_mix_f32(_ptr(x2), _ptr(perm), _ptr(lam), B, T, _ptr(kernel), _ptr(pool_w), _ptr(pool_b),
+                                               _ptr(alpha), _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, algo, _ptr(out),
+                                               _ptr(raw), _ptr(ws), ws.numel(), stream_ptr(dev))
+            check(rc, "leaf_forward_save_mix_f32")
+            return out, raw
+        rc = lib.leaf_forward_mix_f32(_ptr(x2), _ptr(perm), _ptr(lam), B, T, _ptr(kernel), _ptr(pool_w), _ptr(pool_b), _ptr(alpha),
+                                      _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, algo, _ptr(out), _ptr(ws), ws.numel(),
+                                      stream_ptr(dev))
+    check(rc, "leaf_forward_mix_f32")
+    return out
+
+
+def leaf_backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, grad_out: torch.Tensor,
+                      pcen: bool = True, staged: bool = False, pooled_raw: Optional[torch.Tensor] = None, mfma: bool = False,
+                      full_transforms: bool = False, strict_band_classes: bool = False, log1p: bool = False):
+    """Parameter gradients of ``leaf_forward_mix`` (leaf_backward_mix_f32): the seven of ``leaf_backward`` and None for dL/dx,
+    which a mixed call does not have."""
+    lib = load()
+    x2 = _mix_x(x, "leaf_backward_mix")
+    dev = x2.device
+    B, T = x2.shape
+    perm, lam = mix_args(perm, lam, B, dev)
+    F = kernel.shape[0]
+    kernel = _dev_f32(kernel, "kernel", dev)
+    pw = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
+    pb = _dev_f32(pool_b, "pool_b", dev)
+    go = _dev_f32(grad_out, "grad_out", dev)
+    TP = lib.leaf_num_frames(T, K, hop)
+    if tuple(go.shape) != (B, F, TP):
+        raise RuntimeError(f"grad_out has shape {tuple(go.shape)}, expected {(B, F, TP)}")
+    g_kernel = torch.empty_like(kernel)
+    g_pw, g_pb = torch.empty_like(pw), torch.empty_like(pb)
+    if pcen:
+        alpha, delta, root, ema_w = (_dev_f32(t, "pcen param", dev) for t in (alpha, delta, root, ema_w))
+        g_pc = [torch.empty(F, dtype=torch.float32, device=dev) for _ in range(4)]
+    else:
+        alpha = delta = root = ema_w = None
+        g_pc = [None] * 4
+    if B == 0:
+        for g in (g_kernel, g_pw, g_pb, *g_pc):
+            if g is not None:
+                g.zero_()
+        return g_kernel, g_pw.reshape(pool_w.shape), g_pb, g_pc[0], g_pc[1], g_pc[2], g_pc[3], None
+    if B * T >= (1 << 31):
+        raise RuntimeError("leaf_backward_mix: a batch beyond one C-ABI call (B * T >= 2^31) cannot be mixed across its slices")
+    flags = ((FLAG_PCEN if pcen else 0) | (FLAG_BWD_STAGED if staged else 0) | (FLAG_BWD_MFMA if mfma else 0) |
+             (FLAG_BWD_FULL_TRANSFORMS if full_transforms else 0) | (FLAG_BWD_STRICT_BAND_CLASSES if strict_band_classes else 0) |
+             (FLAG_LOG1P if log1p and not pcen else 0) | (FLAG_X_PCM16 if x2.dtype == torch.int16 else 0))
+    with torch.cuda.device(dev):
+        ws = workspace(lib.leaf_backward_mix_workspace_bytes(B, T, F, K, hop, flags), dev)
+        rc = lib.leaf_backward_mix_f32(_ptr(x2), _ptr(perm), _ptr(lam), B, T, _ptr(kernel), _ptr(pw), _ptr(pb), _ptr(alpha),
+                                       _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, _ptr(go), _ptr(pooled_raw),
+                                       _ptr(g_kernel), _ptr(g_pw), _ptr(g_pb), _ptr(g_pc[0]), _ptr(g_pc[1]), _ptr(g_pc[2]),
+                                       _ptr(g_pc[3]), None, _ptr(ws), ws.numel(), stream_ptr(dev))
+    check(rc, "leaf_backward_mix_f32")
+    return g_kernel, g_pw.reshape(pool_w.shape), g_pb, g_pc[0], g_pc[1], g_pc[2], g_pc[3], None
 
 
 def leaf_forward_profiled(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, pcen: bool = True,

@@ -118,6 +118,50 @@ def _register_python_side() -> None:
         return (gx if need_dx else None, gk, gpw, gpb, *pc, None, None, None, None)
 
     torch.library.register_autograd("leaf_amd::forward_train", backward, setup_context=setup_context)
+
+    # ---- waveform mixup: the same three ops with (perm, lam) behind x; parameter gradients only
+    @torch.library.register_fake("leaf_amd::forward_mix")
+    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo):
+        return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)), dtype=torch.float32)
+
+    @torch.library.register_fake("leaf_amd::forward_train_mix")
+    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p=False):
+        shape = (x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop))
+        return x.new_empty(shape, dtype=torch.float32), x.new_empty(shape, dtype=torch.float32)
+
+    @torch.library.register_fake("leaf_amd::backward_mix")
+    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out, pooled_raw, flags):
+        pc = kernel.shape[0] if alpha is not None else 0
+        e = lambda *s: kernel.new_empty(s)
+        return [torch.empty_like(kernel), torch.empty_like(pool_w), torch.empty_like(pool_b), e(pc), e(pc), e(pc), e(pc)]
+
+    def setup_context_mix(ctx, inputs, output):
+        x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p = inputs
+        _, raw = output
+        ctx.pcen = alpha is not None
+        ctx.log1p = bool(log1p) and not ctx.pcen
+        ctx.geom = (K, hop)
+        ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)
+        ctx.strict = bool(algo & _native.ALGO_STRICT_BAND_CLASSES)
+        ctx.save_for_backward(x, perm, lam, kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if ctx.pcen else []))
+
+    def backward_mix(ctx, grad_out, grad_raw):
+        K, hop = ctx.geom
+        saved = ctx.saved_tensors
+        x, perm, lam, kernel, pool_w, pool_b, raw = saved[:7]
+        alpha, delta, root, ema_w = saved[7:] if ctx.pcen else (None,) * 4
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+            raise RuntimeError("leaf_amd::forward_train_mix has no gradient for x or lam: the mixed waveform is data "
+                               "(dL/dx under mixup is a scatter over perm and is not built)")
+        gk, gpw, gpb, ga, gd, gr, gw = torch.ops.leaf_amd.backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K,
+                                                                       hop, grad_out.contiguous(), raw,
+                                                                       (_native.FLAG_BWD_FULL_TRANSFORMS if ctx.full else 0) |
+                                                                       (_native.FLAG_BWD_STRICT_BAND_CLASSES if ctx.strict else 0) |
+                                                                       (_native.FLAG_LOG1P if ctx.log1p else 0))
+        pc = (ga, gd, gr, gw) if ctx.pcen else (None,) * 4
+        return (None, None, None, gk, gpw, gpb, *pc, None, None, None, None)
+
+    torch.library.register_autograd("leaf_amd::forward_train_mix", backward_mix, setup_context=setup_context_mix)
     from . import _second_order
     _second_order.register()                  # gradients of gradients: leaf_amd::backward's own autograd formula
 
@@ -130,3 +174,13 @@ def forward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: i
 def forward_train(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int,
                   algo: int = _native.ALGO_AUTO, log1p: bool = False) -> torch.Tensor:
     return torch.ops.leaf_amd.forward_train(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p)[0]
+
+
+def forward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, log1p: bool = False,
+                algo: int = _native.ALGO_AUTO) -> torch.Tensor:
+    return torch.ops.leaf_amd.forward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo)
+
+
+def forward_train_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int,
+                      algo: int = _native.ALGO_AUTO, log1p: bool = False) -> torch.Tensor:
+    return torch.ops.leaf_amd.forward_train_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p)[0]

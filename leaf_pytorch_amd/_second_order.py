@@ -122,5 +122,15 @@ def backward(ctx, grads):
     return gx, gk, gpw, gpb, *gpc, None, None, ggo, None, None, None
 
 
+def _setup_context_mix(ctx, inputs, output):
+    pass
+
+
+def _backward_mix(ctx, *grads):
+    raise RuntimeError("gradients of gradients through Leaf.forward_mixup are not supported: second order needs the mixed batch "
+                       "itself (create_graph=True: mix with transforms.Mixup / _native.mixup and call forward on the result)")
+
+
 def register() -> None:
     torch.library.register_autograd("leaf_amd::backward", backward, setup_context=setup_context)
+    torch.library.register_autograd("leaf_amd::backward_mix", _backward_mix, setup_context=_setup_context_mix)

@@ -21,4 +21,14 @@ const void* leaf_inst_fft(int sk, int g2, int rs, int bwd) {
     return reinterpret_cast<const void*>(fn);
 }
 
+// the static odd windows for a mixed call (waveform mixup in the block load)
+const void* leaf_inst_fft_mix(int sk, int bwd) {
+    using K = void (*)(const FftParams);
+    K fn = nullptr;
+    if (sk == 401) fn = bwd ? leaf_fft_kernel<401, 160, 1, 1, 1, true> : leaf_fft_kernel<401, 160, 1, 1, 0, true>;
+    else if (sk == 801) fn = bwd ? leaf_fft_kernel<801, 320, 1, 1, 1, true> : leaf_fft_kernel<801, 320, 1, 1, 0, true>;
+    else if (sk == 201) fn = bwd ? leaf_fft_kernel<201, 80, 1, 1, 1, true> : leaf_fft_kernel<201, 80, 1, 1, 0, true>;
+    return reinterpret_cast<const void*>(fn);
+}
+
 unsigned leaf_layout_fft() { return leaf_layout_hash_fft(); }                // parameter-struct layout this unit was compiled with (leaf_inst.hpp)

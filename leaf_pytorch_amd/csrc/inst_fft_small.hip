@@ -12,4 +12,12 @@ const void* leaf_inst_fft_small(int sk, bool split) {
     return reinterpret_cast<const void*>(fn);
 }
 
+// ... for a mixed call (waveform mixup in the block load)
+const void* leaf_inst_fft_small_mix(int sk, bool split) {
+    void (*fn)(const SmallParams) = nullptr;
+    if (sk == 401) fn = split ? leaf_fft_small_kernel<401, 160, true, true> : leaf_fft_small_kernel<401, 160, false, true>;
+    else if (sk == 201) fn = split ? leaf_fft_small_kernel<201, 80, true, true> : leaf_fft_small_kernel<201, 80, false, true>;
+    return reinterpret_cast<const void*>(fn);
+}
+
 unsigned leaf_layout_fft_small() { return leaf_layout_hash_small(); }                // parameter-struct layout this unit was compiled with (leaf_inst.hpp)

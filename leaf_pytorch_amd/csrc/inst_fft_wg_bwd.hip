@@ -13,6 +13,16 @@ const void* leaf_inst_fft_wg_bwd(int sk) {
     return reinterpret_cast<const void*>(fn);
 }
 
+// ... for a mixed call (waveform mixup in the block load)
+const void* leaf_inst_fft_wg_bwd_mix(int sk) {
+    using K = void (*)(const FftParams);
+    K fn = nullptr;
+    if (sk == 401) fn = leaf_fft_wg_bwd_kernel<401, 160, 12, false, true>;
+    else if (sk == 801) fn = leaf_fft_wg_bwd_kernel<801, 320, 12, false, true>;
+    else if (sk == 201) fn = leaf_fft_wg_bwd_kernel<201, 80, 12, false, true>;
+    return reinterpret_cast<const void*>(fn);
+}
+
 const void* leaf_inst_fft_blk_bwd_dx(int sk) {
     using K = void (*)(const FftParams);
     K fn = nullptr;

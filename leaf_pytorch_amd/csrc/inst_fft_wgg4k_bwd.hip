@@ -15,6 +15,23 @@ const void* leaf_inst_fft_wgg4k_bwd(int ni2) {
     return reinterpret_cast<const void*>(fn);
 }
 
+// ... for a mixed call (waveform mixup in the block load)
+const void* leaf_inst_fft_wgg4k_bwd_mix(int ni2) {
+    using K = void (*)(const FftParams);
+    K fn = nullptr;
+    switch (ni2) {
+        case 10: fn = leaf_fft_wgg4k_bwd_kernel<12, 10, false, false, true>; break;
+        case 13: fn = leaf_fft_wgg4k_bwd_kernel<12, 13, false, false, true>; break;
+        case 17: fn = leaf_fft_wgg4k_bwd_kernel<12, 17, false, false, true>; break;
+    }
+    return reinterpret_cast<const void*>(fn);
+}
+const void* leaf_inst_fft_wg4k_bwd_mix() {
+    using K = void (*)(const FftParams);
+    K fn = leaf_fft_wgg4k_bwd_kernel<LEAF_4K_BWD_NW, 7, true, false, true>;
+    return reinterpret_cast<const void*>(fn);
+}
+
 // the static 32 kHz geometry (K = 801, hop = 320)
 const void* leaf_inst_fft_wg4k_bwd() {
     using K = void (*)(const FftParams);

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <math.h>
 #include <algorithm>
+#include <type_traits>
 #include "leaf_hip.h"
 
 namespace {
@@ -34,6 +35,56 @@ __device__ __forceinline__ float io_load(const void* p, size_t i, int st) {
     if (st == kSamplePcm16) return pcm16_widen(static_cast<const short*>(p)[i]);
     return static_cast<const float*>(p)[i];
 }
+// Waveform mixup in the load (the reference's training loop, utilities/data/mixup.py: x' = x lam + x[perm] (1 - lam) per clip): a
+// mixed sample is rn(rn(x[b][n] lam) + rn(x[perm[b]][n] om)) with om = rn(1 - lam), three separately rounded fp32 operations -- bit for
+// bit what the torch expression gives.  The library is compiled with contraction on, so the helper switches it off for its own body
+// (a fused multiply-add would round once where the definition rounds twice).  `clip` / `partner`: element offsets of the two rows in
+// `x`; `st`: kSampleF32 or kSamplePcm16 (the widened sample v / 32768 is exact; bfloat16 is not mixed).
+__device__ __forceinline__ float mix_load(const void* x, size_t clip, size_t partner, size_t i, float lam, float om, int st) {
+#pragma clang fp contract(off)
+    const float a = io_load(x, clip + i, st) * lam;
+    const float b = io_load(x, partner + i, st) * om;
+    return a + b;
+}
+// The per-clip constants of mix_load, read once per (wave, block) where the block's clip index is decoded: wave-uniform, so the
+// partner's row offset and the two weights live in SGPRs.  The partner index is clamped into [0, B): a device-side `perm` with an
+// out-of-range entry reads a wrong clip, never out of bounds.
+struct MixClip {
+    size_t partner;         // element offset of row perm[b]
+    float lam, om;
+};
+__device__ __forceinline__ MixClip mix_clip(const int* perm, const float* lam, int b, int B, int T) {
+#pragma clang fp contract(off)
+    const int bu = __builtin_amdgcn_readfirstlane(b);
+    const int pb = __builtin_amdgcn_readfirstlane(min(max(perm[bu], 0), B - 1));
+    const float l = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(lam[bu])));
+    return MixClip{(size_t)pb * T, l, 1.0f - l};
+}
+// The kernels' load sites: mixed sample n of the clip at element offset `clip`, zero outside [0, T) for both partners (halo and padding
+// as without the mix).  Every lane loads (index clamped into the clip, value zeroed outside it): the loads of a block stay in flight
+// together.  ST is a compile-time sample type: the sites branch once per block on the wave-uniform type, not per sample.
+template <int ST>
+__device__ __forceinline__ float mix_sample(const void* x, size_t clip, const MixClip& mc, int n, int T) {
+    const float w = mix_load(x, clip, mc.partner, (size_t)min(max(n, 0), T - 1), mc.lam, mc.om, ST);
+    return (n >= 0 && n < T) ? w : 0.0f;
+}
+#ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
+// The stand-alone mix (leaf_mixup_f32): out[b][n] = the mixed sample, fp32, read two rows / write one.  Grid B * tiles, tiles = ceil(T / 1024):
+// a workgroup mixes 1024 samples of one clip.
+__global__ __launch_bounds__(256) void mixup_kernel(const void* __restrict__ x, int st, int B, int T, int tiles, const int* __restrict__ perm,
+                                                    const float* __restrict__ lam, float* __restrict__ out) {
+    const int b = blockIdx.x / tiles;
+    const MixClip mc = mix_clip(perm, lam, b, B, T);
+    const size_t row = (size_t)b * T;
+    const int n0 = (blockIdx.x - b * tiles) * 1024 + threadIdx.x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int n = n0 + 256 * j;
+        if (n < T) out[row + n] = st == kSamplePcm16 ? mix_load(x, row, mc.partner, n, mc.lam, mc.om, kSamplePcm16)
+                                                     : mix_load(x, row, mc.partner, n, mc.lam, mc.om, kSampleF32);
+    }
+}
+#endif
 __device__ __forceinline__ void io_store(void* p, size_t i, int bf16, float v) {
     if (bf16) static_cast<unsigned short*>(p)[i] = bf16_round(v);
     else static_cast<float*>(p)[i] = v;

@@ -603,6 +603,9 @@ struct FftParams {
     BandParams band;       // band-limited filter tasks (rec == NULL: off)
     const float2* spec0;   // [workgroups][kWgRingFloat2]: the half spectrum of every workgroup's FIRST block, computed by the table
                            // launch on CUs it leaves idle (fft_prep_band_kernel); NULL: the kernel transforms it itself
+    // Waveform mixup in the load (leaf_common.hpp: mix_load), the kernels with a fused mix only; mix_lam == NULL: off
+    const int* mix_perm;   // [B] partner clip of every clip (clamped into [0, B) on the device)
+    const float* mix_lam;  // [B] weight of the clip itself; its partner gets 1 - lam
 };
 
 constexpr unsigned leaf_layout_hash_fft() {                              // see leaf_layout_hash_fused (leaf_fused.hpp)
@@ -612,6 +615,7 @@ constexpr unsigned leaf_layout_hash_fft() {                              // see 
     h = leaf_mix(h, sizeof(FinParams)); h = leaf_mix(h, offsetof(FinParams, geo)); h = leaf_mix(h, offsetof(FinParams, out));
     h = leaf_mix(h, offsetof(FinParams, lds_row0)); h = leaf_mix(h, sizeof(OwnedClips)); h = leaf_mix(h, sizeof(SlotGeom));
     h = leaf_mix(h, offsetof(FftParams, band)); h = leaf_mix(h, sizeof(BandParams)); h = leaf_mix(h, offsetof(BandParams, n_edge));
+    h = leaf_mix(h, offsetof(FftParams, mix_perm)); h = leaf_mix(h, offsetof(FftParams, mix_lam));
     return h;
 }
 
@@ -636,8 +640,11 @@ constexpr unsigned leaf_layout_hash_fft() {                              // see 
 // to request the NEXT filter's spectrum during this filter's pooling -- which hides the L2 latency that otherwise
 // stalls every filter (18 % of the kernel, tools/ablate_fft.py).  RS = 0 (even K: one unpaired tap breaks the
 // symmetry): complex spectrum, loaded at the multiply.
-template <int SK, int SHOP, int G2, int RS, int BWD>
+// MIX: the instances for a mixed call (waveform mixup in the block load, leaf_common.hpp; static odd windows); the unmixed instances
+// carry no trace of it (this kernel sits at the register limit)
+template <int SK, int SHOP, int G2, int RS, int BWD, bool MIX = false>
 __global__ __launch_bounds__(kFftWaves * 64, 2) void leaf_fft_kernel(const FftParams p) {
+    static_assert(!MIX || (SK > 0 && RS == 1), "mixed loads: the static odd-window instances (no time-domain re-reads of x)");
     extern __shared__ __attribute__((aligned(16))) float fsm2[];
     float2* twl = reinterpret_cast<float2*>(fsm2);                       // [32][64]
     float2* twh = twl + 32 * 64;                                          // [32][2]
@@ -717,6 +724,25 @@ __global__ __launch_bounds__(kFftWaves * 64, 2) void leaf_fft_kernel(const FftPa
             // 2-byte loads are in flight together instead of one exec-masked load at a time (-9 % on 10 s clips)
             // 16-bit PCM shares the loop (this kernel sits at the register limit: a third loop put the fp32 path into scratch): the
             // conversion is chosen per sample by a wave-uniform select between the shift and sign-extend / convert / scale
+            if constexpr (MIX) {                                         // the clip mixed with its partner; a loop per sample type (fp32 / 16-bit PCM)
+                const MixClip mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
+                const size_t row = (size_t)b * p.T;
+                if (p.io_bf16 == kSamplePcm16) {
+#pragma unroll
+                    for (int r = 0; r < 32; ++r) {
+                        const int i = 64 * r + lane;
+                        are[r] = mix_sample<kSamplePcm16>(p.x, row, mc, n_c - p.padL + ((i + p.rot) & (kFftN - 1)), p.T);
+                        aim[r] = 0.0f;
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 32; ++r) {
+                        const int i = 64 * r + lane;
+                        are[r] = mix_sample<kSampleF32>(p.x, row, mc, n_c - p.padL + ((i + p.rot) & (kFftN - 1)), p.T);
+                        aim[r] = 0.0f;
+                    }
+                }
+            } else
             if (p.io_bf16) {
                 const bool pcm = p.io_bf16 == kSamplePcm16;
 #pragma unroll

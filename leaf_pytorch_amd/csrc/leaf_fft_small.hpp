@@ -54,11 +54,14 @@ struct SmallParams {
     // [B][F] pairs (epoch, value bits) in the workspace; `epoch` is this launch's 64-bit ticket (host counter from a random seed)
     unsigned long long epoch;
     unsigned long long* carry;
+    // Waveform mixup in the load (leaf_common.hpp: mix_load); mix_lam == NULL: off
+    const int* mix_perm;    // [B]
+    const float* mix_lam;   // [B]
 };
 
 constexpr unsigned leaf_layout_hash_small() {
-    return leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_layout_hash_fft(), sizeof(SmallParams)), offsetof(SmallParams, fin)), offsetof(SmallParams, ring)),
-                    offsetof(SmallParams, carry));
+    return leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_layout_hash_fft(), sizeof(SmallParams)), offsetof(SmallParams, fin)), offsetof(SmallParams, ring)),
+                             offsetof(SmallParams, carry)), offsetof(SmallParams, mix_lam));
 }
 
 // dynamic LDS: twiddles | R (the taps first) | full transposition scratch of every wave | frame sums | finalize coefficients |
@@ -103,7 +106,8 @@ __device__ __forceinline__ void wave_affine_scan(float& a, float& b) {
 // state at the seam travels through the workspace: the first half publishes it (value, then this launch's 64-bit ticket with
 // release), the second half's finalize wave scans its frames' recurrence first and waits for the ticket only to apply the state.  First halves have the lower workgroup ids: they are dispatched
 // first and wait for nothing, so the wait always ends.
-template <int SK, int SHOP, bool SPLIT = false>
+// MIX: the instances for a mixed call (waveform mixup in the block load, leaf_common.hpp); the unmixed instances carry no trace of it
+template <int SK, int SHOP, bool SPLIT = false, bool MIX = false>
 __global__ __launch_bounds__((SPLIT ? kSmallSplitWaves : kSmallWaves) * 64, SPLIT ? 2 : 3) void leaf_fft_small_kernel(const SmallParams p) {
     constexpr int NW = SPLIT ? kSmallSplitWaves : kSmallWaves;
     constexpr int SCRF = kWgScrFloats;
@@ -154,8 +158,28 @@ __global__ __launch_bounds__((SPLIT ? kSmallSplitWaves : kSmallWaves) * 64, SPLI
     const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
     const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
     float zre[32], zim[32];             // a block wave's samples -> spectrum (kept across the barrier) -> filter outputs
+    MixClip mc{};                                                          // waveform mixup in the load (leaf_common.hpp): one clip per workgroup
+    if constexpr (MIX) mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
     auto load_block = [&](int c, int lane_) {                             // block c, rotated left by padL samples
         const int n_c = c * LS;
+        if constexpr (MIX) {                                              // mixed with the partner clip: a loop per sample type (fp32 / 16-bit PCM)
+            const size_t row = (size_t)b * p.T;
+            if (p.io_bf16 == kSamplePcm16) {
+#pragma unroll
+                for (int r = 0; r < 32; ++r) {
+                    const int i = 64 * r + lane_;
+                    zre[r] = mix_sample<kSamplePcm16>(p.x, row, mc, n_c - PADL + ((i + PADL) & (kFftN - 1)), p.T);
+                    zim[r] = 0.0f;
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 32; ++r) {
+                    const int i = 64 * r + lane_;
+                    zre[r] = mix_sample<kSampleF32>(p.x, row, mc, n_c - PADL + ((i + PADL) & (kFftN - 1)), p.T);
+                    zim[r] = 0.0f;
+                }
+            }
+        } else
         if (p.io_bf16) {
             const bool pcm = p.io_bf16 == kSamplePcm16;     // 16-bit PCM shares the loop: a wave-uniform select of the conversion
 #pragma unroll

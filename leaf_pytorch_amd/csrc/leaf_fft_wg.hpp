@@ -1102,7 +1102,27 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
                 float are[32], aim[32];
                 const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
                 const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
-                if (p.io_bf16) {
+                if (p.mix_lam) {
+                    // waveform mixup in the load (leaf_common.hpp): the block's clip mixed with its partner, weights and partner row
+                    // read once per block; a loop per sample type (fp32 / 16-bit PCM)
+                    const MixClip mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
+                    const size_t row = (size_t)b * p.T;
+                    if (p.io_bf16 == kSamplePcm16) {
+#pragma unroll
+                        for (int r = 0; r < 32; ++r) {
+                            const int i = 64 * r + lane;
+                            are[r] = mix_sample<kSamplePcm16>(p.x, row, mc, n_c - PADL + ((i + PADL) & (kFftN - 1)), p.T);
+                            aim[r] = 0.0f;
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 32; ++r) {
+                            const int i = 64 * r + lane;
+                            are[r] = mix_sample<kSampleF32>(p.x, row, mc, n_c - PADL + ((i + PADL) & (kFftN - 1)), p.T);
+                            aim[r] = 0.0f;
+                        }
+                    }
+                } else if (p.io_bf16) {
                     const bool pcm = p.io_bf16 == kSamplePcm16;     // 16-bit PCM shares the loop: a wave-uniform select of the conversion
 #pragma unroll
                     for (int r = 0; r < 32; ++r) {

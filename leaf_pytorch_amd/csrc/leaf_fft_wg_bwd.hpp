@@ -488,8 +488,10 @@ constexpr bool fft_wg_bwd_dx_half(int NW, int SK) {
 constexpr size_t fft_wg_bwd_dx_lds_bytes(int NW, int SK) {
     return fft_wg_bwd_lds_bytes_with(NW, SK, fft_wg_bwd_dx_half(NW, SK) ? kWgScrHalfFloats : kWgScrFloats) + (size_t)2 * kWgRingFloat2 * 8;
 }
-template <int SK, int SHOP, int NW, bool DX = false>
+// MIX: the instance for a mixed call (waveform mixup in the block load, leaf_common.hpp); the unmixed instances carry no trace of it
+template <int SK, int SHOP, int NW, bool DX = false, bool MIX = false>
 __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(const FftParams p) {
+    static_assert(!(MIX && DX), "a mixed call has no dL/dx");
     constexpr bool HALF = DX ? fft_wg_bwd_dx_half(NW, SK) : fft_wg_bwd_half(NW, SK);
     constexpr int SCRF = HALF ? kWgScrHalfFloats : kWgScrFloats;
     extern __shared__ __attribute__((aligned(16))) float wsm[];
@@ -578,6 +580,26 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
                 float are[32], aim[32];
                 const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
                 const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
+                if constexpr (MIX) {
+                    // waveform mixup in the load (leaf_common.hpp), as the forward; a loop per sample type (fp32 / 16-bit PCM)
+                    const MixClip mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
+                    const size_t row = (size_t)b * p.T;
+                    if (p.io_bf16 == kSamplePcm16) {
+#pragma unroll
+                        for (int r = 0; r < 32; ++r) {
+                            const int i = 64 * r + lane;
+                            are[r] = mix_sample<kSamplePcm16>(p.x, row, mc, n_c - PADL + ((i + PADL) & (kFftN - 1)), p.T);
+                            aim[r] = 0.0f;
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 32; ++r) {
+                            const int i = 64 * r + lane;
+                            are[r] = mix_sample<kSampleF32>(p.x, row, mc, n_c - PADL + ((i + PADL) & (kFftN - 1)), p.T);
+                            aim[r] = 0.0f;
+                        }
+                    }
+                } else
                 if (p.io_bf16) {                                          // 16-bit waveform, widened in the load (as the forward, leaf_fft_wg.hpp)
                     const bool pcm = p.io_bf16 == kSamplePcm16;     // 16-bit PCM shares the loop: a wave-uniform select of the conversion
 #pragma unroll

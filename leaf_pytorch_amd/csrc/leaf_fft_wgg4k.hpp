@@ -104,15 +104,37 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_kernel(c
                     }
                     return (n >= 0 && n < p.T) ? xb[n] : 0.0f;
                 };
-                float xre[32], xim[32];
+                // waveform mixup in the load (leaf_common.hpp): the block's clip mixed with its partner, weights and partner row read
+                // once per block; ST: the compile-time sample type of the loop (fp32 / 16-bit PCM)
+                MixClip mc{};
+                if (p.mix_lam) mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
+                auto load_mixed = [&](float (&v)[32], int odd, auto st) {
 #pragma unroll
-                for (int r = 0; r < 32; ++r) { xre[r] = sample(2 * (64 * r + lane)); xim[r] = 0.0f; }
+                    for (int r = 0; r < 32; ++r) {
+                        const int i = 2 * (64 * r + lane) + odd;
+                        v[r] = mix_sample<decltype(st)::value>(p.x, (size_t)b * p.T, mc, n_c - PADL + ((i + ROT) & (kFft4N - 1)), p.T);
+                    }
+                };
+                auto load_half = [&](float (&v)[32], int odd) {
+                    if (p.mix_lam) {
+                        if (p.io_bf16 == kSamplePcm16) load_mixed(v, odd, std::integral_constant<int, kSamplePcm16>{});
+                        else load_mixed(v, odd, std::integral_constant<int, kSampleF32>{});
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 32; ++r) v[r] = sample(2 * (64 * r + lane) + odd);
+                    }
+                };
+                float xre[32], xim[32];
+                load_half(xre, 0);
+#pragma unroll
+                for (int r = 0; r < 32; ++r) xim[r] = 0.0f;
                 fft2048w<true>(xre, xim, scr, scr_lds, twl, twh, lane);
                 wg_wait_ge(&q[3 + slot], gen * p.F);                      // the slot's previous readers are done
 #pragma unroll
                 for (int i = 0; i < 32; ++i) A[64 * brev5(i) + lane] = make_float2(xre[i], xim[i]);
+                load_half(xre, 1);
 #pragma unroll
-                for (int r = 0; r < 32; ++r) { xre[r] = sample(2 * (64 * r + lane) + 1); xim[r] = 0.0f; }
+                for (int r = 0; r < 32; ++r) xim[r] = 0.0f;
                 fft2048w<true>(xre, xim, scr, scr_lds, twl, twh, lane);
                 const float2 wl = tw4b[lane];
 #pragma unroll

@@ -159,8 +159,10 @@ __device__ __forceinline__ void wg4k_dx_finish(const FftParams& p, float2* S0, f
     }
 }
 
-template <int NW, int NI2, bool S801 = false, bool DX = false>
+// MIX: the instance for a mixed call (waveform mixup in the block load, leaf_common.hpp); the unmixed instances carry no trace of it
+template <int NW, int NI2, bool S801 = false, bool DX = false, bool MIX = false>
 __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kernel(const FftParams p) {
+    static_assert(!(MIX && DX), "a mixed call has no dL/dx");
     using gfp = const __attribute__((address_space(1))) float*;          // table pointers that stay `global` when made opaque
     using gf2p = const __attribute__((address_space(1))) v2f*;            // (a builtin vector: HIP's float2 class does not load through address spaces)
     static_assert(!DX || S801, "dL/dx on 4096-sample blocks: the static 32 kHz instance only");
@@ -260,15 +262,40 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
                     }
                     return (n >= 0 && n < p.T) ? xb[n] : 0.0f;
                 };
-                float xre[32], xim[32];
+                // waveform mixup in the load (leaf_common.hpp): the block's clip mixed with its partner, weights and partner row read
+                // once per block; ST: the compile-time sample type of the loop (fp32 / 16-bit PCM)
+                MixClip mc{};
+                if constexpr (MIX) mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
+                auto load_mixed = [&](float (&v)[32], int odd, auto st) {
 #pragma unroll
-                for (int r = 0; r < 32; ++r) { xre[r] = sample(2 * (64 * r + lane)); xim[r] = 0.0f; }
+                    for (int r = 0; r < 32; ++r) {
+                        const int i = 2 * (64 * r + lane) + odd;
+                        v[r] = mix_sample<decltype(st)::value>(p.x, (size_t)b * p.T, mc, n_c - PADL + ((i + ROT) & (kFft4N - 1)), p.T);
+                    }
+                };
+                auto load_half = [&](float (&v)[32], float (&vi)[32], int odd) {      // (MIX instances only)
+                    if (p.io_bf16 == kSamplePcm16) load_mixed(v, odd, std::integral_constant<int, kSamplePcm16>{});
+                    else load_mixed(v, odd, std::integral_constant<int, kSampleF32>{});
+#pragma unroll
+                    for (int r = 0; r < 32; ++r) vi[r] = 0.0f;
+                };
+                float xre[32], xim[32];
+                if constexpr (MIX) {
+                    load_half(xre, xim, 0);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 32; ++r) { xre[r] = sample(2 * (64 * r + lane)); xim[r] = 0.0f; }
+                }
                 fft2048w<HS>(xre, xim, scr, scr_lds, twl, twh, lane);
                 wg_wait_ge(&q[9 + slot], gen);                            // the slot's previous occupant has been released
 #pragma unroll
                 for (int i = 0; i < 32; ++i) A[64 * brev5(i) + lane] = make_float2(xre[i], xim[i]);
+                if constexpr (MIX) {
+                    load_half(xre, xim, 1);
+                } else {
 #pragma unroll
-                for (int r = 0; r < 32; ++r) { xre[r] = sample(2 * (64 * r + lane) + 1); xim[r] = 0.0f; }
+                    for (int r = 0; r < 32; ++r) { xre[r] = sample(2 * (64 * r + lane) + 1); xim[r] = 0.0f; }
+                }
                 fft2048w<HS>(xre, xim, scr, scr_lds, twl, twh, lane);
                 const float2 wl = tw4b[lane];
 #pragma unroll

@@ -32,6 +32,13 @@ const void* leaf_inst_fft_wgg4k_bwd(int ni2);                                  /
 const void* leaf_inst_fft_wg4k_bwd();                                          // leaf_fft_wgg4k_bwd_kernel<12, 7, true>: K = 801, hop = 320
 const void* leaf_inst_fft_wg4k_bwd_dx();                                       // leaf_fft_wgg4k_bwd_kernel<9, 7, true, true>: the same with dL/dx
 
+// the instances for a mixed call (waveform mixup in the block load, leaf_common.hpp); nullptr where there is none
+const void* leaf_inst_fft_mix(int sk, int bwd);                                // leaf_fft_kernel<SK, SHOP, 1, 1, BWD, true>: sk = 401 | 801 | 201
+const void* leaf_inst_fft_small_mix(int sk, bool split);                       // leaf_fft_small_kernel<SK, SHOP, SPLIT, true>
+const void* leaf_inst_fft_wg_bwd_mix(int sk);                                  // leaf_fft_wg_bwd_kernel<SK, SHOP, 12, false, true>
+const void* leaf_inst_fft_wgg4k_bwd_mix(int ni2);                              // leaf_fft_wgg4k_bwd_kernel<12, NI2, false, false, true>
+const void* leaf_inst_fft_wg4k_bwd_mix();                                      // leaf_fft_wgg4k_bwd_kernel<12, 7, true, false, true>
+
 // Parameter-struct layout fingerprint of each unit (leaf_layout_hash_* of leaf_fused.hpp / leaf_fft.hpp / ...): compared by
 // leaf_kernels.hip with the fingerprint of ITS copy of the structs before the first launch (inst_layouts_ok).
 unsigned leaf_layout_fft();

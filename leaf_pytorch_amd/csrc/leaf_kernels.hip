@@ -84,6 +84,15 @@ struct ReserveCus {
     }
     ~ReserveCus() { tl_reserved_cus = prev; tl_stream_finalize = prev_stream; tl_band_off = prev_band_off; tl_band_strict = prev_band_strict; }
 };
+// Waveform mixup of the current call (leaf_forward_mix_f32 / leaf_backward_mix_f32), set only while a kernel family that mixes in its
+// loads serves the call (the other families get a mixed copy, mixup_kernel); lam == NULL: off
+struct MixArgs { const int* perm; const float* lam; };
+thread_local MixArgs tl_mix{nullptr, nullptr};
+struct MixScope {
+    MixArgs prev;
+    explicit MixScope(MixArgs m) : prev(tl_mix) { tl_mix = m; }
+    ~MixScope() { tl_mix = prev; }
+};
 int device_cus();
 // CUs this call may fill: the device's count minus the call's reservation (at least one)
 int num_cus() { return std::max(1, device_cus() - tl_reserved_cus); }
@@ -512,6 +521,12 @@ FftKernel pick_fft_kernel(const FftPlan& fp, int K, int hop, bool bwd) {
     return as_fft_kernel(leaf_inst_fft(0, fp.g_bufs == 2 ? 1 : 0, (K & 1) ? 1 : 2, bwd ? 1 : 0));
 }
 
+// the MIX instances (waveform mixup in the block load): the static odd windows only; nullptr elsewhere
+FftKernel pick_fft_kernel_mix(const FftPlan& fp, int K, int hop, bool bwd) {
+    const bool stat = fp.ok && fft_static_geometry(K, hop) && fp.g_bufs == 2 && !LEAF_FFT_FORCE_GENERIC;
+    return stat && (K & 1) ? as_fft_kernel(leaf_inst_fft_mix(K, bwd ? 1 : 0)) : nullptr;
+}
+
 // Even K (real-spectrum form): the unpaired taps live behind the real spectra, in the second half of the float2 slab that
 // the (retired) complex-spectrum layout sized: [F][2048] floats of spectra, then [F][2] floats.  Odd K: none.
 float* fft_lone_taps(float* tables, int F, int K) { return (K & 1) ? nullptr : tables + (size_t)F * kFftN; }
@@ -669,7 +684,7 @@ const char* leaf_status_string(int status) {
         case LEAF_ERR_LAUNCH: return "HIP kernel launch failed";
         case LEAF_ERR_NO_DEVICE: return "no usable gfx950 device";
         case LEAF_ERR_ALIGNMENT: return "buffer not 4-byte aligned (2-byte for bfloat16 and 16-bit PCM buffers; 16-byte for workspace and tables)";
-        case LEAF_ERR_UNSUPPORTED: return "combination not supported (bfloat16 I/O and 16-bit PCM input (LEAF_FLAG_X_PCM16) have no staged forward: use float32 buffers; LEAF_FLAG_X_PCM16 excludes LEAF_FLAG_IO_BF16 and has no dL/dx (g_x must be NULL); LEAF_FLAG_PEAKNORM needs an overlap-save path and has no backward)";
+        case LEAF_ERR_UNSUPPORTED: return "combination not supported (bfloat16 I/O and 16-bit PCM input (LEAF_FLAG_X_PCM16) have no staged forward: use float32 buffers; LEAF_FLAG_X_PCM16 excludes LEAF_FLAG_IO_BF16 and has no dL/dx (g_x must be NULL); the waveform-mixup entries (leaf_*_mix_f32) take neither LEAF_FLAG_IO_BF16 nor LEAF_FLAG_PEAKNORM nor g_x; LEAF_FLAG_PEAKNORM needs an overlap-save path and has no backward)";
     }
     return "unknown status";
 }
@@ -1009,7 +1024,7 @@ static int fft_forward(const FftPlan& fp, const void* x, int xtype, int B, int T
             size_t prep_dyn = 0;
             // (16-bit PCM: the table launch reads fp32 and bf16 only -- a third sample type in its first-block loads cost the fp32 path
             // 0.9 us of the table launch at cfg1 -- so the main kernel transforms its first blocks itself: the same bits)
-            if (LEAF_WG_SPEC0 && !spec0_off && !tables_ready && main_grid <= kMaxCusForSpec0 && wl.nw <= 12 && xtype != kSamplePcm16) {
+            if (LEAF_WG_SPEC0 && !spec0_off && !tables_ready && main_grid <= kMaxCusForSpec0 && wl.nw <= 12 && xtype != kSamplePcm16 && !tl_mix.lam) {   // (a mixed call likewise: the table launch does not mix)
                 ba.x = x; ba.io_bf16 = xtype; ba.B = B; ba.nblk = fp.nblk; ba.G = main_grid;
                 ba.spec0 = reinterpret_cast<float2*>(dyn + bl.spec0);
                 spec0 = ba.spec0;
@@ -1049,9 +1064,11 @@ static int fft_forward(const FftPlan& fp, const void* x, int xtype, int B, int T
         FftWgLaunch wl = pick_fft_wg_kernel(K, hop);
         static const bool force_generic = [] { const char* e = tools_env("LEAF_WG_GENERIC"); return e && atoi(e) != 0; }();   // tools only
         if (!wl.fn || force_generic) {                        // run-time geometry (any other window, odd or even)
+            if (tl_mix.lam) return LEAF_ERR_BAD_ALGO;         // (these kernels do not mix in their loads: mix_fused_forward sends them a mixed copy)
             wl = pick_fft_wgg_kernel(fp, K, hop);
         }
         if (!wl.fn) return LEAF_ERR_BAD_ALGO;
+        q.mix_perm = tl_mix.perm; q.mix_lam = tl_mix.lam;
         const int grid = std::max(1, std::min(B * fp.nblk, num_cus()));
         static const bool fin_off = [] { const char* e = tools_env("LEAF_FIN_FUSED"); return e && atoi(e) == 0; }();   // tools only: A/B
         if (wl.fused_finalize && LEAF_WG_TAIL && !LEAF_WG_STRIDED && !fin_off) {
@@ -1103,7 +1120,9 @@ static int fft_forward(const FftPlan& fp, const void* x, int xtype, int B, int T
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wl.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl.lds);
         hipLaunchKernelGGL(wl.fn, dim3(grid), dim3(wl.nw * 64), wl.lds, st, q);
     } else {
-        FftKernel kfn = pick_fft_kernel(fp, K, hop, false);
+        FftKernel kfn = tl_mix.lam ? pick_fft_kernel_mix(fp, K, hop, false) : pick_fft_kernel(fp, K, hop, false);
+        if (!kfn) return LEAF_ERR_BAD_ALGO;                   // (mixed call: mix_fused_forward admits the static odd windows only)
+        q.mix_perm = tl_mix.perm; q.mix_lam = tl_mix.lam;
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds);
         hipLaunchKernelGGL(kfn, dim3(std::max(1, std::min(ceil_div(q.total_tasks, kFftWaves), num_cus()))), dim3(kFftWaves * 64),
                            fp.lds, st, q);
@@ -1189,11 +1208,12 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
         const SmallPlan sp = make_small_plan(B, T, F, K, hop);
         if (!sp.ok) return LEAF_ERR_BAD_ALGO;
         using SmallKernel = void (*)(const SmallParams);
-        const SmallKernel kfn = reinterpret_cast<SmallKernel>(const_cast<void*>(leaf_inst_fft_small(K, sp.split)));
+        const SmallKernel kfn = reinterpret_cast<SmallKernel>(const_cast<void*>(tl_mix.lam ? leaf_inst_fft_small_mix(K, sp.split) : leaf_inst_fft_small(K, sp.split)));
         if (!kfn) return LEAF_ERR_BAD_ALGO;
         SmallParams q{};
         q.x = x; q.io_bf16 = xtype; q.kernel = kernel; q.pool_w = pool_w; q.bd = gabor_bounds(K);
         q.B = B; q.T = T; q.TP = sp.TP; q.F = F; q.nblk = sp.nblk; q.ring = sp.split ? kSmallSplitRing : sp.ring;
+        q.mix_perm = tl_mix.perm; q.mix_lam = tl_mix.lam;
         q.fin = FinParams{nullptr, F, sp.TP, SlotGeom{fft_block_len(K, hop, true), K / 2 + K % 2 - 1, K, hop, T, 2}, pool_b, alpha, delta,
                           root, ema_w, 1e-12f, mode, out, pooled_raw, clip_scale2};
         if (ev) { (void)hipEventRecord(ev[0], st); (void)hipEventRecord(ev[1], st); }
@@ -1249,6 +1269,7 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
             q.x = x; q.io_bf16 = xtype; q.H = reinterpret_cast<const float2*>(tab); q.Gz = Grow; q.part = part;
             q.B = B; q.T = T; q.TP = f4.TP; q.F = F; q.K = K; q.hop = hop; q.padL = f4.padL; q.L = f4.L; q.nblk = f4.nblk;
             q.nslot = f4.nslot; q.GZ = f4.RG; q.NT = f4.generic ? fft_wgg4k_frame_floats(K, hop) : 0;
+            q.mix_perm = tl_mix.perm; q.mix_lam = tl_mix.lam;
             q.lone = reinterpret_cast<const float*>(Wt);                  // (static 32 kHz kernel: the shared twiddle table travels in `lone`)
             if (band.rec) {
                 q.band = band;
@@ -1286,6 +1307,7 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
                            tables, part, /*tables_ready=*/false, st, ev, pooled_raw, algo == LEAF_ALGO_FFT_WG, clip_scale2);
     }
 
+    if (tl_mix.lam) return LEAF_ERR_BAD_ALGO;                 // (MFMA and staged kernels do not mix in their loads)
     if (algo == LEAF_ALGO_MFMA) {
         float* W = ws;
         float* G = ws + align_up(pl.w_floats, 64);
@@ -1360,6 +1382,101 @@ int leaf_forward_save_f32(const float* x, int B, int T, const float* kernel, con
     if ((flags & LEAF_FLAG_PEAKNORM) && !(flags & LEAF_FLAG_X_PCM16)) return LEAF_ERR_UNSUPPORTED;
     return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out, workspace,
                         workspace_bytes, stream, nullptr, pooled_raw);
+}
+
+// ---- waveform mixup (leaf_common.hpp: mix_load): x'[b] = x[b] lam[b] + x[perm[b]] (1 - lam[b]), defined in fp32 with separately
+// rounded operations.  The static-geometry and 4096-sample overlap-save families mix in their loads; every other family reads a mixed
+// fp32 copy that mixup_kernel writes behind the family's own workspace.
+static int launch_mixup(const void* x, int xtype, int B, int T, const int* perm, const float* lam, float* out, hipStream_t st) {
+    const int tiles = ceil_div(T, 1024);
+    if ((long long)B * tiles >= (1ll << 31)) return LEAF_ERR_BAD_SHAPE;
+    hipLaunchKernelGGL(mixup_kernel, dim3((unsigned)(B * tiles)), dim3(256), 0, st, x, xtype, B, T, tiles, perm, lam, out);
+    LEAF_LAUNCH_CHECK();
+    return LEAF_OK;
+}
+// does the forward kernel behind the RESOLVED selector mix in its loads?
+static bool mix_fused_forward(int B, int T, int F, int K, int hop, int sel) {
+    if (sel == LEAF_ALGO_FFT_SMALL) return true;
+    if (sel == LEAF_ALGO_FFT) return pick_fft_kernel_mix(make_fft_plan(B, T, F, K, hop), K, hop, false) != nullptr;   // per-wave: static odd windows
+    if (sel != LEAF_ALGO_FFT_WG) return false;                            // MFMA, staged: the mixed copy
+    if (make_fft4k_plan(B, T, F, K, hop).ok) return true;                 // 4096-sample blocks, static and run-time geometry
+    static const bool force_generic = [] { const char* e = tools_env("LEAF_WG_GENERIC"); return e && atoi(e) != 0; }();   // tools only
+    return pick_fft_wg_kernel(K, hop).fn != nullptr && !force_generic;    // 2048-sample blocks: the static instances
+}
+static size_t mix_copy_offset_floats(size_t base_bytes) { return align_up((base_bytes + 3) / 4, 64); }
+
+int leaf_mixup_f32(const void* x, int B, int T, const int* mix_perm, const float* mix_lam, int flags, float* out, void* stream) {
+    if (flags & ~LEAF_FLAG_X_PCM16) return LEAF_ERR_UNSUPPORTED;          // fp32 or 16-bit PCM in, fp32 out
+    if (B == 0 && T >= 1) return LEAF_OK;
+    if (!x || !mix_perm || !mix_lam || !out) return LEAF_ERR_NULL_POINTER;
+    if (B < 1 || T < 1 || (long long)B * T >= (1ll << 31)) return LEAF_ERR_BAD_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(x) & ((flags & LEAF_FLAG_X_PCM16) ? 1u : 3u)) || any_misaligned(mix_perm, mix_lam, out))
+        return LEAF_ERR_ALIGNMENT;
+    return launch_mixup(x, x_sample_type(flags), B, T, mix_perm, mix_lam, out, (hipStream_t)stream);
+}
+
+size_t leaf_forward_mix_workspace_bytes(int B, int T, int F, int K, int hop, int algo) {
+    const size_t base = leaf_workspace_bytes(B, T, F, K, hop, algo);
+    if (!base) return 0;
+    const ReserveCus reserve(algo);
+    int sel = algo & 0xff;
+    if (sel == LEAF_ALGO_AUTO) sel = auto_algo(B, T, F, K, hop);
+    if (mix_fused_forward(B, T, F, K, hop, sel)) return base;
+    return (mix_copy_offset_floats(base) + align_up((size_t)B * T, 64)) * 4;
+}
+
+static int forward_mix_impl(const void* x, const int* mix_perm, const float* mix_lam, int B, int T, const float* kernel,
+                            const float* pool_w, const float* pool_b, const float* alpha, const float* delta, const float* root,
+                            const float* ema_w, int F, int K, int hop, int flags, int algo, void* out, float* pooled_raw,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    // bfloat16 is not mixed (the definition is fp32); peak normalisation would have to follow the mix, which the fused loads cannot do
+    if (flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_PEAKNORM)) return LEAF_ERR_UNSUPPORTED;
+    if (empty_batch(B, T, F, K, hop))                        // selector and layout checks as without the mix; nothing is read
+        return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags & ~LEAF_FLAG_X_PCM16, algo, out, workspace,
+                            workspace_bytes, stream, nullptr, pooled_raw);
+    if (!x || !mix_perm || !mix_lam) return LEAF_ERR_NULL_POINTER;
+    const int rc = check_shape(B, T, F, K, hop);
+    if (rc != LEAF_OK) return rc;
+    if (any_misaligned(mix_perm, mix_lam)) return LEAF_ERR_ALIGNMENT;
+    int sel = algo & 0xff;
+    if (sel != LEAF_ALGO_AUTO && sel != LEAF_ALGO_STAGED && sel != LEAF_ALGO_MFMA && sel != LEAF_ALGO_FFT && sel != LEAF_ALGO_FFT_WG &&
+        sel != LEAF_ALGO_FFT_SMALL)
+        return LEAF_ERR_BAD_ALGO;
+    const ReserveCus reserve(algo);                          // AUTO resolves as forward_impl will
+    if (sel == LEAF_ALGO_AUTO) sel = auto_algo(B, T, F, K, hop);
+    algo = (algo & ~0xff) | sel;
+    if (mix_fused_forward(B, T, F, K, hop, sel)) {
+        const MixScope mix(MixArgs{mix_perm, mix_lam});
+        return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out, workspace,
+                            workspace_bytes, stream, nullptr, pooled_raw);
+    }
+    // the mixed fp32 copy behind the family's own workspace, then the unmixed call on it
+    const size_t base = leaf_workspace_bytes(B, T, F, K, hop, algo);
+    if (!base) return LEAF_ERR_BAD_ALGO;
+    if (reinterpret_cast<uintptr_t>(x) & ((flags & LEAF_FLAG_X_PCM16) ? 1u : 3u) || misaligned16(workspace)) return LEAF_ERR_ALIGNMENT;
+    if (!workspace || workspace_bytes < leaf_forward_mix_workspace_bytes(B, T, F, K, hop, algo)) return LEAF_ERR_WORKSPACE;
+    float* mixed = static_cast<float*>(workspace) + mix_copy_offset_floats(base);
+    const int mrc = launch_mixup(x, x_sample_type(flags), B, T, mix_perm, mix_lam, mixed, (hipStream_t)stream);
+    if (mrc != LEAF_OK) return mrc;
+    return forward_impl(mixed, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags & ~LEAF_FLAG_X_PCM16, algo, out,
+                        workspace, base, stream, nullptr, pooled_raw);
+}
+
+int leaf_forward_mix_f32(const void* x, const int* mix_perm, const float* mix_lam, int B, int T, const float* kernel,
+                         const float* pool_w, const float* pool_b, const float* alpha, const float* delta, const float* root,
+                         const float* ema_w, int F, int K, int hop, int flags, int algo, float* out, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    return forward_mix_impl(x, mix_perm, mix_lam, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out,
+                            nullptr, workspace, workspace_bytes, stream);
+}
+
+int leaf_forward_save_mix_f32(const void* x, const int* mix_perm, const float* mix_lam, int B, int T, const float* kernel,
+                              const float* pool_w, const float* pool_b, const float* alpha, const float* delta, const float* root,
+                              const float* ema_w, int F, int K, int hop, int flags, int algo, float* out, float* pooled_raw,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pooled_raw) return LEAF_ERR_NULL_POINTER;
+    return forward_mix_impl(x, mix_perm, mix_lam, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out,
+                            pooled_raw, workspace, workspace_bytes, stream);
 }
 
 int leaf_forward_profiled_f32(const float* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
@@ -1771,7 +1888,23 @@ size_t leaf_backward_workspace_bytes(int B, int T, int F, int K, int hop, int fl
     return (bwd_own_workspace_floats(path, B, T, F, K, hop, need_dx != 0) + bwd_x32_floats(path, B, T, K, hop, flags)) * 4;
 }
 
-int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
+// Waveform mixup (leaf_backward_mix_f32).  The 4096-sample backwards and the static odd-window kernels of the 2048-sample plan
+// (workgroup-per-block and per-wave, K = 401 / 201 / 801) have MIX instances that mix in their block loads; the run-time-geometry
+// 2048-sample kernels (they re-read samples in their time-domain terms), MFMA and staged read a mixed fp32 copy behind the path's own
+// layout -- where the widened copy of a 16-bit waveform goes, which a mixed call never needs (mixup_kernel widens).
+static bool fft_bwd_mixes_in_loads(const FftPlan& fp, int K, int hop) { return pick_fft_kernel_mix(fp, K, hop, true) != nullptr; }
+static size_t bwd_mix_floats(BwdPath path, int B, int T, int F, int K, int hop) {
+    if (path == BWD_PATH_FFT4K || (path == BWD_PATH_FFT && fft_bwd_mixes_in_loads(make_fft_plan(B, T, F, K, hop), K, hop))) return 0;
+    return align_up((size_t)B * T, 64);
+}
+
+size_t leaf_backward_mix_workspace_bytes(int B, int T, int F, int K, int hop, int flags) {
+    if (check_shape(B, T, F, K, hop) != LEAF_OK) return 0;
+    const BwdPath path = bwd_path(B, T, F, K, hop, flags, false);
+    return (bwd_own_workspace_floats(path, B, T, F, K, hop, false) + bwd_mix_floats(path, B, T, F, K, hop)) * 4;
+}
+
+static int backward_impl(const float* x, const int* mix_perm, const float* mix_lam, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
                       const float* alpha, const float* delta, const float* root, const float* ema_w, int F, int K, int hop,
                       int flags, const float* grad_out, const float* pooled_raw, float* g_kernel, float* g_pool_w,
                       float* g_pool_b, float* g_alpha, float* g_delta, float* g_root, float* g_ema_w, float* g_x,
@@ -1779,6 +1912,8 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
     // LEAF_FLAG_IO_BF16: x, grad_out and g_x are bfloat16 buffers behind the float pointers (as in the forward); everything else fp32
     // LEAF_FLAG_X_PCM16: x alone is a 16-bit PCM buffer (v / 32768); an integer input has no gradient, so g_x must be NULL
     if ((flags & LEAF_FLAG_X_PCM16) && ((flags & LEAF_FLAG_IO_BF16) || g_x)) return LEAF_ERR_UNSUPPORTED;
+    // mix_lam != NULL: the mixed call (leaf_backward_mix_f32 has refused bfloat16, PEAKNORM, g_x and a missing buffer)
+    const bool mixed_call = mix_lam != nullptr;
     if (empty_batch(B, T, F, K, hop)) {
         // the sum over zero clips: every parameter gradient is exactly zero (what autograd returns for the reference)
         if (!g_kernel || !g_pool_w || !g_pool_b) return LEAF_ERR_NULL_POINTER;
@@ -1806,11 +1941,12 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
         if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(grad_out) & io_mask) ||
             (reinterpret_cast<uintptr_t>(g_x) & io_mask) || misaligned16(workspace) ||
             any_misaligned(kernel, pool_w, pool_b, alpha, delta, root, ema_w, pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta,
-                           g_root, g_ema_w))
+                           g_root, g_ema_w) || any_misaligned(mix_perm, mix_lam))
             return LEAF_ERR_ALIGNMENT;
     }
     const BwdPath path = bwd_path(B, T, F, K, hop, flags, g_x != nullptr);
-    if (!workspace || workspace_bytes < leaf_backward_workspace_bytes(B, T, F, K, hop, flags, g_x != nullptr))
+    if (!workspace || workspace_bytes < (mixed_call ? leaf_backward_mix_workspace_bytes(B, T, F, K, hop, flags)
+                                                    : leaf_backward_workspace_bytes(B, T, F, K, hop, flags, g_x != nullptr)))
         return LEAF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int TP = (T - 1) / hop + 1;
@@ -1820,7 +1956,14 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
     const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (io_bf16 ? 4 : 0);
     float* ws = static_cast<float*>(workspace);
     int xtype = x_sample_type(flags);                        // what the kernels below read x as
-    if (float* x32 = bwd_x32_floats(path, B, T, K, hop, flags) ? ws + bwd_own_workspace_floats(path, B, T, F, K, hop, g_x != nullptr) : nullptr) {
+    if (mixed_call && bwd_mix_floats(path, B, T, F, K, hop)) {
+        // this path's kernels do not mix in their loads: the mixed fp32 copy behind the path's own layout, then the unmixed call on it
+        float* xm = ws + bwd_own_workspace_floats(path, B, T, F, K, hop, false);
+        rc = launch_mixup(x, xtype, B, T, mix_perm, mix_lam, xm, st);
+        if (rc != LEAF_OK) return rc;
+        x = xm; xtype = kSampleF32; mix_perm = nullptr; mix_lam = nullptr;
+    }
+    if (float* x32 = !mixed_call && bwd_x32_floats(path, B, T, K, hop, flags) ? ws + bwd_own_workspace_floats(path, B, T, F, K, hop, g_x != nullptr) : nullptr) {
         // these families read fp32: one widening pass into the workspace's tail, then the fp32 path
         const size_t n = (size_t)B * T;
         hipLaunchKernelGGL(x16_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
@@ -1865,6 +2008,7 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
         q.x = x; q.io_bf16 = xtype; q.H = reinterpret_cast<const float2*>(tab3); q.Gz = Grow; q.part = part;
         q.B = B; q.T = T; q.TP = bp.TP; q.F = F; q.K = K; q.hop = hop; q.padL = bp.padL; q.L = bp.L; q.nblk = bp.nblk;
         q.nslot = 2; q.GZ = bp.RG;
+        q.mix_perm = mix_perm; q.mix_lam = mix_lam;                       // (mixed call: the forward recompute and the MIX backward instance mix in their loads)
         q.lone = reinterpret_cast<const float*>(Wt);                      // (read by the static forward kernel when it recomputes below)
         const dim3 grid(std::max(1, std::min(B * bp.nblk, num_cus())));
         const float* raw_in = pooled_raw;              // saved by leaf_forward_save_f32, else recomputed here
@@ -1893,7 +2037,9 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
         // 3. per-(block, filter) partial gradients
         q.gpre = gpre; q.pool_w = pool_w; q.dkpart = dkpart; q.dwpart = dwpart; q.part = nullptr;
         FftKernel kb = bp.dx ? as_fft_kernel(leaf_inst_fft_wg4k_bwd_dx())
-                             : bp.stat ? as_fft_kernel(leaf_inst_fft_wg4k_bwd()) : pick_fft_wgg4k_bwd_kernel(K);
+                             : bp.stat ? as_fft_kernel(mix_lam ? leaf_inst_fft_wg4k_bwd_mix() : leaf_inst_fft_wg4k_bwd())
+                                       : mix_lam ? as_fft_kernel(leaf_inst_fft_wgg4k_bwd_mix(fft_wgg4k_taps_per_lane(K))) : pick_fft_wgg4k_bwd_kernel(K);
+        if (!kb) return LEAF_ERR_BAD_ALGO;
         if (bp.dx) q.part = ws + L.dxblk;                                 // [block][4096] input gradients, un-rotated
         size_t blds = bp.lds;
         if (band_bwd) {
@@ -1969,10 +2115,12 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
             q.L = fp.L; q.nblk = fp.nblk; q.GZ = fp.GZ; q.nslot = fp.nslot; q.g_bufs = fp.g_bufs; q.NT = fp.NT; q.fq = fp.fq; q.nfq = fp.nfq;
             q.scr_floats = fp.scr_floats; q.total_tasks = B * fp.nblk * fp.nfq;
             q.rot = K / 2;
+            q.mix_perm = mix_perm; q.mix_lam = mix_lam;                   // (non-NULL only where the MIX instances below exist)
             const dim3 grid(std::max(1, std::min(ceil_div(q.total_tasks, kFftWaves), num_cus())));
             const float* raw_in = pooled_raw;          // saved by leaf_forward_save_f32, else recomputed here
             if (!raw_in) {
-                FftKernel kf = pick_fft_kernel(fp, K, hop, false);
+                FftKernel kf = mix_lam ? pick_fft_kernel_mix(fp, K, hop, false) : pick_fft_kernel(fp, K, hop, false);
+                if (!kf) return LEAF_ERR_BAD_ALGO;
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds);
                 hipLaunchKernelGGL(kf, grid, dim3(kFftWaves * 64), fp.lds, st, q);
                 LEAF_LAUNCH_CHECK();
@@ -1992,6 +2140,8 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
                 // workgroup-per-block backward; with g_x the per-block input gradients go to dxblk and are gathered below
                 FftWgBwdLaunch wl = pick_fft_wg_bwd_kernel(K, hop, g_x != nullptr, (long long)B * fp.nblk, xtype == kSampleBf16);
                 q.part = g_x ? ws + L.dxblk : nullptr;
+                if (mix_lam) wl.fn = as_fft_kernel(leaf_inst_fft_wg_bwd_mix(K));
+                if (!wl.fn) return LEAF_ERR_BAD_ALGO;
                 if (band_bwd) {
                     band.lds_off = (int)(wl.lds / 4);
                     wl.lds += band_lds_bytes(F);
@@ -2025,7 +2175,8 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
                 hipLaunchKernelGGL(wl.fn, dim3(std::max(1, std::min(B * fp.nblk, num_cus()))), dim3(wl.nw * 64), wl.lds, st, q);
                 LEAF_LAUNCH_CHECK();
             } else {
-                FftKernel kb = pick_fft_kernel(fp, K, hop, true);
+                FftKernel kb = mix_lam ? pick_fft_kernel_mix(fp, K, hop, true) : pick_fft_kernel(fp, K, hop, true);
+                if (!kb) return LEAF_ERR_BAD_ALGO;
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds);
                 hipLaunchKernelGGL(kb, grid, dim3(kFftWaves * 64), fp.lds, st, q);
                 LEAF_LAUNCH_CHECK();
@@ -2154,6 +2305,28 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
         LEAF_LAUNCH_CHECK();
     }
     return LEAF_OK;
+}
+
+int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
+                      const float* alpha, const float* delta, const float* root, const float* ema_w, int F, int K, int hop,
+                      int flags, const float* grad_out, const float* pooled_raw, float* g_kernel, float* g_pool_w,
+                      float* g_pool_b, float* g_alpha, float* g_delta, float* g_root, float* g_ema_w, float* g_x,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    return backward_impl(x, nullptr, nullptr, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, grad_out,
+                         pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w, g_x, workspace, workspace_bytes,
+                         stream);
+}
+
+int leaf_backward_mix_f32(const void* x, const int* mix_perm, const float* mix_lam, int B, int T, const float* kernel,
+                          const float* pool_w, const float* pool_b, const float* alpha, const float* delta, const float* root,
+                          const float* ema_w, int F, int K, int hop, int flags, const float* grad_out, const float* pooled_raw,
+                          float* g_kernel, float* g_pool_w, float* g_pool_b, float* g_alpha, float* g_delta, float* g_root,
+                          float* g_ema_w, float* g_x, void* workspace, size_t workspace_bytes, void* stream) {
+    if (g_x || (flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_PEAKNORM))) return LEAF_ERR_UNSUPPORTED;   // dL/dx under mixup is a scatter over perm: not built
+    if (B != 0 && (!mix_perm || !mix_lam)) return LEAF_ERR_NULL_POINTER;
+    return backward_impl(static_cast<const float*>(x), mix_perm, mix_lam, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K,
+                         hop, flags, grad_out, pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w, g_x,
+                         workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -248,6 +248,117 @@ std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Ten
     return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw, need_dx ? gx.reshape(x.sizes()) : gx};
 }
 
+// ---- waveform mixup (leaf_hip.h: the *_mix_* entries): the three ops above on x * lam + x[perm] * (1 - lam), the mix done inside
+// the kernels' loads where the family has one.  x float32 or int16 PCM; perm int32 [B] and lam float32 [B] on x's device (the Python
+// layer converts and validates, leaf_pytorch_amd/_native.py: mix_args).  One C-ABI call: a mixed batch cannot be sliced (a clip's
+// partner may sit in another slice), so B * T >= 2^31 is refused.
+struct MixCall {
+    Tensor x2, perm, lam;
+    int64_t B;
+    int T, F, TP, xflag;
+};
+MixCall mix_call(const Tensor& x, const Tensor& perm, const Tensor& lam, const Params& p, int64_t K, int64_t hop) {
+    MixCall c;
+    c.x2 = waveform_2d(x);
+    TORCH_CHECK(c.x2.scalar_type() == at::kFloat || c.x2.scalar_type() == at::kShort,
+                "mixup is defined in float32 on a float32 or int16 (PCM) waveform, got ", c.x2.scalar_type());
+    c.B = c.x2.size(0);
+    TORCH_CHECK(c.x2.size(1) < (int64_t(1) << 31) && c.B * c.x2.size(1) < (int64_t(1) << 31),
+                "a mixed batch goes through one C-ABI call: B * T must stay below 2^31, got ", c.B, " x ", c.x2.size(1));
+    c.T = (int)c.x2.size(1); c.F = (int)p.kernel.size(0);
+    c.TP = leaf_num_frames(c.T, (int)K, (int)hop);
+    TORCH_CHECK(c.TP >= 1 && c.F >= 1, "bad shape B=", c.B, " T=", c.T, " F=", c.F, " K=", K, " hop=", hop);
+    TORCH_CHECK(perm.device() == c.x2.device() && perm.scalar_type() == at::kInt && perm.numel() == c.B,
+                "perm must be int32 with one entry per clip on ", c.x2.device());
+    c.perm = perm.reshape({-1}).contiguous();
+    c.lam = dev_f32(lam.reshape({-1}), "lam", c.x2.device());
+    TORCH_CHECK(c.lam.numel() == c.B, "lam must have one entry per clip");
+    c.xflag = c.x2.scalar_type() == at::kShort ? LEAF_FLAG_X_PCM16 : 0;
+    return c;
+}
+
+Tensor forward_mix_impl(const Tensor& x, const Tensor& perm, const Tensor& lam, const Params& p, int64_t K, int64_t hop, bool log1p,
+                        int64_t algo, Tensor* raw) {
+    const MixCall c = mix_call(x, perm, lam, p, K, hop);
+    const auto opt = c.x2.options().dtype(at::kFloat);
+    Tensor out = at::empty({c.B, c.F, c.TP}, opt);
+    if (raw) *raw = at::empty({c.B, c.F, c.TP}, opt);
+    if (c.B == 0) return out;
+    const int flags = c.xflag | (p.pcen ? LEAF_FLAG_PCEN : (log1p ? LEAF_FLAG_LOG1P : 0));
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(c.x2.device());
+    auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(c.x2.device().index());
+    Tensor ws = at::empty({(int64_t)std::max<size_t>(leaf_forward_mix_workspace_bytes((int)c.B, c.T, c.F, (int)K, (int)hop, (int)algo), size_t(4))},
+                          opt.dtype(at::kByte));
+    if (raw) {
+        check_status(leaf_forward_save_mix_f32(c.x2.data_ptr(), c.perm.data_ptr<int>(), fptr(c.lam), (int)c.B, c.T, fptr(p.kernel),
+                                               fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha), fptr(p.delta), fptr(p.root), fptr(p.ema_w),
+                                               c.F, (int)K, (int)hop, flags, (int)algo, out.data_ptr<float>(), raw->data_ptr<float>(),
+                                               ws.data_ptr(), (size_t)ws.numel(), stream.stream()),
+                     "leaf_forward_save_mix_f32");
+    } else {
+        check_status(leaf_forward_mix_f32(c.x2.data_ptr(), c.perm.data_ptr<int>(), fptr(c.lam), (int)c.B, c.T, fptr(p.kernel),
+                                          fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha), fptr(p.delta), fptr(p.root), fptr(p.ema_w), c.F,
+                                          (int)K, (int)hop, flags, (int)algo, out.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(),
+                                          stream.stream()),
+                     "leaf_forward_mix_f32");
+    }
+    return out;
+}
+
+// leaf_amd::forward_mix -- leaf_amd::forward of the mixed batch
+Tensor op_forward_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, const Tensor& kernel, const Tensor& pool_w,
+                      const Tensor& pool_b, const OptTensor& alpha, const OptTensor& delta, const OptTensor& root,
+                      const OptTensor& ema_w, int64_t K, int64_t hop, bool log1p, int64_t algo) {
+    const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
+    return forward_mix_impl(x, perm, lam, p, K, hop, log1p, algo, nullptr);
+}
+
+// leaf_amd::forward_train_mix -- additionally the pre-floor pooled tensor of the mixed batch, for leaf_amd::backward_mix
+std::tuple<Tensor, Tensor> op_forward_train_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, const Tensor& kernel,
+                                                const Tensor& pool_w, const Tensor& pool_b, const OptTensor& alpha,
+                                                const OptTensor& delta, const OptTensor& root, const OptTensor& ema_w, int64_t K,
+                                                int64_t hop, int64_t algo, bool log1p) {
+    const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
+    Tensor raw;
+    Tensor out = forward_mix_impl(x, perm, lam, p, K, hop, log1p, algo, &raw);
+    return {out, raw};
+}
+
+// leaf_amd::backward_mix -- the seven parameter gradients of the mixed call (PCEN entries empty without PCEN); no dL/dx
+std::vector<Tensor> op_backward_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, const Tensor& kernel, const Tensor& pool_w,
+                                    const Tensor& pool_b, const OptTensor& alpha, const OptTensor& delta, const OptTensor& root,
+                                    const OptTensor& ema_w, int64_t K, int64_t hop, const Tensor& grad_out,
+                                    const OptTensor& pooled_raw, int64_t flags) {
+    const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
+    const MixCall c = mix_call(x, perm, lam, p, K, hop);
+    Tensor go = dev_f32(grad_out, "grad_out", c.x2.device());
+    TORCH_CHECK(go.dim() == 3 && go.size(0) == c.B && go.size(1) == c.F && go.size(2) == c.TP, "grad_out has shape ", go.sizes(),
+                ", expected (", c.B, ",", c.F, ",", c.TP, ")");
+    OptTensor raw = dev_f32(pooled_raw, "pooled_raw", c.x2.device());
+    auto opt = c.x2.options().dtype(at::kFloat);
+    const int F = c.F;
+    Tensor gk = at::empty_like(p.kernel), gpw = at::empty_like(p.pool_w), gpb = at::empty_like(p.pool_b);
+    Tensor ga = at::empty({p.pcen ? F : 0}, opt), gd = at::empty({p.pcen ? F : 0}, opt), gr = at::empty({p.pcen ? F : 0}, opt),
+           gw = at::empty({p.pcen ? F : 0}, opt);
+    if (c.B == 0) {
+        for (Tensor* g : {&gk, &gpw, &gpb, &ga, &gd, &gr, &gw}) g->zero_();
+        return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw};
+    }
+    const int fl = ((int)flags & ~(LEAF_FLAG_PCEN | LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16)) | (p.pcen ? LEAF_FLAG_PCEN : 0) | c.xflag;
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(c.x2.device());
+    auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(c.x2.device().index());
+    Tensor ws = at::empty({(int64_t)std::max<size_t>(leaf_backward_mix_workspace_bytes((int)c.B, c.T, F, (int)K, (int)hop, fl), size_t(4))},
+                          opt.dtype(at::kByte));
+    check_status(leaf_backward_mix_f32(c.x2.data_ptr(), c.perm.data_ptr<int>(), fptr(c.lam), (int)c.B, c.T, fptr(p.kernel), fptr(p.pool_w),
+                                       fptr(p.pool_b), fptr(p.alpha), fptr(p.delta), fptr(p.root), fptr(p.ema_w), F, (int)K, (int)hop, fl,
+                                       fptr(go), fptr(raw), gk.data_ptr<float>(), gpw.data_ptr<float>(), gpb.data_ptr<float>(),
+                                       p.pcen ? ga.data_ptr<float>() : nullptr, p.pcen ? gd.data_ptr<float>() : nullptr,
+                                       p.pcen ? gr.data_ptr<float>() : nullptr, p.pcen ? gw.data_ptr<float>() : nullptr, nullptr,
+                                       ws.data_ptr(), (size_t)ws.numel(), stream.stream()),
+                 "leaf_backward_mix_f32");
+    return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(leaf_amd, m) {
@@ -257,6 +368,12 @@ TORCH_LIBRARY(leaf_amd, m) {
           "Tensor? ema_w, int K, int hop, int algo, bool log1p=False) -> (Tensor, Tensor)");
     m.def("backward(Tensor x, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, Tensor? root, "
           "Tensor? ema_w, int K, int hop, Tensor grad_out, Tensor? pooled_raw, bool need_dx, int flags) -> Tensor[]");
+    m.def("forward_mix(Tensor x, Tensor perm, Tensor lam, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, "
+          "Tensor? root, Tensor? ema_w, int K, int hop, bool log1p, int algo) -> Tensor");
+    m.def("forward_train_mix(Tensor x, Tensor perm, Tensor lam, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, "
+          "Tensor? delta, Tensor? root, Tensor? ema_w, int K, int hop, int algo, bool log1p=False) -> (Tensor, Tensor)");
+    m.def("backward_mix(Tensor x, Tensor perm, Tensor lam, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, "
+          "Tensor? root, Tensor? ema_w, int K, int hop, Tensor grad_out, Tensor? pooled_raw, int flags) -> Tensor[]");
 }
 
 // HIP tensors dispatch under the CUDA key in PyTorch-ROCm
@@ -264,4 +381,7 @@ TORCH_LIBRARY_IMPL(leaf_amd, CUDA, m) {
     m.impl("forward", &op_forward);
     m.impl("forward_train", &op_forward_train);
     m.impl("backward", &op_backward);
+    m.impl("forward_mix", &op_forward_mix);
+    m.impl("forward_train_mix", &op_forward_train_mix);
+    m.impl("backward_mix", &op_backward_mix);
 }

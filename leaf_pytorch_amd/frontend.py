@@ -59,6 +59,35 @@ class _LeafForward(torch.autograd.Function):
         return gx, gk, gpw, gpb, ga, gd, gr, gw, None, None, None, None, None
 
 
+class _LeafForwardMix(torch.autograd.Function):
+    """_LeafForward on the mixed batch x * lam + x[perm] * (1 - lam) (leaf_forward_save_mix_f32 / leaf_backward_mix_f32): the
+    path without the dispatcher ops.  Parameter gradients only."""
+
+    @staticmethod
+    def forward(ctx, x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen, algo, log1p=False):
+        out, raw = _native.leaf_forward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen=pcen,
+                                            log1p=log1p, algo=algo, save_raw=True)
+        ctx.log1p = bool(log1p) and not pcen
+        ctx.save_for_backward(x, perm, lam, kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if pcen else []))
+        ctx.geom = (K, hop, pcen)
+        ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)
+        ctx.strict = bool(algo & _native.ALGO_STRICT_BAND_CLASSES)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        K, hop, pcen = ctx.geom
+        saved = ctx.saved_tensors
+        x, perm, lam, kernel, pool_w, pool_b, raw = saved[:7]
+        alpha, delta, root, ema_w = saved[7:] if pcen else (None,) * 4
+        gk, gpw, gpb, ga, gd, gr, gw, _ = _native.leaf_backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K,
+                                                                    hop, grad_out, pcen=pcen, pooled_raw=raw,
+                                                                    full_transforms=ctx.full, strict_band_classes=ctx.strict,
+                                                                    log1p=ctx.log1p)
+        return None, None, None, gk, gpw, gpb, ga, gd, gr, gw, None, None, None, None, None
+
+
 class Leaf(nn.Module):
     def __init__(self, n_filters: int = 40, sample_rate: int = 16000, window_len: float = 25.,
                  window_stride: float = 10., preemp: bool = False, init_min_freq=60.0, init_max_freq=7800.0,
@@ -141,6 +170,49 @@ class Leaf(nn.Module):
             self._tables = _native.prepare_tables(k.detach(), w.detach(), self._complex_conv._kernel_size, self._pooling.strides)
             self._tables_key = key if self._tables is not None else None
         return self._tables
+
+    def forward_mixup(self, x: torch.Tensor, perm, lam) -> torch.Tensor:
+        """Not part of the reference surface: ``forward(x * lam[:, None, None] + x[perm] * (1 - lam[:, None, None]))`` -- the
+        waveform mixup of the reference's training loop (utilities/data/mixup.py) -- bit for bit, with the mix done in fp32 inside
+        the kernels' loads, forward and backward, on the static geometries (16 / 8 / 32 kHz windows) and the 4096-sample plans: there the
+        mixed batch is never written and an int16 batch stays int16 in memory through a training step.  On every other geometry and
+        selector (run-time-geometry windows on 2048-sample blocks, MFMA, staged) the forward and the backward each write the mixed
+        float32 batch into their workspace first and run on that; the result is the same bits.
+
+        ``x``: (B,1,T) float32 or int16 PCM on the device; a bfloat16 ``x`` raises, and so does ``x.requires_grad`` (the gradient
+        would be a scatter over ``perm``; ``x`` is data here).  ``perm``: any integer tensor or sequence of length B, converted to
+        int32 on the device; when it arrives on the CPU it is validated there and an index outside [0, B) raises ValueError
+        before anything is launched (on the device it is clamped by the kernels).  ``lam``: float32, length B.  The parameters
+        train through the call; ``create_graph=True`` is not supported.  ``log_compression()``, ``full_transforms()`` and
+        ``pcen_compression=False`` apply as on ``forward``; ``fuse_peak_normalization()`` is NOT applied on this call (the
+        normalisation would have to follow the mix; peak-normalised clips stay inside |x| <= 1 under a convex mix), nor is
+        ``cache_tables()``.  ``transforms.Mixup`` draws ``perm`` and ``lam`` and mixes the targets."""
+        _native.require_hip(x, "Leaf.forward_mixup")
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.int16):
+            raise RuntimeError(f"Leaf.forward_mixup: the mix is defined in float32 on a float32 or int16 (PCM) waveform, got {x.dtype}")
+        if x.requires_grad:
+            raise RuntimeError("Leaf.forward_mixup: x.requires_grad is not supported (dL/dx under mixup is a scatter over perm, "
+                               "and the waveform is data here)")
+        c = self._compression
+        if c is not None and c._floor != 1e-12:
+            raise NotImplementedError("fused path is specialised for the PCEN floor Leaf constructs (1e-12)")
+        perm, lam = _native.mix_args(perm, lam, x.shape[0], x.device)
+        params = (self._complex_conv._kernel, self._pooling.weights, self._pooling._bias,
+                  c.alpha if c is not None else None, c.delta if c is not None else None,
+                  c.root if c is not None else None, c.ema._weights if c is not None else None)
+        K, hop = self._complex_conv._kernel_size, self._pooling.strides
+        log1p = self._log1p and c is None
+        needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params)
+        if _ops.available():
+            _ops.load()
+            if needs_grad:
+                return _ops.forward_train_mix(x, perm, lam, *params, K, hop, algo=self._algo, log1p=log1p)
+            return _ops.forward_mix(x, perm, lam, *params, K, hop, log1p=log1p, algo=self._algo)
+        if needs_grad:
+            return _LeafForwardMix.apply(x, perm, lam, *params, K, hop, c is not None, self._algo, log1p)
+        return _native.leaf_forward_mix(x, perm, lam, *params, K, hop, pcen=c is not None, log1p=log1p, algo=self._algo)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B,1,T) float32 -> (B,F,T') float32, as the reference.  Not part of the reference surface: a bfloat16 ``x`` gives

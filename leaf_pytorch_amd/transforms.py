@@ -42,3 +42,33 @@ class PeakNormalization:
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         return _native.peak_normalize(x)
+
+
+class Mixup:
+    """utilities/data/mixup.py:5-26 (``do_mixup``) restated for a batch on the device, with the mix itself done by a HIP kernel
+    (``_native.mixup``: fp32 or int16 PCM in, fp32 out, bit for bit the reference's ``inputs * lam + inputs[perms] * (1 - lam)``).
+    One weight per clip from Beta(alpha, alpha) -- drawn from ``numpy.random.RandomState(random_seed)`` as the reference does, so a
+    fixed seed gives the reference's weights -- and one permutation of the batch from torch's generator.
+
+    ``__call__(inputs, targets)`` returns ``(mixed_x, a, b, lam_or_None, perm, lam)``: the reference's four values -- multilabel:
+    ``(mixed_x, mixed_y, None, None)``, any other mode: ``(mixed_x, y_a, y_b, lam)`` -- followed by the permutation and the weights,
+    so that a caller can hand ``(inputs, perm, lam)`` to ``Leaf.forward_mixup`` instead of the mixed batch.  ``mix_inputs=False``
+    skips the waveform kernel for exactly that use (``mixed_x`` is then None).  The targets are mixed with stock ops."""
+
+    def __init__(self, alpha: float = 1., random_seed=1233, mode: str = "multilabel", mix_inputs: bool = True):
+        self.alpha = alpha
+        self.random_seed = random_seed
+        self.mode = mode
+        self.mix_inputs = mix_inputs
+
+    def __call__(self, inputs: torch.Tensor, targets: torch.Tensor):
+        import numpy as np
+        random_state = np.random.RandomState(self.random_seed)      # (re-seeded per call, as the reference's do_mixup)
+        bsize = len(inputs)
+        lam = torch.from_numpy(random_state.beta(self.alpha, self.alpha, bsize)).to(inputs.device).float()
+        perms = torch.randperm(bsize).to(inputs.device)
+        mixed_x = _native.mixup(inputs, perms, lam) if self.mix_inputs else None
+        if self.mode == "multilabel":
+            mixed_y = targets * lam.view(bsize, 1) + targets[perms] * (1 - lam.view(bsize, 1))
+            return mixed_x, mixed_y, None, None, perms, lam
+        return mixed_x, targets, targets[perms], lam, perms, lam

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Time forward and forward+backward of Leaf (parameters require grad) on one GPU.
-   usage: bench_backward.py [--no-pcen | --log1p] [--bf16 | --pcm16] [--interleave V1,V2,..] [B [n_filters sample_rate seconds [nodx]]]
+   usage: bench_backward.py [--no-pcen | --log1p] [--bf16 | --pcm16] [--mixup] [--interleave V1,V2,..] [B [n_filters sample_rate seconds [nodx]]]
    (default 256 clips of the default 40 f / 16 kHz / 1 s, PCEN on, float32;
    nodx skips the dL/dx timing -- staged kernels, hundreds of ms, for geometries without a fused dL/dx)
    --no-pcen: PCEN off (BASELINE configs[3] without compression); --log1p: PCEN off with Leaf.log_compression() (configs[3]);
    --bf16: bfloat16 waveform, features, grad_out and dL/dx (configs[4]).
    --pcm16: int16 waveform (16-bit PCM, a sample v means v / 32768), float32 features and grad_out, no dL/dx.
+   --mixup: waveform mixup folded into the step (Leaf.forward_mixup with a fixed permutation and weights; float32 or --pcm16; no dL/dx).
+   Interleave legs: "+mixup" the fused step, "+mixstock" the reference's stock-op mixup (x * lam + x[perm] * (1 - lam), an int16 batch
+   cast first) followed by the plain step, neither: the plain step.
    --interleave pcen,off,log1p,pcen+bf16,pcen+pcm16,pcen+pcm16cast,...: ("+pcm16cast": the int16 clips converted by the caller,
    x.float().mul_(2**-15), inside the timed step, then the float32 call; "+fwd": the no-grad forward alone instead of the step) instead of the line above, the training step (grad_out resident; with "+dx": incl. dL/dx)
    of each named variant timed in turn, round after round, in this one process: median, min and max of the rounds per variant, so that
@@ -19,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from leaf_pytorch_amd import Leaf  # noqa: E402
 
 dev = torch.device("cuda:0")
-OPTS = {a for a in sys.argv[1:] if a in ("--no-pcen", "--log1p", "--bf16", "--pcm16")}
+OPTS = {a for a in sys.argv[1:] if a in ("--no-pcen", "--log1p", "--bf16", "--pcm16", "--mixup")}
 INTERLEAVE = None
 if "--interleave" in sys.argv:
     i = sys.argv.index("--interleave")
@@ -45,6 +48,11 @@ if "--bf16" in OPTS:
 x16 = torch.round(x.float() * 32767).to(torch.int16)          # the same clips as 16-bit PCM
 if "--pcm16" in OPTS:
     x = x16
+MIX_PERM = torch.randperm(B, device=dev)                     # one fixed draw: the timing is about the kernels, not the RNG
+MIX_LAM = torch.rand(B, device=dev)
+if "--mixup" in OPTS:
+    _plain = m.forward
+    m.forward = lambda xin: m.forward_mixup(xin, MIX_PERM, MIX_LAM) if not xin.requires_grad else _plain(xin)
 
 
 def timed(fn, n=20):
@@ -85,7 +93,7 @@ def fwd_bwd_resident():
     torch.autograd.backward(m(x), go)
 
 
-xg = x.clone().requires_grad_(True) if x.is_floating_point() else None
+xg = x.clone().requires_grad_(True) if x.is_floating_point() and "--mixup" not in OPTS else None
 
 
 def fwd_bwd_dx():
@@ -122,15 +130,20 @@ if INTERLEAVE:
         with torch.no_grad():
             gv = torch.randn_like(mod(xv))
 
-        def step(mod=mod, xv=xv, gv=gv, cast=cast, fwd_only="fwd" in parts):
+        def step(mod=mod, xv=xv, gv=gv, cast=cast, fwd_only="fwd" in parts, fused="mixup" in parts, stock="mixstock" in parts):
             xin = xv.float().mul_(2.0 ** -15) if cast else xv
+            if stock:                                    # utilities/data/mixup.py:20 with stock ops (an integer batch is cast first)
+                xf = xin if xin.is_floating_point() else xin.float().mul_(2.0 ** -15)
+                lam3 = MIX_LAM.view(B, 1, 1)
+                xin = xf * lam3 + xf[MIX_PERM] * (1 - lam3)
+            call = (lambda t: mod.forward_mixup(t, MIX_PERM, MIX_LAM)) if fused else mod
             if fwd_only:
                 with torch.no_grad():
-                    mod(xin)
+                    call(xin)
                 return
             mod.zero_grad(set_to_none=True)
             xv.grad = None
-            torch.autograd.backward(mod(xin), gv)
+            torch.autograd.backward(call(xin), gv)
         steps[name] = step
     res = {name: [] for name in steps}
     for rnd in range(9):
