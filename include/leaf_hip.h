@@ -70,7 +70,9 @@ typedef enum leaf_status {
                                      kernels (the backward takes it on every path, ABI 6); LEAF_FLAG_PEAKNORM with
                                      leaf_forward_save_f32 / leaf_forward_prepared_f32 or off the overlap-save paths;
                                      LEAF_FLAG_X_PCM16 with the staged FORWARD kernels, together with LEAF_FLAG_IO_BF16, or
-                                     with g_x != NULL (an integer input has no gradient) */
+                                     with g_x != NULL (an integer input has no gradient); LEAF_FLAG_OUT_BF16 with the staged
+                                     FORWARD kernels (as bfloat16 I/O: the fused paths narrow in their stores, that one has no
+                                     such store) */
 } leaf_status;
 
 /* flags */
@@ -117,10 +119,28 @@ typedef enum leaf_status {
                                   Backward: the static overlap-save kernels and the 4096-sample plans read int16 directly; the
                                   run-time-geometry 2048-sample kernels, the MFMA and the staged backward read one widened fp32 copy
                                   in the workspace, reported by leaf_backward_workspace_bytes exactly where it is for bfloat16.
-                                  g_x must be NULL (an integer input has no gradient) and LEAF_FLAG_IO_BF16 must be clear (int16
-                                  in with bfloat16 out is not built): LEAF_ERR_UNSUPPORTED, answered before the workspace check
-                                  and before any launch.  LEAF_FLAG_PEAKNORM with it is valid on every entry point and path: no
+                                  g_x must be NULL (an integer input has no gradient) and LEAF_FLAG_IO_BF16 must be clear (that flag
+                                  says x is bfloat16): LEAF_ERR_UNSUPPORTED, answered before the workspace check and before any
+                                  launch.  bfloat16 features from an int16 waveform are LEAF_FLAG_X_PCM16 | LEAF_FLAG_OUT_BF16.
+                                  LEAF_FLAG_PEAKNORM with it is valid on every entry point and path: no
                                   |v / 32768| exceeds 1, so every clip's scale is 1 and the peak pre-pass is skipped. */
+#define LEAF_FLAG_OUT_BF16 0x200 /* extension (additive: the ABI version stays 6): the FEATURE side alone is bfloat16 -- `out` of the
+                                  forward entries and `grad_out` of the backward entries are bfloat16 buffers behind the float
+                                  pointers (2 bytes per element, 2-byte aligned; an odd address: LEAF_ERR_ALIGNMENT) -- while x
+                                  stays what its own flags say (float32, or int16 with LEAF_FLAG_X_PCM16) and everything else
+                                  stays float32: pooled_raw, the parameters, their gradients, and g_x, which follows x.  The
+                                  arithmetic is that of the float32 call: the forward rounds each feature to nearest even where
+                                  it stores it (NaN to the quiet NaN), so `out` holds the float32 call's result narrowed, bit
+                                  for bit; the backward widens grad_out where it reads it (exact), so its gradients are those of
+                                  the float32 call on the widened grad_out.  No cast kernel, no float32 copy: no workspace of any
+                                  path grows with this flag (the one read of grad_out, by the floor / PCEN backward of every
+                                  path, MFMA and staged included, widens in its load).  Honoured by leaf_forward_f32, _save_f32,
+                                  _prepared_f32, _profiled_f32, leaf_backward_f32, leaf_backward_workspace_bytes and the
+                                  waveform-mixup entries leaf_forward_mix_f32, leaf_forward_save_mix_f32, leaf_backward_mix_f32,
+                                  leaf_backward_mix_workspace_bytes (which keep refusing LEAF_FLAG_IO_BF16).  Together with
+                                  LEAF_FLAG_IO_BF16 it is redundant and accepted.  LEAF_ALGO_STAGED, explicit or what AUTO
+                                  resolves to, answers LEAF_ERR_UNSUPPORTED before the workspace check and before any launch,
+                                  as for bfloat16 I/O. */
 
 /* algorithm selector for the fused path */
 #define LEAF_ALGO_AUTO   0     /* _FFT_SMALL for a handful of clips of a LEAF geometry; else the FFT kernels when their plan fits and K >= 224 or the geometry has a static instance, else MFMA, else staged */
@@ -299,6 +319,7 @@ int leaf_band_classes_f32(const float* kernel, const float* pool_w, const float*
  * ABI 6: LEAF_FLAG_LOG1P (PCEN off) and LEAF_FLAG_IO_BF16 (x, grad_out, g_x bfloat16 behind the float pointers) as described
  * at the flags; x, grad_out and g_x must be 4-byte (bfloat16: 2-byte) aligned, the workspace 16-byte, else LEAF_ERR_ALIGNMENT.
  * LEAF_FLAG_X_PCM16: x alone is int16 (2-byte aligned), grad_out stays float32, g_x must be NULL (LEAF_ERR_UNSUPPORTED).
+ * LEAF_FLAG_OUT_BF16: grad_out alone is bfloat16 (2-byte aligned), widened where it is read; x and g_x as the other flags say.
  */
 size_t leaf_backward_workspace_bytes(int B, int T, int F, int K, int hop, int flags, int need_dx);
 int leaf_backward_f32(const float* x, int B, int T,
@@ -327,7 +348,8 @@ int leaf_backward_f32(const float* x, int B, int T,
  * forward and backward, mix inside their loads: x' never exists in memory and an int16 batch stays int16 through a training step.
  * Every other selector and path (run-time-geometry kernels of the 2048-sample plan, MFMA, staged) first writes x' behind its own
  * workspace with the kernel of leaf_mixup_f32 and continues on it; the queries below include that copy where it is needed.  Workspace: leaf_forward_mix_workspace_bytes for the same selector,
- * leaf_backward_mix_workspace_bytes for the same flags.  LEAF_ERR_UNSUPPORTED: LEAF_FLAG_IO_BF16 (the mix is defined in fp32),
+ * leaf_backward_mix_workspace_bytes for the same flags.  LEAF_FLAG_OUT_BF16 (bfloat16 out / grad_out) is taken as by the plain entries.
+ * LEAF_ERR_UNSUPPORTED: LEAF_FLAG_IO_BF16 (the mix is defined in fp32),
  * LEAF_FLAG_PEAKNORM (the normalisation would have to follow the mix) and g_x != NULL (dL/dx would be a scatter over mix_perm, and
  * x is data here).  B == 0 is the empty batch as everywhere; mix_perm and mix_lam may then be NULL.
  */
@@ -448,7 +470,8 @@ int leaf_pcen_backward_f32(const float* p, const float* grad_out, int B, int F, 
 size_t leaf_fft_tables_bytes(int F, int K, int hop);
 int leaf_fft_prepare_tables_f32(const float* kernel /*[F][2]*/, const float* pool_w /*[F]*/, int F, int K, int hop,
                                 void* tables, size_t tables_bytes, void* stream);
-/* x is float32, bfloat16 with LEAF_FLAG_IO_BF16 (then out is bfloat16 too) or int16 with LEAF_FLAG_X_PCM16 (out stays float32); workspace >= leaf_workspace_bytes(...,
+/* x is float32, bfloat16 with LEAF_FLAG_IO_BF16 (then out is bfloat16 too) or int16 with LEAF_FLAG_X_PCM16 (out stays float32);
+ * LEAF_FLAG_OUT_BF16 makes out bfloat16 for a float32 or int16 x; workspace >= leaf_workspace_bytes(...,
  * LEAF_ALGO_FFT). */
 int leaf_forward_prepared_f32(const float* x, int B, int T, const void* tables, size_t tables_bytes,
                               const float* pool_b, const float* alpha, const float* delta, const float* root,

@@ -31,6 +31,7 @@ def algo_reserve_cus(k: int) -> int:
 
 FLAG_PCEN, FLAG_LOG1P, FLAG_IO_BF16, FLAG_BWD_STAGED, FLAG_BWD_MFMA, FLAG_PEAKNORM, FLAG_BWD_FULL_TRANSFORMS = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
 FLAG_X_PCM16 = 0x100           # x is int16 PCM (a sample v means v / 32768); everything else stays float32
+FLAG_OUT_BF16 = 0x200          # the feature side alone is bfloat16: out of the forward, grad_out of the backward; x as its own flags say
 FLAG_BWD_STRICT_BAND_CLASSES = 0x80   # leaf_backward_f32: the backward's band classes by round 5's rule alone (default: the forward's bias-aware decision)
 ALGO_STREAM_FINALIZE = 1 << 25   # LEAF_ALGO_STREAM_FINALIZE: per-frame sums in an LDS ring, finalized as the blocks complete
 ALGO_FULL_TRANSFORMS = 1 << 26   # LEAF_ALGO_FULL_TRANSFORMS: no band-limited filter tasks (every filter on 2048-point transforms)
@@ -298,7 +299,8 @@ def batch_slices(B: int, T: int):
 
 
 def _pcm16_lands_on_staged(lib, x2: torch.Tensor, F: int, K: int, hop: int, algo: int) -> bool:
-    """Whether one C-ABI forward call on the int16 batch ``x2`` runs the staged kernels (the explicit selector, or what AUTO resolves to)."""
+    """Whether one C-ABI forward call on the batch ``x2`` (int16, or any waveform whose features are to be bfloat16) runs the staged
+    kernels (the explicit selector, or what AUTO resolves to)."""
     B, T = x2.shape
     if B == 0 or B * T >= (1 << 31):
         return False
@@ -311,9 +313,12 @@ def _pcm16_lands_on_staged(lib, x2: torch.Tensor, F: int, K: int, hop: int, algo
 
 def leaf_forward(x: torch.Tensor, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int,
                  pcen: bool = True, log1p: bool = False, algo: int = ALGO_AUTO,
-                 out: Optional[torch.Tensor] = None, save_raw: bool = False, peak_normalize: bool = False):
+                 out: Optional[torch.Tensor] = None, save_raw: bool = False, peak_normalize: bool = False,
+                 out_bf16: bool = False):
     """x (B,1,T) or (B,T) float32 (bfloat16, or int16 PCM: a sample v means v / 32768) on a HIP device -> (B,F,T').  Wraps leaf_forward_f32 (leaf_forward_save_f32 when
-    ``save_raw``: then returns (out, pooled_raw) for the backward)."""
+    ``save_raw``: then returns (out, pooled_raw) for the backward).  ``out_bf16``: bfloat16 features from a float32 or int16
+    waveform (LEAF_FLAG_OUT_BF16) -- the float32 call's result rounded to nearest even where the kernels store it; the mode is
+    explicit, never inferred from a tensor's dtype (redundant for a bfloat16 ``x``)."""
     lib = load()
     require_hip(x, "leaf_forward")
     if x.dim() == 3:
@@ -327,18 +332,32 @@ def leaf_forward(x: torch.Tensor, kernel, pool_w, pool_b, alpha, delta, root, em
     dev = x.device
     # extensions: bf16 waveform in, bf16 features out; int16 PCM waveform in (v / 32768), float32 features out; fp32 arithmetic
     x2, flags = _dev_x(x2, dev)
-    io_bf16 = flags == FLAG_IO_BF16
+    out_bf16 = bool(out_bf16) and flags != FLAG_IO_BF16    # (a bfloat16 x: the features are bfloat16 already)
+    io_bf16 = flags == FLAG_IO_BF16 or out_bf16            # the FEATURE dtype below
     B, T = x2.shape
     F = kernel.shape[0]
     kernel = _dev_f32(kernel, "kernel", dev)
     pool_w = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
     pool_b = _dev_f32(pool_b, "pool_b", dev)
-    if flags == FLAG_X_PCM16:
+    if out_bf16 and _pcm16_lands_on_staged(lib, x2, F, K, hop, algo):
+        # the staged forward stores float32 only (LEAF_ERR_UNSUPPORTED from the C ABI): run it in float32 and narrow here -- the
+        # same rounding, so the same bits (how an int16 waveform is handled on that path, below)
+        if out is not None and (out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != dev
+                                or tuple(out.shape) != (B, F, lib.leaf_num_frames(T, K, hop))):
+            raise RuntimeError(f"out must be a contiguous {(B, F, lib.leaf_num_frames(T, K, hop))} tensor on {dev} matching the input dtype (float32; bfloat16 for bfloat16 x)")
+        r = leaf_forward(x2, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen=pcen, log1p=log1p, algo=algo,
+                         save_raw=save_raw, peak_normalize=peak_normalize)
+        f32 = r[0] if save_raw else r
+        narrowed = f32.to(torch.bfloat16) if out is None else out.copy_(f32)
+        return (narrowed, r[1]) if save_raw else narrowed
+    if out_bf16:
+        flags |= FLAG_OUT_BF16
+    if flags & FLAG_X_PCM16:
         peak_normalize = False                     # |v / 32768| <= 1: nothing to normalise for int16, and nothing is launched
         # the staged forward reads float32 only (LEAF_ERR_UNSUPPORTED from the C ABI): where the call lands on it, convert here
         # -- the same values, v / 32768 exactly -- and run the float path (a batch beyond one C-ABI call: slice by slice, below)
         if _pcm16_lands_on_staged(lib, x2, F, K, hop, algo):
-            x2, flags = x2.float().mul_(2.0 ** -15), 0
+            x2, flags = x2.float().mul_(2.0 ** -15), 0         # (never with out_bf16: that call took the branch above)
     if peak_normalize:
         flags |= FLAG_PEAKNORM                     # forward of the peak-normalised clips, the scale folded into the finalize
     if pcen:
@@ -371,7 +390,7 @@ def leaf_forward(x: torch.Tensor, kernel, pool_w, pool_b, alpha, delta, root, em
         raw = torch.empty((B, F, TP), dtype=torch.float32, device=dev) if save_raw else None
         for b0, b1 in batch_slices(B, T):
             r = leaf_forward(x2[b0:b1], kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen=pcen, log1p=log1p, algo=algo,
-                             out=out[b0:b1], save_raw=save_raw, peak_normalize=peak_normalize)
+                             out=out[b0:b1], save_raw=save_raw, peak_normalize=peak_normalize, out_bf16=out_bf16)
             if save_raw:
                 raw[b0:b1].copy_(r[1])
         return (out, raw) if save_raw else out
@@ -395,30 +414,38 @@ def leaf_forward(x: torch.Tensor, kernel, pool_w, pool_b, alpha, delta, root, em
 def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, grad_out: torch.Tensor,
                   pcen: bool = True, need_dx: bool = False, staged: bool = False,
                   pooled_raw: Optional[torch.Tensor] = None, mfma: bool = False, full_transforms: bool = False,
-                  strict_band_classes: bool = False, log1p: bool = False):
+                  strict_band_classes: bool = False, log1p: bool = False, out_bf16: bool = False):
     """Gradients of the forward w.r.t. (kernel, pool_w, pool_b, alpha, delta, root, ema_w[, x]).  Wraps leaf_backward_f32.
     ``staged`` / ``mfma`` force the staged kernels / the fused MFMA backward (default: the overlap-save backward where
     it applies, else MFMA, else staged).  ``log1p``: the backward of the log1p-compressed forward (PCEN off; ignored with
     PCEN on, as in the forward).  A bfloat16 ``x`` selects bfloat16 I/O: ``grad_out`` is bfloat16 too and dL/dx comes back
     in bfloat16; the parameter gradients and ``pooled_raw`` are float32.  An int16 ``x`` (PCM, v / 32768) keeps ``grad_out`` float32
-    and has no dL/dx (``need_dx=True`` raises)."""
+    and has no dL/dx (``need_dx=True`` raises).  ``out_bf16`` (LEAF_FLAG_OUT_BF16, the backward of ``leaf_forward(..., out_bf16=True)``):
+    ``grad_out`` alone is bfloat16, widened where the kernels read it -- the gradients are those of the call on ``grad_out.float()``
+    bit for bit; ``x`` stays float32 (dL/dx float32) or int16."""
     lib = load()
     require_hip(x, "leaf_backward")
     dev = x.device
     x2 = x[:, 0, :] if x.dim() == 3 else x
     x2, io_flags = _dev_x(x2, dev)
     io_bf16 = io_flags == FLAG_IO_BF16
-    if io_flags == FLAG_X_PCM16 and need_dx:
+    if (io_flags & FLAG_X_PCM16) and need_dx:
         raise RuntimeError("an int16 (PCM) input has no gradient: need_dx=True needs a float32 or bfloat16 x")
     B, T = x2.shape
     F = kernel.shape[0]
     kernel = _dev_f32(kernel, "kernel", dev)
     pw = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
     pb = _dev_f32(pool_b, "pool_b", dev)
+    out_bf16 = bool(out_bf16) and not io_bf16              # (a bfloat16 x: grad_out is bfloat16 already)
     if io_bf16:
         if grad_out.dtype != torch.bfloat16 or grad_out.device != dev:
             raise RuntimeError(f"grad_out must be bfloat16 on {dev} when x is bfloat16, got {grad_out.dtype} on {grad_out.device}")
         go = grad_out.detach().contiguous()
+    elif out_bf16:
+        if grad_out.dtype != torch.bfloat16 or grad_out.device != dev:
+            raise RuntimeError(f"grad_out must be bfloat16 on {dev} with out_bf16=True, got {grad_out.dtype} on {grad_out.device}")
+        go = grad_out.detach().contiguous()
+        io_flags |= FLAG_OUT_BF16
     else:
         go = _dev_f32(grad_out, "grad_out", dev)
     TP = lib.leaf_num_frames(T, K, hop)
@@ -444,7 +471,7 @@ def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, 
         for b0, b1 in batch_slices(B, T):
             g = leaf_backward(x2[b0:b1], kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, go[b0:b1], pcen=pcen, need_dx=need_dx,
                               staged=staged, pooled_raw=None if pooled_raw is None else pooled_raw[b0:b1], mfma=mfma,
-                              full_transforms=full_transforms, strict_band_classes=strict_band_classes, log1p=log1p)
+                              full_transforms=full_transforms, strict_band_classes=strict_band_classes, log1p=log1p, out_bf16=out_bf16)
             if need_dx:
                 g_x[b0:b1].copy_(g[7])
             total = list(g[:7]) if total is None else [None if a is None else a.add_(b) for a, b in zip(total, g[:7])]
@@ -521,9 +548,10 @@ def mixup(x: torch.Tensor, perm, lam) -> torch.Tensor:
 
 
 def leaf_forward_mix(x: torch.Tensor, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int,
-                     pcen: bool = True, log1p: bool = False, algo: int = ALGO_AUTO, save_raw: bool = False):
+                     pcen: bool = True, log1p: bool = False, algo: int = ALGO_AUTO, save_raw: bool = False, out_bf16: bool = False):
     """``leaf_forward`` of the mixed batch ``x * lam + x[perm] * (1 - lam)`` without materialising it where the kernels mix in their
-    loads (leaf_forward_mix_f32 / leaf_forward_save_mix_f32).  x float32 or int16 PCM; bfloat16 raises."""
+    loads (leaf_forward_mix_f32 / leaf_forward_save_mix_f32).  x float32 or int16 PCM; bfloat16 raises.  ``out_bf16``: bfloat16
+    features (LEAF_FLAG_OUT_BF16), the float32 result rounded where it is stored."""
     lib = load()
     x2 = _mix_x(x, "leaf_forward_mix")
     dev = x2.device
@@ -547,9 +575,13 @@ def leaf_forward_mix(x: torch.Tensor, perm, lam, kernel, pool_w, pool_b, alpha, 
         raise RuntimeError(f"bad shape B={B} T={T} K={K} hop={hop}")
     if (algo & 0xff) not in (ALGO_AUTO, ALGO_STAGED, ALGO_MFMA, ALGO_FFT, ALGO_FFT_WG, ALGO_FFT_SMALL):
         raise RuntimeError(f"unknown algorithm selector {algo & 0xff}")
-    out = torch.empty((B, F, TP), dtype=torch.float32, device=dev)
+    staged_cast = bool(out_bf16) and _pcm16_lands_on_staged(lib, x2, F, K, hop, algo)   # the staged forward stores float32: narrow here
+    if out_bf16 and not staged_cast:
+        flags |= FLAG_OUT_BF16
+    out = torch.empty((B, F, TP), dtype=torch.bfloat16 if flags & FLAG_OUT_BF16 else torch.float32, device=dev)
     raw = torch.empty((B, F, TP), dtype=torch.float32, device=dev) if save_raw else None
     if B == 0:
+        out = out.to(torch.bfloat16) if out_bf16 else out
         return (out, raw) if save_raw else out
     if B * T >= (1 << 31):
         raise RuntimeError("leaf_forward_mix: a batch beyond one C-ABI call (B * T >= 2^31) cannot be mixed across its slices")
@@ -560,19 +592,19 @@ def leaf_forward_mix(x: torch.Tensor, perm, lam, kernel, pool_w, pool_b, alpha, 
                                                _ptr(alpha), _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, algo, _ptr(out),
                                                _ptr(raw), _ptr(ws), ws.numel(), stream_ptr(dev))
             check(rc, "leaf_forward_save_mix_f32")
-            return out, raw
+            return (out.to(torch.bfloat16) if staged_cast else out), raw
         rc = lib.leaf_forward_mix_f32(_ptr(x2), _ptr(perm), _ptr(lam), B, T, _ptr(kernel), _ptr(pool_w), _ptr(pool_b), _ptr(alpha),
                                       _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, algo, _ptr(out), _ptr(ws), ws.numel(),
                                       stream_ptr(dev))
     check(rc, "leaf_forward_mix_f32")
-    return out
+    return out.to(torch.bfloat16) if staged_cast else out
 
 
 def leaf_backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, grad_out: torch.Tensor,
                       pcen: bool = True, staged: bool = False, pooled_raw: Optional[torch.Tensor] = None, mfma: bool = False,
-                      full_transforms: bool = False, strict_band_classes: bool = False, log1p: bool = False):
+                      full_transforms: bool = False, strict_band_classes: bool = False, log1p: bool = False, out_bf16: bool = False):
     """Parameter gradients of ``leaf_forward_mix`` (leaf_backward_mix_f32): the seven of ``leaf_backward`` and None for dL/dx,
-    which a mixed call does not have."""
+    which a mixed call does not have.  ``out_bf16``: ``grad_out`` is bfloat16 (LEAF_FLAG_OUT_BF16), widened where it is read."""
     lib = load()
     x2 = _mix_x(x, "leaf_backward_mix")
     dev = x2.device
@@ -582,7 +614,12 @@ def leaf_backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, 
     kernel = _dev_f32(kernel, "kernel", dev)
     pw = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
     pb = _dev_f32(pool_b, "pool_b", dev)
-    go = _dev_f32(grad_out, "grad_out", dev)
+    if out_bf16:
+        if grad_out.dtype != torch.bfloat16 or grad_out.device != dev:
+            raise RuntimeError(f"grad_out must be bfloat16 on {dev} with out_bf16=True, got {grad_out.dtype} on {grad_out.device}")
+        go = grad_out.detach().contiguous()
+    else:
+        go = _dev_f32(grad_out, "grad_out", dev)
     TP = lib.leaf_num_frames(T, K, hop)
     if tuple(go.shape) != (B, F, TP):
         raise RuntimeError(f"grad_out has shape {tuple(go.shape)}, expected {(B, F, TP)}")
@@ -603,7 +640,8 @@ def leaf_backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, 
         raise RuntimeError("leaf_backward_mix: a batch beyond one C-ABI call (B * T >= 2^31) cannot be mixed across its slices")
     flags = ((FLAG_PCEN if pcen else 0) | (FLAG_BWD_STAGED if staged else 0) | (FLAG_BWD_MFMA if mfma else 0) |
              (FLAG_BWD_FULL_TRANSFORMS if full_transforms else 0) | (FLAG_BWD_STRICT_BAND_CLASSES if strict_band_classes else 0) |
-             (FLAG_LOG1P if log1p and not pcen else 0) | (FLAG_X_PCM16 if x2.dtype == torch.int16 else 0))
+             (FLAG_LOG1P if log1p and not pcen else 0) | (FLAG_X_PCM16 if x2.dtype == torch.int16 else 0) |
+             (FLAG_OUT_BF16 if out_bf16 else 0))
     with torch.cuda.device(dev):
         ws = workspace(lib.leaf_backward_mix_workspace_bytes(B, T, F, K, hop, flags), dev)
         rc = lib.leaf_backward_mix_f32(_ptr(x2), _ptr(perm), _ptr(lam), B, T, _ptr(kernel), _ptr(pw), _ptr(pb), _ptr(alpha),
@@ -907,8 +945,10 @@ def prepare_tables(kernel: torch.Tensor, pool_w: torch.Tensor, K: int, hop: int)
 
 
 def leaf_forward_prepared(x: torch.Tensor, tables: torch.Tensor, pool_b, alpha, delta, root, ema_w, F: int, K: int, hop: int,
-                          pcen: bool = True, log1p: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Forward with tables from ``prepare_tables`` (same outputs as ``leaf_forward``, without the table kernel)."""
+                          pcen: bool = True, log1p: bool = False, out: Optional[torch.Tensor] = None,
+                          out_bf16: bool = False) -> torch.Tensor:
+    """Forward with tables from ``prepare_tables`` (same outputs as ``leaf_forward``, without the table kernel).  ``out_bf16``:
+    bfloat16 features from a float32 or int16 waveform (LEAF_FLAG_OUT_BF16)."""
     lib = load()
     require_hip(x, "leaf_forward_prepared")
     if x.dim() == 3:
@@ -921,7 +961,9 @@ def leaf_forward_prepared(x: torch.Tensor, tables: torch.Tensor, pool_b, alpha, 
         raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
     dev = x.device
     x2, flags = _dev_x(x2, dev)
-    io_bf16 = flags == FLAG_IO_BF16
+    if out_bf16 and flags != FLAG_IO_BF16:
+        flags |= FLAG_OUT_BF16
+    io_bf16 = bool(flags & (FLAG_IO_BF16 | FLAG_OUT_BF16))   # the feature dtype
     B, T = x2.shape
     pool_b = _dev_f32(pool_b, "pool_b", dev)
     if pcen:

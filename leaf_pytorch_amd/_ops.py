@@ -70,33 +70,35 @@ def _frames(T: int, K: int, hop: int) -> int:
     return (T + pad_l + pad_r - K) // hop + 1
 
 
-def _out_dtype(x: torch.Tensor) -> torch.dtype:
-    """Feature dtype for a waveform: bfloat16 clips give bfloat16 features, int16 PCM (like float32) gives float32."""
-    return torch.bfloat16 if x.dtype == torch.bfloat16 else torch.float32
+def _out_dtype(x: torch.Tensor, out_bf16: bool = False) -> torch.dtype:
+    """Feature dtype for a waveform: bfloat16 clips give bfloat16 features, int16 PCM (like float32) gives float32 -- or bfloat16
+    when the call asks for it (``out_bf16``: LEAF_FLAG_OUT_BF16)."""
+    return torch.bfloat16 if x.dtype == torch.bfloat16 or out_bf16 else torch.float32
 
 
 def _register_python_side() -> None:
     @torch.library.register_fake("leaf_amd::forward")
-    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo):
-        return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)), dtype=_out_dtype(x))
+    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo, out_bf16=False):
+        return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)), dtype=_out_dtype(x, out_bf16))
 
     @torch.library.register_fake("leaf_amd::forward_train")
-    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p=False):
+    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p=False, out_bf16=False):
         shape = (x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop))
-        return x.new_empty(shape, dtype=_out_dtype(x)), x.new_empty(shape, dtype=torch.float32)
+        return x.new_empty(shape, dtype=_out_dtype(x, out_bf16)), x.new_empty(shape, dtype=torch.float32)
 
     @torch.library.register_fake("leaf_amd::backward")
-    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out, pooled_raw, need_dx, flags):
+    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out, pooled_raw, need_dx, flags, out_bf16=False):
         F = kernel.shape[0]
         pc = F if alpha is not None else 0
         e = lambda *s: kernel.new_empty(s)
         return [torch.empty_like(kernel), torch.empty_like(pool_w), torch.empty_like(pool_b), e(pc), e(pc), e(pc), e(pc),
                 torch.empty_like(x) if need_dx else e(0)]            # (g_x in the dtype of x: bfloat16 for bfloat16 I/O)
 
-    def setup_context(ctx, inputs, output):
+    def setup_context(ctx, inputs, keyword_only_inputs, output):
         x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p = inputs
         _, raw = output
         ctx.pcen = alpha is not None
+        ctx.out_bf16 = bool(keyword_only_inputs["out_bf16"])     # the features left in bfloat16: their gradient arrives in bfloat16
         ctx.log1p = bool(log1p) and not ctx.pcen                 # (ignored with PCEN on, as in the forward)
         ctx.geom = (K, hop)
         ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)     # Leaf.full_transforms(): no band tasks in the backward either
@@ -113,32 +115,34 @@ def _register_python_side() -> None:
                                                                      grad_out.contiguous(), raw, need_dx,
                                                                      (_native.FLAG_BWD_FULL_TRANSFORMS if ctx.full else 0) |
                                                                      (_native.FLAG_BWD_STRICT_BAND_CLASSES if ctx.strict else 0) |
-                                                                     (_native.FLAG_LOG1P if ctx.log1p else 0))
+                                                                     (_native.FLAG_LOG1P if ctx.log1p else 0),
+                                                                     out_bf16=ctx.out_bf16)   # (the bfloat16 grad_out goes straight in)
         pc = (ga, gd, gr, gw) if ctx.pcen else (None,) * 4
-        return (gx if need_dx else None, gk, gpw, gpb, *pc, None, None, None, None)
+        return (gx if need_dx else None, gk, gpw, gpb, *pc, None, None, None, None)   # (one per positional input)
 
     torch.library.register_autograd("leaf_amd::forward_train", backward, setup_context=setup_context)
 
     # ---- waveform mixup: the same three ops with (perm, lam) behind x; parameter gradients only
     @torch.library.register_fake("leaf_amd::forward_mix")
-    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo):
-        return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)), dtype=torch.float32)
+    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo, out_bf16=False):
+        return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)), dtype=torch.bfloat16 if out_bf16 else torch.float32)
 
     @torch.library.register_fake("leaf_amd::forward_train_mix")
-    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p=False):
+    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p=False, out_bf16=False):
         shape = (x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop))
-        return x.new_empty(shape, dtype=torch.float32), x.new_empty(shape, dtype=torch.float32)
+        return x.new_empty(shape, dtype=torch.bfloat16 if out_bf16 else torch.float32), x.new_empty(shape, dtype=torch.float32)
 
     @torch.library.register_fake("leaf_amd::backward_mix")
-    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out, pooled_raw, flags):
+    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out, pooled_raw, flags, out_bf16=False):
         pc = kernel.shape[0] if alpha is not None else 0
         e = lambda *s: kernel.new_empty(s)
         return [torch.empty_like(kernel), torch.empty_like(pool_w), torch.empty_like(pool_b), e(pc), e(pc), e(pc), e(pc)]
 
-    def setup_context_mix(ctx, inputs, output):
+    def setup_context_mix(ctx, inputs, keyword_only_inputs, output):
         x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p = inputs
         _, raw = output
         ctx.pcen = alpha is not None
+        ctx.out_bf16 = bool(keyword_only_inputs["out_bf16"])
         ctx.log1p = bool(log1p) and not ctx.pcen
         ctx.geom = (K, hop)
         ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)
@@ -157,7 +161,8 @@ def _register_python_side() -> None:
                                                                        hop, grad_out.contiguous(), raw,
                                                                        (_native.FLAG_BWD_FULL_TRANSFORMS if ctx.full else 0) |
                                                                        (_native.FLAG_BWD_STRICT_BAND_CLASSES if ctx.strict else 0) |
-                                                                       (_native.FLAG_LOG1P if ctx.log1p else 0))
+                                                                       (_native.FLAG_LOG1P if ctx.log1p else 0),
+                                                                       out_bf16=ctx.out_bf16)
         pc = (ga, gd, gr, gw) if ctx.pcen else (None,) * 4
         return (None, None, None, gk, gpw, gpb, *pc, None, None, None, None)
 
@@ -167,20 +172,21 @@ def _register_python_side() -> None:
 
 
 def forward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, log1p: bool = False,
-            algo: int = _native.ALGO_AUTO) -> torch.Tensor:
-    return torch.ops.leaf_amd.forward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo)
+            algo: int = _native.ALGO_AUTO, out_bf16: bool = False) -> torch.Tensor:
+    return torch.ops.leaf_amd.forward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo, out_bf16=out_bf16)
 
 
 def forward_train(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int,
-                  algo: int = _native.ALGO_AUTO, log1p: bool = False) -> torch.Tensor:
-    return torch.ops.leaf_amd.forward_train(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p)[0]
+                  algo: int = _native.ALGO_AUTO, log1p: bool = False, out_bf16: bool = False) -> torch.Tensor:
+    return torch.ops.leaf_amd.forward_train(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p, out_bf16=out_bf16)[0]
 
 
 def forward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, log1p: bool = False,
-                algo: int = _native.ALGO_AUTO) -> torch.Tensor:
-    return torch.ops.leaf_amd.forward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo)
+                algo: int = _native.ALGO_AUTO, out_bf16: bool = False) -> torch.Tensor:
+    return torch.ops.leaf_amd.forward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo, out_bf16=out_bf16)
 
 
 def forward_train_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int,
-                      algo: int = _native.ALGO_AUTO, log1p: bool = False) -> torch.Tensor:
-    return torch.ops.leaf_amd.forward_train_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p)[0]
+                      algo: int = _native.ALGO_AUTO, log1p: bool = False, out_bf16: bool = False) -> torch.Tensor:
+    return torch.ops.leaf_amd.forward_train_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p,
+                                                out_bf16=out_bf16)[0]

@@ -73,8 +73,9 @@ def composite_forward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: i
     return (pooled / (PCEN_FLOOR + m) ** a + d) ** inv_r - d ** inv_r
 
 
-def setup_context(ctx, inputs, output):
+def setup_context(ctx, inputs, output, keyword_only_inputs=None):
     x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out, pooled_raw, need_dx, flags = inputs
+    ctx.out_bf16 = bool((keyword_only_inputs or {}).get("out_bf16", False))   # leaf_amd::backward's keyword: grad_out alone is bfloat16
     ctx.pcen = alpha is not None
     ctx.geom = (K, hop)
     ctx.need_dx = bool(need_dx)
@@ -90,6 +91,9 @@ def backward(ctx, grads):
     if getattr(ctx, "io_bf16", False):
         raise RuntimeError("gradients of gradients through Leaf are float32 only: second order with bfloat16 I/O is not supported "
                            "(feed float32 waveforms for create_graph=True)")
+    if getattr(ctx, "out_bf16", False):
+        raise RuntimeError("gradients of gradients through Leaf are float32 only: second order with bfloat16 features "
+                           "(Leaf.output_dtype) is not supported (leave the features float32 for create_graph=True)")
     if getattr(ctx, "x_pcm16", False):
         raise RuntimeError("gradients of gradients through Leaf are float32 only: second order with an int16 (PCM) waveform is not "
                            "supported (feed x.float() / 32768 for create_graph=True)")
@@ -122,7 +126,7 @@ def backward(ctx, grads):
     return gx, gk, gpw, gpb, *gpc, None, None, ggo, None, None, None
 
 
-def _setup_context_mix(ctx, inputs, output):
+def _setup_context_mix(ctx, inputs, output, keyword_only_inputs=None):
     pass
 
 

@@ -27,6 +27,9 @@ __device__ __forceinline__ unsigned short bf16_round(float v) {
 // Sample type of a waveform buffer, carried in the parameter structs' `io_bf16` field (the name predates 16-bit PCM): 0 fp32,
 // 1 bfloat16 (LEAF_FLAG_IO_BF16), 2 16-bit PCM (LEAF_FLAG_X_PCM16).  A PCM sample v means v / 32768: the int -> float conversion and
 // the scaling by a power of two are both exact, so the result is bit for bit what a caller's float(v) / 32768 holds.
+// The FEATURE type (out of the forward, grad_out of the backward) is a second, independent type: float32 or bfloat16
+// (LEAF_FLAG_OUT_BF16; LEAF_FLAG_IO_BF16 sets both), carried as bit 2 of the kernels' `mode` -- stored through io_store / bf16_round,
+// read through io_load.
 constexpr int kSampleF32 = 0, kSampleBf16 = 1, kSamplePcm16 = 2;
 __device__ __forceinline__ float pcm16_widen(short v) { return (float)(int)v * 0x1p-15f; }
 // element i of an I/O buffer of sample type `st` (one of the three codes above, nothing else: a mode bit is mapped by the caller)

@@ -1107,7 +1107,7 @@ __global__ __launch_bounds__(kFftWaves * 64, 2) void leaf_fft_kernel(const FftPa
 // part is [B][F][nslot][T'] (frame-contiguous).  Per frame: sum of the valid slots in block order (a frame's window meets
 // one or two blocks, three when K - 1 > L: computed from the geometry, so the buffer needs no zero fill), x s_b^2 with
 // LEAF_FLAG_PEAKNORM, + bias (pooling.py:41) -> floor (frontend.py:84) -> EMA (postprocessing.py:13-28) -> PCEN
-// (postprocessing.py:62-69).  Mode bits: 1 PCEN, 2 log1p, 4 bf16 output, 8 no floor (the backward's raw pooled tensor).
+// (postprocessing.py:62-69).  Mode bits: 1 PCEN, 2 log1p, 4 bfloat16 features, 8 no floor (the backward's raw pooled tensor).
 //
 // ONE arithmetic for every kernel that finalizes (round 3): the functions below.  The EMA is the reference's own
 // recurrence, evaluated sequentially in its fp32 operation order -- acc = (w * x) + ((1 - w) * acc), acc_{-1} = x_0 -- so
@@ -1179,12 +1179,9 @@ __device__ __forceinline__ float fin_point_pcen_pos(const FinCoef& c, float floo
     return fin_point(c, mode, floor_, p, M);
 }
 __device__ __forceinline__ void fin_store(const FinParams& q, size_t o, float v) {
-    if (q.mode & 4) {                                            // bf16 output, round to nearest even
-        const unsigned u = __float_as_uint(v);
-        static_cast<unsigned short*>(q.out)[o] = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-    } else {
-        static_cast<float*>(q.out)[o] = v;
-    }
+    // mode bit 2 is the FEATURE type (LEAF_FLAG_OUT_BF16, or LEAF_FLAG_IO_BF16 for both sides); the waveform's sample type travels
+    // separately, in the parameter structs' `io_bf16` field
+    io_store(q.out, o, q.mode & 4, v);
 }
 
 // A tile of up to 64 rows x all T' frames, 64 frames at a time, by NTHREADS threads of one workgroup (all of them call;

@@ -614,10 +614,9 @@ __global__ __launch_bounds__(kFinThreads) void finalize_kernel(
                 r1 = log1pf(v1);
             }
             const size_t o = ((size_t)b * F + f) * TP + m0 + j0;
-            if (mode & 4) {                                  // bf16 output, round to nearest even
-                const unsigned u0 = __float_as_uint(r0), u1 = __float_as_uint(r1);
-                if (j0 < nm) outh[o] = (unsigned short)((u0 + 0x7fffu + ((u0 >> 16) & 1u)) >> 16);
-                if (j1 < nm) outh[o + 1] = (unsigned short)((u1 + 0x7fffu + ((u1 >> 16) & 1u)) >> 16);
+            if (mode & 4) {                                  // bfloat16 features (the feature type, whatever x is): nearest even, torch's NaN
+                if (j0 < nm) outh[o] = bf16_round(r0);
+                if (j1 < nm) outh[o + 1] = bf16_round(r1);
             } else {
                 if (j0 < nm) out[o] = r0;
                 if (j1 < nm) out[o + 1] = r1;

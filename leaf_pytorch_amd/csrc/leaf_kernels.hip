@@ -603,6 +603,9 @@ template <class... P> inline bool any_misaligned(const P*... p) { return (misali
 // accesses -- float2 / float4 / int4 rows, 16-byte direct-to-LDS loads, the 64-bit seam tickets: 16-byte aligned
 inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 // sample type of the waveform buffer (leaf_common.hpp kSample*), the value the kernels' `io_bf16` field carries
+// is the feature side (out of the forward, grad_out of the backward) bfloat16?  LEAF_FLAG_OUT_BF16 says so for that side alone,
+// LEAF_FLAG_IO_BF16 for both sides; the kernels carry it as bit 2 of their `mode`
+inline bool feat_bf16(int flags) { return (flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_OUT_BF16)) != 0; }
 inline int x_sample_type(int flags) {
     return (flags & LEAF_FLAG_IO_BF16) ? kSampleBf16 : (flags & LEAF_FLAG_X_PCM16) ? kSamplePcm16 : kSampleF32;
 }
@@ -684,7 +687,7 @@ const char* leaf_status_string(int status) {
         case LEAF_ERR_LAUNCH: return "HIP kernel launch failed";
         case LEAF_ERR_NO_DEVICE: return "no usable gfx950 device";
         case LEAF_ERR_ALIGNMENT: return "buffer not 4-byte aligned (2-byte for bfloat16 and 16-bit PCM buffers; 16-byte for workspace and tables)";
-        case LEAF_ERR_UNSUPPORTED: return "combination not supported (bfloat16 I/O and 16-bit PCM input (LEAF_FLAG_X_PCM16) have no staged forward: use float32 buffers; LEAF_FLAG_X_PCM16 excludes LEAF_FLAG_IO_BF16 and has no dL/dx (g_x must be NULL); the waveform-mixup entries (leaf_*_mix_f32) take neither LEAF_FLAG_IO_BF16 nor LEAF_FLAG_PEAKNORM nor g_x; LEAF_FLAG_PEAKNORM needs an overlap-save path and has no backward)";
+        case LEAF_ERR_UNSUPPORTED: return "combination not supported (bfloat16 I/O and 16-bit PCM input (LEAF_FLAG_X_PCM16) and bfloat16 features (LEAF_FLAG_OUT_BF16) have no staged forward: use float32 buffers; LEAF_FLAG_X_PCM16 excludes LEAF_FLAG_IO_BF16 and has no dL/dx (g_x must be NULL); the waveform-mixup entries (leaf_*_mix_f32) take neither LEAF_FLAG_IO_BF16 nor LEAF_FLAG_PEAKNORM nor g_x; LEAF_FLAG_PEAKNORM needs an overlap-save path and has no backward)";
     }
     return "unknown status";
 }
@@ -1155,8 +1158,8 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
         if (sel != LEAF_ALGO_AUTO && sel != LEAF_ALGO_STAGED && sel != LEAF_ALGO_MFMA && sel != LEAF_ALGO_FFT && sel != LEAF_ALGO_FFT_WG &&
             sel != LEAF_ALGO_FFT_SMALL)
             return LEAF_ERR_BAD_ALGO;
-        if ((flags & LEAF_FLAG_X_PCM16) && (flags & LEAF_FLAG_IO_BF16)) return LEAF_ERR_UNSUPPORTED;   // int16 in with bfloat16 out: not built
-        if ((flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16)) && sel == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
+        if ((flags & LEAF_FLAG_X_PCM16) && (flags & LEAF_FLAG_IO_BF16)) return LEAF_ERR_UNSUPPORTED;   // two types for x (int16 in, bfloat16 out: LEAF_FLAG_OUT_BF16)
+        if ((flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16 | LEAF_FLAG_OUT_BF16)) && sel == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
         if (B == 0 && !inst_layouts_ok()) return LEAF_ERR_LAUNCH;
     }
     if (empty_batch(B, T, F, K, hop)) return LEAF_OK;
@@ -1166,9 +1169,9 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
     int rc = check_shape(B, T, F, K, hop);
     if (rc != LEAF_OK) return rc;
     {
-        const uintptr_t io_mask = (flags & LEAF_FLAG_IO_BF16) ? 1u : 3u;
-        const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;       // 16-bit PCM: x alone is a 2-byte buffer
-        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & io_mask) || misaligned16(workspace) ||
+        const uintptr_t out_mask = feat_bf16(flags) ? 1u : 3u;                                       // bfloat16 features: 2-byte elements
+        const uintptr_t x_mask = (flags & (LEAF_FLAG_X_PCM16 | LEAF_FLAG_IO_BF16)) ? 1u : 3u;        // 16-bit PCM / bfloat16 waveform
+        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & out_mask) || misaligned16(workspace) ||
             any_misaligned(kernel, pool_w, pool_b, alpha, delta, root, ema_w, pooled_raw))
             return LEAF_ERR_ALIGNMENT;
     }
@@ -1179,18 +1182,19 @@ static int forward_impl(const void* x, int B, int T, const float* kernel, const 
         algo != LEAF_ALGO_FFT_WG && algo != LEAF_ALGO_FFT_SMALL)
         return LEAF_ERR_BAD_ALGO;
     const FusedPlan pl = make_plan(B, T, F, K, hop);
-    const bool io_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;
-    const int xtype = x_sample_type(flags);                                           // what the kernels read x as; out follows io_bf16 alone
-    if (xtype != kSampleF32 && algo == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED; // 16-bit input is a fused-path feature
+    const bool out_bf16 = feat_bf16(flags);                                           // what the finalize sites store out as
+    const int xtype = x_sample_type(flags);                                           // what the kernels read x as: the two types are independent
+    const bool fused_only = xtype != kSampleF32 || out_bf16;                          // 16-bit input and bfloat16 features are fused-path features
+    if (fused_only && algo == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
     if (algo == LEAF_ALGO_MFMA && !pl.ok) return LEAF_ERR_BAD_ALGO;
     if (algo == LEAF_ALGO_AUTO) algo = auto_algo(B, T, F, K, hop);
-    if (xtype != kSampleF32 && algo == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
+    if (fused_only && algo == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
     // a PCM sample means v / 32768, so no clip's peak exceeds 1: peak normalisation is the identity (no pre-pass, every scale 1)
     if (xtype == kSamplePcm16) flags &= ~LEAF_FLAG_PEAKNORM;
     const size_t need = leaf_workspace_bytes(B, T, F, K, hop, algo);
     if (!workspace || workspace_bytes < need) return LEAF_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (io_bf16 ? 4 : 0);
+    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (out_bf16 ? 4 : 0);
     const int TP = pl.TP;
     float* ws = static_cast<float*>(workspace);
     // LEAF_FLAG_PEAKNORM: per-clip scales into the tail of the workspace (the last align_up(B, 64) floats the overlap-save
@@ -1429,7 +1433,7 @@ static int forward_mix_impl(const void* x, const int* mix_perm, const float* mix
                             const float* pool_w, const float* pool_b, const float* alpha, const float* delta, const float* root,
                             const float* ema_w, int F, int K, int hop, int flags, int algo, void* out, float* pooled_raw,
                             void* workspace, size_t workspace_bytes, void* stream) {
-    // bfloat16 is not mixed (the definition is fp32); peak normalisation would have to follow the mix, which the fused loads cannot do
+    // a bfloat16 waveform is not mixed (the definition is fp32; bfloat16 FEATURES, LEAF_FLAG_OUT_BF16, pass through); peak normalisation would have to follow the mix, which the fused loads cannot do
     if (flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_PEAKNORM)) return LEAF_ERR_UNSUPPORTED;
     if (empty_batch(B, T, F, K, hop))                        // selector and layout checks as without the mix; nothing is read
         return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags & ~LEAF_FLAG_X_PCM16, algo, out, workspace,
@@ -1445,6 +1449,8 @@ static int forward_mix_impl(const void* x, const int* mix_perm, const float* mix
     const ReserveCus reserve(algo);                          // AUTO resolves as forward_impl will
     if (sel == LEAF_ALGO_AUTO) sel = auto_algo(B, T, F, K, hop);
     algo = (algo & ~0xff) | sel;
+    // bfloat16 features have no staged forward (as in forward_impl): answered here, before the workspace check and the mixed copy
+    if ((flags & LEAF_FLAG_OUT_BF16) && sel == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
     if (mix_fused_forward(B, T, F, K, hop, sel)) {
         const MixScope mix(MixArgs{mix_perm, mix_lam});
         return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out, workspace,
@@ -1604,14 +1610,14 @@ int leaf_forward_prepared_f32(const float* x, int B, int T, const void* tables, 
     const FftPlan fp = make_fft_plan(B, T, F, K, hop);
     if (!fp.ok) return LEAF_ERR_BAD_ALGO;
     if (tables_bytes < leaf_fft_tables_bytes(F, K, hop)) return LEAF_ERR_WORKSPACE;
-    const bool io_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;
-    const uintptr_t io_mask = io_bf16 ? 1u : 3u;
-    const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;
-    if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & io_mask) || misaligned16(workspace) ||
+    const bool out_bf16 = feat_bf16(flags);
+    const uintptr_t out_mask = out_bf16 ? 1u : 3u;
+    const uintptr_t x_mask = (flags & (LEAF_FLAG_X_PCM16 | LEAF_FLAG_IO_BF16)) ? 1u : 3u;
+    if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & out_mask) || misaligned16(workspace) ||
         misaligned16(tables) || any_misaligned(pool_b, alpha, delta, root, ema_w))
         return LEAF_ERR_ALIGNMENT;
     if (!workspace || workspace_bytes < (align_up(fp.part_floats, 64) + (LEAF_TRACE ? 16 * 64 * 2 : 0)) * 4) return LEAF_ERR_WORKSPACE;
-    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (io_bf16 ? 4 : 0);
+    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (out_bf16 ? 4 : 0);
     // the edge tables of the band-limited filter tasks (they depend on the clip length) go behind the partial sums when the
     // workspace has the room (it has when sized by leaf_workspace_bytes as documented); otherwise full transforms
     const size_t part_end = align_up(fp.part_floats, 64) + (LEAF_TRACE ? 16 * 64 * 2 : 0);
@@ -1911,6 +1917,7 @@ static int backward_impl(const float* x, const int* mix_perm, const float* mix_l
                       void* workspace, size_t workspace_bytes, void* stream) {
     // LEAF_FLAG_IO_BF16: x, grad_out and g_x are bfloat16 buffers behind the float pointers (as in the forward); everything else fp32
     // LEAF_FLAG_X_PCM16: x alone is a 16-bit PCM buffer (v / 32768); an integer input has no gradient, so g_x must be NULL
+    // LEAF_FLAG_OUT_BF16: grad_out alone is bfloat16 (the feature side); x and g_x follow the two flags above
     if ((flags & LEAF_FLAG_X_PCM16) && ((flags & LEAF_FLAG_IO_BF16) || g_x)) return LEAF_ERR_UNSUPPORTED;
     // mix_lam != NULL: the mixed call (leaf_backward_mix_f32 has refused bfloat16, PEAKNORM, g_x and a missing buffer)
     const bool mixed_call = mix_lam != nullptr;
@@ -1934,11 +1941,12 @@ static int backward_impl(const float* x, const int* mix_perm, const float* mix_l
     int rc = check_shape(B, T, F, K, hop);
     if (rc != LEAF_OK) return rc;
     if (2 * F > 65535 || B > 65535) return LEAF_ERR_BAD_SHAPE;
-    const bool io_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;
+    const bool io_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;   // the waveform side: x and g_x
+    const bool go_bf16 = feat_bf16(flags);                   // the feature side: grad_out
     {
         const uintptr_t io_mask = io_bf16 ? 1u : 3u;
         const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;
-        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(grad_out) & io_mask) ||
+        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(grad_out) & (go_bf16 ? 1u : 3u)) ||
             (reinterpret_cast<uintptr_t>(g_x) & io_mask) || misaligned16(workspace) ||
             any_misaligned(kernel, pool_w, pool_b, alpha, delta, root, ema_w, pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta,
                            g_root, g_ema_w) || any_misaligned(mix_perm, mix_lam))
@@ -1953,7 +1961,8 @@ static int backward_impl(const float* x, const int* mix_perm, const float* mix_l
     const int padL = K / 2 + K % 2 - 1;
     // first-stage mode (pcen_bwd_scan_kernel): bit0 PCEN, bit1 log1p compression (PCEN off only, as in the forward), bit2 bf16 grad_out;
     // param_reduce_kernel reads bit0 alone
-    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (io_bf16 ? 4 : 0);
+    // (grad_out is read by that kernel alone, on every path: a bfloat16 grad_out needs no widened copy anywhere)
+    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (go_bf16 ? 4 : 0);
     float* ws = static_cast<float*>(workspace);
     int xtype = x_sample_type(flags);                        // what the kernels below read x as
     if (mixed_call && bwd_mix_floats(path, B, T, F, K, hop)) {

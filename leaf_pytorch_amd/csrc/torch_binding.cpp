@@ -74,9 +74,12 @@ Params gather(const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b, 
     return p;
 }
 
-Tensor forward_impl(const Tensor& x, const Params& p, int64_t K, int64_t hop, bool log1p, int64_t algo, Tensor* raw) {
+// out_bf16 (LEAF_FLAG_OUT_BF16): bfloat16 features from a float32 or int16 waveform, narrowed where the kernels store them; an explicit
+// argument of the ops, never inferred from a tensor (redundant for a bfloat16 x)
+Tensor forward_impl(const Tensor& x, const Params& p, int64_t K, int64_t hop, bool log1p, int64_t algo, Tensor* raw, bool out_bf16) {
     Tensor x2 = waveform_2d(x);
     const bool io_bf16 = x2.scalar_type() == at::kBFloat16;
+    out_bf16 = out_bf16 && !io_bf16;
     const bool pcm16 = x2.scalar_type() == at::kShort;        // 16-bit PCM in (a sample v means v / 32768), float32 out
     TORCH_CHECK(io_bf16 || pcm16 || x2.scalar_type() == at::kFloat,
                 "x must be float32 (or bfloat16 for the bf16-I/O extension, or int16 PCM), got ", x2.scalar_type());
@@ -85,13 +88,14 @@ Tensor forward_impl(const Tensor& x, const Params& p, int64_t K, int64_t hop, bo
     const int T = (int)x2.size(1), F = (int)p.kernel.size(0);
     const int TP = leaf_num_frames(T, (int)K, (int)hop);
     TORCH_CHECK(TP >= 1 && F >= 1, "bad shape B=", B, " T=", T, " F=", F, " K=", K, " hop=", hop);
-    const auto out_opt = pcm16 ? x2.options().dtype(at::kFloat) : x2.options();
+    const auto out_opt = x2.options().dtype(io_bf16 || out_bf16 ? at::kBFloat16 : at::kFloat);
     if (B == 0) {
         // the empty batch: the reference returns (0, F, T') (frontend.py:78-89 -> convolution.py:97); nothing is launched
         if (raw) *raw = at::empty({0, F, TP}, x2.options().dtype(at::kFloat));
         return at::empty({0, F, TP}, out_opt);
     }
-    int flags = (io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (pcm16 ? LEAF_FLAG_X_PCM16 : 0) | (p.pcen ? LEAF_FLAG_PCEN : (log1p ? LEAF_FLAG_LOG1P : 0));
+    int flags = (io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (pcm16 ? LEAF_FLAG_X_PCM16 : 0) | (out_bf16 ? LEAF_FLAG_OUT_BF16 : 0) |
+                (p.pcen ? LEAF_FLAG_PCEN : (log1p ? LEAF_FLAG_LOG1P : 0));
     // call options travelling in the upper bits of the op's `algo` argument (the schema stays as it is): bit 24 = the
     // PeakNormalization prologue folded into the forward (LEAF_FLAG_PEAKNORM; inference only)
     constexpr int64_t kOptPeakNorm = int64_t(1) << 24;
@@ -102,17 +106,20 @@ Tensor forward_impl(const Tensor& x, const Params& p, int64_t K, int64_t hop, bo
     }
     c10::hip::HIPGuardMasqueradingAsCUDA guard(x2.device());
     auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x2.device().index());
-    bool pcm16_staged = false;
-    if (pcm16) {
-        // the staged forward reads float32 only (LEAF_ERR_UNSUPPORTED from the C ABI): where the call lands on it, each slice is
-        // converted below -- the same values, v / 32768 exactly -- and runs the float path
+    bool pcm16_staged = false, bf16_staged = false;
+    if (pcm16 || out_bf16) {
+        // the staged forward reads and writes float32 only (LEAF_ERR_UNSUPPORTED from the C ABI): where the call lands on it, each
+        // slice of an int16 batch is converted below -- the same values, v / 32768 exactly -- and bfloat16 features are narrowed
+        // from its float32 result at the end (the same rounding, the same bits)
         int sel = (int)(algo & 0xff);
         if (sel == LEAF_ALGO_AUTO) sel = leaf_auto_algo((int)std::min<int64_t>(B, batch_slices(B, T).per_call), T, F, (int)K, (int)hop);
-        pcm16_staged = sel == LEAF_ALGO_STAGED;
+        pcm16_staged = pcm16 && sel == LEAF_ALGO_STAGED;
+        bf16_staged = out_bf16 && sel == LEAF_ALGO_STAGED;
         if (pcm16_staged) flags &= ~LEAF_FLAG_X_PCM16;
+        if (bf16_staged) flags &= ~LEAF_FLAG_OUT_BF16;
     }
     const bool x16 = (flags & LEAF_FLAG_X_PCM16) != 0;
-    Tensor out = at::empty({B, F, TP}, out_opt);
+    Tensor out = at::empty({B, F, TP}, bf16_staged ? out_opt.dtype(at::kFloat) : out_opt);
     if (raw) *raw = at::empty({B, F, TP}, x2.options().dtype(at::kFloat));
     // The C ABI indexes the samples of ONE call with 32 bits and refuses B * T >= 2^31 (LEAF_ERR_BAD_SHAPE); the reference's
     // conv1d takes any batch (frontend.py:78-89).  Clips are independent, so a larger batch goes through in balanced slices of
@@ -124,7 +131,7 @@ Tensor forward_impl(const Tensor& x, const Params& p, int64_t K, int64_t hop, bo
     Tensor ws = at::empty({(int64_t)std::max<size_t>({leaf_workspace_bytes((int)sl.per_call, T, F, (int)K, (int)hop, (int)algo),
                                                       leaf_workspace_bytes(last, T, F, (int)K, (int)hop, (int)algo), size_t(4)})},
                           x2.options().dtype(at::kByte));
-    const size_t io = io_bf16 ? 2 : 4, xio = x16 ? 2 : io;
+    const size_t io = (size_t)out.element_size(), xio = x16 || io_bf16 ? 2 : 4;
     for (int64_t b0 = 0; b0 < B; b0 += sl.per_call) {
         const int nb = (int)std::min<int64_t>(sl.per_call, B - b0);
         Tensor xs;                                              // one slice of an int16 batch as float32, for the staged forward
@@ -145,24 +152,25 @@ Tensor forward_impl(const Tensor& x, const Params& p, int64_t K, int64_t hop, bo
             check_status(rc, "leaf_forward_f32");
         }
     }
-    return out;
+    return bf16_staged ? out.to(at::kBFloat16) : out;
 }
 
 // leaf_amd::forward -- frontend.py:78-89 (inference / no-grad)
 Tensor op_forward(const Tensor& x, const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b, const OptTensor& alpha,
                   const OptTensor& delta, const OptTensor& root, const OptTensor& ema_w, int64_t K, int64_t hop, bool log1p,
-                  int64_t algo) {
+                  int64_t algo, bool out_bf16) {
     const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
-    return forward_impl(x, p, K, hop, log1p, algo, nullptr);
+    return forward_impl(x, p, K, hop, log1p, algo, nullptr, out_bf16);
 }
 
 // leaf_amd::forward_train -- the same, additionally returning the pre-floor pooled tensor the backward consumes
 std::tuple<Tensor, Tensor> op_forward_train(const Tensor& x, const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b,
                                             const OptTensor& alpha, const OptTensor& delta, const OptTensor& root,
-                                            const OptTensor& ema_w, int64_t K, int64_t hop, int64_t algo, bool log1p) {
+                                            const OptTensor& ema_w, int64_t K, int64_t hop, int64_t algo, bool log1p,
+                                            bool out_bf16) {
     const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
     Tensor raw;
-    Tensor out = forward_impl(x, p, K, hop, log1p, algo, &raw);
+    Tensor out = forward_impl(x, p, K, hop, log1p, algo, &raw, out_bf16);
     return {out, raw};
 }
 
@@ -171,12 +179,14 @@ std::tuple<Tensor, Tensor> op_forward_train(const Tensor& x, const Tensor& kerne
 // (LEAF_FLAG_BWD_*, and LEAF_FLAG_LOG1P for the backward of the log1p-compressed forward); LEAF_FLAG_PCEN and
 // LEAF_FLAG_IO_BF16 / LEAF_FLAG_X_PCM16 follow from the tensors.  bfloat16 x: grad_out is bfloat16 too, g_x comes back in
 // bfloat16, the parameter gradients and pooled_raw are float32.  int16 x (PCM): grad_out float32, need_dx refused.
+// out_bf16 (LEAF_FLAG_OUT_BF16): grad_out alone is bfloat16, for a float32 (g_x float32) or int16 x.
 std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b,
                                 const OptTensor& alpha, const OptTensor& delta, const OptTensor& root, const OptTensor& ema_w,
                                 int64_t K, int64_t hop, const Tensor& grad_out, const OptTensor& pooled_raw, bool need_dx,
-                                int64_t flags) {
+                                int64_t flags, bool out_bf16) {
     Tensor x2 = waveform_2d(x);
     const bool io_bf16 = x2.scalar_type() == at::kBFloat16;
+    out_bf16 = out_bf16 && !io_bf16;
     const bool pcm16 = x2.scalar_type() == at::kShort;
     TORCH_CHECK(io_bf16 || pcm16 || x2.scalar_type() == at::kFloat,
                 "x must be float32 (or bfloat16 for the bf16-I/O extension, or int16 PCM), got ", x2.scalar_type());
@@ -190,6 +200,10 @@ std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Ten
     if (io_bf16) {
         TORCH_CHECK(grad_out.device() == x2.device(), "grad_out is on ", grad_out.device(), ", expected ", x2.device());
         TORCH_CHECK(grad_out.scalar_type() == at::kBFloat16, "grad_out must be bfloat16 when x is bfloat16, got ", grad_out.scalar_type());
+        go = grad_out.contiguous();
+    } else if (out_bf16) {
+        TORCH_CHECK(grad_out.device() == x2.device(), "grad_out is on ", grad_out.device(), ", expected ", x2.device());
+        TORCH_CHECK(grad_out.scalar_type() == at::kBFloat16, "grad_out must be bfloat16 with out_bf16=True, got ", grad_out.scalar_type());
         go = grad_out.contiguous();
     } else {
         go = dev_f32(grad_out, "grad_out", x2.device());
@@ -208,11 +222,10 @@ std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Ten
         for (Tensor* g : {&gk, &gpw, &gpb, &ga, &gd, &gr, &gw}) g->zero_();
         return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw, need_dx ? gx.reshape(x.sizes()) : gx};
     }
-    const int fl = ((int)flags & ~(LEAF_FLAG_PCEN | LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16)) | (p.pcen ? LEAF_FLAG_PCEN : 0) |
-                   (io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (pcm16 ? LEAF_FLAG_X_PCM16 : 0);
-    const size_t io = io_bf16 ? 2 : 4;
-    auto io_at = [io](const Tensor& t, size_t elems) {      // element offset into a float32 / bfloat16 / int16 I/O tensor, as the C ABI's float pointer
-        return reinterpret_cast<float*>(static_cast<char*>(t.data_ptr()) + elems * (t.scalar_type() == at::kShort ? 2 : io));
+    const int fl = ((int)flags & ~(LEAF_FLAG_PCEN | LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16 | LEAF_FLAG_OUT_BF16)) | (p.pcen ? LEAF_FLAG_PCEN : 0) |
+                   (io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (pcm16 ? LEAF_FLAG_X_PCM16 : 0) | (out_bf16 ? LEAF_FLAG_OUT_BF16 : 0);
+    auto io_at = [](const Tensor& t, size_t elems) {        // element offset into a float32 / bfloat16 / int16 I/O tensor, as the C ABI's float pointer
+        return reinterpret_cast<float*>(static_cast<char*>(t.data_ptr()) + elems * (size_t)t.element_size());
     };
     // B * T >= 2^31: slices of whole clips as in the forward; the parameter gradients of the slices are added in slice order
     // (a fixed order: the step stays bit-reproducible), dL/dx is written slice by slice
@@ -278,49 +291,59 @@ MixCall mix_call(const Tensor& x, const Tensor& perm, const Tensor& lam, const P
 }
 
 Tensor forward_mix_impl(const Tensor& x, const Tensor& perm, const Tensor& lam, const Params& p, int64_t K, int64_t hop, bool log1p,
-                        int64_t algo, Tensor* raw) {
+                        int64_t algo, Tensor* raw, bool out_bf16) {
     const MixCall c = mix_call(x, perm, lam, p, K, hop);
     const auto opt = c.x2.options().dtype(at::kFloat);
-    Tensor out = at::empty({c.B, c.F, c.TP}, opt);
     if (raw) *raw = at::empty({c.B, c.F, c.TP}, opt);
-    if (c.B == 0) return out;
-    const int flags = c.xflag | (p.pcen ? LEAF_FLAG_PCEN : (log1p ? LEAF_FLAG_LOG1P : 0));
+    if (c.B == 0) return at::empty({c.B, c.F, c.TP}, opt.dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
     c10::hip::HIPGuardMasqueradingAsCUDA guard(c.x2.device());
+    // bfloat16 features (LEAF_FLAG_OUT_BF16): narrowed in the kernels' stores; on the staged forward, which stores float32 only, from
+    // its float32 result below (the same rounding, the same bits)
+    bool bf16_staged = false;
+    if (out_bf16) {
+        int sel = (int)(algo & 0xff);
+        if (sel == LEAF_ALGO_AUTO) sel = leaf_auto_algo((int)c.B, c.T, c.F, (int)K, (int)hop);
+        bf16_staged = sel == LEAF_ALGO_STAGED;
+    }
+    const bool fused_bf16 = out_bf16 && !bf16_staged;
+    Tensor out = at::empty({c.B, c.F, c.TP}, opt.dtype(fused_bf16 ? at::kBFloat16 : at::kFloat));
+    float* outp = static_cast<float*>(out.data_ptr());
+    const int flags = c.xflag | (fused_bf16 ? LEAF_FLAG_OUT_BF16 : 0) | (p.pcen ? LEAF_FLAG_PCEN : (log1p ? LEAF_FLAG_LOG1P : 0));
     auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(c.x2.device().index());
     Tensor ws = at::empty({(int64_t)std::max<size_t>(leaf_forward_mix_workspace_bytes((int)c.B, c.T, c.F, (int)K, (int)hop, (int)algo), size_t(4))},
                           opt.dtype(at::kByte));
     if (raw) {
         check_status(leaf_forward_save_mix_f32(c.x2.data_ptr(), c.perm.data_ptr<int>(), fptr(c.lam), (int)c.B, c.T, fptr(p.kernel),
                                                fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha), fptr(p.delta), fptr(p.root), fptr(p.ema_w),
-                                               c.F, (int)K, (int)hop, flags, (int)algo, out.data_ptr<float>(), raw->data_ptr<float>(),
+                                               c.F, (int)K, (int)hop, flags, (int)algo, outp, raw->data_ptr<float>(),
                                                ws.data_ptr(), (size_t)ws.numel(), stream.stream()),
                      "leaf_forward_save_mix_f32");
     } else {
         check_status(leaf_forward_mix_f32(c.x2.data_ptr(), c.perm.data_ptr<int>(), fptr(c.lam), (int)c.B, c.T, fptr(p.kernel),
                                           fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha), fptr(p.delta), fptr(p.root), fptr(p.ema_w), c.F,
-                                          (int)K, (int)hop, flags, (int)algo, out.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(),
+                                          (int)K, (int)hop, flags, (int)algo, outp, ws.data_ptr(), (size_t)ws.numel(),
                                           stream.stream()),
                      "leaf_forward_mix_f32");
     }
-    return out;
+    return bf16_staged ? out.to(at::kBFloat16) : out;
 }
 
 // leaf_amd::forward_mix -- leaf_amd::forward of the mixed batch
 Tensor op_forward_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, const Tensor& kernel, const Tensor& pool_w,
                       const Tensor& pool_b, const OptTensor& alpha, const OptTensor& delta, const OptTensor& root,
-                      const OptTensor& ema_w, int64_t K, int64_t hop, bool log1p, int64_t algo) {
+                      const OptTensor& ema_w, int64_t K, int64_t hop, bool log1p, int64_t algo, bool out_bf16) {
     const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
-    return forward_mix_impl(x, perm, lam, p, K, hop, log1p, algo, nullptr);
+    return forward_mix_impl(x, perm, lam, p, K, hop, log1p, algo, nullptr, out_bf16);
 }
 
 // leaf_amd::forward_train_mix -- additionally the pre-floor pooled tensor of the mixed batch, for leaf_amd::backward_mix
 std::tuple<Tensor, Tensor> op_forward_train_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, const Tensor& kernel,
                                                 const Tensor& pool_w, const Tensor& pool_b, const OptTensor& alpha,
                                                 const OptTensor& delta, const OptTensor& root, const OptTensor& ema_w, int64_t K,
-                                                int64_t hop, int64_t algo, bool log1p) {
+                                                int64_t hop, int64_t algo, bool log1p, bool out_bf16) {
     const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
     Tensor raw;
-    Tensor out = forward_mix_impl(x, perm, lam, p, K, hop, log1p, algo, &raw);
+    Tensor out = forward_mix_impl(x, perm, lam, p, K, hop, log1p, algo, &raw, out_bf16);
     return {out, raw};
 }
 
@@ -328,10 +351,17 @@ std::tuple<Tensor, Tensor> op_forward_train_mix(const Tensor& x, const Tensor& p
 std::vector<Tensor> op_backward_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, const Tensor& kernel, const Tensor& pool_w,
                                     const Tensor& pool_b, const OptTensor& alpha, const OptTensor& delta, const OptTensor& root,
                                     const OptTensor& ema_w, int64_t K, int64_t hop, const Tensor& grad_out,
-                                    const OptTensor& pooled_raw, int64_t flags) {
+                                    const OptTensor& pooled_raw, int64_t flags, bool out_bf16) {
     const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
     const MixCall c = mix_call(x, perm, lam, p, K, hop);
-    Tensor go = dev_f32(grad_out, "grad_out", c.x2.device());
+    Tensor go;
+    if (out_bf16) {                                           // LEAF_FLAG_OUT_BF16: grad_out is bfloat16, widened where the kernels read it
+        TORCH_CHECK(grad_out.device() == c.x2.device(), "grad_out is on ", grad_out.device(), ", expected ", c.x2.device());
+        TORCH_CHECK(grad_out.scalar_type() == at::kBFloat16, "grad_out must be bfloat16 with out_bf16=True, got ", grad_out.scalar_type());
+        go = grad_out.contiguous();
+    } else {
+        go = dev_f32(grad_out, "grad_out", c.x2.device());
+    }
     TORCH_CHECK(go.dim() == 3 && go.size(0) == c.B && go.size(1) == c.F && go.size(2) == c.TP, "grad_out has shape ", go.sizes(),
                 ", expected (", c.B, ",", c.F, ",", c.TP, ")");
     OptTensor raw = dev_f32(pooled_raw, "pooled_raw", c.x2.device());
@@ -344,14 +374,15 @@ std::vector<Tensor> op_backward_mix(const Tensor& x, const Tensor& perm, const T
         for (Tensor* g : {&gk, &gpw, &gpb, &ga, &gd, &gr, &gw}) g->zero_();
         return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw};
     }
-    const int fl = ((int)flags & ~(LEAF_FLAG_PCEN | LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16)) | (p.pcen ? LEAF_FLAG_PCEN : 0) | c.xflag;
+    const int fl = ((int)flags & ~(LEAF_FLAG_PCEN | LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16 | LEAF_FLAG_OUT_BF16)) | (p.pcen ? LEAF_FLAG_PCEN : 0) | c.xflag |
+                   (out_bf16 ? LEAF_FLAG_OUT_BF16 : 0);
     c10::hip::HIPGuardMasqueradingAsCUDA guard(c.x2.device());
     auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(c.x2.device().index());
     Tensor ws = at::empty({(int64_t)std::max<size_t>(leaf_backward_mix_workspace_bytes((int)c.B, c.T, F, (int)K, (int)hop, fl), size_t(4))},
                           opt.dtype(at::kByte));
     check_status(leaf_backward_mix_f32(c.x2.data_ptr(), c.perm.data_ptr<int>(), fptr(c.lam), (int)c.B, c.T, fptr(p.kernel), fptr(p.pool_w),
                                        fptr(p.pool_b), fptr(p.alpha), fptr(p.delta), fptr(p.root), fptr(p.ema_w), F, (int)K, (int)hop, fl,
-                                       fptr(go), fptr(raw), gk.data_ptr<float>(), gpw.data_ptr<float>(), gpb.data_ptr<float>(),
+                                       static_cast<const float*>(go.data_ptr()), fptr(raw), gk.data_ptr<float>(), gpw.data_ptr<float>(), gpb.data_ptr<float>(),
                                        p.pcen ? ga.data_ptr<float>() : nullptr, p.pcen ? gd.data_ptr<float>() : nullptr,
                                        p.pcen ? gr.data_ptr<float>() : nullptr, p.pcen ? gw.data_ptr<float>() : nullptr, nullptr,
                                        ws.data_ptr(), (size_t)ws.numel(), stream.stream()),
@@ -363,17 +394,17 @@ std::vector<Tensor> op_backward_mix(const Tensor& x, const Tensor& perm, const T
 
 TORCH_LIBRARY(leaf_amd, m) {
     m.def("forward(Tensor x, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, Tensor? root, "
-          "Tensor? ema_w, int K, int hop, bool log1p, int algo) -> Tensor");
+          "Tensor? ema_w, int K, int hop, bool log1p, int algo, *, bool out_bf16=False) -> Tensor");
     m.def("forward_train(Tensor x, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, Tensor? root, "
-          "Tensor? ema_w, int K, int hop, int algo, bool log1p=False) -> (Tensor, Tensor)");
+          "Tensor? ema_w, int K, int hop, int algo, bool log1p=False, *, bool out_bf16=False) -> (Tensor, Tensor)");
     m.def("backward(Tensor x, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, Tensor? root, "
-          "Tensor? ema_w, int K, int hop, Tensor grad_out, Tensor? pooled_raw, bool need_dx, int flags) -> Tensor[]");
+          "Tensor? ema_w, int K, int hop, Tensor grad_out, Tensor? pooled_raw, bool need_dx, int flags, *, bool out_bf16=False) -> Tensor[]");
     m.def("forward_mix(Tensor x, Tensor perm, Tensor lam, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, "
-          "Tensor? root, Tensor? ema_w, int K, int hop, bool log1p, int algo) -> Tensor");
+          "Tensor? root, Tensor? ema_w, int K, int hop, bool log1p, int algo, *, bool out_bf16=False) -> Tensor");
     m.def("forward_train_mix(Tensor x, Tensor perm, Tensor lam, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, "
-          "Tensor? delta, Tensor? root, Tensor? ema_w, int K, int hop, int algo, bool log1p=False) -> (Tensor, Tensor)");
+          "Tensor? delta, Tensor? root, Tensor? ema_w, int K, int hop, int algo, bool log1p=False, *, bool out_bf16=False) -> (Tensor, Tensor)");
     m.def("backward_mix(Tensor x, Tensor perm, Tensor lam, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, "
-          "Tensor? root, Tensor? ema_w, int K, int hop, Tensor grad_out, Tensor? pooled_raw, int flags) -> Tensor[]");
+          "Tensor? root, Tensor? ema_w, int K, int hop, Tensor grad_out, Tensor? pooled_raw, int flags, *, bool out_bf16=False) -> Tensor[]");
 }
 
 // HIP tensors dispatch under the CUDA key in PyTorch-ROCm

@@ -29,13 +29,14 @@ class _LeafForward(torch.autograd.Function):
     """Forward = fused HIP path (leaf_forward_f32); backward = leaf_backward_f32 (recomputes on device)."""
 
     @staticmethod
-    def forward(ctx, x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen, algo, log1p=False):
+    def forward(ctx, x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen, algo, log1p=False, out_bf16=False):
         if algo & _native.OPT_PEAKNORM:
             # leaf_forward_save_f32 would hand the backward a pooled tensor of the NORMALISED clips next to the raw x
             raise RuntimeError("the folded PeakNormalization prologue is forward-only (no backward through it)")
         out, raw = _native.leaf_forward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen=pcen,
-                                        log1p=log1p, algo=algo, save_raw=True)
+                                        log1p=log1p, algo=algo, save_raw=True, out_bf16=out_bf16)
         ctx.log1p = bool(log1p) and not pcen
+        ctx.out_bf16 = bool(out_bf16)                             # bfloat16 features: their gradient arrives in bfloat16 and goes straight in
         ctx.save_for_backward(x, kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if pcen else []))
         ctx.geom = (K, hop, pcen)
         ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)      # Leaf.full_transforms(): the backward keeps them too
@@ -53,10 +54,10 @@ class _LeafForward(torch.autograd.Function):
         gk, gpw, gpb, ga, gd, gr, gw, gx = _native.leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop,
                                                                  grad_out, pcen=pcen, need_dx=need_dx, pooled_raw=raw,
                                                                  full_transforms=ctx.full, strict_band_classes=ctx.strict,
-                                                                 log1p=ctx.log1p)
+                                                                 log1p=ctx.log1p, out_bf16=ctx.out_bf16)
         if gx is not None:
             gx = gx.reshape(x.shape)
-        return gx, gk, gpw, gpb, ga, gd, gr, gw, None, None, None, None, None
+        return gx, gk, gpw, gpb, ga, gd, gr, gw, None, None, None, None, None, None
 
 
 class _LeafForwardMix(torch.autograd.Function):
@@ -64,10 +65,11 @@ class _LeafForwardMix(torch.autograd.Function):
     path without the dispatcher ops.  Parameter gradients only."""
 
     @staticmethod
-    def forward(ctx, x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen, algo, log1p=False):
+    def forward(ctx, x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen, algo, log1p=False, out_bf16=False):
         out, raw = _native.leaf_forward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen=pcen,
-                                            log1p=log1p, algo=algo, save_raw=True)
+                                            log1p=log1p, algo=algo, save_raw=True, out_bf16=out_bf16)
         ctx.log1p = bool(log1p) and not pcen
+        ctx.out_bf16 = bool(out_bf16)
         ctx.save_for_backward(x, perm, lam, kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if pcen else []))
         ctx.geom = (K, hop, pcen)
         ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)
@@ -84,8 +86,8 @@ class _LeafForwardMix(torch.autograd.Function):
         gk, gpw, gpb, ga, gd, gr, gw, _ = _native.leaf_backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K,
                                                                     hop, grad_out, pcen=pcen, pooled_raw=raw,
                                                                     full_transforms=ctx.full, strict_band_classes=ctx.strict,
-                                                                    log1p=ctx.log1p)
-        return None, None, None, gk, gpw, gpb, ga, gd, gr, gw, None, None, None, None, None
+                                                                    log1p=ctx.log1p, out_bf16=ctx.out_bf16)
+        return None, None, None, gk, gpw, gpb, ga, gd, gr, gw, None, None, None, None, None, None
 
 
 class Leaf(nn.Module):
@@ -122,6 +124,7 @@ class Leaf(nn.Module):
         self._tables_key = None
         self._fuse_peaknorm = False          # not part of the reference surface: see fuse_peak_normalization()
         self._log1p = False                  # not part of the reference surface: see log_compression()
+        self._out_dtype = None               # not part of the reference surface: see output_dtype()
 
     def full_transforms(self, enable: bool = True) -> "Leaf":
         """Not part of the reference surface: switch the band-limited filter tasks off for this module -- every filter on the
@@ -142,6 +145,42 @@ class Leaf(nn.Module):
             raise ValueError("log_compression() needs a Leaf built with pcen_compression=False (PCEN is the compression of this module)")
         self._log1p = bool(enable)
         return self
+
+    def output_dtype(self, dtype=None) -> "Leaf":
+        """Not part of the reference surface: the dtype of the features, independent of the waveform's.  ``None`` (the default):
+        the features follow the waveform -- float32 for a float32 or int16 ``x``, bfloat16 for a bfloat16 ``x``.
+        ``torch.bfloat16``: bfloat16 features from a float32 or int16 waveform (LEAF_FLAG_OUT_BF16) -- the kernels compute in float32
+        as ever and round each feature to nearest even where they store it, so the result is ``forward(x).to(torch.bfloat16)`` of
+        the float32 call bit for bit, without the float32 tensor and without the cast kernel; in training the bfloat16 gradient of
+        the features is widened where the backward reads it, so the parameter gradients (and ``x.grad``, float32, for a float32
+        ``x``) are those of the float32 call on that gradient widened.  ``"autocast"``: bfloat16 exactly when CUDA autocast is
+        enabled with bfloat16 at the call (the model behind this module under ``torch.autocast("cuda", torch.bfloat16)``), else as
+        ``None``.  ``torch.float32``: float32 features; with a bfloat16 waveform that combination is not built and the call raises
+        ``ValueError``.  Anything else raises ``ValueError`` here -- ``torch.float16`` included: with the compression off the
+        un-normalised pooled energies leave its range.
+
+        Honoured by ``forward``, ``forward_mixup``, ``cache_tables()``, ``log_compression()``, ``full_transforms()``,
+        ``fuse_peak_normalization()`` and training.  Adds no parameter and no buffer: ``state_dict`` keys stay those of the
+        reference.  Gradients of gradients raise, as for bfloat16 I/O.  ``LeafStream`` does not look at this setting: a stream keeps
+        returning float32 chunks (its smoother state is carried in float32 between calls)."""
+        if not (dtype is None or dtype is torch.float32 or dtype is torch.bfloat16 or (isinstance(dtype, str) and dtype == "autocast")):
+            raise ValueError(f"output_dtype: expected None, torch.float32, torch.bfloat16 or 'autocast', got {dtype!r} "
+                             "(float16 is not offered: un-normalised pooled energies overflow it with the compression off)")
+        self._out_dtype = dtype
+        return self
+
+    def _features_bf16(self, x: torch.Tensor) -> bool:
+        """Whether this call asks the kernels for bfloat16 features (the explicit ``out_bf16`` of the host layers)."""
+        mode = self._out_dtype
+        if mode is None:
+            return False
+        if mode is torch.float32:
+            if x.dtype == torch.bfloat16:
+                raise ValueError("output_dtype(torch.float32) with a bfloat16 waveform is not built: the features of a bfloat16 x are bfloat16")
+            return False
+        if mode is torch.bfloat16:
+            return True
+        return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
 
     def fuse_peak_normalization(self, enable: bool = True) -> "Leaf":
         """Not part of the reference surface: make ``forward(x)`` return ``Leaf(PeakNormalization(x))`` -- the last transform
@@ -204,22 +243,25 @@ class Leaf(nn.Module):
                   c.root if c is not None else None, c.ema._weights if c is not None else None)
         K, hop = self._complex_conv._kernel_size, self._pooling.strides
         log1p = self._log1p and c is None
+        bf16 = self._features_bf16(x)                             # output_dtype(): bfloat16 features of the mixed batch
         needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params)
         if _ops.available():
             _ops.load()
             if needs_grad:
-                return _ops.forward_train_mix(x, perm, lam, *params, K, hop, algo=self._algo, log1p=log1p)
-            return _ops.forward_mix(x, perm, lam, *params, K, hop, log1p=log1p, algo=self._algo)
+                return _ops.forward_train_mix(x, perm, lam, *params, K, hop, algo=self._algo, log1p=log1p, out_bf16=bf16)
+            return _ops.forward_mix(x, perm, lam, *params, K, hop, log1p=log1p, algo=self._algo, out_bf16=bf16)
         if needs_grad:
-            return _LeafForwardMix.apply(x, perm, lam, *params, K, hop, c is not None, self._algo, log1p)
-        return _native.leaf_forward_mix(x, perm, lam, *params, K, hop, pcen=c is not None, log1p=log1p, algo=self._algo)
+            return _LeafForwardMix.apply(x, perm, lam, *params, K, hop, c is not None, self._algo, log1p, bf16)
+        return _native.leaf_forward_mix(x, perm, lam, *params, K, hop, pcen=c is not None, log1p=log1p, algo=self._algo, out_bf16=bf16)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(B,1,T) float32 -> (B,F,T') float32, as the reference.  Not part of the reference surface: a bfloat16 ``x`` gives
         bfloat16 features, and an int16 ``x`` is 16-bit PCM -- a sample v means v / 32768, converted inside the kernels' loads --
         and gives the float32 features of ``x.float() / 32768`` bit for bit, on every path (inference, ``cache_tables()``,
-        training of the parameters, ``log_compression()``, ``full_transforms()``); it has no gradient of its own."""
+        training of the parameters, ``log_compression()``, ``full_transforms()``); it has no gradient of its own.
+        ``output_dtype()`` chooses the dtype of the features independently of the waveform's."""
         _native.require_hip(x, "Leaf.forward")
+        bf16 = self._features_bf16(x)                             # output_dtype(): bfloat16 features from a float32 / int16 waveform
         algo = self._algo
         c = self._compression
         params = (self._complex_conv._kernel, self._pooling.weights, self._pooling._bias,
@@ -256,11 +298,11 @@ class Leaf(nn.Module):
             # dispatcher ops (csrc/torch_binding.cpp): traceable by torch.compile / export, one hop per eager call
             _ops.load()
             if needs_grad:
-                return _ops.forward_train(*args[:10], algo=args[11], log1p=log1p)
+                return _ops.forward_train(*args[:10], algo=args[11], log1p=log1p, out_bf16=bf16)
             if not (self._cache_tables and not torch.compiler.is_compiling()):
-                return _ops.forward(*args[:10], log1p=log1p, algo=args[11])
+                return _ops.forward(*args[:10], log1p=log1p, algo=args[11], out_bf16=bf16)
         if needs_grad:
-            return _LeafForward.apply(*args, log1p)
+            return _LeafForward.apply(*args, log1p, bf16)
         if self._cache_tables and self._algo in (_native.ALGO_AUTO, _native.ALGO_FFT):
             K, hop = args[8], args[9]
             B, T, F = x.shape[0], x.shape[-1], args[1].shape[0]
@@ -273,6 +315,6 @@ class Leaf(nn.Module):
                 tables = self._prepared_tables()
                 if tables is not None:
                     return _native.leaf_forward_prepared(x, tables, args[3], args[4], args[5], args[6], args[7],
-                                                         args[1].shape[0], K, hop, pcen=args[10], log1p=log1p)
+                                                         args[1].shape[0], K, hop, pcen=args[10], log1p=log1p, out_bf16=bf16)
         return _native.leaf_forward(*args[:8], args[8], args[9], pcen=args[10], log1p=log1p, algo=args[11] & ~_native.OPT_PEAKNORM,
-                                    peak_normalize=bool(args[11] & _native.OPT_PEAKNORM))
+                                    peak_normalize=bool(args[11] & _native.OPT_PEAKNORM), out_bf16=bf16)

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Time forward and forward+backward of Leaf (parameters require grad) on one GPU.
-   usage: bench_backward.py [--no-pcen | --log1p] [--bf16 | --pcm16] [--mixup] [--interleave V1,V2,..] [B [n_filters sample_rate seconds [nodx]]]
+   usage: bench_backward.py [--no-pcen | --log1p] [--bf16 | --pcm16] [--out-bf16] [--mixup] [--interleave V1,V2,..] [B [n_filters sample_rate seconds [nodx]]]
    (default 256 clips of the default 40 f / 16 kHz / 1 s, PCEN on, float32;
    nodx skips the dL/dx timing -- staged kernels, hundreds of ms, for geometries without a fused dL/dx)
    --no-pcen: PCEN off (BASELINE configs[3] without compression); --log1p: PCEN off with Leaf.log_compression() (configs[3]);
    --bf16: bfloat16 waveform, features, grad_out and dL/dx (configs[4]).
    --pcm16: int16 waveform (16-bit PCM, a sample v means v / 32768), float32 features and grad_out, no dL/dx.
+   --out-bf16: bfloat16 features and grad_out from the float32 or --pcm16 waveform (Leaf.output_dtype(torch.bfloat16)); dL/dx stays float32.
+   Interleave legs: "+outbf16" the same, fused in the kernels' stores and loads; "+outcast" the stock float32 forward followed by
+   .to(torch.bfloat16) (whose backward is grad.float()): the cast kernels the fused leg saves, one per direction.
    --mixup: waveform mixup folded into the step (Leaf.forward_mixup with a fixed permutation and weights; float32 or --pcm16; no dL/dx).
    Interleave legs: "+mixup" the fused step, "+mixstock" the reference's stock-op mixup (x * lam + x[perm] * (1 - lam), an int16 batch
    cast first) followed by the plain step, neither: the plain step.
@@ -22,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from leaf_pytorch_amd import Leaf  # noqa: E402
 
 dev = torch.device("cuda:0")
-OPTS = {a for a in sys.argv[1:] if a in ("--no-pcen", "--log1p", "--bf16", "--pcm16", "--mixup")}
+OPTS = {a for a in sys.argv[1:] if a in ("--no-pcen", "--log1p", "--bf16", "--pcm16", "--out-bf16", "--mixup")}
 INTERLEAVE = None
 if "--interleave" in sys.argv:
     i = sys.argv.index("--interleave")
@@ -42,6 +45,8 @@ def make(pcen=True, log1p=False):
 
 
 m = make(pcen="--no-pcen" not in OPTS, log1p="--log1p" in OPTS)
+if "--out-bf16" in OPTS:
+    m.output_dtype(torch.bfloat16)
 x = 2 * torch.rand(B, 1, int(SR * SECS), device=dev) - 1
 if "--bf16" in OPTS:
     x = x.to(torch.bfloat16)
@@ -126,17 +131,25 @@ if INTERLEAVE:
         parts = name.split("+")
         mod = make(pcen=parts[0] == "pcen", log1p=parts[0] == "log1p")
         pcm, cast = "pcm16" in parts, "pcm16cast" in parts
+        outcast = "outcast" in parts
+        if "outbf16" in parts:
+            mod.output_dtype(torch.bfloat16)
         xv = x16.clone() if pcm or cast else (x.to(torch.bfloat16) if "bf16" in parts else x.float()).clone().requires_grad_("dx" in parts)
         with torch.no_grad():
             gv = torch.randn_like(mod(xv))
+        if outcast:
+            gv = gv.to(torch.bfloat16)
 
-        def step(mod=mod, xv=xv, gv=gv, cast=cast, fwd_only="fwd" in parts, fused="mixup" in parts, stock="mixstock" in parts):
+        def step(mod=mod, xv=xv, gv=gv, cast=cast, fwd_only="fwd" in parts, fused="mixup" in parts, stock="mixstock" in parts, outcast=outcast):
             xin = xv.float().mul_(2.0 ** -15) if cast else xv
             if stock:                                    # utilities/data/mixup.py:20 with stock ops (an integer batch is cast first)
                 xf = xin if xin.is_floating_point() else xin.float().mul_(2.0 ** -15)
                 lam3 = MIX_LAM.view(B, 1, 1)
                 xin = xf * lam3 + xf[MIX_PERM] * (1 - lam3)
             call = (lambda t: mod.forward_mixup(t, MIX_PERM, MIX_LAM)) if fused else mod
+            if outcast:                                  # float32 features, then the cast (autograd widens the gradient on the way back)
+                inner = call
+                call = lambda t: inner(t).to(torch.bfloat16)
             if fwd_only:
                 with torch.no_grad():
                     call(xin)
