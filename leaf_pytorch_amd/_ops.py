@@ -76,26 +76,39 @@ def _out_dtype(x: torch.Tensor, out_bf16: bool = False) -> torch.dtype:
     return torch.bfloat16 if x.dtype == torch.bfloat16 or out_bf16 else torch.float32
 
 
-def _register_python_side() -> None:
-    @torch.library.register_fake("leaf_amd::forward")
-    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo, out_bf16=False):
-        return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)), dtype=_out_dtype(x, out_bf16))
+def _register_family(mixed: bool) -> None:
+    """Fake kernels and the autograd formula of one family of three ops: forward / forward_train / backward, or (``mixed``) the
+    same three with (perm, lam) behind x -- waveform mixup, parameter gradients only."""
+    sfx = "_mix" if mixed else ""
+    lead = 3 if mixed else 1                                     # x [, perm, lam] in front of the seven parameters
 
-    @torch.library.register_fake("leaf_amd::forward_train")
-    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p=False, out_bf16=False):
+    def feat_dtype(x, out_bf16):                                 # (a mixed call takes no bfloat16 waveform)
+        return (torch.bfloat16 if out_bf16 else torch.float32) if mixed else _out_dtype(x, out_bf16)
+
+    @torch.library.register_fake(f"leaf_amd::forward{sfx}")
+    def _(*args, out_bf16=False):
+        x, kernel, (K, hop) = args[0], args[lead], args[lead + 7:lead + 9]
+        return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)), dtype=feat_dtype(x, out_bf16))
+
+    @torch.library.register_fake(f"leaf_amd::forward_train{sfx}")
+    def _(*args, out_bf16=False):
+        x, kernel, (K, hop) = args[0], args[lead], args[lead + 7:lead + 9]
         shape = (x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop))
-        return x.new_empty(shape, dtype=_out_dtype(x, out_bf16)), x.new_empty(shape, dtype=torch.float32)
+        return x.new_empty(shape, dtype=feat_dtype(x, out_bf16)), x.new_empty(shape, dtype=torch.float32)
 
-    @torch.library.register_fake("leaf_amd::backward")
-    def _(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out, pooled_raw, need_dx, flags, out_bf16=False):
-        F = kernel.shape[0]
-        pc = F if alpha is not None else 0
+    @torch.library.register_fake(f"leaf_amd::backward{sfx}")
+    def _(*args, out_bf16=False):
+        x, (kernel, pool_w, pool_b, alpha) = args[0], args[lead:lead + 4]
+        pc = kernel.shape[0] if alpha is not None else 0
         e = lambda *s: kernel.new_empty(s)
-        return [torch.empty_like(kernel), torch.empty_like(pool_w), torch.empty_like(pool_b), e(pc), e(pc), e(pc), e(pc),
-                torch.empty_like(x) if need_dx else e(0)]            # (g_x in the dtype of x: bfloat16 for bfloat16 I/O)
+        grads = [torch.empty_like(kernel), torch.empty_like(pool_w), torch.empty_like(pool_b), e(pc), e(pc), e(pc), e(pc)]
+        if mixed:
+            return grads
+        need_dx = args[lead + 11]
+        return grads + [torch.empty_like(x) if need_dx else e(0)]    # (g_x in the dtype of x: bfloat16 for bfloat16 I/O)
 
     def setup_context(ctx, inputs, keyword_only_inputs, output):
-        x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p = inputs
+        kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p = inputs[lead:]
         _, raw = output
         ctx.pcen = alpha is not None
         ctx.out_bf16 = bool(keyword_only_inputs["out_bf16"])     # the features left in bfloat16: their gradient arrives in bfloat16
@@ -103,70 +116,35 @@ def _register_python_side() -> None:
         ctx.geom = (K, hop)
         ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)     # Leaf.full_transforms(): no band tasks in the backward either
         ctx.strict = bool(algo & _native.ALGO_STRICT_BAND_CLASSES)
-        ctx.save_for_backward(x, kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if ctx.pcen else []))
+        ctx.save_for_backward(*inputs[:lead], kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if ctx.pcen else []))
 
     def backward(ctx, grad_out, grad_raw):
         K, hop = ctx.geom
         saved = ctx.saved_tensors
-        x, kernel, pool_w, pool_b, raw = saved[:5]
-        alpha, delta, root, ema_w = saved[5:] if ctx.pcen else (None,) * 4
-        need_dx = ctx.needs_input_grad[0]
-        gk, gpw, gpb, ga, gd, gr, gw, gx = torch.ops.leaf_amd.backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop,
-                                                                     grad_out.contiguous(), raw, need_dx,
-                                                                     (_native.FLAG_BWD_FULL_TRANSFORMS if ctx.full else 0) |
-                                                                     (_native.FLAG_BWD_STRICT_BAND_CLASSES if ctx.strict else 0) |
-                                                                     (_native.FLAG_LOG1P if ctx.log1p else 0),
-                                                                     out_bf16=ctx.out_bf16)   # (the bfloat16 grad_out goes straight in)
-        pc = (ga, gd, gr, gw) if ctx.pcen else (None,) * 4
-        return (gx if need_dx else None, gk, gpw, gpb, *pc, None, None, None, None)   # (one per positional input)
+        kernel, pool_w, pool_b, raw = saved[lead:lead + 4]
+        alpha, delta, root, ema_w = saved[lead + 4:] if ctx.pcen else (None,) * 4
+        flags = ((_native.FLAG_BWD_FULL_TRANSFORMS if ctx.full else 0) | (_native.FLAG_BWD_STRICT_BAND_CLASSES if ctx.strict else 0) |
+                 (_native.FLAG_LOG1P if ctx.log1p else 0))
+        params = (kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out.contiguous(), raw)
+        if mixed:
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
+                raise RuntimeError("leaf_amd::forward_train_mix has no gradient for x or lam: the mixed waveform is data "
+                                   "(dL/dx under mixup is a scatter over perm and is not built)")
+            grads, gx = torch.ops.leaf_amd.backward_mix(*saved[:lead], *params, flags, out_bf16=ctx.out_bf16), None
+        else:
+            need_dx = ctx.needs_input_grad[0]
+            *grads, gx = torch.ops.leaf_amd.backward(saved[0], *params, need_dx, flags,
+                                                     out_bf16=ctx.out_bf16)   # (the bfloat16 grad_out goes straight in)
+            gx = gx if need_dx else None
+        gk, gpw, gpb, *pc = grads
+        return (gx, *(None,) * (lead - 1), gk, gpw, gpb, *(pc if ctx.pcen else (None,) * 4), None, None, None, None)   # (one per positional input)
 
-    torch.library.register_autograd("leaf_amd::forward_train", backward, setup_context=setup_context)
+    torch.library.register_autograd(f"leaf_amd::forward_train{sfx}", backward, setup_context=setup_context)
 
-    # ---- waveform mixup: the same three ops with (perm, lam) behind x; parameter gradients only
-    @torch.library.register_fake("leaf_amd::forward_mix")
-    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, log1p, algo, out_bf16=False):
-        return x.new_empty((x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop)), dtype=torch.bfloat16 if out_bf16 else torch.float32)
 
-    @torch.library.register_fake("leaf_amd::forward_train_mix")
-    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p=False, out_bf16=False):
-        shape = (x.shape[0], kernel.shape[0], _frames(x.shape[-1], K, hop))
-        return x.new_empty(shape, dtype=torch.bfloat16 if out_bf16 else torch.float32), x.new_empty(shape, dtype=torch.float32)
-
-    @torch.library.register_fake("leaf_amd::backward_mix")
-    def _(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out, pooled_raw, flags, out_bf16=False):
-        pc = kernel.shape[0] if alpha is not None else 0
-        e = lambda *s: kernel.new_empty(s)
-        return [torch.empty_like(kernel), torch.empty_like(pool_w), torch.empty_like(pool_b), e(pc), e(pc), e(pc), e(pc)]
-
-    def setup_context_mix(ctx, inputs, keyword_only_inputs, output):
-        x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, algo, log1p = inputs
-        _, raw = output
-        ctx.pcen = alpha is not None
-        ctx.out_bf16 = bool(keyword_only_inputs["out_bf16"])
-        ctx.log1p = bool(log1p) and not ctx.pcen
-        ctx.geom = (K, hop)
-        ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)
-        ctx.strict = bool(algo & _native.ALGO_STRICT_BAND_CLASSES)
-        ctx.save_for_backward(x, perm, lam, kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if ctx.pcen else []))
-
-    def backward_mix(ctx, grad_out, grad_raw):
-        K, hop = ctx.geom
-        saved = ctx.saved_tensors
-        x, perm, lam, kernel, pool_w, pool_b, raw = saved[:7]
-        alpha, delta, root, ema_w = saved[7:] if ctx.pcen else (None,) * 4
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
-            raise RuntimeError("leaf_amd::forward_train_mix has no gradient for x or lam: the mixed waveform is data "
-                               "(dL/dx under mixup is a scatter over perm and is not built)")
-        gk, gpw, gpb, ga, gd, gr, gw = torch.ops.leaf_amd.backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K,
-                                                                       hop, grad_out.contiguous(), raw,
-                                                                       (_native.FLAG_BWD_FULL_TRANSFORMS if ctx.full else 0) |
-                                                                       (_native.FLAG_BWD_STRICT_BAND_CLASSES if ctx.strict else 0) |
-                                                                       (_native.FLAG_LOG1P if ctx.log1p else 0),
-                                                                       out_bf16=ctx.out_bf16)
-        pc = (ga, gd, gr, gw) if ctx.pcen else (None,) * 4
-        return (None, None, None, gk, gpw, gpb, *pc, None, None, None, None)
-
-    torch.library.register_autograd("leaf_amd::forward_train_mix", backward_mix, setup_context=setup_context_mix)
+def _register_python_side() -> None:
+    _register_family(mixed=False)
+    _register_family(mixed=True)
     from . import _second_order
     _second_order.register()                  # gradients of gradients: leaf_amd::backward's own autograd formula
 

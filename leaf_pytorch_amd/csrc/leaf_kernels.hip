@@ -67,35 +67,28 @@ inline const char* tools_env(const char* name) { return LEAF_TOOLS ? getenv(name
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// LEAF_ALGO_RESERVE_CUS(k): CUs the current call leaves free (thread-local and scoped to one ABI call by ReserveCus: the
-// library stays re-entrant and keeps nothing between calls)
-thread_local int tl_reserved_cus = 0;
-thread_local bool tl_stream_finalize = false;                // LEAF_ALGO_STREAM_FINALIZE of the current call
-thread_local bool tl_band_off = false;                       // LEAF_ALGO_FULL_TRANSFORMS of the current call
-thread_local bool tl_band_strict = false;                    // LEAF_ALGO_STRICT_BAND_CLASSES of the current call
-struct ReserveCus {
-    int prev;
-    bool prev_stream, prev_band_off, prev_band_strict;
-    explicit ReserveCus(int algo) : prev(tl_reserved_cus), prev_stream(tl_stream_finalize), prev_band_off(tl_band_off), prev_band_strict(tl_band_strict) {
-        if ((algo >> 16) & 0xff) tl_reserved_cus = (algo >> 16) & 0xff;   // nested calls pass the masked selector: they inherit
-        if (algo & LEAF_ALGO_STREAM_FINALIZE) tl_stream_finalize = true;
-        if (algo & LEAF_ALGO_FULL_TRANSFORMS) tl_band_off = true;
-        if (algo & LEAF_ALGO_STRICT_BAND_CLASSES) tl_band_strict = true;
-    }
-    ~ReserveCus() { tl_reserved_cus = prev; tl_stream_finalize = prev_stream; tl_band_off = prev_band_off; tl_band_strict = prev_band_strict; }
-};
-// Waveform mixup of the current call (leaf_forward_mix_f32 / leaf_backward_mix_f32), set only while a kernel family that mixes in its
+// Waveform mixup of a call (leaf_forward_mix_f32 / leaf_backward_mix_f32), set only where a kernel family that mixes in its
 // loads serves the call (the other families get a mixed copy, mixup_kernel); lam == NULL: off
 struct MixArgs { const int* perm; const float* lam; };
-thread_local MixArgs tl_mix{nullptr, nullptr};
-struct MixScope {
-    MixArgs prev;
-    explicit MixScope(MixArgs m) : prev(tl_mix) { tl_mix = m; }
-    ~MixScope() { tl_mix = prev; }
+// The per-call options of one ABI call: built once at the entry point (forward_ctx / backward_ctx) and passed down by const
+// reference, so that every decision names what it depends on.  Nothing is kept between calls: the library stays re-entrant.
+struct CallCtx {
+    int cus;                 // CUs this call may fill: the device's count minus LEAF_ALGO_RESERVE_CUS(k), at least one
+    bool stream_finalize;    // LEAF_ALGO_STREAM_FINALIZE
+    bool band_off;           // LEAF_ALGO_FULL_TRANSFORMS / LEAF_FLAG_BWD_FULL_TRANSFORMS
+    bool band_strict;        // LEAF_ALGO_STRICT_BAND_CLASSES / LEAF_FLAG_BWD_STRICT_BAND_CLASSES
+    int desync;              // LEAF_ALGO_TUNE_DESYNC(n); -1 = automatic
+    int sel;                 // the selector (low byte of `algo`); resolve_selector() turns LEAF_ALGO_AUTO into what runs
+    MixArgs mix;
 };
-int device_cus();
-// CUs this call may fill: the device's count minus the call's reservation (at least one)
-int num_cus() { return std::max(1, device_cus() - tl_reserved_cus); }
+// the host-only bundles of what every internal function of a full forward / backward repeats (nothing to do with the kernels'
+// parameter structs, whose layouts are hashed): the shape, and with it the seven parameter pointers and the stream
+struct Shape { int B, T, F, K, hop; };
+struct LeafArgs {
+    Shape s;
+    const float *kernel, *pool_w, *pool_b, *alpha, *delta, *root, *ema_w;
+    hipStream_t st;
+};
 // CU count of the CURRENT device (cached per device ordinal; plans are sized for the device the call runs on)
 int device_cus() {
     constexpr int kMaxDev = 64;
@@ -109,6 +102,33 @@ int device_cus() {
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
     if (dev >= 0 && dev < kMaxDev) cached[dev].store(n, std::memory_order_relaxed);
     return n;
+}
+// the one place that unpacks the forward's `algo` word
+CallCtx forward_ctx(int algo) {
+    CallCtx c{};
+    c.cus = std::max(1, device_cus() - ((algo >> 16) & 0xff));           // LEAF_ALGO_RESERVE_CUS(k): grids of this call leave k CUs free
+    c.stream_finalize = (algo & LEAF_ALGO_STREAM_FINALIZE) != 0;
+    c.band_off = (algo & LEAF_ALGO_FULL_TRANSFORMS) != 0;
+    c.band_strict = (algo & LEAF_ALGO_STRICT_BAND_CLASSES) != 0;
+    c.desync = ((algo >> 8) & 0xff) - 1;
+    c.sel = algo & 0xff;
+    return c;
+}
+// ... and the backward's, whose options travel in `flags` (no reservation, no selector: bwd_path() decides)
+CallCtx backward_ctx(int flags, MixArgs mix) {
+    CallCtx c{};
+    c.cus = device_cus();
+    c.band_off = (flags & LEAF_FLAG_BWD_FULL_TRANSFORMS) != 0;
+    c.band_strict = (flags & LEAF_FLAG_BWD_STRICT_BAND_CLASSES) != 0;
+    c.desync = -1;
+    c.sel = LEAF_ALGO_AUTO;
+    c.mix = mix;
+    return c;
+}
+// Tools-only switch LEAF_WG_GENERIC=1: the static geometries through the run-time-geometry workgroup kernel (A/B measurements)
+inline bool wg_force_generic() {
+    static const bool on = [] { const char* e = tools_env("LEAF_WG_GENERIC"); return e && atoi(e) != 0; }();
+    return on;
 }
 
 struct FusedPlan {
@@ -124,7 +144,8 @@ inline size_t fused_lds_bytes(int R, int rt, int XS) {
     return ((size_t)(R + 4) * 32 * rt + (size_t)kWavesPerWG * (XS + 16)) * 4;
 }
 
-FusedPlan make_plan(int B, int T, int F, int K, int hop) {
+FusedPlan make_plan(const Shape& s, int cus) {
+    const auto [B, T, F, K, hop] = s;
     FusedPlan pl{};
     pl.padL = K / 2 + K % 2 - 1;
     pl.TP = (T + (K - 1) - K) / hop + 1;
@@ -152,7 +173,7 @@ FusedPlan make_plan(int B, int T, int F, int K, int hop) {
     // Widest register tile whose taps fit LDS -- unless the batch is so small that (tasks x filter groups) would not
     // even give every wave slot of the chip one task: then narrower tiles (more filter groups, shorter per-wave
     // dependency chains) cut the latency of a small forward.
-    const long long wave_slots = (long long)num_cus() * kWavesPerWG;
+    const long long wave_slots = (long long)cus * kWavesPerWG;
     // NOFF = 6 instances (4..6 overlapping frames per hop-block): the widest register tiles spill (720 B/lane at RT = 3,
     // 188 B at RT = 2, -Rpass-analysis=kernel-resource-usage), so the tile is capped where it stays in registers;
     // LEAF_FUSED_RT_CAP (environment, tools only) overrides the cap for measurements.
@@ -220,8 +241,7 @@ hipError_t launch_dtaps(const DtapsParams& prm, int rt, int tpw, int groups, siz
 }
 
 // the fused kernel over all filter groups: full groups of rt_main tiles, then the remainder group
-hipError_t launch_fused_groups(FusedParams prm, const FusedPlan& pl, hipStream_t st) {
-    const int cus = num_cus();
+hipError_t launch_fused_groups(FusedParams prm, const FusedPlan& pl, int cus, hipStream_t st) {
     const int wg_needed = ceil_div(prm.total_tasks, kWavesPerWG);
     if (pl.groups_main > 0) {
         prm.tile_base = 0;
@@ -238,7 +258,8 @@ hipError_t launch_fused_groups(FusedParams prm, const FusedPlan& pl, hipStream_t
     return hipSuccess;
 }
 
-FusedParams base_fused_params(const FusedPlan& pl, int B, int T, int F, int K, int hop, int tuning_desync) {
+FusedParams base_fused_params(const FusedPlan& pl, const Shape& s, int tuning_desync) {
+    const auto [B, T, F, K, hop] = s;
     FusedParams prm{};
     prm.B = B; prm.T = T; prm.TP = pl.TP; prm.F = F; prm.FP = pl.FP; prm.K = K; prm.hop = hop; prm.padL = pl.padL;
     prm.KS = pl.KS; prm.Hf = pl.Hf; prm.xshift = pl.xshift; prm.NU = pl.NU; prm.HP = pl.HP; prm.XS = pl.XS;
@@ -332,7 +353,8 @@ inline bool band_edges(int T, int K, int hop, int L, int padL, BandParams& bp, B
     return true;
 }
 
-FftPlan make_fft_plan(int B, int T, int F, int K, int hop) {
+FftPlan make_fft_plan(const Shape& s, int cus) {
+    const auto [B, T, F, K, hop] = s;
     FftPlan fp{};
     if (K < 2 || K > 64 * kPoolRowsMax - 63) return fp;         // pooling rows per window <= kPoolRowsMax (K <= 1217)
     fp.padL = K / 2 + K % 2 - 1;
@@ -343,7 +365,7 @@ FftPlan make_fft_plan(int B, int T, int F, int K, int hop) {
     fp.GZ = (kGPad + K + 256 + 3) / 4 * 4;                   // pooling reads run up to 3 rows + 63 lanes past the window
     // filters per task: as many as keeps one wave slot per SIMD pair busy everywhere -- fewer filters per task means the
     // block's forward transform is repeated more often, which only matters once the chip is full
-    fp.fq = (int)std::min<long long>(kFftFQ, std::max<long long>(1, (long long)B * fp.nblk * F / ((long long)num_cus() * kFftWaves)));
+    fp.fq = (int)std::min<long long>(kFftFQ, std::max<long long>(1, (long long)B * fp.nblk * F / ((long long)cus * kFftWaves)));
     fp.nfq = ceil_div(F, fp.fq);
     fp.scr_floats = 32 * 65;                                 // transposes only: the energies stay in registers
     const size_t scr = (size_t)fp.scr_floats;
@@ -396,7 +418,8 @@ inline bool fft4k_disabled() {
     return off || LEAF_FFT_NO_4K || LEAF_FFT_FORCE_GENERIC;
 }
 FftKernel pick_fft_wgg4k_kernel(int K) { return as_fft_kernel(leaf_inst_fft_wgg4k(fft_wgg4k_taps_per_lane(K))); }
-Fft4kPlan make_fft4k_plan(int B, int T, int F, int K, int hop) {
+Fft4kPlan make_fft4k_plan(const Shape& s) {
+    const auto [B, T, F, K, hop] = s;
     Fft4kPlan fp{};
     if (fft4k_disabled()) return fp;
     fp.padL = K / 2 + K % 2 - 1;
@@ -501,17 +524,17 @@ bool fft_wg_available(const FftPlan& fp, int K, int hop) {
 // Blocks from which the workgroup kernels beat the per-wave kernel: a little under half a block per CU (measured crossover,
 // tools/sweep_batch_wg.py: 80 -> 160 blocks at 16 kHz, 60 -> 120 at 22.05 kHz, 80 -> 120 at 8 kHz, 68 -> 136 4096-sample
 // blocks at 48 kHz; one block per workgroup costs the same 42 / 53 / 104 us from 1 to 256 blocks)
-inline long long fft_wg_min_blocks() { return (long long)num_cus() * 7 / 16; }
+inline long long fft_wg_min_blocks(int cus) { return (long long)cus * 7 / 16; }
 // the same question for the backward kernels, in sixteenths of a block per CU (measured, tools/sweep_batch_wg_bwd.py: the static
 // kernel against the per-wave backward crosses between 320 and 480 blocks at 16 kHz, the run-time-geometry one between 120
 // and 180 at 22.05 kHz, the 4096-sample one between 68 and 136 at 48 kHz); LEAF_WG_BWD_MIN_BLOCKS (environment, tools only)
 // overrides it for the sweep
-inline long long fft_wg_bwd_min_blocks(int sixteenths) {
+inline long long fft_wg_bwd_min_blocks(int cus, int sixteenths) {
     static const long long forced = [] { const char* e = tools_env("LEAF_WG_BWD_MIN_BLOCKS"); return e ? atoll(e) : -1ll; }();
-    return forced >= 0 ? forced : (long long)num_cus() * sixteenths / 16;
+    return forced >= 0 ? forced : (long long)cus * sixteenths / 16;
 }
-bool fft_wg_auto(const FftPlan& fp, int B, int K, int hop) {
-    return fft_wg_available(fp, K, hop) && (long long)B * fp.nblk >= fft_wg_min_blocks() &&
+bool fft_wg_auto(const FftPlan& fp, int B, int K, int hop, int cus) {
+    return fft_wg_available(fp, K, hop) && (long long)B * fp.nblk >= fft_wg_min_blocks(cus) &&
            (K >= 224 || fft_static_geometry(K, hop));
 }
 FftKernel pick_fft_kernel(const FftPlan& fp, int K, int hop, bool bwd) {
@@ -553,7 +576,8 @@ struct SmallPlan {
 #ifndef LEAF_SMALL_ROUNDS
 #define LEAF_SMALL_ROUNDS 2            // rounds of (clip, filter) workgroups over the CUs up to which a batch takes the one-launch kernel (2: 7 .. 12 clips of the default front end 41 -> 30 us; 4: slower than three launches from 16 clips)
 #endif
-SmallPlan make_small_plan(int B, int T, int F, int K, int hop) {
+SmallPlan make_small_plan(const Shape& s, int cus) {
+    const auto [B, T, F, K, hop] = s;
     SmallPlan sp{};
     if (LEAF_FFT_FORCE_GENERIC || !((K == 401 && hop == 160) || (K == 201 && hop == 80))) return sp;
     const int L = fft_block_len(K, hop, true);
@@ -562,9 +586,9 @@ SmallPlan make_small_plan(int B, int T, int F, int K, int hop) {
     sp.ring = std::min(sp.nblk, kSmallRing);
     sp.lds = fft_small_lds_bytes(kSmallWaves, sp.TP);
     // every (clip, filter) pair gets a CU of its own in one round (LEAF_SMALL_ROUNDS = 2: or in two); clips of up to two ring passes
-    sp.ok = (long long)B * F <= (long long)LEAF_SMALL_ROUNDS * num_cus() && F <= 65535 && B <= 65535 && sp.nblk <= kSmallMaxBlocks && sp.lds <= (size_t)kMaxLds;
+    sp.ok = (long long)B * F <= (long long)LEAF_SMALL_ROUNDS * cus && F <= 65535 && B <= 65535 && sp.nblk <= kSmallMaxBlocks && sp.lds <= (size_t)kMaxLds;
     static const bool split_off = [] { const char* e = tools_env("LEAF_SMALL_SPLIT"); return e && atoi(e) == 0; }();   // tools only: A/B
-    if (sp.ok && !split_off && 2ll * B * F <= num_cus() && sp.nblk >= 2 && sp.nblk <= 2 * (kSmallSplitRing - 1) &&
+    if (sp.ok && !split_off && 2ll * B * F <= cus && sp.nblk >= 2 && sp.nblk <= 2 * (kSmallSplitRing - 1) &&
         fft_small_split_lds_bytes(sp.TP) <= (size_t)kMaxLds) {
         sp.split = true;
         sp.lds = fft_small_split_lds_bytes(sp.TP);
@@ -579,20 +603,28 @@ SmallPlan make_small_plan(int B, int T, int F, int K, int hop) {
 // K = 251: 389 vs 841 us; K = 401: 386 vs 1122 us; K = 801: 1.43 vs 4.24 ms.  Batch size does not enter: with the
 // filters-per-task adaptation the FFT path also wins at B = 1 (37 vs 58 us, tools/sweep_small_batch.py).
 // Short windows / geometries the FFT plan rejects -> MFMA; staged as the last resort.
-int auto_algo(int B, int T, int F, int K, int hop, bool allow_small = true) {
-    if (allow_small && make_small_plan(B, T, F, K, hop).ok) return LEAF_ALGO_FFT_SMALL;  // a handful of clips: tables, transforms and PCEN in one launch
-    const FftPlan fp = make_fft_plan(B, T, F, K, hop);
-    const Fft4kPlan f4 = make_fft4k_plan(B, T, F, K, hop);               // long windows: 4096-sample blocks from ~half a block per CU
-    if (f4.ok && (long long)B * f4.nblk >= fft_wg_min_blocks()) return LEAF_ALGO_FFT_WG;
+int auto_algo(const Shape& s, int cus, bool allow_small = true) {
+    const int B = s.B, K = s.K, hop = s.hop;
+    if (allow_small && make_small_plan(s, cus).ok) return LEAF_ALGO_FFT_SMALL;  // a handful of clips: tables, transforms and PCEN in one launch
+    const FftPlan fp = make_fft_plan(s, cus);
+    const Fft4kPlan f4 = make_fft4k_plan(s);                             // long windows: 4096-sample blocks from ~half a block per CU
+    if (f4.ok && (long long)B * f4.nblk >= fft_wg_min_blocks(cus)) return LEAF_ALGO_FFT_WG;
     if (f4.ok) {                                                          // ... below that the 2048-sample per-wave kernel, if it fits
         // (also for the static K = 801 geometry: LEAF_ALGO_FFT_WG always means the 4096-sample kernel there, which the
         // threshold above just ruled out)
         if (fp.ok) return LEAF_ALGO_FFT;
-        return make_plan(B, T, F, K, hop).ok ? LEAF_ALGO_MFMA : LEAF_ALGO_STAGED;
+        return make_plan(s, cus).ok ? LEAF_ALGO_MFMA : LEAF_ALGO_STAGED;
     }
-    if (fft_wg_auto(fp, B, K, hop)) return LEAF_ALGO_FFT_WG;
+    if (fft_wg_auto(fp, B, K, hop, cus)) return LEAF_ALGO_FFT_WG;
     if (fp.ok && (K >= 224 || fft_static_geometry(K, hop))) return LEAF_ALGO_FFT;
-    return make_plan(B, T, F, K, hop).ok ? LEAF_ALGO_MFMA : LEAF_ALGO_STAGED;
+    return make_plan(s, cus).ok ? LEAF_ALGO_MFMA : LEAF_ALGO_STAGED;
+}
+// The one selector resolver: validates the low byte of `algo` and resolves LEAF_ALGO_AUTO; the selector that runs, or
+// LEAF_ERR_BAD_ALGO.  (valid_selector alone where the answer is due before the shape is known to be usable: the empty batch)
+inline bool valid_selector(int sel) { return sel >= LEAF_ALGO_AUTO && sel <= LEAF_ALGO_FFT_SMALL; }
+int resolve_selector(int sel, const Shape& s, int cus) {
+    if (!valid_selector(sel)) return LEAF_ERR_BAD_ALGO;
+    return sel == LEAF_ALGO_AUTO ? auto_algo(s, cus) : sel;
 }
 
 inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
@@ -641,19 +673,18 @@ int check_shape(int B, int T, int F, int K, int hop) {
 // empty batch may be NULL.  Every other extent must still be valid.
 inline bool empty_batch(int B, int T, int F, int K, int hop) { return B == 0 && T >= 1 && F >= 1 && K >= 1 && hop >= 1; }
 
-size_t staged_workspace_floats(int B, int T, int F, int K, int hop) {
-    const int padL = K / 2 + K % 2 - 1;
+size_t staged_workspace_floats(const Shape& s) {
+    const auto [B, T, F, K, hop] = s;
     const int TP = (T + (K - 1) - K) / hop + 1;
-    (void)padL;
     return align_up((size_t)2 * F * K, 64) + align_up((size_t)F * K, 64) + align_up((size_t)B * 2 * F * T, 64) +
            align_up((size_t)B * F * T, 64) + align_up((size_t)B * F * TP, 64);
 }
 
 // the row kernel of the overlap-save paths; `own` = the dealing of the main kernel when that kernel finalized the clips it
 // owned outright (OwnedClips{} = none: every row is finalized here)
-inline void launch_fft_finalize(const FinParams& fin, int B, const OwnedClips& own, hipStream_t st) {
+inline void launch_fft_finalize(const FinParams& fin, int B, const OwnedClips& own, int cus, hipStream_t st) {
     const int tiles = ceil_div(B * fin.F, kFinKernelRows);
-    if (tiles > 2 * num_cus())
+    if (tiles > 2 * cus)
         hipLaunchKernelGGL(fft_finalize_kernel<512>, dim3(tiles), dim3(512), 0, st, fin, B, own);
     else
         hipLaunchKernelGGL(fft_finalize_kernel<1024>, dim3(tiles), dim3(1024), 0, st, fin, B, own);
@@ -670,6 +701,92 @@ inline bool all_clips_owned(const OwnedClips& own) {
     do {                                                     \
         if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH; \
     } while (0)
+
+// workspace of the forward behind a RESOLVED selector (bytes); 0: the selector does not apply to the shape
+size_t forward_workspace_bytes(const Shape& s, int sel, int cus) {
+    switch (sel) {
+        case LEAF_ALGO_FFT_SMALL: {                           // nothing but the per-clip scales of LEAF_FLAG_PEAKNORM
+            const SmallPlan sp = make_small_plan(s, cus);
+            return sp.ok ? (align_up((size_t)s.B, 64) + sp.carry_floats) * 4 : 0;
+        }
+        case LEAF_ALGO_FFT:
+        case LEAF_ALGO_FFT_WG: {
+            const FftPlan fp = make_fft_plan(s, cus);
+            const Fft4kPlan f4 = make_fft4k_plan(s);
+            if (sel == LEAF_ALGO_FFT_WG && f4.ok) return fft4k_workspace_floats(f4, s.B) * 4;
+            if (sel == LEAF_ALGO_FFT_WG && !fft_wg_available(fp, s.K, s.hop)) return 0;
+            return fp.ok ? fft_workspace_floats(fp, s.F, s.B) * 4 : 0;
+        }
+        case LEAF_ALGO_MFMA: {
+            const FusedPlan pl = make_plan(s, cus);
+            return pl.ok ? (align_up(pl.w_floats, 64) + align_up(pl.g_floats, 64) + align_up(pl.meta_ints, 64) +
+                            align_up(pl.part_floats, 64) + (LEAF_TRACE ? 16 * 64 * 2 : 0)) * 4
+                         : 0;
+        }
+        case LEAF_ALGO_STAGED: return staged_workspace_floats(s) * 4;
+    }
+    return 0;
+}
+
+// a kernel with dynamic LDS: raise the function's limit (the attribute is per function and device: set on every call -- a
+// host-side table lookup), launch, report a launch error
+template <class Params>
+int launch_lds(void (*fn)(const Params), dim3 grid, int waves, size_t lds, hipStream_t st, const Params& prm) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(fn, grid, dim3(waves * 64), lds, st, prm);
+    LEAF_LAUNCH_CHECK();
+    return LEAF_OK;
+}
+inline int cu_grid(int work, int cus) { return std::max(1, std::min(work, cus)); }   // persistent workgroups: one per CU at most
+
+// the FftParams fields that an FftPlan decides (the 2048-sample kernels, forward and backward)
+void fill_fft_params(FftParams& q, const FftPlan& fp, const Shape& s) {
+    q.B = s.B; q.T = s.T; q.TP = fp.TP; q.F = s.F; q.K = s.K; q.hop = s.hop; q.padL = fp.padL;
+    q.L = fp.L; q.nblk = fp.nblk; q.GZ = fp.GZ; q.nslot = fp.nslot; q.g_bufs = fp.g_bufs; q.NT = fp.NT; q.fq = fp.fq; q.nfq = fp.nfq;
+    q.scr_floats = fp.scr_floats;
+    q.total_tasks = s.B * fp.nblk * fp.nfq;
+    q.rot = s.K / 2;
+}
+
+// Band-limited filter tasks (leaf_band.hpp, leaf_band_bwd.hpp): where a call's tables live, and the wiring of the table launch's
+// arguments (`ba`) and the main kernel's (`band`) that the four sites share -- the 2048- and 4096-sample forwards and backwards.
+// What differs between them is explicit: the backward's derivative slabs (`bwd_slabs`, with gz2 / edge2 in `t`) and where the
+// bias-aware energy bound applies (`bias`, `smax`: the forward always, the backward unless it is asked for round 5's rule);
+// `cross`, `edge_only` and the tools' `force` belong to single sites and are set there.
+struct BandTabs { int* rec; float* gz; float* gz2; float* edge; float* edge2; int* elist; };
+void wire_band(BandTabArgs& ba, BandParams& band, const BandTabs& t, const Shape& s, int L, int padL, bool strict, int bwd_slabs,
+               const float* bias, float smax) {
+    ba.T = s.T; ba.L = L; ba.hop = s.hop; ba.padL = padL;
+    ba.eps2 = kBandEps2; ba.eta = strict ? kBandEta : kBandEtaFree;      // (leaf_band.hpp: round 6's aliasing bound)
+    ba.bwd_slabs = bwd_slabs;
+    ba.rec = t.rec; ba.gz = t.gz; ba.gz2 = t.gz2; ba.edge = t.edge; ba.edge2 = t.edge2; ba.elist = t.elist; ba.n_edge = band.n_edge;
+    band.rec = t.rec; band.gz = t.gz; band.gz2 = t.gz2; band.edge = t.edge; band.edge2 = t.edge2; band.elist = t.elist;
+    band.bias = bias; band.smax = smax;                                   // the energy bound follows this call's bias (leaf_band.hpp)
+}
+// tools only (LEAF_BAND): 0 switches the forward's band tasks off, 1 / 2 force a class
+inline int band_env() {
+    static const int v = [] { const char* e = tools_env("LEAF_BAND"); return e ? atoi(e) : -1; }();
+    return v;
+}
+// tools only (LEAF_FIN_FUSED=0): no finalize in the workgroup kernels' tails (A/B)
+inline bool fin_fused_off() {
+    static const bool off = [] { const char* e = tools_env("LEAF_FIN_FUSED"); return e && atoi(e) == 0; }();
+    return off;
+}
+
+// the pre-floor pooled energies from the overlap-save partial sums (mode 8), where the caller of the backward saved none
+void finalize_pooled_raw(const LeafArgs& a, const float* part, const SlotGeom& geom, float* raw, int cus) {
+    const int TP = (a.s.T - 1) / a.s.hop + 1;
+    launch_fft_finalize(FinParams{part, a.s.F, TP, geom, a.pool_b, a.alpha, a.delta, a.root, a.ema_w, 1e-12f, 8, raw, raw, nullptr},
+                        a.s.B, OwnedClips{}, cus, a.st);
+}
+// dL/dx from the per-block input gradients: `planes` planes of `N` samples per block
+int launch_dx_gather(bool bf16, const float* dxblk, const Shape& s, int nblk, int planes, int L, int padL, float* g_x, int N, hipStream_t st) {
+    hipLaunchKernelGGL(bf16 ? fft_dx_gather_kernel<true> : fft_dx_gather_kernel<false>, dim3(ceil_div(s.T, 1024), s.B), dim3(256), 0, st,
+                       dxblk, s.T, nblk, planes, L, padL, g_x, N);
+    LEAF_LAUNCH_CHECK();
+    return LEAF_OK;
+}
 
 }  // namespace
 
@@ -694,15 +811,16 @@ const char* leaf_status_string(int status) {
 
 int leaf_auto_algo(int B, int T, int F, int K, int hop) {
     if (check_shape(B, T, F, K, hop) != LEAF_OK) return LEAF_ERR_BAD_SHAPE;
-    return auto_algo(B, T, F, K, hop);
+    return auto_algo(Shape{B, T, F, K, hop}, device_cus());
 }
 
 int leaf_fft_plan_info(int B, int T, int F, int K, int hop, int* info) {
     if (!info) return LEAF_ERR_NULL_POINTER;
     if (check_shape(B, T, F, K, hop) != LEAF_OK) return LEAF_ERR_BAD_SHAPE;
-    const FftPlan fp = make_fft_plan(B, T, F, K, hop);
-    const Fft4kPlan f4 = make_fft4k_plan(B, T, F, K, hop);
-    if (f4.ok && auto_algo(B, T, F, K, hop) == LEAF_ALGO_FFT_WG) {        // what AUTO runs is the 4096-sample plan
+    const Shape s{B, T, F, K, hop};
+    const FftPlan fp = make_fft_plan(s, device_cus());
+    const Fft4kPlan f4 = make_fft4k_plan(s);
+    if (f4.ok && auto_algo(s, device_cus()) == LEAF_ALGO_FFT_WG) {        // what AUTO runs is the 4096-sample plan
         info[0] = kFft4N; info[1] = f4.L; info[2] = f4.nblk; info[3] = F; info[4] = 1; info[5] = f4.nslot;
         info[6] = 0; info[7] = (int)f4.lds;
         return LEAF_OK;
@@ -721,31 +839,10 @@ int leaf_num_frames(int T, int K, int hop) {
 
 size_t leaf_workspace_bytes(int B, int T, int F, int K, int hop, int algo) {
     if (check_shape(B, T, F, K, hop) != LEAF_OK) return 0;
-    const ReserveCus reserve(algo);                          // LEAF_ALGO_RESERVE_CUS(k): AUTO resolves as the forward call will
-    algo &= 0xff;
-    if (algo == LEAF_ALGO_AUTO) algo = auto_algo(B, T, F, K, hop);
-    if (algo == LEAF_ALGO_FFT_SMALL)                          // nothing but the per-clip scales of LEAF_FLAG_PEAKNORM
-        return make_small_plan(B, T, F, K, hop).ok ? (align_up((size_t)B, 64) + make_small_plan(B, T, F, K, hop).carry_floats) * 4 : 0;
-    const FusedPlan pl = make_plan(B, T, F, K, hop);
-    const size_t fused = pl.ok ? (align_up(pl.w_floats, 64) + align_up(pl.g_floats, 64) + align_up(pl.meta_ints, 64) +
-                                  align_up(pl.part_floats, 64) + (LEAF_TRACE ? 16 * 64 * 2 : 0)) * 4
-                               : 0;
-    const size_t staged = staged_workspace_floats(B, T, F, K, hop) * 4;
-    if (algo == LEAF_ALGO_FFT || algo == LEAF_ALGO_FFT_WG) {
-        const FftPlan fp = make_fft_plan(B, T, F, K, hop);
-        const Fft4kPlan f4 = make_fft4k_plan(B, T, F, K, hop);
-        if (algo == LEAF_ALGO_FFT_WG && f4.ok) return fft4k_workspace_floats(f4, B) * 4;
-        if (algo == LEAF_ALGO_FFT_WG && !fft_wg_available(fp, K, hop)) return 0;
-        return fp.ok ? fft_workspace_floats(fp, F, B) * 4 : 0;
-    }
-    if (algo == LEAF_ALGO_MFMA) return fused;
-    if (algo == LEAF_ALGO_STAGED) return staged;
-    if (algo == LEAF_ALGO_AUTO) {
-        const int a = auto_algo(B, T, F, K, hop);
-        if (a == LEAF_ALGO_FFT || a == LEAF_ALGO_FFT_WG) return leaf_workspace_bytes(B, T, F, K, hop, a);
-        return a == LEAF_ALGO_MFMA ? fused : staged;
-    }
-    return 0;
+    const CallCtx ctx = forward_ctx(algo);                   // LEAF_ALGO_RESERVE_CUS(k): AUTO resolves as the forward call will
+    const Shape s{B, T, F, K, hop};
+    const int sel = resolve_selector(ctx.sel, s, ctx.cus);
+    return sel < 0 ? 0 : forward_workspace_bytes(s, sel, ctx.cus);
 }
 
 int leaf_gabor_taps_f32(const float* kernel, int F, int K, float* taps, void* stream) {
@@ -979,162 +1076,183 @@ int leaf_pcen_backward_f32(const float* p, const float* grad_out, int B, int F, 
     return LEAF_OK;
 }
 
-// The overlap-save forward: (tables) -> main kernel -> finalize.  With tables_ready the tables were produced earlier by
-// leaf_fft_prepare_tables_f32 from the same parameters (inference with frozen parameters) and the prep launch is skipped.
-static int fft_forward(const FftPlan& fp, const void* x, int xtype, int B, int T, const float* kernel, const float* pool_w,
-                       const float* pool_b, const float* alpha, const float* delta, const float* root, const float* ema_w,
-                       int F, int K, int hop, int mode, void* out, float* tables, float* part, bool tables_ready,
-                       hipStream_t st, hipEvent_t* ev, float* pooled_raw, bool use_wg, const float* clip_scale2 = nullptr,
-                       float* band_scratch = nullptr) {
-    float2* H = reinterpret_cast<float2*>(tables);
+// what a forward path reads and writes besides the parameters
+struct FwdIo {
+    const void* x;
+    int xtype;                       // sample type of x (leaf_common.hpp kSample*)
+    int mode;                        // finalize mode: bit0 PCEN, bit1 log1p compression, bit2 bfloat16 features
+    void* out;
+    float* pooled_raw;               // leaf_forward_save_f32: the pre-floor pooled energies, else NULL
+    const float* clip_scale2;        // LEAF_FLAG_PEAKNORM: the per-clip scales, else NULL
+    hipEvent_t* ev;                  // leaf_forward_profiled_f32: the four stage events, else NULL
+};
+static inline FinParams fwd_fin_params(const LeafArgs& a, const FwdIo& io, const float* part, int TP, const SlotGeom& geom) {
+    return FinParams{part, a.s.F, TP, geom, a.pool_b, a.alpha, a.delta, a.root, a.ema_w, 1e-12f, io.mode, io.out, io.pooled_raw, io.clip_scale2};
+}
+static inline void record(hipEvent_t* ev, int i, hipStream_t st) { if (ev) (void)hipEventRecord(ev[i], st); }
+
+// the tables of the 2048-sample plan inside one buffer: [spectra | pooling rows | col_of | band tables]
+struct FftTabPtrs { float2* H; float* Gz; int* col_of; float* band; };
+static inline FftTabPtrs fft_tab_ptrs(const FftPlan& fp, float* tables, int F) {
     float* Gz = tables + align_up(fp.h_floats, 64);
     int* col_of = reinterpret_cast<int*>(Gz + align_up(fp.gz_floats, 64));
-    if (ev) (void)hipEventRecord(ev[0], st);
-    // ---- band-limited filter tasks (leaf_band.hpp): narrow-band filters on 256- / 512-point inverse transforms.  Needs the static
-    // workgroup kernel of a geometry they are built for (the training forward takes them too: the pooled tensor it saves for
-    // the backward differs from the full-transform one by ~1e-6, the backward recomputes with full transforms).  The tables are
-    // built by the prep launch itself (fft_prep_band_kernel); with frozen-parameter tables
-    // (tables_ready) the parameter-only part is in them and only the edge tables of this clip length are built here, into
-    // band_scratch.  The plan takes band_lds bytes of LDS behind everything else.
-    BandParams band{};
-    size_t band_lds = 0;
-    const float2* spec0 = nullptr;
-    if (use_wg && !tl_band_off && (!tables_ready || band_scratch)) {
-        static const int band_env = [] { const char* e = tools_env("LEAF_BAND"); return e ? atoi(e) : -1; }();   // tools only: 0 off, 1 / 2 force a class
-        static const bool force_generic = [] { const char* e = tools_env("LEAF_WG_GENERIC"); return e && atoi(e) != 0; }();   // tools only
+    return {reinterpret_cast<float2*>(tables), Gz, col_of, reinterpret_cast<float*>(col_of) + align_up((size_t)F, 64)};
+}
+
+// the band tasks of one 2048-sample forward call: band.rec == NULL when it runs none
+struct FwdBand { BandParams band; size_t lds; const float2* spec0; };
+
+// The table launch of the overlap-save forward, and with it the decision whether this call runs band-limited filter tasks
+// (leaf_band.hpp): narrow-band filters on 256- / 512-point inverse transforms.  They need the static
+// workgroup kernel of a geometry they are built for (the training forward takes them too: the pooled tensor it saves for
+// the backward differs from the full-transform one by ~1e-6, the backward recomputes with full transforms).  The tables are
+// built by the prep launch itself (fft_prep_band_kernel); with frozen-parameter tables
+// (tables_ready) the parameter-only part is in them and only the edge tables of this clip length are built here, into
+// band_scratch.  The plan takes fb.lds bytes of LDS behind everything else.
+static int fft_forward_tables(const CallCtx& ctx, const FftPlan& fp, const LeafArgs& a, const FwdIo& io, float* tables,
+                              bool tables_ready, bool use_wg, float* band_scratch, FwdBand& fb) {
+    const auto [B, T, F, K, hop] = a.s;
+    const FftTabPtrs tp = fft_tab_ptrs(fp, tables, F);
+    if (use_wg && !ctx.band_off && (!tables_ready || band_scratch)) {
         const FftWgLaunch wl = pick_fft_wg_kernel(K, hop);
         const BandLayout bl = band_layout(F, K, hop);
         BandTabArgs ba{};
-        if (bl.stat && wl.fn && wl.nw <= 12 && !force_generic && band_env != 0 && fp.nslot == 2 &&
-            wl.lds + band_lds_bytes(F) <= (size_t)kMaxLds && band_edges(T, K, hop, fp.L, fp.padL, band, ba.e)) {
-            float* bt = reinterpret_cast<float*>(col_of) + align_up((size_t)F, 64);
-            float* dyn = tables_ready ? band_scratch : bt + bl.stat;
-            ba.T = T; ba.L = fp.L; ba.hop = hop; ba.padL = fp.padL;
-            ba.eps2 = kBandEps2; ba.eta = tl_band_strict ? kBandEta : kBandEtaFree; ba.cross = tl_band_strict ? 0 : 1;   // (leaf_band.hpp: round 6's aliasing bound, windows across Nyquist)
-            ba.force = band_env > 0 ? band_env : 0;
-            ba.rec = reinterpret_cast<int*>(bt + bl.rec); ba.gz = bt + bl.gz; ba.edge = dyn + bl.edge;
-            ba.elist = reinterpret_cast<int*>(dyn + bl.elist); ba.n_edge = band.n_edge;
+        if (bl.stat && wl.fn && wl.nw <= 12 && !wg_force_generic() && band_env() != 0 && fp.nslot == 2 &&
+            wl.lds + band_lds_bytes(F) <= (size_t)kMaxLds && band_edges(T, K, hop, fp.L, fp.padL, fb.band, ba.e)) {
+            float* dyn = tables_ready ? band_scratch : tp.band + bl.stat;
+            wire_band(ba, fb.band, BandTabs{reinterpret_cast<int*>(tp.band + bl.rec), tp.band + bl.gz, nullptr, dyn + bl.edge, nullptr,
+                                            reinterpret_cast<int*>(dyn + bl.elist)},
+                      a.s, fp.L, fp.padL, ctx.band_strict, /*bwd_slabs=*/0, a.pool_b, ctx.band_strict ? 1.0f : 2.0f);
+            ba.cross = ctx.band_strict ? 0 : 1;                   // (windows across Nyquist)
+            ba.force = band_env() > 0 ? band_env() : 0;
             ba.edge_only = tables_ready ? 1 : 0;
-            band.rec = ba.rec; band.gz = ba.gz; band.edge = ba.edge; band.elist = ba.elist;
-            band.bias = pool_b; band.smax = tl_band_strict ? 1.0f : 2.0f;   // the energy bound follows this call's bias (leaf_band.hpp)
-            band_lds = band_lds_bytes(F);
+            fb.lds = band_lds_bytes(F);
             // the main kernel's workgroups' FIRST blocks are transformed by this launch too (waves 1..7 of the workgroups (f, 0),
             // idle while wave 0 transforms the taps): the one forward transform nothing in the main kernel overlaps with (eleven
             // waves waited ~12 k cycles for it).  Other launches of this kernel (leaf_fft_prepare_tables_f32, leaf_band_classes_f32)
             // pass no dynamic LDS and spec0 = NULL.
             static const bool spec0_off = [] { const char* e = tools_env("LEAF_SPEC0"); return e && atoi(e) == 0; }();   // tools only: A/B
-            const int main_grid = std::max(1, std::min(B * fp.nblk, num_cus()));
+            const int main_grid = cu_grid(B * fp.nblk, ctx.cus);
             size_t prep_dyn = 0;
             // (16-bit PCM: the table launch reads fp32 and bf16 only -- a third sample type in its first-block loads cost the fp32 path
             // 0.9 us of the table launch at cfg1 -- so the main kernel transforms its first blocks itself: the same bits)
-            if (LEAF_WG_SPEC0 && !spec0_off && !tables_ready && main_grid <= kMaxCusForSpec0 && wl.nw <= 12 && xtype != kSamplePcm16 && !tl_mix.lam) {   // (a mixed call likewise: the table launch does not mix)
-                ba.x = x; ba.io_bf16 = xtype; ba.B = B; ba.nblk = fp.nblk; ba.G = main_grid;
+            if (LEAF_WG_SPEC0 && !spec0_off && !tables_ready && main_grid <= kMaxCusForSpec0 && wl.nw <= 12 && io.xtype != kSamplePcm16 && !ctx.mix.lam) {   // (a mixed call likewise: the table launch does not mix)
+                ba.x = io.x; ba.io_bf16 = io.xtype; ba.B = B; ba.nblk = fp.nblk; ba.G = main_grid;
                 ba.spec0 = reinterpret_cast<float2*>(dyn + bl.spec0);
-                spec0 = ba.spec0;
+                fb.spec0 = ba.spec0;
                 prep_dyn = (size_t)(kPrepWaves - 1) * kWgScrFloats * 4;
                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fft_prep_band_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_dyn);
             }
-            if (!tables_ready || band.n_edge > 0) {
-                hipLaunchKernelGGL(fft_prep_band_kernel, dim3(F, tables_ready ? band.n_edge : 2 + band.n_edge), dim3(kPrepWaves * 64), prep_dyn, st,
-                                   kernel, pool_w, F, K, fp.GZ, gabor_bounds(K), H, Gz, col_of, ba);
+            if (!tables_ready || fb.band.n_edge > 0) {
+                hipLaunchKernelGGL(fft_prep_band_kernel, dim3(F, tables_ready ? fb.band.n_edge : 2 + fb.band.n_edge), dim3(kPrepWaves * 64), prep_dyn, a.st,
+                                   a.kernel, a.pool_w, F, K, fp.GZ, gabor_bounds(K), tp.H, tp.Gz, tp.col_of, ba);
                 LEAF_LAUNCH_CHECK();
             }
         }
     }
-    if (!tables_ready && !band.rec) {
-        hipLaunchKernelGGL(fft_prep_kernel, dim3(F, 1), dim3(kPrepWaves * 64), 0, st, kernel, pool_w, F, K, fp.GZ,
-                           gabor_bounds(K), 1, H, Gz, col_of, fft_lone_taps(tables, F, K));
+    if (!tables_ready && !fb.band.rec) {
+        hipLaunchKernelGGL(fft_prep_kernel, dim3(F, 1), dim3(kPrepWaves * 64), 0, a.st, a.kernel, a.pool_w, F, K, fp.GZ,
+                           gabor_bounds(K), 1, tp.H, tp.Gz, tp.col_of, fft_lone_taps(tables, F, K));
         LEAF_LAUNCH_CHECK();
     }
-    if (ev) (void)hipEventRecord(ev[1], st);
+    return LEAF_OK;
+}
+
+// How the static workgroup kernel finalizes: blocks are dealt contiguously.  Whole clips per workgroup (the batch a multiple of the
+// grid, or fewer clips than CUs never happens here: grid = min(blocks, CUs)) -> the STREAM variant: frame sums in
+// an LDS ring, finalized as the blocks complete, no `part`, no second kernel.  Otherwise a workgroup finalizes the
+// clips it owns outright in its tail and the row kernel sees the clips that straddle two workgroups.
+// Adjusts the launch (`wl`: kernel and LDS) and the kernel's arguments (`q`); true: every clip is finalized by the main kernel.
+static bool fft_wg_fused_finalize(const CallCtx& ctx, const FftPlan& fp, const Shape& s, int grid, size_t band_lds,
+                                  const FinParams& fin, FftWgLaunch& wl, FftParams& q, OwnedClips& own) {
+    const int B = s.B, F = s.F;
+    own = OwnedClips{B * fp.nblk, grid, fp.nblk};
+    const bool all_owned = all_clips_owned(own);
+    q.fin = fin;
+    q.fin_fused = 1;
+    // every workgroup gets the same number of whole clips and their per-frame sums fit behind its scratch: the sums stay
+    // in LDS (ds_add_f32 of the two blocks a window meets; the tail reads them there) -- no `part` traffic at all
+    static const bool lds_sums_off = [] { const char* e = tools_env("LEAF_LDS_SUMS"); return e && atoi(e) == 0; }();   // tools only: A/B
+    if (all_owned && wl.lds_sums && fp.nslot == 2 && !lds_sums_off && !ctx.stream_finalize && (B * fp.nblk) % grid == 0) {
+        const size_t extra = (((size_t)(B / grid) * F * fp.TP + 7) / 8 * 8 + (size_t)F * 8) * 4;   // the sums + the filters' finalize coefficients
+        if (B % grid == 0 && wl.lds + extra + band_lds <= (size_t)kMaxLds) {
+            wl.lds += extra;
+            q.fin_fused = 3;
+        }
+    }
+    static const int stream_env = [] { const char* e = tools_env("LEAF_WG_STREAM"); return e ? atoi(e) : -1; }();   // tools only: A/B
+    // LEAF_ALGO_STREAM_FINALIZE asks for it; without the flag it is what runs wherever the workgroups own whole clips
+    // but their frame sums do NOT fit the LDS (several clips per workgroup, long clips: BASELINE configs[3], [4]) --
+    // there the alternative is the round trip of every partial sum through `part` in HBM (2x the algorithmic traffic)
+#ifndef LEAF_STREAM_AUTO
+#define LEAF_STREAM_AUTO 1         // 0 (A/B builds, tools/compare_builds.py): streaming finalize only on request, as in round 3
+#endif
+    const bool want_stream = stream_env >= 0 ? stream_env != 0 : (ctx.stream_finalize || (LEAF_STREAM_AUTO && q.fin_fused != 3));
+    if (all_owned && wl.fn_stream && fp.nslot == 2 && want_stream) {
+        // the longest ring the LDS holds, up to four times the minimum (lag >= 4: the forward tasks never wait)
+        int ring = 0;
+        for (int r = 4 * wg_stream_ring_min(wl.sk, wl.shop); r >= wg_stream_ring_min(wl.sk, wl.shop); r >>= 1)
+            if (fft_wg_stream_lds_bytes(wl.nw, wl.sk, r, F) + band_lds <= (size_t)kMaxLds) { ring = r; break; }
+        if (ring) {
+            wl.fn = wl.fn_stream;
+            wl.lds = fft_wg_stream_lds_bytes(wl.nw, wl.sk, ring, F);
+            q.stream_ring = ring;
+            q.fin_fused = 2;
+        }
+    }
+    return all_owned;
+}
+
+// The overlap-save forward: (tables) -> main kernel -> finalize.  With tables_ready the tables were produced earlier by
+// leaf_fft_prepare_tables_f32 from the same parameters (inference with frozen parameters) and the prep launch is skipped.
+static int fft_forward(const CallCtx& ctx, const FftPlan& fp, const LeafArgs& a, const FwdIo& io, float* tables, float* part,
+                       bool tables_ready, bool use_wg, float* band_scratch = nullptr) {
+    const auto [B, T, F, K, hop] = a.s;
+    const FftTabPtrs tp = fft_tab_ptrs(fp, tables, F);
+    record(io.ev, 0, a.st);
+    FwdBand fb{};
+    int rc = fft_forward_tables(ctx, fp, a, io, tables, tables_ready, use_wg, band_scratch, fb);
+    if (rc != LEAF_OK) return rc;
+    record(io.ev, 1, a.st);
     FftParams q{};
-    q.x = x; q.io_bf16 = xtype; q.H = H; q.Gz = Gz; q.part = part;
-    q.B = B; q.T = T; q.TP = fp.TP; q.F = F; q.K = K; q.hop = hop; q.padL = fp.padL;
-    q.L = fp.L; q.nblk = fp.nblk; q.GZ = fp.GZ; q.nslot = fp.nslot; q.g_bufs = fp.g_bufs; q.NT = fp.NT; q.fq = fp.fq; q.nfq = fp.nfq;
-    q.scr_floats = fp.scr_floats;
-    q.total_tasks = B * fp.nblk * fp.nfq;
-    q.rot = K / 2;
+    q.x = io.x; q.io_bf16 = io.xtype; q.H = tp.H; q.Gz = tp.Gz; q.part = part;
+    fill_fft_params(q, fp, a.s);
     q.lone = fft_lone_taps(tables, F, K);
+    q.mix_perm = ctx.mix.perm; q.mix_lam = ctx.mix.lam;
 #if LEAF_TRACE
     q.trace = reinterpret_cast<unsigned long long*>(part + align_up(fp.part_floats, 64));
 #endif
-    const FinParams fin{part, F, fp.TP, SlotGeom{fp.L, fp.padL, K, hop, T, fp.nslot}, pool_b, alpha, delta, root, ema_w, 1e-12f, mode,
-                        out, pooled_raw, clip_scale2};
+    const FinParams fin = fwd_fin_params(a, io, part, fp.TP, SlotGeom{fp.L, fp.padL, K, hop, T, fp.nslot});
     OwnedClips own{};                                        // which clips the main kernel finalizes itself (none by default)
     bool all_owned = false;
     if (use_wg) {
         // one persistent workgroup per CU walks its blocks through an LDS task queue (leaf_fft_wg.hpp)
         FftWgLaunch wl = pick_fft_wg_kernel(K, hop);
-        static const bool force_generic = [] { const char* e = tools_env("LEAF_WG_GENERIC"); return e && atoi(e) != 0; }();   // tools only
-        if (!wl.fn || force_generic) {                        // run-time geometry (any other window, odd or even)
-            if (tl_mix.lam) return LEAF_ERR_BAD_ALGO;         // (these kernels do not mix in their loads: mix_fused_forward sends them a mixed copy)
+        if (!wl.fn || wg_force_generic()) {                   // run-time geometry (any other window, odd or even)
+            if (ctx.mix.lam) return LEAF_ERR_BAD_ALGO;        // (these kernels do not mix in their loads: mix_fused_forward sends them a mixed copy)
             wl = pick_fft_wgg_kernel(fp, K, hop);
         }
         if (!wl.fn) return LEAF_ERR_BAD_ALGO;
-        q.mix_perm = tl_mix.perm; q.mix_lam = tl_mix.lam;
-        const int grid = std::max(1, std::min(B * fp.nblk, num_cus()));
-        static const bool fin_off = [] { const char* e = tools_env("LEAF_FIN_FUSED"); return e && atoi(e) == 0; }();   // tools only: A/B
-        if (wl.fused_finalize && LEAF_WG_TAIL && !LEAF_WG_STRIDED && !fin_off) {
-            // clip-resident finalize: blocks are dealt contiguously.  Whole clips per workgroup (the batch a multiple of the
-            // grid, or fewer clips than CUs never happens here: grid = min(blocks, CUs)) -> the STREAM variant: frame sums in
-            // an LDS ring, finalized as the blocks complete, no `part`, no second kernel.  Otherwise a workgroup finalizes the
-            // clips it owns outright in its tail and the row kernel below sees the clips that straddle two workgroups.
-            own = OwnedClips{B * fp.nblk, grid, fp.nblk};
-            all_owned = all_clips_owned(own);
-            q.fin = fin;
-            q.fin_fused = 1;
-            // every workgroup gets the same number of whole clips and their per-frame sums fit behind its scratch: the sums stay
-            // in LDS (ds_add_f32 of the two blocks a window meets; the tail reads them there) -- no `part` traffic at all
-            static const bool lds_sums_off = [] { const char* e = tools_env("LEAF_LDS_SUMS"); return e && atoi(e) == 0; }();   // tools only: A/B
-            if (all_owned && wl.lds_sums && fp.nslot == 2 && !lds_sums_off && !tl_stream_finalize && (B * fp.nblk) % grid == 0) {
-                const size_t extra = (((size_t)(B / grid) * F * fp.TP + 7) / 8 * 8 + (size_t)F * 8) * 4;   // the sums + the filters' finalize coefficients
-                if (B % grid == 0 && wl.lds + extra + band_lds <= (size_t)kMaxLds) {
-                    wl.lds += extra;
-                    q.fin_fused = 3;
-                }
-            }
-            static const int stream_env = [] { const char* e = tools_env("LEAF_WG_STREAM"); return e ? atoi(e) : -1; }();   // tools only: A/B
-            // LEAF_ALGO_STREAM_FINALIZE asks for it; without the flag it is what runs wherever the workgroups own whole clips
-            // but their frame sums do NOT fit the LDS (several clips per workgroup, long clips: BASELINE configs[3], [4]) --
-            // there the alternative is the round trip of every partial sum through `part` in HBM (2x the algorithmic traffic)
-#ifndef LEAF_STREAM_AUTO
-#define LEAF_STREAM_AUTO 1         // 0 (A/B builds, tools/compare_builds.py): streaming finalize only on request, as in round 3
-#endif
-            const bool want_stream = stream_env >= 0 ? stream_env != 0 : (tl_stream_finalize || (LEAF_STREAM_AUTO && q.fin_fused != 3));
-            if (all_owned && wl.fn_stream && fp.nslot == 2 && want_stream) {
-                // the longest ring the LDS holds, up to four times the minimum (lag >= 4: the forward tasks never wait)
-                int ring = 0;
-                for (int r = 4 * wg_stream_ring_min(wl.sk, wl.shop); r >= wg_stream_ring_min(wl.sk, wl.shop); r >>= 1)
-                    if (fft_wg_stream_lds_bytes(wl.nw, wl.sk, r, F) + band_lds <= (size_t)kMaxLds) { ring = r; break; }
-                if (ring) {
-                    wl.fn = wl.fn_stream;
-                    wl.lds = fft_wg_stream_lds_bytes(wl.nw, wl.sk, ring, F);
-                    q.stream_ring = ring;
-                    q.fin_fused = 2;
-                }
-            }
-        }
-        if (band.rec) {                                       // (decided before the prep launch, which built the tables)
-            q.spec0 = grid == std::max(1, std::min(B * fp.nblk, num_cus())) ? spec0 : nullptr;
-            q.band = band;
+        const int grid = cu_grid(B * fp.nblk, ctx.cus);
+        if (wl.fused_finalize && LEAF_WG_TAIL && !LEAF_WG_STRIDED && !fin_fused_off())
+            all_owned = fft_wg_fused_finalize(ctx, fp, a.s, grid, fb.lds, fin, wl, q, own);
+        if (fb.band.rec) {                                    // (decided before the prep launch, which built the tables)
+            q.spec0 = fb.spec0;
+            q.band = fb.band;
             q.band.lds_off = (int)(wl.lds / 4);
-            wl.lds += band_lds;
+            wl.lds += fb.lds;
         }
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wl.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl.lds);
-        hipLaunchKernelGGL(wl.fn, dim3(grid), dim3(wl.nw * 64), wl.lds, st, q);
+        rc = launch_lds(wl.fn, dim3(grid), wl.nw, wl.lds, a.st, q);
     } else {
-        FftKernel kfn = tl_mix.lam ? pick_fft_kernel_mix(fp, K, hop, false) : pick_fft_kernel(fp, K, hop, false);
+        FftKernel kfn = ctx.mix.lam ? pick_fft_kernel_mix(fp, K, hop, false) : pick_fft_kernel(fp, K, hop, false);
         if (!kfn) return LEAF_ERR_BAD_ALGO;                   // (mixed call: mix_fused_forward admits the static odd windows only)
-        q.mix_perm = tl_mix.perm; q.mix_lam = tl_mix.lam;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds);
-        hipLaunchKernelGGL(kfn, dim3(std::max(1, std::min(ceil_div(q.total_tasks, kFftWaves), num_cus()))), dim3(kFftWaves * 64),
-                           fp.lds, st, q);
+        rc = launch_lds(kfn, dim3(cu_grid(ceil_div(q.total_tasks, kFftWaves), ctx.cus)), kFftWaves, fp.lds, a.st, q);
     }
+    if (rc != LEAF_OK) return rc;
+    record(io.ev, 2, a.st);
+    if (!all_owned) launch_fft_finalize(fin, B, own, ctx.cus, a.st);
     LEAF_LAUNCH_CHECK();
-    if (ev) (void)hipEventRecord(ev[2], st);
-    if (!all_owned) launch_fft_finalize(fin, B, own, st);
-    LEAF_LAUNCH_CHECK();
-    if (ev) (void)hipEventRecord(ev[3], st);
+    record(io.ev, 3, a.st);
     return LEAF_OK;
 }
 
@@ -1147,233 +1265,226 @@ int leaf_peak_normalize_f32(const float* x, int B, int T, float* out, void* stre
     return LEAF_OK;
 }
 
-static int forward_impl(const void* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
-                        const float* alpha, const float* delta, const float* root, const float* ema_w, int F, int K, int hop,
-                        int flags, int algo, void* out, void* workspace, size_t workspace_bytes, void* stream,
-                        hipEvent_t* ev, float* pooled_raw = nullptr) {
-    {
-        // the selector, the flag combination and the build's layout check hold for the empty batch too (a bad selector or a
-        // mismatched build must not go unnoticed on an empty shard): only then (0, F, T') -- nothing to compute, nothing launched
-        const int sel = algo & 0xff;
-        if (sel != LEAF_ALGO_AUTO && sel != LEAF_ALGO_STAGED && sel != LEAF_ALGO_MFMA && sel != LEAF_ALGO_FFT && sel != LEAF_ALGO_FFT_WG &&
-            sel != LEAF_ALGO_FFT_SMALL)
-            return LEAF_ERR_BAD_ALGO;
-        if ((flags & LEAF_FLAG_X_PCM16) && (flags & LEAF_FLAG_IO_BF16)) return LEAF_ERR_UNSUPPORTED;   // two types for x (int16 in, bfloat16 out: LEAF_FLAG_OUT_BF16)
-        if ((flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16 | LEAF_FLAG_OUT_BF16)) && sel == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
-        if (B == 0 && !inst_layouts_ok()) return LEAF_ERR_LAUNCH;
+// LEAF_ALGO_FFT_SMALL -- one launch: grid (F, B), every workgroup builds its filter's tables, transforms its clip's blocks and
+// finalizes its row
+static int forward_small(const CallCtx& ctx, const LeafArgs& a, const FwdIo& io, float* ws) {
+    const auto [B, T, F, K, hop] = a.s;
+    const SmallPlan sp = make_small_plan(a.s, ctx.cus);
+    if (!sp.ok) return LEAF_ERR_BAD_ALGO;
+    using SmallKernel = void (*)(const SmallParams);
+    const SmallKernel kfn = reinterpret_cast<SmallKernel>(const_cast<void*>(ctx.mix.lam ? leaf_inst_fft_small_mix(K, sp.split) : leaf_inst_fft_small(K, sp.split)));
+    if (!kfn) return LEAF_ERR_BAD_ALGO;
+    SmallParams q{};
+    q.x = io.x; q.io_bf16 = io.xtype; q.kernel = a.kernel; q.pool_w = a.pool_w; q.bd = gabor_bounds(K);
+    q.B = B; q.T = T; q.TP = sp.TP; q.F = F; q.nblk = sp.nblk; q.ring = sp.split ? kSmallSplitRing : sp.ring;
+    q.mix_perm = ctx.mix.perm; q.mix_lam = ctx.mix.lam;
+    q.fin = fwd_fin_params(a, io, nullptr, sp.TP, SlotGeom{fft_block_len(K, hop, true), K / 2 + K % 2 - 1, K, hop, T, 2});
+    record(io.ev, 0, a.st); record(io.ev, 1, a.st);
+    if (sp.split) {
+        // this launch's ticket for the seam hand-over (64 bits from a random seed: stale or uninitialised workspace never matches)
+        static std::atomic<unsigned long long> ticket{[] { std::random_device rd; return ((unsigned long long)rd() << 32) ^ rd(); }()};
+        q.epoch = ticket.fetch_add(1, std::memory_order_relaxed) + 1;
+        if (q.epoch == 0) q.epoch = ticket.fetch_add(1, std::memory_order_relaxed) + 1;   // 0 = "taken out" (the consumer resets the slot)
+        q.carry = reinterpret_cast<unsigned long long*>(ws);          // (the per-clip scales sit at the workspace's end)
     }
-    if (empty_batch(B, T, F, K, hop)) return LEAF_OK;
-    if (!x || !kernel || !pool_w || !pool_b || !out) return LEAF_ERR_NULL_POINTER;
-    const bool use_pcen = (flags & LEAF_FLAG_PCEN) != 0;
-    if (use_pcen && (!alpha || !delta || !root || !ema_w)) return LEAF_ERR_NULL_POINTER;
-    int rc = check_shape(B, T, F, K, hop);
+    const int rc = launch_lds(kfn, dim3(F, B, sp.split ? 2 : 1), sp.split ? kSmallSplitWaves : kSmallWaves, sp.lds, a.st, q);
     if (rc != LEAF_OK) return rc;
-    {
-        const uintptr_t out_mask = feat_bf16(flags) ? 1u : 3u;                                       // bfloat16 features: 2-byte elements
-        const uintptr_t x_mask = (flags & (LEAF_FLAG_X_PCM16 | LEAF_FLAG_IO_BF16)) ? 1u : 3u;        // 16-bit PCM / bfloat16 waveform
-        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & out_mask) || misaligned16(workspace) ||
-            any_misaligned(kernel, pool_w, pool_b, alpha, delta, root, ema_w, pooled_raw))
-            return LEAF_ERR_ALIGNMENT;
-    }
-    const int tuning_desync = ((algo >> 8) & 0xff) - 1;      // LEAF_ALGO_TUNE_DESYNC(n); -1 = automatic
-    const ReserveCus reserve(algo);                          // LEAF_ALGO_RESERVE_CUS(k): grids of this call leave k CUs free
-    algo &= 0xff;
-    if (algo != LEAF_ALGO_AUTO && algo != LEAF_ALGO_STAGED && algo != LEAF_ALGO_MFMA && algo != LEAF_ALGO_FFT &&
-        algo != LEAF_ALGO_FFT_WG && algo != LEAF_ALGO_FFT_SMALL)
-        return LEAF_ERR_BAD_ALGO;
-    const FusedPlan pl = make_plan(B, T, F, K, hop);
-    const bool out_bf16 = feat_bf16(flags);                                           // what the finalize sites store out as
-    const int xtype = x_sample_type(flags);                                           // what the kernels read x as: the two types are independent
-    const bool fused_only = xtype != kSampleF32 || out_bf16;                          // 16-bit input and bfloat16 features are fused-path features
-    if (fused_only && algo == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
-    if (algo == LEAF_ALGO_MFMA && !pl.ok) return LEAF_ERR_BAD_ALGO;
-    if (algo == LEAF_ALGO_AUTO) algo = auto_algo(B, T, F, K, hop);
-    if (fused_only && algo == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
-    // a PCM sample means v / 32768, so no clip's peak exceeds 1: peak normalisation is the identity (no pre-pass, every scale 1)
-    if (xtype == kSamplePcm16) flags &= ~LEAF_FLAG_PEAKNORM;
-    const size_t need = leaf_workspace_bytes(B, T, F, K, hop, algo);
-    if (!workspace || workspace_bytes < need) return LEAF_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (out_bf16 ? 4 : 0);
-    const int TP = pl.TP;
-    float* ws = static_cast<float*>(workspace);
-    // LEAF_FLAG_PEAKNORM: per-clip scales into the tail of the workspace (the last align_up(B, 64) floats the overlap-save
-    // plans reserve), applied to the pooled energies by the finalize step
-    float* clip_scale2 = nullptr;
-    if (flags & LEAF_FLAG_PEAKNORM) {
-        if (algo != LEAF_ALGO_FFT && algo != LEAF_ALGO_FFT_WG && algo != LEAF_ALGO_FFT_SMALL) return LEAF_ERR_UNSUPPORTED;
-        clip_scale2 = ws + need / 4 - align_up((size_t)B, 64);
-        hipLaunchKernelGGL(peak_scale2_kernel, dim3(B), dim3(1024), 0, st, x, xtype, T, clip_scale2);
-        LEAF_LAUNCH_CHECK();
-    }
+    record(io.ev, 2, a.st); record(io.ev, 3, a.st);
+    return LEAF_OK;
+}
 
-    if (algo == LEAF_ALGO_FFT_SMALL) {
-        // one launch: grid (F, B), every workgroup builds its filter's tables, transforms its clip's blocks and finalizes its row
-        const SmallPlan sp = make_small_plan(B, T, F, K, hop);
-        if (!sp.ok) return LEAF_ERR_BAD_ALGO;
-        using SmallKernel = void (*)(const SmallParams);
-        const SmallKernel kfn = reinterpret_cast<SmallKernel>(const_cast<void*>(tl_mix.lam ? leaf_inst_fft_small_mix(K, sp.split) : leaf_inst_fft_small(K, sp.split)));
-        if (!kfn) return LEAF_ERR_BAD_ALGO;
-        SmallParams q{};
-        q.x = x; q.io_bf16 = xtype; q.kernel = kernel; q.pool_w = pool_w; q.bd = gabor_bounds(K);
-        q.B = B; q.T = T; q.TP = sp.TP; q.F = F; q.nblk = sp.nblk; q.ring = sp.split ? kSmallSplitRing : sp.ring;
-        q.mix_perm = tl_mix.perm; q.mix_lam = tl_mix.lam;
-        q.fin = FinParams{nullptr, F, sp.TP, SlotGeom{fft_block_len(K, hop, true), K / 2 + K % 2 - 1, K, hop, T, 2}, pool_b, alpha, delta,
-                          root, ema_w, 1e-12f, mode, out, pooled_raw, clip_scale2};
-        if (ev) { (void)hipEventRecord(ev[0], st); (void)hipEventRecord(ev[1], st); }
-        // (the attribute is per function and device: set on every call like the other kernels -- a host-side table lookup)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.lds);
-        if (sp.split) {
-            // this launch's ticket for the seam hand-over (64 bits from a random seed: stale or uninitialised workspace never matches)
-            static std::atomic<unsigned long long> ticket{[] { std::random_device rd; return ((unsigned long long)rd() << 32) ^ rd(); }()};
-            q.epoch = ticket.fetch_add(1, std::memory_order_relaxed) + 1;
-            if (q.epoch == 0) q.epoch = ticket.fetch_add(1, std::memory_order_relaxed) + 1;   // 0 = "taken out" (the consumer resets the slot)
-            q.carry = reinterpret_cast<unsigned long long*>(ws);          // (the per-clip scales sit at the workspace's end)
-        }
-        hipLaunchKernelGGL(kfn, dim3(F, B, sp.split ? 2 : 1), dim3((sp.split ? kSmallSplitWaves : kSmallWaves) * 64), sp.lds, st, q);
-        LEAF_LAUNCH_CHECK();
-        if (ev) { (void)hipEventRecord(ev[2], st); (void)hipEventRecord(ev[3], st); }
-        return LEAF_OK;
+// LEAF_ALGO_FFT_WG on 4096-sample blocks: tables -> workgroup kernel -> the same finalize kernel (partials keep their layout)
+static int forward_4k(const CallCtx& ctx, const Fft4kPlan& f4, const LeafArgs& a, const FwdIo& io, float* ws) {
+    const auto [B, T, F, K, hop] = a.s;
+    float* tab = ws;
+    float* Grow = tab + align_up(f4.tab_floats, 64);
+    float* part = Grow + align_up(f4.grow_floats, 64);
+    record(io.ev, 0, a.st);
+    float2* Wt = reinterpret_cast<float2*>(Grow + (size_t)F * 2 * f4.RG);
+    // band-limited filter tasks (leaf_band.hpp): the static instance runs the filters whose spectrum sits in a 512-bin window
+    // of the 4096-point spectrum four to a task on 512-point transforms (decided per call by the prep kernel from the
+    // spectrum it has just built; tables by fft4k_band_tab_kernel); LEAF_ALGO_FULL_TRANSFORMS switches them off
+    BandParams band{};
+    BandTabArgs ba{};
+    size_t band_lds = 0;
+    if (!f4.generic && f4.band_floats && !ctx.band_off && band_env() != 0 && f4.lds + band_lds_bytes(F) <= (size_t)kMaxLds &&
+        band_edges(T, K, hop, f4.L, f4.padL, band, ba.e)) {
+        const Band4kLayout bl = band4k_layout(F, K, hop);
+        float* bt = part + align_up(f4.part_floats, 64);
+        wire_band(ba, band, BandTabs{reinterpret_cast<int*>(bt + bl.rec), bt + bl.gz, nullptr, bt + bl.edge, nullptr, reinterpret_cast<int*>(bt + bl.elist)},
+                  a.s, f4.L, f4.padL, ctx.band_strict, /*bwd_slabs=*/0, a.pool_b, ctx.band_strict ? 1.0f : 2.0f);
+        ba.force = band_env() > 0 ? band_env() : 0;           // (tools: 2 = every filter)
+        band_lds = band_lds_bytes(F);
     }
-    if (algo == LEAF_ALGO_FFT_WG) {
-        const Fft4kPlan f4 = make_fft4k_plan(B, T, F, K, hop);
-        if (f4.ok) {
-            // 4096-sample blocks: tables -> workgroup kernel -> the same finalize kernel (partials keep their layout)
-            float* tab = ws;
-            float* Grow = tab + align_up(f4.tab_floats, 64);
-            float* part = Grow + align_up(f4.grow_floats, 64);
-            if (ev) (void)hipEventRecord(ev[0], st);
-            float2* Wt = reinterpret_cast<float2*>(Grow + (size_t)F * 2 * f4.RG);
-            // band-limited filter tasks (leaf_band.hpp): the static instance runs the filters whose spectrum sits in a 512-bin window
-            // of the 4096-point spectrum four to a task on 512-point transforms (decided per call by the prep kernel from the
-            // spectrum it has just built; tables by fft4k_band_tab_kernel); LEAF_ALGO_FULL_TRANSFORMS switches them off
-            BandParams band{};
-            BandTabArgs ba{};
-            size_t band_lds = 0;
-            static const int band_env = [] { const char* e = tools_env("LEAF_BAND"); return e ? atoi(e) : -1; }();   // tools only: 0 off, 2 every filter
-            if (!f4.generic && f4.band_floats && !tl_band_off && band_env != 0 && f4.lds + band_lds_bytes(F) <= (size_t)kMaxLds &&
-                band_edges(T, K, hop, f4.L, f4.padL, band, ba.e)) {
-                const Band4kLayout bl = band4k_layout(F, K, hop);
-                float* bt = part + align_up(f4.part_floats, 64);
-                ba.T = T; ba.L = f4.L; ba.hop = hop; ba.padL = f4.padL;
-                ba.eps2 = kBandEps2; ba.eta = tl_band_strict ? kBandEta : kBandEtaFree; ba.force = band_env > 0 ? band_env : 0;
-                ba.rec = reinterpret_cast<int*>(bt + bl.rec); ba.gz = bt + bl.gz; ba.edge = bt + bl.edge;
-                ba.elist = reinterpret_cast<int*>(bt + bl.elist); ba.n_edge = band.n_edge;
-                band.rec = ba.rec; band.gz = ba.gz; band.edge = ba.edge; band.elist = ba.elist;
-                band.bias = pool_b; band.smax = tl_band_strict ? 1.0f : 2.0f;   // the energy bound follows this call's bias
-                band_lds = band_lds_bytes(F);
-            }
-            hipLaunchKernelGGL(fft4k_prep_kernel, dim3(F), dim3(kPrepWaves * 64), 0, st, kernel, pool_w, F, K, gabor_bounds(K), tab,
-                               Grow, f4.RG, Wt, ba);
-            LEAF_LAUNCH_CHECK();
-            if (band.rec) hipLaunchKernelGGL(fft4k_band_tab_kernel, dim3(F, 1 + band.n_edge), dim3(kPrepWaves * 64), 0, st, pool_w, F, K, ba);
-            LEAF_LAUNCH_CHECK();
-            if (ev) (void)hipEventRecord(ev[1], st);
-            FftParams q{};
-            q.x = x; q.io_bf16 = xtype; q.H = reinterpret_cast<const float2*>(tab); q.Gz = Grow; q.part = part;
-            q.B = B; q.T = T; q.TP = f4.TP; q.F = F; q.K = K; q.hop = hop; q.padL = f4.padL; q.L = f4.L; q.nblk = f4.nblk;
-            q.nslot = f4.nslot; q.GZ = f4.RG; q.NT = f4.generic ? fft_wgg4k_frame_floats(K, hop) : 0;
-            q.mix_perm = tl_mix.perm; q.mix_lam = tl_mix.lam;
-            q.lone = reinterpret_cast<const float*>(Wt);                  // (static 32 kHz kernel: the shared twiddle table travels in `lone`)
-            if (band.rec) {
-                q.band = band;
-                q.band.lds_off = (int)(f4.lds / 4);
-            }
-            FftKernel kfn = f4.generic ? pick_fft_wgg4k_kernel(K) : as_fft_kernel(leaf_inst_fft_wg4k());
-            const size_t lds = f4.lds + band_lds;
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            // blocks dealt contiguously; a workgroup finalizes the clips it ran every block of in its tail (as fft_forward)
-            const int grid = std::max(1, std::min(B * f4.nblk, num_cus()));
-            const FinParams fin{part, F, f4.TP, SlotGeom{f4.L, f4.padL, K, hop, T, f4.nslot}, pool_b, alpha, delta, root, ema_w,
-                                1e-12f, mode, out, pooled_raw, clip_scale2};
-            static const bool fin_off = [] { const char* e = tools_env("LEAF_FIN_FUSED"); return e && atoi(e) == 0; }();   // tools only: A/B
-            OwnedClips own{};
-            if (!fin_off) {
-                own = OwnedClips{B * f4.nblk, grid, f4.nblk};
-                q.fin = fin;
-                q.fin_fused = 1;
-            }
-            hipLaunchKernelGGL(kfn, dim3(grid), dim3(f4.nw * 64), lds, st, q);
-            LEAF_LAUNCH_CHECK();
-            if (ev) (void)hipEventRecord(ev[2], st);
-            if (fin_off || !all_clips_owned(own)) launch_fft_finalize(fin, B, own, st);
-            LEAF_LAUNCH_CHECK();
-            if (ev) (void)hipEventRecord(ev[3], st);
-            return LEAF_OK;
-        }
+    hipLaunchKernelGGL(fft4k_prep_kernel, dim3(F), dim3(kPrepWaves * 64), 0, a.st, a.kernel, a.pool_w, F, K, gabor_bounds(K), tab,
+                       Grow, f4.RG, Wt, ba);
+    LEAF_LAUNCH_CHECK();
+    if (band.rec) hipLaunchKernelGGL(fft4k_band_tab_kernel, dim3(F, 1 + band.n_edge), dim3(kPrepWaves * 64), 0, a.st, a.pool_w, F, K, ba);
+    LEAF_LAUNCH_CHECK();
+    record(io.ev, 1, a.st);
+    FftParams q{};
+    q.x = io.x; q.io_bf16 = io.xtype; q.H = reinterpret_cast<const float2*>(tab); q.Gz = Grow; q.part = part;
+    q.B = B; q.T = T; q.TP = f4.TP; q.F = F; q.K = K; q.hop = hop; q.padL = f4.padL; q.L = f4.L; q.nblk = f4.nblk;
+    q.nslot = f4.nslot; q.GZ = f4.RG; q.NT = f4.generic ? fft_wgg4k_frame_floats(K, hop) : 0;
+    q.mix_perm = ctx.mix.perm; q.mix_lam = ctx.mix.lam;
+    q.lone = reinterpret_cast<const float*>(Wt);                  // (static 32 kHz kernel: the shared twiddle table travels in `lone`)
+    if (band.rec) {
+        q.band = band;
+        q.band.lds_off = (int)(f4.lds / 4);
     }
-    if (algo == LEAF_ALGO_FFT || algo == LEAF_ALGO_FFT_WG) {
-        const FftPlan fp = make_fft_plan(B, T, F, K, hop);
-        if (!fp.ok) return LEAF_ERR_BAD_ALGO;
-        float* tables = ws;                                        // [spectra | pooling rows | col_of], then the partials
-        float* part = ws + fft_table_floats(fp, F);
-        return fft_forward(fp, x, xtype, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, mode, out,
-                           tables, part, /*tables_ready=*/false, st, ev, pooled_raw, algo == LEAF_ALGO_FFT_WG, clip_scale2);
+    // blocks dealt contiguously; a workgroup finalizes the clips it ran every block of in its tail (as fft_forward)
+    const int grid = cu_grid(B * f4.nblk, ctx.cus);
+    const FinParams fin = fwd_fin_params(a, io, part, f4.TP, SlotGeom{f4.L, f4.padL, K, hop, T, f4.nslot});
+    OwnedClips own{};
+    if (!fin_fused_off()) {
+        own = OwnedClips{B * f4.nblk, grid, f4.nblk};
+        q.fin = fin;
+        q.fin_fused = 1;
     }
+    const int rc = launch_lds(f4.generic ? pick_fft_wgg4k_kernel(K) : as_fft_kernel(leaf_inst_fft_wg4k()), dim3(grid), f4.nw, f4.lds + band_lds, a.st, q);
+    if (rc != LEAF_OK) return rc;
+    record(io.ev, 2, a.st);
+    if (fin_fused_off() || !all_clips_owned(own)) launch_fft_finalize(fin, B, own, ctx.cus, a.st);
+    LEAF_LAUNCH_CHECK();
+    record(io.ev, 3, a.st);
+    return LEAF_OK;
+}
 
-    if (tl_mix.lam) return LEAF_ERR_BAD_ALGO;                 // (MFMA and staged kernels do not mix in their loads)
-    if (algo == LEAF_ALGO_MFMA) {
-        float* W = ws;
-        float* G = ws + align_up(pl.w_floats, 64);
-        int* meta = reinterpret_cast<int*>(G + align_up(pl.g_floats, 64));
-        int* perm = meta;
-        int* col_of = meta + pl.FP;
-        int* tile_ks = meta + 2 * pl.FP;
-        float* part = G + align_up(pl.g_floats, 64) + align_up(pl.meta_ints, 64);
-        if (ev) (void)hipEventRecord(ev[0], st);
-        hipLaunchKernelGGL(fused_prep_kernel, dim3(ceil_div(pl.R * 2 * pl.FP + pl.FP * pl.GJ, 256)), dim3(256), 0, st,
-                           kernel, pool_w, F, pl.FP, K, pl.R, pl.GJ, gabor_bounds(K), W, G, (float*)nullptr, perm, col_of,
-                           tile_ks);
-        LEAF_LAUNCH_CHECK();
-        if (ev) (void)hipEventRecord(ev[1], st);
-        FusedParams prm = base_fused_params(pl, B, T, F, K, hop, tuning_desync);
-        prm.x = x; prm.io_bf16 = xtype; prm.W = W; prm.G = G; prm.tile_ks = tile_ks; prm.part = part;
+// the tables of the MFMA kernels inside the workspace (forward: behind each other from its start)
+struct FusedTabs { float* W; float* G; int *perm, *col_of, *tile_ks; };
+static inline FusedTabs fused_tabs(const FusedPlan& pl, float* W, float* G, int* meta) { return {W, G, meta, meta + pl.FP, meta + 2 * pl.FP}; }
+static inline void launch_fused_finalize(const FusedPlan& pl, const LeafArgs& a, const float* part, const int* col_of, int mode, void* out, float* pooled_raw) {
+    hipLaunchKernelGGL(finalize_kernel, dim3(a.s.B, ceil_div(a.s.F, kFinGroup)), dim3(kFinGroup * 64), (size_t)kFinGroup * (kFinStride + 3) * 4, a.st, part, a.s.F, pl.FP, pl.TP, pl.noff,
+                       pl.q_lo, pl.q_hi, SlotGeom{}, col_of, a.pool_b, a.alpha, a.delta, a.root, a.ema_w, 1e-12f, mode, out, pooled_raw);
+}
+
+// LEAF_ALGO_MFMA: tables -> the direct-form kernel over the filter groups -> finalize
+static int forward_mfma(const CallCtx& ctx, const FusedPlan& pl, const LeafArgs& a, const FwdIo& io, float* ws) {
+    const auto [B, T, F, K, hop] = a.s;
+    float* G = ws + align_up(pl.w_floats, 64);
+    const FusedTabs t = fused_tabs(pl, ws, G, reinterpret_cast<int*>(G + align_up(pl.g_floats, 64)));
+    float* part = G + align_up(pl.g_floats, 64) + align_up(pl.meta_ints, 64);
+    record(io.ev, 0, a.st);
+    hipLaunchKernelGGL(fused_prep_kernel, dim3(ceil_div(pl.R * 2 * pl.FP + pl.FP * pl.GJ, 256)), dim3(256), 0, a.st,
+                       a.kernel, a.pool_w, F, pl.FP, K, pl.R, pl.GJ, gabor_bounds(K), t.W, t.G, (float*)nullptr, t.perm, t.col_of,
+                       t.tile_ks);
+    LEAF_LAUNCH_CHECK();
+    record(io.ev, 1, a.st);
+    FusedParams prm = base_fused_params(pl, a.s, ctx.desync);
+    prm.x = io.x; prm.io_bf16 = io.xtype; prm.W = t.W; prm.G = t.G; prm.tile_ks = t.tile_ks; prm.part = part;
 #if LEAF_TRACE
-        prm.trace = reinterpret_cast<unsigned long long*>(part + align_up(pl.part_floats, 64));
+    prm.trace = reinterpret_cast<unsigned long long*>(part + align_up(pl.part_floats, 64));
 #endif
-        if (launch_fused_groups(prm, pl, st) != hipSuccess) return LEAF_ERR_LAUNCH;
-        if (ev) (void)hipEventRecord(ev[2], st);
-        hipLaunchKernelGGL(finalize_kernel, dim3(B, ceil_div(F, kFinGroup)), dim3(kFinGroup * 64), (size_t)kFinGroup * (kFinStride + 3) * 4, st, part, F, pl.FP, TP, pl.noff,
-                           pl.q_lo, pl.q_hi, SlotGeom{}, col_of, pool_b, alpha, delta, root, ema_w, 1e-12f, mode, out, pooled_raw);
-        LEAF_LAUNCH_CHECK();
-        if (ev) (void)hipEventRecord(ev[3], st);
-        return LEAF_OK;
-    }
+    if (launch_fused_groups(prm, pl, ctx.cus, a.st) != hipSuccess) return LEAF_ERR_LAUNCH;
+    record(io.ev, 2, a.st);
+    launch_fused_finalize(pl, a, part, t.col_of, io.mode, io.out, io.pooled_raw);
+    LEAF_LAUNCH_CHECK();
+    record(io.ev, 3, a.st);
+    return LEAF_OK;
+}
 
-    // staged path: every intermediate of the reference graph is materialised in the workspace
+// LEAF_ALGO_STAGED: every intermediate of the reference graph is materialised in the workspace
+static int forward_staged(const LeafArgs& a, const FwdIo& io, float* ws) {
+    const auto [B, T, F, K, hop] = a.s;
     if (2 * F > 65535 || B > 65535) return LEAF_ERR_BAD_SHAPE;
-    const float* xf32 = static_cast<const float*>(x);
-    float* outf32 = static_cast<float*>(out);
+    const int TP = (T - 1) / hop + 1;
+    float* outf32 = static_cast<float*>(io.out);
     float* taps = ws;
     float* g = taps + align_up((size_t)2 * F * K, 64);
     float* y = g + align_up((size_t)F * K, 64);
     float* e = y + align_up((size_t)B * 2 * F * T, 64);
     float* pooled = e + align_up((size_t)B * F * T, 64);
-    rc = leaf_gabor_conv_f32(xf32, B, T, kernel, F, K, y, taps, (size_t)2 * F * K * 4, stream);
+    int rc = leaf_gabor_conv_f32(static_cast<const float*>(io.x), B, T, a.kernel, F, K, y, taps, (size_t)2 * F * K * 4, a.st);
     if (rc != LEAF_OK) return rc;
-    rc = leaf_squared_modulus_f32(y, B, F, T, e, stream);
+    rc = leaf_squared_modulus_f32(y, B, F, T, e, a.st);
     if (rc != LEAF_OK) return rc;
-    rc = leaf_gaussian_lowpass_f32(e, B, F, T, pool_w, pool_b, K, hop, pooled, g, (size_t)F * K * 4, stream);
+    rc = leaf_gaussian_lowpass_f32(e, B, F, T, a.pool_w, a.pool_b, K, hop, pooled, g, (size_t)F * K * 4, a.st);
     if (rc != LEAF_OK) return rc;
     const size_t n = (size_t)B * F * TP;
-    if (pooled_raw && hipMemcpyAsync(pooled_raw, pooled, n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    if (io.pooled_raw && hipMemcpyAsync(io.pooled_raw, pooled, n * 4, hipMemcpyDeviceToDevice, a.st) != hipSuccess)
         return LEAF_ERR_LAUNCH;
-    if (use_pcen) {
+    if (io.mode & 1) {
         // floor in place, then PCEN
-        hipLaunchKernelGGL(floor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pooled, n, 0, pooled);
+        hipLaunchKernelGGL(floor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, a.st, pooled, n, 0, pooled);
         LEAF_LAUNCH_CHECK();
-        return leaf_pcen_f32(pooled, B, F, TP, alpha, delta, root, ema_w, 1e-12f, outf32, stream);
+        return leaf_pcen_f32(pooled, B, F, TP, a.alpha, a.delta, a.root, a.ema_w, 1e-12f, outf32, a.st);
     }
-    hipLaunchKernelGGL(floor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pooled, n, mode, outf32);
+    hipLaunchKernelGGL(floor_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, a.st, pooled, n, io.mode, outf32);
     LEAF_LAUNCH_CHECK();
     return LEAF_OK;
+}
+
+// checks in the order the ABI documents, then one function per path
+static int forward_impl(const void* x, const LeafArgs& a, int flags, CallCtx ctx, void* out, void* workspace, size_t workspace_bytes,
+                        hipEvent_t* ev, float* pooled_raw = nullptr) {
+    const auto [B, T, F, K, hop] = a.s;
+    const bool out_bf16 = feat_bf16(flags);                                           // what the finalize sites store out as
+    const int xtype = x_sample_type(flags);                                           // what the kernels read x as: the two types are independent
+    const bool fused_only = xtype != kSampleF32 || out_bf16;                          // 16-bit input and bfloat16 features are fused-path features
+    // the selector, the flag combination and the build's layout check hold for the empty batch too (a bad selector or a
+    // mismatched build must not go unnoticed on an empty shard): only then (0, F, T') -- nothing to compute, nothing launched
+    if (!valid_selector(ctx.sel)) return LEAF_ERR_BAD_ALGO;
+    if ((flags & LEAF_FLAG_X_PCM16) && (flags & LEAF_FLAG_IO_BF16)) return LEAF_ERR_UNSUPPORTED;   // two types for x (int16 in, bfloat16 out: LEAF_FLAG_OUT_BF16)
+    if (fused_only && ctx.sel == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
+    if (B == 0 && !inst_layouts_ok()) return LEAF_ERR_LAUNCH;
+    if (empty_batch(B, T, F, K, hop)) return LEAF_OK;
+    if (!x || !a.kernel || !a.pool_w || !a.pool_b || !out) return LEAF_ERR_NULL_POINTER;
+    const bool use_pcen = (flags & LEAF_FLAG_PCEN) != 0;
+    if (use_pcen && (!a.alpha || !a.delta || !a.root || !a.ema_w)) return LEAF_ERR_NULL_POINTER;
+    const int rc = check_shape(B, T, F, K, hop);
+    if (rc != LEAF_OK) return rc;
+    {
+        const uintptr_t out_mask = out_bf16 ? 1u : 3u;                                               // bfloat16 features: 2-byte elements
+        const uintptr_t x_mask = (flags & (LEAF_FLAG_X_PCM16 | LEAF_FLAG_IO_BF16)) ? 1u : 3u;        // 16-bit PCM / bfloat16 waveform
+        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & out_mask) || misaligned16(workspace) ||
+            any_misaligned(a.kernel, a.pool_w, a.pool_b, a.alpha, a.delta, a.root, a.ema_w, pooled_raw))
+            return LEAF_ERR_ALIGNMENT;
+    }
+    const FusedPlan pl = make_plan(a.s, ctx.cus);
+    if (ctx.sel == LEAF_ALGO_MFMA && !pl.ok) return LEAF_ERR_BAD_ALGO;
+    ctx.sel = resolve_selector(ctx.sel, a.s, ctx.cus);
+    if (fused_only && ctx.sel == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;       // (what AUTO resolved to)
+    // a PCM sample means v / 32768, so no clip's peak exceeds 1: peak normalisation is the identity (no pre-pass, every scale 1)
+    if (xtype == kSamplePcm16) flags &= ~LEAF_FLAG_PEAKNORM;
+    const size_t need = forward_workspace_bytes(a.s, ctx.sel, ctx.cus);
+    if (!workspace || workspace_bytes < need) return LEAF_ERR_WORKSPACE;
+    float* ws = static_cast<float*>(workspace);
+    const bool overlap_save = ctx.sel == LEAF_ALGO_FFT || ctx.sel == LEAF_ALGO_FFT_WG || ctx.sel == LEAF_ALGO_FFT_SMALL;
+    // LEAF_FLAG_PEAKNORM: per-clip scales into the tail of the workspace (the last align_up(B, 64) floats the overlap-save
+    // plans reserve), applied to the pooled energies by the finalize step
+    float* clip_scale2 = nullptr;
+    if (flags & LEAF_FLAG_PEAKNORM) {
+        if (!overlap_save) return LEAF_ERR_UNSUPPORTED;
+        clip_scale2 = ws + need / 4 - align_up((size_t)B, 64);
+        hipLaunchKernelGGL(peak_scale2_kernel, dim3(B), dim3(1024), 0, a.st, x, xtype, T, clip_scale2);
+        LEAF_LAUNCH_CHECK();
+    }
+    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (out_bf16 ? 4 : 0);
+    const FwdIo io{x, xtype, mode, out, pooled_raw, clip_scale2, ev};
+    if (ctx.mix.lam && !overlap_save) return LEAF_ERR_BAD_ALGO;                       // (MFMA and staged kernels do not mix in their loads)
+    switch (ctx.sel) {
+        case LEAF_ALGO_FFT_SMALL: return forward_small(ctx, a, io, ws);
+        case LEAF_ALGO_FFT_WG: {
+            const Fft4kPlan f4 = make_fft4k_plan(a.s);
+            if (f4.ok) return forward_4k(ctx, f4, a, io, ws);
+        }
+            [[fallthrough]];                                   // the 2048-sample workgroup kernels
+        case LEAF_ALGO_FFT: {
+            const FftPlan fp = make_fft_plan(a.s, ctx.cus);
+            if (!fp.ok) return LEAF_ERR_BAD_ALGO;
+            // [spectra | pooling rows | col_of | band tables], then the partials
+            return fft_forward(ctx, fp, a, io, ws, ws + fft_table_floats(fp, F), /*tables_ready=*/false, ctx.sel == LEAF_ALGO_FFT_WG);
+        }
+        case LEAF_ALGO_MFMA: return forward_mfma(ctx, pl, a, io, ws);
+        default: return forward_staged(a, io, ws);
+    }
 }
 
 int leaf_forward_f32(const float* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
                      const float* alpha, const float* delta, const float* root, const float* ema_w, int F, int K, int hop,
                      int flags, int algo, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out, workspace,
-                        workspace_bytes, stream, nullptr);
+    return forward_impl(x, LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream}, flags,
+                        forward_ctx(algo), out, workspace, workspace_bytes, nullptr);
 }
 
 int leaf_forward_save_f32(const float* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
@@ -1384,8 +1495,8 @@ int leaf_forward_save_f32(const float* x, int B, int T, const float* kernel, con
     // forward-only: pooled_raw would be that of the normalised clips while leaf_backward_f32 differentiates against x
     // (16-bit PCM: normalisation is the identity, so the flag is accepted and changes nothing)
     if ((flags & LEAF_FLAG_PEAKNORM) && !(flags & LEAF_FLAG_X_PCM16)) return LEAF_ERR_UNSUPPORTED;
-    return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out, workspace,
-                        workspace_bytes, stream, nullptr, pooled_raw);
+    return forward_impl(x, LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream}, flags,
+                        forward_ctx(algo), out, workspace, workspace_bytes, nullptr, pooled_raw);
 }
 
 // ---- waveform mixup (leaf_common.hpp: mix_load): x'[b] = x[b] lam[b] + x[perm[b]] (1 - lam[b]), defined in fp32 with separately
@@ -1399,15 +1510,20 @@ static int launch_mixup(const void* x, int xtype, int B, int T, const int* perm,
     return LEAF_OK;
 }
 // does the forward kernel behind the RESOLVED selector mix in its loads?
-static bool mix_fused_forward(int B, int T, int F, int K, int hop, int sel) {
+static bool mix_fused_forward(const Shape& s, int sel, int cus) {
     if (sel == LEAF_ALGO_FFT_SMALL) return true;
-    if (sel == LEAF_ALGO_FFT) return pick_fft_kernel_mix(make_fft_plan(B, T, F, K, hop), K, hop, false) != nullptr;   // per-wave: static odd windows
+    if (sel == LEAF_ALGO_FFT) return pick_fft_kernel_mix(make_fft_plan(s, cus), s.K, s.hop, false) != nullptr;   // per-wave: static odd windows
     if (sel != LEAF_ALGO_FFT_WG) return false;                            // MFMA, staged: the mixed copy
-    if (make_fft4k_plan(B, T, F, K, hop).ok) return true;                 // 4096-sample blocks, static and run-time geometry
-    static const bool force_generic = [] { const char* e = tools_env("LEAF_WG_GENERIC"); return e && atoi(e) != 0; }();   // tools only
-    return pick_fft_wg_kernel(K, hop).fn != nullptr && !force_generic;    // 2048-sample blocks: the static instances
+    if (make_fft4k_plan(s).ok) return true;                               // 4096-sample blocks, static and run-time geometry
+    return pick_fft_wg_kernel(s.K, s.hop).fn != nullptr && !wg_force_generic();   // 2048-sample blocks: the static instances
 }
 static size_t mix_copy_offset_floats(size_t base_bytes) { return align_up((base_bytes + 3) / 4, 64); }
+// workspace of the mixed forward behind a RESOLVED selector: the family's own, and the mixed copy where the family needs one
+static size_t forward_mix_workspace_bytes(const Shape& s, int sel, int cus) {
+    const size_t base = forward_workspace_bytes(s, sel, cus);
+    if (!base || mix_fused_forward(s, sel, cus)) return base;
+    return (mix_copy_offset_floats(base) + align_up((size_t)s.B * s.T, 64)) * 4;
+}
 
 int leaf_mixup_f32(const void* x, int B, int T, const int* mix_perm, const float* mix_lam, int flags, float* out, void* stream) {
     if (flags & ~LEAF_FLAG_X_PCM16) return LEAF_ERR_UNSUPPORTED;          // fp32 or 16-bit PCM in, fp32 out
@@ -1420,60 +1536,50 @@ int leaf_mixup_f32(const void* x, int B, int T, const int* mix_perm, const float
 }
 
 size_t leaf_forward_mix_workspace_bytes(int B, int T, int F, int K, int hop, int algo) {
-    const size_t base = leaf_workspace_bytes(B, T, F, K, hop, algo);
-    if (!base) return 0;
-    const ReserveCus reserve(algo);
-    int sel = algo & 0xff;
-    if (sel == LEAF_ALGO_AUTO) sel = auto_algo(B, T, F, K, hop);
-    if (mix_fused_forward(B, T, F, K, hop, sel)) return base;
-    return (mix_copy_offset_floats(base) + align_up((size_t)B * T, 64)) * 4;
+    if (check_shape(B, T, F, K, hop) != LEAF_OK) return 0;
+    const CallCtx ctx = forward_ctx(algo);
+    const Shape s{B, T, F, K, hop};
+    const int sel = resolve_selector(ctx.sel, s, ctx.cus);
+    return sel < 0 ? 0 : forward_mix_workspace_bytes(s, sel, ctx.cus);
 }
 
-static int forward_mix_impl(const void* x, const int* mix_perm, const float* mix_lam, int B, int T, const float* kernel,
-                            const float* pool_w, const float* pool_b, const float* alpha, const float* delta, const float* root,
-                            const float* ema_w, int F, int K, int hop, int flags, int algo, void* out, float* pooled_raw,
-                            void* workspace, size_t workspace_bytes, void* stream) {
+static int forward_mix_impl(const void* x, MixArgs mix, const LeafArgs& a, int flags, int algo, void* out, float* pooled_raw,
+                            void* workspace, size_t workspace_bytes) {
+    const auto [B, T, F, K, hop] = a.s;
     // a bfloat16 waveform is not mixed (the definition is fp32; bfloat16 FEATURES, LEAF_FLAG_OUT_BF16, pass through); peak normalisation would have to follow the mix, which the fused loads cannot do
     if (flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_PEAKNORM)) return LEAF_ERR_UNSUPPORTED;
+    CallCtx ctx = forward_ctx(algo);
     if (empty_batch(B, T, F, K, hop))                        // selector and layout checks as without the mix; nothing is read
-        return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags & ~LEAF_FLAG_X_PCM16, algo, out, workspace,
-                            workspace_bytes, stream, nullptr, pooled_raw);
-    if (!x || !mix_perm || !mix_lam) return LEAF_ERR_NULL_POINTER;
+        return forward_impl(x, a, flags & ~LEAF_FLAG_X_PCM16, ctx, out, workspace, workspace_bytes, nullptr, pooled_raw);
+    if (!x || !mix.perm || !mix.lam) return LEAF_ERR_NULL_POINTER;
     const int rc = check_shape(B, T, F, K, hop);
     if (rc != LEAF_OK) return rc;
-    if (any_misaligned(mix_perm, mix_lam)) return LEAF_ERR_ALIGNMENT;
-    int sel = algo & 0xff;
-    if (sel != LEAF_ALGO_AUTO && sel != LEAF_ALGO_STAGED && sel != LEAF_ALGO_MFMA && sel != LEAF_ALGO_FFT && sel != LEAF_ALGO_FFT_WG &&
-        sel != LEAF_ALGO_FFT_SMALL)
-        return LEAF_ERR_BAD_ALGO;
-    const ReserveCus reserve(algo);                          // AUTO resolves as forward_impl will
-    if (sel == LEAF_ALGO_AUTO) sel = auto_algo(B, T, F, K, hop);
-    algo = (algo & ~0xff) | sel;
+    if (any_misaligned(mix.perm, mix.lam)) return LEAF_ERR_ALIGNMENT;
+    ctx.sel = resolve_selector(ctx.sel, a.s, ctx.cus);
+    if (ctx.sel < 0) return ctx.sel;
     // bfloat16 features have no staged forward (as in forward_impl): answered here, before the workspace check and the mixed copy
-    if ((flags & LEAF_FLAG_OUT_BF16) && sel == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
-    if (mix_fused_forward(B, T, F, K, hop, sel)) {
-        const MixScope mix(MixArgs{mix_perm, mix_lam});
-        return forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out, workspace,
-                            workspace_bytes, stream, nullptr, pooled_raw);
+    if ((flags & LEAF_FLAG_OUT_BF16) && ctx.sel == LEAF_ALGO_STAGED) return LEAF_ERR_UNSUPPORTED;
+    if (mix_fused_forward(a.s, ctx.sel, ctx.cus)) {
+        ctx.mix = mix;
+        return forward_impl(x, a, flags, ctx, out, workspace, workspace_bytes, nullptr, pooled_raw);
     }
     // the mixed fp32 copy behind the family's own workspace, then the unmixed call on it
-    const size_t base = leaf_workspace_bytes(B, T, F, K, hop, algo);
+    const size_t base = forward_workspace_bytes(a.s, ctx.sel, ctx.cus);
     if (!base) return LEAF_ERR_BAD_ALGO;
     if (reinterpret_cast<uintptr_t>(x) & ((flags & LEAF_FLAG_X_PCM16) ? 1u : 3u) || misaligned16(workspace)) return LEAF_ERR_ALIGNMENT;
-    if (!workspace || workspace_bytes < leaf_forward_mix_workspace_bytes(B, T, F, K, hop, algo)) return LEAF_ERR_WORKSPACE;
+    if (!workspace || workspace_bytes < forward_mix_workspace_bytes(a.s, ctx.sel, ctx.cus)) return LEAF_ERR_WORKSPACE;
     float* mixed = static_cast<float*>(workspace) + mix_copy_offset_floats(base);
-    const int mrc = launch_mixup(x, x_sample_type(flags), B, T, mix_perm, mix_lam, mixed, (hipStream_t)stream);
+    const int mrc = launch_mixup(x, x_sample_type(flags), B, T, mix.perm, mix.lam, mixed, a.st);
     if (mrc != LEAF_OK) return mrc;
-    return forward_impl(mixed, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags & ~LEAF_FLAG_X_PCM16, algo, out,
-                        workspace, base, stream, nullptr, pooled_raw);
+    return forward_impl(mixed, a, flags & ~LEAF_FLAG_X_PCM16, ctx, out, workspace, base, nullptr, pooled_raw);
 }
 
 int leaf_forward_mix_f32(const void* x, const int* mix_perm, const float* mix_lam, int B, int T, const float* kernel,
                          const float* pool_w, const float* pool_b, const float* alpha, const float* delta, const float* root,
                          const float* ema_w, int F, int K, int hop, int flags, int algo, float* out, void* workspace,
                          size_t workspace_bytes, void* stream) {
-    return forward_mix_impl(x, mix_perm, mix_lam, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out,
-                            nullptr, workspace, workspace_bytes, stream);
+    return forward_mix_impl(x, MixArgs{mix_perm, mix_lam}, LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream},
+                            flags, algo, out, nullptr, workspace, workspace_bytes);
 }
 
 int leaf_forward_save_mix_f32(const void* x, const int* mix_perm, const float* mix_lam, int B, int T, const float* kernel,
@@ -1481,8 +1587,8 @@ int leaf_forward_save_mix_f32(const void* x, const int* mix_perm, const float* m
                               const float* ema_w, int F, int K, int hop, int flags, int algo, float* out, float* pooled_raw,
                               void* workspace, size_t workspace_bytes, void* stream) {
     if (!pooled_raw) return LEAF_ERR_NULL_POINTER;
-    return forward_mix_impl(x, mix_perm, mix_lam, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out,
-                            pooled_raw, workspace, workspace_bytes, stream);
+    return forward_mix_impl(x, MixArgs{mix_perm, mix_lam}, LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream},
+                            flags, algo, out, pooled_raw, workspace, workspace_bytes);
 }
 
 int leaf_forward_profiled_f32(const float* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
@@ -1494,18 +1600,11 @@ int leaf_forward_profiled_f32(const float* x, int B, int T, const float* kernel,
     hipEvent_t ev[4];
     for (int i = 0; i < 4; ++i)
         if (hipEventCreate(&ev[i]) != hipSuccess) return LEAF_ERR_LAUNCH;
-    {
-        const ReserveCus reserve(algo);                      // AUTO resolves as the forward call will
-        int sel = algo & 0xff;
-        if (sel == LEAF_ALGO_AUTO) sel = auto_algo(B, T, F, K, hop);
-        if (sel != LEAF_ALGO_MFMA && sel != LEAF_ALGO_FFT && sel != LEAF_ALGO_FFT_WG && sel != LEAF_ALGO_FFT_SMALL) {
-            for (int i = 0; i < 4; ++i) (void)hipEventDestroy(ev[i]);
-            return LEAF_ERR_BAD_ALGO;
-        }
-        algo = (algo & ~0xff) | sel;
-    }
-    int rc = forward_impl(x, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, algo, out, workspace,
-                          workspace_bytes, stream, ev);
+    const LeafArgs a{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream};
+    CallCtx ctx = forward_ctx(algo);
+    ctx.sel = resolve_selector(ctx.sel, a.s, ctx.cus);       // the fused paths only: the staged forward has no stages to time
+    int rc = ctx.sel < 0 || ctx.sel == LEAF_ALGO_STAGED ? LEAF_ERR_BAD_ALGO
+                                                        : forward_impl(x, a, flags, ctx, out, workspace, workspace_bytes, ev);
     if (rc == LEAF_OK) {
         if (hipEventSynchronize(ev[3]) != hipSuccess) rc = LEAF_ERR_LAUNCH;
         for (int i = 0; i < 3 && rc == LEAF_OK; ++i)
@@ -1519,7 +1618,7 @@ int leaf_forward_profiled_f32(const float* x, int B, int T, const float* kernel,
 // ---- inference with frozen parameters: parameter-derived tables prepared once, reused by every forward
 size_t leaf_fft_tables_bytes(int F, int K, int hop) {
     if (F < 1 || K < 1 || hop < 1) return 0;
-    const FftPlan fp = make_fft_plan(1, std::max(K, 2 * kFftN), F, K, hop);      // table sizes depend on (F, K) only
+    const FftPlan fp = make_fft_plan(Shape{1, std::max(K, 2 * kFftN), F, K, hop}, device_cus());      // table sizes depend on (F, K) only
     return fp.ok ? fft_table_floats(fp, F, false) * 4 : 0;
 }
 
@@ -1530,22 +1629,20 @@ int leaf_fft_prepare_tables_f32(const float* kernel, const float* pool_w, int F,
     if (need == 0) return LEAF_ERR_BAD_ALGO;
     if (misaligned16(tables) || any_misaligned(kernel, pool_w)) return LEAF_ERR_ALIGNMENT;
     if (tables_bytes < need) return LEAF_ERR_WORKSPACE;
-    const FftPlan fp = make_fft_plan(1, std::max(K, 2 * kFftN), F, K, hop);
+    const FftPlan fp = make_fft_plan(Shape{1, std::max(K, 2 * kFftN), F, K, hop}, device_cus());
     float* t = static_cast<float*>(tables);
-    float* Gz = t + align_up(fp.h_floats, 64);
-    int* col_of = reinterpret_cast<int*>(Gz + align_up(fp.gz_floats, 64));
+    const FftTabPtrs tp = fft_tab_ptrs(fp, t, F);
     const BandLayout bl = band_layout(F, K, hop);
     if (bl.stat) {
         // + the parameter-only tables of the band-limited filter tasks (per-filter records, decimated pooling windows)
-        float* bt = reinterpret_cast<float*>(col_of) + align_up((size_t)F, 64);
         BandTabArgs ba{};
         ba.hop = hop; ba.padL = fp.padL; ba.L = fp.L; ba.eps2 = kBandEps2; ba.eta = kBandEtaFree; ba.cross = 1;   // (the forward's default rule)
-        ba.rec = reinterpret_cast<int*>(bt + bl.rec); ba.gz = bt + bl.gz;
+        ba.rec = reinterpret_cast<int*>(tp.band + bl.rec); ba.gz = tp.band + bl.gz;
         hipLaunchKernelGGL(fft_prep_band_kernel, dim3(F, 2), dim3(kPrepWaves * 64), 0, (hipStream_t)stream, kernel, pool_w, F, K, fp.GZ,
-                           gabor_bounds(K), reinterpret_cast<float2*>(t), Gz, col_of, ba);
+                           gabor_bounds(K), tp.H, tp.Gz, tp.col_of, ba);
     } else {
         hipLaunchKernelGGL(fft_prep_kernel, dim3(F, 1), dim3(kPrepWaves * 64), 0, (hipStream_t)stream, kernel, pool_w, F, K, fp.GZ,
-                           gabor_bounds(K), 1, reinterpret_cast<float2*>(t), Gz, col_of, fft_lone_taps(t, F, K));
+                           gabor_bounds(K), 1, tp.H, tp.Gz, tp.col_of, fft_lone_taps(t, F, K));
     }
     LEAF_LAUNCH_CHECK();
     return LEAF_OK;
@@ -1557,7 +1654,7 @@ int leaf_band_classes_f32(const float* kernel, const float* pool_w, const float*
     if (F < 1 || K < 1 || hop < 1) return LEAF_ERR_BAD_SHAPE;
     {
         // the 4096-sample plan (K = 801 / hop = 320): one class, decided by fft4k_prep_kernel; classes[f] = 512 or 4096
-        const Fft4kPlan f4 = make_fft4k_plan(1, 2 * kFft4N, F, K, hop);
+        const Fft4kPlan f4 = make_fft4k_plan(Shape{1, 2 * kFft4N, F, K, hop});
         if (f4.ok && !f4.generic && f4.band_floats) {
             if (misaligned16(workspace) || any_misaligned(kernel, pool_w, pool_b, classes)) return LEAF_ERR_ALIGNMENT;
             if (!workspace || workspace_bytes < fft4k_workspace_floats(f4, 1) * 4) return LEAF_ERR_WORKSPACE;
@@ -1580,17 +1677,15 @@ int leaf_band_classes_f32(const float* kernel, const float* pool_w, const float*
     const size_t need = leaf_fft_tables_bytes(F, K, hop);
     if (misaligned16(workspace) || any_misaligned(kernel, pool_w, pool_b, classes)) return LEAF_ERR_ALIGNMENT;
     if (!workspace || need == 0 || workspace_bytes < need) return LEAF_ERR_WORKSPACE;
-    const FftPlan fp = make_fft_plan(1, std::max(K, 2 * kFftN), F, K, hop);
+    const FftPlan fp = make_fft_plan(Shape{1, std::max(K, 2 * kFftN), F, K, hop}, device_cus());
     float* t = static_cast<float*>(workspace);
-    float* Gz = t + align_up(fp.h_floats, 64);
-    int* col_of = reinterpret_cast<int*>(Gz + align_up(fp.gz_floats, 64));
-    float* bt = reinterpret_cast<float*>(col_of) + align_up((size_t)F, 64);
+    const FftTabPtrs tp = fft_tab_ptrs(fp, t, F);
     BandTabArgs ba{};
     ba.hop = hop; ba.padL = fp.padL; ba.L = fp.L; ba.eps2 = kBandEps2; ba.eta = pool_b ? kBandEtaFree : kBandEta; ba.cross = pool_b ? 1 : 0;   // (pool_b = NULL: round 5's decision)
-    ba.rec = reinterpret_cast<int*>(bt + bl.rec); ba.gz = bt + bl.gz; ba.classes = classes;
+    ba.rec = reinterpret_cast<int*>(tp.band + bl.rec); ba.gz = tp.band + bl.gz; ba.classes = classes;
     ba.cls_bias = pool_b;
     hipLaunchKernelGGL(fft_prep_band_kernel, dim3(F, 2), dim3(kPrepWaves * 64), 0, (hipStream_t)stream, kernel, pool_w, F, K, fp.GZ,
-                       gabor_bounds(K), reinterpret_cast<float2*>(t), Gz, col_of, ba);
+                       gabor_bounds(K), tp.H, tp.Gz, tp.col_of, ba);
     LEAF_LAUNCH_CHECK();
     return LEAF_OK;
 }
@@ -1607,7 +1702,9 @@ int leaf_forward_prepared_f32(const float* x, int B, int T, const void* tables, 
     if (use_pcen && (!alpha || !delta || !root || !ema_w)) return LEAF_ERR_NULL_POINTER;
     int rc = check_shape(B, T, F, K, hop);
     if (rc != LEAF_OK) return rc;
-    const FftPlan fp = make_fft_plan(B, T, F, K, hop);
+    const CallCtx ctx = forward_ctx(LEAF_ALGO_AUTO);          // this entry takes no option word: the defaults, every CU
+    const LeafArgs a{{B, T, F, K, hop}, nullptr, nullptr, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream};
+    const FftPlan fp = make_fft_plan(a.s, ctx.cus);
     if (!fp.ok) return LEAF_ERR_BAD_ALGO;
     if (tables_bytes < leaf_fft_tables_bytes(F, K, hop)) return LEAF_ERR_WORKSPACE;
     const bool out_bf16 = feat_bf16(flags);
@@ -1622,11 +1719,10 @@ int leaf_forward_prepared_f32(const float* x, int B, int T, const void* tables, 
     // workspace has the room (it has when sized by leaf_workspace_bytes as documented); otherwise full transforms
     const size_t part_end = align_up(fp.part_floats, 64) + (LEAF_TRACE ? 16 * 64 * 2 : 0);
     float* band_scratch = fp.band_dyn && workspace_bytes >= (part_end + fp.band_dyn) * 4 ? static_cast<float*>(workspace) + part_end : nullptr;
-    return fft_forward(fp, x, x_sample_type(flags), B, T, nullptr, nullptr, pool_b, alpha, delta, root, ema_w, F, K, hop, mode, out,
+    return fft_forward(ctx, fp, a, FwdIo{x, x_sample_type(flags), mode, out, nullptr, nullptr, nullptr},
                        static_cast<float*>(const_cast<void*>(tables)), static_cast<float*>(workspace), /*tables_ready=*/true,
-                       (hipStream_t)stream, nullptr, nullptr,
-                       auto_algo(B, T, F, K, hop, /*allow_small=*/false) == LEAF_ALGO_FFT_WG,   // the workgroup kernel from the batch AUTO takes it at
-                       nullptr, band_scratch);
+                       auto_algo(a.s, ctx.cus, /*allow_small=*/false) == LEAF_ALGO_FFT_WG,   // the workgroup kernel from the batch AUTO takes it at
+                       band_scratch);
 }
 
 // ---- overlap-save backward: which geometries it covers, and its workspace layout (float offsets)
@@ -1669,19 +1765,18 @@ static bool wg_block_dx_enabled() {
 #define LEAF_WG4K_BWD_BAND_SIXTEENTHS 8        // the same for the static 801 / 320 parameter-gradient backward on 4096-sample blocks (below: the 2048-sample kernels)
 #endif
 // the lowered thresholds hold only where band tasks CAN run in this call -- not with LEAF_FLAG_BWD_FULL_TRANSFORMS, more
-// than kBandMaxFilters filters or clips whose edge frames band_edges() cannot table; leaf_backward_f32 says so here before it picks
+// than kBandMaxFilters filters or clips whose edge frames band_edges() cannot table; backward_fft says so (`band_possible`) when it picks
 // its kernels (the workspace layout does not depend on the pick), and such calls keep the 20/16 crossing measured without band tasks.
-thread_local bool tl_bwd_band_possible = true;
-inline int wg_bwd_sixteenths(int K, int hop, bool dx) {
-    if (!band_geometry_ok(K, hop) || !LEAF_BAND_BWD || !tl_bwd_band_possible) return 20;
+inline int wg_bwd_sixteenths(int K, int hop, bool dx, bool band_possible) {
+    if (!band_geometry_ok(K, hop) || !LEAF_BAND_BWD || !band_possible) return 20;
     return dx ? (LEAF_BAND_BWD_DX ? LEAF_WG_BWD_DX_BAND_SIXTEENTHS : 20) : LEAF_WG_BWD_BAND_SIXTEENTHS;
 }
-FftWgBwdLaunch pick_fft_wg_bwd_kernel(int K, int hop, bool dx, long long blocks = 0, bool io_bf16 = false) {
+FftWgBwdLaunch pick_fft_wg_bwd_kernel(int K, int hop, bool dx, int cus, bool band_possible, long long blocks = 0, bool io_bf16 = false) {
     if (LEAF_FFT_FORCE_GENERIC) return {nullptr, 0, 0};
     if (dx) {
         if (!(fft_static_geometry(K, hop) && (K & 1))) return {nullptr, 0, 0};
         // (not K = 801: there the block-per-wave kernel measures 5 % faster, 1.89 vs 1.99 ms at 256 x 1 s)
-        if (wg_block_dx_enabled() && K != 801 && blocks >= fft_wg_bwd_min_blocks(wg_bwd_sixteenths(K, hop, true)) &&
+        if (wg_block_dx_enabled() && K != 801 && blocks >= fft_wg_bwd_min_blocks(cus, wg_bwd_sixteenths(K, hop, true, band_possible)) &&
             fft_wg_bwd_dx_lds_bytes(12, K) <= (size_t)kMaxLds)
             return {as_fft_kernel(leaf_inst_fft_wg_bwd_dx(K)), 12, fft_wg_bwd_dx_lds_bytes(12, K), true};
         // below that: one wave per block, G in registers (leaf_fft_blk_bwd_dx_kernel)
@@ -1711,17 +1806,17 @@ FftWgBwdLaunch pick_fft_wgg_bwd_kernel(const FftPlan& fp, int K, int hop) {
 }
 static_assert(fft_wg_bwd_lds_bytes(12, 801) <= (size_t)kMaxLds && fft_blk_bwd_lds_bytes(801) <= (size_t)kMaxLds, "LDS budget");
 // used for dL/dx always (nothing else fused yields it), and for the parameter gradients once every CU gets a block
-bool fft_wg_bwd_use(const FftPlan& fp, int B, int K, int hop, bool need_dx) {
-    return fp.ok && pick_fft_wg_bwd_kernel(K, hop, need_dx).fn != nullptr && (need_dx || (long long)B * fp.nblk >= fft_wg_bwd_min_blocks(wg_bwd_sixteenths(K, hop, false)));
+bool fft_wg_bwd_use(const FftPlan& fp, int B, int K, int hop, bool need_dx, int cus, bool band_possible) {
+    return fp.ok && pick_fft_wg_bwd_kernel(K, hop, need_dx, cus, band_possible).fn != nullptr &&
+           (need_dx || (long long)B * fp.nblk >= fft_wg_bwd_min_blocks(cus, wg_bwd_sixteenths(K, hop, false, band_possible)));
 }
 // dL/dx for the other windows of the 2048-sample plan, odd or even, at every batch: the workgroup-per-block kernel with the
 // block's G shared in LDS (leaf_fft_wgg_bwd_kernel<.., DX = true>), twelve-wave structure and dynamic filter queue.  (A
 // block-per-wave run-time-geometry kernel served fewer than 10/16 block per CU until round 4; measured equal or slower there
 // -- profiles/r04/dx_small_batches.txt -- and it carried 264..408 B of scratch per lane, so it is gone.)
-FftWgBwdLaunch pick_fft_wgg_bwd_dx_kernel(const FftPlan& fp, int B, int K, int hop) {
+FftWgBwdLaunch pick_fft_wgg_bwd_dx_kernel(const FftPlan& fp, int K, int hop, int cus) {
     static const bool off = [] { const char* e = tools_env("LEAF_WGG_BWD_DX"); return e && atoi(e) == 0; }();   // tools only: A/B
-    if (off || !fp.ok || K < 64 || K > 64 * 19 || pick_fft_wg_bwd_kernel(K, hop, true).fn) return {nullptr, 0, 0};
-    (void)B;
+    if (off || !fp.ok || K < 64 || K > 64 * 19 || pick_fft_wg_bwd_kernel(K, hop, true, cus, /*band_possible=*/true).fn) return {nullptr, 0, 0};   // (only whether a static instance exists)
     int nw = 12;
     while (nw > 6 && fft_wgg_bwd_dx_lds_bytes(nw, K) > (size_t)kMaxLds) --nw;
     const size_t lds = fft_wgg_bwd_dx_lds_bytes(nw, K);
@@ -1729,10 +1824,10 @@ FftWgBwdLaunch pick_fft_wgg_bwd_dx_kernel(const FftPlan& fp, int B, int K, int h
     return {as_fft_kernel(leaf_inst_fft_wgg_bwd_dx(fft_wgg_taps_per_lane(K))), nw, lds};
 }
 // the run-time-geometry kernel: parameter gradients, once every CU gets a block
-bool fft_wgg_bwd_use(const FftPlan& fp, int B, int K, int hop, bool need_dx) {
+bool fft_wgg_bwd_use(const FftPlan& fp, int B, int K, int hop, bool need_dx, int cus) {
     static const bool off = [] { const char* e = tools_env("LEAF_WGG_BWD"); return e && atoi(e) == 0; }();   // tools only: A/B
-    return !off && !need_dx && fp.ok && !pick_fft_wg_bwd_kernel(K, hop, false).fn && pick_fft_wgg_bwd_kernel(fp, K, hop).fn &&
-           (long long)B * fp.nblk >= fft_wg_bwd_min_blocks(10);
+    return !off && !need_dx && fp.ok && !pick_fft_wg_bwd_kernel(K, hop, false, cus, /*band_possible=*/true).fn && pick_fft_wgg_bwd_kernel(fp, K, hop).fn &&
+           (long long)B * fp.nblk >= fft_wg_bwd_min_blocks(cus, 10);
 }
 
 #ifndef LEAF_BWD_ROWSUMS
@@ -1779,7 +1874,8 @@ struct Fft4kBwdPlan {
     size_t lds;
 };
 FftKernel pick_fft_wgg4k_bwd_kernel(int K) { return as_fft_kernel(leaf_inst_fft_wgg4k_bwd(fft_wgg4k_taps_per_lane(K))); }
-Fft4kBwdPlan make_fft4k_bwd_plan(int B, int T, int F, int K, int hop, bool need_dx) {
+Fft4kBwdPlan make_fft4k_bwd_plan(const Shape& s, bool need_dx, int cus) {
+    const auto [B, T, F, K, hop] = s;
     Fft4kBwdPlan bp{};
     static const bool off = [] { const char* e = tools_env("LEAF_4K_BWD"); return e && atoi(e) == 0; }();   // tools only: A/B
     static const int min_k = [] { const char* e = tools_env("LEAF_4K_BWD_MIN_K"); return e ? atoi(e) : 833; }();   // tools only
@@ -1798,7 +1894,7 @@ Fft4kBwdPlan make_fft4k_bwd_plan(int B, int T, int F, int K, int hop, bool need_
     bp.L = stat ? 3200 : (kFft4N - K + 1) & ~1;                         // static: a multiple of the hop (the forward's plan)
     if ((bp.L + K - 2) / hop + 2 > 64) return bp;                        // g_pre of a block's frames: one per lane
     bp.nblk = ceil_div(T, bp.L);
-    if ((long long)B * bp.nblk >= (1ll << 30) || (long long)B * bp.nblk < fft_wg_bwd_min_blocks(stat && !need_dx ? LEAF_WG4K_BWD_BAND_SIXTEENTHS : 8)) return bp;
+    if ((long long)B * bp.nblk >= (1ll << 30) || (long long)B * bp.nblk < fft_wg_bwd_min_blocks(cus, stat && !need_dx ? LEAF_WG4K_BWD_BAND_SIXTEENTHS : 8)) return bp;
     if (stat) {
         bp.RG = kWg4RowFloats;
         bp.nw = need_dx ? kWg4BwdDxWaves : LEAF_4K_BWD_NW;                           // half scratch + the two parity pooling rows per wave
@@ -1848,27 +1944,29 @@ Fft4kBwdLayout fft4k_bwd_layout(const Fft4kBwdPlan& bp, int B, int F) {
 
 // Which backward implementation serves a call (the same decision sizes the workspace and dispatches the kernels).
 enum BwdPath { BWD_PATH_FFT = 0, BWD_PATH_MFMA = 1, BWD_PATH_STAGED = 2, BWD_PATH_FFT4K = 3 };
-static BwdPath bwd_path(int B, int T, int F, int K, int hop, int flags, bool need_dx) {
+static BwdPath bwd_path(const Shape& s, int flags, bool need_dx, int cus) {
     if (!(flags & (LEAF_FLAG_BWD_STAGED | LEAF_FLAG_BWD_MFMA))) {
-        if (make_fft4k_bwd_plan(B, T, F, K, hop, need_dx).ok) return BWD_PATH_FFT4K;
-        const FftPlan fp = make_fft_plan(B, T, F, K, hop);
-        if (fft_backward_ok(fp, K, hop) &&
-            (!need_dx || fft_wg_bwd_use(fp, B, K, hop, true) || pick_fft_wgg_bwd_dx_kernel(fp, B, K, hop).fn))
+        if (make_fft4k_bwd_plan(s, need_dx, cus).ok) return BWD_PATH_FFT4K;
+        const FftPlan fp = make_fft_plan(s, cus);
+        if (fft_backward_ok(fp, s.K, s.hop) &&
+            (!need_dx || fft_wg_bwd_use(fp, s.B, s.K, s.hop, true, cus, /*band_possible=*/true) ||   // (sizing: with dL/dx the answer does not depend on it)
+             pick_fft_wgg_bwd_dx_kernel(fp, s.K, s.hop, cus).fn))
             return BWD_PATH_FFT;
     }
     if (!need_dx && !(flags & LEAF_FLAG_BWD_STAGED)) {
-        const FusedPlan pl = make_plan(B, T, F, K, hop);
-        if (make_bwd_plan(pl, T).ok) return BWD_PATH_MFMA;
+        const FusedPlan pl = make_plan(s, cus);
+        if (make_bwd_plan(pl, s.T).ok) return BWD_PATH_MFMA;
     }
     return BWD_PATH_STAGED;
 }
-static size_t bwd_own_workspace_floats(BwdPath path, int B, int T, int F, int K, int hop, bool need_dx) {
+static size_t bwd_own_workspace_floats(BwdPath path, const Shape& s, bool need_dx, int cus) {
+    const auto [B, T, F, K, hop] = s;
     switch (path) {
-        case BWD_PATH_FFT: return fft_bwd_layout(make_fft_plan(B, T, F, K, hop), B, F, need_dx).total;
-        case BWD_PATH_FFT4K: return fft4k_bwd_layout(make_fft4k_bwd_plan(B, T, F, K, hop, need_dx), B, F).total;
+        case BWD_PATH_FFT: return fft_bwd_layout(make_fft_plan(s, cus), B, F, need_dx).total;
+        case BWD_PATH_FFT4K: return fft4k_bwd_layout(make_fft4k_bwd_plan(s, need_dx, cus), B, F).total;
         case BWD_PATH_MFMA: {
-            const FusedPlan pl = make_plan(B, T, F, K, hop);
-            return bwd_layout(pl, make_bwd_plan(pl, T), B, T, F, num_cus()).total;
+            const FusedPlan pl = make_plan(s, cus);
+            return bwd_layout(pl, make_bwd_plan(pl, T), B, T, F, cus).total;
         }
         default: break;
     }
@@ -1882,398 +1980,318 @@ static size_t bwd_own_workspace_floats(BwdPath path, int B, int T, int F, int K,
 // LEAF_FLAG_IO_BF16 / LEAF_FLAG_X_PCM16 (a 16-bit waveform): the static-geometry overlap-save backwards (K = 401 / 160, 801 / 320, 201 / 80) and the 4096-sample plans read
 // the 16-bit waveform directly (nothing added); the run-time-geometry kernels of the 2048-sample plan, the MFMA and the staged backward
 // read fp32 only and get a widened copy of x behind their own layout
-static size_t bwd_x32_floats(BwdPath path, int B, int T, int K, int hop, int flags) {
+static size_t bwd_x32_floats(BwdPath path, const Shape& s, int flags) {
     if (!(flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16)) || path == BWD_PATH_FFT4K) return 0;
-    if (path == BWD_PATH_FFT && fft_static_geometry(K, hop) && (K & 1) && !LEAF_FFT_FORCE_GENERIC) return 0;
-    return align_up((size_t)B * T, 64);
+    if (path == BWD_PATH_FFT && fft_static_geometry(s.K, s.hop) && (s.K & 1) && !LEAF_FFT_FORCE_GENERIC) return 0;
+    return align_up((size_t)s.B * s.T, 64);
 }
 
 size_t leaf_backward_workspace_bytes(int B, int T, int F, int K, int hop, int flags, int need_dx) {
     if (check_shape(B, T, F, K, hop) != LEAF_OK) return 0;
-    const BwdPath path = bwd_path(B, T, F, K, hop, flags, need_dx != 0);
-    return (bwd_own_workspace_floats(path, B, T, F, K, hop, need_dx != 0) + bwd_x32_floats(path, B, T, K, hop, flags)) * 4;
+    const Shape s{B, T, F, K, hop};
+    const int cus = backward_ctx(flags, MixArgs{nullptr, nullptr}).cus;
+    const BwdPath path = bwd_path(s, flags, need_dx != 0, cus);
+    return (bwd_own_workspace_floats(path, s, need_dx != 0, cus) + bwd_x32_floats(path, s, flags)) * 4;
 }
 
 // Waveform mixup (leaf_backward_mix_f32).  The 4096-sample backwards and the static odd-window kernels of the 2048-sample plan
 // (workgroup-per-block and per-wave, K = 401 / 201 / 801) have MIX instances that mix in their block loads; the run-time-geometry
 // 2048-sample kernels (they re-read samples in their time-domain terms), MFMA and staged read a mixed fp32 copy behind the path's own
 // layout -- where the widened copy of a 16-bit waveform goes, which a mixed call never needs (mixup_kernel widens).
-static bool fft_bwd_mixes_in_loads(const FftPlan& fp, int K, int hop) { return pick_fft_kernel_mix(fp, K, hop, true) != nullptr; }
-static size_t bwd_mix_floats(BwdPath path, int B, int T, int F, int K, int hop) {
-    if (path == BWD_PATH_FFT4K || (path == BWD_PATH_FFT && fft_bwd_mixes_in_loads(make_fft_plan(B, T, F, K, hop), K, hop))) return 0;
-    return align_up((size_t)B * T, 64);
+static size_t bwd_mix_floats(BwdPath path, const Shape& s, int cus) {
+    if (path == BWD_PATH_FFT4K || (path == BWD_PATH_FFT && pick_fft_kernel_mix(make_fft_plan(s, cus), s.K, s.hop, true) != nullptr)) return 0;
+    return align_up((size_t)s.B * s.T, 64);
 }
 
 size_t leaf_backward_mix_workspace_bytes(int B, int T, int F, int K, int hop, int flags) {
     if (check_shape(B, T, F, K, hop) != LEAF_OK) return 0;
-    const BwdPath path = bwd_path(B, T, F, K, hop, flags, false);
-    return (bwd_own_workspace_floats(path, B, T, F, K, hop, false) + bwd_mix_floats(path, B, T, F, K, hop)) * 4;
+    const Shape s{B, T, F, K, hop};
+    const int cus = backward_ctx(flags, MixArgs{nullptr, nullptr}).cus;
+    const BwdPath path = bwd_path(s, flags, false, cus);
+    return (bwd_own_workspace_floats(path, s, false, cus) + bwd_mix_floats(path, s, cus)) * 4;
 }
 
-static int backward_impl(const float* x, const int* mix_perm, const float* mix_lam, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
-                      const float* alpha, const float* delta, const float* root, const float* ema_w, int F, int K, int hop,
-                      int flags, const float* grad_out, const float* pooled_raw, float* g_kernel, float* g_pool_w,
-                      float* g_pool_b, float* g_alpha, float* g_delta, float* g_root, float* g_ema_w, float* g_x,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-    // LEAF_FLAG_IO_BF16: x, grad_out and g_x are bfloat16 buffers behind the float pointers (as in the forward); everything else fp32
-    // LEAF_FLAG_X_PCM16: x alone is a 16-bit PCM buffer (v / 32768); an integer input has no gradient, so g_x must be NULL
-    // LEAF_FLAG_OUT_BF16: grad_out alone is bfloat16 (the feature side); x and g_x follow the two flags above
-    if ((flags & LEAF_FLAG_X_PCM16) && ((flags & LEAF_FLAG_IO_BF16) || g_x)) return LEAF_ERR_UNSUPPORTED;
-    // mix_lam != NULL: the mixed call (leaf_backward_mix_f32 has refused bfloat16, PEAKNORM, g_x and a missing buffer)
-    const bool mixed_call = mix_lam != nullptr;
-    if (empty_batch(B, T, F, K, hop)) {
-        // the sum over zero clips: every parameter gradient is exactly zero (what autograd returns for the reference)
-        if (!g_kernel || !g_pool_w || !g_pool_b) return LEAF_ERR_NULL_POINTER;
-        const bool pc = (flags & LEAF_FLAG_PCEN) != 0;
-        if (pc && (!g_alpha || !g_delta || !g_root || !g_ema_w)) return LEAF_ERR_NULL_POINTER;
-        hipStream_t s0 = (hipStream_t)stream;
-        bool ok = hipMemsetAsync(g_kernel, 0, (size_t)2 * F * 4, s0) == hipSuccess;
-        ok = ok && hipMemsetAsync(g_pool_w, 0, (size_t)F * 4, s0) == hipSuccess;
-        ok = ok && hipMemsetAsync(g_pool_b, 0, (size_t)F * 4, s0) == hipSuccess;
-        if (pc)
-            for (float* g : {g_alpha, g_delta, g_root, g_ema_w}) ok = ok && hipMemsetAsync(g, 0, (size_t)F * 4, s0) == hipSuccess;
-        return ok ? LEAF_OK : LEAF_ERR_LAUNCH;
-    }
-    if (!x || !kernel || !pool_w || !pool_b || !grad_out || !g_kernel || !g_pool_w || !g_pool_b) return LEAF_ERR_NULL_POINTER;
-    const bool use_pcen = (flags & LEAF_FLAG_PCEN) != 0;
-    if (use_pcen && (!alpha || !delta || !root || !ema_w || !g_alpha || !g_delta || !g_root || !g_ema_w))
-        return LEAF_ERR_NULL_POINTER;
-    int rc = check_shape(B, T, F, K, hop);
-    if (rc != LEAF_OK) return rc;
-    if (2 * F > 65535 || B > 65535) return LEAF_ERR_BAD_SHAPE;
-    const bool io_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;   // the waveform side: x and g_x
-    const bool go_bf16 = feat_bf16(flags);                   // the feature side: grad_out
-    {
-        const uintptr_t io_mask = io_bf16 ? 1u : 3u;
-        const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;
-        if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(grad_out) & (go_bf16 ? 1u : 3u)) ||
-            (reinterpret_cast<uintptr_t>(g_x) & io_mask) || misaligned16(workspace) ||
-            any_misaligned(kernel, pool_w, pool_b, alpha, delta, root, ema_w, pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta,
-                           g_root, g_ema_w) || any_misaligned(mix_perm, mix_lam))
-            return LEAF_ERR_ALIGNMENT;
-    }
-    const BwdPath path = bwd_path(B, T, F, K, hop, flags, g_x != nullptr);
-    if (!workspace || workspace_bytes < (mixed_call ? leaf_backward_mix_workspace_bytes(B, T, F, K, hop, flags)
-                                                    : leaf_backward_workspace_bytes(B, T, F, K, hop, flags, g_x != nullptr)))
-        return LEAF_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int TP = (T - 1) / hop + 1;
-    const int padL = K / 2 + K % 2 - 1;
+// what a backward path reads and writes besides the parameters
+struct BwdIo {
+    const float* x;                  // the waveform the kernels read: the caller's, or the mixed / widened fp32 copy
+    int xtype;                       // its sample type (leaf_common.hpp kSample*)
+    const float* grad_out;
+    const float* pooled_raw;         // saved by leaf_forward_save_f32, else NULL: recomputed
+    float *g_kernel, *g_pool_w, *g_pool_b, *g_alpha, *g_delta, *g_root, *g_ema_w, *g_x;
     // first-stage mode (pcen_bwd_scan_kernel): bit0 PCEN, bit1 log1p compression (PCEN off only, as in the forward), bit2 bf16 grad_out;
     // param_reduce_kernel reads bit0 alone
     // (grad_out is read by that kernel alone, on every path: a bfloat16 grad_out needs no widened copy anywhere)
-    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (go_bf16 ? 4 : 0);
-    float* ws = static_cast<float*>(workspace);
-    int xtype = x_sample_type(flags);                        // what the kernels below read x as
-    if (mixed_call && bwd_mix_floats(path, B, T, F, K, hop)) {
-        // this path's kernels do not mix in their loads: the mixed fp32 copy behind the path's own layout, then the unmixed call on it
-        float* xm = ws + bwd_own_workspace_floats(path, B, T, F, K, hop, false);
-        rc = launch_mixup(x, xtype, B, T, mix_perm, mix_lam, xm, st);
+    int mode;
+    bool gx_bf16;                    // LEAF_FLAG_IO_BF16: g_x is a bfloat16 buffer
+};
+// floor + PCEN backward per (b,f) row; `col_of` / `gcols`: the MFMA path's column-major copy, `rowsums`: sum_m g_pre per row
+static int launch_pcen_bwd_scan(const LeafArgs& a, const BwdIo& io, const float* raw_in, float* ema, float* gpre, float* rowsum,
+                                const int* col_of, int FP, float* gcols, float* rowsums) {
+    const int B = a.s.B, F = a.s.F, TP = (a.s.T - 1) / a.s.hop + 1;
+    hipLaunchKernelGGL(pcen_bwd_scan_kernel, dim3(ceil_div(B * F, 4)), dim3(256), 0, a.st, raw_in, io.grad_out, B * F, F, TP, a.alpha,
+                       a.delta, a.root, a.ema_w, 1e-12f, io.mode, ema, gpre, rowsum, col_of, FP, gcols, LEAF_BWD_ROWSUMS ? rowsums : nullptr);
+    LEAF_LAUNCH_CHECK();
+    return LEAF_OK;
+}
+// reductions over blocks and the batch, clamp sub-gradients, of the overlap-save backwards
+// (the per-block (d mu, d sigma) partials are summed by param_reduce_kernel too: one launch less)
+static int launch_fft_param_reduce(const LeafArgs& a, const BwdIo& io, const float* gpre, const float* rowsum, const float* dwpart,
+                                   const float* dkpart, int nblocks, const int* col_of, const float* rowsums) {
+    const int B = a.s.B, F = a.s.F, K = a.s.K, TP = (a.s.T - 1) / a.s.hop + 1;
+    hipLaunchKernelGGL(param_reduce_kernel, dim3(F), dim3(kParamRedThreads), 0, a.st, gpre, (const float*)nullptr,
+                       (const float*)nullptr, rowsum, a.pool_w, B, F, TP, K, io.mode, dwpart, nblocks, F, col_of, io.g_pool_w,
+                       io.g_pool_b, io.g_alpha, io.g_delta, io.g_root, io.g_ema_w,
+                       dkpart, nblocks, a.kernel, gabor_bounds(K), io.g_kernel, LEAF_BWD_ROWSUMS ? rowsums : nullptr);
+    LEAF_LAUNCH_CHECK();
+    return LEAF_OK;
+}
+// tools only (LEAF_BAND_BWD=0): no band tasks in the backwards (A/B)
+static inline bool band_bwd_off() {
+    static const bool off = [] { const char* e = tools_env("LEAF_BAND_BWD"); return e && atoi(e) == 0; }();
+    return off;
+}
+
+// ---- overlap-save backward on 4096-sample blocks: long odd windows, parameter gradients (static 801 / 320: dL/dx too)
+static int backward_4k(const CallCtx& ctx, const LeafArgs& a, const BwdIo& io, float* ws) {
+    const auto [B, T, F, K, hop] = a.s;
+    const Fft4kBwdPlan bp = make_fft4k_bwd_plan(a.s, io.g_x != nullptr, ctx.cus);
+    const Fft4kBwdLayout L = fft4k_bwd_layout(bp, B, F);
+    float* tab3 = ws + L.tab3; float* Grow = ws + L.grow; float* part = ws + L.part; float* raw = ws + L.raw;
+    float* gpre = ws + L.gpre; float* rowsum = ws + L.rowsum; int* col_of = reinterpret_cast<int*>(ws + L.col_of);
+    // 1. tables: 4096-point real spectra of w, dw/dmu, dw/dsigma (+ the D tables of w) and the de-interleaved pooling rows
+    float2* Wt = reinterpret_cast<float2*>(Grow + (size_t)F * 2 * bp.RG);
+    // band tasks of the static 32 kHz backward (leaf_band_bwd.hpp): decision by fft4k_prep_kernel's workgroups (f, 0), G~, G~2 and
+    // the edge tables by fft4k_band_tab_kernel, from the parameters of this call
+    BandParams band{};
+    BandTabArgs ba{};
+    const bool band_bwd = LEAF_BAND_BWD && !band_bwd_off() && !ctx.band_off && bp.stat && !bp.dx && L.bgz2 &&
+                          LEAF_4K_BWD_REGW && LEAF_4K_BWD_FULLSCR && bp.lds + band_lds_bytes(F) <= (size_t)kMaxLds &&
+                          band_edges(T, K, hop, bp.L, bp.padL, band, ba.e);
+    if (band_bwd)   // (bwd_slabs = 2: the class decision also asks band_deriv_fits, leaf_band.hpp; no extra grid rows in this kernel)
+        wire_band(ba, band, BandTabs{reinterpret_cast<int*>(ws + L.brec), ws + L.bgz, ws + L.bgz2, ws + L.bedge, ws + L.bedge2, reinterpret_cast<int*>(ws + L.belist)},
+                  a.s, bp.L, bp.padL, ctx.band_strict, /*bwd_slabs=*/2, ctx.band_strict ? nullptr : a.pool_b, ctx.band_strict ? 0.0f : 2.0f);   // the forward's bias-aware class decision (leaf_band.hpp)
+    hipLaunchKernelGGL(fft4k_prep_kernel, dim3(F, 3), dim3(kPrepWaves * 64), 0, a.st, a.kernel, a.pool_w, F, K, gabor_bounds(K), tab3,
+                       Grow, bp.RG, Wt, ba);
+    LEAF_LAUNCH_CHECK();
+    if (band_bwd) hipLaunchKernelGGL(fft4k_band_tab_kernel, dim3(F, 1 + band.n_edge), dim3(kPrepWaves * 64), 0, a.st, a.pool_w, F, K, ba);
+    LEAF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(iota_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, a.st, col_of, F);
+    LEAF_LAUNCH_CHECK();
+    FftParams q{};
+    q.x = io.x; q.io_bf16 = io.xtype; q.H = reinterpret_cast<const float2*>(tab3); q.Gz = Grow; q.part = part;
+    q.B = B; q.T = T; q.TP = bp.TP; q.F = F; q.K = K; q.hop = hop; q.padL = bp.padL; q.L = bp.L; q.nblk = bp.nblk;
+    q.nslot = 2; q.GZ = bp.RG;
+    q.mix_perm = ctx.mix.perm; q.mix_lam = ctx.mix.lam;              // (mixed call: the forward recompute and the MIX backward instance mix in their loads)
+    q.lone = reinterpret_cast<const float*>(Wt);                      // (read by the static forward kernel when it recomputes below)
+    const dim3 grid(cu_grid(B * bp.nblk, ctx.cus));
+    const float* raw_in = io.pooled_raw;
+    int rc;
+    if (!raw_in) {
+        // the forward with its own wave count and LDS (run-time geometry: it parks frame sums between the halves)
+        const int fbn = bp.stat ? 0 : fft_wgg4k_frame_floats(K, hop);
+        int fnw = bp.stat ? LEAF_4K_FWD_NW : 12;
+        while (!bp.stat && fnw > 6 && fft_wgg4k_lds_bytes(fnw, K, fbn) > (size_t)kMaxLds) --fnw;
+        const size_t flds = bp.stat ? fft_wg4k_lds_bytes(LEAF_4K_FWD_NW) : fft_wgg4k_lds_bytes(fnw, K, fbn);
+        if (flds > (size_t)kMaxLds) return LEAF_ERR_BAD_ALGO;
+        q.NT = fbn;
+        rc = launch_lds(bp.stat ? as_fft_kernel(leaf_inst_fft_wg4k()) : pick_fft_wgg4k_kernel(K), grid, fnw, flds, a.st, q);
         if (rc != LEAF_OK) return rc;
-        x = xm; xtype = kSampleF32; mix_perm = nullptr; mix_lam = nullptr;
+        q.NT = 0;
+        finalize_pooled_raw(a, part, SlotGeom{bp.L, bp.padL, K, hop, T, 2}, raw, ctx.cus);
+        LEAF_LAUNCH_CHECK();
+        raw_in = raw;
     }
-    if (float* x32 = !mixed_call && bwd_x32_floats(path, B, T, K, hop, flags) ? ws + bwd_own_workspace_floats(path, B, T, F, K, hop, g_x != nullptr) : nullptr) {
-        // these families read fp32: one widening pass into the workspace's tail, then the fp32 path
-        const size_t n = (size_t)B * T;
-        hipLaunchKernelGGL(x16_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                           reinterpret_cast<const unsigned short*>(x), xtype, n, x32);
-        LEAF_LAUNCH_CHECK();
-        x = x32;
-        xtype = kSampleF32;
+    // 2. floor + PCEN backward per (b,f) row
+    rc = launch_pcen_bwd_scan(a, io, raw_in, ws + L.ema, gpre, rowsum, nullptr, 0, nullptr, ws + L.gsrow);
+    if (rc != LEAF_OK) return rc;
+    // 3. per-(block, filter) partial gradients
+    q.gpre = gpre; q.pool_w = a.pool_w; q.dkpart = ws + L.dkpart; q.dwpart = ws + L.dwpart; q.part = nullptr;
+    const bool mixed = ctx.mix.lam != nullptr;
+    FftKernel kb = bp.dx ? as_fft_kernel(leaf_inst_fft_wg4k_bwd_dx())
+                         : bp.stat ? as_fft_kernel(mixed ? leaf_inst_fft_wg4k_bwd_mix() : leaf_inst_fft_wg4k_bwd())
+                                   : mixed ? as_fft_kernel(leaf_inst_fft_wgg4k_bwd_mix(fft_wgg4k_taps_per_lane(K))) : pick_fft_wgg4k_bwd_kernel(K);
+    if (!kb) return LEAF_ERR_BAD_ALGO;
+    if (bp.dx) q.part = ws + L.dxblk;                                 // [block][4096] input gradients, un-rotated
+    size_t blds = bp.lds;
+    if (band_bwd) {
+        band.lds_off = (int)(blds / 4);
+        blds += band_lds_bytes(F);
+        q.band = band;
     }
-    if (path == BWD_PATH_FFT4K) {
-        // ---- overlap-save backward on 4096-sample blocks: long odd windows, parameter gradients
-        const Fft4kBwdPlan bp = make_fft4k_bwd_plan(B, T, F, K, hop, g_x != nullptr);
-        const Fft4kBwdLayout L = fft4k_bwd_layout(bp, B, F);
-        float* tab3 = ws + L.tab3; float* Grow = ws + L.grow; float* part = ws + L.part; float* raw = ws + L.raw;
-        float* ema = ws + L.ema; float* gpre = ws + L.gpre; float* rowsum = ws + L.rowsum; float* dkpart = ws + L.dkpart;
-        float* dwpart = ws + L.dwpart; int* col_of = reinterpret_cast<int*>(ws + L.col_of);
-        // 1. tables: 4096-point real spectra of w, dw/dmu, dw/dsigma (+ the D tables of w) and the de-interleaved pooling rows
-        float2* Wt = reinterpret_cast<float2*>(Grow + (size_t)F * 2 * bp.RG);
-        // band tasks of the static 32 kHz backward (leaf_band_bwd.hpp): decision by fft4k_prep_kernel's workgroups (f, 0), G~, G~2 and
-        // the edge tables by fft4k_band_tab_kernel, from the parameters of this call
-        static const bool band_bwd_off4 = [] { const char* e = tools_env("LEAF_BAND_BWD"); return e && atoi(e) == 0; }();   // tools only: A/B
-        BandParams band{};
-        BandTabArgs ba{};
-        const bool band_bwd = LEAF_BAND_BWD && !band_bwd_off4 && !(flags & LEAF_FLAG_BWD_FULL_TRANSFORMS) && bp.stat && !bp.dx && L.bgz2 &&
-                              LEAF_4K_BWD_REGW && LEAF_4K_BWD_FULLSCR && bp.lds + band_lds_bytes(F) <= (size_t)kMaxLds &&
-                              band_edges(T, K, hop, bp.L, bp.padL, band, ba.e);
+    rc = launch_lds(kb, grid, bp.nw, blds, a.st, q);
+    if (rc == LEAF_OK && bp.dx) rc = launch_dx_gather(io.gx_bf16, ws + L.dxblk, a.s, bp.nblk, 1, bp.L, bp.padL, io.g_x, kFft4N, a.st);
+    if (rc != LEAF_OK) return rc;
+    // 4. reductions over blocks and the batch, clamp sub-gradients
+    return launch_fft_param_reduce(a, io, gpre, rowsum, ws + L.dwpart, ws + L.dkpart, B * bp.nblk, col_of, ws + L.gsrow);
+}
+
+// ---- overlap-save backward on 2048-sample blocks: the windows the FFT forward is chosen for (K >= 224 or a static geometry)
+static int backward_fft(const CallCtx& ctx, const LeafArgs& a, const BwdIo& io, float* ws) {
+    const auto [B, T, F, K, hop] = a.s;
+    const bool need_dx = io.g_x != nullptr;
+    const FftPlan fp = make_fft_plan(a.s, ctx.cus);
+    // the lowered thresholds of wg_bwd_sixteenths hold only where band tasks CAN run in this call
+    BandParams band_probe{};
+    BandEdge edge_probe[kBandMaxEdge];
+    const bool band_possible = fp.ok && !ctx.band_off && (K & 1) && F <= kBandMaxFilters && fp.nslot == 2 &&
+                               band_edges(T, K, hop, fp.L, fp.padL, band_probe, edge_probe);
+    const FftBwdLayout L = fft_bwd_layout(fp, B, F, need_dx);
+    float* R3 = ws + L.R3; float* Gz = ws + L.Gz; int* col_of = reinterpret_cast<int*>(ws + L.col_of);
+    float* part = ws + L.part; float* raw = ws + L.raw; float* gpre = ws + L.gpre; float* rowsum = ws + L.rowsum;
+    // 1. tables: real spectra of w, dw/dmu, dw/dsigma and the pooling rows -- with the band tasks of the static backward
+    // (leaf_band_bwd.hpp: the filters the forward runs on 256- / 512-point transforms get their parameter gradients at the
+    // decimated rate too) one launch of fft_prep_band_kernel builds them together with the decision, G~, G~2 and the edge
+    // tables, from the parameters of THIS call (the decision the forward took from the same parameters)
+    BandParams band{};
+    BandTabArgs ba{};
+    // (with dL/dx: in the workgroup-per-block kernel, whose band tasks add their members' shares to the block's G)
+    const bool use_wg = fft_wg_bwd_use(fp, B, K, hop, need_dx, ctx.cus, band_possible);
+    const FftWgBwdLaunch bwl = pick_fft_wg_bwd_kernel(K, hop, need_dx, ctx.cus, band_possible, (long long)B * fp.nblk);
+    const bool band_bwd = LEAF_BAND_BWD && !band_bwd_off() && !ctx.band_off && L.bgz2 && (K & 1) &&
+                          F <= kBandMaxFilters && fp.nslot == 2 && use_wg &&
+                          (need_dx ? LEAF_BAND_BWD_DX && bwl.block_dx : true) &&
+                          bwl.lds + band_lds_bytes(F) <= (size_t)kMaxLds && band_edges(T, K, hop, fp.L, fp.padL, band, ba.e);
+    if (band_bwd) {
+        wire_band(ba, band, BandTabs{reinterpret_cast<int*>(ws + L.brec), ws + L.bgz, ws + L.bgz2, ws + L.bedge, ws + L.bedge2, reinterpret_cast<int*>(ws + L.belist)},
+                  a.s, fp.L, fp.padL, ctx.band_strict, /*bwd_slabs=*/1, ctx.band_strict ? nullptr : a.pool_b, ctx.band_strict ? 0.0f : 2.0f);   // the forward's bias-aware class decision
+        hipLaunchKernelGGL(fft_prep_band_kernel, dim3(F, 2 + band.n_edge + 2), dim3(kPrepWaves * 64), 0, a.st, a.kernel, a.pool_w, F, K, fp.GZ,
+                           gabor_bounds(K), reinterpret_cast<float2*>(R3), Gz, col_of, ba);
+    } else {
+        hipLaunchKernelGGL(fft_prep_kernel, dim3(F, 3), dim3(kPrepWaves * 64), 0, a.st, a.kernel, a.pool_w, F, K, fp.GZ,
+                           gabor_bounds(K), 1, reinterpret_cast<float2*>(R3), Gz, col_of, (K & 1) ? (float*)nullptr : ws + L.lone);
+    }
+    LEAF_LAUNCH_CHECK();
+    FftParams q{};
+    q.x = io.x; q.io_bf16 = io.xtype; q.H = reinterpret_cast<const float2*>(R3); q.Gz = Gz; q.part = part;
+    q.lone = (K & 1) ? nullptr : ws + L.lone;
+    fill_fft_params(q, fp, a.s);
+    q.mix_perm = ctx.mix.perm; q.mix_lam = ctx.mix.lam;               // (non-NULL only where the MIX instances below exist)
+    const bool mixed = ctx.mix.lam != nullptr;
+    const dim3 wave_grid(cu_grid(ceil_div(q.total_tasks, kFftWaves), ctx.cus)), block_grid(cu_grid(B * fp.nblk, ctx.cus));
+    const float* raw_in = io.pooled_raw;
+    int rc;
+    if (!raw_in) {
+        FftKernel kf = mixed ? pick_fft_kernel_mix(fp, K, hop, false) : pick_fft_kernel(fp, K, hop, false);
+        if (!kf) return LEAF_ERR_BAD_ALGO;
+        rc = launch_lds(kf, wave_grid, kFftWaves, fp.lds, a.st, q);
+        if (rc != LEAF_OK) return rc;
+        finalize_pooled_raw(a, part, SlotGeom{fp.L, fp.padL, K, hop, T, fp.nslot}, raw, ctx.cus);
+        LEAF_LAUNCH_CHECK();
+        raw_in = raw;
+    }
+    // 2. floor + PCEN backward per (b,f) row
+    rc = launch_pcen_bwd_scan(a, io, raw_in, ws + L.ema, gpre, rowsum, nullptr, 0, nullptr, ws + L.grow);
+    if (rc != LEAF_OK) return rc;
+    // 3. filterbank recompute + transposed pooling + second transform: per-block (d mu, d sigma, d pool_w)
+    q.gpre = gpre; q.pool_w = a.pool_w; q.dkpart = ws + L.dkpart; q.dwpart = ws + L.dwpart; q.part = nullptr;
+    if (use_wg) {
+        // workgroup-per-block backward; with g_x the per-block input gradients go to dxblk and are gathered below
+        FftWgBwdLaunch wl = pick_fft_wg_bwd_kernel(K, hop, need_dx, ctx.cus, band_possible, (long long)B * fp.nblk, io.xtype == kSampleBf16);
+        q.part = need_dx ? ws + L.dxblk : nullptr;
+        if (mixed) wl.fn = as_fft_kernel(leaf_inst_fft_wg_bwd_mix(K));
+        if (!wl.fn) return LEAF_ERR_BAD_ALGO;
         if (band_bwd) {
-            ba.T = T; ba.L = bp.L; ba.hop = hop; ba.padL = bp.padL; ba.eps2 = kBandEps2; ba.eta = (flags & LEAF_FLAG_BWD_STRICT_BAND_CLASSES) ? kBandEta : kBandEtaFree;
-            ba.bwd_slabs = 2;                     // (a backward launch: the class decision also asks band_deriv_fits, leaf_band.hpp; no extra grid rows in this kernel)
-            ba.rec = reinterpret_cast<int*>(ws + L.brec); ba.gz = ws + L.bgz; ba.gz2 = ws + L.bgz2; ba.edge = ws + L.bedge;
-            ba.edge2 = ws + L.bedge2; ba.elist = reinterpret_cast<int*>(ws + L.belist); ba.n_edge = band.n_edge;
-            band.rec = ba.rec; band.gz = ba.gz; band.gz2 = ba.gz2; band.edge = ba.edge; band.edge2 = ba.edge2; band.elist = ba.elist;
-            if (!(flags & LEAF_FLAG_BWD_STRICT_BAND_CLASSES)) { band.bias = pool_b; band.smax = 2.0f; }   // the forward's bias-aware class decision (leaf_band.hpp)
-        }
-        hipLaunchKernelGGL(fft4k_prep_kernel, dim3(F, 3), dim3(kPrepWaves * 64), 0, st, kernel, pool_w, F, K, gabor_bounds(K), tab3,
-                           Grow, bp.RG, Wt, ba);
-        LEAF_LAUNCH_CHECK();
-        if (band_bwd) hipLaunchKernelGGL(fft4k_band_tab_kernel, dim3(F, 1 + band.n_edge), dim3(kPrepWaves * 64), 0, st, pool_w, F, K, ba);
-        LEAF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(iota_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, col_of, F);
-        LEAF_LAUNCH_CHECK();
-        FftParams q{};
-        q.x = x; q.io_bf16 = xtype; q.H = reinterpret_cast<const float2*>(tab3); q.Gz = Grow; q.part = part;
-        q.B = B; q.T = T; q.TP = bp.TP; q.F = F; q.K = K; q.hop = hop; q.padL = bp.padL; q.L = bp.L; q.nblk = bp.nblk;
-        q.nslot = 2; q.GZ = bp.RG;
-        q.mix_perm = mix_perm; q.mix_lam = mix_lam;                       // (mixed call: the forward recompute and the MIX backward instance mix in their loads)
-        q.lone = reinterpret_cast<const float*>(Wt);                      // (read by the static forward kernel when it recomputes below)
-        const dim3 grid(std::max(1, std::min(B * bp.nblk, num_cus())));
-        const float* raw_in = pooled_raw;              // saved by leaf_forward_save_f32, else recomputed here
-        if (!raw_in) {
-            // the forward with its own wave count and LDS (run-time geometry: it parks frame sums between the halves)
-            const int fbn = bp.stat ? 0 : fft_wgg4k_frame_floats(K, hop);
-            int fnw = bp.stat ? LEAF_4K_FWD_NW : 12;
-            while (!bp.stat && fnw > 6 && fft_wgg4k_lds_bytes(fnw, K, fbn) > (size_t)kMaxLds) --fnw;
-            const size_t flds = bp.stat ? fft_wg4k_lds_bytes(LEAF_4K_FWD_NW) : fft_wgg4k_lds_bytes(fnw, K, fbn);
-            if (flds > (size_t)kMaxLds) return LEAF_ERR_BAD_ALGO;
-            FftKernel kf = bp.stat ? as_fft_kernel(leaf_inst_fft_wg4k()) : pick_fft_wgg4k_kernel(K);
-            q.NT = fbn;
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds);
-            hipLaunchKernelGGL(kf, grid, dim3(fnw * 64), flds, st, q);
-            LEAF_LAUNCH_CHECK();
-            q.NT = 0;
-            launch_fft_finalize(FinParams{part, F, TP, SlotGeom{bp.L, bp.padL, K, hop, T, 2}, pool_b, alpha, delta, root, ema_w, 1e-12f, 8,
-                                          raw, raw, nullptr}, B, OwnedClips{}, st);
-            LEAF_LAUNCH_CHECK();
-            raw_in = raw;
-        }
-        // 2. floor + PCEN backward per (b,f) row
-        hipLaunchKernelGGL(pcen_bwd_scan_kernel, dim3(ceil_div(B * F, 4)), dim3(256), 0, st, raw_in, grad_out, B * F, F, TP, alpha,
-                           delta, root, ema_w, 1e-12f, mode, ema, gpre, rowsum, (const int*)nullptr, 0, (float*)nullptr, LEAF_BWD_ROWSUMS ? ws + L.gsrow : nullptr);
-        LEAF_LAUNCH_CHECK();
-        // 3. per-(block, filter) partial gradients
-        q.gpre = gpre; q.pool_w = pool_w; q.dkpart = dkpart; q.dwpart = dwpart; q.part = nullptr;
-        FftKernel kb = bp.dx ? as_fft_kernel(leaf_inst_fft_wg4k_bwd_dx())
-                             : bp.stat ? as_fft_kernel(mix_lam ? leaf_inst_fft_wg4k_bwd_mix() : leaf_inst_fft_wg4k_bwd())
-                                       : mix_lam ? as_fft_kernel(leaf_inst_fft_wgg4k_bwd_mix(fft_wgg4k_taps_per_lane(K))) : pick_fft_wgg4k_bwd_kernel(K);
-        if (!kb) return LEAF_ERR_BAD_ALGO;
-        if (bp.dx) q.part = ws + L.dxblk;                                 // [block][4096] input gradients, un-rotated
-        size_t blds = bp.lds;
-        if (band_bwd) {
-            band.lds_off = (int)(blds / 4);
-            blds += band_lds_bytes(F);
+            band.lds_off = (int)(wl.lds / 4);
+            wl.lds += band_lds_bytes(F);
             q.band = band;
         }
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-        hipLaunchKernelGGL(kb, grid, dim3(bp.nw * 64), blds, st, q);
+        // dx kernels: one (block, group) per WAVE, or (block_dx) a workgroup per block like the parameter-gradient kernel
+        const int wgs = need_dx && !wl.block_dx ? ceil_div(q.total_tasks, wl.nw) : B * fp.nblk;
+        rc = launch_lds(wl.fn, dim3(cu_grid(wgs, ctx.cus)), wl.nw, wl.lds, a.st, q);
+        if (rc == LEAF_OK && need_dx)
+            rc = launch_dx_gather(io.gx_bf16, ws + L.dxblk, a.s, fp.nblk, wl.block_dx ? 1 : fp.nfq, fp.L, fp.padL, io.g_x, kFftN, a.st);
+    } else if (need_dx) {
+        // dL/dx on a window without a static instance: workgroup per block, G in LDS
+        const FftWgBwdLaunch wl = pick_fft_wgg_bwd_dx_kernel(fp, K, hop, ctx.cus);
+        if (!wl.fn) return LEAF_ERR_BAD_ALGO;                         // bwd_path() admits the FFT path only with a dL/dx kernel
+        q.part = ws + L.dxblk;                                        // [block][2048]: one plane per block
+        rc = launch_lds(wl.fn, block_grid, wl.nw, wl.lds, a.st, q);
+        if (rc == LEAF_OK) rc = launch_dx_gather(io.gx_bf16, ws + L.dxblk, a.s, fp.nblk, 1, fp.L, fp.padL, io.g_x, kFftN, a.st);
+    } else if (fft_wgg_bwd_use(fp, B, K, hop, need_dx, ctx.cus)) {
+        const FftWgBwdLaunch wl = pick_fft_wgg_bwd_kernel(fp, K, hop);
+        rc = launch_lds(wl.fn, block_grid, wl.nw, wl.lds, a.st, q);
+    } else {
+        FftKernel kb = mixed ? pick_fft_kernel_mix(fp, K, hop, true) : pick_fft_kernel(fp, K, hop, true);
+        if (!kb) return LEAF_ERR_BAD_ALGO;
+        rc = launch_lds(kb, wave_grid, kFftWaves, fp.lds, a.st, q);
+    }
+    if (rc != LEAF_OK) return rc;
+    // 4. reductions over blocks and the batch, clamp sub-gradients
+    return launch_fft_param_reduce(a, io, gpre, rowsum, ws + L.dwpart, ws + L.dkpart, B * fp.nblk, col_of, ws + L.grow);
+}
+
+// ---- fused backward (MFMA): used whenever the geometry fits and dL/dx is not requested
+static int backward_mfma(const CallCtx& ctx, const LeafArgs& a, const BwdIo& io, float* ws) {
+    const auto [B, T, F, K, hop] = a.s;
+    const int cus = ctx.cus, TP = (T - 1) / hop + 1;
+    const FusedPlan pl = make_plan(a.s, cus);
+    const BwdPlan bp = make_bwd_plan(pl, T);
+    const BwdLayout L = bwd_layout(pl, bp, B, T, F, cus);
+    const FusedTabs t = fused_tabs(pl, ws + L.W, ws + L.G, reinterpret_cast<int*>(ws + L.meta));
+    float* Gs = ws + L.Gs; float* part = ws + L.part; float* raw = ws + L.raw; float* gpre = ws + L.gpre;
+    float* gcols = ws + L.gcols; float* rowsum = ws + L.rowsum; float* dwpart = ws + L.dwpart;
+    float* dHpart = ws + L.dHpart; float* dY = ws + L.dY;
+    const int Rp = 16 * bp.NKT;
+    // 1. tables, forward recompute up to the pre-floor pooled value
+    hipLaunchKernelGGL(fused_prep_kernel, dim3(ceil_div(pl.R * 2 * pl.FP + pl.FP * pl.GJ, 256)), dim3(256), 0, a.st,
+                       a.kernel, a.pool_w, F, pl.FP, K, pl.R, pl.GJ, gabor_bounds(K), t.W, t.G, Gs, t.perm, t.col_of, t.tile_ks);
+    LEAF_LAUNCH_CHECK();
+    FusedParams prm = base_fused_params(pl, a.s, -1);
+    prm.x = io.x; prm.W = t.W; prm.G = t.G; prm.tile_ks = t.tile_ks; prm.part = part;
+    const float* raw_in = io.pooled_raw;
+    if (!raw_in) {
+        if (launch_fused_groups(prm, pl, cus, a.st) != hipSuccess) return LEAF_ERR_LAUNCH;
+        launch_fused_finalize(pl, a, part, t.col_of, 8, raw, nullptr);
         LEAF_LAUNCH_CHECK();
-        if (bp.dx) {
-            hipLaunchKernelGGL(io_bf16 ? fft_dx_gather_kernel<true> : fft_dx_gather_kernel<false>, dim3(ceil_div(T, 1024), B), dim3(256), 0, st, ws + L.dxblk, T, bp.nblk, 1, bp.L,
-                               bp.padL, g_x, kFft4N);
-            LEAF_LAUNCH_CHECK();
-        }
-        // 4. reductions over blocks and the batch, clamp sub-gradients
-        // (the per-block (d mu, d sigma) partials are summed by param_reduce_kernel below: one launch less)
-        hipLaunchKernelGGL(param_reduce_kernel, dim3(F), dim3(kParamRedThreads), 0, st, gpre, (const float*)nullptr,
-                           (const float*)nullptr, rowsum, pool_w, B, F, TP, K, mode, dwpart, B * bp.nblk, F, col_of, g_pool_w,
-                           g_pool_b, g_alpha, g_delta, g_root, g_ema_w,
-                           dkpart, B * bp.nblk, kernel, gabor_bounds(K), g_kernel, LEAF_BWD_ROWSUMS ? ws + L.gsrow : nullptr);
-        LEAF_LAUNCH_CHECK();
-        return LEAF_OK;
+        raw_in = raw;
     }
-    {
-        // ---- overlap-save backward: odd windows the FFT forward is chosen for (K >= 224), dL/dx not requested
-        const FftPlan fp = make_fft_plan(B, T, F, K, hop);
-        struct BandPossible {                                   // scoped: the thresholds of THIS call (wg_bwd_sixteenths)
-            bool prev;
-            explicit BandPossible(bool v) : prev(tl_bwd_band_possible) { tl_bwd_band_possible = v; }
-            ~BandPossible() { tl_bwd_band_possible = prev; }
-        };
-        BandParams band_probe{};
-        BandEdge edge_probe[kBandMaxEdge];
-        const BandPossible band_possible(fp.ok && !(flags & LEAF_FLAG_BWD_FULL_TRANSFORMS) && (K & 1) && F <= kBandMaxFilters &&
-                                         fp.nslot == 2 && band_edges(T, K, hop, fp.L, fp.padL, band_probe, edge_probe));
-        if (path == BWD_PATH_FFT) {
-            const FftBwdLayout L = fft_bwd_layout(fp, B, F, g_x != nullptr);
-            float* R3 = ws + L.R3; float* Gz = ws + L.Gz; int* col_of = reinterpret_cast<int*>(ws + L.col_of);
-            float* part = ws + L.part; float* raw = ws + L.raw; float* ema = ws + L.ema; float* gpre = ws + L.gpre;
-            float* rowsum = ws + L.rowsum; float* dkpart = ws + L.dkpart; float* dwpart = ws + L.dwpart;
-            // 1. tables: real spectra of w, dw/dmu, dw/dsigma and the pooling rows -- with the band tasks of the static backward
-            // (leaf_band_bwd.hpp: the filters the forward runs on 256- / 512-point transforms get their parameter gradients at the
-            // decimated rate too) one launch of fft_prep_band_kernel builds them together with the decision, G~, G~2 and the edge
-            // tables, from the parameters of THIS call (the decision the forward took from the same parameters)
-            static const bool band_bwd_off = [] { const char* e = tools_env("LEAF_BAND_BWD"); return e && atoi(e) == 0; }();   // tools only: A/B
-            BandParams band{};
-            BandTabArgs ba{};
-            // (with dL/dx: in the workgroup-per-block kernel, whose band tasks add their members' shares to the block's G)
-            const FftWgBwdLaunch bwl = pick_fft_wg_bwd_kernel(K, hop, g_x != nullptr, (long long)B * fp.nblk);
-            const bool band_bwd = LEAF_BAND_BWD && !band_bwd_off && !(flags & LEAF_FLAG_BWD_FULL_TRANSFORMS) && L.bgz2 && (K & 1) &&
-                                  F <= kBandMaxFilters && fp.nslot == 2 && fft_wg_bwd_use(fp, B, K, hop, g_x != nullptr) &&
-                                  (g_x ? LEAF_BAND_BWD_DX && bwl.block_dx : true) &&
-                                  bwl.lds + band_lds_bytes(F) <= (size_t)kMaxLds && band_edges(T, K, hop, fp.L, fp.padL, band, ba.e);
-            if (band_bwd) {
-                ba.T = T; ba.L = fp.L; ba.hop = hop; ba.padL = fp.padL; ba.eps2 = kBandEps2; ba.eta = (flags & LEAF_FLAG_BWD_STRICT_BAND_CLASSES) ? kBandEta : kBandEtaFree;
-                ba.rec = reinterpret_cast<int*>(ws + L.brec); ba.gz = ws + L.bgz; ba.gz2 = ws + L.bgz2; ba.edge = ws + L.bedge;
-                ba.edge2 = ws + L.bedge2; ba.elist = reinterpret_cast<int*>(ws + L.belist); ba.n_edge = band.n_edge;
-                ba.bwd_slabs = 1;
-                hipLaunchKernelGGL(fft_prep_band_kernel, dim3(F, 2 + band.n_edge + 2), dim3(kPrepWaves * 64), 0, st, kernel, pool_w, F, K, fp.GZ,
-                                   gabor_bounds(K), reinterpret_cast<float2*>(R3), Gz, col_of, ba);
-                band.rec = ba.rec; band.gz = ba.gz; band.gz2 = ba.gz2; band.edge = ba.edge; band.edge2 = ba.edge2; band.elist = ba.elist;
-                if (!(flags & LEAF_FLAG_BWD_STRICT_BAND_CLASSES)) { band.bias = pool_b; band.smax = 2.0f; }   // the forward's bias-aware class decision
-            } else {
-                hipLaunchKernelGGL(fft_prep_kernel, dim3(F, 3), dim3(kPrepWaves * 64), 0, st, kernel, pool_w, F, K, fp.GZ,
-                                   gabor_bounds(K), 1, reinterpret_cast<float2*>(R3), Gz, col_of, (K & 1) ? (float*)nullptr : ws + L.lone);
-            }
-            LEAF_LAUNCH_CHECK();
-            FftParams q{};
-            q.x = x; q.io_bf16 = xtype; q.H = reinterpret_cast<const float2*>(R3); q.Gz = Gz; q.part = part;
-            q.lone = (K & 1) ? nullptr : ws + L.lone;
-            q.B = B; q.T = T; q.TP = fp.TP; q.F = F; q.K = K; q.hop = hop; q.padL = fp.padL;
-            q.L = fp.L; q.nblk = fp.nblk; q.GZ = fp.GZ; q.nslot = fp.nslot; q.g_bufs = fp.g_bufs; q.NT = fp.NT; q.fq = fp.fq; q.nfq = fp.nfq;
-            q.scr_floats = fp.scr_floats; q.total_tasks = B * fp.nblk * fp.nfq;
-            q.rot = K / 2;
-            q.mix_perm = mix_perm; q.mix_lam = mix_lam;                   // (non-NULL only where the MIX instances below exist)
-            const dim3 grid(std::max(1, std::min(ceil_div(q.total_tasks, kFftWaves), num_cus())));
-            const float* raw_in = pooled_raw;          // saved by leaf_forward_save_f32, else recomputed here
-            if (!raw_in) {
-                FftKernel kf = mix_lam ? pick_fft_kernel_mix(fp, K, hop, false) : pick_fft_kernel(fp, K, hop, false);
-                if (!kf) return LEAF_ERR_BAD_ALGO;
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds);
-                hipLaunchKernelGGL(kf, grid, dim3(kFftWaves * 64), fp.lds, st, q);
-                LEAF_LAUNCH_CHECK();
-                launch_fft_finalize(FinParams{part, F, TP, SlotGeom{fp.L, fp.padL, K, hop, T, fp.nslot}, pool_b, alpha, delta, root, ema_w,
-                                              1e-12f, 8, raw, raw, nullptr}, B, OwnedClips{}, st);
-                LEAF_LAUNCH_CHECK();
-                raw_in = raw;
-            }
-            // 2. floor + PCEN backward per (b,f) row
-            hipLaunchKernelGGL(pcen_bwd_scan_kernel, dim3(ceil_div(B * F, 4)), dim3(256), 0, st, raw_in, grad_out, B * F, F, TP,
-                               alpha, delta, root, ema_w, 1e-12f, mode, ema, gpre, rowsum, (const int*)nullptr, 0,
-                               (float*)nullptr, LEAF_BWD_ROWSUMS ? ws + L.grow : nullptr);
-            LEAF_LAUNCH_CHECK();
-            // 3. filterbank recompute + transposed pooling + second transform: per-block (d mu, d sigma, d pool_w)
-            q.gpre = gpre; q.pool_w = pool_w; q.dkpart = dkpart; q.dwpart = dwpart; q.part = nullptr;
-            if (fft_wg_bwd_use(fp, B, K, hop, g_x != nullptr)) {
-                // workgroup-per-block backward; with g_x the per-block input gradients go to dxblk and are gathered below
-                FftWgBwdLaunch wl = pick_fft_wg_bwd_kernel(K, hop, g_x != nullptr, (long long)B * fp.nblk, xtype == kSampleBf16);
-                q.part = g_x ? ws + L.dxblk : nullptr;
-                if (mix_lam) wl.fn = as_fft_kernel(leaf_inst_fft_wg_bwd_mix(K));
-                if (!wl.fn) return LEAF_ERR_BAD_ALGO;
-                if (band_bwd) {
-                    band.lds_off = (int)(wl.lds / 4);
-                    wl.lds += band_lds_bytes(F);
-                    q.band = band;
-                }
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wl.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl.lds);
-                // dx kernels: one (block, group) per WAVE, or (block_dx) a workgroup per block like the parameter-gradient kernel
-                const int wgs = g_x && !wl.block_dx ? ceil_div(q.total_tasks, wl.nw) : B * fp.nblk;
-                hipLaunchKernelGGL(wl.fn, dim3(std::max(1, std::min(wgs, num_cus()))), dim3(wl.nw * 64), wl.lds, st, q);
-                LEAF_LAUNCH_CHECK();
-                if (g_x) {
-                    hipLaunchKernelGGL(io_bf16 ? fft_dx_gather_kernel<true> : fft_dx_gather_kernel<false>, dim3(ceil_div(T, 1024), B), dim3(256), 0, st, ws + L.dxblk, T, fp.nblk,
-                                       wl.block_dx ? 1 : fp.nfq, fp.L, fp.padL, g_x, kFftN);
-                    LEAF_LAUNCH_CHECK();
-                }
-            } else if (g_x && pick_fft_wgg_bwd_dx_kernel(fp, B, K, hop).fn) {
-                // dL/dx on a window without a static instance: workgroup per block, G in LDS
-                const FftWgBwdLaunch wl = pick_fft_wgg_bwd_dx_kernel(fp, B, K, hop);
-                q.part = ws + L.dxblk;                                    // [block][2048]: one plane per block
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wl.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl.lds);
-                hipLaunchKernelGGL(wl.fn, dim3(std::max(1, std::min(B * fp.nblk, num_cus()))), dim3(wl.nw * 64), wl.lds, st, q);
-                LEAF_LAUNCH_CHECK();
-                hipLaunchKernelGGL(io_bf16 ? fft_dx_gather_kernel<true> : fft_dx_gather_kernel<false>, dim3(ceil_div(T, 1024), B), dim3(256), 0, st, ws + L.dxblk, T, fp.nblk, 1, fp.L,
-                                   fp.padL, g_x, kFftN);
-                LEAF_LAUNCH_CHECK();
-            } else if (g_x) {
-                return LEAF_ERR_BAD_ALGO;                                 // bwd_path() admits the FFT path only with a dL/dx kernel
-            } else if (fft_wgg_bwd_use(fp, B, K, hop, g_x != nullptr)) {
-                const FftWgBwdLaunch wl = pick_fft_wgg_bwd_kernel(fp, K, hop);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wl.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl.lds);
-                hipLaunchKernelGGL(wl.fn, dim3(std::max(1, std::min(B * fp.nblk, num_cus()))), dim3(wl.nw * 64), wl.lds, st, q);
-                LEAF_LAUNCH_CHECK();
-            } else {
-                FftKernel kb = mix_lam ? pick_fft_kernel_mix(fp, K, hop, true) : pick_fft_kernel(fp, K, hop, true);
-                if (!kb) return LEAF_ERR_BAD_ALGO;
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds);
-                hipLaunchKernelGGL(kb, grid, dim3(kFftWaves * 64), fp.lds, st, q);
-                LEAF_LAUNCH_CHECK();
-            }
-            // 4. reductions over blocks and the batch, clamp sub-gradients
-            // (the per-block (d mu, d sigma) partials are summed by param_reduce_kernel below: one launch less)
-            hipLaunchKernelGGL(param_reduce_kernel, dim3(F), dim3(kParamRedThreads), 0, st, gpre, (const float*)nullptr,
-                               (const float*)nullptr, rowsum, pool_w, B, F, TP, K, mode, dwpart, B * fp.nblk, F, col_of,
-                               g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w,
-                               dkpart, B * fp.nblk, kernel, gabor_bounds(K), g_kernel, LEAF_BWD_ROWSUMS ? ws + L.grow : nullptr);
-            LEAF_LAUNCH_CHECK();
-            return LEAF_OK;
-        }
+    // 2. floor + PCEN backward per (b,f) row
+    if (hipMemsetAsync(gcols, 0, (size_t)B * TP * pl.FP * 4, a.st) != hipSuccess) return LEAF_ERR_LAUNCH;
+    int rc = launch_pcen_bwd_scan(a, io, raw_in, ws + L.ema, gpre, rowsum, t.col_of, pl.FP, gcols, nullptr);
+    if (rc != LEAF_OK) return rc;
+    // 3. filterbank recompute with the backward epilogue: dY (time-major) and d pool_w partials
+    if (hipMemsetAsync(dwpart, 0, (size_t)cus * kWavesPerWG * pl.FP * 4, a.st) != hipSuccess) return LEAF_ERR_LAUNCH;
+    if (hipMemsetAsync(dHpart, 0, (size_t)cus * Rp * 2 * pl.FP * 4, a.st) != hipSuccess) return LEAF_ERR_LAUNCH;
+    prm.Gs = Gs; prm.gcols = gcols; prm.dY = dY; prm.dwpart = dwpart; prm.part = nullptr;
+    if (launch_fused_groups(prm, pl, cus, a.st) != hipSuccess) return LEAF_ERR_LAUNCH;
+    // 4. tap gradients: dH = S^T dY on the MFMA, then chain to (mu, sigma)
+    DtapsParams dp{};
+    dp.x = io.x; dp.dY = dY; dp.tile_ks = t.tile_ks; dp.dHpart = dHpart;
+    dp.B = B; dp.T = T; dp.FP = pl.FP; dp.K = K; dp.Hf = pl.Hf; dp.xshift = pl.xshift;
+    dp.NKT = bp.NKT; dp.NW = bp.NW; dp.NS = bp.NS; dp.HPc = bp.HPc; dp.XSC = bp.XSC; dp.LD = bp.LD;
+    dp.nch = bp.nch; dp.total_chunks = B * bp.nch;
+    if (pl.groups_main > 0) {
+        dp.tile_base = 0;
+        const int gx = cu_grid(dp.total_chunks, std::max(1, cus / pl.groups_main));
+        if (launch_dtaps(dp, pl.rt_main, bp.TPW, pl.groups_main, bp.lds, gx, a.st) != hipSuccess) return LEAF_ERR_LAUNCH;
     }
-    {
-        // ---- fused backward (MFMA): used whenever the geometry fits and dL/dx is not requested
-        const FusedPlan pl = make_plan(B, T, F, K, hop);
-        const BwdPlan bp = make_bwd_plan(pl, T);
-        if (path == BWD_PATH_MFMA) {
-            const int cus = num_cus();
-            const BwdLayout L = bwd_layout(pl, bp, B, T, F, cus);
-            float* W = ws + L.W; float* G = ws + L.G; float* Gs = ws + L.Gs;
-            int* meta = reinterpret_cast<int*>(ws + L.meta);
-            int* perm = meta; int* col_of = meta + pl.FP; int* tile_ks = meta + 2 * pl.FP;
-            float* part = ws + L.part; float* raw = ws + L.raw; float* ema = ws + L.ema; float* gpre = ws + L.gpre;
-            float* gcols = ws + L.gcols; float* rowsum = ws + L.rowsum; float* dwpart = ws + L.dwpart;
-            float* dHpart = ws + L.dHpart; float* dY = ws + L.dY;
-            const int Rp = 16 * bp.NKT;
-            // 1. tables, forward recompute up to the pre-floor pooled value
-            hipLaunchKernelGGL(fused_prep_kernel, dim3(ceil_div(pl.R * 2 * pl.FP + pl.FP * pl.GJ, 256)), dim3(256), 0, st,
-                               kernel, pool_w, F, pl.FP, K, pl.R, pl.GJ, gabor_bounds(K), W, G, Gs, perm, col_of, tile_ks);
-            LEAF_LAUNCH_CHECK();
-            FusedParams prm = base_fused_params(pl, B, T, F, K, hop, -1);
-            prm.x = x; prm.W = W; prm.G = G; prm.tile_ks = tile_ks; prm.part = part;
-            const float* raw_in = pooled_raw;          // saved by leaf_forward_save_f32, else recomputed here
-            if (!raw_in) {
-                if (launch_fused_groups(prm, pl, st) != hipSuccess) return LEAF_ERR_LAUNCH;
-                hipLaunchKernelGGL(finalize_kernel, dim3(B, ceil_div(F, kFinGroup)), dim3(kFinGroup * 64), (size_t)kFinGroup * (kFinStride + 3) * 4, st, part, F, pl.FP, TP,
-                                   pl.noff, pl.q_lo, pl.q_hi, SlotGeom{}, col_of, pool_b, alpha, delta, root, ema_w, 1e-12f, 8, raw,
-                                   (float*)nullptr);
-                LEAF_LAUNCH_CHECK();
-                raw_in = raw;
-            }
-            // 2. floor + PCEN backward per (b,f) row
-            if (hipMemsetAsync(gcols, 0, (size_t)B * TP * pl.FP * 4, st) != hipSuccess) return LEAF_ERR_LAUNCH;
-            hipLaunchKernelGGL(pcen_bwd_scan_kernel, dim3(ceil_div(B * F, 4)), dim3(256), 0, st, raw_in, grad_out, B * F, F, TP,
-                               alpha, delta, root, ema_w, 1e-12f, mode, ema, gpre, rowsum, col_of, pl.FP, gcols);
-            LEAF_LAUNCH_CHECK();
-            // 3. filterbank recompute with the backward epilogue: dY (time-major) and d pool_w partials
-            if (hipMemsetAsync(dwpart, 0, (size_t)cus * kWavesPerWG * pl.FP * 4, st) != hipSuccess) return LEAF_ERR_LAUNCH;
-            if (hipMemsetAsync(dHpart, 0, (size_t)cus * Rp * 2 * pl.FP * 4, st) != hipSuccess) return LEAF_ERR_LAUNCH;
-            prm.Gs = Gs; prm.gcols = gcols; prm.dY = dY; prm.dwpart = dwpart; prm.part = nullptr;
-            if (launch_fused_groups(prm, pl, st) != hipSuccess) return LEAF_ERR_LAUNCH;
-            // 4. tap gradients: dH = S^T dY on the MFMA, then chain to (mu, sigma)
-            DtapsParams dp{};
-            dp.x = x; dp.dY = dY; dp.tile_ks = tile_ks; dp.dHpart = dHpart;
-            dp.B = B; dp.T = T; dp.FP = pl.FP; dp.K = K; dp.Hf = pl.Hf; dp.xshift = pl.xshift;
-            dp.NKT = bp.NKT; dp.NW = bp.NW; dp.NS = bp.NS; dp.HPc = bp.HPc; dp.XSC = bp.XSC; dp.LD = bp.LD;
-            dp.nch = bp.nch; dp.total_chunks = B * bp.nch;
-            if (pl.groups_main > 0) {
-                dp.tile_base = 0;
-                const int gx = std::max(1, std::min(dp.total_chunks, std::max(1, cus / pl.groups_main)));
-                if (launch_dtaps(dp, pl.rt_main, bp.TPW, pl.groups_main, bp.lds, gx, st) != hipSuccess) return LEAF_ERR_LAUNCH;
-            }
-            if (pl.rt_rem > 0) {
-                dp.tile_base = pl.groups_main * pl.rt_main;
-                const int gx = std::max(1, std::min(dp.total_chunks, cus));
-                if (launch_dtaps(dp, pl.rt_rem, bp.TPW, 1, bp.lds, gx, st) != hipSuccess) return LEAF_ERR_LAUNCH;
-            }
-            {
-                // slab 0 doubles as the reduction target: reduce slabs 1.. into a scratch slab placed after the last one
-                const size_t slab = (size_t)Rp * 2 * pl.FP;
-                float* dHsum = dHpart + (size_t)cus * slab;
-                hipLaunchKernelGGL(dh_reduce_kernel, dim3((unsigned)((slab + 255) / 256)), dim3(256), 0, st, dHpart, cus, slab,
-                                   dHsum);
-                LEAF_LAUNCH_CHECK();
-                hipLaunchKernelGGL(dkernel_fused_kernel, dim3(F), dim3(256), 0, st, dHsum, 1, Rp, W, pl.R, pl.FP, col_of,
-                                   kernel, F, gabor_bounds(K), g_kernel);
-            }
-            LEAF_LAUNCH_CHECK();
-            // 5. parameter sums over the batch
-            hipLaunchKernelGGL(param_reduce_kernel, dim3(F), dim3(kParamRedThreads), 0, st, gpre, (const float*)nullptr,
-                               (const float*)nullptr, rowsum, pool_w, B, F, TP, K, mode, dwpart, cus * kWavesPerWG, pl.FP,
-                               col_of, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w);
-            LEAF_LAUNCH_CHECK();
-            return LEAF_OK;
-        }
+    if (pl.rt_rem > 0) {
+        dp.tile_base = pl.groups_main * pl.rt_main;
+        if (launch_dtaps(dp, pl.rt_rem, bp.TPW, 1, bp.lds, cu_grid(dp.total_chunks, cus), a.st) != hipSuccess) return LEAF_ERR_LAUNCH;
     }
+    // slab 0 doubles as the reduction target: reduce slabs 1.. into a scratch slab placed after the last one
+    const size_t slab = (size_t)Rp * 2 * pl.FP;
+    float* dHsum = dHpart + (size_t)cus * slab;
+    hipLaunchKernelGGL(dh_reduce_kernel, dim3((unsigned)((slab + 255) / 256)), dim3(256), 0, a.st, dHpart, cus, slab, dHsum);
+    LEAF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dkernel_fused_kernel, dim3(F), dim3(256), 0, a.st, dHsum, 1, Rp, t.W, pl.R, pl.FP, t.col_of,
+                       a.kernel, F, gabor_bounds(K), io.g_kernel);
+    LEAF_LAUNCH_CHECK();
+    // 5. parameter sums over the batch
+    hipLaunchKernelGGL(param_reduce_kernel, dim3(F), dim3(kParamRedThreads), 0, a.st, gpre, (const float*)nullptr,
+                       (const float*)nullptr, rowsum, a.pool_w, B, F, TP, K, io.mode, dwpart, cus * kWavesPerWG, pl.FP,
+                       t.col_of, io.g_pool_w, io.g_pool_b, io.g_alpha, io.g_delta, io.g_root, io.g_ema_w);
+    LEAF_LAUNCH_CHECK();
+    return LEAF_OK;
+}
+
+// ---- staged backward: the reference graph's kernels, every intermediate in the workspace; the fallback, and dL/dx for the
+// geometries nothing else covers
+static int backward_staged(const LeafArgs& a, const BwdIo& io, float* ws) {
+    const auto [B, T, F, K, hop] = a.s;
+    hipStream_t st = a.st;
+    const int TP = (T - 1) / hop + 1;
+    const int padL = K / 2 + K % 2 - 1;
     float* taps = ws;                         ws += align_up((size_t)2 * F * K, 64) * 2;
     float* g = ws;                            ws += align_up((size_t)F * K, 64);
     float* dg = ws;                           ws += align_up((size_t)F * K, 64);
@@ -2285,35 +2303,102 @@ static int backward_impl(const float* x, const int* mix_perm, const float* mix_l
     float* rowsum = ws;                       ws += align_up((size_t)B * F * 4, 64);
     float* tpart = ws;
     // forward recompute (staged kernels = the reference graph)
-    rc = leaf_gabor_conv_f32(x, B, T, kernel, F, K, y, taps, (size_t)2 * F * K * 4, stream);
+    int rc = leaf_gabor_conv_f32(io.x, B, T, a.kernel, F, K, y, taps, (size_t)2 * F * K * 4, a.st);
     if (rc != LEAF_OK) return rc;
-    rc = leaf_squared_modulus_f32(y, B, F, T, e, stream);
+    rc = leaf_squared_modulus_f32(y, B, F, T, e, a.st);
     if (rc != LEAF_OK) return rc;
-    rc = leaf_gaussian_lowpass_f32(e, B, F, T, pool_w, pool_b, K, hop, raw, g, (size_t)F * K * 4, stream);
+    rc = leaf_gaussian_lowpass_f32(e, B, F, T, a.pool_w, a.pool_b, K, hop, raw, g, (size_t)F * K * 4, a.st);
     if (rc != LEAF_OK) return rc;
     // PCEN + floor backward
-    hipLaunchKernelGGL(pcen_bwd_scan_kernel, dim3(ceil_div(B * F, 4)), dim3(256), 0, st, raw, grad_out, B * F, F, TP, alpha,
-                       delta, root, ema_w, 1e-12f, mode, ema, gpre, rowsum, (const int*)nullptr, 0, (float*)nullptr);
+    hipLaunchKernelGGL(pcen_bwd_scan_kernel, dim3(ceil_div(B * F, 4)), dim3(256), 0, st, raw, io.grad_out, B * F, F, TP, a.alpha,
+                       a.delta, a.root, a.ema_w, 1e-12f, io.mode, ema, gpre, rowsum, (const int*)nullptr, 0, (float*)nullptr);
     LEAF_LAUNCH_CHECK();
     // pooling backward: window gradient needs e, sample gradient turns y into dy in place
     hipLaunchKernelGGL(pool_bwd_dg_kernel, dim3(ceil_div(K, 128), F), dim3(128), 0, st, e, gpre, B, F, T, TP, K, hop, padL, dg);
     LEAF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(param_reduce_kernel, dim3(F), dim3(kParamRedThreads), 0, st, gpre, dg, g, rowsum, pool_w, B, F, TP, K, mode,
-                       (const float*)nullptr, 0, 0, (const int*)nullptr, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w);
+    hipLaunchKernelGGL(param_reduce_kernel, dim3(F), dim3(kParamRedThreads), 0, st, gpre, dg, g, rowsum, a.pool_w, B, F, TP, K, io.mode,
+                       (const float*)nullptr, 0, 0, (const int*)nullptr, io.g_pool_w, io.g_pool_b, io.g_alpha, io.g_delta, io.g_root, io.g_ema_w);
     LEAF_LAUNCH_CHECK();
     hipLaunchKernelGGL(pool_bwd_dy_kernel, dim3(ceil_div(T, 256), F, B), dim3(256), 0, st, y, g, gpre, F, T, TP, K, hop, padL);
     LEAF_LAUNCH_CHECK();
     // filterbank backward
-    hipLaunchKernelGGL(dtaps_partial_kernel, dim3(ceil_div(K, 128), 2 * F, B), dim3(128), 0, st, y, x, T, 2 * F, K, padL,
+    hipLaunchKernelGGL(dtaps_partial_kernel, dim3(ceil_div(K, 128), 2 * F, B), dim3(128), 0, st, y, io.x, T, 2 * F, K, padL,
                        tpart);
     LEAF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dkernel_kernel, dim3(F), dim3(256), 0, st, tpart, taps, kernel, B, F, K, gabor_bounds(K), g_kernel);
+    hipLaunchKernelGGL(dkernel_kernel, dim3(F), dim3(256), 0, st, tpart, taps, a.kernel, B, F, K, gabor_bounds(K), io.g_kernel);
     LEAF_LAUNCH_CHECK();
-    if (g_x) {
-        hipLaunchKernelGGL(dx_kernel, dim3(ceil_div(T, 256), B), dim3(256), 0, st, y, taps, T, 2 * F, K, padL, g_x, io_bf16 ? 1 : 0);
+    if (io.g_x) {
+        hipLaunchKernelGGL(dx_kernel, dim3(ceil_div(T, 256), B), dim3(256), 0, st, y, taps, T, 2 * F, K, padL, io.g_x, io.gx_bf16 ? 1 : 0);
         LEAF_LAUNCH_CHECK();
     }
     return LEAF_OK;
+}
+
+// checks in the order the ABI documents, the mixed / widened copy of the waveform where the path's kernels need one, then one
+// function per path.  io.x arrives as the caller's buffer; ctx.mix.lam != NULL: the mixed call (leaf_backward_mix_f32 has refused
+// bfloat16, PEAKNORM, g_x and a missing buffer)
+static int backward_impl(CallCtx ctx, const LeafArgs& a, int flags, BwdIo io, void* workspace, size_t workspace_bytes) {
+    const auto [B, T, F, K, hop] = a.s;
+    // LEAF_FLAG_IO_BF16: x, grad_out and g_x are bfloat16 buffers behind the float pointers (as in the forward); everything else fp32
+    // LEAF_FLAG_X_PCM16: x alone is a 16-bit PCM buffer (v / 32768); an integer input has no gradient, so g_x must be NULL
+    // LEAF_FLAG_OUT_BF16: grad_out alone is bfloat16 (the feature side); x and g_x follow the two flags above
+    if ((flags & LEAF_FLAG_X_PCM16) && ((flags & LEAF_FLAG_IO_BF16) || io.g_x)) return LEAF_ERR_UNSUPPORTED;
+    const bool mixed_call = ctx.mix.lam != nullptr, need_dx = io.g_x != nullptr;
+    const bool use_pcen = (flags & LEAF_FLAG_PCEN) != 0;
+    if (empty_batch(B, T, F, K, hop)) {
+        // the sum over zero clips: every parameter gradient is exactly zero (what autograd returns for the reference)
+        if (!io.g_kernel || !io.g_pool_w || !io.g_pool_b) return LEAF_ERR_NULL_POINTER;
+        if (use_pcen && (!io.g_alpha || !io.g_delta || !io.g_root || !io.g_ema_w)) return LEAF_ERR_NULL_POINTER;
+        bool ok = hipMemsetAsync(io.g_kernel, 0, (size_t)2 * F * 4, a.st) == hipSuccess;
+        ok = ok && hipMemsetAsync(io.g_pool_w, 0, (size_t)F * 4, a.st) == hipSuccess;
+        ok = ok && hipMemsetAsync(io.g_pool_b, 0, (size_t)F * 4, a.st) == hipSuccess;
+        if (use_pcen)
+            for (float* g : {io.g_alpha, io.g_delta, io.g_root, io.g_ema_w}) ok = ok && hipMemsetAsync(g, 0, (size_t)F * 4, a.st) == hipSuccess;
+        return ok ? LEAF_OK : LEAF_ERR_LAUNCH;
+    }
+    if (!io.x || !a.kernel || !a.pool_w || !a.pool_b || !io.grad_out || !io.g_kernel || !io.g_pool_w || !io.g_pool_b) return LEAF_ERR_NULL_POINTER;
+    if (use_pcen && (!a.alpha || !a.delta || !a.root || !a.ema_w || !io.g_alpha || !io.g_delta || !io.g_root || !io.g_ema_w))
+        return LEAF_ERR_NULL_POINTER;
+    int rc = check_shape(B, T, F, K, hop);
+    if (rc != LEAF_OK) return rc;
+    if (2 * F > 65535 || B > 65535) return LEAF_ERR_BAD_SHAPE;
+    io.gx_bf16 = (flags & LEAF_FLAG_IO_BF16) != 0;           // the waveform side: x and g_x
+    const bool go_bf16 = feat_bf16(flags);                   // the feature side: grad_out
+    {
+        const uintptr_t io_mask = io.gx_bf16 ? 1u : 3u;
+        const uintptr_t x_mask = (flags & LEAF_FLAG_X_PCM16) ? 1u : io_mask;
+        if ((reinterpret_cast<uintptr_t>(io.x) & x_mask) || (reinterpret_cast<uintptr_t>(io.grad_out) & (go_bf16 ? 1u : 3u)) ||
+            (reinterpret_cast<uintptr_t>(io.g_x) & io_mask) || misaligned16(workspace) ||
+            any_misaligned(a.kernel, a.pool_w, a.pool_b, a.alpha, a.delta, a.root, a.ema_w, io.pooled_raw, io.g_kernel, io.g_pool_w, io.g_pool_b,
+                           io.g_alpha, io.g_delta, io.g_root, io.g_ema_w) || any_misaligned(ctx.mix.perm, ctx.mix.lam))
+            return LEAF_ERR_ALIGNMENT;
+    }
+    const BwdPath path = bwd_path(a.s, flags, need_dx, ctx.cus);
+    const size_t own = bwd_own_workspace_floats(path, a.s, need_dx, ctx.cus);
+    const size_t copy = mixed_call ? bwd_mix_floats(path, a.s, ctx.cus) : bwd_x32_floats(path, a.s, flags);
+    if (!workspace || workspace_bytes < (own + copy) * 4) return LEAF_ERR_WORKSPACE;
+    io.mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (go_bf16 ? 4 : 0);
+    io.xtype = x_sample_type(flags);                         // what the kernels below read x as
+    float* ws = static_cast<float*>(workspace);
+    if (mixed_call && copy) {
+        // this path's kernels do not mix in their loads: the mixed fp32 copy behind the path's own layout, then the unmixed call on it
+        rc = launch_mixup(io.x, io.xtype, B, T, ctx.mix.perm, ctx.mix.lam, ws + own, a.st);
+        if (rc != LEAF_OK) return rc;
+        io.x = ws + own; io.xtype = kSampleF32; ctx.mix = MixArgs{nullptr, nullptr};
+    } else if (copy) {
+        // these families read fp32: one widening pass into the workspace's tail, then the fp32 path
+        const size_t n = (size_t)B * T;
+        hipLaunchKernelGGL(x16_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, a.st,
+                           reinterpret_cast<const unsigned short*>(io.x), io.xtype, n, ws + own);
+        LEAF_LAUNCH_CHECK();
+        io.x = ws + own; io.xtype = kSampleF32;
+    }
+    switch (path) {
+        case BWD_PATH_FFT4K: return backward_4k(ctx, a, io, ws);
+        case BWD_PATH_FFT: return backward_fft(ctx, a, io, ws);
+        case BWD_PATH_MFMA: return backward_mfma(ctx, a, io, ws);
+        default: return backward_staged(a, io, ws);
+    }
 }
 
 int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
@@ -2321,9 +2406,10 @@ int leaf_backward_f32(const float* x, int B, int T, const float* kernel, const f
                       int flags, const float* grad_out, const float* pooled_raw, float* g_kernel, float* g_pool_w,
                       float* g_pool_b, float* g_alpha, float* g_delta, float* g_root, float* g_ema_w, float* g_x,
                       void* workspace, size_t workspace_bytes, void* stream) {
-    return backward_impl(x, nullptr, nullptr, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K, hop, flags, grad_out,
-                         pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w, g_x, workspace, workspace_bytes,
-                         stream);
+    return backward_impl(backward_ctx(flags, MixArgs{nullptr, nullptr}),
+                         LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream}, flags,
+                         BwdIo{x, 0, grad_out, pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w, g_x, 0, false},
+                         workspace, workspace_bytes);
 }
 
 int leaf_backward_mix_f32(const void* x, const int* mix_perm, const float* mix_lam, int B, int T, const float* kernel,
@@ -2333,9 +2419,10 @@ int leaf_backward_mix_f32(const void* x, const int* mix_perm, const float* mix_l
                           float* g_ema_w, float* g_x, void* workspace, size_t workspace_bytes, void* stream) {
     if (g_x || (flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_PEAKNORM))) return LEAF_ERR_UNSUPPORTED;   // dL/dx under mixup is a scatter over perm: not built
     if (B != 0 && (!mix_perm || !mix_lam)) return LEAF_ERR_NULL_POINTER;
-    return backward_impl(static_cast<const float*>(x), mix_perm, mix_lam, B, T, kernel, pool_w, pool_b, alpha, delta, root, ema_w, F, K,
-                         hop, flags, grad_out, pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w, g_x,
-                         workspace, workspace_bytes, stream);
+    return backward_impl(backward_ctx(flags, MixArgs{mix_perm, mix_lam}),
+                         LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream}, flags,
+                         BwdIo{static_cast<const float*>(x), 0, grad_out, pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w, g_x, 0, false},
+                         workspace, workspace_bytes);
 }
 
 }  // extern "C"

@@ -74,166 +74,181 @@ Params gather(const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b, 
     return p;
 }
 
+// ---- One forward and one backward serve the plain ops and the waveform-mixup ops (leaf_hip.h: the *_mix_* entries), which are the same
+// code with (perm, lam) present: the ops on x * lam + x[perm] * (1 - lam), the mix done inside the kernels' loads where the family
+// has one.  What a mixed call does differently: x float32 or int16 PCM only (no bfloat16 waveform); perm int32 [B] and lam float32 [B]
+// on x's device (the Python layer converts and validates, leaf_pytorch_amd/_native.py: mix_args); ONE C-ABI call -- a mixed batch
+// cannot be sliced (a clip's partner may sit in another slice), so B * T >= 2^31 is refused; no g_x.
+struct Mix { const Tensor& perm; const Tensor& lam; };
+struct Call {
+    Tensor x2, perm, lam;          // perm / lam: defined for a mixed call only
+    bool mixed, io_bf16, pcm16;
+    int64_t B;
+    int T, F, TP;
+};
+Call make_call(const Tensor& x, const Mix* mix, const Params& p, int64_t K, int64_t hop, bool check_frames) {
+    Call c;
+    c.x2 = waveform_2d(x);
+    c.mixed = mix != nullptr;
+    c.io_bf16 = c.x2.scalar_type() == at::kBFloat16;
+    c.pcm16 = c.x2.scalar_type() == at::kShort;                // 16-bit PCM in (a sample v means v / 32768), float32 out
+    c.B = c.x2.size(0);
+    if (mix) {
+        TORCH_CHECK(c.x2.scalar_type() == at::kFloat || c.pcm16,
+                    "mixup is defined in float32 on a float32 or int16 (PCM) waveform, got ", c.x2.scalar_type());
+        TORCH_CHECK(c.x2.size(1) < (int64_t(1) << 31) && c.B * c.x2.size(1) < (int64_t(1) << 31),
+                    "a mixed batch goes through one C-ABI call: B * T must stay below 2^31, got ", c.B, " x ", c.x2.size(1));
+    } else {
+        TORCH_CHECK(c.io_bf16 || c.pcm16 || c.x2.scalar_type() == at::kFloat,
+                    "x must be float32 (or bfloat16 for the bf16-I/O extension, or int16 PCM), got ", c.x2.scalar_type());
+        TORCH_CHECK(c.x2.size(1) < (int64_t(1) << 31), "a clip of ", c.x2.size(1), " samples is beyond the C ABI's 32-bit sample index");
+    }
+    c.T = (int)c.x2.size(1); c.F = (int)p.kernel.size(0);
+    c.TP = leaf_num_frames(c.T, (int)K, (int)hop);
+    if (check_frames) TORCH_CHECK(c.TP >= 1 && c.F >= 1, "bad shape B=", c.B, " T=", c.T, " F=", c.F, " K=", K, " hop=", hop);
+    if (mix) {
+        TORCH_CHECK(mix->perm.device() == c.x2.device() && mix->perm.scalar_type() == at::kInt && mix->perm.numel() == c.B,
+                    "perm must be int32 with one entry per clip on ", c.x2.device());
+        c.perm = mix->perm.reshape({-1}).contiguous();
+        c.lam = dev_f32(mix->lam.reshape({-1}), "lam", c.x2.device());
+        TORCH_CHECK(c.lam.numel() == c.B, "lam must have one entry per clip");
+    }
+    return c;
+}
+// Slices of the batch, one C-ABI call each.  The C ABI indexes the samples of ONE call with 32 bits and refuses B * T >= 2^31
+// (LEAF_ERR_BAD_SHAPE); the reference's conv1d takes any batch (frontend.py:78-89).  Clips are independent, so a larger batch goes
+// through in balanced slices of whole clips into the one preallocated output: the bits of a clip do not depend on its slice (within
+// one kernel family; the slices are far beyond every AUTO threshold).  A mixed batch is one slice (make_call has refused the rest).
+BatchSlices call_slices(const Call& c) { return c.mixed ? BatchSlices{c.B, 1} : batch_slices(c.B, c.T); }
+// element offset into a float32 / bfloat16 / int16 I/O tensor, as the C ABI's float pointer
+float* io_at(const Tensor& t, size_t elems) {
+    return reinterpret_cast<float*>(static_cast<char*>(t.data_ptr()) + elems * (size_t)t.element_size());
+}
+
 // out_bf16 (LEAF_FLAG_OUT_BF16): bfloat16 features from a float32 or int16 waveform, narrowed where the kernels store them; an explicit
 // argument of the ops, never inferred from a tensor (redundant for a bfloat16 x)
-Tensor forward_impl(const Tensor& x, const Params& p, int64_t K, int64_t hop, bool log1p, int64_t algo, Tensor* raw, bool out_bf16) {
-    Tensor x2 = waveform_2d(x);
-    const bool io_bf16 = x2.scalar_type() == at::kBFloat16;
-    out_bf16 = out_bf16 && !io_bf16;
-    const bool pcm16 = x2.scalar_type() == at::kShort;        // 16-bit PCM in (a sample v means v / 32768), float32 out
-    TORCH_CHECK(io_bf16 || pcm16 || x2.scalar_type() == at::kFloat,
-                "x must be float32 (or bfloat16 for the bf16-I/O extension, or int16 PCM), got ", x2.scalar_type());
-    TORCH_CHECK(x2.size(1) < (int64_t(1) << 31), "a clip of ", x2.size(1), " samples is beyond the C ABI's 32-bit sample index");
-    const int64_t B = x2.size(0);
-    const int T = (int)x2.size(1), F = (int)p.kernel.size(0);
-    const int TP = leaf_num_frames(T, (int)K, (int)hop);
-    TORCH_CHECK(TP >= 1 && F >= 1, "bad shape B=", B, " T=", T, " F=", F, " K=", K, " hop=", hop);
-    const auto out_opt = x2.options().dtype(io_bf16 || out_bf16 ? at::kBFloat16 : at::kFloat);
-    if (B == 0) {
-        // the empty batch: the reference returns (0, F, T') (frontend.py:78-89 -> convolution.py:97); nothing is launched
-        if (raw) *raw = at::empty({0, F, TP}, x2.options().dtype(at::kFloat));
-        return at::empty({0, F, TP}, out_opt);
-    }
-    int flags = (io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (pcm16 ? LEAF_FLAG_X_PCM16 : 0) | (out_bf16 ? LEAF_FLAG_OUT_BF16 : 0) |
+Tensor forward_impl(const Tensor& x, const Mix* mix, const Params& p, int64_t K, int64_t hop, bool log1p, int64_t algo, Tensor* raw,
+                    bool out_bf16) {
+    const Call c = make_call(x, mix, p, K, hop, /*check_frames=*/true);
+    const int64_t B = c.B;
+    const int T = c.T, F = c.F, TP = c.TP;
+    out_bf16 = out_bf16 && !c.io_bf16;
+    const auto f32_opt = c.x2.options().dtype(at::kFloat);
+    const auto out_opt = f32_opt.dtype(c.io_bf16 || out_bf16 ? at::kBFloat16 : at::kFloat);
+    if (raw) *raw = at::empty({B, F, TP}, f32_opt);
+    // the empty batch: the reference returns (0, F, T') (frontend.py:78-89 -> convolution.py:97); nothing is launched
+    if (B == 0) return at::empty({0, F, TP}, out_opt);
+    int flags = (c.io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (c.pcm16 ? LEAF_FLAG_X_PCM16 : 0) | (out_bf16 ? LEAF_FLAG_OUT_BF16 : 0) |
                 (p.pcen ? LEAF_FLAG_PCEN : (log1p ? LEAF_FLAG_LOG1P : 0));
     // call options travelling in the upper bits of the op's `algo` argument (the schema stays as it is): bit 24 = the
-    // PeakNormalization prologue folded into the forward (LEAF_FLAG_PEAKNORM; inference only)
+    // PeakNormalization prologue folded into the forward (LEAF_FLAG_PEAKNORM; inference only, the plain ops only)
     constexpr int64_t kOptPeakNorm = int64_t(1) << 24;
-    if (algo & kOptPeakNorm) {
+    if (!c.mixed && (algo & kOptPeakNorm)) {
         TORCH_CHECK(!raw, "the fused PeakNormalization prologue is forward-only");
-        if (!pcm16) flags |= LEAF_FLAG_PEAKNORM;                // (|v / 32768| <= 1: nothing to normalise, nothing launched)
+        if (!c.pcm16) flags |= LEAF_FLAG_PEAKNORM;              // (|v / 32768| <= 1: nothing to normalise, nothing launched)
         algo &= ~kOptPeakNorm;
     }
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(x2.device());
-    auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x2.device().index());
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(c.x2.device());
+    auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(c.x2.device().index());
+    const BatchSlices sl = call_slices(c);
+    const int last = (int)(B - (sl.calls - 1) * sl.per_call);
     bool pcm16_staged = false, bf16_staged = false;
-    if (pcm16 || out_bf16) {
+    if (c.pcm16 || out_bf16) {
         // the staged forward reads and writes float32 only (LEAF_ERR_UNSUPPORTED from the C ABI): where the call lands on it, each
-        // slice of an int16 batch is converted below -- the same values, v / 32768 exactly -- and bfloat16 features are narrowed
-        // from its float32 result at the end (the same rounding, the same bits)
+        // slice of an int16 batch is converted below -- the same values, v / 32768 exactly (a mixed call: mixup_kernel widens) -- and
+        // bfloat16 features are narrowed from its float32 result at the end (the same rounding, the same bits)
         int sel = (int)(algo & 0xff);
-        if (sel == LEAF_ALGO_AUTO) sel = leaf_auto_algo((int)std::min<int64_t>(B, batch_slices(B, T).per_call), T, F, (int)K, (int)hop);
-        pcm16_staged = pcm16 && sel == LEAF_ALGO_STAGED;
+        if (sel == LEAF_ALGO_AUTO) sel = leaf_auto_algo((int)std::min<int64_t>(B, sl.per_call), T, F, (int)K, (int)hop);
+        pcm16_staged = c.pcm16 && !c.mixed && sel == LEAF_ALGO_STAGED;
         bf16_staged = out_bf16 && sel == LEAF_ALGO_STAGED;
         if (pcm16_staged) flags &= ~LEAF_FLAG_X_PCM16;
         if (bf16_staged) flags &= ~LEAF_FLAG_OUT_BF16;
     }
-    const bool x16 = (flags & LEAF_FLAG_X_PCM16) != 0;
-    Tensor out = at::empty({B, F, TP}, bf16_staged ? out_opt.dtype(at::kFloat) : out_opt);
-    if (raw) *raw = at::empty({B, F, TP}, x2.options().dtype(at::kFloat));
-    // The C ABI indexes the samples of ONE call with 32 bits and refuses B * T >= 2^31 (LEAF_ERR_BAD_SHAPE); the reference's
-    // conv1d takes any batch (frontend.py:78-89).  Clips are independent, so a larger batch goes through in balanced slices of
-    // whole clips, one C-ABI call each, into the one preallocated output: the bits of a clip do not depend on its slice (within
-    // one kernel family; the slices are far beyond every AUTO threshold).  One workspace, sized for the largest slice, serves
-    // the stream-ordered calls in turn.
-    const BatchSlices sl = batch_slices(B, T);
-    const int last = (int)(B - (sl.calls - 1) * sl.per_call);
-    Tensor ws = at::empty({(int64_t)std::max<size_t>({leaf_workspace_bytes((int)sl.per_call, T, F, (int)K, (int)hop, (int)algo),
-                                                      leaf_workspace_bytes(last, T, F, (int)K, (int)hop, (int)algo), size_t(4)})},
-                          x2.options().dtype(at::kByte));
-    const size_t io = (size_t)out.element_size(), xio = x16 || io_bf16 ? 2 : 4;
+    Tensor out = at::empty({B, F, TP}, bf16_staged ? f32_opt : out_opt);
+    // One workspace, sized for the largest slice, serves the stream-ordered calls in turn.
+    auto ws_bytes = [&](int nb) {
+        return c.mixed ? leaf_forward_mix_workspace_bytes(nb, T, F, (int)K, (int)hop, (int)algo) : leaf_workspace_bytes(nb, T, F, (int)K, (int)hop, (int)algo);
+    };
+    Tensor ws = at::empty({(int64_t)std::max<size_t>({ws_bytes((int)sl.per_call), ws_bytes(last), size_t(4)})}, f32_opt.dtype(at::kByte));
+    void* wsp = ws.data_ptr();
+    const size_t wsn = (size_t)ws.numel();
+    const float *pk = fptr(p.kernel), *pw = fptr(p.pool_w), *pb = fptr(p.pool_b), *pa = fptr(p.alpha), *pd = fptr(p.delta), *pr = fptr(p.root),
+                *pe = fptr(p.ema_w);
     for (int64_t b0 = 0; b0 < B; b0 += sl.per_call) {
         const int nb = (int)std::min<int64_t>(sl.per_call, B - b0);
         Tensor xs;                                              // one slice of an int16 batch as float32, for the staged forward
-        if (pcm16_staged) xs = x2.narrow(0, b0, nb).to(at::kFloat).mul_(1.0 / 32768.0);
-        const float* xin = pcm16_staged ? xs.data_ptr<float>()
-                                        : reinterpret_cast<const float*>(static_cast<const char*>(x2.data_ptr()) + (size_t)b0 * T * xio);
-        float* o = reinterpret_cast<float*>(static_cast<char*>(out.data_ptr()) + (size_t)b0 * F * TP * io);
-        int rc;
-        if (raw) {
-            rc = leaf_forward_save_f32(xin, nb, T, fptr(p.kernel), fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha), fptr(p.delta),
-                                       fptr(p.root), fptr(p.ema_w), F, (int)K, (int)hop, flags, (int)algo, o,
-                                       raw->data_ptr<float>() + (size_t)b0 * F * TP, ws.data_ptr(), (size_t)ws.numel(), stream.stream());
-            check_status(rc, "leaf_forward_save_f32");
-        } else {
-            rc = leaf_forward_f32(xin, nb, T, fptr(p.kernel), fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha), fptr(p.delta),
-                                  fptr(p.root), fptr(p.ema_w), F, (int)K, (int)hop, flags, (int)algo, o, ws.data_ptr(),
-                                  (size_t)ws.numel(), stream.stream());
-            check_status(rc, "leaf_forward_f32");
-        }
+        if (pcm16_staged) xs = c.x2.narrow(0, b0, nb).to(at::kFloat).mul_(1.0 / 32768.0);
+        const float* xin = pcm16_staged ? xs.data_ptr<float>() : io_at(c.x2, (size_t)b0 * T);
+        float* o = io_at(out, (size_t)b0 * F * TP);
+        float* r = raw ? raw->data_ptr<float>() + (size_t)b0 * F * TP : nullptr;
+        if (c.mixed && raw)
+            check_status(leaf_forward_save_mix_f32(xin, c.perm.data_ptr<int>(), fptr(c.lam), nb, T, pk, pw, pb, pa, pd, pr, pe, F, (int)K, (int)hop,
+                                                   flags, (int)algo, o, r, wsp, wsn, stream.stream()), "leaf_forward_save_mix_f32");
+        else if (c.mixed)
+            check_status(leaf_forward_mix_f32(xin, c.perm.data_ptr<int>(), fptr(c.lam), nb, T, pk, pw, pb, pa, pd, pr, pe, F, (int)K, (int)hop,
+                                              flags, (int)algo, o, wsp, wsn, stream.stream()), "leaf_forward_mix_f32");
+        else if (raw)
+            check_status(leaf_forward_save_f32(xin, nb, T, pk, pw, pb, pa, pd, pr, pe, F, (int)K, (int)hop, flags, (int)algo, o, r, wsp, wsn,
+                                               stream.stream()), "leaf_forward_save_f32");
+        else
+            check_status(leaf_forward_f32(xin, nb, T, pk, pw, pb, pa, pd, pr, pe, F, (int)K, (int)hop, flags, (int)algo, o, wsp, wsn,
+                                          stream.stream()), "leaf_forward_f32");
     }
     return bf16_staged ? out.to(at::kBFloat16) : out;
 }
 
-// leaf_amd::forward -- frontend.py:78-89 (inference / no-grad)
-Tensor op_forward(const Tensor& x, const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b, const OptTensor& alpha,
-                  const OptTensor& delta, const OptTensor& root, const OptTensor& ema_w, int64_t K, int64_t hop, bool log1p,
-                  int64_t algo, bool out_bf16) {
-    const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
-    return forward_impl(x, p, K, hop, log1p, algo, nullptr, out_bf16);
-}
-
-// leaf_amd::forward_train -- the same, additionally returning the pre-floor pooled tensor the backward consumes
-std::tuple<Tensor, Tensor> op_forward_train(const Tensor& x, const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b,
-                                            const OptTensor& alpha, const OptTensor& delta, const OptTensor& root,
-                                            const OptTensor& ema_w, int64_t K, int64_t hop, int64_t algo, bool log1p,
-                                            bool out_bf16) {
-    const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
-    Tensor raw;
-    Tensor out = forward_impl(x, p, K, hop, log1p, algo, &raw, out_bf16);
-    return {out, raw};
-}
-
-// leaf_amd::backward -- what autograd derives for frontend.py:78-89: (g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root,
-// g_ema_w, g_x); the PCEN entries are empty tensors without PCEN, g_x is empty unless need_dx.  `flags` are C-ABI flags
-// (LEAF_FLAG_BWD_*, and LEAF_FLAG_LOG1P for the backward of the log1p-compressed forward); LEAF_FLAG_PCEN and
+// What autograd derives for frontend.py:78-89: (g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w[, g_x]); the PCEN
+// entries are empty tensors without PCEN; the plain op appends g_x (empty unless need_dx), a mixed call has none.  `flags` are C-ABI
+// flags (LEAF_FLAG_BWD_*, and LEAF_FLAG_LOG1P for the backward of the log1p-compressed forward); LEAF_FLAG_PCEN and
 // LEAF_FLAG_IO_BF16 / LEAF_FLAG_X_PCM16 follow from the tensors.  bfloat16 x: grad_out is bfloat16 too, g_x comes back in
 // bfloat16, the parameter gradients and pooled_raw are float32.  int16 x (PCM): grad_out float32, need_dx refused.
 // out_bf16 (LEAF_FLAG_OUT_BF16): grad_out alone is bfloat16, for a float32 (g_x float32) or int16 x.
-std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Tensor& pool_w, const Tensor& pool_b,
-                                const OptTensor& alpha, const OptTensor& delta, const OptTensor& root, const OptTensor& ema_w,
-                                int64_t K, int64_t hop, const Tensor& grad_out, const OptTensor& pooled_raw, bool need_dx,
-                                int64_t flags, bool out_bf16) {
-    Tensor x2 = waveform_2d(x);
-    const bool io_bf16 = x2.scalar_type() == at::kBFloat16;
-    out_bf16 = out_bf16 && !io_bf16;
-    const bool pcm16 = x2.scalar_type() == at::kShort;
-    TORCH_CHECK(io_bf16 || pcm16 || x2.scalar_type() == at::kFloat,
-                "x must be float32 (or bfloat16 for the bf16-I/O extension, or int16 PCM), got ", x2.scalar_type());
-    TORCH_CHECK(!(pcm16 && need_dx), "an int16 (PCM) input has no gradient: need_dx needs a float32 or bfloat16 x");
-    const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
-    TORCH_CHECK(x2.size(1) < (int64_t(1) << 31), "a clip of ", x2.size(1), " samples is beyond the C ABI's 32-bit sample index");
-    const int64_t B = x2.size(0);
-    const int T = (int)x2.size(1), F = (int)p.kernel.size(0);
-    const int TP = leaf_num_frames(T, (int)K, (int)hop);
+std::vector<Tensor> backward_impl(const Tensor& x, const Mix* mix, const Params& p, const Tensor& pool_w, int64_t K, int64_t hop,
+                                  const Tensor& grad_out, const OptTensor& pooled_raw, bool need_dx, int64_t flags, bool out_bf16) {
+    const Call c = make_call(x, mix, p, K, hop, /*check_frames=*/mix != nullptr);
+    TORCH_CHECK(!(c.pcm16 && need_dx), "an int16 (PCM) input has no gradient: need_dx needs a float32 or bfloat16 x");
+    const int64_t B = c.B;
+    const int T = c.T, F = c.F, TP = c.TP;
+    out_bf16 = out_bf16 && !c.io_bf16;
     Tensor go;
-    if (io_bf16) {
-        TORCH_CHECK(grad_out.device() == x2.device(), "grad_out is on ", grad_out.device(), ", expected ", x2.device());
-        TORCH_CHECK(grad_out.scalar_type() == at::kBFloat16, "grad_out must be bfloat16 when x is bfloat16, got ", grad_out.scalar_type());
-        go = grad_out.contiguous();
-    } else if (out_bf16) {
-        TORCH_CHECK(grad_out.device() == x2.device(), "grad_out is on ", grad_out.device(), ", expected ", x2.device());
-        TORCH_CHECK(grad_out.scalar_type() == at::kBFloat16, "grad_out must be bfloat16 with out_bf16=True, got ", grad_out.scalar_type());
+    if (c.io_bf16 || out_bf16) {                              // a bfloat16 grad_out goes straight in: widened where the kernels read it
+        TORCH_CHECK(grad_out.device() == c.x2.device(), "grad_out is on ", grad_out.device(), ", expected ", c.x2.device());
+        TORCH_CHECK(grad_out.scalar_type() == at::kBFloat16, c.io_bf16 ? "grad_out must be bfloat16 when x is bfloat16, got " : "grad_out must be bfloat16 with out_bf16=True, got ",
+                    grad_out.scalar_type());
         go = grad_out.contiguous();
     } else {
-        go = dev_f32(grad_out, "grad_out", x2.device());
+        go = dev_f32(grad_out, "grad_out", c.x2.device());
     }
     TORCH_CHECK(go.dim() == 3 && go.size(0) == B && go.size(1) == F && go.size(2) == TP, "grad_out has shape ", go.sizes(),
                 ", expected (", B, ",", F, ",", TP, ")");
-    OptTensor raw = dev_f32(pooled_raw, "pooled_raw", x2.device());
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(x2.device());
-    auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(x2.device().index());
-    auto opt = x2.options().dtype(at::kFloat);                // parameter gradients are float32 whatever the I/O type
+    OptTensor raw = dev_f32(pooled_raw, "pooled_raw", c.x2.device());
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(c.x2.device());
+    auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(c.x2.device().index());
+    auto opt = c.x2.options().dtype(at::kFloat);              // parameter gradients are float32 whatever the I/O type
     Tensor gk = at::empty_like(p.kernel), gpw = at::empty_like(p.pool_w), gpb = at::empty_like(p.pool_b);
     Tensor ga = at::empty({p.pcen ? F : 0}, opt), gd = at::empty({p.pcen ? F : 0}, opt), gr = at::empty({p.pcen ? F : 0}, opt),
            gw = at::empty({p.pcen ? F : 0}, opt);
-    Tensor gx = need_dx ? at::empty_like(x2) : at::empty({0}, opt);
+    Tensor gx = need_dx ? at::empty_like(c.x2) : at::empty({0}, opt);
+    auto result = [&]() {
+        std::vector<Tensor> g{gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw};
+        if (!c.mixed) g.push_back(need_dx ? gx.reshape(x.sizes()) : gx);
+        return g;
+    };
     if (B == 0) {                                             // the sum over no clips (C ABI: zero-fills, launches nothing else)
         for (Tensor* g : {&gk, &gpw, &gpb, &ga, &gd, &gr, &gw}) g->zero_();
-        return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw, need_dx ? gx.reshape(x.sizes()) : gx};
+        return result();
     }
     const int fl = ((int)flags & ~(LEAF_FLAG_PCEN | LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16 | LEAF_FLAG_OUT_BF16)) | (p.pcen ? LEAF_FLAG_PCEN : 0) |
-                   (io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (pcm16 ? LEAF_FLAG_X_PCM16 : 0) | (out_bf16 ? LEAF_FLAG_OUT_BF16 : 0);
-    auto io_at = [](const Tensor& t, size_t elems) {        // element offset into a float32 / bfloat16 / int16 I/O tensor, as the C ABI's float pointer
-        return reinterpret_cast<float*>(static_cast<char*>(t.data_ptr()) + elems * (size_t)t.element_size());
-    };
+                   (c.io_bf16 ? LEAF_FLAG_IO_BF16 : 0) | (c.pcm16 ? LEAF_FLAG_X_PCM16 : 0) | (out_bf16 ? LEAF_FLAG_OUT_BF16 : 0);
     // B * T >= 2^31: slices of whole clips as in the forward; the parameter gradients of the slices are added in slice order
     // (a fixed order: the step stays bit-reproducible), dL/dx is written slice by slice
-    const BatchSlices sl = batch_slices(B, T);
+    const BatchSlices sl = call_slices(c);
     const int last = (int)(B - (sl.calls - 1) * sl.per_call);
-    Tensor ws = at::empty({(int64_t)std::max<size_t>({leaf_backward_workspace_bytes((int)sl.per_call, T, F, (int)K, (int)hop, fl, need_dx ? 1 : 0),
-                                                      leaf_backward_workspace_bytes(last, T, F, (int)K, (int)hop, fl, need_dx ? 1 : 0), size_t(4)})},
-                          opt.dtype(at::kByte));
+    auto ws_bytes = [&](int nb) {
+        return c.mixed ? leaf_backward_mix_workspace_bytes(nb, T, F, (int)K, (int)hop, fl)
+                       : leaf_backward_workspace_bytes(nb, T, F, (int)K, (int)hop, fl, need_dx ? 1 : 0);
+    };
+    Tensor ws = at::empty({(int64_t)std::max<size_t>({ws_bytes((int)sl.per_call), ws_bytes(last), size_t(4)})}, opt.dtype(at::kByte));
     Tensor tk, tpw, tpb, ta, td, tr, tw;
     if (sl.calls > 1) {
         tk = at::empty_like(gk); tpw = at::empty_like(gpw); tpb = at::empty_like(gpb);
@@ -244,151 +259,66 @@ std::vector<Tensor> op_backward(const Tensor& x, const Tensor& kernel, const Ten
         const bool first = b0 == 0;
         Tensor &k_ = first ? gk : tk, &pw_ = first ? gpw : tpw, &pb_ = first ? gpb : tpb, &a_ = first ? ga : ta, &d_ = first ? gd : td,
                &r_ = first ? gr : tr, &w_ = first ? gw : tw;
-        const int rc = leaf_backward_f32(io_at(x2, (size_t)b0 * T), nb, T, fptr(p.kernel), fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha),
-                                         fptr(p.delta), fptr(p.root), fptr(p.ema_w), F, (int)K, (int)hop, fl,
-                                         io_at(go, (size_t)b0 * F * TP), raw ? fptr(raw) + (size_t)b0 * F * TP : nullptr,
-                                         k_.data_ptr<float>(), pw_.data_ptr<float>(), pb_.data_ptr<float>(),
-                                         p.pcen ? a_.data_ptr<float>() : nullptr, p.pcen ? d_.data_ptr<float>() : nullptr,
-                                         p.pcen ? r_.data_ptr<float>() : nullptr, p.pcen ? w_.data_ptr<float>() : nullptr,
-                                         need_dx ? io_at(gx, (size_t)b0 * T) : nullptr, ws.data_ptr(), (size_t)ws.numel(),
-                                         stream.stream());
-        check_status(rc, "leaf_backward_f32");
+        const float* rawp = raw ? fptr(raw) + (size_t)b0 * F * TP : nullptr;
+        float *pa = p.pcen ? a_.data_ptr<float>() : nullptr, *pd = p.pcen ? d_.data_ptr<float>() : nullptr,
+              *pr = p.pcen ? r_.data_ptr<float>() : nullptr, *pw = p.pcen ? w_.data_ptr<float>() : nullptr;
+        if (c.mixed)
+            check_status(leaf_backward_mix_f32(io_at(c.x2, (size_t)b0 * T), c.perm.data_ptr<int>(), fptr(c.lam), nb, T, fptr(p.kernel),
+                                               fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha), fptr(p.delta), fptr(p.root), fptr(p.ema_w), F,
+                                               (int)K, (int)hop, fl, io_at(go, (size_t)b0 * F * TP), rawp, k_.data_ptr<float>(),
+                                               pw_.data_ptr<float>(), pb_.data_ptr<float>(), pa, pd, pr, pw, nullptr, ws.data_ptr(),
+                                               (size_t)ws.numel(), stream.stream()), "leaf_backward_mix_f32");
+        else
+            check_status(leaf_backward_f32(io_at(c.x2, (size_t)b0 * T), nb, T, fptr(p.kernel), fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha),
+                                           fptr(p.delta), fptr(p.root), fptr(p.ema_w), F, (int)K, (int)hop, fl,
+                                           io_at(go, (size_t)b0 * F * TP), rawp, k_.data_ptr<float>(), pw_.data_ptr<float>(),
+                                           pb_.data_ptr<float>(), pa, pd, pr, pw, need_dx ? io_at(gx, (size_t)b0 * T) : nullptr,
+                                           ws.data_ptr(), (size_t)ws.numel(), stream.stream()), "leaf_backward_f32");
         if (!first) {
             gk.add_(tk); gpw.add_(tpw); gpb.add_(tpb);
             if (p.pcen) { ga.add_(ta); gd.add_(td); gr.add_(tr); gw.add_(tw); }
         }
     }
-    return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw, need_dx ? gx.reshape(x.sizes()) : gx};
+    return result();
 }
 
-// ---- waveform mixup (leaf_hip.h: the *_mix_* entries): the three ops above on x * lam + x[perm] * (1 - lam), the mix done inside
-// the kernels' loads where the family has one.  x float32 or int16 PCM; perm int32 [B] and lam float32 [B] on x's device (the Python
-// layer converts and validates, leaf_pytorch_amd/_native.py: mix_args).  One C-ABI call: a mixed batch cannot be sliced (a clip's
-// partner may sit in another slice), so B * T >= 2^31 is refused.
-struct MixCall {
-    Tensor x2, perm, lam;
-    int64_t B;
-    int T, F, TP, xflag;
-};
-MixCall mix_call(const Tensor& x, const Tensor& perm, const Tensor& lam, const Params& p, int64_t K, int64_t hop) {
-    MixCall c;
-    c.x2 = waveform_2d(x);
-    TORCH_CHECK(c.x2.scalar_type() == at::kFloat || c.x2.scalar_type() == at::kShort,
-                "mixup is defined in float32 on a float32 or int16 (PCM) waveform, got ", c.x2.scalar_type());
-    c.B = c.x2.size(0);
-    TORCH_CHECK(c.x2.size(1) < (int64_t(1) << 31) && c.B * c.x2.size(1) < (int64_t(1) << 31),
-                "a mixed batch goes through one C-ABI call: B * T must stay below 2^31, got ", c.B, " x ", c.x2.size(1));
-    c.T = (int)c.x2.size(1); c.F = (int)p.kernel.size(0);
-    c.TP = leaf_num_frames(c.T, (int)K, (int)hop);
-    TORCH_CHECK(c.TP >= 1 && c.F >= 1, "bad shape B=", c.B, " T=", c.T, " F=", c.F, " K=", K, " hop=", hop);
-    TORCH_CHECK(perm.device() == c.x2.device() && perm.scalar_type() == at::kInt && perm.numel() == c.B,
-                "perm must be int32 with one entry per clip on ", c.x2.device());
-    c.perm = perm.reshape({-1}).contiguous();
-    c.lam = dev_f32(lam.reshape({-1}), "lam", c.x2.device());
-    TORCH_CHECK(c.lam.numel() == c.B, "lam must have one entry per clip");
-    c.xflag = c.x2.scalar_type() == at::kShort ? LEAF_FLAG_X_PCM16 : 0;
-    return c;
+// ---- the six ops: leaf_amd::forward -- frontend.py:78-89 (inference / no-grad); forward_train -- the same, additionally returning
+// the pre-floor pooled tensor the backward consumes; backward; and the three on the mixed batch (forward_mix, forward_train_mix,
+// backward_mix: the seven parameter gradients, no dL/dx)
+#define LEAF_PARAM_ARGS const Tensor &kernel, const Tensor &pool_w, const Tensor &pool_b, const OptTensor &alpha, const OptTensor &delta, \
+                        const OptTensor &root, const OptTensor &ema_w
+#define LEAF_GATHER gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device())
+Tensor op_forward(const Tensor& x, LEAF_PARAM_ARGS, int64_t K, int64_t hop, bool log1p, int64_t algo, bool out_bf16) {
+    return forward_impl(x, nullptr, LEAF_GATHER, K, hop, log1p, algo, nullptr, out_bf16);
 }
-
-Tensor forward_mix_impl(const Tensor& x, const Tensor& perm, const Tensor& lam, const Params& p, int64_t K, int64_t hop, bool log1p,
-                        int64_t algo, Tensor* raw, bool out_bf16) {
-    const MixCall c = mix_call(x, perm, lam, p, K, hop);
-    const auto opt = c.x2.options().dtype(at::kFloat);
-    if (raw) *raw = at::empty({c.B, c.F, c.TP}, opt);
-    if (c.B == 0) return at::empty({c.B, c.F, c.TP}, opt.dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(c.x2.device());
-    // bfloat16 features (LEAF_FLAG_OUT_BF16): narrowed in the kernels' stores; on the staged forward, which stores float32 only, from
-    // its float32 result below (the same rounding, the same bits)
-    bool bf16_staged = false;
-    if (out_bf16) {
-        int sel = (int)(algo & 0xff);
-        if (sel == LEAF_ALGO_AUTO) sel = leaf_auto_algo((int)c.B, c.T, c.F, (int)K, (int)hop);
-        bf16_staged = sel == LEAF_ALGO_STAGED;
-    }
-    const bool fused_bf16 = out_bf16 && !bf16_staged;
-    Tensor out = at::empty({c.B, c.F, c.TP}, opt.dtype(fused_bf16 ? at::kBFloat16 : at::kFloat));
-    float* outp = static_cast<float*>(out.data_ptr());
-    const int flags = c.xflag | (fused_bf16 ? LEAF_FLAG_OUT_BF16 : 0) | (p.pcen ? LEAF_FLAG_PCEN : (log1p ? LEAF_FLAG_LOG1P : 0));
-    auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(c.x2.device().index());
-    Tensor ws = at::empty({(int64_t)std::max<size_t>(leaf_forward_mix_workspace_bytes((int)c.B, c.T, c.F, (int)K, (int)hop, (int)algo), size_t(4))},
-                          opt.dtype(at::kByte));
-    if (raw) {
-        check_status(leaf_forward_save_mix_f32(c.x2.data_ptr(), c.perm.data_ptr<int>(), fptr(c.lam), (int)c.B, c.T, fptr(p.kernel),
-                                               fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha), fptr(p.delta), fptr(p.root), fptr(p.ema_w),
-                                               c.F, (int)K, (int)hop, flags, (int)algo, outp, raw->data_ptr<float>(),
-                                               ws.data_ptr(), (size_t)ws.numel(), stream.stream()),
-                     "leaf_forward_save_mix_f32");
-    } else {
-        check_status(leaf_forward_mix_f32(c.x2.data_ptr(), c.perm.data_ptr<int>(), fptr(c.lam), (int)c.B, c.T, fptr(p.kernel),
-                                          fptr(p.pool_w), fptr(p.pool_b), fptr(p.alpha), fptr(p.delta), fptr(p.root), fptr(p.ema_w), c.F,
-                                          (int)K, (int)hop, flags, (int)algo, outp, ws.data_ptr(), (size_t)ws.numel(),
-                                          stream.stream()),
-                     "leaf_forward_mix_f32");
-    }
-    return bf16_staged ? out.to(at::kBFloat16) : out;
-}
-
-// leaf_amd::forward_mix -- leaf_amd::forward of the mixed batch
-Tensor op_forward_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, const Tensor& kernel, const Tensor& pool_w,
-                      const Tensor& pool_b, const OptTensor& alpha, const OptTensor& delta, const OptTensor& root,
-                      const OptTensor& ema_w, int64_t K, int64_t hop, bool log1p, int64_t algo, bool out_bf16) {
-    const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
-    return forward_mix_impl(x, perm, lam, p, K, hop, log1p, algo, nullptr, out_bf16);
-}
-
-// leaf_amd::forward_train_mix -- additionally the pre-floor pooled tensor of the mixed batch, for leaf_amd::backward_mix
-std::tuple<Tensor, Tensor> op_forward_train_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, const Tensor& kernel,
-                                                const Tensor& pool_w, const Tensor& pool_b, const OptTensor& alpha,
-                                                const OptTensor& delta, const OptTensor& root, const OptTensor& ema_w, int64_t K,
-                                                int64_t hop, int64_t algo, bool log1p, bool out_bf16) {
-    const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
+std::tuple<Tensor, Tensor> op_forward_train(const Tensor& x, LEAF_PARAM_ARGS, int64_t K, int64_t hop, int64_t algo, bool log1p, bool out_bf16) {
     Tensor raw;
-    Tensor out = forward_mix_impl(x, perm, lam, p, K, hop, log1p, algo, &raw, out_bf16);
+    Tensor out = forward_impl(x, nullptr, LEAF_GATHER, K, hop, log1p, algo, &raw, out_bf16);
     return {out, raw};
 }
-
-// leaf_amd::backward_mix -- the seven parameter gradients of the mixed call (PCEN entries empty without PCEN); no dL/dx
-std::vector<Tensor> op_backward_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, const Tensor& kernel, const Tensor& pool_w,
-                                    const Tensor& pool_b, const OptTensor& alpha, const OptTensor& delta, const OptTensor& root,
-                                    const OptTensor& ema_w, int64_t K, int64_t hop, const Tensor& grad_out,
-                                    const OptTensor& pooled_raw, int64_t flags, bool out_bf16) {
-    const Params p = gather(kernel, pool_w, pool_b, alpha, delta, root, ema_w, x.device());
-    const MixCall c = mix_call(x, perm, lam, p, K, hop);
-    Tensor go;
-    if (out_bf16) {                                           // LEAF_FLAG_OUT_BF16: grad_out is bfloat16, widened where the kernels read it
-        TORCH_CHECK(grad_out.device() == c.x2.device(), "grad_out is on ", grad_out.device(), ", expected ", c.x2.device());
-        TORCH_CHECK(grad_out.scalar_type() == at::kBFloat16, "grad_out must be bfloat16 with out_bf16=True, got ", grad_out.scalar_type());
-        go = grad_out.contiguous();
-    } else {
-        go = dev_f32(grad_out, "grad_out", c.x2.device());
-    }
-    TORCH_CHECK(go.dim() == 3 && go.size(0) == c.B && go.size(1) == c.F && go.size(2) == c.TP, "grad_out has shape ", go.sizes(),
-                ", expected (", c.B, ",", c.F, ",", c.TP, ")");
-    OptTensor raw = dev_f32(pooled_raw, "pooled_raw", c.x2.device());
-    auto opt = c.x2.options().dtype(at::kFloat);
-    const int F = c.F;
-    Tensor gk = at::empty_like(p.kernel), gpw = at::empty_like(p.pool_w), gpb = at::empty_like(p.pool_b);
-    Tensor ga = at::empty({p.pcen ? F : 0}, opt), gd = at::empty({p.pcen ? F : 0}, opt), gr = at::empty({p.pcen ? F : 0}, opt),
-           gw = at::empty({p.pcen ? F : 0}, opt);
-    if (c.B == 0) {
-        for (Tensor* g : {&gk, &gpw, &gpb, &ga, &gd, &gr, &gw}) g->zero_();
-        return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw};
-    }
-    const int fl = ((int)flags & ~(LEAF_FLAG_PCEN | LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16 | LEAF_FLAG_OUT_BF16)) | (p.pcen ? LEAF_FLAG_PCEN : 0) | c.xflag |
-                   (out_bf16 ? LEAF_FLAG_OUT_BF16 : 0);
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(c.x2.device());
-    auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(c.x2.device().index());
-    Tensor ws = at::empty({(int64_t)std::max<size_t>(leaf_backward_mix_workspace_bytes((int)c.B, c.T, F, (int)K, (int)hop, fl), size_t(4))},
-                          opt.dtype(at::kByte));
-    check_status(leaf_backward_mix_f32(c.x2.data_ptr(), c.perm.data_ptr<int>(), fptr(c.lam), (int)c.B, c.T, fptr(p.kernel), fptr(p.pool_w),
-                                       fptr(p.pool_b), fptr(p.alpha), fptr(p.delta), fptr(p.root), fptr(p.ema_w), F, (int)K, (int)hop, fl,
-                                       static_cast<const float*>(go.data_ptr()), fptr(raw), gk.data_ptr<float>(), gpw.data_ptr<float>(), gpb.data_ptr<float>(),
-                                       p.pcen ? ga.data_ptr<float>() : nullptr, p.pcen ? gd.data_ptr<float>() : nullptr,
-                                       p.pcen ? gr.data_ptr<float>() : nullptr, p.pcen ? gw.data_ptr<float>() : nullptr, nullptr,
-                                       ws.data_ptr(), (size_t)ws.numel(), stream.stream()),
-                 "leaf_backward_mix_f32");
-    return {gk, gpw.reshape(pool_w.sizes()), gpb, ga, gd, gr, gw};
+std::vector<Tensor> op_backward(const Tensor& x, LEAF_PARAM_ARGS, int64_t K, int64_t hop, const Tensor& grad_out, const OptTensor& pooled_raw,
+                                bool need_dx, int64_t flags, bool out_bf16) {
+    return backward_impl(x, nullptr, LEAF_GATHER, pool_w, K, hop, grad_out, pooled_raw, need_dx, flags, out_bf16);
 }
+Tensor op_forward_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, LEAF_PARAM_ARGS, int64_t K, int64_t hop, bool log1p,
+                      int64_t algo, bool out_bf16) {
+    const Mix mix{perm, lam};
+    return forward_impl(x, &mix, LEAF_GATHER, K, hop, log1p, algo, nullptr, out_bf16);
+}
+std::tuple<Tensor, Tensor> op_forward_train_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, LEAF_PARAM_ARGS, int64_t K,
+                                                int64_t hop, int64_t algo, bool log1p, bool out_bf16) {
+    const Mix mix{perm, lam};
+    Tensor raw;
+    Tensor out = forward_impl(x, &mix, LEAF_GATHER, K, hop, log1p, algo, &raw, out_bf16);
+    return {out, raw};
+}
+std::vector<Tensor> op_backward_mix(const Tensor& x, const Tensor& perm, const Tensor& lam, LEAF_PARAM_ARGS, int64_t K, int64_t hop,
+                                    const Tensor& grad_out, const OptTensor& pooled_raw, int64_t flags, bool out_bf16) {
+    const Mix mix{perm, lam};
+    return backward_impl(x, &mix, LEAF_GATHER, pool_w, K, hop, grad_out, pooled_raw, /*need_dx=*/false, flags, out_bf16);
+}
+#undef LEAF_PARAM_ARGS
+#undef LEAF_GATHER
 
 }  // namespace
 
