@@ -422,6 +422,47 @@ int leaf_pcen_stream_f32(const float* p, int B, int F, int n, const float* alpha
                          void* stream);
 
 /*
+ * One-launch streaming step (additive: the ABI version stays 6).  A running stream of B waveforms is fed chunk by chunk; the
+ * waveform history the next frames still need and the PCEN smoother's state stay ON THE DEVICE, in a `state` buffer the caller
+ * owns; WHERE the stream stands stays on the host, in six integers the caller carries from call to call (nothing is read back
+ * from the device, nothing synchronises, there is no workspace).  Static geometries of the one-launch kernel only (K = 401 /
+ * hop = 160, K = 201 / hop = 80); every other geometry: LEAF_ERR_UNSUPPORTED, and leaf_stream_state_bytes answers 0.
+ *
+ * leaf_stream_history_samples(K, hop): the most samples a stream can owe its next step, H = 2 (K - 1 - padL) + ceil(2 padL / hop) hop
+ *   (880 at 401 / 160): a frame is final once sample m hop + 2 (K - 1 - padL) has arrived, and the buffer is kept from a whole
+ *   number of hops, at least 2 padL samples, in front of the next frame (the derivation is next to the function).  Any K, hop >= 1.
+ * leaf_stream_state_bytes(B, F, K, hop, flags): two history halves of [B][H] samples in the sample type `flags` names (float32, or
+ *   int16 with LEAF_FLAG_X_PCM16) and [B][F] float32 smoother state, each region starting at a multiple of 256 bytes.  The buffer
+ *   may hold anything when a stream begins: a step with hist_len = 0 and started = 0 reads none of it.  0: nothing to size -- a
+ *   geometry without the kernel, B < 1 or F < 1, or a flag the step refuses (LEAF_FLAG_IO_BF16, LEAF_FLAG_PEAKNORM).
+ *
+ * leaf_stream_step_f32: the step's signal is the virtual concatenation [history (hist_len samples per stream, in history half
+ *   `parity`) | chunk[b][0 .. Tc)], chunk row b starting `chunk_stride` samples behind row b - 1 (a slice of a longer recording goes
+ *   in without a copy; Tc = 0: chunk may be NULL).  Frames first .. first + n - 1, numbered from the virtual buffer's first
+ *   sample as in a clip of hist_len + Tc samples, are written to out [B][F][n], every element (n = 0: out is not touched and may
+ *   be NULL); with LEAF_FLAG_PCEN the smoother starts from the state the previous step left when `started` is 1 and at the first
+ *   emitted frame otherwise (postprocessing.py:15), and leaves its state after frame first + n - 1.  Samples
+ *   [drop_samples, hist_len + Tc) of the virtual buffer are copied to the OTHER history half: the next call passes
+ *   hist_len' = hist_len + Tc - drop_samples and parity' = 1 - parity.  Samples behind the virtual buffer's end count as the
+ *   reference's zero padding, which is what the final step of a stream wants (Tc = 0, every remaining frame) and concerns no
+ *   frame whose receptive field is complete.  leaf_pytorch_amd/streaming.py: stream_plan() is the arithmetic of the six integers.
+ *   Flags: LEAF_FLAG_PCEN, LEAF_FLAG_LOG1P, LEAF_FLAG_X_PCM16 (chunk and history are int16), LEAF_FLAG_OUT_BF16 (out is
+ *   bfloat16); LEAF_FLAG_IO_BF16 and LEAF_FLAG_PEAKNORM: LEAF_ERR_UNSUPPORTED.  Checks in this order, all before the launch:
+ *   unsupported flag or geometry; B = 0 (LEAF_OK, nothing launched); NULL; shape; alignment (state 16 bytes, chunk and out by
+ *   element); the position -- hist_len > H, hist_len + Tc beyond one pass of the kernel (16000 samples), drop_samples >
+ *   hist_len + Tc, a new history longer than H, frames outside the virtual buffer: LEAF_ERR_BAD_SHAPE; state_bytes below
+ *   leaf_stream_state_bytes: LEAF_ERR_WORKSPACE.  One launch per call, also when n = 0 (then only the history moves); the one
+ *   exception is a call with nothing to emit AND nothing to keep (n = 0 and drop_samples = hist_len + Tc: the end of a stream that
+ *   owes no frame): LEAF_OK, nothing launched.  Steps of one stream must execute in order (one HIP stream, or events).
+ */
+int leaf_stream_history_samples(int K, int hop);
+size_t leaf_stream_state_bytes(int B, int F, int K, int hop, int flags);
+int leaf_stream_step_f32(const void* chunk, int B, int Tc, long long chunk_stride, void* state, size_t state_bytes, int hist_len,
+                         int parity, int drop_samples, int first, int n, int started, const float* kernel, const float* pool_w,
+                         const float* pool_b, const float* alpha, const float* delta, const float* root, const float* ema_w, int F,
+                         int K, int hop, int flags, void* out, void* stream);
+
+/*
  * Stage backwards: the gradient autograd derives for each of the modules above when it is called ON ITS OWN (the
  * reference's sub-modules are ordinary differentiable nn.Modules; Leaf.forward as a whole has leaf_backward_f32).
  * One-lane-per-output kernels, every intermediate materialised; clamp sub-gradients as torch.clamp gives them.

@@ -106,6 +106,11 @@ _SIGNATURES = {
     "leaf_backward_mix_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
     "leaf_backward_mix_f32": (ctypes.c_int, [_f32p] * 3 + [ctypes.c_int, ctypes.c_int] + [_f32p] * 7 + [ctypes.c_int] * 4 + [_f32p] * 10
                               + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # one-launch streaming step: history and smoother state resident in a caller-owned state buffer
+    "leaf_stream_history_samples": (ctypes.c_int, [ctypes.c_int] * 2),
+    "leaf_stream_state_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "leaf_stream_step_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_size_t]
+                             + [ctypes.c_int] * 6 + [_f32p] * 7 + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -780,6 +785,27 @@ def pcen(p: torch.Tensor, alpha, delta, root, ema_w, floor: float) -> torch.Tens
         check(lib.leaf_pcen_f32(_ptr(p), B, F, TP, _ptr(alpha), _ptr(delta), _ptr(root), _ptr(w), float(floor), _ptr(out),
                                 stream_ptr(dev)), "leaf_pcen_f32")
     return out
+
+
+def stream_state(B: int, F: int, K: int, hop: int, flags: int, device: torch.device) -> torch.Tensor:
+    """The device-resident state of one fused stream (leaf_stream_state_bytes: two history halves and the smoother state),
+    uninitialised -- a stream's first step reads none of it."""
+    nbytes = load().leaf_stream_state_bytes(B, F, K, hop, flags)
+    if nbytes == 0:
+        raise RuntimeError(f"leaf_stream_state_bytes: no one-launch streaming kernel for window {K} / hop {hop}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def stream_step(chunk_ptr: int, B: int, Tc: int, chunk_stride: int, state: torch.Tensor, hist_len: int, parity: int, drop_samples: int,
+                first: int, n: int, started: bool, params, F: int, K: int, hop: int, flags: int, out_ptr: int,
+                device: torch.device) -> None:
+    """leaf_stream_step_f32 on the current stream of ``device``: one launch.  ``params``: the seven parameter tensors (float32,
+    contiguous, on the device; the four PCEN ones None without FLAG_PCEN); ``chunk_ptr`` / ``out_ptr``: device addresses
+    (0 where Tc / n is 0)."""
+    with torch.cuda.device(device):
+        check(load().leaf_stream_step_f32(ctypes.c_void_p(chunk_ptr), B, Tc, chunk_stride, _ptr(state), state.numel(), hist_len, parity,
+                                          drop_samples, first, n, int(started), *(_ptr(t) for t in params), F, K, hop, flags,
+                                          ctypes.c_void_p(out_ptr), stream_ptr(device)), "leaf_stream_step_f32")
 
 
 # ---- stage backwards (what autograd derives for a sub-module called on its own; modules.py wraps them) ----------

@@ -44,6 +44,7 @@
 #include "leaf_fft.hpp"
 #include "leaf_fft_wg.hpp"
 #include "leaf_fft_small.hpp"
+#include "leaf_fft_stream.hpp"
 #include "leaf_fft_wg_bwd.hpp"
 #include "leaf_fft_wg4k.hpp"
 #include "leaf_fft_wgg.hpp"
@@ -649,6 +650,7 @@ bool inst_layouts_ok() {
     static const bool ok =
         leaf_layout_fft() == leaf_layout_hash_fft() &&
         leaf_layout_fft_small() == leaf_layout_hash_small() &&
+        leaf_layout_fft_stream() == leaf_layout_hash_stream() &&
         leaf_layout_fft_wg() == leaf_layout_hash_fft() &&
         leaf_layout_fft_wg_bwd() == leaf_layout_hash_fft() &&
         leaf_layout_fft_wg_bwd_dx() == leaf_layout_hash_fft() &&
@@ -1291,6 +1293,104 @@ static int forward_small(const CallCtx& ctx, const LeafArgs& a, const FwdIo& io,
     if (rc != LEAF_OK) return rc;
     record(io.ev, 2, a.st); record(io.ev, 3, a.st);
     return LEAF_OK;
+}
+
+// ---- the one-launch streaming step (leaf_fft_stream.hpp): history and smoother state resident in `state` between calls
+// state = [history half 0 | history half 1 | ema], each region a multiple of 256 bytes behind the base
+static inline bool stream_geometry(int K, int hop) { return !LEAF_FFT_FORCE_GENERIC && ((K == 401 && hop == 160) || (K == 201 && hop == 80)); }
+struct StreamLayout { int H; size_t half, ema, total; };               // samples per clip and half; byte offsets
+static StreamLayout stream_layout(int B, int F, int K, int hop, bool pcm) {
+    StreamLayout L{};
+    L.H = leaf_stream_history_samples(K, hop);
+    L.half = align_up((size_t)B * L.H * (pcm ? 2 : 4), 256);
+    L.ema = 2 * L.half;
+    L.total = L.ema + (size_t)B * F * 4;
+    return L;
+}
+
+// The most samples a stream owes its next step.  LeafStream (leaf_pytorch_amd/streaming.py) keeps the buffer from a whole number of
+// hops, `lead` = ceil(2 padL / hop) frames, in front of the next frame to emit (the frame's pooling window reaches padL back, the
+// filters another padL), and emits frame m once sample m hop + reach has arrived, reach = 2 (K - 1 - padL).  After a step that
+// saw L samples and emitted up to frame `last` = floor((L - 1 - reach) / hop), _advance keeps L - (last + 1 - lead) hop samples,
+// and (last + 1) hop >= L - reach: at most reach + lead hop.  A step that emits nothing has floor((L - 1 - reach) / hop) < next
+// <= lead, so it too holds L <= reach + lead hop samples.
+int leaf_stream_history_samples(int K, int hop) {
+    if (K < 1 || hop < 1) return 0;
+    const int padL = K / 2 + K % 2 - 1;
+    return 2 * (K - 1 - padL) + ceil_div(2 * padL, hop) * hop;
+}
+
+size_t leaf_stream_state_bytes(int B, int F, int K, int hop, int flags) {
+    if (B < 1 || F < 1 || !stream_geometry(K, hop) || (flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_PEAKNORM))) return 0;
+    return stream_layout(B, F, K, hop, (flags & LEAF_FLAG_X_PCM16) != 0).total;
+}
+
+// where a stream stands (host-side bookkeeping of the caller: nothing is read back from the device) and its buffers
+struct StreamIo {
+    const void* chunk;
+    long long chunk_stride;
+    void* state;
+    int pcm, hist_len, parity, drop, first, n, started, mode;
+    void* out;
+};
+// one launch: grid (F, B), or (1, B) for a step that only moves history.  (No per-call option reaches this path: one workgroup per
+// (stream, filter) whatever the CU count.)
+static int stream_step(const CallCtx&, const LeafArgs& a, const StreamIo& io) {
+    const auto [B, T, F, K, hop] = a.s;                       // T: the virtual buffer [history | chunk]
+    using StreamKernel = void (*)(const StreamParams);
+    const StreamKernel kfn = reinterpret_cast<StreamKernel>(const_cast<void*>(leaf_inst_fft_stream(K)));
+    if (!kfn) return LEAF_ERR_UNSUPPORTED;
+    const StreamLayout L = stream_layout(B, F, K, hop, io.pcm == kSamplePcm16);
+    const int LS = fft_block_len(K, hop, true), padL = K / 2 + K % 2 - 1;
+    char* base = static_cast<char*>(io.state);
+    StreamParams q{};
+    q.chunk = io.chunk; q.chunk_stride = io.chunk_stride; q.pcm = io.pcm;
+    q.hist_in = base + (io.parity ? L.half : 0); q.hist_out = base + (io.parity ? 0 : L.half);
+    q.ema_state = reinterpret_cast<float*>(base + L.ema);
+    q.kernel = a.kernel; q.pool_w = a.pool_w; q.bd = gabor_bounds(K);
+    q.B = B; q.F = F; q.H = L.H; q.hist_len = io.hist_len; q.Tc = T - io.hist_len; q.drop = io.drop;
+    q.first = io.first; q.n = io.n; q.started = io.started;
+    if (io.n > 0) {                                           // the blocks the emitted frames' windows meet
+        q.c_lo = std::max(0, io.first * hop - padL) / LS;
+        q.nb = std::min(T - 1, (io.first + io.n - 1) * hop - padL + K - 1) / LS - q.c_lo + 1;
+    }
+    q.fin = FinParams{nullptr, F, io.n, SlotGeom{LS, padL, K, hop, T, 2}, a.pool_b, a.alpha, a.delta, a.root, a.ema_w, 1e-12f, io.mode, io.out, nullptr, nullptr};
+    return launch_lds(kfn, dim3(io.n > 0 ? F : 1, B), kSmallWaves, io.n > 0 ? fft_small_lds_bytes(kSmallWaves, io.n) : 0, a.st, q);
+}
+
+int leaf_stream_step_f32(const void* chunk, int B, int Tc, long long chunk_stride, void* state, size_t state_bytes, int hist_len,
+                         int parity, int drop_samples, int first, int n, int started, const float* kernel, const float* pool_w,
+                         const float* pool_b, const float* alpha, const float* delta, const float* root, const float* ema_w, int F,
+                         int K, int hop, int flags, void* out, void* stream) {
+    if (flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_PEAKNORM)) return LEAF_ERR_UNSUPPORTED;
+    if (K >= 1 && hop >= 1 && !stream_geometry(K, hop)) return LEAF_ERR_UNSUPPORTED;
+    if (B == 0 && !inst_layouts_ok()) return LEAF_ERR_LAUNCH;
+    if (B == 0 && Tc >= 0 && F >= 1 && K >= 1 && hop >= 1) return LEAF_OK;
+    const bool use_pcen = (flags & LEAF_FLAG_PCEN) != 0;
+    if (!state || !kernel || !pool_w || !pool_b || (Tc > 0 && !chunk) || (n > 0 && !out)) return LEAF_ERR_NULL_POINTER;
+    if (use_pcen && (!alpha || !delta || !root || !ema_w)) return LEAF_ERR_NULL_POINTER;
+    if (B < 1 || B > 65535 || F < 1 || F > 65535 || K < 1 || hop < 1 || Tc < 0 || (Tc > 0 && B > 1 && chunk_stride < Tc)) return LEAF_ERR_BAD_SHAPE;
+    if (!inst_layouts_ok()) return LEAF_ERR_LAUNCH;
+    const bool pcm = (flags & LEAF_FLAG_X_PCM16) != 0, out_bf16 = (flags & LEAF_FLAG_OUT_BF16) != 0;
+    if (misaligned16(state) || (reinterpret_cast<uintptr_t>(chunk) & (pcm ? 1u : 3u)) || (reinterpret_cast<uintptr_t>(out) & (out_bf16 ? 1u : 3u)) ||
+        any_misaligned(kernel, pool_w, pool_b, alpha, delta, root, ema_w))
+        return LEAF_ERR_ALIGNMENT;
+    // the position: everything the kernel derives an address in `state`, `chunk` or `out` from
+    const StreamLayout L = stream_layout(B, F, K, hop, pcm);
+    const int LS = fft_block_len(K, hop, true);
+    if (hist_len < 0 || hist_len > L.H || Tc > kSmallRing * LS || (parity & ~1) || (started & ~1)) return LEAF_ERR_BAD_SHAPE;
+    const int T = hist_len + Tc;
+    if (T > kSmallRing * LS) return LEAF_ERR_BAD_SHAPE;                   // one pass of the ring
+    if (drop_samples < 0 || drop_samples > T || T - drop_samples > L.H) return LEAF_ERR_BAD_SHAPE;
+    const int TPv = T > 0 ? (T - 1) / hop + 1 : 0;
+    if (first < 0 || n < 0 || first > TPv || n > TPv - first) return LEAF_ERR_BAD_SHAPE;
+    if (n > 0 && fft_small_lds_bytes(kSmallWaves, n) > (size_t)kMaxLds) return LEAF_ERR_BAD_SHAPE;
+    if (state_bytes < L.total) return LEAF_ERR_WORKSPACE;
+    if (n == 0 && T - drop_samples == 0) return LEAF_OK;                  // nothing to emit and no history to keep
+    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (out_bf16 ? 4 : 0);
+    const CallCtx ctx = forward_ctx(LEAF_ALGO_AUTO);          // this entry takes no option word
+    return stream_step(ctx, LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream},
+                       StreamIo{chunk, chunk_stride, state, pcm ? kSamplePcm16 : kSampleF32, hist_len, parity, drop_samples, first, n, started, mode, out});
 }
 
 // LEAF_ALGO_FFT_WG on 4096-sample blocks: tables -> workgroup kernel -> the same finalize kernel (partials keep their layout)

@@ -9,9 +9,15 @@ device (2 (K - 1) samples plus alignment), and the PCEN smoother's state travels
 
 Every call is two launches of the product kernels: the fused forward without compression on [history | chunk] (the
 overlap-save or MFMA path ``LEAF_ALGO_AUTO`` picks for that length), then the stateful PCEN over the new frames.
+
+``LeafStream(leaf, fused=True)`` is the same stream with ONE launch per step (``leaf_stream_step_f32``,
+csrc/leaf_fft_stream.hpp): the history and the smoother state live in one device buffer allocated once, the kernel reads
+[history | chunk] from the two buffers, emits only the new frames and hands the history over; no ``cat``, no slicing, no
+allocation per step beyond the frames returned.  16 kHz and 8 kHz geometries (the static instances of the one-launch kernel).
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -19,8 +25,51 @@ import torch
 from . import _native
 
 
+def _geometry(K: int, hop: int):
+    """(lead, reach) of a window / hop: see LeafStream.__init__."""
+    pad_l = K // 2 + K % 2 - 1
+    return -(-2 * pad_l // hop), 2 * (K - 1 - pad_l)
+
+
+def stream_plan(hist_len: int, next_frame: int, Tc: int, K: int, hop: int, final: bool):
+    """Where one step takes a stream: the arithmetic of ``step``, ``_advance`` and ``flush`` in one place, on integers alone.
+
+    The stream holds ``hist_len`` samples, ``next_frame`` (numbered from the first of them) is the next frame to emit, and ``Tc``
+    samples arrive (``final``: none do, the stream ends and the frames still owed come with zero padding behind the last sample).
+    Returns ``(first, n, drop_samples, new_hist_len, new_next)``: frames ``first .. first + n - 1`` of the buffer [history | chunk]
+    are emitted, its samples from ``drop_samples`` on are the next step's history, ``new_hist_len`` of them, and ``new_next`` is the
+    next frame to emit in that buffer's numbering.  These are the position arguments of ``leaf_stream_step_f32``."""
+    lead, reach = _geometry(K, hop)
+    L = hist_len + Tc
+    last = (L - 1) // hop if final else (L - 1 - reach) // hop            # last frame of the clip / whose receptive field is complete
+    n = max(0, last - next_frame + 1)
+    if final:
+        return next_frame, n, L, 0, 0
+    if n == 0:
+        return next_frame, 0, 0, L, next_frame
+    drop = max(0, last + 1 - lead)                                        # whole hops in front that frame last + 1 no longer needs
+    return next_frame, n, drop * hop, L - drop * hop, last + 1 - drop
+
+
+def stream_capacity(K: int, hop: int) -> int:
+    """Samples [history | chunk] of one ``leaf_stream_step_f32`` call: one pass of the one-launch kernel's ring, kSmallRing = 10
+    blocks of fft_block_len(K, hop) valid outputs of a 2048-point transform (csrc/leaf_fft.hpp, csrc/leaf_fft_small.hpp)."""
+    unit = 64 // math.gcd(64, hop) * hop
+    return 10 * ((2048 - K + 1) // unit * unit)
+
+
 class LeafStream:
-    def __init__(self, leaf, log1p: bool = False):
+    def __new__(cls, leaf, log1p: bool = False, fused: bool = False, out_dtype=None):
+        return object.__new__(_FusedLeafStream if fused and cls is LeafStream else cls)
+
+    def __init__(self, leaf, log1p: bool = False, fused: bool = False, out_dtype=None):
+        """``fused=True``: one launch per step (module docstring; ``ValueError`` for a geometry the one-launch kernel does not
+        serve).  ``out_dtype=torch.bfloat16`` (needs ``fused=True``, ``ValueError`` otherwise): the frames come back in bfloat16,
+        rounded where the kernel stores them; the module's own ``output_dtype()`` is not consulted."""
+        if out_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError(f"LeafStream: out_dtype must be None, torch.float32 or torch.bfloat16, got {out_dtype!r}")
+        if out_dtype is torch.bfloat16 and not fused:
+            raise ValueError("LeafStream: out_dtype=torch.bfloat16 needs fused=True (the two-launch stream returns float32 frames)")
         conv, pool = leaf._complex_conv, leaf._pooling
         self.leaf = leaf
         self.K, self.hop, self.F = conv._kernel_size, pool.strides, conv._filters
@@ -94,5 +143,90 @@ class LeafStream:
         out = self._emit(self.next, last) if last >= self.next else self.buf.new_empty((self.buf.shape[0], self.F, 0), dtype=torch.float32)
         self.buf = self.state = None
         self.next = 0
+        self.started = False
+        return out
+
+
+class _FusedLeafStream(LeafStream):
+    """``LeafStream(leaf, fused=True)``: every step is one ``leaf_stream_step_f32`` launch per piece of the chunk (a chunk beyond
+    the kernel's one-pass capacity goes in pieces).  The host keeps where the stream stands -- ``hist_len``, ``next``, ``parity``,
+    ``started`` -- and ``stream_plan`` moves it; the device buffer ``state_buf`` is allocated by the first step and kept.
+    Inherited from the two-launch class and NOT used here: ``buf`` and ``state`` (they stay None: history and smoother live in
+    ``state_buf``), ``_pooled``, ``_emit`` and ``_advance``; the geometry (``K`` .. ``reach``), ``log1p``, ``next`` and ``started`` are."""
+
+    def __init__(self, leaf, log1p: bool = False, fused: bool = True, out_dtype=None):
+        super().__init__(leaf, log1p, True, out_dtype)
+        if _native.load().leaf_stream_state_bytes(1, self.F, self.K, self.hop, 0) == 0:
+            raise ValueError(f"LeafStream(fused=True): no one-launch streaming kernel for window {self.K} / hop {self.hop} "
+                             "(16 kHz and 8 kHz geometries: 401 / 160, 201 / 80); use fused=False")
+        c = leaf._compression
+        if c is not None and c._floor != 1e-12:
+            raise NotImplementedError("fused path is specialised for the PCEN floor Leaf constructs (1e-12)")
+        self.out_dtype = torch.bfloat16 if out_dtype is torch.bfloat16 else torch.float32
+        self.capacity = stream_capacity(self.K, self.hop)
+        self.state_buf: Optional[torch.Tensor] = None                     # [history half 0 | history half 1 | smoother], never cleared
+        self.state_key = None                                             # (B, int16?, device) the buffer was sized for
+        self.pcm: Optional[bool] = None                                   # sample type of the running stream
+        self.hist_len = 0
+        self.parity = 0
+
+    def _launch(self, x2: Optional[torch.Tensor], at: int, Tc: int, final: bool) -> torch.Tensor:
+        B, pcm, dev = self.state_key
+        first, n, drop, new_hist, new_next = stream_plan(self.hist_len, self.next, Tc, self.K, self.hop, final)
+        sd, c = self.leaf, self.leaf._compression
+        params = [_native._dev_f32(t, nm, dev) for t, nm in ((sd._complex_conv._kernel, "kernel"), (sd._pooling.weights.reshape(-1), "pool_w"),
+                                                            (sd._pooling._bias, "pool_b"))]
+        params += [None] * 4 if c is None else [_native._dev_f32(t, nm, dev) for t, nm in
+                                                ((c.alpha, "alpha"), (c.delta, "delta"), (c.root, "root"), (c.ema._weights, "ema_w"))]
+        flags = (_native.FLAG_PCEN if c is not None else _native.FLAG_LOG1P if self.log1p else 0) | (_native.FLAG_X_PCM16 if pcm else 0) \
+            | (_native.FLAG_OUT_BF16 if self.out_dtype is torch.bfloat16 else 0)
+        out = torch.empty((B, self.F, n), dtype=self.out_dtype, device=dev)
+        _native.stream_step(x2.data_ptr() + at * x2.element_size() if Tc else 0, B, Tc, x2.stride(0) if Tc else 0, self.state_buf,
+                            self.hist_len, self.parity, drop, first, n, self.started, params, self.F, self.K, self.hop, flags,
+                            out.data_ptr() if n else 0, dev)
+        self.hist_len, self.next, self.parity = new_hist, new_next, self.parity ^ 1
+        self.started = self.started or n > 0
+        return out
+
+    @torch.no_grad()
+    def step(self, chunk: torch.Tensor) -> torch.Tensor:
+        """As ``LeafStream.step``; the frames are ``out_dtype``.  ``chunk`` may be a view into a longer recording
+        (``x[:, :, a:b]``): its row stride is passed down, nothing is copied."""
+        pcm = chunk.dtype == torch.int16
+        if self.pcm is not None and pcm != self.pcm:
+            raise RuntimeError(f"LeafStream.step: this stream holds {'int16 PCM' if self.pcm else 'float32'} "
+                               f"samples and got a {chunk.dtype} chunk: one sample type per stream (flush() ends it)")
+        _native.require_hip(chunk, "LeafStream.step")
+        x2 = chunk[:, 0, :] if chunk.dim() == 3 else chunk
+        x2 = x2 if pcm else x2.float()
+        B, Tc = x2.shape
+        if (Tc > 1 and x2.stride(1) != 1) or (Tc >= 1 and B > 1 and x2.stride(0) < Tc):     # (an expanded view: rows overlap)
+            x2 = x2.contiguous()
+        if self.pcm is None:                                              # a stream begins
+            key = (B, pcm, x2.device)
+            if self.state_key != key:
+                self.state_buf = _native.stream_state(B, self.F, self.K, self.hop, _native.FLAG_X_PCM16 if pcm else 0, x2.device)
+                self.state_key = key
+            self.pcm = pcm
+        elif (B, x2.device) != (self.state_key[0], self.state_key[2]):
+            raise RuntimeError(f"LeafStream.step: this stream runs {self.state_key[0]} waveforms on {self.state_key[2]} and got "
+                               f"{B} on {x2.device} (flush() ends it)")
+        outs, at = [], 0
+        while at < Tc:                                                    # one piece unless the chunk exceeds the kernel's one pass
+            take = min(Tc - at, self.capacity - self.hist_len)
+            outs.append(self._launch(x2, at, take, False))
+            at += take
+        if not outs:
+            return x2.new_empty((B, self.F, 0), dtype=self.out_dtype)
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=2)
+
+    @torch.no_grad()
+    def flush(self) -> torch.Tensor:
+        """As ``LeafStream.flush``: one final step without samples.  The state buffer is kept for the next stream as it is."""
+        if self.pcm is None:
+            return torch.empty((0, self.F, 0), device="cuda")
+        out = self._launch(None, 0, 0, True)
+        self.pcm = None
+        self.hist_len = self.next = 0
         self.started = False
         return out

@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Per-step time of a running LeafStream, fused (one leaf_stream_step_f32 launch) against unfused (the two-launch class: cat ->
+forward -> slice -> leaf_pcen_stream_f32 -> slice), 16 kHz / 40 filters / PCEN, in steady state.
+
+    python tools/bench_stream.py [--rounds 6] [--steps 40] [--out profiles/stream_fused.txt]
+
+Both legs run in ONE process, in turn, round after round after a warm-up round (the order of the legs alternates), on views of one
+long recording.  Two figures per leg and shape, each the median / min / max over the rounds of (time of `steps` steps) / steps:
+  wall    host clock from the first step() to the end of a device synchronisation behind the last: what a serving loop sees
+  device  HIP events around the same steps, ENQUEUED WHILE THE DEVICE IS KEPT BUSY by matrix products queued in front, so that the
+          steps run back to back from a full queue: the device's own time per step, launch gaps between dependent kernels included,
+          the host's enqueue time excluded
+No assertion on any time; prints the table and, with --out, writes it."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import leaf_pytorch_amd as L  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def run_steps(stream, x, chunk, steps, pos):
+    T = x.shape[-1]
+    for _ in range(steps):
+        if pos + chunk > T:
+            pos = 0
+        stream.step(x[:, :, pos:pos + chunk])
+        pos += chunk
+    return pos
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    torch.manual_seed(0)
+    m = L.Leaf().eval().to(DEV)
+    for p in m.parameters():
+        p.requires_grad_(False)
+    blocker = torch.randn(8192, 8192, device=DEV)
+    lines = [f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {args.rounds} timed rounds x {args.steps} steps per leg after a warm-up round; "
+             "us per step: median (min .. max)",
+             f"{'B':>3} {'chunk':>6} {'leg':<8} {'wall us':>26} {'device us':>26}"]
+    for B in (1, 4, 16):
+        x = (2 * torch.rand(B, 1, 160000, device=DEV) - 1)
+        for chunk in (160, 1600, 8000):
+            legs = {"fused": L.LeafStream(m, fused=True), "unfused": L.LeafStream(m)}
+            pos = {k: 0 for k in legs}
+            wall, dev = {k: [] for k in legs}, {k: [] for k in legs}
+            for rnd in range(args.rounds + 1):
+                order = list(legs) if rnd % 2 == 0 else list(legs)[::-1]
+                for name in order:
+                    s = legs[name]
+                    pos[name] = run_steps(s, x, chunk, 5, pos[name])      # the leg's code and data warm again after the other leg
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    pos[name] = run_steps(s, x, chunk, args.steps, pos[name])
+                    torch.cuda.synchronize()
+                    w = (time.perf_counter() - t0) / args.steps
+                    # device time: the same steps behind enough queued work to cover the host's enqueue time twice over
+                    t0 = time.perf_counter()
+                    blocker @ blocker
+                    torch.cuda.synchronize()
+                    one = time.perf_counter() - t0
+                    for _ in range(max(2, int(2 * w * args.steps / one) + 1)):
+                        blocker @ blocker
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    pos[name] = run_steps(s, x, chunk, args.steps, pos[name])
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if rnd:
+                        wall[name].append(w * 1e6)
+                        dev[name].append(e0.elapsed_time(e1) * 1e3 / args.steps)
+            for name in legs:
+                fmt = lambda v: f"{statistics.median(v):8.1f} ({min(v):7.1f} .. {max(v):7.1f})"
+                lines.append(f"{B:>3} {chunk:>6} {name:<8} {fmt(wall[name])} {fmt(dev[name])}")
+            for s in legs.values():
+                s.flush()
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
