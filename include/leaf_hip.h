@@ -230,6 +230,11 @@ typedef enum leaf_status {
  * the half spectrum (their own switch: LEAF_FLAG_BWD_STRICT_BAND_CLASSES). */
 #define LEAF_ALGO_STRICT_BAND_CLASSES (1 << 27)
 
+/* No table cache, OR-ed into `algo` (additive: the ABI version stays 6): leaf_forward_cached_f32 takes the route of
+ * leaf_forward_f32 -- the table launch rebuilds everything into the workspace, the cache is neither read nor written.  What tests
+ * and A/B runs compare the cached route against; ignored by every other entry point. */
+#define LEAF_ALGO_NO_TABLE_CACHE (1 << 28)
+
 int leaf_abi_version(void);
 const char* leaf_status_string(int status);
 
@@ -255,6 +260,36 @@ int leaf_forward_f32(const float* x, int B, int T,
                      const float* alpha, const float* delta, const float* root, const float* ema_w,
                      int F, int K, int hop, int flags, int algo,
                      float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * leaf_forward_f32 with a SELF-VALIDATING TABLE CACHE (additive: the ABI version stays 6).  Everything the table launch of the
+ * 2048-sample plan writes except the first-block spectra depends only on (kernel, pool_w, F, K, hop), the band edge tables on T as
+ * well; in inference these stay the same from call to call.  `cache` is a caller-owned device buffer of leaf_table_cache_bytes(F, K,
+ * hop, T) bytes (16-byte aligned, exact-size, read-write) that holds those tables between calls -- spectra, pooling rows, col_of, the
+ * band records and decimated pooling windows, the edge tables and edge list of this T -- and one STAMP per workgroup of the table
+ * launch: a magic word and the bit patterns of every input that workgroup reads (kernel[f], pool_w[f], F, K, hop, T, its edge entry,
+ * the class rule's constants and options).  The table launch runs in validate-or-build form: a workgroup whose stamp matches returns,
+ * any other invalidates its stamp, builds what leaf_forward_f32's launch builds and writes the stamp last (a build cut short never
+ * reads as valid).  The tables therefore follow the parameters OF THIS CALL, by content -- no staleness window, nothing keyed on a
+ * pointer or a version -- and the result equals leaf_forward_f32's bit for bit (the main kernel transforms its first blocks itself,
+ * as for 16-bit PCM input: the same bits).  A default step is then a validator launch (a few microseconds) + the main kernel.
+ *   - the caller ZEROES the buffer once, before first use (a zeroed stamp is invalid); afterwards the library alone writes it.
+ *   - one cache belongs to one stream at a time, like a workspace; a buffer sized for a T with more edge entries serves one with fewer.
+ *   - the pooling bias is not part of a stamp: the tables do not depend on it (the main kernel builds its plan from pool_b of the call).
+ *   - served: the workgroup kernels (static and run-time geometry) and the per-wave kernel of the 2048-sample plan.  Every other plan
+ *     (4096-sample blocks, the one-launch small-batch kernel, MFMA, staged), LEAF_FLAG_PEAKNORM and LEAF_ALGO_NO_TABLE_CACHE take
+ *     leaf_forward_f32's route unchanged and leave the cache untouched; so does cache == NULL.
+ *   - a misaligned cache: LEAF_ERR_ALIGNMENT; cache_bytes below the size query on a served route: LEAF_ERR_WORKSPACE; both before any
+ *     launch.  `workspace` is leaf_workspace_bytes' as for leaf_forward_f32.
+ * leaf_table_cache_bytes returns 0 where the shape has no 2048-sample plan (nothing to cache).
+ */
+size_t leaf_table_cache_bytes(int F, int K, int hop, int T);
+int leaf_forward_cached_f32(const float* x, int B, int T,
+                            const float* kernel, const float* pool_w, const float* pool_b,
+                            const float* alpha, const float* delta, const float* root, const float* ema_w,
+                            int F, int K, int hop, int flags, int algo,
+                            float* out, void* workspace, size_t workspace_bytes,
+                            void* cache, size_t cache_bytes, void* stream);
 
 /*
  * Training forward: leaf_forward_f32 that additionally stores pooled_raw [B][F][T'] = bias + pooled energy BEFORE

@@ -36,6 +36,7 @@ FLAG_BWD_STRICT_BAND_CLASSES = 0x80   # leaf_backward_f32: the backward's band c
 ALGO_STREAM_FINALIZE = 1 << 25   # LEAF_ALGO_STREAM_FINALIZE: per-frame sums in an LDS ring, finalized as the blocks complete
 ALGO_FULL_TRANSFORMS = 1 << 26   # LEAF_ALGO_FULL_TRANSFORMS: no band-limited filter tasks (every filter on 2048-point transforms)
 ALGO_STRICT_BAND_CLASSES = 1 << 27   # LEAF_ALGO_STRICT_BAND_CLASSES: the band classes' energy bound does not follow the pooling bias (round 5's decision)
+ALGO_NO_TABLE_CACHE = 1 << 28   # LEAF_ALGO_NO_TABLE_CACHE: the forward rebuilds its tables on every call (no self-validating table cache)
 OPT_PEAKNORM = 1 << 24          # torch.ops.leaf_amd.forward: option bit in `algo` that sets LEAF_FLAG_PEAKNORM (torch_binding.cpp)
 STAGE_GABOR_CONV, STAGE_LOWPASS, STAGE_EMA, STAGE_PCEN = 1, 2, 3, 4
 
@@ -51,6 +52,9 @@ _SIGNATURES = {
     "leaf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
     "leaf_forward_f32": (ctypes.c_int, [_f32p, ctypes.c_int, ctypes.c_int] + [_f32p] * 7 + [ctypes.c_int] * 5
                          + [_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "leaf_table_cache_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "leaf_forward_cached_f32": (ctypes.c_int, [_f32p, ctypes.c_int, ctypes.c_int] + [_f32p] * 7 + [ctypes.c_int] * 5
+                                + [_f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "leaf_auto_algo": (ctypes.c_int, [ctypes.c_int] * 5),
     "leaf_fft_plan_info": (ctypes.c_int, [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]),
     "leaf_band_classes_f32": (ctypes.c_int, [_f32p, _f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,

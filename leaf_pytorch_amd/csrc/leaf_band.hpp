@@ -245,6 +245,8 @@ struct BandTabArgs {
     int io_bf16, B, nblk, G;
     float2* spec0;
     int cross;             // != 0 (forward launches of the 2048-sample plan, round 6): windows may reach bin kWgFwdBins - 1 (beyond Nyquist)
+    unsigned* stamps;      // the table cache's stamps, [2 + n_edge][F][kStampWords] (leaf_fft.hpp); NULL everywhere else
+    int strict;            // (stamped launches) LEAF_ALGO_STRICT_BAND_CLASSES, part of the stamp
     int bwd_slabs;         // (backward) != 0: the class decision also asks band_deriv_fits; 1 (2048-sample plan): two more grid rows, (f, 2 + n_edge) and (f, 3 + n_edge), build the spectra of d w / d mu and
                            // d w / d sigma into slabs 1 and 2 of H (what fft_prep_kernel's grid (F, 3) does): one table launch
 };
@@ -265,9 +267,9 @@ __device__ __forceinline__ float band_row_sum(float v) {
 //   workgroup (f, 1 + n_edge): the decimated pooling windows G~ of both classes } and done before wave 0's transform is
 // Sixteen lanes per table entry: the sum over the window samples within lphi of the entry's position.
 // (Workgroup (0, 0) also copies the edge list to device memory for the main kernel.)
-__global__ __launch_bounds__(kPrepWaves * 64) void fft_prep_band_kernel(const float* __restrict__ kernel, const float* __restrict__ pool_w,
-                                                                        int F, int K, int GZ, GaborBounds bd, float2* __restrict__ H,
-                                                                        float* __restrict__ Gz, int* __restrict__ col_of, const BandTabArgs a) {
+__device__ __forceinline__ void fft_prep_band_body(const float* __restrict__ kernel, const float* __restrict__ pool_w,
+                                                   int F, int K, int GZ, const GaborBounds& bd, float2* __restrict__ H,
+                                                   float* __restrict__ Gz, int* __restrict__ col_of, const BandTabArgs& a) {
     __shared__ float2 s_twl[32 * 64];
     __shared__ float2 s_twh[64];
     __shared__ float2 s_twp[64];
@@ -538,6 +540,30 @@ __global__ __launch_bounds__(kPrepWaves * 64) void fft_prep_band_kernel(const fl
         a.rec[4 * f + 2] = kbv[1];
         a.rec[4 * f + 3] = need;          // bmin(256) | bmin(512) << 16, fp16 codes
     }
+}
+// a.stamps != NULL (the table cache, leaf_forward_cached_f32; forward launches with grid (F, 2 + n_edge) only): every workgroup
+// validates its stamp (leaf_fft.hpp) and returns, or builds what it builds without one and stamps it
+__global__ __launch_bounds__(kPrepWaves * 64) void fft_prep_band_kernel(const float* __restrict__ kernel, const float* __restrict__ pool_w,
+                                                                        int F, int K, int GZ, GaborBounds bd, float2* __restrict__ H,
+                                                                        float* __restrict__ Gz, int* __restrict__ col_of, const BandTabArgs a) {
+    const int tid = threadIdx.x, f = blockIdx.x, y = blockIdx.y;
+    unsigned* slot = nullptr;
+    unsigned word = 0u;
+    if (a.stamps) {
+        // role 0: workgroup (f, 0); role 1: the decimated pooling windows (f, 1 + n_edge); role 2 + s: the edge table (f, 1 + s)
+        const int s = y - 1, role = y == 0 ? 0 : y == 1 + a.n_edge ? 1 : 2 + s;
+        StampKey key{};
+        key.kind = 2; key.F = F; key.K = K; key.hop = a.hop; key.T = a.T; key.role = role; key.n_edge = a.n_edge;
+#pragma unroll
+        for (int i = 0; i < kBandMaxEdge; ++i)
+            if (role == 2 + i) { key.e[0] = a.e[i].c; key.e[1] = a.e[i].m; key.e[2] = a.e[i].lo; key.e[3] = a.e[i].hi; }
+        key.eps2 = a.eps2; key.eta = a.eta; key.cross = a.cross; key.force = a.force; key.strict = a.strict;
+        slot = a.stamps + ((size_t)role * F + f) * kStampWords;
+        if (tid < kStampWords) word = stamp_word(tid, key, kernel, pool_w, f);
+        if (stamp_check(slot, word, tid)) return;
+    }
+    fft_prep_band_body(kernel, pool_w, F, K, GZ, bd, H, Gz, col_of, a);
+    if (slot) stamp_publish(slot, word, tid);
 }
 #endif
 

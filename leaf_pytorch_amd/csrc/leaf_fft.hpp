@@ -409,6 +409,68 @@ constexpr bool fft_static_geometry(int K, int hop) {
 // One workgroup per filter: all waves evaluate the taps (into LDS), the pooling row and the twiddle tables; wave 0 then
 // runs the transform.
 constexpr int kPrepWaves = 8;
+
+// ---- self-validating table cache (leaf_forward_cached_f32) ------------------------------------------------------------------
+// With a stamp pointer a table workgroup first compares its STAMP -- a magic word and the bit patterns of every input it reads --
+// with what this call would write, and returns on a match: the tables behind it were built from the same values.  Otherwise it
+// invalidates the stamp, builds exactly what it builds without one and writes the stamp last, so that a build cut short never reads
+// as valid.  Slots are laid out by role, [role][F]: role 0 the workgroup (f, 0) (spectra, pooling row, col_of, the band record and,
+// for f = 0, the edge list), role 1 the decimated pooling windows, role 2 + s the edge table of edge entry s.  A zeroed slot is invalid.
+constexpr int kStampWords = 32;                          // 128 bytes per slot
+constexpr unsigned kStampMagic = 0x4c454146u;
+struct StampKey {
+    int kind;              // 1: fft_prep_kernel, 2: fft_prep_band_kernel
+    int F, K, hop, T, role, n_edge;
+    int e[4];              // the role's edge entry (c, m, lo, hi); zeros for the other roles
+    float eps2, eta;
+    int cross, force, strict;
+};
+// word i of filter f's stamp for this call
+__device__ __forceinline__ unsigned stamp_word(int i, const StampKey& k, const float* __restrict__ kernel, const float* __restrict__ pool_w, int f) {
+    switch (i) {
+        case 0: return kStampMagic;
+        case 1: return __float_as_uint(kernel[2 * f]);
+        case 2: return __float_as_uint(kernel[2 * f + 1]);
+        case 3: return __float_as_uint(pool_w[f]);
+        case 4: return (unsigned)k.F;
+        case 5: return (unsigned)k.K;
+        case 6: return (unsigned)k.hop;
+        case 7: return (unsigned)k.T;
+        case 8: return (unsigned)k.e[0];
+        case 9: return (unsigned)k.e[1];
+        case 10: return (unsigned)k.e[2];
+        case 11: return (unsigned)k.e[3];
+        case 12: return __float_as_uint(k.eps2);
+        case 13: return __float_as_uint(k.eta);
+        case 14: return (unsigned)k.cross;
+        case 15: return (unsigned)k.force;
+        case 16: return (unsigned)k.strict;
+        case 17: return (unsigned)k.kind;
+        case 18: return (unsigned)k.role;
+        case 19: return (unsigned)k.n_edge;
+        case 20: return (unsigned)f;
+    }
+    return 0u;
+}
+// workgroup-uniform: does the slot hold this call's stamp?  On a miss the slot reads invalid before anything is built.
+__device__ __forceinline__ bool stamp_check(unsigned* slot, unsigned word, int tid) {
+    const bool same = tid >= kStampWords || slot[tid] == word;
+    if (__syncthreads_and(same)) return true;
+    if (tid == 0) slot[0] = 0u;
+    __threadfence();
+    __syncthreads();
+    return false;
+}
+// after the build: every table store of the workgroup is visible device-wide before the stamp, the magic word last
+__device__ __forceinline__ void stamp_publish(unsigned* slot, unsigned word, int tid) {
+    __threadfence();
+    __syncthreads();
+    if (tid > 0 && tid < kStampWords) slot[tid] = word;
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) slot[0] = word;
+}
+
 // Part A (every thread of the workgroup): conj(taps) of filter f into s_taps, the pooling row (global, and an LDS copy of the
 // window when g_lds != NULL), the twiddle tables.  The caller synchronises before part B.
 __device__ __forceinline__ void fft_prep_front(const float* __restrict__ kernel, const float* __restrict__ pool_w, int F, int K, int GZ,
@@ -497,19 +559,30 @@ __global__ __launch_bounds__(kPrepWaves * 64) void fft_prep_kernel(const float* 
                                                                    const float* __restrict__ pool_w, int F, int K, int GZ,
                                                                    GaborBounds bd, int real_spec, float2* __restrict__ H,
                                                                    float* __restrict__ Gz, int* __restrict__ col_of,
-                                                                   float* __restrict__ lone) {
+                                                                   float* __restrict__ lone, unsigned* __restrict__ stamps,
+                                                                   int hop, int T) {
     __shared__ float2 s_twl[32 * 64];
     __shared__ float2 s_twh[64];
     __shared__ float s_scr[32 * 65];
     __shared__ float2 s_taps[kFftN / 2 + 64];            // conj(w_f), K <= N/2 + 1
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int f = blockIdx.x;
+    // stamps != NULL (the table cache; grid (F, 1) only): validate or build, role 0
+    unsigned* slot = stamps ? stamps + (size_t)f * kStampWords : nullptr;
+    unsigned word = 0u;
+    if (slot) {
+        StampKey key{};
+        key.kind = 1; key.F = F; key.K = K; key.hop = hop; key.T = T; key.cross = real_spec;
+        if (tid < kStampWords) word = stamp_word(tid, key, kernel, pool_w, f);
+        if (stamp_check(slot, word, tid)) return;
+    }
     // blockIdx.y (backward tables, real-spectrum form only): 0 the taps w, 1 d w/d mu = i t w, 2 d w/d sigma =
     // (t^2/s^3 - 1/s) w (impulse_responses.py:5-16 differentiated; both stay Hermitian, so their spectra are real too)
     const int which = blockIdx.y;
     fft_prep_front(kernel, pool_w, F, K, GZ, bd, Gz, f, which, s_twl, s_twh, s_taps, nullptr, tid);
     __syncthreads();
     if (wave == 0) fft_prep_transform(F, K, real_spec, H, col_of, lone, f, which, s_twl, s_twh, s_scr, s_taps, nullptr, lane);
+    if (slot) stamp_publish(slot, word, tid);
 }
 #endif
 

@@ -78,6 +78,7 @@ struct CallCtx {
     bool stream_finalize;    // LEAF_ALGO_STREAM_FINALIZE
     bool band_off;           // LEAF_ALGO_FULL_TRANSFORMS / LEAF_FLAG_BWD_FULL_TRANSFORMS
     bool band_strict;        // LEAF_ALGO_STRICT_BAND_CLASSES / LEAF_FLAG_BWD_STRICT_BAND_CLASSES
+    bool no_table_cache;     // LEAF_ALGO_NO_TABLE_CACHE: leaf_forward_cached_f32 runs as leaf_forward_f32
     int desync;              // LEAF_ALGO_TUNE_DESYNC(n); -1 = automatic
     int sel;                 // the selector (low byte of `algo`); resolve_selector() turns LEAF_ALGO_AUTO into what runs
     MixArgs mix;
@@ -111,6 +112,7 @@ CallCtx forward_ctx(int algo) {
     c.stream_finalize = (algo & LEAF_ALGO_STREAM_FINALIZE) != 0;
     c.band_off = (algo & LEAF_ALGO_FULL_TRANSFORMS) != 0;
     c.band_strict = (algo & LEAF_ALGO_STRICT_BAND_CLASSES) != 0;
+    c.no_table_cache = (algo & LEAF_ALGO_NO_TABLE_CACHE) != 0;
     c.desync = ((algo >> 8) & 0xff) - 1;
     c.sel = algo & 0xff;
     return c;
@@ -564,6 +566,25 @@ size_t fft_table_floats(const FftPlan& fp, int F, bool band_dyn = true) {
 // (+ B floats behind the partial sums: the per-clip scales of LEAF_FLAG_PEAKNORM)
 size_t fft_workspace_floats(const FftPlan& fp, int F, int B) {
     return fft_table_floats(fp, F) + align_up(fp.part_floats, 64) + (LEAF_TRACE ? 16 * 64 * 2 : 0) + align_up((size_t)B, 64);
+}
+
+// ---- the self-validating table cache of leaf_forward_cached_f32 (stamps: leaf_fft.hpp).  One caller-owned buffer holds the tables of
+// the 2048-sample plan as a forward call's workspace does -- [spectra | pooling rows | col_of | band records, G~ | edge tables | edge
+// list] -- and, where the workspace has the first-block spectra, the stamps [roles][F][kStampWords]: roles = 2 + the edge entries of
+// this clip length where the geometry has band tasks, else 1.
+struct TableCache { float* p; size_t bytes; };
+int cache_edge_entries(const FftPlan& fp, const Shape& s) {
+    BandParams bp{};
+    BandEdge e[kBandMaxEdge];
+    return band_edges(s.T, s.K, s.hop, fp.L, fp.padL, bp, e) ? bp.n_edge : 0;
+}
+size_t table_cache_floats(const FftPlan& fp, const Shape& s) {
+    const BandLayout bl = band_layout(s.F, s.K, s.hop);
+    const int roles = bl.stat ? 2 + cache_edge_entries(fp, s) : 1;
+    return fft_table_floats(fp, s.F, false) + bl.spec0 + (size_t)roles * s.F * kStampWords;
+}
+unsigned* table_cache_stamps(const FftPlan& fp, float* cache, const Shape& s) {
+    return reinterpret_cast<unsigned*>(cache + fft_table_floats(fp, s.F, false) + band_layout(s.F, s.K, s.hop).spec0);
 }
 
 // ---- single-launch small-batch forward (leaf_fft_small.hpp): one workgroup per (clip, filter)
@@ -1112,7 +1133,7 @@ struct FwdBand { BandParams band; size_t lds; const float2* spec0; };
 // (tables_ready) the parameter-only part is in them and only the edge tables of this clip length are built here, into
 // band_scratch.  The plan takes fb.lds bytes of LDS behind everything else.
 static int fft_forward_tables(const CallCtx& ctx, const FftPlan& fp, const LeafArgs& a, const FwdIo& io, float* tables,
-                              bool tables_ready, bool use_wg, float* band_scratch, FwdBand& fb) {
+                              bool tables_ready, bool use_wg, float* band_scratch, unsigned* stamps, FwdBand& fb) {
     const auto [B, T, F, K, hop] = a.s;
     const FftTabPtrs tp = fft_tab_ptrs(fp, tables, F);
     if (use_wg && !ctx.band_off && (!tables_ready || band_scratch)) {
@@ -1128,6 +1149,7 @@ static int fft_forward_tables(const CallCtx& ctx, const FftPlan& fp, const LeafA
             ba.cross = ctx.band_strict ? 0 : 1;                   // (windows across Nyquist)
             ba.force = band_env() > 0 ? band_env() : 0;
             ba.edge_only = tables_ready ? 1 : 0;
+            ba.stamps = stamps; ba.strict = ctx.band_strict ? 1 : 0;   // (the table cache: validate or build)
             fb.lds = band_lds_bytes(F);
             // the main kernel's workgroups' FIRST blocks are transformed by this launch too (waves 1..7 of the workgroups (f, 0),
             // idle while wave 0 transforms the taps): the one forward transform nothing in the main kernel overlaps with (eleven
@@ -1138,7 +1160,8 @@ static int fft_forward_tables(const CallCtx& ctx, const FftPlan& fp, const LeafA
             size_t prep_dyn = 0;
             // (16-bit PCM: the table launch reads fp32 and bf16 only -- a third sample type in its first-block loads cost the fp32 path
             // 0.9 us of the table launch at cfg1 -- so the main kernel transforms its first blocks itself: the same bits)
-            if (LEAF_WG_SPEC0 && !spec0_off && !tables_ready && main_grid <= kMaxCusForSpec0 && wl.nw <= 12 && io.xtype != kSamplePcm16 && !ctx.mix.lam) {   // (a mixed call likewise: the table launch does not mix)
+            // (the table cache has no first-block spectra -- they depend on x: the main kernel transforms its first blocks itself, the same bits)
+            if (LEAF_WG_SPEC0 && !spec0_off && !tables_ready && !stamps && main_grid <= kMaxCusForSpec0 && wl.nw <= 12 && io.xtype != kSamplePcm16 && !ctx.mix.lam) {   // (a mixed call likewise: the table launch does not mix)
                 ba.x = io.x; ba.io_bf16 = io.xtype; ba.B = B; ba.nblk = fp.nblk; ba.G = main_grid;
                 ba.spec0 = reinterpret_cast<float2*>(dyn + bl.spec0);
                 fb.spec0 = ba.spec0;
@@ -1154,7 +1177,7 @@ static int fft_forward_tables(const CallCtx& ctx, const FftPlan& fp, const LeafA
     }
     if (!tables_ready && !fb.band.rec) {
         hipLaunchKernelGGL(fft_prep_kernel, dim3(F, 1), dim3(kPrepWaves * 64), 0, a.st, a.kernel, a.pool_w, F, K, fp.GZ,
-                           gabor_bounds(K), 1, tp.H, tp.Gz, tp.col_of, fft_lone_taps(tables, F, K));
+                           gabor_bounds(K), 1, tp.H, tp.Gz, tp.col_of, fft_lone_taps(tables, F, K), stamps, hop, T);
         LEAF_LAUNCH_CHECK();
     }
     return LEAF_OK;
@@ -1207,13 +1230,14 @@ static bool fft_wg_fused_finalize(const CallCtx& ctx, const FftPlan& fp, const S
 
 // The overlap-save forward: (tables) -> main kernel -> finalize.  With tables_ready the tables were produced earlier by
 // leaf_fft_prepare_tables_f32 from the same parameters (inference with frozen parameters) and the prep launch is skipped.
+// With `stamps` (leaf_forward_cached_f32) `tables` is the caller's table cache: the prep launch validates or builds it.
 static int fft_forward(const CallCtx& ctx, const FftPlan& fp, const LeafArgs& a, const FwdIo& io, float* tables, float* part,
-                       bool tables_ready, bool use_wg, float* band_scratch = nullptr) {
+                       bool tables_ready, bool use_wg, float* band_scratch = nullptr, unsigned* stamps = nullptr) {
     const auto [B, T, F, K, hop] = a.s;
     const FftTabPtrs tp = fft_tab_ptrs(fp, tables, F);
     record(io.ev, 0, a.st);
     FwdBand fb{};
-    int rc = fft_forward_tables(ctx, fp, a, io, tables, tables_ready, use_wg, band_scratch, fb);
+    int rc = fft_forward_tables(ctx, fp, a, io, tables, tables_ready, use_wg, band_scratch, stamps, fb);
     if (rc != LEAF_OK) return rc;
     record(io.ev, 1, a.st);
     FftParams q{};
@@ -1516,7 +1540,7 @@ static int forward_staged(const LeafArgs& a, const FwdIo& io, float* ws) {
 
 // checks in the order the ABI documents, then one function per path
 static int forward_impl(const void* x, const LeafArgs& a, int flags, CallCtx ctx, void* out, void* workspace, size_t workspace_bytes,
-                        hipEvent_t* ev, float* pooled_raw = nullptr) {
+                        hipEvent_t* ev, float* pooled_raw = nullptr, TableCache tc = TableCache{nullptr, 0}) {
     const auto [B, T, F, K, hop] = a.s;
     const bool out_bf16 = feat_bf16(flags);                                           // what the finalize sites store out as
     const int xtype = x_sample_type(flags);                                           // what the kernels read x as: the two types are independent
@@ -1537,7 +1561,7 @@ static int forward_impl(const void* x, const LeafArgs& a, int flags, CallCtx ctx
         const uintptr_t out_mask = out_bf16 ? 1u : 3u;                                               // bfloat16 features: 2-byte elements
         const uintptr_t x_mask = (flags & (LEAF_FLAG_X_PCM16 | LEAF_FLAG_IO_BF16)) ? 1u : 3u;        // 16-bit PCM / bfloat16 waveform
         if ((reinterpret_cast<uintptr_t>(x) & x_mask) || (reinterpret_cast<uintptr_t>(out) & out_mask) || misaligned16(workspace) ||
-            any_misaligned(a.kernel, a.pool_w, a.pool_b, a.alpha, a.delta, a.root, a.ema_w, pooled_raw))
+            misaligned16(tc.p) || any_misaligned(a.kernel, a.pool_w, a.pool_b, a.alpha, a.delta, a.root, a.ema_w, pooled_raw))
             return LEAF_ERR_ALIGNMENT;
     }
     const FusedPlan pl = make_plan(a.s, ctx.cus);
@@ -1550,6 +1574,17 @@ static int forward_impl(const void* x, const LeafArgs& a, int flags, CallCtx ctx
     if (!workspace || workspace_bytes < need) return LEAF_ERR_WORKSPACE;
     float* ws = static_cast<float*>(workspace);
     const bool overlap_save = ctx.sel == LEAF_ALGO_FFT || ctx.sel == LEAF_ALGO_FFT_WG || ctx.sel == LEAF_ALGO_FFT_SMALL;
+    // The table cache serves the kernels of the 2048-sample plan (workgroup -- static and run-time geometry -- and per wave); every
+    // other plan, a mixed call and a peak-normalised call take the route of leaf_forward_f32 and leave the cache untouched.
+    unsigned* stamps = nullptr;
+    if (tc.p && !ctx.no_table_cache && !ctx.mix.lam && !(flags & LEAF_FLAG_PEAKNORM) && !ev && !pooled_raw &&
+        (ctx.sel == LEAF_ALGO_FFT || (ctx.sel == LEAF_ALGO_FFT_WG && !make_fft4k_plan(a.s).ok))) {
+        const FftPlan fp = make_fft_plan(a.s, ctx.cus);
+        if (fp.ok) {
+            if (tc.bytes < table_cache_floats(fp, a.s) * 4) return LEAF_ERR_WORKSPACE;
+            stamps = table_cache_stamps(fp, tc.p, a.s);
+        }
+    }
     // LEAF_FLAG_PEAKNORM: per-clip scales into the tail of the workspace (the last align_up(B, 64) floats the overlap-save
     // plans reserve), applied to the pooled energies by the finalize step
     float* clip_scale2 = nullptr;
@@ -1573,7 +1608,8 @@ static int forward_impl(const void* x, const LeafArgs& a, int flags, CallCtx ctx
             const FftPlan fp = make_fft_plan(a.s, ctx.cus);
             if (!fp.ok) return LEAF_ERR_BAD_ALGO;
             // [spectra | pooling rows | col_of | band tables], then the partials
-            return fft_forward(ctx, fp, a, io, ws, ws + fft_table_floats(fp, F), /*tables_ready=*/false, ctx.sel == LEAF_ALGO_FFT_WG);
+            return fft_forward(ctx, fp, a, io, stamps ? tc.p : ws, ws + fft_table_floats(fp, F), /*tables_ready=*/false,
+                               ctx.sel == LEAF_ALGO_FFT_WG, nullptr, stamps);
         }
         case LEAF_ALGO_MFMA: return forward_mfma(ctx, pl, a, io, ws);
         default: return forward_staged(a, io, ws);
@@ -1585,6 +1621,21 @@ int leaf_forward_f32(const float* x, int B, int T, const float* kernel, const fl
                      int flags, int algo, float* out, void* workspace, size_t workspace_bytes, void* stream) {
     return forward_impl(x, LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream}, flags,
                         forward_ctx(algo), out, workspace, workspace_bytes, nullptr);
+}
+
+size_t leaf_table_cache_bytes(int F, int K, int hop, int T) {
+    if (check_shape(1, T, F, K, hop) != LEAF_OK) return 0;
+    const Shape s{1, T, F, K, hop};
+    const FftPlan fp = make_fft_plan(s, device_cus());       // (the tables' sizes do not depend on the batch)
+    return fp.ok ? table_cache_floats(fp, s) * 4 : 0;
+}
+
+int leaf_forward_cached_f32(const float* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
+                            const float* alpha, const float* delta, const float* root, const float* ema_w, int F, int K, int hop,
+                            int flags, int algo, float* out, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                            void* stream) {
+    return forward_impl(x, LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream}, flags,
+                        forward_ctx(algo), out, workspace, workspace_bytes, nullptr, nullptr, TableCache{static_cast<float*>(cache), cache_bytes});
 }
 
 int leaf_forward_save_f32(const float* x, int B, int T, const float* kernel, const float* pool_w, const float* pool_b,
@@ -1742,7 +1793,7 @@ int leaf_fft_prepare_tables_f32(const float* kernel, const float* pool_w, int F,
                            gabor_bounds(K), tp.H, tp.Gz, tp.col_of, ba);
     } else {
         hipLaunchKernelGGL(fft_prep_kernel, dim3(F, 1), dim3(kPrepWaves * 64), 0, (hipStream_t)stream, kernel, pool_w, F, K, fp.GZ,
-                           gabor_bounds(K), 1, tp.H, tp.Gz, tp.col_of, fft_lone_taps(t, F, K));
+                           gabor_bounds(K), 1, tp.H, tp.Gz, tp.col_of, fft_lone_taps(t, F, K), (unsigned*)nullptr, hop, 0);
     }
     LEAF_LAUNCH_CHECK();
     return LEAF_OK;
@@ -2258,7 +2309,8 @@ static int backward_fft(const CallCtx& ctx, const LeafArgs& a, const BwdIo& io, 
                            gabor_bounds(K), reinterpret_cast<float2*>(R3), Gz, col_of, ba);
     } else {
         hipLaunchKernelGGL(fft_prep_kernel, dim3(F, 3), dim3(kPrepWaves * 64), 0, a.st, a.kernel, a.pool_w, F, K, fp.GZ,
-                           gabor_bounds(K), 1, reinterpret_cast<float2*>(R3), Gz, col_of, (K & 1) ? (float*)nullptr : ws + L.lone);
+                           gabor_bounds(K), 1, reinterpret_cast<float2*>(R3), Gz, col_of, (K & 1) ? (float*)nullptr : ws + L.lone,
+                           (unsigned*)nullptr, hop, 0);
     }
     LEAF_LAUNCH_CHECK();
     FftParams q{};

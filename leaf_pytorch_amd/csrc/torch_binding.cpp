@@ -8,11 +8,15 @@
 // Plain C++ (compiled with g++ against the torch headers); reference counterpart: leaf_pytorch/frontend.py:78-89 and
 // what autograd derives for it.
 #include <algorithm>
+#include <list>
+#include <mutex>
+#include <tuple>
 
 #include <torch/library.h>
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>      // PyTorch-ROCm presents HIP devices under the "cuda" device type
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
+#include <c10/hip/HIPGraphsC10Utils.h>
 
 #include "leaf_hip.h"
 
@@ -125,6 +129,41 @@ float* io_at(const Tensor& t, size_t elems) {
     return reinterpret_cast<float*>(static_cast<char*>(t.data_ptr()) + elems * (size_t)t.element_size());
 }
 
+// ---- The table caches of the no-grad forward (leaf_hip.h: leaf_forward_cached_f32).  A small per-process LRU of zero-filled device
+// buffers; the key only FINDS a candidate buffer -- whether its tables are valid is decided on the device, by content, in the table
+// launch of every call.  The stream is part of the key so that two streams never share a buffer.  The list is never destroyed (a
+// static destructor would free device memory after the runtime has gone).
+struct TableCaches {
+    using Key = std::tuple<int, int64_t, const void*, const void*, int, int, int, int>;   // device, stream, kernel, pool_w, F, K, hop, T
+    static constexpr size_t kEntries = 8;
+    std::mutex mu;
+    std::list<std::pair<Key, Tensor>> lru;                     // most recently used first
+    int64_t cached_calls = 0, created = 0;
+    Tensor get(const Key& key, size_t bytes, const at::TensorOptions& byte_opt) {
+        std::lock_guard<std::mutex> lock(mu);
+        ++cached_calls;
+        for (auto it = lru.begin(); it != lru.end(); ++it)
+            if (it->first == key && (size_t)it->second.numel() == bytes) {
+                lru.splice(lru.begin(), lru, it);
+                return lru.front().second;
+            }
+        lru.emplace_front(key, at::zeros({(int64_t)bytes}, byte_opt));
+        ++created;
+        if (lru.size() > kEntries) lru.pop_back();
+        return lru.front().second;
+    }
+};
+TableCaches& table_caches() {
+    static TableCaches* c = new TableCaches();
+    return *c;
+}
+// [buffers held, calls sent through leaf_forward_cached_f32, buffers created] -- for tests and tools
+std::vector<int64_t> op_table_cache_info() {
+    TableCaches& c = table_caches();
+    std::lock_guard<std::mutex> lock(c.mu);
+    return {(int64_t)c.lru.size(), c.cached_calls, c.created};
+}
+
 // out_bf16 (LEAF_FLAG_OUT_BF16): bfloat16 features from a float32 or int16 waveform, narrowed where the kernels store them; an explicit
 // argument of the ops, never inferred from a tensor (redundant for a bfloat16 x)
 Tensor forward_impl(const Tensor& x, const Mix* mix, const Params& p, int64_t K, int64_t hop, bool log1p, int64_t algo, Tensor* raw,
@@ -174,8 +213,24 @@ Tensor forward_impl(const Tensor& x, const Mix* mix, const Params& p, int64_t K,
     const size_t wsn = (size_t)ws.numel();
     const float *pk = fptr(p.kernel), *pw = fptr(p.pool_w), *pb = fptr(p.pool_b), *pa = fptr(p.alpha), *pd = fptr(p.delta), *pr = fptr(p.root),
                 *pe = fptr(p.ema_w);
+    // The no-grad forward keeps the tables of the 2048-sample plan in a self-validating cache (leaf_forward_cached_f32).  Not while the
+    // stream is being captured (a captured graph must not allocate or depend on a buffer of this list), not on the training forward, not
+    // for a mixed or peak-normalised call, not with LEAF_ALGO_NO_TABLE_CACHE: those take today's path.  (Fake and meta tensors never
+    // reach this function: their kernels are registered from Python.)
+    const bool cacheable = !raw && !c.mixed && !(flags & LEAF_FLAG_PEAKNORM) && !(algo & LEAF_ALGO_NO_TABLE_CACHE) && !pcm16_staged &&
+                           c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None;
+    const size_t cache_bytes = cacheable ? leaf_table_cache_bytes(F, (int)K, (int)hop, T) : 0;
     for (int64_t b0 = 0; b0 < B; b0 += sl.per_call) {
         const int nb = (int)std::min<int64_t>(sl.per_call, B - b0);
+        Tensor cache;                                           // only where the slice lands on a kernel of the 2048-sample plan
+        if (cache_bytes) {
+            int sel = (int)(algo & 0xff), info[8] = {0};
+            if (sel == LEAF_ALGO_AUTO) sel = leaf_auto_algo(nb, T, F, (int)K, (int)hop);
+            const bool plan4k = sel == LEAF_ALGO_FFT_WG && leaf_fft_plan_info(nb, T, F, (int)K, (int)hop, info) == LEAF_OK && info[0] != 2048;
+            if ((sel == LEAF_ALGO_FFT || sel == LEAF_ALGO_FFT_WG) && !plan4k)
+                cache = table_caches().get(TableCaches::Key{(int)c.x2.device().index(), (int64_t)stream.id(), pk, pw, F, (int)K, (int)hop, T},
+                                           cache_bytes, f32_opt.dtype(at::kByte));
+        }
         Tensor xs;                                              // one slice of an int16 batch as float32, for the staged forward
         if (pcm16_staged) xs = c.x2.narrow(0, b0, nb).to(at::kFloat).mul_(1.0 / 32768.0);
         const float* xin = pcm16_staged ? xs.data_ptr<float>() : io_at(c.x2, (size_t)b0 * T);
@@ -187,6 +242,9 @@ Tensor forward_impl(const Tensor& x, const Mix* mix, const Params& p, int64_t K,
         else if (c.mixed)
             check_status(leaf_forward_mix_f32(xin, c.perm.data_ptr<int>(), fptr(c.lam), nb, T, pk, pw, pb, pa, pd, pr, pe, F, (int)K, (int)hop,
                                               flags, (int)algo, o, wsp, wsn, stream.stream()), "leaf_forward_mix_f32");
+        else if (cache.defined())
+            check_status(leaf_forward_cached_f32(xin, nb, T, pk, pw, pb, pa, pd, pr, pe, F, (int)K, (int)hop, flags, (int)algo, o, wsp, wsn,
+                                                 cache.data_ptr(), (size_t)cache.numel(), stream.stream()), "leaf_forward_cached_f32");
         else if (raw)
             check_status(leaf_forward_save_f32(xin, nb, T, pk, pw, pb, pa, pd, pr, pe, F, (int)K, (int)hop, flags, (int)algo, o, r, wsp, wsn,
                                                stream.stream()), "leaf_forward_save_f32");
@@ -335,6 +393,7 @@ TORCH_LIBRARY(leaf_amd, m) {
           "Tensor? delta, Tensor? root, Tensor? ema_w, int K, int hop, int algo, bool log1p=False, *, bool out_bf16=False) -> (Tensor, Tensor)");
     m.def("backward_mix(Tensor x, Tensor perm, Tensor lam, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, "
           "Tensor? root, Tensor? ema_w, int K, int hop, Tensor grad_out, Tensor? pooled_raw, int flags, *, bool out_bf16=False) -> Tensor[]");
+    m.def("table_cache_info() -> int[]", &op_table_cache_info);
 }
 
 // HIP tensors dispatch under the CUDA key in PyTorch-ROCm
