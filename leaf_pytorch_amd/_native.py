@@ -236,14 +236,47 @@ def _dev_f32(t: torch.Tensor, name: str, device: torch.device) -> torch.Tensor:
     return t.detach().contiguous()
 
 
-def _dev_x(x2: torch.Tensor, device: torch.device):
-    """The waveform buffer of a call and its I/O flags: float32 (0), bfloat16 (FLAG_IO_BF16: the features come back in bfloat16
-    too) or int16 PCM (FLAG_X_PCM16: a sample v means v / 32768, the features are float32)."""
+def _unpack_x(x: torch.Tensor, who: str, mixed: bool = False):
+    """The waveform of a call, (B,1,T) or (B,T), as a contiguous (B,T) buffer on its HIP device, and its I/O flag: float32 (0),
+    bfloat16 (FLAG_IO_BF16: the features come back in bfloat16 too) or int16 PCM (FLAG_X_PCM16: a sample v means v / 32768, the
+    features are float32).  ``mixed``: a call that mixes the clips takes float32 and int16 only."""
+    require_hip(x, who)
+    if x.dim() == 3 and x.shape[1] == 1:
+        x2 = x[:, 0, :]
+    elif x.dim() == 2:
+        x2 = x
+    else:
+        raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
+    if mixed and x2.dtype not in (torch.float32, torch.int16):
+        raise RuntimeError(f"{who}: the mix is defined in float32 on a float32 or int16 (PCM) waveform, got {x2.dtype}")
     if x2.dtype == torch.bfloat16 or x2.dtype == torch.int16:
-        if x2.device != device:
-            raise RuntimeError(f"x is on {x2.device}, expected {device}")
         return x2.detach().contiguous(), (FLAG_IO_BF16 if x2.dtype == torch.bfloat16 else FLAG_X_PCM16)
-    return _dev_f32(x2, "x", device), 0
+    return _dev_f32(x2, "x", x.device), 0
+
+
+def _gather(dev: torch.device, params, pcen: bool, log1p: bool):
+    """The seven parameters as the C ABI reads them -- float32, contiguous, on ``dev``, ``pool_w`` flat; the PCEN four None when PCEN
+    is off (``kernel`` / ``pool_w`` may be None for a call that takes prepared tables instead) -- and the compression's flag bits."""
+    kernel, pool_w, pool_b, alpha, delta, root, ema_w = params
+    kernel = None if kernel is None else _dev_f32(kernel, "kernel", dev)
+    pool_w = None if pool_w is None else _dev_f32(pool_w.reshape(-1), "pool_w", dev)
+    pool_b = _dev_f32(pool_b, "pool_b", dev)
+    if not pcen:
+        return (kernel, pool_w, pool_b, None, None, None, None), (FLAG_LOG1P if log1p else 0)
+    return (kernel, pool_w, pool_b, _dev_f32(alpha, "alpha", dev), _dev_f32(delta, "delta", dev), _dev_f32(root, "root", dev),
+            _dev_f32(ema_w, "ema_w", dev)), FLAG_PCEN
+
+
+def _features(io_flags: int, out_bf16: bool = False):
+    """(``out_bf16`` as the call means it, the feature dtype): bfloat16 features for a bfloat16 waveform, or on request
+    (LEAF_FLAG_OUT_BF16; redundant for a bfloat16 ``x``, where it is dropped)."""
+    out_bf16 = bool(out_bf16) and io_flags != FLAG_IO_BF16
+    return out_bf16, (torch.bfloat16 if io_flags == FLAG_IO_BF16 or out_bf16 else torch.float32)
+
+
+def _check_out(out: torch.Tensor, shape: tuple, dtype: torch.dtype, dev: torch.device) -> None:
+    if (out.dtype != dtype or not out.is_contiguous() or tuple(out.shape) != shape or out.device != dev):
+        raise RuntimeError(f"out must be a contiguous {shape} tensor on {dev} matching the input dtype (float32; bfloat16 for bfloat16 x)")
 
 
 def require_hip(x: torch.Tensor, who: str) -> None:
@@ -255,6 +288,23 @@ def require_hip(x: torch.Tensor, who: str) -> None:
 
 def stream_ptr(device: torch.device) -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _call(dev: torch.device, entry: str, *args, ws=None, after=(), tolerate=()) -> int:
+    """Run the C-ABI entry ``entry`` under the device guard of ``dev`` on its current stream and check the status by the entry's name
+    (a status in ``tolerate`` is returned instead).  Tensors among ``args`` go in as their addresses; the stream is appended.
+    ``ws``: the scratch workspace the entry takes in front of the stream, as its size in bytes or as a function of the loaded library
+    that answers it (asked under the same guard: the plans follow the device's CU count); ``after``: arguments behind the stream."""
+    lib = load()
+    with torch.cuda.device(dev):
+        tail = ()
+        if ws is not None:
+            w = workspace(ws if isinstance(ws, int) else ws(lib), dev)
+            tail = (_ptr(w), w.numel())
+        rc = getattr(lib, entry)(*[ctypes.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args], *tail, stream_ptr(dev), *after)
+    if rc not in tolerate:
+        check(rc, entry)
+    return rc
 
 
 def num_frames(T: int, K: int, hop: int) -> int:
@@ -274,9 +324,9 @@ def band_classes(kernel: torch.Tensor, pool_w: torch.Tensor, K: int, hop: int,
                  pool_b: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
     """Inverse-transform length (256 / 512 / 2048; 512 / 4096 on the 4096-sample plan of the 32 kHz window) each filter gets from the band-limited filter tasks for these parameters
     (leaf_band_classes_f32), as an int32 tensor [F] on the parameters' device; None for a geometry without band tasks.
-    ``pool_b``: the pooling biases the decision is taken for (what a forward call with them runs: the energy bound follows the
-    bias, ABI 5); None: the strict decision (LEAF_ALGO_STRICT_BAND_CLASSES; the backward's)."""
-    lib = load()
+    ``pool_b``: the pooling biases the decision is taken for (what a forward call with them runs, and the default backward: the
+    energy bound follows the bias, ABI 5); None: the strict decision, which looks at no bias (LEAF_ALGO_STRICT_BAND_CLASSES in the
+    forward, LEAF_FLAG_BWD_STRICT_BAND_CLASSES in the backward)."""
     require_hip(kernel, "band_classes")
     dev = kernel.device
     kernel = _dev_f32(kernel, "kernel", dev)
@@ -284,40 +334,113 @@ def band_classes(kernel: torch.Tensor, pool_w: torch.Tensor, K: int, hop: int,
     pool_b = None if pool_b is None else _dev_f32(pool_b.reshape(-1), "pool_b", dev)
     F = kernel.shape[0]
     out = torch.empty(F, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        ws = workspace(max(lib.leaf_fft_tables_bytes(F, K, hop), lib.leaf_workspace_bytes(1, 8192, F, K, hop, ALGO_FFT_WG)), dev)
-        rc = lib.leaf_band_classes_f32(_ptr(kernel), _ptr(pool_w), _ptr(pool_b), F, K, hop, _ptr(out), _ptr(ws), ws.numel(), stream_ptr(dev))
-    if rc == -8:
-        return None
-    check(rc, "leaf_band_classes_f32")
-    return out
+    rc = _call(dev, "leaf_band_classes_f32", kernel, pool_w, pool_b, F, K, hop, out, tolerate=(-8,),
+               ws=lambda lib: max(lib.leaf_fft_tables_bytes(F, K, hop), lib.leaf_workspace_bytes(1, 8192, F, K, hop, ALGO_FFT_WG)))
+    return None if rc == -8 else out
 
 
 def workspace(nbytes: int, device: torch.device) -> torch.Tensor:
     return torch.empty(max(nbytes, 4), dtype=torch.uint8, device=device)
 
 
+CALL_SAMPLES = 1 << 31           # the C ABI indexes the samples of one call with 32 bits: B * T of a call stays below this
+
+
 def batch_slices(B: int, T: int):
     """Slices of whole clips for a batch beyond one C-ABI call.  The C ABI indexes the samples of one call with 32 bits and
     refuses B * T >= 2^31 (LEAF_ERR_BAD_SHAPE); the reference's conv1d takes any batch (frontend.py:78-89), and clips are
     independent, so such a batch goes through in as few balanced slices as possible (the same plan as csrc/torch_binding.cpp)."""
-    most = max(1, ((1 << 31) - 1) // max(T, 1))
+    if T >= CALL_SAMPLES:
+        raise RuntimeError(f"a clip of {T} samples is beyond the C ABI's 32-bit sample index")
+    most = max(1, (CALL_SAMPLES - 1) // max(T, 1))
     calls = max(1, -(-B // most))
     per = -(-B // calls)
     return [(b0, min(B, b0 + per)) for b0 in range(0, B, per)]
 
 
 def _pcm16_lands_on_staged(lib, x2: torch.Tensor, F: int, K: int, hop: int, algo: int) -> bool:
-    """Whether one C-ABI forward call on the batch ``x2`` (int16, or any waveform whose features are to be bfloat16) runs the staged
-    kernels (the explicit selector, or what AUTO resolves to)."""
+    """Whether one C-ABI forward call on the batch ``x2`` runs the staged kernels (the explicit selector, or what AUTO resolves to):
+    they read and store float32 only, so an int16 waveform is widened and bfloat16 features are narrowed on the host around them."""
     B, T = x2.shape
-    if B == 0 or B * T >= (1 << 31):
+    if B == 0 or B * T >= CALL_SAMPLES:
         return False
     sel = algo & 0xff
     if sel == ALGO_AUTO:
         with torch.cuda.device(x2.device):
             sel = lib.leaf_auto_algo(B, T, F, K, hop)
     return sel == ALGO_STAGED
+
+
+def _forward(who: str, x, mix, params, K: int, hop: int, pcen: bool, log1p: bool, algo: int, out=None, save_raw: bool = False,
+             peak_normalize: bool = False, out_bf16: bool = False):
+    """``leaf_forward`` and, with ``mix = (perm, lam)``, ``leaf_forward_mix``.  The mixed call differs as in csrc/torch_binding.cpp:
+    no bfloat16 x, one C-ABI call (a batch cannot be mixed across slices), the ``*_mix_*`` entry and workspace query."""
+    lib = load()
+    x2, flags = _unpack_x(x, who, mix is not None)
+    dev = x.device
+    B, T = x2.shape
+    mix = () if mix is None else mix_args(*mix, B, dev)
+    F = params[0].shape[0]
+    prm, compression = _gather(dev, params, pcen, log1p)
+    prm = [_ptr(p) for p in prm]
+    TP = lib.leaf_num_frames(T, K, hop)
+    if TP < 1:
+        raise RuntimeError(f"bad shape B={B} T={T} K={K} hop={hop}")
+    out_bf16, feat = _features(flags, out_bf16)
+    if out is not None:
+        _check_out(out, (B, F, TP), feat, dev)
+    if (algo & 0xff) not in (ALGO_AUTO, ALGO_STAGED, ALGO_MFMA, ALGO_FFT, ALGO_FFT_WG, ALGO_FFT_SMALL):
+        raise RuntimeError(f"unknown algorithm selector {algo & 0xff}")
+    # the staged forward reads and stores float32 only (LEAF_ERR_UNSUPPORTED from the C ABI).  Where the call lands on it, bfloat16
+    # features are narrowed here -- the same rounding, so the same bits -- and an int16 waveform is converted here -- the same values,
+    # v / 32768 exactly (a mixed call writes its float32 mix into the workspace anyway; a batch beyond one call: slice by slice)
+    staged = (out_bf16 or flags == FLAG_X_PCM16) and _pcm16_lands_on_staged(lib, x2, F, K, hop, algo)
+    narrow = out_bf16 and staged
+    if flags == FLAG_X_PCM16:
+        peak_normalize = False                     # |v / 32768| <= 1: nothing to normalise for int16, and nothing is launched
+        if staged and not mix:
+            x2, flags = x2.float().mul_(2.0 ** -15), 0
+    if out_bf16 and not narrow:
+        flags |= FLAG_OUT_BF16
+    if peak_normalize:
+        flags |= FLAG_PEAKNORM                     # forward of the peak-normalised clips, the scale folded into the finalize
+    flags |= compression
+    if B == 0:
+        # the empty batch: (0, F, T') like the reference (frontend.py:78-89 -> convolution.py:97); nothing is launched
+        # (`out`, the selector and the flags are validated above, and a caller-supplied `out` is what comes back)
+        if save_raw and (flags & FLAG_PEAKNORM):
+            raise RuntimeError("the folded PeakNormalization prologue is forward-only")
+        empty = out if out is not None else torch.empty((0, F, TP), dtype=feat, device=dev)
+        return (empty, torch.empty((0, F, TP), dtype=torch.float32, device=dev)) if save_raw else empty
+    if B * T >= CALL_SAMPLES:
+        if mix:
+            raise RuntimeError(f"{who}: a batch beyond one C-ABI call (B * T >= 2^31) cannot be mixed across its slices")
+        # one C-ABI call per slice of whole clips, into the one output (see batch_slices: it refuses a clip beyond one call first)
+        slices = batch_slices(B, T)
+        raw = torch.empty((B, F, TP), dtype=torch.float32, device=dev) if save_raw else None
+        if out is None:
+            out = torch.empty((B, F, TP), dtype=feat, device=dev)
+        for b0, b1 in slices:
+            r = _forward(who, x2[b0:b1], None, params, K, hop, pcen, log1p, algo, out[b0:b1], save_raw, peak_normalize, out_bf16)
+            if save_raw:
+                raw[b0:b1].copy_(r[1])
+        return (out, raw) if save_raw else out
+    res = out if out is not None and not narrow else torch.empty((B, F, TP), dtype=torch.float32 if narrow else feat, device=dev)
+    raw = torch.empty((B, F, TP), dtype=torch.float32, device=dev) if save_raw else None
+    head = (_ptr(x2), _ptr(mix[0]), _ptr(mix[1]), B, T) if mix else (_ptr(x2), B, T)
+    with torch.cuda.device(dev):
+        ws = workspace((lib.leaf_forward_mix_workspace_bytes if mix else lib.leaf_workspace_bytes)(B, T, F, K, hop, algo), dev)
+        if save_raw:
+            entry = lib.leaf_forward_save_mix_f32 if mix else lib.leaf_forward_save_f32
+            rc = entry(*head, *prm, F, K, hop, flags, algo, _ptr(res), _ptr(raw), _ptr(ws), ws.numel(), stream_ptr(dev))
+        else:
+            entry = lib.leaf_forward_mix_f32 if mix else lib.leaf_forward_f32
+            rc = entry(*head, *prm, F, K, hop, flags, algo, _ptr(res), _ptr(ws), ws.numel(), stream_ptr(dev))
+    if rc:
+        check(rc, "leaf_forward" + ("_save" if save_raw else "") + ("_mix" if mix else "") + "_f32")
+    if narrow:
+        res = res.to(torch.bfloat16) if out is None else out.copy_(res)
+    return (res, raw) if save_raw else res
 
 
 def leaf_forward(x: torch.Tensor, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int,
@@ -328,96 +451,78 @@ def leaf_forward(x: torch.Tensor, kernel, pool_w, pool_b, alpha, delta, root, em
     ``save_raw``: then returns (out, pooled_raw) for the backward).  ``out_bf16``: bfloat16 features from a float32 or int16
     waveform (LEAF_FLAG_OUT_BF16) -- the float32 call's result rounded to nearest even where the kernels store it; the mode is
     explicit, never inferred from a tensor's dtype (redundant for a bfloat16 ``x``)."""
+    return _forward("leaf_forward", x, None, (kernel, pool_w, pool_b, alpha, delta, root, ema_w), K, hop, pcen, log1p, algo, out, save_raw,
+                    peak_normalize, out_bf16)
+
+
+def backward_flags(pcen: bool = False, staged: bool = False, mfma: bool = False, full_transforms: bool = False,
+                   strict_band_classes: bool = False, log1p: bool = False, io_flags: int = 0) -> int:
+    """The ``flags`` of leaf_backward_f32 / leaf_backward_mix_f32 (``full_transforms``: no band-limited filter tasks in the backward;
+    ``log1p`` is ignored with PCEN on, as in the forward; ``io_flags``: the waveform's and the features' dtype bits)."""
+    return ((FLAG_PCEN if pcen else 0) | (FLAG_BWD_STAGED if staged else 0) | (FLAG_BWD_MFMA if mfma else 0) |
+            (FLAG_BWD_FULL_TRANSFORMS if full_transforms else 0) | (FLAG_BWD_STRICT_BAND_CLASSES if strict_band_classes else 0) |
+            (FLAG_LOG1P if log1p and not pcen else 0) | io_flags)
+
+
+def _backward(who: str, x, mix, params, K: int, hop: int, grad_out: torch.Tensor, flags: int, need_dx: bool, pooled_raw, out_bf16: bool):
+    """``leaf_backward`` and, with ``mix = (perm, lam)``, ``leaf_backward_mix`` (one C-ABI call, no dL/dx, the ``*_mix_*`` entry and
+    workspace query).  ``flags``: the path and compression bits of ``backward_flags``; the dtype bits are added here."""
+    pcen = bool(flags & FLAG_PCEN)
     lib = load()
-    require_hip(x, "leaf_forward")
-    if x.dim() == 3:
-        if x.shape[1] != 1:
-            raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
-        x2 = x[:, 0, :]
-    elif x.dim() == 2:
-        x2 = x
-    else:
-        raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
+    x2, io_flags = _unpack_x(x, who, mix is not None)
     dev = x.device
-    # extensions: bf16 waveform in, bf16 features out; int16 PCM waveform in (v / 32768), float32 features out; fp32 arithmetic
-    x2, flags = _dev_x(x2, dev)
-    out_bf16 = bool(out_bf16) and flags != FLAG_IO_BF16    # (a bfloat16 x: the features are bfloat16 already)
-    io_bf16 = flags == FLAG_IO_BF16 or out_bf16            # the FEATURE dtype below
+    if io_flags == FLAG_X_PCM16 and need_dx:
+        raise RuntimeError("an int16 (PCM) input has no gradient: need_dx=True needs a float32 or bfloat16 x")
     B, T = x2.shape
-    F = kernel.shape[0]
-    kernel = _dev_f32(kernel, "kernel", dev)
-    pool_w = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
-    pool_b = _dev_f32(pool_b, "pool_b", dev)
-    if out_bf16 and _pcm16_lands_on_staged(lib, x2, F, K, hop, algo):
-        # the staged forward stores float32 only (LEAF_ERR_UNSUPPORTED from the C ABI): run it in float32 and narrow here -- the
-        # same rounding, so the same bits (how an int16 waveform is handled on that path, below)
-        if out is not None and (out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != dev
-                                or tuple(out.shape) != (B, F, lib.leaf_num_frames(T, K, hop))):
-            raise RuntimeError(f"out must be a contiguous {(B, F, lib.leaf_num_frames(T, K, hop))} tensor on {dev} matching the input dtype (float32; bfloat16 for bfloat16 x)")
-        r = leaf_forward(x2, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen=pcen, log1p=log1p, algo=algo,
-                         save_raw=save_raw, peak_normalize=peak_normalize)
-        f32 = r[0] if save_raw else r
-        narrowed = f32.to(torch.bfloat16) if out is None else out.copy_(f32)
-        return (narrowed, r[1]) if save_raw else narrowed
-    if out_bf16:
-        flags |= FLAG_OUT_BF16
-    if flags & FLAG_X_PCM16:
-        peak_normalize = False                     # |v / 32768| <= 1: nothing to normalise for int16, and nothing is launched
-        # the staged forward reads float32 only (LEAF_ERR_UNSUPPORTED from the C ABI): where the call lands on it, convert here
-        # -- the same values, v / 32768 exactly -- and run the float path (a batch beyond one C-ABI call: slice by slice, below)
-        if _pcm16_lands_on_staged(lib, x2, F, K, hop, algo):
-            x2, flags = x2.float().mul_(2.0 ** -15), 0         # (never with out_bf16: that call took the branch above)
-    if peak_normalize:
-        flags |= FLAG_PEAKNORM                     # forward of the peak-normalised clips, the scale folded into the finalize
-    if pcen:
-        flags |= FLAG_PCEN
-        alpha, delta, root, ema_w = (_dev_f32(t, n, dev) for t, n in
-                                     ((alpha, "alpha"), (delta, "delta"), (root, "root"), (ema_w, "ema_w")))
+    mix = () if mix is None else mix_args(*mix, B, dev)
+    F = params[0].shape[0]
+    prm, _ = _gather(dev, params, pcen, False)
+    out_bf16 = bool(out_bf16) and io_flags != FLAG_IO_BF16     # (a bfloat16 x: grad_out is bfloat16 already)
+    if io_flags == FLAG_IO_BF16 or out_bf16:
+        if grad_out.dtype != torch.bfloat16 or grad_out.device != dev:
+            raise RuntimeError(f"grad_out must be bfloat16 on {dev} {'with out_bf16=True' if out_bf16 else 'when x is bfloat16'}, "
+                               f"got {grad_out.dtype} on {grad_out.device}")
+        go = grad_out.detach().contiguous()
+        io_flags |= FLAG_OUT_BF16 if out_bf16 else 0
     else:
-        alpha = delta = root = ema_w = None
-        if log1p:
-            flags |= FLAG_LOG1P
+        go = _dev_f32(grad_out, "grad_out", dev)
     TP = lib.leaf_num_frames(T, K, hop)
-    if TP < 1:
-        raise RuntimeError(f"bad shape B={B} T={T} K={K} hop={hop}")
-    if out is not None and (out.dtype != (torch.bfloat16 if io_bf16 else torch.float32) or not out.is_contiguous()
-                            or tuple(out.shape) != (B, F, TP) or out.device != dev):
-        raise RuntimeError(f"out must be a contiguous {(B, F, TP)} tensor on {dev} matching the input dtype (float32; bfloat16 for bfloat16 x)")
-    if (algo & 0xff) not in (ALGO_AUTO, ALGO_STAGED, ALGO_MFMA, ALGO_FFT, ALGO_FFT_WG, ALGO_FFT_SMALL):
-        raise RuntimeError(f"unknown algorithm selector {algo & 0xff}")
-    if B == 0:
-        # the empty batch: (0, F, T') like the reference (frontend.py:78-89 -> convolution.py:97); nothing is launched
-        # (`out`, the selector and the flags are validated above, and a caller-supplied `out` is what comes back)
-        if save_raw and (flags & FLAG_PEAKNORM):
-            raise RuntimeError("the folded PeakNormalization prologue is forward-only")
-        empty = out if out is not None else torch.empty((0, F, TP), dtype=torch.bfloat16 if io_bf16 else torch.float32, device=dev)
-        return (empty, torch.empty((0, F, TP), dtype=torch.float32, device=dev)) if save_raw else empty
-    if out is None:
-        out = torch.empty((B, F, TP), dtype=torch.bfloat16 if io_bf16 else torch.float32, device=dev)
-    if B * T >= (1 << 31):
-        # one C-ABI call per slice of whole clips, into the one output (see batch_slices)
-        raw = torch.empty((B, F, TP), dtype=torch.float32, device=dev) if save_raw else None
+    if tuple(go.shape) != (B, F, TP):
+        raise RuntimeError(f"grad_out has shape {tuple(go.shape)}, expected {(B, F, TP)}")
+    grads = [torch.empty_like(p) for p in prm[:3]] + [torch.empty(F, dtype=torch.float32, device=dev) if pcen else None for _ in range(4)]
+    g_x = torch.empty_like(x2) if need_dx else None
+    if B == 0:                                     # the sum over no clips: zero parameter gradients, nothing launched
+        for g in grads:
+            if g is not None:
+                g.zero_()
+    elif B * T >= CALL_SAMPLES:
+        if mix:
+            raise RuntimeError(f"{who}: a batch beyond one C-ABI call (B * T >= 2^31) cannot be mixed across its slices")
+        # slices of whole clips (batch_slices); parameter gradients added in slice order (fixed: bit-reproducible)
+        total = None
         for b0, b1 in batch_slices(B, T):
-            r = leaf_forward(x2[b0:b1], kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen=pcen, log1p=log1p, algo=algo,
-                             out=out[b0:b1], save_raw=save_raw, peak_normalize=peak_normalize, out_bf16=out_bf16)
-            if save_raw:
-                raw[b0:b1].copy_(r[1])
-        return (out, raw) if save_raw else out
-    with torch.cuda.device(dev):
-        nbytes = lib.leaf_workspace_bytes(B, T, F, K, hop, algo)
-        ws = workspace(nbytes, dev)
-        if save_raw:
-            raw = torch.empty((B, F, TP), dtype=torch.float32, device=dev)
-            rc = lib.leaf_forward_save_f32(_ptr(x2), B, T, _ptr(kernel), _ptr(pool_w), _ptr(pool_b), _ptr(alpha),
-                                           _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, algo, _ptr(out),
-                                           _ptr(raw), _ptr(ws), ws.numel(), stream_ptr(dev))
-            check(rc, "leaf_forward_save_f32")
-            return out, raw
-        rc = lib.leaf_forward_f32(_ptr(x2), B, T, _ptr(kernel), _ptr(pool_w), _ptr(pool_b), _ptr(alpha), _ptr(delta),
-                                  _ptr(root), _ptr(ema_w), F, K, hop, flags, algo, _ptr(out), _ptr(ws),
-                                  ws.numel(), stream_ptr(dev))
-    check(rc, "leaf_forward_f32")
-    return out
+            g = _backward(who, x2[b0:b1], None, params, K, hop, go[b0:b1], flags, need_dx, None if pooled_raw is None else pooled_raw[b0:b1],
+                          out_bf16)
+            if need_dx:
+                g_x[b0:b1].copy_(g[7])
+            total = list(g[:7]) if total is None else [None if a is None else a.add_(b) for a, b in zip(total, g[:7])]
+        return (*total, g_x)
+    else:
+        flags |= io_flags
+        tail = (F, K, hop, flags, _ptr(go), _ptr(pooled_raw), *[_ptr(g) for g in grads], _ptr(g_x))
+        with torch.cuda.device(dev):
+            # sized for the path these flags select (a few MB for the overlap-save backward, not the staged path's dL/dy)
+            if mix:
+                entry = "leaf_backward_mix_f32"
+                ws = workspace(lib.leaf_backward_mix_workspace_bytes(B, T, F, K, hop, flags), dev)
+                rc = lib.leaf_backward_mix_f32(_ptr(x2), _ptr(mix[0]), _ptr(mix[1]), B, T, *[_ptr(p) for p in prm], *tail, _ptr(ws), ws.numel(), stream_ptr(dev))
+            else:
+                entry = "leaf_backward_f32"
+                ws = workspace(lib.leaf_backward_workspace_bytes(B, T, F, K, hop, flags, int(need_dx)), dev)
+                rc = lib.leaf_backward_f32(_ptr(x2), B, T, *[_ptr(p) for p in prm], *tail, _ptr(ws), ws.numel(), stream_ptr(dev))
+        if rc:
+            check(rc, entry)
+    return (grads[0], grads[1].reshape(params[1].shape), *grads[2:], g_x)
 
 
 def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, grad_out: torch.Tensor,
@@ -432,73 +537,8 @@ def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, 
     and has no dL/dx (``need_dx=True`` raises).  ``out_bf16`` (LEAF_FLAG_OUT_BF16, the backward of ``leaf_forward(..., out_bf16=True)``):
     ``grad_out`` alone is bfloat16, widened where the kernels read it -- the gradients are those of the call on ``grad_out.float()``
     bit for bit; ``x`` stays float32 (dL/dx float32) or int16."""
-    lib = load()
-    require_hip(x, "leaf_backward")
-    dev = x.device
-    x2 = x[:, 0, :] if x.dim() == 3 else x
-    x2, io_flags = _dev_x(x2, dev)
-    io_bf16 = io_flags == FLAG_IO_BF16
-    if (io_flags & FLAG_X_PCM16) and need_dx:
-        raise RuntimeError("an int16 (PCM) input has no gradient: need_dx=True needs a float32 or bfloat16 x")
-    B, T = x2.shape
-    F = kernel.shape[0]
-    kernel = _dev_f32(kernel, "kernel", dev)
-    pw = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
-    pb = _dev_f32(pool_b, "pool_b", dev)
-    out_bf16 = bool(out_bf16) and not io_bf16              # (a bfloat16 x: grad_out is bfloat16 already)
-    if io_bf16:
-        if grad_out.dtype != torch.bfloat16 or grad_out.device != dev:
-            raise RuntimeError(f"grad_out must be bfloat16 on {dev} when x is bfloat16, got {grad_out.dtype} on {grad_out.device}")
-        go = grad_out.detach().contiguous()
-    elif out_bf16:
-        if grad_out.dtype != torch.bfloat16 or grad_out.device != dev:
-            raise RuntimeError(f"grad_out must be bfloat16 on {dev} with out_bf16=True, got {grad_out.dtype} on {grad_out.device}")
-        go = grad_out.detach().contiguous()
-        io_flags |= FLAG_OUT_BF16
-    else:
-        go = _dev_f32(grad_out, "grad_out", dev)
-    TP = lib.leaf_num_frames(T, K, hop)
-    if tuple(go.shape) != (B, F, TP):
-        raise RuntimeError(f"grad_out has shape {tuple(go.shape)}, expected {(B, F, TP)}")
-    g_kernel = torch.empty_like(kernel)
-    g_pw, g_pb = torch.empty_like(pw), torch.empty_like(pb)
-    if pcen:
-        alpha, delta, root, ema_w = (_dev_f32(t, "pcen param", dev) for t in (alpha, delta, root, ema_w))
-        g_pc = [torch.empty(F, dtype=torch.float32, device=dev) for _ in range(4)]
-    else:
-        alpha = delta = root = ema_w = None
-        g_pc = [None] * 4
-    g_x = torch.empty_like(x2) if need_dx else None
-    if B == 0:                                     # the sum over no clips: zero parameter gradients, nothing launched
-        for g in (g_kernel, g_pw, g_pb, *g_pc):
-            if g is not None:
-                g.zero_()
-        return g_kernel, g_pw.reshape(pool_w.shape), g_pb, g_pc[0], g_pc[1], g_pc[2], g_pc[3], g_x
-    if B * T >= (1 << 31):
-        # slices of whole clips (batch_slices); parameter gradients added in slice order (fixed: bit-reproducible)
-        total = None
-        for b0, b1 in batch_slices(B, T):
-            g = leaf_backward(x2[b0:b1], kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, go[b0:b1], pcen=pcen, need_dx=need_dx,
-                              staged=staged, pooled_raw=None if pooled_raw is None else pooled_raw[b0:b1], mfma=mfma,
-                              full_transforms=full_transforms, strict_band_classes=strict_band_classes, log1p=log1p, out_bf16=out_bf16)
-            if need_dx:
-                g_x[b0:b1].copy_(g[7])
-            total = list(g[:7]) if total is None else [None if a is None else a.add_(b) for a, b in zip(total, g[:7])]
-        return (*total, g_x)
-    flags = ((FLAG_PCEN if pcen else 0) | (FLAG_BWD_STAGED if staged else 0) | (FLAG_BWD_MFMA if mfma else 0) |
-             (FLAG_BWD_FULL_TRANSFORMS if full_transforms else 0) |   # full_transforms: no band-limited filter tasks in the backward
-             (FLAG_BWD_STRICT_BAND_CLASSES if strict_band_classes else 0) |
-             (FLAG_LOG1P if log1p and not pcen else 0) | io_flags)
-    with torch.cuda.device(dev):
-        # sized for the path these flags select (a few MB for the overlap-save backward, not the staged path's dL/dy)
-        ws = workspace(lib.leaf_backward_workspace_bytes(B, T, F, K, hop, flags, int(need_dx)), dev)
-        rc = lib.leaf_backward_f32(_ptr(x2), B, T, _ptr(kernel), _ptr(pw), _ptr(pb), _ptr(alpha), _ptr(delta), _ptr(root),
-                                   _ptr(ema_w), F, K, hop, flags,
-                                   _ptr(go), _ptr(pooled_raw), _ptr(g_kernel), _ptr(g_pw),
-                                   _ptr(g_pb), _ptr(g_pc[0]), _ptr(g_pc[1]), _ptr(g_pc[2]), _ptr(g_pc[3]), _ptr(g_x),
-                                   _ptr(ws), ws.numel(), stream_ptr(dev))
-    check(rc, "leaf_backward_f32")
-    return g_kernel, g_pw.reshape(pool_w.shape), g_pb, g_pc[0], g_pc[1], g_pc[2], g_pc[3], g_x
+    return _backward("leaf_backward", x, None, (kernel, pool_w, pool_b, alpha, delta, root, ema_w), K, hop, grad_out,
+                     backward_flags(pcen, staged, mfma, full_transforms, strict_band_classes, log1p), need_dx, pooled_raw, out_bf16)
 
 
 def mix_args(perm, lam, B: int, device: torch.device):
@@ -525,34 +565,18 @@ def mix_args(perm, lam, B: int, device: torch.device):
     return (perm.detach().to(device=device, dtype=torch.int32).contiguous(), lam.detach().to(device=device).contiguous())
 
 
-def _mix_x(x: torch.Tensor, who: str) -> torch.Tensor:
-    require_hip(x, who)
-    if x.dim() == 3 and x.shape[1] == 1:
-        x2 = x[:, 0, :]
-    elif x.dim() == 2:
-        x2 = x
-    else:
-        raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
-    if x2.dtype not in (torch.float32, torch.int16):
-        raise RuntimeError(f"{who}: the mix is defined in float32 on a float32 or int16 (PCM) waveform, got {x2.dtype}")
-    return x2.detach().contiguous()
-
-
 def mixup(x: torch.Tensor, perm, lam) -> torch.Tensor:
     """The mixed waveform itself (leaf_mixup_f32): x (B,1,T) or (B,T), float32 or int16 PCM (v / 32768) ->
     float32 of the same shape, ``x * lam + x[perm] * (1 - lam)`` per clip with separately rounded fp32 operations."""
-    lib = load()
-    x2 = _mix_x(x, "mixup")
+    x2, flags = _unpack_x(x, "mixup", mixed=True)
     B, T = x2.shape
     dev = x2.device
     perm, lam = mix_args(perm, lam, B, dev)
     out = torch.empty((B, T), dtype=torch.float32, device=dev)
-    if B * T >= (1 << 31):
+    if B * T >= CALL_SAMPLES:
         raise RuntimeError("mixup: a batch beyond one C-ABI call (B * T >= 2^31) cannot be mixed across its slices")
     if B and T:
-        with torch.cuda.device(dev):
-            check(lib.leaf_mixup_f32(_ptr(x2), B, T, _ptr(perm), _ptr(lam), FLAG_X_PCM16 if x2.dtype == torch.int16 else 0, _ptr(out),
-                                     stream_ptr(dev)), "leaf_mixup_f32")
+        _call(dev, "leaf_mixup_f32", x2, B, T, perm, lam, flags, out)
     return out.reshape(x.shape)
 
 
@@ -561,52 +585,8 @@ def leaf_forward_mix(x: torch.Tensor, perm, lam, kernel, pool_w, pool_b, alpha, 
     """``leaf_forward`` of the mixed batch ``x * lam + x[perm] * (1 - lam)`` without materialising it where the kernels mix in their
     loads (leaf_forward_mix_f32 / leaf_forward_save_mix_f32).  x float32 or int16 PCM; bfloat16 raises.  ``out_bf16``: bfloat16
     features (LEAF_FLAG_OUT_BF16), the float32 result rounded where it is stored."""
-    lib = load()
-    x2 = _mix_x(x, "leaf_forward_mix")
-    dev = x2.device
-    B, T = x2.shape
-    perm, lam = mix_args(perm, lam, B, dev)
-    flags = FLAG_X_PCM16 if x2.dtype == torch.int16 else 0
-    F = kernel.shape[0]
-    kernel = _dev_f32(kernel, "kernel", dev)
-    pool_w = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
-    pool_b = _dev_f32(pool_b, "pool_b", dev)
-    if pcen:
-        flags |= FLAG_PCEN
-        alpha, delta, root, ema_w = (_dev_f32(t, n, dev) for t, n in
-                                     ((alpha, "alpha"), (delta, "delta"), (root, "root"), (ema_w, "ema_w")))
-    else:
-        alpha = delta = root = ema_w = None
-        if log1p:
-            flags |= FLAG_LOG1P
-    TP = lib.leaf_num_frames(T, K, hop)
-    if TP < 1:
-        raise RuntimeError(f"bad shape B={B} T={T} K={K} hop={hop}")
-    if (algo & 0xff) not in (ALGO_AUTO, ALGO_STAGED, ALGO_MFMA, ALGO_FFT, ALGO_FFT_WG, ALGO_FFT_SMALL):
-        raise RuntimeError(f"unknown algorithm selector {algo & 0xff}")
-    staged_cast = bool(out_bf16) and _pcm16_lands_on_staged(lib, x2, F, K, hop, algo)   # the staged forward stores float32: narrow here
-    if out_bf16 and not staged_cast:
-        flags |= FLAG_OUT_BF16
-    out = torch.empty((B, F, TP), dtype=torch.bfloat16 if flags & FLAG_OUT_BF16 else torch.float32, device=dev)
-    raw = torch.empty((B, F, TP), dtype=torch.float32, device=dev) if save_raw else None
-    if B == 0:
-        out = out.to(torch.bfloat16) if out_bf16 else out
-        return (out, raw) if save_raw else out
-    if B * T >= (1 << 31):
-        raise RuntimeError("leaf_forward_mix: a batch beyond one C-ABI call (B * T >= 2^31) cannot be mixed across its slices")
-    with torch.cuda.device(dev):
-        ws = workspace(lib.leaf_forward_mix_workspace_bytes(B, T, F, K, hop, algo), dev)
-        if save_raw:
-            rc = lib.leaf_forward_save_mix_f32(_ptr(x2), _ptr(perm), _ptr(lam), B, T, _ptr(kernel), _ptr(pool_w), _ptr(pool_b),
-                                               _ptr(alpha), _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, algo, _ptr(out),
-                                               _ptr(raw), _ptr(ws), ws.numel(), stream_ptr(dev))
-            check(rc, "leaf_forward_save_mix_f32")
-            return (out.to(torch.bfloat16) if staged_cast else out), raw
-        rc = lib.leaf_forward_mix_f32(_ptr(x2), _ptr(perm), _ptr(lam), B, T, _ptr(kernel), _ptr(pool_w), _ptr(pool_b), _ptr(alpha),
-                                      _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, algo, _ptr(out), _ptr(ws), ws.numel(),
-                                      stream_ptr(dev))
-    check(rc, "leaf_forward_mix_f32")
-    return out.to(torch.bfloat16) if staged_cast else out
+    return _forward("leaf_forward_mix", x, (perm, lam), (kernel, pool_w, pool_b, alpha, delta, root, ema_w), K, hop, pcen, log1p, algo,
+                    save_raw=save_raw, out_bf16=out_bf16)
 
 
 def leaf_backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, grad_out: torch.Tensor,
@@ -614,51 +594,8 @@ def leaf_backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, 
                       full_transforms: bool = False, strict_band_classes: bool = False, log1p: bool = False, out_bf16: bool = False):
     """Parameter gradients of ``leaf_forward_mix`` (leaf_backward_mix_f32): the seven of ``leaf_backward`` and None for dL/dx,
     which a mixed call does not have.  ``out_bf16``: ``grad_out`` is bfloat16 (LEAF_FLAG_OUT_BF16), widened where it is read."""
-    lib = load()
-    x2 = _mix_x(x, "leaf_backward_mix")
-    dev = x2.device
-    B, T = x2.shape
-    perm, lam = mix_args(perm, lam, B, dev)
-    F = kernel.shape[0]
-    kernel = _dev_f32(kernel, "kernel", dev)
-    pw = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
-    pb = _dev_f32(pool_b, "pool_b", dev)
-    if out_bf16:
-        if grad_out.dtype != torch.bfloat16 or grad_out.device != dev:
-            raise RuntimeError(f"grad_out must be bfloat16 on {dev} with out_bf16=True, got {grad_out.dtype} on {grad_out.device}")
-        go = grad_out.detach().contiguous()
-    else:
-        go = _dev_f32(grad_out, "grad_out", dev)
-    TP = lib.leaf_num_frames(T, K, hop)
-    if tuple(go.shape) != (B, F, TP):
-        raise RuntimeError(f"grad_out has shape {tuple(go.shape)}, expected {(B, F, TP)}")
-    g_kernel = torch.empty_like(kernel)
-    g_pw, g_pb = torch.empty_like(pw), torch.empty_like(pb)
-    if pcen:
-        alpha, delta, root, ema_w = (_dev_f32(t, "pcen param", dev) for t in (alpha, delta, root, ema_w))
-        g_pc = [torch.empty(F, dtype=torch.float32, device=dev) for _ in range(4)]
-    else:
-        alpha = delta = root = ema_w = None
-        g_pc = [None] * 4
-    if B == 0:
-        for g in (g_kernel, g_pw, g_pb, *g_pc):
-            if g is not None:
-                g.zero_()
-        return g_kernel, g_pw.reshape(pool_w.shape), g_pb, g_pc[0], g_pc[1], g_pc[2], g_pc[3], None
-    if B * T >= (1 << 31):
-        raise RuntimeError("leaf_backward_mix: a batch beyond one C-ABI call (B * T >= 2^31) cannot be mixed across its slices")
-    flags = ((FLAG_PCEN if pcen else 0) | (FLAG_BWD_STAGED if staged else 0) | (FLAG_BWD_MFMA if mfma else 0) |
-             (FLAG_BWD_FULL_TRANSFORMS if full_transforms else 0) | (FLAG_BWD_STRICT_BAND_CLASSES if strict_band_classes else 0) |
-             (FLAG_LOG1P if log1p and not pcen else 0) | (FLAG_X_PCM16 if x2.dtype == torch.int16 else 0) |
-             (FLAG_OUT_BF16 if out_bf16 else 0))
-    with torch.cuda.device(dev):
-        ws = workspace(lib.leaf_backward_mix_workspace_bytes(B, T, F, K, hop, flags), dev)
-        rc = lib.leaf_backward_mix_f32(_ptr(x2), _ptr(perm), _ptr(lam), B, T, _ptr(kernel), _ptr(pw), _ptr(pb), _ptr(alpha),
-                                       _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, _ptr(go), _ptr(pooled_raw),
-                                       _ptr(g_kernel), _ptr(g_pw), _ptr(g_pb), _ptr(g_pc[0]), _ptr(g_pc[1]), _ptr(g_pc[2]),
-                                       _ptr(g_pc[3]), None, _ptr(ws), ws.numel(), stream_ptr(dev))
-    check(rc, "leaf_backward_mix_f32")
-    return g_kernel, g_pw.reshape(pool_w.shape), g_pb, g_pc[0], g_pc[1], g_pc[2], g_pc[3], None
+    return _backward("leaf_backward_mix", x, (perm, lam), (kernel, pool_w, pool_b, alpha, delta, root, ema_w), K, hop, grad_out,
+                     backward_flags(pcen, staged, mfma, full_transforms, strict_band_classes, log1p), False, pooled_raw, out_bf16)
 
 
 def leaf_forward_profiled(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, hop: int, pcen: bool = True,
@@ -666,55 +603,38 @@ def leaf_forward_profiled(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, 
     """Measurement call: returns (out, [taps_ms, fused_ms, finalize_ms]) from HIP events on the current stream.  Same flags
     as ``leaf_forward`` (PCEN on / off, log1p, bfloat16 I/O when ``x`` is bfloat16, PCM input when it is int16), so every BASELINE config can be timed."""
     lib = load()
-    require_hip(x, "leaf_forward_profiled")
+    x2, flags = _unpack_x(x, "leaf_forward_profiled")
     dev = x.device
-    x2 = x[:, 0, :] if x.dim() == 3 else x
-    x2, flags = _dev_x(x2, dev)
-    io_bf16 = flags == FLAG_IO_BF16
     B, T = x2.shape
     F = kernel.shape[0]
-    kernel = _dev_f32(kernel, "kernel", dev)
-    pool_w = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
-    pool_b = _dev_f32(pool_b, "pool_b", dev)
-    if pcen:
-        flags |= FLAG_PCEN
-        alpha, delta, root, ema_w = (_dev_f32(t, "pcen param", dev) for t in (alpha, delta, root, ema_w))
-    else:
-        alpha = delta = root = ema_w = None
-        if log1p:
-            flags |= FLAG_LOG1P
-    out = torch.empty((B, F, lib.leaf_num_frames(T, K, hop)), dtype=torch.bfloat16 if io_bf16 else torch.float32, device=dev)
+    prm, compression = _gather(dev, (kernel, pool_w, pool_b, alpha, delta, root, ema_w), pcen, log1p)
+    _, feat = _features(flags)
+    out = torch.empty((B, F, lib.leaf_num_frames(T, K, hop)), dtype=feat, device=dev)
     ms = (ctypes.c_float * 3)()
-    with torch.cuda.device(dev):
-        ws = workspace(lib.leaf_workspace_bytes(B, T, F, K, hop, algo), dev)
-        rc = lib.leaf_forward_profiled_f32(_ptr(x2), B, T, _ptr(kernel), _ptr(pool_w), _ptr(pool_b), _ptr(alpha),
-                                           _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, algo,
-                                           _ptr(out), _ptr(ws), ws.numel(), stream_ptr(dev), ms)
-    check(rc, "leaf_forward_profiled_f32")
+    _call(dev, "leaf_forward_profiled_f32", x2, B, T, *prm, F, K, hop, flags | compression, algo, out,
+          ws=lambda lib: lib.leaf_workspace_bytes(B, T, F, K, hop, algo), after=(ms,))
     return out, [float(v) for v in ms]
 
 
 def gabor_taps(kernel: torch.Tensor, K: int) -> torch.Tensor:
-    lib = load(); require_hip(kernel, "gabor_taps")
+    require_hip(kernel, "gabor_taps")
     kernel = _dev_f32(kernel, "kernel", kernel.device)
     F = kernel.shape[0]
     taps = torch.empty((2 * F, K), dtype=torch.float32, device=kernel.device)
-    with torch.cuda.device(kernel.device):
-        check(lib.leaf_gabor_taps_f32(_ptr(kernel), F, K, _ptr(taps), stream_ptr(kernel.device)), "leaf_gabor_taps_f32")
+    _call(kernel.device, "leaf_gabor_taps_f32", kernel, F, K, taps)
     return taps
 
 
 def lowpass_window(pool_w: torch.Tensor, K: int) -> torch.Tensor:
-    lib = load(); require_hip(pool_w, "lowpass_window")
+    require_hip(pool_w, "lowpass_window")
     w = _dev_f32(pool_w.reshape(-1), "pool_w", pool_w.device)
     g = torch.empty((w.numel(), K), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        check(lib.leaf_lowpass_window_f32(_ptr(w), w.numel(), K, _ptr(g), stream_ptr(w.device)), "leaf_lowpass_window_f32")
+    _call(w.device, "leaf_lowpass_window_f32", w, w.numel(), K, g)
     return g
 
 
 def gabor_conv(x: torch.Tensor, kernel: torch.Tensor, K: int) -> torch.Tensor:
-    lib = load(); require_hip(x, "gabor_conv")
+    require_hip(x, "gabor_conv")
     if x.dim() != 3 or x.shape[1] != 1:
         raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
     dev = x.device
@@ -722,72 +642,64 @@ def gabor_conv(x: torch.Tensor, kernel: torch.Tensor, K: int) -> torch.Tensor:
     kernel = _dev_f32(kernel, "kernel", dev)
     B, T = x2.shape; F = kernel.shape[0]
     y = torch.empty((B, 2 * F, T), dtype=torch.float32, device=dev)
-    if B == 0:                                     # the empty batch passes through every stage as an empty tensor
-        return y
-    with torch.cuda.device(dev):
-        ws = workspace(2 * F * K * 4, dev)
-        check(lib.leaf_gabor_conv_f32(_ptr(x2), B, T, _ptr(kernel), F, K, _ptr(y), _ptr(ws), ws.numel(), stream_ptr(dev)),
-              "leaf_gabor_conv_f32")
+    if B:                                          # (the empty batch passes through every stage as an empty tensor)
+        _call(dev, "leaf_gabor_conv_f32", x2, B, T, kernel, F, K, y, ws=2 * F * K * 4)
     return y
 
 
 def squared_modulus(y: torch.Tensor) -> torch.Tensor:
-    lib = load(); require_hip(y, "squared_modulus")
+    require_hip(y, "squared_modulus")
     y = _dev_f32(y, "y", y.device)
     B, C2, T = y.shape
     if C2 % 2:
         raise RuntimeError("channel count must be even (interleaved re/im)")
     e = torch.empty((B, C2 // 2, T), dtype=torch.float32, device=y.device)
-    if B == 0:
-        return e
-    with torch.cuda.device(y.device):
-        check(lib.leaf_squared_modulus_f32(_ptr(y), B, C2 // 2, T, _ptr(e), stream_ptr(y.device)), "leaf_squared_modulus_f32")
+    if B:
+        _call(y.device, "leaf_squared_modulus_f32", y, B, C2 // 2, T, e)
     return e
 
 
 def gaussian_lowpass(e: torch.Tensor, pool_w: torch.Tensor, pool_b: Optional[torch.Tensor], K: int, hop: int) -> torch.Tensor:
-    lib = load(); require_hip(e, "gaussian_lowpass")
+    require_hip(e, "gaussian_lowpass")
     dev = e.device
     e = _dev_f32(e, "e", dev)
     B, F, T = e.shape
     w = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
     b = None if pool_b is None else _dev_f32(pool_b, "pool_b", dev)
-    TP = lib.leaf_num_frames(T, K, hop)
-    pooled = torch.empty((B, F, TP), dtype=torch.float32, device=dev)
-    if B == 0:
-        return pooled
-    with torch.cuda.device(dev):
-        ws = workspace(F * K * 4, dev)
-        check(lib.leaf_gaussian_lowpass_f32(_ptr(e), B, F, T, _ptr(w), _ptr(b), K, hop, _ptr(pooled), _ptr(ws), ws.numel(),
-                                            stream_ptr(dev)), "leaf_gaussian_lowpass_f32")
+    pooled = torch.empty((B, F, load().leaf_num_frames(T, K, hop)), dtype=torch.float32, device=dev)
+    if B:
+        _call(dev, "leaf_gaussian_lowpass_f32", e, B, F, T, w, b, K, hop, pooled, ws=F * K * 4)
     return pooled
 
 
+def _ema_w(ema_w: torch.Tensor, F: int, dev: torch.device):
+    """The smoother's coefficients as the kernels read them, one per channel (a shared coefficient expanded), and the fold of their
+    per-channel gradient back into ``ema_w``'s own shape (summed over the channels when the coefficient is shared)."""
+    shared = ema_w.numel() == 1
+    w = _dev_f32(ema_w.reshape(-1).expand(F) if shared else ema_w, "ema_w", dev)
+    return w, lambda gw: (gw.sum() if shared else gw).reshape(ema_w.shape)
+
+
 def ema(p: torch.Tensor, ema_w: torch.Tensor) -> torch.Tensor:
-    lib = load(); require_hip(p, "ema")
+    require_hip(p, "ema")
     dev = p.device
     p = _dev_f32(p, "p", dev); B, F, TP = p.shape
-    w = _dev_f32(ema_w.reshape(-1).expand(F) if ema_w.numel() == 1 else ema_w, "ema_w", dev)
+    w, _ = _ema_w(ema_w, F, dev)
     out = torch.empty_like(p)
-    if B == 0:
-        return out
-    with torch.cuda.device(dev):
-        check(lib.leaf_ema_f32(_ptr(p), B, F, TP, _ptr(w), _ptr(out), stream_ptr(dev)), "leaf_ema_f32")
+    if B:
+        _call(dev, "leaf_ema_f32", p, B, F, TP, w, out)
     return out
 
 
 def pcen(p: torch.Tensor, alpha, delta, root, ema_w, floor: float) -> torch.Tensor:
-    lib = load(); require_hip(p, "pcen")
+    require_hip(p, "pcen")
     dev = p.device
     p = _dev_f32(p, "p", dev); B, F, TP = p.shape
     alpha, delta, root = (_dev_f32(t, n, dev) for t, n in ((alpha, "alpha"), (delta, "delta"), (root, "root")))
-    w = _dev_f32(ema_w.reshape(-1).expand(F) if ema_w.numel() == 1 else ema_w, "ema_w", dev)
+    w, _ = _ema_w(ema_w, F, dev)
     out = torch.empty_like(p)
-    if B == 0:
-        return out
-    with torch.cuda.device(dev):
-        check(lib.leaf_pcen_f32(_ptr(p), B, F, TP, _ptr(alpha), _ptr(delta), _ptr(root), _ptr(w), float(floor), _ptr(out),
-                                stream_ptr(dev)), "leaf_pcen_f32")
+    if B:
+        _call(dev, "leaf_pcen_f32", p, B, F, TP, alpha, delta, root, w, float(floor), out)
     return out
 
 
@@ -806,10 +718,8 @@ def stream_step(chunk_ptr: int, B: int, Tc: int, chunk_stride: int, state: torch
     """leaf_stream_step_f32 on the current stream of ``device``: one launch.  ``params``: the seven parameter tensors (float32,
     contiguous, on the device; the four PCEN ones None without FLAG_PCEN); ``chunk_ptr`` / ``out_ptr``: device addresses
     (0 where Tc / n is 0)."""
-    with torch.cuda.device(device):
-        check(load().leaf_stream_step_f32(ctypes.c_void_p(chunk_ptr), B, Tc, chunk_stride, _ptr(state), state.numel(), hist_len, parity,
-                                          drop_samples, first, n, int(started), *(_ptr(t) for t in params), F, K, hop, flags,
-                                          ctypes.c_void_p(out_ptr), stream_ptr(device)), "leaf_stream_step_f32")
+    _call(device, "leaf_stream_step_f32", ctypes.c_void_p(chunk_ptr), B, Tc, chunk_stride, state, state.numel(), hist_len, parity,
+          drop_samples, first, n, int(started), *params, F, K, hop, flags, ctypes.c_void_p(out_ptr))
 
 
 # ---- stage backwards (what autograd derives for a sub-module called on its own; modules.py wraps them) ----------
@@ -818,34 +728,29 @@ def pcen_stream(p: torch.Tensor, alpha, delta, root, ema_w, floor: float, ema_st
                 log1p: bool = False):
     """leaf_pcen_stream_f32: PCEN of one chunk (B,F,n) of floored pooled frames with the smoother state carried between
     calls.  Returns (out, new_state); ``alpha is None``: no PCEN (state stays None)."""
-    lib = load()
     require_hip(p, "pcen_stream")
     dev = p.device
     p = _dev_f32(p, "p", dev)
     B, F, n = p.shape
     out = torch.empty_like(p)
     if alpha is None:
-        with torch.cuda.device(dev):
-            check(lib.leaf_pcen_stream_f32(_ptr(p), B, F, n, None, None, None, None, float(floor), int(log1p), None, None, _ptr(out),
-                                           stream_ptr(dev)), "leaf_pcen_stream_f32")
+        _call(dev, "leaf_pcen_stream_f32", p, B, F, n, None, None, None, None, float(floor), int(log1p), None, None, out)
         return out, None
     alpha, delta, root, ema_w = (_dev_f32(t, nm, dev) for t, nm in
                                  ((alpha, "alpha"), (delta, "delta"), (root, "root"), (ema_w, "ema_w")))
     new_state = torch.empty((B, F), dtype=torch.float32, device=dev)
     if ema_state is not None:
         ema_state = _dev_f32(ema_state, "ema_state", dev)
-    with torch.cuda.device(dev):
-        check(lib.leaf_pcen_stream_f32(_ptr(p), B, F, n, _ptr(alpha), _ptr(delta), _ptr(root), _ptr(ema_w), float(floor), 0,
-                                       _ptr(ema_state), _ptr(new_state), _ptr(out), stream_ptr(dev)), "leaf_pcen_stream_f32")
+    _call(dev, "leaf_pcen_stream_f32", p, B, F, n, alpha, delta, root, ema_w, float(floor), 0, ema_state, new_state, out)
     return out, new_state
 
 
-def _stage_ws(stage: int, B: int, T: int, F: int, K: int, hop: int, dev) -> torch.Tensor:
-    return workspace(load().leaf_stage_backward_workspace_bytes(stage, B, T, F, K, hop), dev)
+def _stage_ws(stage: int, B: int, T: int, F: int, K: int, hop: int):
+    return lambda lib: lib.leaf_stage_backward_workspace_bytes(stage, B, T, F, K, hop)
 
 
 def gabor_conv_backward(x, kernel, K: int, grad_y, need_dk: bool = True, need_dx: bool = False):
-    lib = load(); require_hip(x, "gabor_conv_backward")
+    require_hip(x, "gabor_conv_backward")
     dev = x.device
     x2 = _dev_f32(x[:, 0, :], "x", dev)
     kernel = _dev_f32(kernel, "kernel", dev)
@@ -854,31 +759,26 @@ def gabor_conv_backward(x, kernel, K: int, grad_y, need_dk: bool = True, need_dx
     gk = torch.empty_like(kernel) if need_dk else None
     gx = torch.empty_like(x2) if need_dx else None
     if B == 0:                                     # the sum over no clips
-        return (gk.zero_() if gk is not None else None), (gx.reshape(x.shape) if gx is not None else None)
-    with torch.cuda.device(dev):
-        ws = _stage_ws(STAGE_GABOR_CONV, B, T, F, K, 1, dev)
-        check(lib.leaf_gabor_conv_backward_f32(_ptr(x2), B, T, _ptr(kernel), F, K, _ptr(gy), _ptr(gk), _ptr(gx), _ptr(ws),
-                                               ws.numel(), stream_ptr(dev)), "leaf_gabor_conv_backward_f32")
-    return gk, (gx.reshape(x.shape) if gx is not None else None)
+        gk = gk.zero_() if need_dk else None
+    else:
+        _call(dev, "leaf_gabor_conv_backward_f32", x2, B, T, kernel, F, K, gy, gk, gx, ws=_stage_ws(STAGE_GABOR_CONV, B, T, F, K, 1))
+    return gk, (gx.reshape(x.shape) if need_dx else None)
 
 
 def squared_modulus_backward(y, grad_e):
-    lib = load(); require_hip(y, "squared_modulus_backward")
+    require_hip(y, "squared_modulus_backward")
     dev = y.device
     y = _dev_f32(y, "y", dev); ge = _dev_f32(grad_e, "grad_e", dev)
     B, C2, T = y.shape
     gy = torch.empty_like(y)
-    if B == 0:
-        return gy
-    with torch.cuda.device(dev):
-        check(lib.leaf_squared_modulus_backward_f32(_ptr(y), _ptr(ge), B, C2 // 2, T, _ptr(gy), stream_ptr(dev)),
-              "leaf_squared_modulus_backward_f32")
+    if B:
+        _call(dev, "leaf_squared_modulus_backward_f32", y, ge, B, C2 // 2, T, gy)
     return gy
 
 
 def gaussian_lowpass_backward(e, pool_w, K: int, hop: int, grad_pooled, need_de: bool = True, need_dw: bool = True,
                               need_db: bool = True):
-    lib = load(); require_hip(e, "gaussian_lowpass_backward")
+    require_hip(e, "gaussian_lowpass_backward")
     dev = e.device
     e = _dev_f32(e, "e", dev); gp = _dev_f32(grad_pooled, "grad_pooled", dev)
     w = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
@@ -887,57 +787,48 @@ def gaussian_lowpass_backward(e, pool_w, K: int, hop: int, grad_pooled, need_de:
     gw = torch.empty_like(w) if need_dw else None
     gb = torch.empty_like(w) if need_db else None
     if B == 0:
-        return ge, (gw.zero_().reshape(pool_w.shape) if gw is not None else None), (gb.zero_() if gb is not None else None)
-    with torch.cuda.device(dev):
-        ws = _stage_ws(STAGE_LOWPASS, B, T, F, K, hop, dev)
-        check(lib.leaf_gaussian_lowpass_backward_f32(_ptr(e), _ptr(gp), B, F, T, _ptr(w), K, hop, _ptr(ge), _ptr(gw), _ptr(gb),
-                                                     _ptr(ws), ws.numel(), stream_ptr(dev)), "leaf_gaussian_lowpass_backward_f32")
-    return ge, (gw.reshape(pool_w.shape) if gw is not None else None), gb
+        for g in (gw, gb):
+            if g is not None:
+                g.zero_()
+    else:
+        _call(dev, "leaf_gaussian_lowpass_backward_f32", e, gp, B, F, T, w, K, hop, ge, gw, gb, ws=_stage_ws(STAGE_LOWPASS, B, T, F, K, hop))
+    return ge, (gw.reshape(pool_w.shape) if need_dw else None), gb
 
 
 def ema_backward(p, ema_w, grad_ema):
-    lib = load(); require_hip(p, "ema_backward")
+    require_hip(p, "ema_backward")
     dev = p.device
     p = _dev_f32(p, "p", dev); g = _dev_f32(grad_ema, "grad_ema", dev)
     B, F, TP = p.shape
-    shared = ema_w.numel() == 1
-    w = _dev_f32(ema_w.reshape(-1).expand(F) if shared else ema_w, "ema_w", dev)
+    w, fold = _ema_w(ema_w, F, dev)
     gp, gw = torch.empty_like(p), torch.empty(F, dtype=torch.float32, device=dev)
     if B == 0:
         gw.zero_()
-        return gp, (gw.sum().reshape(ema_w.shape) if shared else gw.reshape(ema_w.shape))
-    with torch.cuda.device(dev):
-        ws = _stage_ws(STAGE_EMA, B, TP, F, 1, 1, dev)
-        check(lib.leaf_ema_backward_f32(_ptr(p), _ptr(g), B, F, TP, _ptr(w), _ptr(gp), _ptr(gw), _ptr(ws), ws.numel(),
-                                        stream_ptr(dev)), "leaf_ema_backward_f32")
-    return gp, (gw.sum().reshape(ema_w.shape) if shared else gw.reshape(ema_w.shape))
+    else:
+        _call(dev, "leaf_ema_backward_f32", p, g, B, F, TP, w, gp, gw, ws=_stage_ws(STAGE_EMA, B, TP, F, 1, 1))
+    return gp, fold(gw)
 
 
 def pcen_backward(p, alpha, delta, root, ema_w, floor: float, grad_out):
-    lib = load(); require_hip(p, "pcen_backward")
+    require_hip(p, "pcen_backward")
     dev = p.device
     p = _dev_f32(p, "p", dev); g = _dev_f32(grad_out, "grad_out", dev)
     B, F, TP = p.shape
     alpha, delta, root = (_dev_f32(t, n, dev) for t, n in ((alpha, "alpha"), (delta, "delta"), (root, "root")))
-    shared = ema_w.numel() == 1
-    w = _dev_f32(ema_w.reshape(-1).expand(F) if shared else ema_w, "ema_w", dev)
+    w, fold = _ema_w(ema_w, F, dev)
     gp = torch.empty_like(p)
     ga, gd, gr, gw = (torch.empty(F, dtype=torch.float32, device=dev) for _ in range(4))
     if B == 0:
         for g_ in (ga, gd, gr, gw):
             g_.zero_()
-        return gp, ga, gd, gr, (gw.sum().reshape(ema_w.shape) if shared else gw.reshape(ema_w.shape))
-    with torch.cuda.device(dev):
-        ws = _stage_ws(STAGE_PCEN, B, TP, F, 1, 1, dev)
-        check(lib.leaf_pcen_backward_f32(_ptr(p), _ptr(g), B, F, TP, _ptr(alpha), _ptr(delta), _ptr(root), _ptr(w), float(floor),
-                                         _ptr(gp), _ptr(ga), _ptr(gd), _ptr(gr), _ptr(gw), _ptr(ws), ws.numel(),
-                                         stream_ptr(dev)), "leaf_pcen_backward_f32")
-    return gp, ga, gd, gr, (gw.sum().reshape(ema_w.shape) if shared else gw.reshape(ema_w.shape))
+    else:
+        _call(dev, "leaf_pcen_backward_f32", p, g, B, F, TP, alpha, delta, root, w, float(floor), gp, ga, gd, gr, gw,
+              ws=_stage_ws(STAGE_PCEN, B, TP, F, 1, 1))
+    return gp, ga, gd, gr, fold(gw)
 
 
 def peak_normalize(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Clips (rows of a (B,T) or (B,1,T) tensor) whose peak |x| exceeds 1 are divided by it; wraps leaf_peak_normalize_f32."""
-    lib = load()
     require_hip(x, "peak_normalize")
     per_clip = 1
     for d in x.shape[1:]:
@@ -948,29 +839,24 @@ def peak_normalize(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch
         out = torch.empty_like(x2)
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != x2.numel():
         raise RuntimeError("out must be a contiguous float32 tensor of the input's size")
-    if B == 0:
-        return out.reshape(x.shape)
-    with torch.cuda.device(x.device):
-        check(lib.leaf_peak_normalize_f32(_ptr(x2), B, T, _ptr(out), stream_ptr(x.device)), "leaf_peak_normalize_f32")
+    if B:
+        _call(x.device, "leaf_peak_normalize_f32", x2, B, T, out)
     return out.reshape(x.shape)
 
 
 def prepare_tables(kernel: torch.Tensor, pool_w: torch.Tensor, K: int, hop: int) -> Optional[torch.Tensor]:
     """Parameter-derived tables of the overlap-save path (filter spectra + pooling rows) for frozen-parameter inference;
     ``None`` when that path does not cover the geometry.  Wraps leaf_fft_prepare_tables_f32."""
-    lib = load()
     require_hip(kernel, "prepare_tables")
     dev = kernel.device
     kernel = _dev_f32(kernel, "kernel", dev)
     pw = _dev_f32(pool_w.reshape(-1), "pool_w", dev)
     F = kernel.shape[0]
-    nbytes = lib.leaf_fft_tables_bytes(F, K, hop)
+    nbytes = load().leaf_fft_tables_bytes(F, K, hop)
     if nbytes == 0:
         return None
     tables = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        check(lib.leaf_fft_prepare_tables_f32(_ptr(kernel), _ptr(pw), F, K, hop, _ptr(tables), nbytes, stream_ptr(dev)),
-              "leaf_fft_prepare_tables_f32")
+    _call(dev, "leaf_fft_prepare_tables_f32", kernel, pw, F, K, hop, tables, nbytes)
     return tables
 
 
@@ -980,35 +866,17 @@ def leaf_forward_prepared(x: torch.Tensor, tables: torch.Tensor, pool_b, alpha, 
     """Forward with tables from ``prepare_tables`` (same outputs as ``leaf_forward``, without the table kernel).  ``out_bf16``:
     bfloat16 features from a float32 or int16 waveform (LEAF_FLAG_OUT_BF16)."""
     lib = load()
-    require_hip(x, "leaf_forward_prepared")
-    if x.dim() == 3:
-        if x.shape[1] != 1:
-            raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
-        x2 = x[:, 0, :]
-    elif x.dim() == 2:
-        x2 = x
-    else:
-        raise RuntimeError(f"expected input of shape (B,1,T), got {tuple(x.shape)}")
+    x2, flags = _unpack_x(x, "leaf_forward_prepared")
     dev = x.device
-    x2, flags = _dev_x(x2, dev)
-    if out_bf16 and flags != FLAG_IO_BF16:
-        flags |= FLAG_OUT_BF16
-    io_bf16 = bool(flags & (FLAG_IO_BF16 | FLAG_OUT_BF16))   # the feature dtype
     B, T = x2.shape
-    pool_b = _dev_f32(pool_b, "pool_b", dev)
-    if pcen:
-        flags |= FLAG_PCEN
-        alpha, delta, root, ema_w = (_dev_f32(t, "pcen param", dev) for t in (alpha, delta, root, ema_w))
-    else:
-        alpha = delta = root = ema_w = None
-        if log1p:
-            flags |= FLAG_LOG1P
+    prm, compression = _gather(dev, (None, None, pool_b, alpha, delta, root, ema_w), pcen, log1p)
     TP = lib.leaf_num_frames(T, K, hop)
+    out_bf16, feat = _features(flags, out_bf16)
+    if out is not None:
+        _check_out(out, (B, F, TP), feat, dev)
+    flags |= compression | (FLAG_OUT_BF16 if out_bf16 else 0)
     if out is None:
-        out = torch.empty((B, F, TP), dtype=torch.bfloat16 if io_bf16 else torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws = workspace(lib.leaf_workspace_bytes(B, T, F, K, hop, ALGO_FFT), dev)
-        check(lib.leaf_forward_prepared_f32(_ptr(x2), B, T, _ptr(tables), tables.numel(), _ptr(pool_b), _ptr(alpha),
-                                            _ptr(delta), _ptr(root), _ptr(ema_w), F, K, hop, flags, _ptr(out), _ptr(ws),
-                                            ws.numel(), stream_ptr(dev)), "leaf_forward_prepared_f32")
+        out = torch.empty((B, F, TP), dtype=feat, device=dev)
+    _call(dev, "leaf_forward_prepared_f32", x2, B, T, tables, tables.numel(), *prm[2:], F, K, hop, flags, out,
+          ws=lambda lib: lib.leaf_workspace_bytes(B, T, F, K, hop, ALGO_FFT))
     return out

@@ -123,8 +123,7 @@ def _register_family(mixed: bool) -> None:
         saved = ctx.saved_tensors
         kernel, pool_w, pool_b, raw = saved[lead:lead + 4]
         alpha, delta, root, ema_w = saved[lead + 4:] if ctx.pcen else (None,) * 4
-        flags = ((_native.FLAG_BWD_FULL_TRANSFORMS if ctx.full else 0) | (_native.FLAG_BWD_STRICT_BAND_CLASSES if ctx.strict else 0) |
-                 (_native.FLAG_LOG1P if ctx.log1p else 0))
+        flags = _native.backward_flags(full_transforms=ctx.full, strict_band_classes=ctx.strict, log1p=ctx.log1p)   # (the op adds PCEN and the dtype bits)
         params = (kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, grad_out.contiguous(), raw)
         if mixed:
             if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:

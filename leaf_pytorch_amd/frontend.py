@@ -25,69 +25,39 @@ class SquaredModulus(nn.Module):
         return _native.squared_modulus(x)
 
 
-class _LeafForward(torch.autograd.Function):
-    """Forward = fused HIP path (leaf_forward_f32); backward = leaf_backward_f32 (recomputes on device)."""
+class _LeafFn(torch.autograd.Function):
+    """The path without the dispatcher ops.  Forward = fused HIP path (leaf_forward_save_f32); backward = leaf_backward_f32 (recomputes
+    on device).  ``lead`` inputs stand in front of the seven parameters: x alone, or x, perm, lam for the mixed batch
+    x * lam + x[perm] * (1 - lam) (leaf_forward_save_mix_f32 / leaf_backward_mix_f32: parameter gradients only)."""
 
     @staticmethod
-    def forward(ctx, x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen, algo, log1p=False, out_bf16=False):
+    def forward(ctx, lead, *args):
+        head, params, (K, hop, pcen, algo, log1p, out_bf16) = args[:lead], args[lead:lead + 7], args[lead + 7:]
         if algo & _native.OPT_PEAKNORM:
             # leaf_forward_save_f32 would hand the backward a pooled tensor of the NORMALISED clips next to the raw x
             raise RuntimeError("the folded PeakNormalization prologue is forward-only (no backward through it)")
-        out, raw = _native.leaf_forward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen=pcen,
-                                        log1p=log1p, algo=algo, save_raw=True, out_bf16=out_bf16)
-        ctx.log1p = bool(log1p) and not pcen
-        ctx.out_bf16 = bool(out_bf16)                             # bfloat16 features: their gradient arrives in bfloat16 and goes straight in
-        ctx.save_for_backward(x, kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if pcen else []))
-        ctx.geom = (K, hop, pcen)
-        ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)      # Leaf.full_transforms(): the backward keeps them too
-        ctx.strict = bool(algo & _native.ALGO_STRICT_BAND_CLASSES)
+        fwd = _native.leaf_forward if lead == 1 else _native.leaf_forward_mix
+        out, raw = fwd(*head, *params, K, hop, pcen=pcen, log1p=log1p, algo=algo, save_raw=True, out_bf16=out_bf16)
+        ctx.lead, ctx.geom = lead, (K, hop)
+        ctx.how = dict(pcen=pcen, log1p=bool(log1p) and not pcen,
+                       out_bf16=bool(out_bf16),                   # bfloat16 features: their gradient arrives in bfloat16 and goes straight in
+                       full_transforms=bool(algo & _native.ALGO_FULL_TRANSFORMS),   # Leaf.full_transforms(): the backward keeps them too
+                       strict_band_classes=bool(algo & _native.ALGO_STRICT_BAND_CLASSES))
+        ctx.save_for_backward(*head, *params[:3], raw, *(params[3:] if pcen else ()))
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable      # (gradients of gradients: the dispatcher-op path, _second_order.py; here they raise)
     def backward(ctx, grad_out):
-        K, hop, pcen = ctx.geom
-        saved = ctx.saved_tensors
-        x, kernel, pool_w, pool_b, raw = saved[:5]
-        alpha, delta, root, ema_w = saved[5:] if pcen else (None,) * 4
-        need_dx = ctx.needs_input_grad[0]
-        gk, gpw, gpb, ga, gd, gr, gw, gx = _native.leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop,
-                                                                 grad_out, pcen=pcen, need_dx=need_dx, pooled_raw=raw,
-                                                                 full_transforms=ctx.full, strict_band_classes=ctx.strict,
-                                                                 log1p=ctx.log1p, out_bf16=ctx.out_bf16)
-        if gx is not None:
-            gx = gx.reshape(x.shape)
-        return gx, gk, gpw, gpb, ga, gd, gr, gw, None, None, None, None, None, None
-
-
-class _LeafForwardMix(torch.autograd.Function):
-    """_LeafForward on the mixed batch x * lam + x[perm] * (1 - lam) (leaf_forward_save_mix_f32 / leaf_backward_mix_f32): the
-    path without the dispatcher ops.  Parameter gradients only."""
-
-    @staticmethod
-    def forward(ctx, x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen, algo, log1p=False, out_bf16=False):
-        out, raw = _native.leaf_forward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K, hop, pcen=pcen,
-                                            log1p=log1p, algo=algo, save_raw=True, out_bf16=out_bf16)
-        ctx.log1p = bool(log1p) and not pcen
-        ctx.out_bf16 = bool(out_bf16)
-        ctx.save_for_backward(x, perm, lam, kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if pcen else []))
-        ctx.geom = (K, hop, pcen)
-        ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)
-        ctx.strict = bool(algo & _native.ALGO_STRICT_BAND_CLASSES)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        K, hop, pcen = ctx.geom
-        saved = ctx.saved_tensors
-        x, perm, lam, kernel, pool_w, pool_b, raw = saved[:7]
-        alpha, delta, root, ema_w = saved[7:] if pcen else (None,) * 4
-        gk, gpw, gpb, ga, gd, gr, gw, _ = _native.leaf_backward_mix(x, perm, lam, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K,
-                                                                    hop, grad_out, pcen=pcen, pooled_raw=raw,
-                                                                    full_transforms=ctx.full, strict_band_classes=ctx.strict,
-                                                                    log1p=ctx.log1p, out_bf16=ctx.out_bf16)
-        return None, None, None, gk, gpw, gpb, ga, gd, gr, gw, None, None, None, None, None, None
+        lead, saved = ctx.lead, ctx.saved_tensors
+        head, (kernel, pool_w, pool_b, raw), pc = saved[:lead], saved[lead:lead + 4], saved[lead + 4:] or (None,) * 4
+        if lead == 1:
+            *grads, gx = _native.leaf_backward(*head, kernel, pool_w, pool_b, *pc, *ctx.geom, grad_out, need_dx=ctx.needs_input_grad[1],
+                                               pooled_raw=raw, **ctx.how)
+            gx = None if gx is None else gx.reshape(head[0].shape)
+        else:
+            *grads, gx = _native.leaf_backward_mix(*head, kernel, pool_w, pool_b, *pc, *ctx.geom, grad_out, pooled_raw=raw, **ctx.how)
+        return (None, gx, *(None,) * (lead - 1), *grads, *(None,) * 6)          # (one per input of forward)
 
 
 class Leaf(nn.Module):
@@ -210,6 +180,12 @@ class Leaf(nn.Module):
             self._tables_key = key if self._tables is not None else None
         return self._tables
 
+    def _kernel_params(self):
+        """The seven parameter tensors in the order every host layer takes them (the PCEN four None without PCEN)."""
+        c = self._compression
+        pcen = (None,) * 4 if c is None else (c.alpha, c.delta, c.root, c.ema._weights)
+        return (self._complex_conv._kernel, self._pooling.weights, self._pooling._bias, *pcen)
+
     def forward_mixup(self, x: torch.Tensor, perm, lam) -> torch.Tensor:
         """Not part of the reference surface: ``forward(x * lam[:, None, None] + x[perm] * (1 - lam[:, None, None]))`` -- the
         waveform mixup of the reference's training loop (utilities/data/mixup.py) -- bit for bit, with the mix done in fp32 inside
@@ -238,9 +214,7 @@ class Leaf(nn.Module):
         if c is not None and c._floor != 1e-12:
             raise NotImplementedError("fused path is specialised for the PCEN floor Leaf constructs (1e-12)")
         perm, lam = _native.mix_args(perm, lam, x.shape[0], x.device)
-        params = (self._complex_conv._kernel, self._pooling.weights, self._pooling._bias,
-                  c.alpha if c is not None else None, c.delta if c is not None else None,
-                  c.root if c is not None else None, c.ema._weights if c is not None else None)
+        params = self._kernel_params()
         K, hop = self._complex_conv._kernel_size, self._pooling.strides
         log1p = self._log1p and c is None
         bf16 = self._features_bf16(x)                             # output_dtype(): bfloat16 features of the mixed batch
@@ -251,7 +225,7 @@ class Leaf(nn.Module):
                 return _ops.forward_train_mix(x, perm, lam, *params, K, hop, algo=self._algo, log1p=log1p, out_bf16=bf16)
             return _ops.forward_mix(x, perm, lam, *params, K, hop, log1p=log1p, algo=self._algo, out_bf16=bf16)
         if needs_grad:
-            return _LeafForwardMix.apply(x, perm, lam, *params, K, hop, c is not None, self._algo, log1p, bf16)
+            return _LeafFn.apply(3, x, perm, lam, *params, K, hop, c is not None, self._algo, log1p, bf16)
         return _native.leaf_forward_mix(x, perm, lam, *params, K, hop, pcen=c is not None, log1p=log1p, algo=self._algo, out_bf16=bf16)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -264,15 +238,13 @@ class Leaf(nn.Module):
         bf16 = self._features_bf16(x)                             # output_dtype(): bfloat16 features from a float32 / int16 waveform
         algo = self._algo
         c = self._compression
-        params = (self._complex_conv._kernel, self._pooling.weights, self._pooling._bias,
-                  c.alpha if c is not None else None, c.delta if c is not None else None,
-                  c.root if c is not None else None, c.ema._weights if c is not None else None)
+        params = self._kernel_params()
+        K, hop, F = self._complex_conv._kernel_size, self._pooling.strides, self._complex_conv._filters
         # from the tensors actually handed to the kernel, not self.parameters(): nn.DataParallel replicas hold plain
         # (non-leaf) tensors, for which parameters() is empty
         params_need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params)
         # an int16 waveform (16-bit PCM: a sample v means v / 32768) lies in [-1, 1) by construction: nothing to normalise
         if self._fuse_peaknorm and x.dtype != torch.int16:
-            K_, hop_ = self._complex_conv._kernel_size, self._pooling.strides
             # the folded prologue is forward-only: the same condition that sends the call to the training path below
             fused_ok = (not (params_need_grad or (torch.is_grad_enabled() and x.requires_grad))
                         and not self._cache_tables and x.dim() == 3 and x.shape[1] == 1 and x.shape[0] > 0)
@@ -280,7 +252,7 @@ class Leaf(nn.Module):
                 with torch.cuda.device(x.device):
                     sel = algo & 0xff
                     if sel == _native.ALGO_AUTO:
-                        sel = _native.load().leaf_auto_algo(x.shape[0], x.shape[-1], self._complex_conv._filters, K_, hop_)
+                        sel = _native.load().leaf_auto_algo(x.shape[0], x.shape[-1], F, K, hop)
                 fused_ok = sel in (_native.ALGO_FFT, _native.ALGO_FFT_WG, _native.ALGO_FFT_SMALL)
             if fused_ok:
                 algo = algo | _native.OPT_PEAKNORM
@@ -289,8 +261,8 @@ class Leaf(nn.Module):
                 x = PeakNormalization()(x)
         if c is not None and c._floor != 1e-12:
             raise NotImplementedError("fused path is specialised for the PCEN floor Leaf constructs (1e-12)")
-        args = (x, *params, self._complex_conv._kernel_size, self._pooling.strides, c is not None, algo)
-        log1p = self._log1p and c is None
+        pcen = c is not None
+        log1p = self._log1p and not pcen
         needs_grad = params_need_grad or (torch.is_grad_enabled() and x.requires_grad)
         if needs_grad and (algo & _native.OPT_PEAKNORM):
             raise RuntimeError("Leaf.forward: the folded PeakNormalization prologue is forward-only")   # unreachable by design
@@ -298,14 +270,13 @@ class Leaf(nn.Module):
             # dispatcher ops (csrc/torch_binding.cpp): traceable by torch.compile / export, one hop per eager call
             _ops.load()
             if needs_grad:
-                return _ops.forward_train(*args[:10], algo=args[11], log1p=log1p, out_bf16=bf16)
+                return _ops.forward_train(x, *params, K, hop, algo=algo, log1p=log1p, out_bf16=bf16)
             if not (self._cache_tables and not torch.compiler.is_compiling()):
-                return _ops.forward(*args[:10], log1p=log1p, algo=args[11], out_bf16=bf16)
+                return _ops.forward(x, *params, K, hop, log1p=log1p, algo=algo, out_bf16=bf16)
         if needs_grad:
-            return _LeafForward.apply(*args, log1p, bf16)
+            return _LeafFn.apply(1, x, *params, K, hop, pcen, algo, log1p, bf16)
         if self._cache_tables and self._algo in (_native.ALGO_AUTO, _native.ALGO_FFT):
-            K, hop = args[8], args[9]
-            B, T, F = x.shape[0], x.shape[-1], args[1].shape[0]
+            B, T = x.shape[0], x.shape[-1]
             with torch.cuda.device(x.device):            # the plan is sized for the CU count of the device the call runs on
                 plan = _native.fft_plan_info(B, T, F, K, hop)
                 auto = _native.load().leaf_auto_algo(B, T, F, K, hop)
@@ -314,7 +285,6 @@ class Leaf(nn.Module):
             if auto in (_native.ALGO_FFT, _native.ALGO_FFT_WG) and plan is not None and plan["fft_n"] == 2048:
                 tables = self._prepared_tables()
                 if tables is not None:
-                    return _native.leaf_forward_prepared(x, tables, args[3], args[4], args[5], args[6], args[7],
-                                                         args[1].shape[0], K, hop, pcen=args[10], log1p=log1p, out_bf16=bf16)
-        return _native.leaf_forward(*args[:8], args[8], args[9], pcen=args[10], log1p=log1p, algo=args[11] & ~_native.OPT_PEAKNORM,
-                                    peak_normalize=bool(args[11] & _native.OPT_PEAKNORM), out_bf16=bf16)
+                    return _native.leaf_forward_prepared(x, tables, *params[2:], F, K, hop, pcen=pcen, log1p=log1p, out_bf16=bf16)
+        return _native.leaf_forward(x, *params, K, hop, pcen=pcen, log1p=log1p, algo=algo & ~_native.OPT_PEAKNORM,
+                                    peak_normalize=bool(algo & _native.OPT_PEAKNORM), out_bf16=bf16)

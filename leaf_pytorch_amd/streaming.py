@@ -173,13 +173,8 @@ class _FusedLeafStream(LeafStream):
     def _launch(self, x2: Optional[torch.Tensor], at: int, Tc: int, final: bool) -> torch.Tensor:
         B, pcm, dev = self.state_key
         first, n, drop, new_hist, new_next = stream_plan(self.hist_len, self.next, Tc, self.K, self.hop, final)
-        sd, c = self.leaf, self.leaf._compression
-        params = [_native._dev_f32(t, nm, dev) for t, nm in ((sd._complex_conv._kernel, "kernel"), (sd._pooling.weights.reshape(-1), "pool_w"),
-                                                            (sd._pooling._bias, "pool_b"))]
-        params += [None] * 4 if c is None else [_native._dev_f32(t, nm, dev) for t, nm in
-                                                ((c.alpha, "alpha"), (c.delta, "delta"), (c.root, "root"), (c.ema._weights, "ema_w"))]
-        flags = (_native.FLAG_PCEN if c is not None else _native.FLAG_LOG1P if self.log1p else 0) | (_native.FLAG_X_PCM16 if pcm else 0) \
-            | (_native.FLAG_OUT_BF16 if self.out_dtype is torch.bfloat16 else 0)
+        params, flags = _native._gather(dev, self.leaf._kernel_params(), self.leaf._compression is not None, self.log1p)
+        flags |= (_native.FLAG_X_PCM16 if pcm else 0) | (_native.FLAG_OUT_BF16 if self.out_dtype is torch.bfloat16 else 0)
         out = torch.empty((B, self.F, n), dtype=self.out_dtype, device=dev)
         _native.stream_step(x2.data_ptr() + at * x2.element_size() if Tc else 0, B, Tc, x2.stride(0) if Tc else 0, self.state_buf,
                             self.hist_len, self.parity, drop, first, n, self.started, params, self.F, self.K, self.hop, flags,
