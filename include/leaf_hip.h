@@ -498,6 +498,49 @@ int leaf_stream_step_f32(const void* chunk, int B, int Tc, long long chunk_strid
                          int K, int hop, int flags, void* out, void* stream);
 
 /*
+ * The bank: one step of B INDEPENDENT streams in one launch (additive: the ABI version stays 6).  leaf_stream_step_f32 moves B
+ * streams in lock-step; here every slot b stands at a position of its own -- streams begin and end at different times, take chunks
+ * of different lengths, or take nothing in a step -- described by slots[b], a HOST array of B records that the call reads before it
+ * returns (the records travel to the kernel by value: no plan buffer on the device, no copy, no readback, nothing synchronises).
+ * `state` has the layout and size of leaf_stream_state_bytes(B, F, K, hop, flags); slot b owns row b of both history halves and row
+ * b of the smoother state, and carries a parity of its own.  Geometries and flags are those of leaf_stream_step_f32.
+ *
+ * A slot's record:
+ *   idle = 1: the slot takes no part in the step.  Nothing of its state is read or written, no other field of the record is looked
+ *     at, its rows of out are zeros; the caller leaves its parity as it is.
+ *   idle = 0: hist_len, Tc, parity, drop_samples, first, n, started mean what leaf_stream_step_f32's arguments mean, for this slot
+ *     alone: the signal is [history (hist_len samples of row b of half `parity`) | chunk[b * chunk_stride .. + Tc)], frames first ..
+ *     first + n - 1 of it are emitted, samples [drop_samples, hist_len + Tc) go to row b of the other half, and the caller flips the
+ *     slot's parity.  Only the first Tc samples of a chunk row are read.  A slot whose stream begins passes hist_len = 0 and
+ *     started = 0 and reads nothing of the state.
+ *   end_n > 0: the stream ENDS with this step, on a chunk that also completed frames.  After the step's frames, frames end_first ..
+ *     end_first + end_n - 1 of the buffer made of the samples [drop_samples, hist_len + Tc) -- numbered from that buffer's first
+ *     sample, with the reference's zero padding behind its last -- are emitted by the same workgroups, with the smoother carried on;
+ *     nothing is handed over to the other half.  These are the frames, bit for bit, that a final leaf_stream_step_f32 (Tc = 0) on
+ *     the handed-over history would give.  (A stream that ends without the step completing a frame needs no second pass: n counts
+ *     all its remaining frames and drop_samples = hist_len + Tc.)
+ * out is [B][F][n_max] (float32, or bfloat16 with LEAF_FLAG_OUT_BF16): row (b, f) holds the slot's n + end_n frames, then zeros up to
+ * n_max; EVERY element of out is written.  n_max = 0: out is not touched and may be NULL.  chunk may be NULL when no slot has samples.
+ *
+ * Checks, all on the host before anything is launched, in leaf_stream_step_f32's order: unsupported flag or geometry; B = 0
+ * (LEAF_OK); NULL (slots, state, parameters; chunk when a slot has Tc > 0; out when n_max > 0); shape (B, F, n_max, a slot's idle
+ * or Tc, chunk_stride below the longest Tc when B > 1); alignment; then per slot every position of leaf_stream_step_f32's list, the
+ * ending pass's frames inside its buffer, n + end_n <= n_max, and the kernel's LDS at n_max: LEAF_ERR_BAD_SHAPE -- one bad slot
+ * refuses the whole call; state_bytes: LEAF_ERR_WORKSPACE.  A bank of more than 128 slots is served by several launches (128 pass
+ * records each; an ending pass is a record of its own); a call in which no slot emits or keeps anything (n_max = 0 and every slot
+ * idle or drop_samples = hist_len + Tc) launches nothing.  Steps on one `state` must execute in order.
+ */
+typedef struct leaf_stream_slot {
+    int idle;
+    int hist_len, Tc, parity, drop_samples, first, n, started;
+    int end_first, end_n;
+} leaf_stream_slot;
+int leaf_stream_bank_step_f32(const void* chunk, long long chunk_stride, int B, const leaf_stream_slot* slots, int n_max, void* state,
+                              size_t state_bytes, const float* kernel, const float* pool_w, const float* pool_b, const float* alpha,
+                              const float* delta, const float* root, const float* ema_w, int F, int K, int hop, int flags, void* out,
+                              void* stream);
+
+/*
  * Stage backwards: the gradient autograd derives for each of the modules above when it is called ON ITS OWN (the
  * reference's sub-modules are ordinary differentiable nn.Modules; Leaf.forward as a whole has leaf_backward_f32).
  * One-lane-per-output kernels, every intermediate materialised; clamp sub-gradients as torch.clamp gives them.

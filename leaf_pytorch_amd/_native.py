@@ -115,6 +115,9 @@ _SIGNATURES = {
     "leaf_stream_state_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "leaf_stream_step_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_size_t]
                              + [ctypes.c_int] * 6 + [_f32p] * 7 + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_void_p]),
+    # the bank: chunk, chunk_stride, B, slots (leaf_stream_slot[B], a host array), n_max, state, state_bytes
+    "leaf_stream_bank_step_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                 ctypes.c_size_t] + [_f32p] * 7 + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -720,6 +723,19 @@ def stream_step(chunk_ptr: int, B: int, Tc: int, chunk_stride: int, state: torch
     (0 where Tc / n is 0)."""
     _call(device, "leaf_stream_step_f32", ctypes.c_void_p(chunk_ptr), B, Tc, chunk_stride, state, state.numel(), hist_len, parity,
           drop_samples, first, n, int(started), *params, F, K, hop, flags, ctypes.c_void_p(out_ptr))
+
+
+class StreamSlot(ctypes.Structure):
+    """leaf_stream_slot (include/leaf_hip.h): where one slot of a bank stands in one step."""
+    _fields_ = [(name, ctypes.c_int) for name in ("idle", "hist_len", "Tc", "parity", "drop_samples", "first", "n", "started", "end_first", "end_n")]
+
+
+def stream_bank_step(chunk_ptr: int, chunk_stride: int, slots, n_max: int, state: torch.Tensor, params, F: int, K: int, hop: int,
+                     flags: int, out_ptr: int, device: torch.device) -> None:
+    """leaf_stream_bank_step_f32 on the current stream of ``device``.  ``slots``: a ctypes array of ``StreamSlot`` (host memory, read
+    before the call returns); ``params`` as in ``stream_step``."""
+    _call(device, "leaf_stream_bank_step_f32", ctypes.c_void_p(chunk_ptr), chunk_stride, len(slots), ctypes.cast(slots, ctypes.c_void_p), n_max,
+          state, state.numel(), *params, F, K, hop, flags, ctypes.c_void_p(out_ptr))
 
 
 # ---- stage backwards (what autograd derives for a sub-module called on its own; modules.py wraps them) ----------

@@ -23,6 +23,26 @@
 //     stores in the stream's own sample type, by the waves that idle while wave 0 finalizes the row.
 //   * n == 0 (a chunk too short to complete a frame): the host launches grid (1, B) and the kernel only moves history.
 //
+// The bank (leaf_stream_bank_step_f32, leaf_fft_stream_bank_kernel): B INDEPENDENT streams in one launch.  A workgroup is still one
+// (slot b, filter f), reads only row b of the history and word (b, f) of the smoother state and waits for no other workgroup; what
+// the uniform step takes from StreamParams -- where the stream stands -- it takes from slot b's record instead:
+//   * the records travel BY VALUE in the kernel's parameter struct (StreamBankParams: kBankSlots packed records of 24 bytes, the
+//     struct stays below 4 KB; a larger bank is several launches).  The host computes and checks every field (StreamPassRec).  blockIdx.y is wave-uniform, so a record comes in through scalar
+//     loads from the argument segment: no plan buffer on the device, no copy, no readback.
+//   * slot b reads history half parity_b, row b, and writes the other half, row b (the layout is leaf_stream_state_bytes').
+//   * out is [B][F][n_max]: a row holds the slot's frames and zeros behind them, every element written by the row's workgroup.  An
+//     idle slot's workgroups write their zeros and touch nothing else: no history, no smoother word.
+//   * the dynamic LDS is sized by the launch's largest frame count (n_lds): what is laid out behind lsum sits at that offset.
+//   * a stream that ENDS on a chunk that also completes frames takes two passes of the body in the same workgroup: the step's frames
+//     from [history | chunk], then the frames still owed from the samples [drop, hist_len + Tc) of that buffer, numbered from `drop`
+//     with the reference's zero padding behind the last sample -- the very buffer, block alignment included, a uniform stream's
+//     final step would read from the history it had just been handed, so the frames are the same bits.  Nothing is handed over (the
+//     stream ends); the smoother's state goes from the first pass to the second through the row's own state word, behind the
+//     workgroup barrier that also separates the two passes' use of the LDS.
+//
+// ONE device body (leaf_fft_stream_body) and two entries: the position (StreamPos) is built from the uniform parameters or from
+// the slot's record; in the uniform step its extra fields are constants (no offsets, rows of n frames) and fold away.
+//
 // The transform loop is the small kernel's two-trip loop through ONE copy of fft2048w, and for the same reason: the code runs
 // once per launch from a cold instruction cache.
 #pragma once
@@ -32,8 +52,8 @@ namespace {
 
 struct StreamParams {
     const void* chunk;        // [B][chunk_stride], the first Tc samples of a row; fp32 or 16-bit PCM by `pcm`
-    const void* hist_in;      // [B][H]: the history half this step reads, hist_len samples of a row
-    void* hist_out;           // [B][H]: the other half, receives the next step's history
+    const void* hist_in;      // [B][H]: the history half this step reads, hist_len samples of a row (the bank: half 0)
+    void* hist_out;           // [B][H]: the other half, receives the next step's history (the bank: half 1)
     float* ema_state;         // [B][F]
     long long chunk_stride;   // samples
     int pcm;                  // sample type of chunk and history: kSampleF32 / kSamplePcm16 (leaf_common.hpp)
@@ -47,14 +67,44 @@ struct StreamParams {
     FinParams fin;            // part unused: the sums stay in LDS; fin.out is [B][F][n]
 };
 
+// where ONE stream stands in one pass of the body (wave-uniform: from the kernel arguments alone)
+struct StreamPos {
+    const void* hist_in;      // the history half the stream reads ...
+    void* hist_out;           // ... and the one it hands over to
+    int hist_len, Tc, drop, first, n, started, c_lo, nb;   // as in StreamParams
+    int hist_off, chunk_off;  // samples skipped in front of the history row / the chunk row (the bank's ending pass; else 0)
+    int n_lds;                // frame sums the launch's LDS holds (>= n)
+    int n_row, o_lo, o_end;   // out rows are n_row long; this pass's frames start at column o_lo and zeros follow them up to o_end
+};
+
+// the bank: up to kBankSlots slots per launch and as many PASS records of 6 words; a slot has one record, or two when its stream
+// ends on a chunk that also completes frames (header comment), consecutive, the last one marked
+constexpr int kBankSlots = 128;
+struct StreamPassRec {
+    // w[0] = hist_len | Tc << 16          w[1] = drop | first << 16       w[2] = n | c_lo << 16 | nb << 24
+    // w[3] = hist_off | chunk_off << 16   w[4] = o_lo | o_end << 16       (StreamPos)
+    // w[5] = started | parity << 1 | idle << 2 | last << 3
+    unsigned w[6];
+};
+struct StreamBankParams {
+    StreamParams c;                   // what the slots share; its position fields are unused; fin.out is [B][F][n_max]
+    int b0;                           // the launch's first slot: workgroup (f, y) serves row b0 + y
+    int n_lds, n_max;
+    unsigned first[kBankSlots / 4];   // byte y: slot y's first record
+    StreamPassRec rec[kBankSlots];
+};
+static_assert(sizeof(StreamBankParams) <= 4096, "the records travel in the kernel argument segment");
+
 constexpr unsigned leaf_layout_hash_stream() {
-    return leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_layout_hash_fft(), sizeof(StreamParams)), offsetof(StreamParams, fin)), offsetof(StreamParams, bd)),
-                    offsetof(StreamParams, c_lo));
+    return leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_layout_hash_fft(), sizeof(StreamParams)), offsetof(StreamParams, fin)),
+                                               offsetof(StreamParams, bd)), offsetof(StreamParams, c_lo)),
+                             sizeof(StreamBankParams)), offsetof(StreamBankParams, rec));
 }
 
-// dynamic LDS: the small kernel's layout with n frame sums (fft_small_lds_bytes(kSmallWaves, n))
-template <int SK, int SHOP>
-__global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(const StreamParams p) {
+// one pass of stream b at position s; dynamic LDS: the small kernel's layout with s.n_lds frame sums.  BANK: out rows are longer
+// than the pass's frames and get their zeros here (the uniform step has no such columns and carries no code for them)
+template <int SK, int SHOP, bool BANK>
+__device__ __forceinline__ void leaf_fft_stream_body(const StreamParams& p, const StreamPos& s, const int b, const int tid) {
     constexpr int NW = kSmallWaves;
     constexpr int SCRF = kWgScrFloats;
     constexpr int PADL = SK / 2 + SK % 2 - 1;
@@ -74,37 +124,42 @@ __global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(co
     float* R = reinterpret_cast<float*>(twp + 64);                        // [2048]; first the taps, conj(w)[K] as float2
     float* scr0 = R + kFftN;
     float* lsum = scr0 + (size_t)NW * SCRF;                               // [n]: the emitted frames' sums
-    FinCoef* cfs = reinterpret_cast<FinCoef*>(lsum + (p.n + 3) / 4 * 4);  // the row's finalize coefficients (phase 0 -> phase 3)
+    FinCoef* cfs = reinterpret_cast<FinCoef*>(lsum + (s.n_lds + 3) / 4 * 4);  // the row's finalize coefficients (phase 0 -> phase 3)
     float* gw = reinterpret_cast<float*>(cfs + 1);                        // [NJ][64]: the filter's pooling-weight vectors (phase 0 -> phase 2)
-    const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int lane = tid & 63;
-    const int f = blockIdx.x, b = blockIdx.y;
-    const int hl = p.hist_len, T = p.hist_len + p.Tc;                     // the virtual buffer's length
+    const int f = blockIdx.x;
+    const int hl = s.hist_len, T = s.hist_len + s.Tc;                     // the virtual buffer's length
     const int TPv = T > 0 ? (T - 1) / SHOP + 1 : 0;                       // ... and its frames
 
     // the history hand-over (f == 0 only): virtual samples [drop, T) -> hist_out[b][0 .. T - drop), by threads t0, t0 + nt, ...
     auto move_history = [&](int t0, int nt) {
-        const int tail = T - p.drop;
+        const int drop = s.drop, tail = T - drop;
         if (p.pcm) {
-            const unsigned short* hi = static_cast<const unsigned short*>(p.hist_in) + (size_t)b * p.H;
-            const unsigned short* ch = static_cast<const unsigned short*>(p.chunk) + (size_t)b * (size_t)p.chunk_stride;
-            unsigned short* ho = static_cast<unsigned short*>(p.hist_out) + (size_t)b * p.H;
+            const unsigned short* hi = static_cast<const unsigned short*>(s.hist_in) + (size_t)b * p.H + s.hist_off;
+            const unsigned short* ch = static_cast<const unsigned short*>(p.chunk) + (size_t)b * (size_t)p.chunk_stride + s.chunk_off;
+            unsigned short* ho = static_cast<unsigned short*>(s.hist_out) + (size_t)b * p.H;
             for (int j = t0; j < tail; j += nt) {
-                const int s = j + p.drop;
-                ho[j] = s < hl ? hi[s] : ch[s - hl];
+                const int v = j + drop;
+                ho[j] = v < hl ? hi[v] : ch[v - hl];
             }
         } else {
-            const float* hi = static_cast<const float*>(p.hist_in) + (size_t)b * p.H;
-            const float* ch = static_cast<const float*>(p.chunk) + (size_t)b * (size_t)p.chunk_stride;
-            float* ho = static_cast<float*>(p.hist_out) + (size_t)b * p.H;
+            const float* hi = static_cast<const float*>(s.hist_in) + (size_t)b * p.H + s.hist_off;
+            const float* ch = static_cast<const float*>(p.chunk) + (size_t)b * (size_t)p.chunk_stride + s.chunk_off;
+            float* ho = static_cast<float*>(s.hist_out) + (size_t)b * p.H;
             for (int j = t0; j < tail; j += nt) {
-                const int s = j + p.drop;
-                ho[j] = s < hl ? hi[s] : ch[s - hl];
+                const int v = j + drop;
+                ho[j] = v < hl ? hi[v] : ch[v - hl];
             }
         }
     };
-    if (p.n == 0) {                                                       // nothing to emit: grid (1, B), history only
+    // the row's columns behind its frames (the bank's out rows are n_max long; none in the uniform step), by threads t0, t0 + nt, ...
+    auto zero_tail = [&](int t0, int nt) {
+        if constexpr (BANK)
+            for (int k = s.o_lo + s.n + t0; k < s.o_end; k += nt) fin_store(p.fin, ((size_t)b * p.F + f) * s.n_row + k, 0.0f);
+    };
+    if (s.n == 0) {                                                       // nothing to emit: history only (grid (1, B) when no row of out exists)
+        zero_tail(tid, NW * 64);
         if (f == 0) move_history(tid, NW * 64);
         return;
     }
@@ -115,13 +170,13 @@ __global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(co
     const float mu = p.kernel[2 * f], sg = p.kernel[2 * f + 1], pw_raw = p.pool_w[f];
     const int row = b * p.F + f;
     float M = 0.0f;                                                       // the smoother's state (wave 0): requested here, used in phase 3
-    if (wave == 0 && (p.fin.mode & 1) && p.started) M = p.ema_state[row];
+    if (wave == 0 && (p.fin.mode & 1) && s.started) M = p.ema_state[row];
     float zre[32], zim[32];             // a block wave's samples -> spectrum (kept across the barrier) -> filter outputs
     auto load_block = [&](int c, int lane_) {                             // block c of the virtual buffer, rotated left by padL samples
         const int n_c = c * LS;
         if (p.pcm) {
-            const short* hi = static_cast<const short*>(p.hist_in) + (size_t)b * p.H;
-            const short* ch = static_cast<const short*>(p.chunk) + (size_t)b * (size_t)p.chunk_stride - hl;
+            const short* hi = static_cast<const short*>(s.hist_in) + (size_t)b * p.H + s.hist_off;
+            const short* ch = static_cast<const short*>(p.chunk) + (size_t)b * (size_t)p.chunk_stride + s.chunk_off - hl;
 #pragma unroll
             for (int r = 0; r < 32; ++r) {
                 const int i = 64 * r + lane_;
@@ -131,8 +186,8 @@ __global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(co
                 zim[r] = 0.0f;
             }
         } else {
-            const float* hi = static_cast<const float*>(p.hist_in) + (size_t)b * p.H;
-            const float* ch = static_cast<const float*>(p.chunk) + (size_t)b * (size_t)p.chunk_stride - hl;
+            const float* hi = static_cast<const float*>(s.hist_in) + (size_t)b * p.H + s.hist_off;
+            const float* ch = static_cast<const float*>(p.chunk) + (size_t)b * (size_t)p.chunk_stride + s.chunk_off - hl;
 #pragma unroll
             for (int r = 0; r < 32; ++r) {
                 const int i = 64 * r + lane_;
@@ -154,7 +209,7 @@ __global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(co
             taps[j] = make_float2(a, -c);                                 // conj(w), as fft_prep_kernel
         }
     }
-    for (int m = tid; m < p.n; m += NW * 64) lsum[m] = 0.0f;
+    for (int m = tid; m < s.n; m += NW * 64) lsum[m] = 0.0f;
     if (tid == 64) cfs[0] = fin_coef(p.fin, f);
     {
         const float half = 0.5f * (float)(SK - 1);
@@ -174,9 +229,9 @@ __global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(co
     for (int step = 0; step < 2; ++step) {
         const bool inv = step != 0;
         const bool table = !inv && wave == NW - 1;
-        if (wave < p.nb || table) {
+        if (wave < s.nb || table) {
             asm volatile("" : "+v"(lane));
-            const int c = p.c_lo + wave, n_c = c * LS;
+            const int c = s.c_lo + wave, n_c = c * LS;
             if (table) {
                 const float2* taps = reinterpret_cast<const float2*>(R);
 #pragma unroll
@@ -221,8 +276,8 @@ __global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(co
                 const int Lv = min(LS, T - n_c);
                 int mlo = n_c + PADL - SK + 1;                            // first frame whose window reaches the block
                 mlo = mlo <= 0 ? 0 : (mlo + SHOP - 1) / SHOP;
-                mlo = max(mlo, p.first);                                  // ... that is emitted
-                const int mhi = min(min(TPv, p.first + p.n) - 1, (n_c + Lv - 1 + PADL) / SHOP);
+                mlo = max(mlo, s.first);                                  // ... that is emitted
+                const int mhi = min(min(TPv, s.first + s.n) - 1, (n_c + Lv - 1 + PADL) / SHOP);
                 float er[NROW];
 #pragma unroll
                 for (int i = 0; i < 32; ++i) {
@@ -257,7 +312,7 @@ __global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(co
                     const int fi = 16 * g + ((lane >> 5) & 1) * 8 + ((lane >> 4) & 1) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 2) & 1);
                     const int m = n_c / SHOP + DMIN + fi;
                     if ((lane & 3) == 0 && fi < NFR && m >= mlo && m <= mhi)
-                        __hip_atomic_fetch_add(&lsum[m - p.first], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_add(&lsum[m - s.first], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
         }
@@ -269,9 +324,9 @@ __global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(co
         const FinParams& fin = p.fin;
         const int mode = fin.mode;
         const FinCoef cf = cfs[0];
-        for (int m0 = 0; m0 < p.n; m0 += 64) {
+        for (int m0 = 0; m0 < s.n; m0 += 64) {
             const int k = m0 + lane;
-            const bool on = k < p.n;
+            const bool on = k < s.n;
             float x = pooled_floor(fin_pooled(lsum[on ? k : 0], 0.0f, 0.0f, 1, false, 1.0f, cf.bias));
             float Mv = 0.0f;
             if (mode & 1) {
@@ -280,16 +335,60 @@ __global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(co
                 wave_affine_scan(sa, sb);
                 // the state before the chunk's first frame: the stream's first frame itself (postprocessing.py:15), the state the
                 // previous step left, or the previous 64 frames' last
-                const float carry = (m0 == 0 && !p.started) ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))) : M;
+                const float carry = (m0 == 0 && !s.started) ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))) : M;
                 Mv = sa * carry + sb;
-                M = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Mv), min(64, p.n - m0) - 1));
+                M = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Mv), min(64, s.n - m0) - 1));
             }
             const float o = fin_point(cf, mode, fin.floor_, x, Mv);
-            if (on) fin_store(fin, (size_t)row * p.n + k, o);
+            if (on) fin_store(fin, (size_t)row * s.n_row + s.o_lo + k, o);
         }
         if ((mode & 1) && lane == 0) p.ema_state[row] = M;                // after the last emitted frame: the next step's carry
-    } else if (f == 0) {
-        move_history(tid - 64, (NW - 1) * 64);
+    } else {
+        zero_tail(tid - 64, (NW - 1) * 64);
+        if (f == 0) move_history(tid - 64, (NW - 1) * 64);
+    }
+}
+
+
+// the uniform step: every stream stands where StreamParams says; dynamic LDS fft_small_lds_bytes(kSmallWaves, n)
+template <int SK, int SHOP>
+__global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_kernel(const StreamParams p) {
+    const StreamPos s{p.hist_in, p.hist_out, p.hist_len, p.Tc, p.drop, p.first, p.n, p.started, p.c_lo, p.nb, 0, 0, p.n, p.n, 0, p.n};
+    leaf_fft_stream_body<SK, SHOP, false>(p, s, blockIdx.y, threadIdx.x);
+}
+
+// the bank: slot blockIdx.y of this launch stands where its record says; dynamic LDS fft_small_lds_bytes(kSmallWaves, n_lds)
+template <int SK, int SHOP>
+__global__ __launch_bounds__(kSmallWaves * 64, 3) void leaf_fft_stream_bank_kernel(const StreamBankParams q) {
+    // The arguments are read through the argument segment's own address, taken anew in every trip: what a trip loads it loads for
+    // itself (scalar loads), and nothing but the record's index is carried across the body.  (Read through `q`, every argument is
+    // loop-invariant, stays in scalar registers across both trips and costs the kernel scratch.)
+    // Likewise the thread's index: the wave's number is kept in a scalar register and the lane's is counted anew in every trip.
+    const int y = blockIdx.y, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    int i = (int)((q.first[y >> 2] >> (8 * (y & 3))) & 0xff);
+#pragma nounroll
+    for (;;) {                                                            // one trip, or two for a stream that ends (header comment)
+        const __attribute__((address_space(4))) StreamBankParams* a =
+            (const __attribute__((address_space(4))) StreamBankParams*)__builtin_amdgcn_kernarg_segment_ptr();
+        int yy = y, tid = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+s"(a), "+s"(yy), "+v"(tid));                  // (nothing derived from them is hoisted out of the loop)
+        tid += 64 * wave;
+        const StreamBankParams& g = *(const StreamBankParams*)a;
+        const unsigned w0 = g.rec[i].w[0], w1 = g.rec[i].w[1], w2 = g.rec[i].w[2], w3 = g.rec[i].w[3], w4 = g.rec[i].w[4], w5 = g.rec[i].w[5];
+        const bool par = (w5 & 2) != 0, idle = (w5 & 4) != 0;             // an idle slot: an empty pass (its zeros, nothing else)
+        StreamPos s;
+        s.hist_in = par ? static_cast<const void*>(g.c.hist_out) : g.c.hist_in;
+        s.hist_out = par ? const_cast<void*>(g.c.hist_in) : g.c.hist_out;
+        s.hist_len = idle ? 0 : (int)(w0 & 0xffff); s.Tc = idle ? 0 : (int)(w0 >> 16); s.drop = idle ? 0 : (int)(w1 & 0xffff);
+        s.first = (int)(w1 >> 16); s.n = idle ? 0 : (int)(w2 & 0xffff); s.started = (int)(w5 & 1);
+        s.c_lo = (int)((w2 >> 16) & 0xff); s.nb = (int)(w2 >> 24);
+        s.hist_off = (int)(w3 & 0xffff); s.chunk_off = (int)(w3 >> 16);
+        s.n_lds = g.n_lds; s.n_row = g.n_max;
+        s.o_lo = (int)(w4 & 0xffff); s.o_end = (int)(w4 >> 16);
+        leaf_fft_stream_body<SK, SHOP, true>(g.c, s, g.b0 + yy, tid);
+        if (w5 & 8) break;
+        ++i;
+        __syncthreads();                                                  // the pass is done with the LDS; its smoother state word is visible
     }
 }
 

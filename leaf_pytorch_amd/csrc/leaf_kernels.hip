@@ -1349,6 +1349,18 @@ size_t leaf_stream_state_bytes(int B, int F, int K, int hop, int flags) {
     return stream_layout(B, F, K, hop, (flags & LEAF_FLAG_X_PCM16) != 0).total;
 }
 
+// the blocks c_lo .. c_lo + nb - 1 of a buffer of T samples that the windows of its frames first .. first + n - 1 (n > 0) meet
+static void stream_blocks(int first, int n, int T, int K, int hop, int& c_lo, int& nb) {
+    const int LS = fft_block_len(K, hop, true), padL = K / 2 + K % 2 - 1;
+    c_lo = std::max(0, first * hop - padL) / LS;
+    nb = std::min(T - 1, (first + n - 1) * hop - padL + K - 1) / LS - c_lo + 1;
+}
+// are frames first .. first + n - 1 frames of a clip of T samples?
+static inline bool stream_frames_ok(int first, int n, int T, int hop) {
+    const int TPv = T > 0 ? (T - 1) / hop + 1 : 0;
+    return first >= 0 && n >= 0 && first <= TPv && n <= TPv - first;
+}
+
 // where a stream stands (host-side bookkeeping of the caller: nothing is read back from the device) and its buffers
 struct StreamIo {
     const void* chunk;
@@ -1374,10 +1386,7 @@ static int stream_step(const CallCtx&, const LeafArgs& a, const StreamIo& io) {
     q.kernel = a.kernel; q.pool_w = a.pool_w; q.bd = gabor_bounds(K);
     q.B = B; q.F = F; q.H = L.H; q.hist_len = io.hist_len; q.Tc = T - io.hist_len; q.drop = io.drop;
     q.first = io.first; q.n = io.n; q.started = io.started;
-    if (io.n > 0) {                                           // the blocks the emitted frames' windows meet
-        q.c_lo = std::max(0, io.first * hop - padL) / LS;
-        q.nb = std::min(T - 1, (io.first + io.n - 1) * hop - padL + K - 1) / LS - q.c_lo + 1;
-    }
+    if (io.n > 0) stream_blocks(io.first, io.n, T, K, hop, q.c_lo, q.nb);
     q.fin = FinParams{nullptr, F, io.n, SlotGeom{LS, padL, K, hop, T, 2}, a.pool_b, a.alpha, a.delta, a.root, a.ema_w, 1e-12f, io.mode, io.out, nullptr, nullptr};
     return launch_lds(kfn, dim3(io.n > 0 ? F : 1, B), kSmallWaves, io.n > 0 ? fft_small_lds_bytes(kSmallWaves, io.n) : 0, a.st, q);
 }
@@ -1406,8 +1415,7 @@ int leaf_stream_step_f32(const void* chunk, int B, int Tc, long long chunk_strid
     const int T = hist_len + Tc;
     if (T > kSmallRing * LS) return LEAF_ERR_BAD_SHAPE;                   // one pass of the ring
     if (drop_samples < 0 || drop_samples > T || T - drop_samples > L.H) return LEAF_ERR_BAD_SHAPE;
-    const int TPv = T > 0 ? (T - 1) / hop + 1 : 0;
-    if (first < 0 || n < 0 || first > TPv || n > TPv - first) return LEAF_ERR_BAD_SHAPE;
+    if (!stream_frames_ok(first, n, T, hop)) return LEAF_ERR_BAD_SHAPE;
     if (n > 0 && fft_small_lds_bytes(kSmallWaves, n) > (size_t)kMaxLds) return LEAF_ERR_BAD_SHAPE;
     if (state_bytes < L.total) return LEAF_ERR_WORKSPACE;
     if (n == 0 && T - drop_samples == 0) return LEAF_OK;                  // nothing to emit and no history to keep
@@ -1415,6 +1423,114 @@ int leaf_stream_step_f32(const void* chunk, int B, int Tc, long long chunk_strid
     const CallCtx ctx = forward_ctx(LEAF_ALGO_AUTO);          // this entry takes no option word
     return stream_step(ctx, LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream},
                        StreamIo{chunk, chunk_stride, state, pcm ? kSamplePcm16 : kSampleF32, hist_len, parity, drop_samples, first, n, started, mode, out});
+}
+
+// ---- the bank (leaf_fft_stream.hpp): B independent streams, every slot at its own position, kBankSlots slots per launch
+// One slot's position as the kernel takes it: one pass record, or two for a stream that ends on a chunk that completes frames.
+static int bank_records(const leaf_stream_slot& sl, int K, int hop, int n_max, StreamPassRec* rec) {
+    auto pack = [](int lo, int hi) { return (unsigned)lo | ((unsigned)hi << 16); };
+    const unsigned bits = (unsigned)sl.started | ((unsigned)sl.parity << 1);
+    if (sl.idle) {
+        *rec = StreamPassRec{{0, 0, 0, 0, pack(0, n_max), 4u | 8u}};
+        return 1;
+    }
+    const int T = sl.hist_len + sl.Tc, two = sl.end_n > 0;
+    int c_lo = 0, nb = 0;
+    if (sl.n > 0) stream_blocks(sl.first, sl.n, T, K, hop, c_lo, nb);
+    // the step; one that is followed by the ending pass hands nothing over and leaves the row's zeros to that pass
+    rec[0] = StreamPassRec{{pack(sl.hist_len, sl.Tc), pack(two ? T : sl.drop_samples, sl.first), (unsigned)sl.n | ((unsigned)c_lo << 16) | ((unsigned)nb << 24),
+                            0, pack(0, two ? sl.n : n_max), bits | (two ? 0u : 8u)}};
+    if (!two) return 1;
+    // the ending pass: the samples [drop, T) as a buffer of their own, nothing kept
+    const int d = sl.drop_samples, T2 = T - d, hl2 = std::max(sl.hist_len - d, 0);
+    stream_blocks(sl.end_first, sl.end_n, T2, K, hop, c_lo, nb);
+    rec[1] = StreamPassRec{{pack(hl2, T2 - hl2), pack(T2, sl.end_first), (unsigned)sl.end_n | ((unsigned)c_lo << 16) | ((unsigned)nb << 24),
+                            pack(std::min(d, sl.hist_len), std::max(d - sl.hist_len, 0)), pack(sl.n, n_max),
+                            ((unsigned)(sl.started | (sl.n > 0))) | ((unsigned)sl.parity << 1) | 8u}};
+    return 2;
+}
+
+int leaf_stream_bank_step_f32(const void* chunk, long long chunk_stride, int B, const leaf_stream_slot* slots, int n_max, void* state,
+                              size_t state_bytes, const float* kernel, const float* pool_w, const float* pool_b, const float* alpha,
+                              const float* delta, const float* root, const float* ema_w, int F, int K, int hop, int flags, void* out,
+                              void* stream) {
+    if (flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_PEAKNORM)) return LEAF_ERR_UNSUPPORTED;
+    if (K >= 1 && hop >= 1 && !stream_geometry(K, hop)) return LEAF_ERR_UNSUPPORTED;
+    if (B == 0 && !inst_layouts_ok()) return LEAF_ERR_LAUNCH;
+    if (B == 0 && n_max >= 0 && F >= 1 && K >= 1 && hop >= 1) return LEAF_OK;
+    const bool use_pcen = (flags & LEAF_FLAG_PCEN) != 0;
+    if (!slots || !state || !kernel || !pool_w || !pool_b || (n_max > 0 && !out)) return LEAF_ERR_NULL_POINTER;
+    if (use_pcen && (!alpha || !delta || !root || !ema_w)) return LEAF_ERR_NULL_POINTER;
+    if (B < 1 || F < 1 || F > 65535 || K < 1 || hop < 1 || n_max < 0) return LEAF_ERR_BAD_SHAPE;
+    int Tc_max = 0;
+    for (int b = 0; b < B; ++b) {
+        if (slots[b].idle & ~1) return LEAF_ERR_BAD_SHAPE;
+        if (!slots[b].idle && slots[b].Tc < 0) return LEAF_ERR_BAD_SHAPE;
+        if (!slots[b].idle) Tc_max = std::max(Tc_max, slots[b].Tc);
+    }
+    if (Tc_max > 0 && !chunk) return LEAF_ERR_NULL_POINTER;
+    if (Tc_max > 0 && B > 1 && chunk_stride < Tc_max) return LEAF_ERR_BAD_SHAPE;
+    if (!inst_layouts_ok()) return LEAF_ERR_LAUNCH;
+    const bool pcm = (flags & LEAF_FLAG_X_PCM16) != 0, out_bf16 = (flags & LEAF_FLAG_OUT_BF16) != 0;
+    if (misaligned16(state) || (reinterpret_cast<uintptr_t>(chunk) & (pcm ? 1u : 3u)) || (reinterpret_cast<uintptr_t>(out) & (out_bf16 ? 1u : 3u)) ||
+        any_misaligned(kernel, pool_w, pool_b, alpha, delta, root, ema_w))
+        return LEAF_ERR_ALIGNMENT;
+    // the positions: everything the kernel derives an address in `state`, `chunk` or `out` from, slot by slot
+    const StreamLayout L = stream_layout(B, F, K, hop, pcm);
+    const int LS = fft_block_len(K, hop, true), padL = K / 2 + K % 2 - 1;
+    if (n_max > 0 && fft_small_lds_bytes(kSmallWaves, n_max) > (size_t)kMaxLds) return LEAF_ERR_BAD_SHAPE;
+    bool work = n_max > 0;
+    for (int b = 0; b < B; ++b) {
+        const leaf_stream_slot& sl = slots[b];
+        if (sl.idle) continue;
+        if (sl.hist_len < 0 || sl.hist_len > L.H || sl.Tc > kSmallRing * LS || (sl.parity & ~1) || (sl.started & ~1)) return LEAF_ERR_BAD_SHAPE;
+        const int T = sl.hist_len + sl.Tc;
+        if (T > kSmallRing * LS) return LEAF_ERR_BAD_SHAPE;               // one pass of the ring
+        if (sl.drop_samples < 0 || sl.drop_samples > T) return LEAF_ERR_BAD_SHAPE;
+        if (sl.end_n < 0 || (sl.end_n == 0 && T - sl.drop_samples > L.H)) return LEAF_ERR_BAD_SHAPE;   // (an ending pass keeps nothing)
+        if (!stream_frames_ok(sl.first, sl.n, T, hop)) return LEAF_ERR_BAD_SHAPE;
+        if (sl.end_n > 0 && !stream_frames_ok(sl.end_first, sl.end_n, T - sl.drop_samples, hop)) return LEAF_ERR_BAD_SHAPE;
+        if (sl.n > n_max || sl.end_n > n_max - sl.n) return LEAF_ERR_BAD_SHAPE;
+        work = work || T - sl.drop_samples > 0;
+    }
+    if (state_bytes < L.total) return LEAF_ERR_WORKSPACE;
+    if (!work) return LEAF_OK;                                            // no slot emits anything or keeps anything
+    using BankKernel = void (*)(const StreamBankParams);
+    const BankKernel kfn = reinterpret_cast<BankKernel>(const_cast<void*>(leaf_inst_fft_stream_bank(K)));
+    if (!kfn) return LEAF_ERR_UNSUPPORTED;
+    const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (out_bf16 ? 4 : 0);
+    char* base = static_cast<char*>(state);
+    StreamBankParams q{};
+    q.c.chunk = chunk; q.c.chunk_stride = chunk_stride; q.c.pcm = pcm ? kSamplePcm16 : kSampleF32;
+    q.c.hist_in = base; q.c.hist_out = base + L.half;                     // halves 0 and 1: a slot's parity picks the one it reads
+    q.c.ema_state = reinterpret_cast<float*>(base + L.ema);
+    q.c.kernel = kernel; q.c.pool_w = pool_w; q.c.bd = gabor_bounds(K);
+    q.c.B = B; q.c.F = F; q.c.H = L.H;
+    q.c.fin = FinParams{nullptr, F, n_max, SlotGeom{LS, padL, K, hop, 0, 2}, pool_b, alpha, delta, root, ema_w, 1e-12f, mode, out, nullptr, nullptr};
+    q.n_max = n_max;
+    // launches of up to kBankSlots slots and kBankSlots pass records (a slot's records stay together)
+    for (int b0 = 0; b0 < B;) {
+        int ns = 0, nr = 0, n_lds = 0;
+        bool keep = false;
+        while (b0 + ns < B && ns < kBankSlots && nr + (slots[b0 + ns].idle || slots[b0 + ns].end_n == 0 ? 1 : 2) <= kBankSlots) {
+            const leaf_stream_slot& sl = slots[b0 + ns];
+            if (ns % 4 == 0) q.first[ns / 4] = 0;
+            q.first[ns / 4] |= (unsigned)nr << (8 * (ns % 4));
+            nr += bank_records(sl, K, hop, n_max, q.rec + nr);
+            if (!sl.idle) {
+                n_lds = std::max(n_lds, std::max(sl.n, sl.end_n));
+                keep = keep || sl.hist_len + sl.Tc - sl.drop_samples > 0;
+            }
+            ++ns;
+        }
+        q.b0 = b0; q.n_lds = n_lds;
+        if (n_max > 0 || keep) {                                          // (n_max = 0: a launch whose slots keep nothing has nothing to do)
+            const int rc = launch_lds(kfn, dim3(n_max > 0 ? F : 1, ns), kSmallWaves, n_lds > 0 ? fft_small_lds_bytes(kSmallWaves, n_lds) : 0, (hipStream_t)stream, q);
+            if (rc != LEAF_OK) return rc;
+        }
+        b0 += ns;
+    }
+    return LEAF_OK;
 }
 
 // LEAF_ALGO_FFT_WG on 4096-sample blocks: tables -> workgroup kernel -> the same finalize kernel (partials keep their layout)

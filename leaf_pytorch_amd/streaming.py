@@ -14,6 +14,9 @@ overlap-save or MFMA path ``LEAF_ALGO_AUTO`` picks for that length), then the st
 csrc/leaf_fft_stream.hpp): the history and the smoother state live in one device buffer allocated once, the kernel reads
 [history | chunk] from the two buffers, emits only the new frames and hands the history over; no ``cat``, no slicing, no
 allocation per step beyond the frames returned.  16 kHz and 8 kHz geometries (the static instances of the one-launch kernel).
+
+``LeafStreamBank(leaf, slots)`` serves INDEPENDENT streams -- they begin and end at different times and take chunks of different
+lengths -- with that kernel, one call per step for the whole bank (``leaf_stream_bank_step_f32``).
 """
 from __future__ import annotations
 
@@ -225,3 +228,137 @@ class _FusedLeafStream(LeafStream):
         self.hist_len = self.next = 0
         self.started = False
         return out
+
+
+class LeafStreamBank:
+    """``slots`` INDEPENDENT streams served by one ``leaf_stream_bank_step_f32`` call per step (csrc/leaf_fft_stream.hpp: the fused
+    stream's kernel with the position taken per slot).  Streams begin and end at different times, take chunks of different lengths,
+    or take nothing in a step: what a server with many connections needs, where ``LeafStream(fused=True)`` moves a batch in lock-step.
+
+    The host keeps, per slot, what ``_FusedLeafStream`` keeps for its batch -- ``hist_len``, ``next``, ``parity``, ``started`` -- and
+    ``stream_plan`` moves it; the device buffer (``state_buf``: ``leaf_stream_state_bytes`` for ``slots`` rows) is allocated by the
+    first step and never cleared.  Every stream's frames are, bit for bit, those of a one-waveform ``LeafStream(leaf, fused=True)`` fed
+    the same chunks and flushed."""
+
+    def __init__(self, leaf, slots: int, sample_dtype=torch.float32, log1p: bool = False, out_dtype=None, device=None):
+        if out_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError(f"LeafStreamBank: out_dtype must be None, torch.float32 or torch.bfloat16, got {out_dtype!r}")
+        if sample_dtype not in (torch.float32, torch.int16):
+            raise ValueError(f"LeafStreamBank: sample_dtype must be torch.float32 or torch.int16 (16-bit PCM), got {sample_dtype!r}")
+        if int(slots) < 1:
+            raise ValueError(f"LeafStreamBank: slots must be at least 1, got {slots!r}")
+        conv, pool = leaf._complex_conv, leaf._pooling
+        self.leaf = leaf
+        self.slots = int(slots)
+        self.K, self.hop, self.F = conv._kernel_size, pool.strides, conv._filters
+        self.pcm = sample_dtype is torch.int16                            # fixed for the bank's life: the state layout depends on it
+        self.sample_dtype = sample_dtype
+        if _native.load().leaf_stream_state_bytes(self.slots, self.F, self.K, self.hop, 0) == 0:
+            raise ValueError(f"LeafStreamBank: no one-launch streaming kernel for window {self.K} / hop {self.hop} "
+                             "(16 kHz and 8 kHz geometries: 401 / 160, 201 / 80)")
+        c = leaf._compression
+        if c is not None and c._floor != 1e-12:
+            raise NotImplementedError("fused path is specialised for the PCEN floor Leaf constructs (1e-12)")
+        self.log1p = bool(log1p) or bool(getattr(leaf, "_log1p", False))
+        self.out_dtype = torch.bfloat16 if out_dtype is torch.bfloat16 else torch.float32
+        self.max_chunk = stream_capacity(self.K, self.hop) - _native.load().leaf_stream_history_samples(self.K, self.hop)
+        self.device = None if device is None else torch.device(device)
+        self.state_buf: Optional[torch.Tensor] = None                     # [history half 0 | history half 1 | smoother], never cleared
+        self.running = [False] * self.slots
+        self.hist_len = [0] * self.slots
+        self.next = [0] * self.slots
+        self.parity = [0] * self.slots
+        self.started = [False] * self.slots
+
+    def _plan(self, lengths, end):
+        """The host side of a step, on integers alone: moves every slot's position through ``stream_plan`` and returns
+        (the slots' ``_native.StreamSlot`` records, the frames each slot emits)."""
+        B = self.slots
+        lengths = [int(v) for v in lengths]
+        end = [False] * B if end is None else [bool(v) for v in end]
+        if len(lengths) != B or len(end) != B:
+            raise ValueError(f"LeafStreamBank.step: lengths and end must have one entry per slot ({B})")
+        for b, Tc in enumerate(lengths):
+            if not 0 <= Tc <= self.max_chunk:
+                raise ValueError(f"LeafStreamBank.step: lengths[{b}] = {Tc} is outside 0 .. max_chunk = {self.max_chunk}")
+        recs, counts = (_native.StreamSlot * B)(), [0] * B
+        for b in range(B):
+            Tc, r = lengths[b], recs[b]
+            if Tc == 0 and not (end[b] and self.running[b]):              # idle, or `end` on a slot that is not running
+                r.idle = 1
+                continue
+            if not self.running[b]:                                       # a stream begins: nothing of the state is read
+                self.running[b], self.hist_len[b], self.next[b], self.started[b] = True, 0, 0, False
+            hist, T = self.hist_len[b], self.hist_len[b] + Tc
+            r.hist_len, r.Tc, r.parity, r.started = hist, Tc, self.parity[b], int(self.started[b])
+            first, n, drop, hist2, next2 = stream_plan(hist, self.next[b], Tc, self.K, self.hop, False) if Tc else (self.next[b], 0, 0, hist, self.next[b])
+            if not end[b]:
+                r.first, r.n, r.drop_samples = first, n, drop
+                self.hist_len[b], self.next[b] = hist2, next2
+            else:
+                # the stream ends: what a step and then a flush would emit.  The flush's frames are those of the buffer the step
+                # keeps, [drop, T); where the step itself emits nothing that is the whole buffer, and one pass serves
+                first2, n2, _, _, _ = stream_plan(hist2, next2, 0, self.K, self.hop, True)
+                if n == 0:
+                    r.first, r.n, r.drop_samples = first2, n2, T
+                else:
+                    r.first, r.n, r.drop_samples, r.end_first, r.end_n = first, n, drop, first2, n2
+                n += n2
+                self.running[b], self.hist_len[b], self.next[b] = False, 0, 0
+            counts[b] = n
+            self.started[b] = (self.started[b] or n > 0) and self.running[b]
+            self.parity[b] ^= 1
+        return recs, counts
+
+    @torch.no_grad()
+    def step(self, chunk: Optional[torch.Tensor], lengths, end=None):
+        """One step of every slot.  ``chunk``: (slots,1,Tmax) or (slots,Tmax) on the device, ``sample_dtype`` samples; a strided view
+        is read in place, and only ``chunk[b, :lengths[b]]`` is ever read (None: no slot has samples).  ``lengths``: per slot, host
+        integers in 0 .. min(Tmax, max_chunk).  ``end``: per slot, host booleans -- the slot's stream ends with this chunk, its
+        remaining frames come out in this step with the reference's zero padding behind the last sample, and the slot is free.  A
+        slot that is not running begins a new stream with its first samples; no samples and no ``end`` leaves a slot idle (its state
+        is not touched); ``end`` on a slot that is not running does nothing.  Returns ``(frames, counts)``: ``frames`` is
+        (slots, F, max(counts)) in ``out_dtype``, row b holding ``counts[b]`` frames and zeros behind them; ``counts`` is computed on
+        the host, nothing synchronises."""
+        B = self.slots
+        for b, Tc in enumerate(lengths):                                  # before anything else: nothing is launched, no state moves
+            if int(Tc) > self.max_chunk:
+                raise ValueError(f"LeafStreamBank.step: lengths[{b}] = {int(Tc)} is outside 0 .. max_chunk = {self.max_chunk}")
+        x2 = None
+        if chunk is not None:
+            _native.require_hip(chunk, "LeafStreamBank.step")
+            if chunk.dtype != self.sample_dtype:
+                raise ValueError(f"LeafStreamBank.step: this bank takes {self.sample_dtype} samples and got a {chunk.dtype} chunk")
+            x2 = chunk[:, 0, :] if chunk.dim() == 3 else chunk
+            if x2.dim() != 2 or x2.shape[0] != B:
+                raise ValueError(f"LeafStreamBank.step: chunk must be ({B},1,Tmax) or ({B},Tmax), got {tuple(chunk.shape)}")
+            if self.device is not None and x2.device != self.device:
+                raise ValueError(f"LeafStreamBank.step: this bank lives on {self.device} and got a chunk on {x2.device}")
+        Tmax = 0 if x2 is None else x2.shape[1]
+        for b, Tc in enumerate(lengths):
+            if int(Tc) > Tmax:
+                raise ValueError(f"LeafStreamBank.step: lengths[{b}] = {int(Tc)} exceeds the chunk's {Tmax} samples")
+        if self.device is None:
+            if x2 is None:
+                return torch.empty((B, self.F, 0), dtype=self.out_dtype), [0] * B   # (nothing has ever run)
+            self.device = x2.device
+        if x2 is not None and ((Tmax > 1 and x2.stride(1) != 1) or (B > 1 and x2.stride(0) < Tmax)):    # (an expanded view: rows overlap)
+            x2 = x2.contiguous()
+        recs, counts = self._plan(lengths, end)
+        dev, n_max = self.device, max(counts)
+        if self.state_buf is None:
+            self.state_buf = _native.stream_state(B, self.F, self.K, self.hop, _native.FLAG_X_PCM16 if self.pcm else 0, dev)
+        params, flags = _native._gather(dev, self.leaf._kernel_params(), self.leaf._compression is not None, self.log1p)
+        flags |= (_native.FLAG_X_PCM16 if self.pcm else 0) | (_native.FLAG_OUT_BF16 if self.out_dtype is torch.bfloat16 else 0)
+        out = torch.empty((B, self.F, n_max), dtype=self.out_dtype, device=dev)
+        _native.stream_bank_step(x2.data_ptr() if Tmax else 0, x2.stride(0) if Tmax else 0, recs, n_max, self.state_buf, params,
+                                 self.F, self.K, self.hop, flags, out.data_ptr() if n_max else 0, dev)
+        return out, counts
+
+    def flush(self, slots=None):
+        """A step without samples that ends the named slots (all running slots by default): ``(frames, counts)`` as ``step``."""
+        ending = range(self.slots) if slots is None else [int(b) for b in slots]
+        end = [False] * self.slots
+        for b in ending:
+            end[b] = True
+        return self.step(None, [0] * self.slots, end)

@@ -10,7 +10,14 @@ long recording.  Two figures per leg and shape, each the median / min / max over
   device  HIP events around the same steps, ENQUEUED WHILE THE DEVICE IS KEPT BUSY by matrix products queued in front, so that the
           steps run back to back from a full queue: the device's own time per step, launch gaps between dependent kernels included,
           the host's enqueue time excluded
-No assertion on any time; prints the table and, with --out, writes it."""
+No assertion on any time; prints the table and, with --out, writes it.
+
+    python tools/bench_stream.py --bank [--rounds 20] [--steps 40] [--out profiles/stream_bank.txt]
+
+The bank leg: B INDEPENDENT streams, one LeafStreamBank step for all of them against what a server does without the bank -- a Python
+loop over B LeafStream(fused=True) objects of one waveform each -- in one process, the two sides taking turns round after round (the
+order alternates) after a warm-up round.  B = 4 / 16 / 64, chunks of 160 and 1600 samples; wall time per step (all B streams served,
+device synchronised behind the last step): median [p10, p90] over the rounds, and the ratio of the medians."""
 import argparse
 import os
 import statistics
@@ -36,9 +43,57 @@ def run_steps(stream, x, chunk, steps, pos):
     return pos
 
 
+def bank_leg(m, args):
+    rounds = args.rounds if args.rounds > 6 else 20
+    lines = [f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {rounds} timed rounds x {args.steps} steps per side after a warm-up round; "
+             "wall us per step (all B streams): median [p10, p90]",
+             f"{'B':>3} {'chunk':>6} {'bank step':>30} {'loop of B fused streams':>30} {'bank / loop':>12}"]
+    pct = lambda v, q: sorted(v)[min(len(v) - 1, int(round(q * (len(v) - 1))))]
+    for B in (4, 16, 64):
+        x = (2 * torch.rand(B, 1, 160000, device=DEV) - 1)
+        for chunk in (160, 1600):
+            bank = L.LeafStreamBank(m, B)
+            loop = [L.LeafStream(m, fused=True) for _ in range(B)]
+            lengths = [chunk] * B
+
+            def bank_steps(n, pos):
+                for _ in range(n):
+                    pos = 0 if pos + chunk > x.shape[-1] else pos
+                    bank.step(x[:, :, pos:pos + chunk], lengths)
+                    pos += chunk
+                return pos
+
+            def loop_steps(n, pos):
+                for _ in range(n):
+                    pos = 0 if pos + chunk > x.shape[-1] else pos
+                    for b, s in enumerate(loop):
+                        s.step(x[b:b + 1, :, pos:pos + chunk])
+                    pos += chunk
+                return pos
+
+            sides = {"bank": bank_steps, "loop": loop_steps}
+            pos, wall = {k: 0 for k in sides}, {k: [] for k in sides}
+            for rnd in range(rounds + 1):
+                for name in (list(sides) if rnd % 2 == 0 else list(sides)[::-1]):
+                    pos[name] = sides[name](5, pos[name])                 # the side's code and data warm again after the other side
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    pos[name] = sides[name](args.steps, pos[name])
+                    torch.cuda.synchronize()
+                    if rnd:
+                        wall[name].append((time.perf_counter() - t0) / args.steps * 1e6)
+            fmt = lambda v: f"{statistics.median(v):9.1f} [{pct(v, 0.1):8.1f}, {pct(v, 0.9):8.1f}]"
+            lines.append(f"{B:>3} {chunk:>6} {fmt(wall['bank']):>30} {fmt(wall['loop']):>30} {statistics.median(wall['bank']) / statistics.median(wall['loop']):>12.3f}")
+            bank.flush()
+            for s in loop:
+                s.flush()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--bank", action="store_true", help="the LeafStreamBank leg (module docstring) instead of fused against unfused")
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -46,6 +101,13 @@ def main():
     m = L.Leaf().eval().to(DEV)
     for p in m.parameters():
         p.requires_grad_(False)
+    if args.bank:
+        text = "\n".join(bank_leg(m, args))
+        print(text)
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write(text + "\n")
+        return
     blocker = torch.randn(8192, 8192, device=DEV)
     lines = [f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {args.rounds} timed rounds x {args.steps} steps per leg after a warm-up round; "
              "us per step: median (min .. max)",
