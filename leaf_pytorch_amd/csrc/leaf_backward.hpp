@@ -102,9 +102,6 @@ __global__ void pcen_bwd_rows_kernel(const float* __restrict__ raw, const void* 
 // time) are first-order linear recurrences = compositions of affine maps: composed in-lane for the pair, scanned across
 // the wavefront with 6 shuffle steps (up for the EMA, down for gM), with a carried state between chunks.  The serial
 // kernel spends 137 us on B F = 10240 rows of 100 frames (160 waves, latency-bound); this one keeps the whole chip busy.
-#ifndef LEAF_BWD_SCAN_REG
-#define LEAF_BWD_SCAN_REG 1            // pcen_bwd_scan_kernel: rows of up to 512 frames keep the smoother's values in registers between its two passes; 0: through `ema` (A/B)
-#endif
 constexpr int kScanRegChunks = 4;
 #ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
 __global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restrict__ raw, const void* __restrict__ gout, int BF,
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restr
     // needs M_m and M_{m-1} of the lane's own two frames: a neighbour's register, not a round trip through `ema` in memory); longer
     // rows store them and read them back
     constexpr int RC = kScanRegChunks;
-    const bool inreg = LEAF_BWD_SCAN_REG && nchunk <= RC;
+    const bool inreg = nchunk <= RC;
     float M0r[RC], M1r[RC];
     // ---- forward in time: M_m = w p_m + (1-w) M_{m-1}, M_{-1} = p_0 (postprocessing.py:15)
     float carry = p0;
@@ -363,9 +360,6 @@ __global__ void pool_bwd_dg_kernel(const float* __restrict__ e, const float* __r
 
 // One block per filter: d pool_b, d pool_w and the PCEN parameter sums over the batch.
 constexpr int kParamRedThreads = 1024;
-#ifndef LEAF_PARAM_REDUCE_BATCHED
-#define LEAF_PARAM_REDUCE_BATCHED 1    // param_reduce_kernel: the eight sums of the overlap-save backwards loaded together, one barrier; 0: one after the other (A/B, same bits)
-#endif
 #ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
 __global__ __launch_bounds__(kParamRedThreads) void param_reduce_kernel(const float* __restrict__ gpre, const float* __restrict__ dg,
                                     const float* __restrict__ g, const float* __restrict__ rowsum,
@@ -394,7 +388,7 @@ __global__ __launch_bounds__(kParamRedThreads) void param_reduce_kernel(const fl
         for (int w = 0; w < kParamRedThreads / 64; ++w) t += r[w];
         return t;
     };
-    if (LEAF_PARAM_REDUCE_BATCHED && grow && dwpart) {
+    if (grow && dwpart) {
         // The overlap-save backwards (rows' sums from the scan kernel, per-block partials from the main kernel): every load of all
         // eight sums first, four strides of each at a time, then ONE barrier for the eight block sums -- one memory latency and one
         // barrier instead of eight of each (this kernel is a launch of a few microseconds between the main kernel and the caller).

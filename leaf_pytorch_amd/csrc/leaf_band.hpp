@@ -40,17 +40,8 @@
 
 namespace {
 
-#ifndef LEAF_BAND_EDGE_PIPE
-#define LEAF_BAND_EDGE_PIPE 0      // band tasks: 1 = the next edge frame's table requested before the current one is consumed -- measured 7 % SLOWER
-#endif                             // (0.1314 vs 0.1223 ms at cfg1, same box: 32 more live registers, 25 more spill instructions per task)
-#ifndef LEAF_BAND_EDGE_EARLY
-#define LEAF_BAND_EDGE_EARLY 0     // band tasks: 1 = the first edge table requested before the reduction of the regular frames -- 2 % slower
-#endif                             // (0.1251 vs 0.1222 ms at cfg1, same box) and 32 B of scratch; 0: after it, no scratch
 #ifndef LEAF_PREP_ABLATE
 #define LEAF_PREP_ABLATE 0         // measurement only (results wrong): fft_prep_band_kernel without 1 = the edge-table workgroups, 2 = the G~ workgroup, 4 = the decision sums, 8 = the first-block spectra, 16 = the taps' transform, 32 = the twiddle tables (bits)
-#endif
-#ifndef LEAF_BAND_PW_EARLY
-#define LEAF_BAND_PW_EARLY 1       // band tasks: pooling weights requested before the second transforms (0: after them, A/B)
 #endif
 constexpr int kBandLh = 12;                                   // half length of phi_D in decimated samples (leaf_band_phi.inc)
 constexpr float kBandEps2 = 9e-12f;                           // eps^2, eps = 3e-6
@@ -857,19 +848,18 @@ __device__ __forceinline__ void band_task(const FftParams& p, const float (&rq)[
         pin32(ti);
     }
     stamp(12);                                                           // transposed
-    // the pooling weights of this lane's filter: requested before the second transforms (LEAF_BAND_PW_EARLY) they land under them
+    // the pooling weights of this lane's filter: requested before the second transforms they land under them
     const int me2 = mem[g2];
     const int fid2 = me2 & 0xffff;
     const bool valid = !(me2 & kBandInvalid);
     float pw[NV];
-    auto load_weights = [&]() {
+    {
         const float* gsrc = p.band.gz + (size_t)fid2 * GEO::GZF + GEO::GZ0 + l2;
         asm volatile("" ::: "memory");
 #pragma unroll
         for (int k = 0; k < NV; ++k) pw[k] = gsrc[PG / D * k];
         asm volatile("" ::: "memory");
-    };
-    if constexpr (LEAF_BAND_PW_EARLY) load_weights();
+    }
     if constexpr (A == 16) {
         band_dit16_stage<1, 0>(tr, ti);
         band_dit16_stage<1, 16>(tr, ti);
@@ -883,7 +873,6 @@ __device__ __forceinline__ void band_task(const FftParams& p, const float (&rq)[
         fft32_dif(tr, ti);                                               // register i <-> m1 = brev5(i), m2 = l2
     }
     stamp(5);                                                            // transforms done
-    if constexpr (!LEAF_BAND_PW_EARLY) load_weights();
     float e[32];
 #pragma unroll
     for (int k = 0; k < 32; ++k) e[k] = tr[k] * tr[k] + ti[k] * ti[k];
@@ -892,8 +881,8 @@ __device__ __forceinline__ void band_task(const FftParams& p, const float (&rq)[
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // (issued before those 32 loads) have landed
     stamp(6);                                                            // energies, next task reserved, weights landed
     // Edge frames of this block (block 0 and the clip's last blocks only): dense tables over all 32 registers (the tails wrap
-    // around the block).  The first entry's table is requested before the reduction of the regular frames, each further one before the
-    // previous is consumed (those unconditionally -- a clamped entry when there is none -- so that the waits can be counted).
+    // around the block).  The first entry's table is requested after the reduction of the regular frames, each further one once
+    // the previous is consumed (requesting them earlier measured 2 % and 7 % slower: profiles/r05/ab_band_edge.txt).
     const int n_edge = p.band.n_edge;
     auto next_edge = [&](int s) {
         while (s < n_edge && __builtin_amdgcn_readfirstlane(elist[4 * s]) != c) ++s;
@@ -908,7 +897,7 @@ __device__ __forceinline__ void band_task(const FftParams& p, const float (&rq)[
         for (int k = 0; k < 32; ++k) et[k] = tab[k * LPF];
         asm volatile("" ::: "memory");
     };
-    float et0[32], et1[32];
+    float et0[32];
     int s0 = n_edge;
     float acc[16];
 #pragma unroll
@@ -923,10 +912,6 @@ __device__ __forceinline__ void band_task(const FftParams& p, const float (&rq)[
         }
     }
     asm volatile("" : "+v"(acc[0]));
-    if (LEAF_BAND_EDGE_EARLY && has_edges) {                             // (the pooling weights are dead: registers for the first table)
-        s0 = next_edge(0);
-        if (s0 < n_edge) issue_edge(et0, s0);
-    }
     // halving butterfly over the lanes of a filter (frame_butterfly16 without the stages inside a filter's lanes):
     // afterwards acc[0] (and acc[1] for A = 16) hold the totals of frame fi0 (+ 1)
 #pragma unroll
@@ -965,7 +950,7 @@ __device__ __forceinline__ void band_task(const FftParams& p, const float (&rq)[
         }
     }
     stamp(13);                                                           // pooling, reduction, sums added
-    if (!LEAF_BAND_EDGE_EARLY && has_edges) {
+    if (has_edges) {
         s0 = next_edge(0);
         if (s0 < n_edge) issue_edge(et0, s0);
     }
@@ -976,24 +961,11 @@ __device__ __forceinline__ void band_task(const FftParams& p, const float (&rq)[
         v = band_filter_sum<A>(v);
         if (valid && l2 == 0) out(fid2, elist[4 * s + 1], v);
     };
-#if LEAF_BAND_EDGE_PIPE
-    while (s0 < n_edge) {
-        const int s1 = next_edge(s0 + 1);
-        issue_edge(et1, s1);
-        consume_edge(et0, s0);
-        if (s1 >= n_edge) break;
-        s0 = next_edge(s1 + 1);
-        issue_edge(et0, s0);
-        consume_edge(et1, s1);
-    }
-#else
-    (void)et1;
     while (s0 < n_edge) {
         consume_edge(et0, s0);
         s0 = next_edge(s0 + 1);
         if (s0 < n_edge) issue_edge(et0, s0);
     }
-#endif
 }
 
 }  // namespace

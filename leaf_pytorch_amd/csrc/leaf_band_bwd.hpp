@@ -327,7 +327,7 @@ __device__ __forceinline__ void band_bwd_task(const FftParams& p, const float (&
 #ifndef LEAF_DX_NOWAIT                 // measurement only (wrong sums): what the ordered turn costs
         wg_wait_ge(gticket, want);
 #endif
-        if (LEAF_DX_PRIO) __builtin_amdgcn_s_setprio(3);
+        __builtin_amdgcn_s_setprio(3);
 #pragma unroll
         for (int g = 0; g < G; ++g) {                                     // member after member: their windows overlap (a wave's LDS
             const int me = __builtin_amdgcn_readfirstlane(mem[g]);        // operations execute in order)
@@ -345,7 +345,7 @@ __device__ __forceinline__ void band_bwd_task(const FftParams& p, const float (&
         }
         wg_release();
         if (lane == 0) __hip_atomic_fetch_add(gticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (LEAF_DX_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
     }
     amu = band_filter_sum<A>(amu);
     asg = band_filter_sum<A>(asg);

@@ -102,9 +102,6 @@ __device__ __forceinline__ void io_store(void* p, size_t i, int bf16, float v) {
 #ifndef LEAF_KLOOP_SINGLE_BUFFER_RT
 #define LEAF_KLOOP_SINGLE_BUFFER_RT 4    // register tiles with >= this many filter tiles use a single-buffered k-loop
 #endif
-#ifndef LEAF_DMA_PREFETCH
-#define LEAF_DMA_PREFETCH 1              // next task's waveform window via global_load_lds under the epilogue
-#endif
 #ifndef LEAF_TRACE
 #define LEAF_TRACE 0                     // tools/trace.py: per-phase s_memtime stamps of block 0 into the workspace tail
 #endif

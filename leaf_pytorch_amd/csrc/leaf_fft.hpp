@@ -23,12 +23,6 @@
 #include "leaf_common.hpp"
 #include "leaf_fused.hpp"      // SlotGeom, the PCEN row helpers
 
-#ifndef LEAF_FFT32_DIT
-#define LEAF_FFT32_DIT 1               // 32-point register transforms: 1 decimation in time with FMA-fused butterflies, 0 DIF
-#endif
-#ifndef LEAF_FFT_SWAP
-#define LEAF_FFT_SWAP 1                // half-wave exchange of the wave-level FFT: 1 v_permlane32_swap (VALU), 0 ds_bpermute
-#endif
 #ifndef LEAF_FFT_ABLATE
 #define LEAF_FFT_ABLATE 0              // measurement only (tools/ablate_fft.py; results are wrong by construction):
 #endif                                 // bit 0 no spectrum loads, 1 no inverse transform, 2 no pooling FMAs / LDS reads,
@@ -45,43 +39,14 @@ __host__ __device__ constexpr int brev5(int i) {
     return ((i & 1) << 4) | ((i & 2) << 2) | (i & 4) | ((i & 8) >> 2) | ((i & 16) >> 4);
 }
 
-template <int HALF>
-__device__ __forceinline__ void fft32_stage(float (&re)[32], float (&im)[32]) {
-    constexpr float C[16] = {1.0f, 0.98078528f, 0.923879533f, 0.831469612f, 0.707106781f, 0.555570233f, 0.382683432f, 0.195090322f, 0.0f, -0.195090322f, -0.382683432f, -0.555570233f, -0.707106781f, -0.831469612f, -0.923879533f, -0.98078528f};
-    constexpr float S[16] = {0.0f, -0.195090322f, -0.382683432f, -0.555570233f, -0.707106781f, -0.831469612f, -0.923879533f, -0.98078528f, -1.0f, -0.98078528f, -0.923879533f, -0.831469612f, -0.707106781f, -0.555570233f, -0.382683432f, -0.195090322f};
-#pragma unroll
-    for (int blk = 0; blk < 32; blk += 2 * HALF) {
-#pragma unroll
-        for (int j = 0; j < HALF; ++j) {
-            const int a = blk + j, b = a + HALF;
-            constexpr int STEP = 16 / HALF;
-            const int tw = j * STEP;
-            const float ur = re[a] + re[b], ui = im[a] + im[b];
-            const float vr = re[a] - re[b], vi = im[a] - im[b];
-            re[a] = ur;
-            im[a] = ui;
-            if (tw == 0) {
-                re[b] = vr;
-                im[b] = vi;
-            } else if (tw == 8) {                        // W = -i
-                re[b] = vi;
-                im[b] = -vr;
-            } else {
-                re[b] = vr * C[tw] - vi * S[tw];
-                im[b] = vr * S[tw] + vi * C[tw];
-            }
-        }
-    }
-}
-
 // 32-point forward DFT (e^{-2 pi i nk/32}) in registers: register i ends up holding X[brev5(i)].
 //
-// LEAF_FFT32_DIT = 1 (default): radix-2 decimation in TIME on the bit-reversed register labelling (position p of the
-// flow graph lives in register brev5(p) -- a compile-time relabel -- so input and output conventions are those of the
-// DIF version).  A DIT butterfly is a +- w b, which fuses with the twiddle product: a + w b takes two FMAs per
-// component, and a - w b = 2a - (a + w b) one more: 6 instructions instead of the DIF butterfly's 8 (subtract, then a
-// 4-instruction complex multiply).  388 instead of 456 instructions per transform; the kernel is VALU-issue-bound, so
-// this is time.  LEAF_FFT32_DIT = 0: the decimation-in-frequency version.
+// Radix-2 decimation in TIME on the bit-reversed register labelling (position p of the flow graph lives in register
+// brev5(p) -- a compile-time relabel -- so input and output conventions are those of a decimation-in-frequency
+// transform, whence the name fft32_dif).  A DIT butterfly is a +- w b, which fuses with the twiddle product: a + w b
+// takes two FMAs per component, and a - w b = 2a - (a + w b) one more: 6 instructions instead of a DIF butterfly's 8
+// (subtract, then a 4-instruction complex multiply).  388 instead of 456 instructions per transform; the kernel is
+// VALU-issue-bound, so this is time.
 template <int HALF>
 __device__ __forceinline__ void fft32_dit_stage(float (&re)[32], float (&im)[32]) {
     constexpr float C[16] = {1.0f, 0.98078528f, 0.923879533f, 0.831469612f, 0.707106781f, 0.555570233f, 0.382683432f, 0.195090322f, 0.0f, -0.195090322f, -0.382683432f, -0.555570233f, -0.707106781f, -0.831469612f, -0.923879533f, -0.98078528f};
@@ -117,19 +82,11 @@ __device__ __forceinline__ void fft32_dit_stage(float (&re)[32], float (&im)[32]
 }
 
 __device__ __forceinline__ void fft32_dif(float (&re)[32], float (&im)[32]) {
-#if LEAF_FFT32_DIT
     fft32_dit_stage<1>(re, im);
     fft32_dit_stage<2>(re, im);
     fft32_dit_stage<4>(re, im);
     fft32_dit_stage<8>(re, im);
     fft32_dit_stage<16>(re, im);
-#else
-    fft32_stage<16>(re, im);
-    fft32_stage<8>(re, im);
-    fft32_stage<4>(re, im);
-    fft32_stage<2>(re, im);
-    fft32_stage<1>(re, im);
-#endif
 }
 
 // Twiddle tables of the wave-level FFT, built once per workgroup in LDS:
@@ -178,7 +135,6 @@ __device__ __forceinline__ void fft2048(float (&re)[32], float (&im)[32], float*
     // time: v_permlane32_swap (gfx950: swaps the upper half of one VGPR with the lower half of another, in the VALU --
     // no LDS round trip) gathers [a_j | a_j'] and [b_j | b_j'], one add and one subtract serve both halves, and a second
     // swap puts [a+b | a-b] back in place.  Then the per-lane twiddle (1 on the lower half) and 32 points over j.
-#if LEAF_FFT_SWAP
     auto cross = [](float& x0, float& x1) {
         auto g = __builtin_amdgcn_permlane32_swap(__float_as_uint(x0), __float_as_uint(x1), false, false);
         const float a = __uint_as_float(g[0]), b = __uint_as_float(g[1]);            // [a_j | a_j'], [b_j | b_j']
@@ -202,24 +158,6 @@ __device__ __forceinline__ void fft2048(float (&re)[32], float (&im)[32], float*
             im[j] = tr[j] * w.y + ti[j] * w.x;
         }
     }
-#else
-    const float sgn = h ? -1.0f : 1.0f;
-    const int paddr = (lane ^ 32) << 2;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-        const float pr = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(tr[j])));
-        const float pi = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(ti[j])));
-        const float ur = fmaf(tr[j], sgn, pr), ui = fmaf(ti[j], sgn, pi);
-        if (j == 0) {
-            re[j] = ur;
-            im[j] = ui;
-        } else {
-            const float2 w = twh[2 * j + h];
-            re[j] = ur * w.x - ui * w.y;
-            im[j] = ur * w.y + ui * w.x;
-        }
-    }
-#endif
     fft32_dif(re, im);                                   // register i <-> k' = brev5(i): element 64 k' + lane
 }
 

@@ -111,11 +111,7 @@ __device__ __forceinline__ void lds_stream32(unsigned addr, OffFn, Body body) {
     for (int j = 0; j < 8; ++j) body(24 + j, buf[1][j]);
 }
 struct OffTwl { static constexpr int off(int i) { return 512 * brev5(i); } };      // twl[brev5(i)][lane], register order
-struct OffTwh { static constexpr int off(int j) { return 16 * (j & 15) + 8 * (j >> 4); } };   // twp[h][j & 15][j >> 4] from &twp[h][0][0]
 struct OffRow { static constexpr int off(int k) { return 512 * (k & 15); } };      // 16 consecutive 64-entry rows
-#ifndef LEAF_FFT_TWL_PAIRS
-#define LEAF_FFT_TWL_PAIRS 0       // 1: first-stage twiddles in register-pair order, 16 ds_read_b128 instead of 31 ds_read_b64 --
-#endif                             // measured slower (0.2188 vs 0.2178 ms whole forward, interleaved): kept as an A/B switch
 
 // scr[brev5(i) * 68 + lane] = v[i], i = 0..31, through M0-relative add-tid stores (M0 saved and restored: the compiler
 // owns it for the LDS-DMA builtin).  scr_lds = the wave's scr as an LDS byte address (wave-uniform).
@@ -163,92 +159,6 @@ __device__ __forceinline__ void wg_transpose_store(const float (&v)[32], unsigne
                  : "=&s"(keep)
                  : "v"(v[16]), "v"(v[17]), "v"(v[18]), "v"(v[19]), "v"(v[20]), "v"(v[21]), "v"(v[22]), "v"(v[23]), "v"(v[24]), "v"(v[25]), "v"(v[26]), "v"(v[27]), "v"(v[28]), "v"(v[29]), "v"(v[30]), "v"(v[31]), "s"(scr_lds)
                  : "memory");
-}
-
-// Half-buffer transposition (16-wave workgroups: the LDS only has room for 16 rows of scr per wave).  Step S stores the
-// 16 registers whose row brev5(i) lies in [16 S, 16 S + 16) as rows 0..15; the lanes whose row k1r = lane & 31 lies in that
-// range then read their 32 values (8 ds_read_b128 under an exec mask set inside the statement, so that the two steps
-// fill the same destination registers without compiler-made copies).
-template <int STEP>
-__device__ __forceinline__ void wg_transpose_store_half(const float (&v)[32], unsigned scr_lds) {
-    unsigned keep;
-    if constexpr (STEP == 0) {
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %17\n\ts_nop 0\n\t"
-                     "ds_write_addtid_b32 %1 offset:0\n\t"
-                     "ds_write_addtid_b32 %2 offset:2176\n\t"
-                     "ds_write_addtid_b32 %3 offset:1088\n\t"
-                     "ds_write_addtid_b32 %4 offset:3264\n\t"
-                     "ds_write_addtid_b32 %5 offset:544\n\t"
-                     "ds_write_addtid_b32 %6 offset:2720\n\t"
-                     "ds_write_addtid_b32 %7 offset:1632\n\t"
-                     "ds_write_addtid_b32 %8 offset:3808\n\t"
-                     "ds_write_addtid_b32 %9 offset:272\n\t"
-                     "ds_write_addtid_b32 %10 offset:2448\n\t"
-                     "ds_write_addtid_b32 %11 offset:1360\n\t"
-                     "ds_write_addtid_b32 %12 offset:3536\n\t"
-                     "ds_write_addtid_b32 %13 offset:816\n\t"
-                     "ds_write_addtid_b32 %14 offset:2992\n\t"
-                     "ds_write_addtid_b32 %15 offset:1904\n\t"
-                     "ds_write_addtid_b32 %16 offset:4080\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(v[0]), "v"(v[2]), "v"(v[4]), "v"(v[6]), "v"(v[8]), "v"(v[10]), "v"(v[12]), "v"(v[14]), "v"(v[16]), "v"(v[18]), "v"(v[20]), "v"(v[22]), "v"(v[24]), "v"(v[26]), "v"(v[28]), "v"(v[30]), "s"(scr_lds)
-                     : "memory");
-    } else {
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %17\n\ts_nop 0\n\t"
-                     "ds_write_addtid_b32 %1 offset:0\n\t"
-                     "ds_write_addtid_b32 %2 offset:2176\n\t"
-                     "ds_write_addtid_b32 %3 offset:1088\n\t"
-                     "ds_write_addtid_b32 %4 offset:3264\n\t"
-                     "ds_write_addtid_b32 %5 offset:544\n\t"
-                     "ds_write_addtid_b32 %6 offset:2720\n\t"
-                     "ds_write_addtid_b32 %7 offset:1632\n\t"
-                     "ds_write_addtid_b32 %8 offset:3808\n\t"
-                     "ds_write_addtid_b32 %9 offset:272\n\t"
-                     "ds_write_addtid_b32 %10 offset:2448\n\t"
-                     "ds_write_addtid_b32 %11 offset:1360\n\t"
-                     "ds_write_addtid_b32 %12 offset:3536\n\t"
-                     "ds_write_addtid_b32 %13 offset:816\n\t"
-                     "ds_write_addtid_b32 %14 offset:2992\n\t"
-                     "ds_write_addtid_b32 %15 offset:1904\n\t"
-                     "ds_write_addtid_b32 %16 offset:4080\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(v[1]), "v"(v[3]), "v"(v[5]), "v"(v[7]), "v"(v[9]), "v"(v[11]), "v"(v[13]), "v"(v[15]), "v"(v[17]), "v"(v[19]), "v"(v[21]), "v"(v[23]), "v"(v[25]), "v"(v[27]), "v"(v[29]), "v"(v[31]), "s"(scr_lds)
-                     : "memory");
-    }
-}
-// t[q] = row[4 q .. 4 q + 3] for the lanes of `mask`; valid after a wait naming t (lds_wait_b128x16)
-__device__ __forceinline__ void wg_transpose_load_masked(f32x4 (&t)[8], unsigned row_addr, unsigned long long mask) {
-    unsigned long long save;
-    asm volatile("s_mov_b64 %8, exec\n\ts_mov_b64 exec, %10\n\t"
-                 "ds_read_b128 %0, %9 offset:0\n\tds_read_b128 %1, %9 offset:16\n\t"
-                 "ds_read_b128 %2, %9 offset:32\n\tds_read_b128 %3, %9 offset:48\n\t"
-                 "ds_read_b128 %4, %9 offset:64\n\tds_read_b128 %5, %9 offset:80\n\t"
-                 "ds_read_b128 %6, %9 offset:96\n\tds_read_b128 %7, %9 offset:112\n\t"
-                 "s_mov_b64 exec, %8"
-                 : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]), "=&s"(save)
-                 : "v"(row_addr), "s"(mask)
-                 : "memory");
-}
-// The first of the two masked loads of a plane: destinations are pure outputs (no value carried in), so that the compiler
-// does not have to materialise -- and keep alive through the whole previous phase -- 64 registers of zeros for them.
-__device__ __forceinline__ void wg_transpose_load_masked_first(f32x4 (&t)[8], unsigned row_addr, unsigned long long mask) {
-    unsigned long long save;
-    asm volatile("s_mov_b64 %8, exec\n\ts_mov_b64 exec, %10\n\t"
-                 "ds_read_b128 %0, %9 offset:0\n\tds_read_b128 %1, %9 offset:16\n\t"
-                 "ds_read_b128 %2, %9 offset:32\n\tds_read_b128 %3, %9 offset:48\n\t"
-                 "ds_read_b128 %4, %9 offset:64\n\tds_read_b128 %5, %9 offset:80\n\t"
-                 "ds_read_b128 %6, %9 offset:96\n\tds_read_b128 %7, %9 offset:112\n\t"
-                 "s_mov_b64 exec, %8"
-                 : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7]), "=&s"(save)
-                 : "v"(row_addr), "s"(mask)
-                 : "memory");
-}
-__device__ __forceinline__ void lds_wait_b128x16(f32x4 (&a)[8], f32x4 (&b)[8]) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]),
-                   "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]));
 }
 
 // Column-half transposition (swap-free cross stage, below): the 32 lanes of one half-wave store their 32 registers as
@@ -307,19 +217,13 @@ __device__ __forceinline__ void wg_transpose_store_cols(const float (&v)[32], un
                  : "memory");
 }
 
-// Twiddle tables of the workgroup kernels: twl as fft_build_twiddles (LEAF_FFT_TWL_PAIRS = 1: in register-pair order,
-// twq[pr][l][w] = W_2048^(l brev5(2 pr + w)), one ds_read_b128 per two registers -- measured slower); the half-wave twiddles in
-// PAIR order,
+// Twiddle tables of the workgroup kernels: twl as fft_build_twiddles; the half-wave twiddles in PAIR order,
 //   twp[h][j][w]  = h ? W_64^(j + 16 w) : 1,  j < 16, w < 2   (float2; same 64 entries as twh[j][h]),
 // so that the fused first stage of the second 32-point transform gets both twiddles of a register pair (j, j + 16) with one
 // ds_read_b128 (16 LDS instructions per transform instead of 32).
 __device__ __forceinline__ void fft_build_twiddles_wg(float2* twl, float2* twp, int tid, int nthreads) {
     for (int i = tid; i < 32 * 64; i += nthreads) {
-#if LEAF_FFT_TWL_PAIRS
-        const int pr = i >> 7, l = (i >> 1) & 63, k1 = brev5(2 * pr + (i & 1));   // twq[pr][l][w] = W_2048^(l brev5(2 pr + w))
-#else
         const int k1 = i >> 6, l = i & 63;                                       // twl[k1][l]
-#endif
         float s, c;
         sincospif(2.0f * (float)((l * k1) & (kFftN - 1)) / (float)kFftN, &s, &c);
         twl[i] = make_float2(c, -s);
@@ -331,7 +235,7 @@ __device__ __forceinline__ void fft_build_twiddles_wg(float2* twl, float2* twp, 
         twp[i] = h ? make_float2(c, -s) : make_float2(1.0f, 0.0f);
     }
 }
-// sixteen 16-byte table entries at addr + STRIDE k, four at a time, two groups in flight: body(k, value)
+// sixteen 16-byte table entries at addr + 16 k, four at a time, two groups in flight: body(k, value)
 template <int OFF>
 __device__ __forceinline__ void lds_rd16(f32x4& dst, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
@@ -340,13 +244,13 @@ template <int N>
 __device__ __forceinline__ void lds_wait16x4(f32x4 (&a)[4]) {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : "i"(N));
 }
-template <int STRIDE = 16, typename Body>
+template <typename Body>
 __device__ __forceinline__ void lds_stream16q(unsigned addr, Body body) {
     f32x4 buf[2][4];
     auto issue = [&](auto cc) {
         constexpr int c = decltype(cc)::value;
-        lds_rd16<STRIDE * (4 * c + 0)>(buf[c & 1][0], addr); lds_rd16<STRIDE * (4 * c + 1)>(buf[c & 1][1], addr);
-        lds_rd16<STRIDE * (4 * c + 2)>(buf[c & 1][2], addr); lds_rd16<STRIDE * (4 * c + 3)>(buf[c & 1][3], addr);
+        lds_rd16<16 * (4 * c + 0)>(buf[c & 1][0], addr); lds_rd16<16 * (4 * c + 1)>(buf[c & 1][1], addr);
+        lds_rd16<16 * (4 * c + 2)>(buf[c & 1][2], addr); lds_rd16<16 * (4 * c + 3)>(buf[c & 1][3], addr);
     };
     issue(std::integral_constant<int, 0>{});
     issue(std::integral_constant<int, 1>{});
@@ -370,19 +274,12 @@ __device__ __forceinline__ void lds_stream16q(unsigned addr, Body body) {
 #include "leaf_band.hpp"           // band-limited filter tasks (uses the LDS helpers above)
 namespace {
 
-#ifndef LEAF_FFT_FUSE_TWIDDLE
-#define LEAF_FFT_FUSE_TWIDDLE 1    // 0: separate half-wave twiddle products, then the full 32-point transform (A/B)
-#endif
-#ifndef LEAF_FFT_NOSWAP
-#define LEAF_FFT_NOSWAP 1          // 0: the v_permlane32_swap exchange of round 2's first kernels (A/B measurements)
-#endif
 // SKIP1: the caller has already run the first decimation-in-time stage (registers (k, k + 16), unit twiddles) -- fused with the
 // spectral multiply that produced the input (wg_multiply_stage1)
 template <bool HALF, bool SKIP1 = false>
 __device__ __forceinline__ void fft2048w(float (&re)[32], float (&im)[32], float* scr, unsigned scr_lds, const float2* twl,
                                          const float2* twh, int lane) {
     if constexpr (SKIP1) {
-        static_assert(LEAF_FFT32_DIT, "the fused first stage is the decimation-in-time one");
         fft32_dit_stage<2>(re, im);
         fft32_dit_stage<4>(re, im);
         fft32_dit_stage<8>(re, im);
@@ -390,28 +287,14 @@ __device__ __forceinline__ void fft2048w(float (&re)[32], float (&im)[32], float
     } else {
         fft32_dif(re, im);                               // register i <-> k1 = brev5(i), lane = n2
     }
-#if LEAF_FFT_TWL_PAIRS
-    lds_stream16q<1024>(lds_addr(twl + 2 * lane), [&](int pr, f32x4 w) {    // (w.x, w.y), (w.z, w.w): twiddles of registers 2 pr, 2 pr + 1
-        if (pr > 0) {                                     // register 0: W^0 = 1
-            const float r = re[2 * pr] * w.x - im[2 * pr] * w.y;
-            im[2 * pr] = re[2 * pr] * w.y + im[2 * pr] * w.x;
-            re[2 * pr] = r;
-        }
-        const float r1 = re[2 * pr + 1] * w.z - im[2 * pr + 1] * w.w;
-        im[2 * pr + 1] = re[2 * pr + 1] * w.w + im[2 * pr + 1] * w.z;
-        re[2 * pr + 1] = r1;
-    });
-#else
     lds_stream32(lds_addr(twl + lane), OffTwl{}, [&](int i, v2f w) {
         if (i == 0) return;                               // W^0 = 1
         const float r = re[i] * w.x - im[i] * w.y;
         im[i] = re[i] * w.y + im[i] * w.x;
         re[i] = r;
     });
-#endif
     const int k1r = lane & 31, h = lane >> 5;
     float tr[32], ti[32];
-#if LEAF_FFT_NOSWAP
     // 64-point DFT over n2 = j + 32 hh, first radix-2 step WITHOUT a cross-lane exchange: every lane reads both halves of
     // its transposed row (its own 32 columns and the other half-wave's) and forms a + b (lower half-wave) or a - b (upper)
     // itself -- one FMA per value.  v_permlane32_swap issues at ~8 cycles (profiles/r01/ubench_valu.txt), the 64 swaps
@@ -462,55 +345,6 @@ __device__ __forceinline__ void fft2048w(float (&re)[32], float (&im)[32], float
         plane(im, ti);
         pin32(ti);
     }
-#else
-    if constexpr (HALF) {
-        const unsigned row_addr = scr_lds + 4 * ((k1r & 15) * kWgScrStride + 32 * h);
-        constexpr unsigned long long kLo = 0x0000FFFF0000FFFFull, kHi = 0xFFFF0000FFFF0000ull;   // lanes with k1r < 16 / >= 16
-        f32x4 qr[8], qi[8];
-        wg_transpose_store_half<0>(re, scr_lds);
-        wg_transpose_load_masked_first(qr, row_addr, kLo);
-        wg_transpose_store_half<1>(re, scr_lds);
-        wg_transpose_load_masked(qr, row_addr, kHi);
-        wg_transpose_store_half<0>(im, scr_lds);
-        wg_transpose_load_masked_first(qi, row_addr, kLo);
-        wg_transpose_store_half<1>(im, scr_lds);
-        wg_transpose_load_masked(qi, row_addr, kHi);
-        lds_wait_b128x16(qr, qi);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            tr[4 * q] = qr[q].x; tr[4 * q + 1] = qr[q].y; tr[4 * q + 2] = qr[q].z; tr[4 * q + 3] = qr[q].w;
-            ti[4 * q] = qi[q].x; ti[4 * q + 1] = qi[q].y; ti[4 * q + 2] = qi[q].z; ti[4 * q + 3] = qi[q].w;
-        }
-    } else {
-        const f32x4* row = reinterpret_cast<const f32x4*>(scr + k1r * kWgScrStride + 32 * h);
-        wg_transpose_store(re, scr_lds);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const f32x4 t = row[q];
-            tr[4 * q] = t.x; tr[4 * q + 1] = t.y; tr[4 * q + 2] = t.z; tr[4 * q + 3] = t.w;
-        }
-        asm volatile("" ::: "memory");
-        wg_transpose_store(im, scr_lds);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const f32x4 t = row[q];
-            ti[4 * q] = t.x; ti[4 * q + 1] = t.y; ti[4 * q + 2] = t.z; ti[4 * q + 3] = t.w;
-        }
-    }
-    auto cross = [](float& x0, float& x1) {
-        auto g = __builtin_amdgcn_permlane32_swap(__float_as_uint(x0), __float_as_uint(x1), false, false);
-        const float a = __uint_as_float(g[0]), b = __uint_as_float(g[1]);
-        auto qq = __builtin_amdgcn_permlane32_swap(__float_as_uint(a + b), __float_as_uint(a - b), false, false);
-        x0 = __uint_as_float(qq[0]);
-        x1 = __uint_as_float(qq[1]);
-    };
-#pragma unroll
-    for (int j = 0; j < 32; j += 2) {
-        cross(tr[j], tr[j + 1]);
-        cross(ti[j], ti[j + 1]);
-    }
-#endif
-#if LEAF_FFT32_DIT && LEAF_FFT_FUSE_TWIDDLE
     // The half-wave twiddle fused into the first decimation-in-time stage of the 32-point transform over j: that stage
     // pairs registers (j, j + 16) with unit twiddles, so with a = t[j] w[j] and b = t[j + 16] w[j + 16]
     //     out[j] = a + b = a + w_b t_b  (four FMAs on top of a),   out[j + 16] = a - b = 2 a - out[j]  (two FMAs):
@@ -537,164 +371,7 @@ __device__ __forceinline__ void fft2048w(float (&re)[32], float (&im)[32], float
     fft32_dit_stage<4>(re, im);
     fft32_dit_stage<8>(re, im);
     fft32_dit_stage<16>(re, im);                         // register i <-> k' = brev5(i): element 64 k' + lane
-#else
-    lds_stream32(lds_addr(twh + 32 * h), OffTwh{}, [&](int j, v2f w) {
-        if (j == 0) {
-            re[j] = tr[j];
-            im[j] = ti[j];
-        } else {
-            re[j] = tr[j] * w.x - ti[j] * w.y;
-            im[j] = tr[j] * w.y + ti[j] * w.x;
-        }
-    });
-    fft32_dif(re, im);                                   // register i <-> k' = brev5(i): element 64 k' + lane
-#endif
 }
-
-// ---- packed front half (LEAF_WG_PK, round 4 experiment -> see DESIGN.md section 9) -------------------------------------------
-// At three waves per SIMD the scarce resource is VALU issue slots, and a packed fp32 instruction spends one slot on two flops per
-// lane (tools/ubench_valu.hip: the 32-point transform on complex register pairs takes 942 SIMD cycles against 1 160 in scalar
-// form).  Everything of a filter task BEFORE the LDS transposition can run on complex pairs without a single shuffle, because
-// those values are computed into registers of our choosing: the spectral multiply (its operands arrive from LDS as (re, im)
-// pairs already), the first 32-point transform and the first-level twiddle products.  op_sel picks the halves of each source
-// (swapped operands), neg_lo / neg_hi flip signs: a complex product is two packed instructions, a twiddled butterfly three.
-// After the transposition the data comes back plane by plane (ds_read_b128 into consecutive registers) and stays scalar.
-__device__ __forceinline__ void pk_add(v2f& d, const v2f& a, const v2f& b) { asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); }
-__device__ __forceinline__ void pk_sub(v2f& d, const v2f& a, const v2f& b) {
-    asm volatile("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-}
-// a + (-i) b = (a.x + b.y, a.y - b.x);  a - (-i) b = (a.x - b.y, a.y + b.x)
-__device__ __forceinline__ void pk_add_mib(v2f& d, const v2f& a, const v2f& b) {
-    asm volatile("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void pk_sub_mib(v2f& d, const v2f& a, const v2f& b) {
-    asm volatile("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-}
-// the DIT butterfly a' = a + w b, b' = 2 a - a' with w = C + i S held as the register pair (C, S):
-//   ROT = false: w = (C, S);   ROT = true: w = -i (C, S) = (S, -C)  (W_32^(8 + k) from the pair of W_32^k)
-template <bool ROT>
-__device__ __forceinline__ void pk_bfly(v2f& a, v2f& b, const v2f& w, const v2f& two) {
-    v2f t;
-    if constexpr (!ROT) {
-        asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(t) : "v"(b), "v"(w), "v"(a));             // a + b (C, C)
-        asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" : "+v"(t) : "v"(b), "v"(w));      // + (b.y, b.x) (-S, S)
-    } else {
-        asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(t) : "v"(b), "v"(w), "v"(a));             // a + b (S, S)
-        asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[0,0,1] neg_hi:[0,1,0]" : "+v"(t) : "v"(b), "v"(w));      // + (b.y, b.x) (C, -C)
-    }
-    asm volatile("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[0,0,1] neg_hi:[0,0,1]" : "=v"(b) : "v"(two), "v"(a), "v"(t));                   // 2 a - a'
-    a = t;
-}
-// one decimation-in-time stage of the 32-point transform on complex pairs (the register conventions of fft32_dit_stage)
-template <int HALF>
-__device__ __forceinline__ void pk_dit_stage(v2f (&z)[32], const v2f (&W)[8], const v2f& two) {
-#pragma unroll
-    for (int blk = 0; blk < 32; blk += 2 * HALF) {
-#pragma unroll
-        for (int j = 0; j < HALF; ++j) {
-            const int a = brev5(blk + j), b = brev5(blk + j + HALF);
-            constexpr int STEP = 16 / HALF;
-            const int tw = j * STEP;                                        // w = W_32^tw
-            if (tw == 0) {
-                v2f s0;
-                pk_add(s0, z[a], z[b]);
-                pk_sub(z[b], z[a], z[b]);
-                z[a] = s0;
-            } else if (tw == 8) {
-                v2f s0;
-                pk_add_mib(s0, z[a], z[b]);
-                pk_sub_mib(z[b], z[a], z[b]);
-                z[a] = s0;
-            } else if (tw < 8) {
-                pk_bfly<false>(z[a], z[b], W[tw], two);
-            } else {
-                pk_bfly<true>(z[a], z[b], W[tw - 8], two);
-            }
-        }
-    }
-}
-// the twiddle constants of the 32-point transform as register pairs: W[k] = (cos, -sin)(2 pi k / 32), k = 1..7 (W[0] unused)
-__device__ __forceinline__ void pk_twiddle_pairs(v2f (&W)[8], v2f& two) {
-    constexpr float C[8] = {1.0f, 0.98078528f, 0.923879533f, 0.831469612f, 0.707106781f, 0.555570233f, 0.382683432f, 0.195090322f};
-    constexpr float S[8] = {0.0f, -0.195090322f, -0.382683432f, -0.555570233f, -0.707106781f, -0.831469612f, -0.923879533f, -0.98078528f};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        W[k] = v2f{C[k], S[k]};
-        asm volatile("" : "+v"(W[k]));                                    // live in registers, not re-materialised literal by literal
-    }
-    two = v2f{2.0f, 2.0f};
-    asm volatile("" : "+v"(two));
-}
-// scr[brev5(i) * 68 + lane] = z[i].x (COMP = 0) or .y (COMP = 1): wg_transpose_store on one component of the pairs
-template <int COMP>
-__device__ __forceinline__ void wg_transpose_store_pk(const v2f (&z)[32], unsigned scr_lds) {
-    float v[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) v[i] = COMP ? z[i].y : z[i].x;            // sub-register views: no instruction
-    wg_transpose_store(v, scr_lds);
-}
-// fft2048w<false, SKIP1 = true> with the front half on complex pairs: z holds the output of the fused first stage
-__device__ __forceinline__ void fft2048w_pkfront(v2f (&z)[32], float (&re)[32], float (&im)[32], float* scr, unsigned scr_lds,
-                                                 const float2* twl, const float2* twh, int lane, const v2f (&W)[8], const v2f& two) {
-    pk_dit_stage<2>(z, W, two);
-    pk_dit_stage<4>(z, W, two);
-    pk_dit_stage<8>(z, W, two);
-    pk_dit_stage<16>(z, W, two);                                          // register i <-> k1 = brev5(i), lane = n2
-    lds_stream32(lds_addr(twl + lane), OffTwl{}, [&](int i, v2f w) {
-        if (i == 0) return;                                               // W^0 = 1
-        v2f t;
-        asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(t) : "v"(z[i]), "v"(w));                         // z (w.x, w.x)
-        asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[0,1,0]" : "+v"(t) : "v"(z[i]), "v"(w)); // + (z.y, z.x) (-w.y, w.y)
-        z[i] = t;
-    });
-    const int k1r = lane & 31, h = lane >> 5;
-    float tr[32], ti[32];
-    const float sg = h ? -1.0f : 1.0f;
-    const f32x4* lo = reinterpret_cast<const f32x4*>(scr + k1r * kWgScrStride);
-    auto plane = [&](auto comp, float (&t)[32]) {
-        wg_transpose_store_pk<decltype(comp)::value>(z, scr_lds);
-#pragma unroll
-        for (int q0 = 0; q0 < 8; q0 += 4) {
-#pragma unroll
-            for (int q = q0; q < q0 + 4; ++q) {
-                const f32x4 a = lo[q], b = lo[q + 8];
-                t[4 * q] = fmaf(b.x, sg, a.x); t[4 * q + 1] = fmaf(b.y, sg, a.y);
-                t[4 * q + 2] = fmaf(b.z, sg, a.z); t[4 * q + 3] = fmaf(b.w, sg, a.w);
-            }
-            asm volatile("" ::: "memory");
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < 32; ++i) asm volatile("" : "+v"(z[i]));          // the twiddle products are complete before the first store
-    plane(std::integral_constant<int, 0>{}, tr);
-    pin32(tr);
-    plane(std::integral_constant<int, 1>{}, ti);
-    pin32(ti);
-    lds_stream16q(lds_addr(twh + 32 * h), [&](int j, f32x4 w) {             // the fused half-wave twiddle + first stage of fft2048w
-        float ar, ai;
-        if (j == 0) {
-            ar = tr[0];
-            ai = ti[0];
-        } else {
-            ar = tr[j] * w.x - ti[j] * w.y;
-            ai = tr[j] * w.y + ti[j] * w.x;
-        }
-        const float br = tr[j + 16], bi = ti[j + 16];
-        const float pr = fmaf(-bi, w.w, fmaf(br, w.z, ar));
-        const float pi = fmaf(bi, w.z, fmaf(br, w.w, ai));
-        re[j] = pr;
-        im[j] = pi;
-        re[j + 16] = fmaf(2.0f, ar, -pr);
-        im[j + 16] = fmaf(2.0f, ai, -pi);
-    });
-    fft32_dit_stage<2>(re, im);
-    fft32_dit_stage<4>(re, im);
-    fft32_dit_stage<8>(re, im);
-    fft32_dit_stage<16>(re, im);
-}
-#ifndef LEAF_WG_PK
-#define LEAF_WG_PK 0               // 1: the static forward kernels run the front half of a filter task on packed complex pairs (A/B)
-#endif
 
 // Task ids over a DENSE grid of F + 1 slots per set: task 0 = fwd(0); task 1 + i (F + 1) + r = slot r of set i, slot 0 being
 // fwd(i + 1) and slots 1..F the set's filters.  u / (F + 1) by multiply-high with M = ceil(2^32 / (F + 1)) -- exact while
@@ -721,15 +398,11 @@ __device__ __forceinline__ void wg_task_decode(const WgTaskGrid& g, int t, int& 
     if (role == 0) set += 1;                                              // the NEXT set's spectrum, ahead of this set's filters
 }
 
-// floats of dynamic LDS for NW waves and a static pooling row of GU floats
-constexpr int fft_wg_row_floats(int SK) { return (kGPad + SK + 63 + 3) / 4 * 4; }
+// floats of dynamic LDS for NW waves
 constexpr int fft_wg_scr_floats(int NW) { return NW > 12 ? kWgScrHalfFloats : kWgScrFloats; }   // > 12 waves: half buffer
-#ifndef LEAF_WG_REGW
-#define LEAF_WG_REGW 1             // static forward kernels: pooling weights in registers (0: round 2's wave-private LDS row, A/B)
-#endif
 constexpr size_t fft_wg_lds_bytes(int NW, int SK) {
     return ((size_t)kTwFloats + 2 * 2 * kWgRingFwdFloat2 + kWgQueueInts +
-            (size_t)NW * (fft_wg_scr_floats(NW) + (LEAF_WG_REGW ? 0 : fft_wg_row_floats(SK)))) * 4;
+            (size_t)NW * fft_wg_scr_floats(NW)) * 4;
 }
 // Static pooling with the weights in REGISTERS.  A 64-sample row r of |y|^2 meets frame fi's window at window index
 // j0 + lane with j0 = 64 r - is(fi), is(fi) = (DMIN + fi) hop - padL: every j0 is congruent to padL modulo g = gcd(64, hop),
@@ -745,12 +418,6 @@ constexpr int wg_pool_jmin(int SK, int SHOP) {       // smallest j0 >= -63 congr
 }
 constexpr int wg_pool_nj(int SK, int SHOP) { return (SK - 1 - wg_pool_jmin(SK, SHOP)) / wg_pool_step(SHOP) + 1; }
 
-#ifndef LEAF_WG_TAIL
-#define LEAF_WG_TAIL 1             // 0: no clip-resident finalize code in the kernel (A/B; the host must then not set fin_fused)
-#endif
-#ifndef LEAF_WG_STRIDED
-#define LEAF_WG_STRIDED 0          // 1: blocks dealt by striding (round 2) instead of contiguously (A/B)
-#endif
 // ---- streaming finalize (STREAM = true) -------------------------------------------------------------------------------
 // When the dealing gives every workgroup whole clips, the per-frame partial sums never leave the CU: an inverse task drops
 // its (at most NFR) frame sums into a small LDS ring, fr[frame mod RING][filter] (ONE accumulator per frame and filter since
@@ -802,12 +469,6 @@ constexpr int kWgOutRow = 2 * kWgOutChunk + 1;
 // 0.2390 -> 0.2073 ms, same box (profiles/r05/ab_stream_finalize.txt; now ahead of the partial-sum path it replaces).  Also
 // measured there: five frames interleaved instead of four (nothing) and every filter task finalizing its own row with lane =
 // frame (8-10 % slower: bookkeeping on every task, a point function per 30 frames of one filter instead of per 400 of forty).
-#ifndef LEAF_WG_SPEC0
-#define LEAF_WG_SPEC0 1            // the workgroups' first-block spectra come from the table launch (0: every forward transform in the kernel, A/B)
-#endif
-#ifndef LEAF_STREAM_PRIO
-#define LEAF_STREAM_PRIO 1         // the finalizing wave raises its issue priority (s_setprio 3) for the duration (0: A/B)
-#endif
 constexpr size_t fft_wg_stream_lds_bytes(int NW, int SK, int ring, int F) {      // + frame ring, EMA state, per-filter coefficients, output staging
     return fft_wg_lds_bytes(NW, SK) + ((size_t)ring * wg_stream_fp(F) + wg_stream_fp(F) + 8 * (size_t)F + 8 +
                                        (size_t)F * kWgOutRow) * 4;
@@ -822,17 +483,14 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
     float2* twh = twl + 32 * 64;                                          // [32][2]
     float2* ring = twh + 64;                                              // [2][kWgRingFwdFloat2]
     int* q = reinterpret_cast<int*>(ring + 2 * kWgRingFwdFloat2);         // q_next | fwd_cnt[2] | inv_cnt[2]
-    constexpr int GU = LEAF_WG_REGW ? 0 : fft_wg_row_floats(SK);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane0 = tid & 63;
-    float* scr = reinterpret_cast<float*>(q + kWgQueueInts) + (size_t)wave * (SCRF + GU);
-    float* sG = scr + SCRF;
-    (void)sG;
+    float* scr = reinterpret_cast<float*>(q + kWgQueueInts) + (size_t)wave * SCRF;
     // STREAM: frame ring [RING][FPS] (one accumulator per frame and filter: the blocks a window meets ADD their sums, the
     // finalize reads it and puts the zero back) and the EMA state [FPS] behind the waves' scratch
     const int RING = p.stream_ring;                                       // power of two (host: fft_forward)
     const int FPS = wg_stream_fp(p.F);
-    float* fr = reinterpret_cast<float*>(q + kWgQueueInts) + (size_t)NW * (SCRF + GU);
+    float* fr = reinterpret_cast<float*>(q + kWgQueueInts) + (size_t)NW * SCRF;
     float* ema_st = fr + (size_t)RING * FPS;
     FinCoef* coefT = reinterpret_cast<FinCoef*>(ema_st + FPS);             // [F]: the filters' finalize coefficients, once per launch
     static_assert(sizeof(FinCoef) == 32, "8 floats per filter");
@@ -843,13 +501,12 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
     // waves' scratch -- every workgroup gets whole clips and they fit (cfg1: one clip, 40 x 100 x 4 B = 16 KB).  The two
     // blocks a window meets add their sums with ds_add_f32 (a + b either way round: the rounding of `part`'s slot 0 + slot 1),
     // the tail reads them from LDS: no partial sums in HBM for these clips.
-    float* lsum = reinterpret_cast<float*>(q + kWgQueueInts) + (size_t)NW * (SCRF + GU);
+    float* lsum = reinterpret_cast<float*>(q + kWgQueueInts) + (size_t)NW * SCRF;
     const bool lds_sums = !STREAM && p.fin_fused == 3;
     const unsigned scr_lds = __builtin_amdgcn_readfirstlane(
         (unsigned)(size_t)(__attribute__((address_space(3))) float*)scr);   // LDS byte address of this wave's scr
     // band-limited filter tasks (leaf_band.hpp): the plan sits behind everything else
-    constexpr bool BANDK = !HALF && band_geometry_ok(SK, SHOP) && LEAF_WG_REGW && LEAF_FFT32_DIT && LEAF_FFT_FUSE_TWIDDLE && !LEAF_WG_PK &&
-                           !LEAF_FFT_TWL_PAIRS;
+    constexpr bool BANDK = !HALF && band_geometry_ok(SK, SHOP);
     const bool band_on = BANDK && p.band.rec != nullptr;
     int* bl = reinterpret_cast<int*>(wsm + p.band.lds_off);
     (void)bl;
@@ -860,7 +517,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
     // The workgroup's first block: its spectrum was computed by the table launch on otherwise idle waves (p.spec0; this transform is
     // the one task nothing here could overlap with: eleven waves waited ~12 k cycles for it).  Wave 1 requests it before the tables
     // are built and publishes it right after the barrier; the task queue then starts behind fwd(0).
-    const bool spec_pre = LEAF_WG_SPEC0 && p.spec0 != nullptr && !HALF && !LEAF_WG_STRIDED && p.B * p.nblk > 0;
+    const bool spec_pre = p.spec0 != nullptr && !HALF && p.B * p.nblk > 0;
     float2 sv[kWgFwdBins / 64];                                           // bins 0..1151 (kWgFwdBins)
     if (spec_pre && wave == 1) {
         const float2* src = p.spec0 + (size_t)blockIdx.x * kWgRingFwdFloat2;
@@ -921,13 +578,8 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
         wg_release();
         if (lane0 == 0) __hip_atomic_fetch_add(&q[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
-#if LEAF_WG_STRIDED
-    const int first_gb = (int)blockIdx.x;
-    const int nset = (deal.nblocks - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-#else
     const int first_gb = deal.start((int)blockIdx.x);
     const int nset = deal.count((int)blockIdx.x);                         // blocks of this workgroup
-#endif
     const int NT = band_on ? __builtin_amdgcn_readfirstlane(bl[0]) : p.F;   // filter tasks per block
     const int* tdesc = bl + kBandPlanHead;
     const int* bmem = tdesc + p.F + 4;
@@ -946,19 +598,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
         if (role <= 0 || role > NT) return 0;
         return band_on ? __builtin_amdgcn_readfirstlane(tdesc[role - 1]) : (role - 1) << 2;
     };
-#if LEAF_WG_PK
-    static_assert(!HALF && LEAF_FFT32_DIT && LEAF_FFT_FUSE_TWIDDLE && LEAF_FFT_NOSWAP, "the packed front half is the 12-wave form of the default transform");
-    v2f rqp[16];                                                          // (R_f[64 k + lane], R_f[64 (k + 16) + lane]): the operand pairs of the fused multiply
-    auto load_real_spectrum = [&](int f, int lane) {
-        const float* src = reinterpret_cast<const float*>(p.H) + (size_t)f * kFftN + lane;
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { rqp[k].x = src[64 * k]; rqp[k].y = src[64 * (k + 16)]; }
-        asm volatile("" ::: "memory");
-    };
-    v2f pkW[8], pk_two;                                                   // twiddle constants of the 32-point transform as register pairs
-    pk_twiddle_pairs(pkW, pk_two);
-#else
     float rq[32];                                                         // R_f[64 k + lane], natural row order
     auto load_real_spectrum = [&](int f, int lane) {
         const float* src = reinterpret_cast<const float*>(p.H) + (size_t)f * kFftN + lane;
@@ -967,12 +606,11 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
         for (int k = 0; k < 32; ++k) rq[k] = src[64 * k];
         asm volatile("" ::: "memory");
     };
-#endif
     // the 32 table values the task `role` starts with: a spectrum row, or the bins of a band task's windows (row 0 as a dummy
     // when there is no filter task)
     auto prefetch_task = [&](int role, int lane) {
         const int d = desc_of(role);
-        if constexpr (BANDK && !LEAF_WG_PK) {
+        if constexpr (BANDK) {
             if ((d & 3) == 1) { band_load_spectrum<16>(rq, reinterpret_cast<const float*>(p.H), bmem[(d >> 2) + lane / band_lpf(16)], lane); return; }
             if ((d & 3) == 2) { band_load_spectrum<32>(rq, reinterpret_cast<const float*>(p.H), bmem[(d >> 2) + lane / band_lpf(32)], lane); return; }
         }
@@ -985,7 +623,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
         WG_STAMP(10);                                                     // finalize: waiting for the previous block's
         if (j > 0) wg_wait_ge(&q[11 + ((j - 1) & 1)], ((j - 1) >> 1) + 1);
         WG_STAMP(8);                                                      // finalize: start
-        if (LEAF_STREAM_PRIO) __builtin_amdgcn_s_setprio(3);               // (see the switch: the launch's one dependent chain goes first)
+        __builtin_amdgcn_s_setprio(3);                                    // (see above: the launch's one dependent chain goes first)
         const int gb = first_gb + j;
         const int b = gb / p.nblk, c = gb - b * p.nblk;
         const int gbase = ((gb - first_gb) / p.nblk) * p.TP;              // ring numbering: clip ordinal x T' + m
@@ -1074,7 +712,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
                 }
             }
         }
-        if (LEAF_STREAM_PRIO) __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_s_setprio(0);
         WG_STAMP(9);                                                      // finalize: done
         wg_release();                // ring entries read, EMA state written: block j is out
         if (lane0 == 0) __hip_atomic_fetch_add(&q[11 + (j & 1)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1096,7 +734,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
         if (role == 0) {
             // ---- forward transform of block gb into ring slot `slot` (skipped past the last set)
             if (set < nset) {
-                const int gb = first_gb + set * (LEAF_WG_STRIDED ? (int)gridDim.x : 1);
+                const int gb = first_gb + set;
                 const int b = gb / p.nblk, c = gb - b * p.nblk;               // the only division per block
                 const int n_c = c * LS;
                 float are[32], aim[32];
@@ -1224,9 +862,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
         // Z = conj(A' R_f): rows 0..15 straight from the ring, rows 16..31 mirrored (A'[N - e] = conj(A'[e]))
         // (8-row chunks, fenced: all 32 ring reads in flight at once would need 64 registers next to rq and Z)
         float zre[32], zim[32];
-#if LEAF_WG_PK
-        v2f zc[32];                                                       // Z as complex pairs (zre / zim are filled by the transform's scalar back half)
-#endif
         {
             // two streams of 16 rows: ascending from A[lane], and the mirror A[2048 - 64 k - lane], k = 16..31, read as
             // rows 15..0 of the base A[1088 - lane] (= k = 31 first); lds_stream32 walks 2 x 16 rows
@@ -1247,26 +882,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
             v2f(&lo1)[8] = *reinterpret_cast<v2f(*)[8]>(&lo[8]);
             v2f(&hi0)[8] = *reinterpret_cast<v2f(*)[8]>(&hi[0]);
             v2f(&hi1)[8] = *reinterpret_cast<v2f(*)[8]>(&hi[8]);
-#if LEAF_WG_PK
-            // the fused multiply on complex pairs: three packed instructions per pair of rows instead of six scalar ones
-            auto pair = [&](int k) {
-                v2f t;
-                asm volatile("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0] neg_hi:[1,0]" : "=v"(t) : "v"(lo[k]), "v"(rqp[k]));   // (a.x ra, -a.y ra)
-                asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(zc[k]) : "v"(hi[k]), "v"(rqp[k]), "v"(t));
-                asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]"
-                             : "=v"(zc[k + 16]) : "v"(hi[k]), "v"(rqp[k]), "v"(t));
-            };
-            LEAF_RD8(0) LEAF_RD8(16) LEAF_RD8(8)
-            lds_wait8<8>(lo0);
-            lds_wait8<8>(hi0);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) pair(k);
-            LEAF_RD8(24)
-            lds_wait8<0>(lo1);
-            lds_wait8<0>(hi1);
-#pragma unroll
-            for (int k = 8; k < 16; ++k) pair(k);
-#elif LEAF_FFT32_DIT && LEAF_FFT_FUSE_TWIDDLE
             // the spectral multiply fused with the first decimation-in-time stage of the transform (pairs of rows (k, k + 16),
             // unit twiddles): with za = conj(A'[k]) R[k] and zb = the mirrored row's product,
             //     out[k] = za + zb,  out[k + 16] = za - zb   as one product and two FMAs per component -- 6 instructions per pair
@@ -1289,49 +904,14 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
             lds_wait8<0>(hi1);
 #pragma unroll
             for (int k = 8; k < 16; ++k) pair(k);
-#else
-            LEAF_RD8(0) LEAF_RD8(8)
-            lds_wait8<8>(lo0);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { zre[k] = lo[k].x * rq[k]; zim[k] = -(lo[k].y * rq[k]); }
-            LEAF_RD8(16)
-            lds_wait8<8>(lo1);
-#pragma unroll
-            for (int k = 8; k < 16; ++k) { zre[k] = lo[k].x * rq[k]; zim[k] = -(lo[k].y * rq[k]); }
-            LEAF_RD8(24)
-            lds_wait8<8>(hi0);
-#pragma unroll
-            for (int k = 16; k < 24; ++k) { zre[k] = hi[k - 16].x * rq[k]; zim[k] = hi[k - 16].y * rq[k]; }
-            lds_wait8<0>(hi1);
-#pragma unroll
-            for (int k = 24; k < 32; ++k) { zre[k] = hi[k - 16].x * rq[k]; zim[k] = hi[k - 16].y * rq[k]; }
-#endif
 #undef LEAF_RD8
         }
-#if LEAF_WG_PK
-        asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(zc[31]) : "memory");
-#else
         asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(zre[31]), "v"(zim[31]) : "memory");
-#endif
         wg_release();
         if (lane == 0) __hip_atomic_fetch_add(&q[3 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        // pooling row of this filter -> wave-private LDS (16 bytes per lane per instruction), lands under the transform
-        if constexpr (!LEAF_WG_REGW) {
-            const float* gsrc = p.Gz + (size_t)f * p.GZ;
-#pragma unroll
-            for (int i0 = 0; i0 < GU; i0 += 256)
-                if (i0 + 256 <= GU || i0 + 4 * lane < GU)
-                    __builtin_amdgcn_global_load_lds(gsrc + i0 + 4 * lane, (__attribute__((address_space(3))) void*)(sG + i0), 16, 0, 0);
-            asm volatile("" ::: "memory");
-        }
         WG_STAMP(4);                                                      // spectral multiply done
-#if LEAF_WG_PK
-        fft2048w_pkfront(zc, zre, zim, scr, scr_lds, twl, twh, lane, pkW, pk_two);
-#else
-        fft2048w<HALF, LEAF_FFT32_DIT && LEAF_FFT_FUSE_TWIDDLE>(zre, zim, scr, scr_lds, twl, twh, lane);   // register i <-> samples 64 brev5(i) + lane
-#endif
+        fft2048w<HALF, true>(zre, zim, scr, scr_lds, twl, twh, lane);   // register i <-> samples 64 brev5(i) + lane
         WG_STAMP(5);                                                      // inverse transform done
-#if LEAF_WG_REGW
         // the filter's pooling weights, NJ vectors (see wg_pool_nj): requested now, consumed after the energies
         constexpr int PG = wg_pool_step(SHOP), PJ0 = wg_pool_jmin(SK, SHOP), NJ = wg_pool_nj(SK, SHOP);
         float pw[NJ];
@@ -1342,7 +922,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
             for (int k = 0; k < NJ; ++k) pw[k] = gsrc[PG * k];
             asm volatile("" ::: "memory");
         }
-#endif
         float er[NROW];
 #pragma unroll
         for (int i = 0; i < 32; ++i) {
@@ -1372,12 +951,8 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
             for (int fi = 0; fi < NFR; ++fi) {
                 const int is = (DMIN + fi) * SHOP - PADL;
                 if (is <= 64 * r + 63 && is + SK > 64 * r) {
-#if LEAF_WG_REGW
                     static_assert((PADL - PJ0) % PG == 0, "window offsets are congruent to padL modulo gcd(64, hop)");
                     acc[fi / 16][fi % 16] = fmaf(er[r], pw[(64 * r - is - PJ0) / PG], acc[fi / 16][fi % 16]);
-#else
-                    acc[fi / 16][fi % 16] = fmaf(er[r], sG[kGPad + 64 * r - is + lane], acc[fi / 16][fi % 16]);
-#endif
                 }
             }
         }
@@ -1409,8 +984,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
             if (done + 1 == ((set >> 3) + 1) * NT) stream_finalize(set);
         }
         WG_STAMP(7);                                                      // pooling, reduction and stores issued
-        // the pooling's LDS reads of sG must be complete before the next task's row DMA overwrites the buffer
-        if constexpr (!LEAF_WG_REGW) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         t = tn;
         set = nset_i;
         role = nrole;
@@ -1419,7 +992,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
     // Release (the stores have reached L2) - barrier - then one wave per pair of (clip, filter) rows: bias, floor, EMA scan,
     // PCEN (fft_finalize_rows; the partial sums are read past the vector cache).  Clips that straddle two workgroups are
     // left to fft_finalize_kernel.
-    if (!STREAM && LEAF_WG_TAIL && !LEAF_WG_STRIDED && p.fin_fused) {
+    if (!STREAM && p.fin_fused) {
         const int b_lo = (first_gb + p.nblk - 1) / p.nblk, b_hi = (first_gb + nset) / p.nblk;
         // <= 64 filters' rows per tile
         constexpr int TR = (HALF || NW < 10) ? 32 : 64;                    // (fewer waves -- A/B builds -- hold a smaller tile)

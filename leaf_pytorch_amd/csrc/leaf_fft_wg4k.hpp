@@ -32,9 +32,6 @@ constexpr int kFft4N = 4096;
 #ifndef LEAF_4K_FWD_NW
 #define LEAF_4K_FWD_NW 12              // waves of the static 4096-sample forward kernel (A/B: 11)
 #endif
-#ifndef LEAF_SWEEP_BACK
-#define LEAF_SWEEP_BACK 1              // 0: every block walks the filters 0 .. F - 1 (A/B)
-#endif
 constexpr int kWg4RingFloat2 = 2056;           // bins 0..2048 of a 4096-point spectrum, padded
 constexpr int kWg4RowFloats = 528;             // one half pooling row: 64 zeros + 401 taps + 63 zeros (as the 401/160 geometry)
 // static forward kernel (round 4): full transposition scratch per wave, no pooling rows (the weights live in registers)
@@ -43,29 +40,10 @@ constexpr size_t fft_wg4k_lds_bytes(int NW) {
 }
 // S801: the pooling backward reads the half's parity row as 13 register vectors per lane (the forward's form) instead of
 // wave-private LDS rows filled by DMA: whole backward at cfg2 5.53 -> 5.41 ms, with dL/dx 7.01 -> 6.78 ms, same box
-// (profiles/r04/ab_bwd_regw.txt).  0: the LDS rows (A/B).
-#ifndef LEAF_4K_BWD_REGW
-#define LEAF_4K_BWD_REGW 1
-#endif
-// ... which frees the rows' LDS: the parameter-gradient kernel then has room for the full transposition scratch of the forward
-// (fewer LDS store instructions per transform): 5.58 -> 5.49 ms, same box.  0: the half-size scratch (A/B).
-#ifndef LEAF_4K_BWD_FULLSCR
-#define LEAF_4K_BWD_FULLSCR 1
-#endif
-#ifndef LEAF_4K_BWD_FUSE2
-#define LEAF_4K_BWD_FUSE2 1            // S801 gradient rows in pairs (r, r + 16) with the following transform's first stage fused (-0.7 % of the cfg2 backward); 0: A/B
-#endif
-#ifndef LEAF_4K_BWD_PW2
-#define LEAF_4K_BWD_PW2 1              // a second register set, the weights times (tap - centre)^2 (d pool_w); 0: squared per use (A/B)
-#endif
-constexpr int fft_wg4k_bwd_rows(bool dx) { return LEAF_4K_BWD_REGW ? 0 : dx ? 1 : 2; }   // wave-private pooling rows in LDS
-// static BACKWARD kernel (leaf_fft_wgg4k_bwd_kernel<12, 7, true>) with the half-size transposition scratch (what it runs with
-// LEAF_4K_BWD_FULLSCR = 0; with it, the forward's fft_wg4k_lds_bytes) and, LEAF_4K_BWD_REGW = 0, the filter's two parity rows
-constexpr size_t fft_wg4k_bwd_lds_bytes(int NW) {
-    return ((size_t)kTwFloats + 2 * (32 + 64) + 2 * 2 * kWg4RingFloat2 + kWgQueueInts +
-            (size_t)NW * (kWgScrHalfFloats + fft_wg4k_bwd_rows(false) * kWg4RowFloats)) * 4;
-}
-// ... with dL/dx (leaf_fft_wgg4k_bwd_kernel<8, 7, true, true>): half-size scratch + three folded gradient spectra and their
+// (profiles/r04/ab_bwd_regw.txt) -- which frees the rows' LDS: the parameter-gradient kernel
+// (leaf_fft_wgg4k_bwd_kernel<12, 7, true>) runs with the forward's full transposition scratch, fft_wg4k_lds_bytes (fewer LDS
+// store instructions per transform: 5.58 -> 5.49 ms, same box).
+// With dL/dx (leaf_fft_wgg4k_bwd_kernel<8, 7, true, true>): half-size scratch + three folded gradient spectra and their
 // tickets.  Eight waves: two per SIMD with 256 VGPRs each -- the filter's R_lo / R_hi stay in
 // registers for the task (nine waves at 168 VGPRs measured 11 % slower: profiles/r04/ab_4k_dx.txt)
 #ifndef LEAF_4K_BWD_NW
@@ -77,9 +55,11 @@ constexpr size_t fft_wg4k_bwd_lds_bytes(int NW) {
 constexpr int kWg4BwdDxWaves = LEAF_4K_DX_NW;
 constexpr size_t fft_wg4k_bwd_dx_lds_bytes(int NW) {
     return ((size_t)kTwFloats + 2 * (32 + 64) + 2 * 2 * kWg4RingFloat2 + kWgQueueInts +
-            (size_t)NW * (kWgScrHalfFloats + fft_wg4k_bwd_rows(true) * kWg4RowFloats)) * 4 + (size_t)3 * kWg4RingFloat2 * 8 + 64;
+            (size_t)NW * kWgScrHalfFloats) * 4 + (size_t)3 * kWg4RingFloat2 * 8 + 64;
 }
 // the filter-independent twiddle table of the odd half, w^e = e^{-2 pi i e / 4096}, e < 2048 (float2), behind the pooling rows
+// (fft4k_prep_kernel still writes it and it travels in FftParams::lone, but no kernel reads it: the forward takes w^(64 k) w^lane
+// from its LDS tables, which measured 1.4 % faster at cfg2.  Dropping it changes the table launch and the workspace layout.)
 constexpr size_t kFft4WtFloats = 2 * 2048;
 // per-filter tables of the 4096-point plan (floats): (R_lo, R_hi)[2048] f2 | (D_lo, D_hi)[2048] f4   (derivative slabs: the second part
 // holds (d/dmu lo, d/dmu hi, d/dsigma lo, d/dsigma hi)[2048] in the mu slab; fft4k_prep_kernel)
@@ -352,9 +332,6 @@ __device__ __forceinline__ void wg4k_ring_chunk(v2f (&a)[8], v2f (&m)[8], unsign
                    "+v"(m[0]), "+v"(m[1]), "+v"(m[2]), "+v"(m[3]), "+v"(m[4]), "+v"(m[5]), "+v"(m[6]), "+v"(m[7]));
 }
 
-#ifndef LEAF_4K_FWD_WT
-#define LEAF_4K_FWD_WT 0               // 1: the odd half's twiddles w^e from the shared global table (32 loads per task) instead of w^(64 k) w^lane from the LDS tables: 1.4 % slower at cfg2 (A/B)
-#endif
 // A table load as  uniform base (SGPR pair) + this lane's byte offset (one VGPR, zero-extended) + a compile-time byte offset:
 // the form global_load takes without any address arithmetic in the VALU.  `voff` is what call sites make opaque to pin a group
 // of loads in place (an opaque element INDEX costs ~3 VALU instructions of 64-bit arithmetic per load; opaque 64-bit pointers
@@ -410,7 +387,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
     // pooling weights of a half in registers: the half-rate geometry is the 401 / 160 one (wg_pool_nj: 15 vectors at stride 32)
     constexpr int PG = wg_pool_step(HHOP), PJ0 = wg_pool_jmin(HK, HHOP), NJ = wg_pool_nj(HK, HHOP);
     static_assert((HPADL - PJ0) % PG == 0, "window offsets are congruent to padL modulo gcd(64, hop)");
-    const float2* Wt = reinterpret_cast<const float2*>(p.lone);           // w^e, e < 2048 (fft4k_prep_kernel; p.lone carries it here)
 
     // blocks dealt contiguously; clips all of whose blocks this workgroup ran are finalized in its tail (as leaf_fft_wg_kernel)
     const OwnedClips deal{p.B * p.nblk, (int)gridDim.x, p.nblk};
@@ -510,7 +486,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
         // ---- filter task of the block in ring slot `slot`.  Odd sets walk the tasks backwards: the per-filter tables (16 KB each
         // for this kernel; 1.3 MB at 80 filters, next to a 4 MB L2 per XCD) are swept once per block by every workgroup, and a
         // sweep that turns around re-reads the tables it used last while they are still resident instead of evicting them in order
-        const int ti = (LEAF_SWEEP_BACK && (set & 1)) ? NT - role : role - 1;
+        const int ti = (set & 1) ? NT - role : role - 1;
         const int tdsc = band_on ? __builtin_amdgcn_readfirstlane(tdesc[ti]) : ti << 2;   // class (0: one filter, two 2048-point halves; 2: band task) | index << 2
         const int f = tdsc >> 2;
         if (set != seen_set) {                                            // this wave's first filter of the block: once the
@@ -653,15 +629,9 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
                     const v2f r = tab_ld<v2f>(Rtab, 2u * vo, 512 * (4 * C4 + j));
                     rl[j] = r.x;
                     rh[j] = r.y;
-#if LEAF_4K_FWD_WT
-                    w[j] = tab_ld<v2f>(Wt, 2 * vo, 512 * (4 * C4 + j));
-#else
-                    {
-                        const float2 wk = tw4a[4 * C4 + j];               // w^(64 k + lane) = w^(64 k) w^lane, both in LDS
-                        w[j].x = wk.x * wl_odd.x - wk.y * wl_odd.y;
-                        w[j].y = wk.x * wl_odd.y + wk.y * wl_odd.x;
-                    }
-#endif
+                    const float2 wk = tw4a[4 * C4 + j];                   // w^(64 k + lane) = w^(64 k) w^lane, both in LDS
+                    w[j].x = wk.x * wl_odd.x - wk.y * wl_odd.y;
+                    w[j].y = wk.x * wl_odd.y + wk.y * wl_odd.x;
                 }
                 asm volatile("" ::: "memory");
                 v2f a[4], m[4];

@@ -21,30 +21,12 @@
 // sample in a fixed order.  No atomics on data anywhere: bit-reproducible.
 #pragma once
 #include "leaf_fft_wg.hpp"
-#ifndef LEAF_DX_PRIO
-#define LEAF_DX_PRIO 1                 // the wave whose turn it is goes first on its SIMD until it has passed the ticket on (0: A/B)
-#endif
 #include "leaf_band_bwd.hpp"
 
 // Static backward kernels: the filter's pooling weights as NJ register vectors per lane (wg_pool_nj: 13 at 401 / 160 -- the
 // forward's form since round 3) instead of a wave-private LDS row filled by DMA and ~80 ds_read_b32 per task.  Same-box A/B,
 // gradients bit-identical (profiles/r04/ab_bwd_regw.txt): whole backward 0.4657 -> 0.4466 ms at cfg1, -2.5 % with dL/dx,
-// -2.8 % at 8 kHz, -4.0 % at 512 clips.  0: the LDS row (A/B).
-#ifndef LEAF_WG_BWD_REGW
-#define LEAF_WG_BWD_REGW 1
-#endif
-#ifndef LEAF_BAND_BWD
-#define LEAF_BAND_BWD 1                // the static 401 / 160 backward (parameter gradients) runs the narrow-band filters as band tasks (leaf_band_bwd.hpp); 0: A/B
-#endif
-#ifndef LEAF_BAND_BWD_DX
-#define LEAF_BAND_BWD_DX 1             // ... and with dL/dx: the band tasks add their members' shares of the block's gradient spectrum (DXB); 0: A/B
-#endif
-#ifndef LEAF_WG_BWD_FUSE2
-#define LEAF_WG_BWD_FUSE2 (LEAF_FFT32_DIT && LEAF_FFT_FUSE_TWIDDLE)    // gy's rows in pairs (r, r + 16) with the second transform's first stage; 0: A/B
-#endif
-#ifndef LEAF_WG_BWD_PW2
-#define LEAF_WG_BWD_PW2 1              // ... and a second set, the weights times (tap - centre)^2 (d pool_w); 0: squared per use (A/B)
-#endif
+// -2.8 % at 8 kHz, -4.0 % at 512 clips.
 
 namespace {
 
@@ -160,7 +142,7 @@ __device__ __forceinline__ void wg_dx_accumulate(const FftParams& p, int f, int 
 #ifndef LEAF_DX_NOWAIT                 // measurement only (wrong sums): what the ordered turn costs
     wg_wait_ge(gticket, want);
 #endif
-    if (LEAF_DX_PRIO) __builtin_amdgcn_s_setprio(3);                      // (the turns are one dependent chain through the block)
+    __builtin_amdgcn_s_setprio(3);                                        // (the turns are one dependent chain through the block)
     // (eight reads in flight per step; sixteen measured slower: 22.05 kHz 1.93 -> 2.01 ms, 48 kHz 5.59 -> 5.97 ms with dL/dx)
     float2* s1 = gS + lane;                                               // bin 64 k + lane, k < 16
 #pragma unroll
@@ -192,7 +174,7 @@ __device__ __forceinline__ void wg_dx_accumulate(const FftParams& p, int f, int 
     }
     wg_release();
     if (lane == 0) __hip_atomic_fetch_add(const_cast<int*>(gticket), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (LEAF_DX_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 }
 // wg_dx_finish: called by the wave that added the block's last filter (filters add in order, so every other one is in).
 // X = the Hermitian spectrum whose transform is dL/da': X[k] = conj(S[k]) / 2 (0 < k < 1024), X[N - k] = S[k] / 2,
@@ -233,10 +215,7 @@ __device__ __forceinline__ void wg_dx_finish(const FftParams& p, const float2* g
 // The recomputed forward of a backward task as the forward kernel does it (leaf_fft_wg_kernel): the spectral multiply
 // Z = conj(A' R_f) fused with the first decimation-in-time stage of the transform that follows (rows (k, k + 16), unit
 // twiddles): out[k] = za + zb, out[k + 16] = za - zb as one product and two FMAs per component -- 6 instructions per pair of
-// rows instead of 4 products + 4 additions; the transform is then called with SKIP1.  0: separate multiply (A/B).
-#ifndef LEAF_WG_BWD_FUSE1
-#define LEAF_WG_BWD_FUSE1 (LEAF_FFT32_DIT && LEAF_FFT_FUSE_TWIDDLE)
-#endif
+// rows instead of 4 products + 4 additions; the transform is then called with SKIP1.
 __device__ __forceinline__ void wg_multiply_stage1(const float2* A, int lane, const float (&rq)[32], float (&zre)[32], float (&zim)[32]) {
     // two streams of 16 rows: ascending from A[lane], and the mirror A[2048 - 64 k - lane], k = 16..31, read as rows 15..0 of the
     // base A[64 - lane]: row k + 16 is hi[k]
@@ -281,11 +260,10 @@ __device__ __forceinline__ void wg_multiply_stage1(const float2* A, int lane, co
 // Returns this lane's shares of d mu, d sigma and d pool_w (before the wave sums) and, DX, adds R_f g to (acc_re, acc_im).
 template <int SK, int SHOP, int DX, bool HALF = true>
 __device__ __forceinline__ void wg_bwd_filter(const FftParams& p, const float2* A, int lane, int f, int b, int c,
-                                              const float (&rq)[32], float* scr, unsigned scr_lds, float* sG, const float2* twl,
+                                              const float (&rq)[32], float* scr, unsigned scr_lds, const float2* twl,
                                               const float2* twh, float (&acc_re)[32], float (&acc_im)[32], float& amu_out,
                                               float& asg_out, float& dpw_out, [[maybe_unused]] float2* gS = nullptr,
                                               [[maybe_unused]] const int* gticket = nullptr, [[maybe_unused]] int want = 0) {
-    constexpr int GU = fft_wg_row_floats(SK);
     constexpr int PADL = SK / 2 + SK % 2 - 1;
     constexpr int LS = fft_block_len(SK, SHOP, true);
     constexpr int DMIN = -((SK - 1 - PADL) / SHOP);
@@ -298,15 +276,7 @@ __device__ __forceinline__ void wg_bwd_filter(const FftParams& p, const float2* 
     mlo = mlo <= 0 ? 0 : (mlo + SHOP - 1) / SHOP;
     const int mhi = min(p.TP - 1, (n_c + Lv - 1 + PADL) / SHOP);
     float zre[32], zim[32];
-#if LEAF_WG_BWD_FUSE1
     wg_multiply_stage1(A, lane, rq, zre, zim);                        // Z = conj(A' R_f) and the transform's first stage
-#else
-    wg_ring_rows(A, lane, [&](int k, float ar, float ai) {           // Z = conj(A' R_f), natural row order
-        zre[k] = ar * rq[k];
-        zim[k] = -(ai * rq[k]);
-    });
-#endif
-#if LEAF_WG_BWD_REGW
     constexpr int PG = wg_pool_step(SHOP), PJ0 = wg_pool_jmin(SK, SHOP), NJ = wg_pool_nj(SK, SHOP);
     float pw[NJ];
     {
@@ -316,18 +286,7 @@ __device__ __forceinline__ void wg_bwd_filter(const FftParams& p, const float2* 
         for (int k = 0; k < NJ; ++k) pw[k] = gsrc[PG * k];
         asm volatile("" ::: "memory");
     }
-    (void)sG; (void)GU;
-#else
-    {   // pooling row of this filter -> wave-private LDS, lands under the transform
-        const float* gsrc = p.Gz + (size_t)f * p.GZ;
-#pragma unroll
-        for (int i0 = 0; i0 < GU; i0 += 256)
-            if (i0 + 256 <= GU || i0 + 4 * lane < GU)
-                __builtin_amdgcn_global_load_lds(gsrc + i0 + 4 * lane, (__attribute__((address_space(3))) void*)(sG + i0), 16, 0, 0);
-        asm volatile("" ::: "memory");
-    }
-#endif
-    fft2048w<HALF, LEAF_WG_BWD_FUSE1 != 0>(zre, zim, scr, scr_lds, twl, twh, lane);   // u = conj(y): register i <-> samples 64 brev5(i) + lane
+    fft2048w<HALF, true>(zre, zim, scr, scr_lds, twl, twh, lane);   // u = conj(y): register i <-> samples 64 brev5(i) + lane
     pin32(zre);
     pin32(zim);
     // g_pre of the NFR frames this block meets, as wave-uniform scalars
@@ -342,7 +301,6 @@ __device__ __forceinline__ void wg_bwd_filter(const FftParams& p, const float2* 
     constexpr float HALFW = 0.5f * (float)(SK - 1);
     const float lanef = (float)lane;
     float dpw = 0.0f;
-#if LEAF_WG_BWD_REGW && LEAF_WG_BWD_PW2
     // the weights times (window position - centre)^2, position = PJ0 + PG k + lane: d pool_w needs sum g (j - c)^2 e, and a
     // second weight vector per offset turns five instructions per (row, frame) into two FMAs
     float pw2[NJ];
@@ -351,9 +309,7 @@ __device__ __forceinline__ void wg_bwd_filter(const FftParams& p, const float2* 
         const float tj = (float)(PJ0 + PG * k) - HALFW + lanef;
         pw2[k] = pw[k] * (tj * tj);
     }
-#endif
     float vre[32], vim[32];                                           // gy = 2 de y, natural row order
-#if LEAF_WG_BWD_REGW && LEAF_WG_BWD_PW2 && LEAF_WG_BWD_FUSE2
     // rows r and r + 16 together, and with them the first decimation-in-time stage of the transform that follows (unit twiddles):
     // out[r] = gy[r] + gy[r + 16], out[r + 16] = gy[r] - gy[r + 16] as one product and two FMAs per component; rows past the
     // block's outputs (r + 16 >= NROW) are zero, so both outputs are gy[r]
@@ -403,53 +359,8 @@ __device__ __forceinline__ void wg_bwd_filter(const FftParams& p, const float2* 
     asm volatile("" : "+v"(vre[B0 + 3]), "+v"(vim[B0 + 3]), "+v"(vre[B0 + 19]), "+v"(vim[B0 + 19]), "+v"(dpw));   /* groups stay in program order */
     LEAF_ROW4(0) LEAF_ROW4(4) LEAF_ROW4(8) LEAF_ROW4(12)
 #undef LEAF_ROW4
-    constexpr bool kSkip1 = true;
-#else
-    constexpr bool kSkip1 = false;
-    int gofs = kGPad + lane;                                          // made opaque per row: keeps the rows in program order
-#pragma unroll
-    for (int r = 0; r < 32; ++r) {
-        const int i = brev5(r);                                       // register holding row r of u
-        if (r < NROW) {
-            const float ur = zre[i], ui = zim[i];
-            const bool ok = 64 * r + lane < Lv;
-            float de = 0.0f, dq = 0.0f;
-            if (r % 4 == 0) asm volatile("" : "+v"(gofs));            // groups of four rows stay in program order
-#pragma unroll
-            for (int fi = 0; fi < NFR; ++fi) {
-                const int is = (DMIN + fi) * SHOP - PADL;
-                if (is <= 64 * r + 63 && is + SK > 64 * r) {
-#if LEAF_WG_BWD_REGW
-#if LEAF_WG_BWD_PW2
-                    de = fmaf(gp[fi], pw[(64 * r - is - PJ0) / PG], de);          // zero outside the window
-                    dq = fmaf(gp[fi], pw2[(64 * r - is - PJ0) / PG], dq);         // the same weight times (window position - centre)^2
-#else
-                    const float gw = gp[fi] * pw[(64 * r - is - PJ0) / PG];      // zero outside the window
-                    const float tj = (float)(64 * r - is) - HALFW + lanef;        // window position - centre
-                    de += gw;
-                    dq = fmaf(gw, tj * tj, dq);
-#endif
-#else
-                    const float gw = gp[fi] * sG[gofs + 64 * r - is];             // zero outside the window
-                    const float tj = (float)(64 * r - is) - HALFW + lanef;        // window position - centre
-                    de += gw;
-                    dq = fmaf(gw, tj * tj, dq);
-#endif
-                }
-            }
-            const float e = ok ? ur * ur + ui * ui : 0.0f;
-            dpw = fmaf(e, dq, dpw);
-            const float s2 = ok ? 2.0f * de : 0.0f;
-            vre[r] = s2 * ur;
-            vim[r] = -(s2 * ui);
-            if (r % 4 == 3) asm volatile("" : "+v"(vre[r]), "+v"(vim[r]), "+v"(dpw));
-        } else {
-            vre[r] = vim[r] = 0.0f;                                   // circular wrap-around outputs: no gradient
-        }
-    }
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // pooling-row reads done before the next task's DMA
-    fft2048w<HALF, kSkip1>(vre, vim, scr, scr_lds, twl, twh, lane);  // g = dL/dS: register i <-> bin 64 brev5(i) + lane
+    fft2048w<HALF, true>(vre, vim, scr, scr_lds, twl, twh, lane);    // g = dL/dS: register i <-> bin 64 brev5(i) + lane
     pin32(vre);
     pin32(vim);
     float amu = 0.0f, asg = 0.0f;
@@ -460,11 +371,10 @@ __device__ __forceinline__ void wg_bwd_filter(const FftParams& p, const float2* 
     dpw_out = dpw * (1.0f / (HALFW * HALFW));
 }
 
-// the full transposition scratch (fewer LDS store instructions: leaf_fft_wg.hpp) where twelve waves of it fit beside the
-// pooling rows -- K = 401 and 201 -- else the half-size column form
-constexpr int fft_wg_bwd_row_floats(int SK) { return LEAF_WG_BWD_REGW ? 0 : fft_wg_row_floats(SK); }   // the wave-private pooling row, if any
+// the full transposition scratch (fewer LDS store instructions: leaf_fft_wg.hpp) where the waves' copies of it fit, else the
+// half-size column form
 constexpr size_t fft_wg_bwd_lds_bytes_with(int NW, int SK, int scr_floats) {
-    return ((size_t)kTwFloats + 2 * 2 * kWgRingFloat2 + kWgQueueInts + (size_t)NW * (scr_floats + fft_wg_bwd_row_floats(SK))) * 4;
+    return ((size_t)kTwFloats + 2 * 2 * kWgRingFloat2 + kWgQueueInts + (size_t)NW * scr_floats) * 4;
 }
 constexpr bool fft_wg_bwd_half(int NW, int SK) { return fft_wg_bwd_lds_bytes_with(NW, SK, kWgScrFloats) > (size_t)kMaxLds; }
 constexpr size_t fft_wg_bwd_lds_bytes(int NW, int SK) {
@@ -472,18 +382,15 @@ constexpr size_t fft_wg_bwd_lds_bytes(int NW, int SK) {
 }
 constexpr int kBlkBwdWaves = 8;                  // leaf_fft_blk_bwd_dx_kernel: two waves per SIMD, 256 VGPRs each
 constexpr size_t fft_blk_bwd_lds_bytes(int SK) {
-    return ((size_t)kTwFloats + (size_t)kBlkBwdWaves * (2 * kWgRingFloat2 + kWgScrHalfFloats + fft_wg_bwd_row_floats(SK))) * 4;
+    return ((size_t)kTwFloats + (size_t)kBlkBwdWaves * (2 * kWgRingFloat2 + kWgScrHalfFloats)) * 4;
 }
 
 // FftParams fields used beyond the forward's: H = [3][F][2048] real spectra (R | R_mu | R_sigma), gpre, pool_w, dkpart,
 // dwpart.
 // DX = true: the kernel also yields dL/dx -- G per block in LDS (wg_dx_accumulate / wg_dx_finish above), the block's 2048
 // input-gradient samples into part[block][2048]; the transposition scratch is full-size where it fits beside G.
-#ifndef LEAF_WG_BWD_DX_FULLSCR
-#define LEAF_WG_BWD_DX_FULLSCR 1       // with the pooling rows gone (LEAF_WG_BWD_REGW) the full scratch fits beside G too; 0: half-size (A/B)
-#endif
 constexpr bool fft_wg_bwd_dx_half(int NW, int SK) {
-    return !LEAF_WG_BWD_DX_FULLSCR || fft_wg_bwd_lds_bytes_with(NW, SK, kWgScrFloats) + (size_t)2 * kWgRingFloat2 * 8 > (size_t)kMaxLds;
+    return fft_wg_bwd_lds_bytes_with(NW, SK, kWgScrFloats) + (size_t)2 * kWgRingFloat2 * 8 > (size_t)kMaxLds;
 }
 constexpr size_t fft_wg_bwd_dx_lds_bytes(int NW, int SK) {
     return fft_wg_bwd_lds_bytes_with(NW, SK, fft_wg_bwd_dx_half(NW, SK) ? kWgScrHalfFloats : kWgScrFloats) + (size_t)2 * kWgRingFloat2 * 8;
@@ -502,15 +409,13 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
     int* q = reinterpret_cast<int*>(ring + (DX ? 4 : 2) * kWgRingFloat2);
     // q: 0 next task | 1,2 spectra stored per slot | 3,4 inverse tasks finished per slot | 5..8 (clip, block) per slot |
     //    9,10 generations released per slot (all readers done) | 11,12 (DX) filters added to the slot's G, ever
-    constexpr int GU = fft_wg_bwd_row_floats(SK);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane0 = tid & 63;
-    float* scr = reinterpret_cast<float*>(q + kWgQueueInts) + (size_t)wave * (SCRF + GU);
-    float* sG = scr + SCRF;
+    float* scr = reinterpret_cast<float*>(q + kWgQueueInts) + (size_t)wave * SCRF;
     const unsigned scr_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) float*)scr);
 
     // band-limited filter tasks (leaf_band_bwd.hpp; parameter gradients only): the plan sits behind the waves' scratch
-    constexpr bool BANDK = !HALF && (!DX || LEAF_BAND_BWD_DX) && band_geometry_ok(SK, SHOP) && LEAF_WG_BWD_REGW;   // (DX: the members' shares of the block's G in the task's turn)
+    constexpr bool BANDK = !HALF && band_geometry_ok(SK, SHOP);           // (DX: the members' shares of the block's G in the task's turn)
     const bool band_on = BANDK && p.band.rec != nullptr;
     int* bl = reinterpret_cast<int*>(wsm + p.band.lds_off);
     if constexpr (BANDK) {
@@ -690,7 +595,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
         float amu, asg, dpw;
         {
             float dummy_re[32], dummy_im[32];
-            wg_bwd_filter<SK, SHOP, DX ? 2 : 0, HALF>(p, A, lane, f, b, c, rq, scr, scr_lds, sG, twl, twh, dummy_re, dummy_im, amu, asg,
+            wg_bwd_filter<SK, SHOP, DX ? 2 : 0, HALF>(p, A, lane, f, b, c, rq, scr, scr_lds, twl, twh, dummy_re, dummy_im, amu, asg,
                                                       dpw, gsum + slot * kWgRingFloat2, &q[11 + slot], gen * NT + role - 1);
         }
         if constexpr (DX) {
@@ -732,7 +637,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
 template <int SK, int SHOP, bool BF16 = false>
 __global__ __launch_bounds__(kBlkBwdWaves * 64, 2) void leaf_fft_blk_bwd_dx_kernel(const FftParams p) {
     constexpr int SCRF = kWgScrHalfFloats;
-    constexpr int GU = fft_wg_bwd_row_floats(SK);
     constexpr int PADL = SK / 2 + SK % 2 - 1;
     constexpr int LS = fft_block_len(SK, SHOP, true);
     extern __shared__ __attribute__((aligned(16))) float wsm[];
@@ -740,10 +644,9 @@ __global__ __launch_bounds__(kBlkBwdWaves * 64, 2) void leaf_fft_blk_bwd_dx_kern
     float2* twh = twl + 32 * 64;
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane0 = tid & 63;
-    float* mine = reinterpret_cast<float*>(twh + 64) + (size_t)wave * (2 * kWgRingFloat2 + SCRF + GU);
+    float* mine = reinterpret_cast<float*>(twh + 64) + (size_t)wave * (2 * kWgRingFloat2 + SCRF);
     float2* A = reinterpret_cast<float2*>(mine);                          // this wave's block spectrum, bins 0..1024
     float* scr = mine + 2 * kWgRingFloat2;
-    float* sG = scr + SCRF;
     const unsigned scr_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) float*)scr);
     fft_build_twiddles_wg(twl, twh, tid, kBlkBwdWaves * 64);
     __syncthreads();
@@ -799,7 +702,7 @@ __global__ __launch_bounds__(kBlkBwdWaves * 64, 2) void leaf_fft_blk_bwd_dx_kern
                 asm volatile("" ::: "memory");
             }
             float amu, asg, dpw;
-            wg_bwd_filter<SK, SHOP, 1>(p, A, lane, f, b, c, rq, scr, scr_lds, sG, twl, twh, acc_re, acc_im, amu, asg, dpw);
+            wg_bwd_filter<SK, SHOP, 1>(p, A, lane, f, b, c, rq, scr, scr_lds, twl, twh, acc_re, acc_im, amu, asg, dpw);
             amu = wave_sum(amu);
             asg = wave_sum(asg);
             dpw = wave_sum(dpw);

@@ -88,14 +88,14 @@ __device__ __forceinline__ void wg4k_dx_accumulate(const float (&rlo)[32], const
 #ifndef LEAF_DX_NOWAIT                 // measurement only (wrong sums): what the ordered turn costs
     wg_wait_ge(ticket, want);                                             // the previous filter's share of this half is in
 #endif
-    if (LEAF_DX_PRIO) __builtin_amdgcn_s_setprio(3);                      // (leaf_fft_wg_bwd.hpp: the turn's holder goes first)
+    __builtin_amdgcn_s_setprio(3);                                        // (leaf_fft_wg_bwd.hpp: the turn's holder goes first)
     work(std::integral_constant<int, 0>{});
     work(std::integral_constant<int, 1>{});
     work(std::integral_constant<int, 2>{});
     work(std::integral_constant<int, 3>{});
     wg_release();
     if (lane == 0) __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (LEAF_DX_PRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 }
 // wg4k_dx_finish: called by the wave that added the block's last share (the second half of the last filter in queue order;
 // both chains add in that order, so every other share is in).  S = S0 + S1;  X = the Hermitian spectrum whose 4096-point
@@ -166,9 +166,9 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
     using gfp = const __attribute__((address_space(1))) float*;          // table pointers that stay `global` when made opaque
     using gf2p = const __attribute__((address_space(1))) v2f*;            // (a builtin vector: HIP's float2 class does not load through address spaces)
     static_assert(!DX || S801, "dL/dx on 4096-sample blocks: the static 32 kHz instance only");
-    constexpr bool FULLSCR = S801 && !DX && LEAF_4K_BWD_REGW && LEAF_4K_BWD_FULLSCR;    // full transposition scratch, no rows
+    constexpr bool FULLSCR = S801 && !DX;                                 // full transposition scratch
     constexpr bool HS = !FULLSCR;
-    constexpr int S801_WAVE_FLOATS = FULLSCR ? kWgScrFloats : kWgScrHalfFloats + fft_wg4k_bwd_rows(DX) * kWg4RowFloats;
+    constexpr int S801_WAVE_FLOATS = FULLSCR ? kWgScrFloats : kWgScrHalfFloats;
     extern __shared__ __attribute__((aligned(16))) float wsm[];
     float2* twl = reinterpret_cast<float2*>(wsm);                        // [32][64]
     float2* twh = twl + 32 * 64;                                          // [32][2]
@@ -179,12 +179,11 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
     const int PF = S801 ? 0 : fft_wgg4k_front_floats(p.K), BP = S801 ? 0 : fft_wgg4k_back_floats(p.K);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane0 = tid & 63;
-    // S801: [transposition scratch | the filter's two parity pooling rows] per wave (fft_wg4k_bwd_lds_bytes)
+    // S801: the transposition scratch per wave (fft_wg4k_lds_bytes; DX: fft_wg4k_bwd_dx_lds_bytes)
     float* wbase = reinterpret_cast<float*>(q + kWgQueueInts) +
                    (size_t)wave * (S801 ? S801_WAVE_FLOATS : PF + kFftN + BP + p.NT);   // p.NT: frame-sum floats
     float* scr = wbase + PF;                                              // energies [0, 2048); transposition scratch in its head
-    [[maybe_unused]] float* sG = scr + kWgScrHalfFloats;                 // (S801)
-    // (DX) behind the per-wave areas (transposition scratch; with LEAF_4K_BWD_REGW = 0 also one pooling row, fetched per half) the folded gradient
+    // (DX) behind the per-wave areas (transposition scratch) the folded gradient
     // spectra -- first-half shares per ring slot [0], [1], second-half shares [2] -- and their tickets (fft_wg4k_bwd_dx_lds_bytes)
     [[maybe_unused]] float2* gsum = reinterpret_cast<float2*>(reinterpret_cast<float*>(q + kWgQueueInts) +
                                                               (size_t)NW * S801_WAVE_FLOATS);
@@ -317,7 +316,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
             continue;
         }
         // ---- backward of filter f on the block in ring slot `slot` (odd sets walk the tasks backwards: leaf_fft_wg4k.hpp)
-        const int ti_ = (LEAF_SWEEP_BACK && (set & 1)) ? NT - role : role - 1;
+        const int ti_ = (set & 1) ? NT - role : role - 1;
         const int tdsc = band_on ? __builtin_amdgcn_readfirstlane(tdesc[ti_]) : ti_ << 2;   // class (0: one filter; 2: band task) | index << 2
         const int f = tdsc >> 2;
         // this filter's tables, wave-uniform bases (tab_ld: base + the lane's byte offset + an immediate):
@@ -376,17 +375,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
         constexpr int kDMin = -((kHK - 1 - kHPad) / kHHop), kDMax = (3200 / 2 - 1 + kHPad) / kHHop, kNFr = kDMax - kDMin + 1;
         [[maybe_unused]] float gp[kNFr];
         if constexpr (S801) {
-            // the filter's two parity rows -> wave-private LDS (the previous task's reads of them are complete: it ended
-            // with s_waitcnt lgkmcnt(0)); they land under the first transform
-            // (DX: one row buffer -- the first half's row now, the second's once the first half has read it: fetch_row below)
-#if !LEAF_4K_BWD_REGW
-            const float* gsrc = p.Gz + (size_t)f * 2 * kWg4RowFloats;
-            constexpr int GU2 = (DX ? 1 : 2) * kWg4RowFloats;
-#pragma unroll
-            for (int i0 = 0; i0 < GU2; i0 += 256)
-                if (i0 + 256 <= GU2 || i0 + 4 * lane < GU2)
-                    __builtin_amdgcn_global_load_lds(gsrc + i0 + 4 * lane, (__attribute__((address_space(3))) void*)(sG + i0), 16, 0, 0);
-#endif
             asm volatile("" ::: "memory");
             const int fi = lane & 31, m = n_c / SHOPr + kDMin + fi;
             const float mine = (fi < kNFr && m >= mlo && m <= mhi) ? p.gpre[((size_t)b * p.F + f) * p.TP + m] : 0.0f;
@@ -409,7 +397,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
         const lds_fp erow = (lds_fp)scr + lane;
         const lds_f4p zrow = (lds_f4p)wbase + lane;
         // pooling backward + second transform + spectral share of one half; (zre, zim) hold u_h on entry
-#if LEAF_4K_BWD_REGW
         // S801: the half's parity row as NJ register vectors, pw[k][lane] = row[PJ0 + PG k + lane]
         constexpr int PG = wg_pool_step(kHHop), PJ0 = wg_pool_jmin(kHK, kHHop), NJ = wg_pool_nj(kHK, kHHop);
         [[maybe_unused]] float pw[S801 ? NJ : 1];
@@ -422,7 +409,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
                 asm volatile("" ::: "memory");
             }
         };
-#endif
         auto half_bwd = [&](auto hh) {
             constexpr int h = decltype(hh)::value;
             pin32(zre);
@@ -431,23 +417,15 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
             if constexpr (S801) {
                 // pooling backward by register gather, row by row (64 half-rate samples each): de = sum over the frames whose
                 // window meets the row of g_pre[m] g_h[i], dq the same with (j - centre)^2, j = 2 i + h
-#if LEAF_4K_BWD_REGW
                 load_pw(h);                                               // (requesting them before the transform measured the same)
-#if LEAF_4K_BWD_PW2
                 float pw2[NJ];                                            // the weights times (full-rate tap index - centre)^2: d pool_w
 #pragma unroll
                 for (int k = 0; k < NJ; ++k) {
                     const float tj = (float)(2 * (PJ0 + PG * k) + h - 400) + 2.0f * (float)lane;
                     pw2[k] = pw[k] * (tj * tj);
                 }
-#endif
-#else
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the rows' DMA has landed (g_pre loads with it)
-                const float* sGh = sG + (DX ? 0 : h) * kWg4RowFloats;
-#endif
-#if LEAF_4K_BWD_REGW && LEAF_4K_BWD_PW2 && LEAF_4K_BWD_FUSE2
                 // rows r and r + 16 together, and with them the first decimation-in-time stage of the transform that follows
-                // (leaf_fft_wg_bwd.hpp, LEAF_WG_BWD_FUSE2): out[r] = gy[r] + gy[r + 16], out[r + 16] = gy[r] - gy[r + 16]
+                // (as wg_bwd_filter of leaf_fft_wg_bwd.hpp): out[r] = gy[r] + gy[r + 16], out[r + 16] = gy[r] - gy[r + 16]
                 auto row_grad = [&](auto rr, float& s2, float& ur, float& ui) {
                     constexpr int r = decltype(rr)::value;
                     ur = zre[brev5(r)];
@@ -493,47 +471,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
                 asm volatile("" : "+v"(vre[B0 + 3]), "+v"(vim[B0 + 3]), "+v"(vre[B0 + 19]), "+v"(vim[B0 + 19]), "+v"(qacc));
                 LEAF_ROW4(0) LEAF_ROW4(4) LEAF_ROW4(8) LEAF_ROW4(12)
 #undef LEAF_ROW4
-#else
-                const float lane2 = 2.0f * (float)lane;
-                int gofs = kGPad + lane;                                  // made opaque per row group: keeps the rows in program order
-#pragma unroll
-                for (int r = 0; r < 32; ++r) {
-                    const int i = brev5(r);                               // register holding row r of u_h
-                    if (r < kHRows) {
-                        const float ur = zre[i], ui = zim[i];
-                        const bool ok = 2 * (64 * r + lane) + h < Lv;
-                        float de = 0.0f, dq = 0.0f;
-                        if (r % 4 == 0) asm volatile("" : "+v"(gofs));
-#pragma unroll
-                        for (int fi = 0; fi < kNFr; ++fi) {
-                            const int is = (kDMin + fi) * kHHop - kHPad;  // half-rate window start relative to the block
-                            if (is <= 64 * r + 63 && is + kHK > 64 * r) {
-#if LEAF_4K_BWD_REGW && LEAF_4K_BWD_PW2
-                                de = fmaf(gp[fi], pw[(64 * r - is - PJ0) / PG], de);       // zero outside the window
-                                dq = fmaf(gp[fi], pw2[(64 * r - is - PJ0) / PG], dq);      // the same weight times (tap - centre)^2
-#else
-#if LEAF_4K_BWD_REGW
-                                const float gw = gp[fi] * pw[(64 * r - is - PJ0) / PG];    // zero outside the window
-#else
-                                const float gw = gp[fi] * sGh[gofs + 64 * r - is];           // zero outside the window
-#endif
-                                const float tj = (float)(2 * (64 * r - is) + h - 400) + lane2;   // full-rate tap index - centre
-                                de += gw;
-                                dq = fmaf(gw, tj * tj, dq);
-#endif
-                            }
-                        }
-                        const float e = ok ? ur * ur + ui * ui : 0.0f;
-                        qacc = fmaf(e, dq, qacc);
-                        const float s2 = ok ? 2.0f * de : 0.0f;
-                        vre[r] = s2 * ur;
-                        vim[r] = -(s2 * ui);
-                        if (r % 4 == 3) asm volatile("" : "+v"(vre[r]), "+v"(vim[r]), "+v"(qacc));
-                    } else {
-                        vre[r] = vim[r] = 0.0f;                           // beyond the block's 3200 samples: no gradient
-                    }
-                }
-#endif
             } else {
             // |y|^2 -> the row; the paddings are cleared too (the previous scatter ran into them)
             for (int i0 = 0; i0 < PF; i0 += 256)
@@ -626,16 +563,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
             }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // the row's reads are done before the transform's scratch writes
-            if constexpr (S801 && DX && h == 0 && !LEAF_4K_BWD_REGW) {
-                // the second half's parity row into the same buffer: it lands under the transform below
-                const float* gsrc1 = p.Gz + ((size_t)f * 2 + 1) * kWg4RowFloats;
-#pragma unroll
-                for (int i0 = 0; i0 < kWg4RowFloats; i0 += 256)
-                    if (i0 + 256 <= kWg4RowFloats || i0 + 4 * lane < kWg4RowFloats)
-                        __builtin_amdgcn_global_load_lds(gsrc1 + i0 + 4 * lane, (__attribute__((address_space(3))) void*)(sG + i0), 16, 0, 0);
-                asm volatile("" ::: "memory");
-            }
-            fft2048w<HS, S801 && LEAF_4K_BWD_REGW && LEAF_4K_BWD_PW2 && LEAF_4K_BWD_FUSE2>(vre, vim, scr, scr_lds, twl, twh, lane);   // V_h: register brev5(k) <-> bin 64 k + lane
+            fft2048w<HS, S801>(vre, vim, scr, scr_lds, twl, twh, lane);   // V_h: register brev5(k) <-> bin 64 k + lane
             pin32(vre);
             pin32(vim);
             // (d) this half's share of the spectral dot products

@@ -356,7 +356,7 @@ __global__ __launch_bounds__(kWavesPerWG * 64, kWavesPerWG / 4) void leaf_fused_
                 fused_ksegment<RT, RT - 2, EVENK>(acc_re, acc_im, xf, xb_, sW, offE, offO, g, p.Hf, ks, ks_t[RT - 3]);
             __builtin_amdgcn_s_setprio(0);
             LEAF_STAMP();                              // k-loop end
-            if (LEAF_DMA_PREFETCH && u == p.NU - 1 && !p.io_bf16 && !(kAblate & 2)) {
+            if (u == p.NU - 1 && !p.io_bf16 && !(kAblate & 2)) {
                 // This task no longer reads its waveform window: stream the NEXT task's window into the same LDS
                 // region with direct-to-LDS loads (no registers), overlapped with this unit's epilogue.  Only for
                 // windows that lie entirely inside the clip (edge windows need zero fill -> staged normally).

@@ -299,9 +299,6 @@ BwdLayout bwd_layout(const FusedPlan& pl, const BwdPlan& bp, int B, int T, int F
     return L;
 }
 
-#ifndef LEAF_FFT_FORCE_GENERIC
-#define LEAF_FFT_FORCE_GENERIC 0       // measurement only: run the static geometries through the generic-pooling instance
-#endif
 // ---- FFT (overlap-save) forward plan
 struct FftPlan {
     bool ok;
@@ -362,7 +359,7 @@ FftPlan make_fft_plan(const Shape& s, int cus) {
     if (K < 2 || K > 64 * kPoolRowsMax - 63) return fp;         // pooling rows per window <= kPoolRowsMax (K <= 1217)
     fp.padL = K / 2 + K % 2 - 1;
     fp.TP = (T - 1) / hop + 1;
-    fp.L = fft_block_len(K, hop, fft_static_geometry(K, hop) && !LEAF_FFT_FORCE_GENERIC);
+    fp.L = fft_block_len(K, hop, fft_static_geometry(K, hop));
     fp.nblk = ceil_div(T, fp.L);
     fp.NT = ceil_div(K + 63, 64);
     fp.GZ = (kGPad + K + 256 + 3) / 4 * 4;                   // pooling reads run up to 3 rows + 63 lanes past the window
@@ -392,9 +389,6 @@ FftPlan make_fft_plan(const Shape& s, int cus) {
 // ---- 4096-sample plan (leaf_fft_wg4k.hpp): the 32 kHz LEAF geometry.  LEAF_ALGO_FFT_WG means THIS kernel for that geometry
 // at every batch size (so that a clip is bit-identical across batch compositions); the frozen-parameter entry points
 // (leaf_fft_prepare_tables_f32 / leaf_forward_prepared_f32) keep the 2048-sample tables and kernels.
-#ifndef LEAF_FFT_NO_4K
-#define LEAF_FFT_NO_4K 0               // measurement only: 1 routes K = 801 through the 2048-sample workgroup kernel
-#endif
 struct Fft4kPlan {
     bool ok;
     bool generic;          // run-time-geometry kernel (leaf_fft_wgg4k.hpp); false: the static K = 801 / hop = 320 instance
@@ -418,7 +412,7 @@ inline Band4kLayout band4k_layout(int F, int K, int hop) {
 // LEAF_NO_4K=1 (environment, tools / tests only): keep every window on the 2048-sample plan
 inline bool fft4k_disabled() {
     static const bool off = [] { const char* e = getenv("LEAF_NO_4K"); return e && atoi(e) != 0; }();
-    return off || LEAF_FFT_NO_4K || LEAF_FFT_FORCE_GENERIC;
+    return off;
 }
 FftKernel pick_fft_wgg4k_kernel(int K) { return as_fft_kernel(leaf_inst_fft_wgg4k(fft_wgg4k_taps_per_lane(K))); }
 Fft4kPlan make_fft4k_plan(const Shape& s) {
@@ -459,7 +453,7 @@ size_t fft4k_workspace_floats(const Fft4kPlan& fp, int B) {
     return align_up(fp.tab_floats, 64) + align_up(fp.grow_floats, 64) + align_up(fp.part_floats, 64) + fp.band_floats + align_up((size_t)B, 64);
 }
 static_assert(fft_wg4k_bwd_dx_lds_bytes(kWg4BwdDxWaves) <= (size_t)kMaxLds, "LDS budget");
-static_assert(fft_wg4k_lds_bytes(12) <= (size_t)kMaxLds && fft_wg4k_bwd_lds_bytes(12) <= (size_t)kMaxLds && fft_wgg4k_lds_bytes(6, 2049, kWgg4MaxFrames) <= (size_t)kMaxLds, "LDS budget");
+static_assert(fft_wg4k_lds_bytes(12) <= (size_t)kMaxLds && fft_wgg4k_lds_bytes(6, 2049, kWgg4MaxFrames) <= (size_t)kMaxLds, "LDS budget");
 
 // ---- which instantiation of leaf_fft_kernel serves a geometry.  Odd K: real-spectrum kernels (the taps are Hermitian
 // about the centre tap); even K: complex spectrum.  The backward instances exist for the real-spectrum form only.
@@ -479,7 +473,6 @@ struct FftWgLaunch {
 // cfg3 0.4215 vs 0.428, cfg4 2.03 vs 2.05: tools/bench_configs.py, interleaved).  LEAF_WG_WAVES=16|12 (environment, tools
 // only) overrides the choice for A/B measurements.
 FftWgLaunch pick_fft_wg_kernel(int K, int hop) {
-    if (LEAF_FFT_FORCE_GENERIC) return {nullptr, 0, 0};
     static const int forced = [] { const char* e = tools_env("LEAF_WG_WAVES"); return e ? atoi(e) : 0; }();
     const bool w16 = forced == 16 || forced == 14;
     int nw = 0;
@@ -541,7 +534,7 @@ bool fft_wg_auto(const FftPlan& fp, int B, int K, int hop, int cus) {
            (K >= 224 || fft_static_geometry(K, hop));
 }
 FftKernel pick_fft_kernel(const FftPlan& fp, int K, int hop, bool bwd) {
-    const bool stat = fft_static_geometry(K, hop) && fp.g_bufs == 2 && !LEAF_FFT_FORCE_GENERIC;
+    const bool stat = fft_static_geometry(K, hop) && fp.g_bufs == 2;
     // odd and even windows alike: real-spectrum kernels (even K: Hermitian K - 1 taps + the unpaired tap in the time domain)
     if (stat && (K & 1)) return as_fft_kernel(leaf_inst_fft(K, 1, 1, bwd ? 1 : 0));
     return as_fft_kernel(leaf_inst_fft(0, fp.g_bufs == 2 ? 1 : 0, (K & 1) ? 1 : 2, bwd ? 1 : 0));
@@ -549,7 +542,7 @@ FftKernel pick_fft_kernel(const FftPlan& fp, int K, int hop, bool bwd) {
 
 // the MIX instances (waveform mixup in the block load): the static odd windows only; nullptr elsewhere
 FftKernel pick_fft_kernel_mix(const FftPlan& fp, int K, int hop, bool bwd) {
-    const bool stat = fp.ok && fft_static_geometry(K, hop) && fp.g_bufs == 2 && !LEAF_FFT_FORCE_GENERIC;
+    const bool stat = fp.ok && fft_static_geometry(K, hop) && fp.g_bufs == 2;
     return stat && (K & 1) ? as_fft_kernel(leaf_inst_fft_mix(K, bwd ? 1 : 0)) : nullptr;
 }
 
@@ -601,7 +594,7 @@ struct SmallPlan {
 SmallPlan make_small_plan(const Shape& s, int cus) {
     const auto [B, T, F, K, hop] = s;
     SmallPlan sp{};
-    if (LEAF_FFT_FORCE_GENERIC || !((K == 401 && hop == 160) || (K == 201 && hop == 80))) return sp;
+    if (!((K == 401 && hop == 160) || (K == 201 && hop == 80))) return sp;
     const int L = fft_block_len(K, hop, true);
     sp.nblk = ceil_div(T, L);
     sp.TP = (T - 1) / hop + 1;
@@ -1161,7 +1154,7 @@ static int fft_forward_tables(const CallCtx& ctx, const FftPlan& fp, const LeafA
             // (16-bit PCM: the table launch reads fp32 and bf16 only -- a third sample type in its first-block loads cost the fp32 path
             // 0.9 us of the table launch at cfg1 -- so the main kernel transforms its first blocks itself: the same bits)
             // (the table cache has no first-block spectra -- they depend on x: the main kernel transforms its first blocks itself, the same bits)
-            if (LEAF_WG_SPEC0 && !spec0_off && !tables_ready && !stamps && main_grid <= kMaxCusForSpec0 && wl.nw <= 12 && io.xtype != kSamplePcm16 && !ctx.mix.lam) {   // (a mixed call likewise: the table launch does not mix)
+            if (!spec0_off && !tables_ready && !stamps && main_grid <= kMaxCusForSpec0 && wl.nw <= 12 && io.xtype != kSamplePcm16 && !ctx.mix.lam) {   // (a mixed call likewise: the table launch does not mix)
                 ba.x = io.x; ba.io_bf16 = io.xtype; ba.B = B; ba.nblk = fp.nblk; ba.G = main_grid;
                 ba.spec0 = reinterpret_cast<float2*>(dyn + bl.spec0);
                 fb.spec0 = ba.spec0;
@@ -1209,10 +1202,7 @@ static bool fft_wg_fused_finalize(const CallCtx& ctx, const FftPlan& fp, const S
     // LEAF_ALGO_STREAM_FINALIZE asks for it; without the flag it is what runs wherever the workgroups own whole clips
     // but their frame sums do NOT fit the LDS (several clips per workgroup, long clips: BASELINE configs[3], [4]) --
     // there the alternative is the round trip of every partial sum through `part` in HBM (2x the algorithmic traffic)
-#ifndef LEAF_STREAM_AUTO
-#define LEAF_STREAM_AUTO 1         // 0 (A/B builds, tools/compare_builds.py): streaming finalize only on request, as in round 3
-#endif
-    const bool want_stream = stream_env >= 0 ? stream_env != 0 : (ctx.stream_finalize || (LEAF_STREAM_AUTO && q.fin_fused != 3));
+    const bool want_stream = stream_env >= 0 ? stream_env != 0 : (ctx.stream_finalize || q.fin_fused != 3);
     if (all_owned && wl.fn_stream && fp.nslot == 2 && want_stream) {
         // the longest ring the LDS holds, up to four times the minimum (lag >= 4: the forward tasks never wait)
         int ring = 0;
@@ -1260,7 +1250,7 @@ static int fft_forward(const CallCtx& ctx, const FftPlan& fp, const LeafArgs& a,
         }
         if (!wl.fn) return LEAF_ERR_BAD_ALGO;
         const int grid = cu_grid(B * fp.nblk, ctx.cus);
-        if (wl.fused_finalize && LEAF_WG_TAIL && !LEAF_WG_STRIDED && !fin_fused_off())
+        if (wl.fused_finalize && !fin_fused_off())
             all_owned = fft_wg_fused_finalize(ctx, fp, a.s, grid, fb.lds, fin, wl, q, own);
         if (fb.band.rec) {                                    // (decided before the prep launch, which built the tables)
             q.spec0 = fb.spec0;
@@ -1321,7 +1311,7 @@ static int forward_small(const CallCtx& ctx, const LeafArgs& a, const FwdIo& io,
 
 // ---- the one-launch streaming step (leaf_fft_stream.hpp): history and smoother state resident in `state` between calls
 // state = [history half 0 | history half 1 | ema], each region a multiple of 256 bytes behind the base
-static inline bool stream_geometry(int K, int hop) { return !LEAF_FFT_FORCE_GENERIC && ((K == 401 && hop == 160) || (K == 201 && hop == 80)); }
+static inline bool stream_geometry(int K, int hop) { return (K == 401 && hop == 160) || (K == 201 && hop == 80); }
 struct StreamLayout { int H; size_t half, ema, total; };               // samples per clip and half; byte offsets
 static StreamLayout stream_layout(int B, int F, int K, int hop, bool pcm) {
     StreamLayout L{};
@@ -2035,11 +2025,10 @@ static bool wg_block_dx_enabled() {
 // than kBandMaxFilters filters or clips whose edge frames band_edges() cannot table; backward_fft says so (`band_possible`) when it picks
 // its kernels (the workspace layout does not depend on the pick), and such calls keep the 20/16 crossing measured without band tasks.
 inline int wg_bwd_sixteenths(int K, int hop, bool dx, bool band_possible) {
-    if (!band_geometry_ok(K, hop) || !LEAF_BAND_BWD || !band_possible) return 20;
-    return dx ? (LEAF_BAND_BWD_DX ? LEAF_WG_BWD_DX_BAND_SIXTEENTHS : 20) : LEAF_WG_BWD_BAND_SIXTEENTHS;
+    if (!band_geometry_ok(K, hop) || !band_possible) return 20;
+    return dx ? LEAF_WG_BWD_DX_BAND_SIXTEENTHS : LEAF_WG_BWD_BAND_SIXTEENTHS;
 }
 FftWgBwdLaunch pick_fft_wg_bwd_kernel(int K, int hop, bool dx, int cus, bool band_possible, long long blocks = 0, bool io_bf16 = false) {
-    if (LEAF_FFT_FORCE_GENERIC) return {nullptr, 0, 0};
     if (dx) {
         if (!(fft_static_geometry(K, hop) && (K & 1))) return {nullptr, 0, 0};
         // (not K = 801: there the block-per-wave kernel measures 5 % faster, 1.89 vs 1.99 ms at 256 x 1 s)
@@ -2097,9 +2086,6 @@ bool fft_wgg_bwd_use(const FftPlan& fp, int B, int K, int hop, bool need_dx, int
            (long long)B * fp.nblk >= fft_wg_bwd_min_blocks(cus, 10);
 }
 
-#ifndef LEAF_BWD_ROWSUMS
-#define LEAF_BWD_ROWSUMS 1             // 0: param_reduce_kernel re-reads the B x T' gradients for d pool_b (A/B)
-#endif
 FftBwdLayout fft_bwd_layout(const FftPlan& fp, int B, int F, bool need_dx) {
     FftBwdLayout L{};
     size_t o = 0;
@@ -2164,9 +2150,8 @@ Fft4kBwdPlan make_fft4k_bwd_plan(const Shape& s, bool need_dx, int cus) {
     if ((long long)B * bp.nblk >= (1ll << 30) || (long long)B * bp.nblk < fft_wg_bwd_min_blocks(cus, stat && !need_dx ? LEAF_WG4K_BWD_BAND_SIXTEENTHS : 8)) return bp;
     if (stat) {
         bp.RG = kWg4RowFloats;
-        bp.nw = need_dx ? kWg4BwdDxWaves : LEAF_4K_BWD_NW;                           // half scratch + the two parity pooling rows per wave
-        bp.lds = need_dx ? fft_wg4k_bwd_dx_lds_bytes(kWg4BwdDxWaves)
-                         : (LEAF_4K_BWD_REGW && LEAF_4K_BWD_FULLSCR) ? fft_wg4k_lds_bytes(LEAF_4K_BWD_NW) : fft_wg4k_bwd_lds_bytes(LEAF_4K_BWD_NW);
+        bp.nw = need_dx ? kWg4BwdDxWaves : LEAF_4K_BWD_NW;
+        bp.lds = need_dx ? fft_wg4k_bwd_dx_lds_bytes(kWg4BwdDxWaves) : fft_wg4k_lds_bytes(LEAF_4K_BWD_NW);   // dx: half scratch; else the forward's
         bp.ok = true;
         return bp;
     }
@@ -2249,7 +2234,7 @@ static size_t bwd_own_workspace_floats(BwdPath path, const Shape& s, bool need_d
 // read fp32 only and get a widened copy of x behind their own layout
 static size_t bwd_x32_floats(BwdPath path, const Shape& s, int flags) {
     if (!(flags & (LEAF_FLAG_IO_BF16 | LEAF_FLAG_X_PCM16)) || path == BWD_PATH_FFT4K) return 0;
-    if (path == BWD_PATH_FFT && fft_static_geometry(s.K, s.hop) && (s.K & 1) && !LEAF_FFT_FORCE_GENERIC) return 0;
+    if (path == BWD_PATH_FFT && fft_static_geometry(s.K, s.hop) && (s.K & 1)) return 0;
     return align_up((size_t)s.B * s.T, 64);
 }
 
@@ -2296,7 +2281,7 @@ static int launch_pcen_bwd_scan(const LeafArgs& a, const BwdIo& io, const float*
                                 const int* col_of, int FP, float* gcols, float* rowsums) {
     const int B = a.s.B, F = a.s.F, TP = (a.s.T - 1) / a.s.hop + 1;
     hipLaunchKernelGGL(pcen_bwd_scan_kernel, dim3(ceil_div(B * F, 4)), dim3(256), 0, a.st, raw_in, io.grad_out, B * F, F, TP, a.alpha,
-                       a.delta, a.root, a.ema_w, 1e-12f, io.mode, ema, gpre, rowsum, col_of, FP, gcols, LEAF_BWD_ROWSUMS ? rowsums : nullptr);
+                       a.delta, a.root, a.ema_w, 1e-12f, io.mode, ema, gpre, rowsum, col_of, FP, gcols, rowsums);
     LEAF_LAUNCH_CHECK();
     return LEAF_OK;
 }
@@ -2308,7 +2293,7 @@ static int launch_fft_param_reduce(const LeafArgs& a, const BwdIo& io, const flo
     hipLaunchKernelGGL(param_reduce_kernel, dim3(F), dim3(kParamRedThreads), 0, a.st, gpre, (const float*)nullptr,
                        (const float*)nullptr, rowsum, a.pool_w, B, F, TP, K, io.mode, dwpart, nblocks, F, col_of, io.g_pool_w,
                        io.g_pool_b, io.g_alpha, io.g_delta, io.g_root, io.g_ema_w,
-                       dkpart, nblocks, a.kernel, gabor_bounds(K), io.g_kernel, LEAF_BWD_ROWSUMS ? rowsums : nullptr);
+                       dkpart, nblocks, a.kernel, gabor_bounds(K), io.g_kernel, rowsums);
     LEAF_LAUNCH_CHECK();
     return LEAF_OK;
 }
@@ -2331,8 +2316,8 @@ static int backward_4k(const CallCtx& ctx, const LeafArgs& a, const BwdIo& io, f
     // the edge tables by fft4k_band_tab_kernel, from the parameters of this call
     BandParams band{};
     BandTabArgs ba{};
-    const bool band_bwd = LEAF_BAND_BWD && !band_bwd_off() && !ctx.band_off && bp.stat && !bp.dx && L.bgz2 &&
-                          LEAF_4K_BWD_REGW && LEAF_4K_BWD_FULLSCR && bp.lds + band_lds_bytes(F) <= (size_t)kMaxLds &&
+    const bool band_bwd = !band_bwd_off() && !ctx.band_off && bp.stat && !bp.dx && L.bgz2 &&
+                          bp.lds + band_lds_bytes(F) <= (size_t)kMaxLds &&
                           band_edges(T, K, hop, bp.L, bp.padL, band, ba.e);
     if (band_bwd)   // (bwd_slabs = 2: the class decision also asks band_deriv_fits, leaf_band.hpp; no extra grid rows in this kernel)
         wire_band(ba, band, BandTabs{reinterpret_cast<int*>(ws + L.brec), ws + L.bgz, ws + L.bgz2, ws + L.bedge, ws + L.bedge2, reinterpret_cast<int*>(ws + L.belist)},
@@ -2414,9 +2399,9 @@ static int backward_fft(const CallCtx& ctx, const LeafArgs& a, const BwdIo& io, 
     // (with dL/dx: in the workgroup-per-block kernel, whose band tasks add their members' shares to the block's G)
     const bool use_wg = fft_wg_bwd_use(fp, B, K, hop, need_dx, ctx.cus, band_possible);
     const FftWgBwdLaunch bwl = pick_fft_wg_bwd_kernel(K, hop, need_dx, ctx.cus, band_possible, (long long)B * fp.nblk);
-    const bool band_bwd = LEAF_BAND_BWD && !band_bwd_off() && !ctx.band_off && L.bgz2 && (K & 1) &&
+    const bool band_bwd = !band_bwd_off() && !ctx.band_off && L.bgz2 && (K & 1) &&
                           F <= kBandMaxFilters && fp.nslot == 2 && use_wg &&
-                          (need_dx ? LEAF_BAND_BWD_DX && bwl.block_dx : true) &&
+                          (!need_dx || bwl.block_dx) &&
                           bwl.lds + band_lds_bytes(F) <= (size_t)kMaxLds && band_edges(T, K, hop, fp.L, fp.padL, band, ba.e);
     if (band_bwd) {
         wire_band(ba, band, BandTabs{reinterpret_cast<int*>(ws + L.brec), ws + L.bgz, ws + L.bgz2, ws + L.bedge, ws + L.bedge2, reinterpret_cast<int*>(ws + L.belist)},

@@ -371,6 +371,59 @@ def test_notes_switch_table_is_current():
     assert r.stdout.strip() in notes, "NOTES.md: regenerate the switches table (python tools/list_switches.py --markdown)"
 
 
+# `#ifdef`-style handles of the HIP sources: defined only by a tool's -D or by an instantiation unit, so list_switches.py (which
+# reads `#ifndef X / #define X default`) does not report them
+SWITCH_HANDLES = {"LEAF_TOOLS", "LEAF_INST_TU", "LEAF_WG_NW", "LEAF_SMALL_STAMP", "LEAF_DX_NOWAIT", "LEAF_4K_DX_NOACC"}
+
+
+def leaf_identifiers_outside_the_switch_list(handles=SWITCH_HANDLES):
+    """(where, name) of every LEAF_* identifier in csrc/ that a preprocessor condition tests, or that code uses as a constant,
+    without tools/list_switches.py reporting it.  Conditions may name only listed switches and the handles above (an undefined
+    name in `#if` is 0 without a word); code may also use the C API's constants (include/leaf_hip.h) and the helper macros the
+    sources #define themselves.  Comments, string literals and function-like macro calls are not constants."""
+    import glob
+    import re
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "list_switches.py")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    listed = {line.split()[0] for line in r.stdout.splitlines() if line.strip()} | set(handles)
+    ident = re.compile(r"\bLEAF_[A-Z0-9_]+\b")
+    const = re.compile(r"\bLEAF_[A-Z0-9_]+\b(?!\s*\()")
+    api = set(ident.findall(open(os.path.join(REPO, "include", "leaf_hip.h")).read()))
+    sources = {}
+    for path in sorted(glob.glob(os.path.join(REPO, "leaf_pytorch_amd", "csrc", "*"))):
+        s = open(path).read()
+        s = re.sub(r"/\*.*?\*/", " ", s, flags=re.S)
+        s = re.sub(r'"(\\.|[^"\\\n])*"', '""', s)
+        s = re.sub(r"//[^\n]*", "", s)
+        sources[os.path.basename(path)] = re.sub(r"\\\n", " ", s).split("\n")
+    directive = re.compile(r"\s*#\s*(if|elif|ifdef|ifndef|define|undef)\b\s*(.*)")
+    local = {m.group(2).split("(")[0].split()[0] for lines in sources.values() for m in map(directive.match, lines)
+             if m and m.group(1) == "define" and m.group(2)}
+    bad = []
+    for name, lines in sources.items():
+        for no, line in enumerate(lines, 1):
+            m = directive.match(line)
+            if m and m.group(1) in ("if", "elif", "ifdef", "ifndef"):
+                bad += [(f"{name}:{no}", n) for n in ident.findall(m.group(2)) if n not in listed]
+                continue
+            if m and m.group(1) == "undef":
+                continue
+            body = line if not m else re.sub(r"^\s*LEAF_[A-Z0-9_]+(\([^)]*\))?", "", m.group(2))   # a #define: its replacement
+            bad += [(f"{name}:{no}", n) for n in const.findall(body) if n not in listed and n not in api and n not in local]
+    return bad
+
+
+def test_every_leaf_identifier_is_a_listed_switch():
+    """A retired switch left behind in a condition (`#if LEAF_WG_PK`) would select the `#else` side silently: every LEAF_* name
+    that csrc/ tests or uses as a constant is one tools/list_switches.py reports, or a handle of SWITCH_HANDLES.  The scan sees
+    what it should: without its allowance for LEAF_INST_TU it reports that handle."""
+    assert leaf_identifiers_outside_the_switch_list() == []
+    missed = leaf_identifiers_outside_the_switch_list(SWITCH_HANDLES - {"LEAF_INST_TU"})
+    assert missed and {n for _, n in missed} == {"LEAF_INST_TU"}
+
+
 def test_gradient_metric_rejects_a_wrong_sigma_derivative():
     """at the default parameters d/d mu of `_complex_conv._kernel` is ~650x d/d sigma, so a comparison against
     the TENSOR's largest entry (round 5) lets a wrong sigma derivative through.  The metric of tests/helpers.py (per column, per

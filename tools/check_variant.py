@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Correctness of a build variant of libleaf_hip.so (leaf_pytorch_amd/build/variants/<name>/) before it is timed: the forward of
 a few shapes against the CPU oracle and against the in-tree library, through the C ABI.
-    python tools/compare_builds.py --build-only pk:-DLEAF_WG_PK=1     # build container
-    python tools/check_variant.py pk                                    # GPU box"""
+    python tools/compare_builds.py --build-only nw11:-DLEAF_4K_FWD_NW=11    # build container
+    python tools/check_variant.py nw11                                       # GPU box"""
 import ctypes, os, sys
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
