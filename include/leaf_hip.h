@@ -602,6 +602,44 @@ int leaf_forward_prepared_f32(const float* x, int B, int T, const void* tables, 
  * exceeds 1 are divided by their peak, others are copied unchanged.  x, out [B][T]; out may alias x. */
 int leaf_peak_normalize_f32(const float* x, int B, int T, float* out, void* stream);
 
+/* Batch assembly from a packed sample store (additive: the ABI version stays 6).  utilities/data/raw_transforms.py per clip, in
+ * the order of get_raw_transforms_v2 -- PadToSize, RandomCrop / CenterCrop, RandomGain, PeakNormalization, TimeMasking -- in ONE
+ * launch, one workgroup per clip: the (B, size) float32 batch the forward entries take, from recordings of any length that lie
+ * back to back in `store`.  The random draws are the caller's (the plan below); the library applies them.
+ *
+ *   store     [store_len] samples, float32, or int16_t with flags = LEAF_FLAG_X_PCM16 (a sample v means v / 32768, as everywhere)
+ *   rec_off   [B] int64: first sample of clip b's recording in the store      rec_len  [B] int32: its length L
+ *   start     [B] int32: crop offset in the padded recording                  pad_mode [B] int32: 0 zero, 1 min, 2 replicate, 3 wrap
+ *   gain      [B] float32 linear factors, or NULL                             normalize: 0 / 1
+ *   masks     [B][M][2] int32 spans (t0, n), or NULL with M = 0              out      [B][size] float32
+ *
+ * With r[j] = store[rec_off[b] + j], S = size, P = max(S - L, 0), left = P / 2 and Lp = max(L, S), for t in [0, S):
+ *   1. pad and crop: j = start[b] + t - left; 0 <= j < L gives r[j]; otherwise (only when L < S) the pad mode decides: 0 -> 0;
+ *      1 -> min(r) over the whole recording (the reference's 'constant', which pads with signal.min()); 2 -> r[clamp(j, 0, L - 1)]
+ *      (torch F.pad 'replicate': what the reference's torch PadToSize(mode='wrap') does); 3 -> r[j mod L], floor modulus, any
+ *      number of periods (numpy.pad 'wrap': PadToSize_NP);
+ *   2. gain: y = v * gain[b], one fp32 multiply (skipped for gain == NULL);
+ *   3. normalize != 0: peak = max |y| over the S samples; peak > 1 gives y * (1 / peak), else y unchanged -- bit for bit
+ *      leaf_peak_normalize_f32 on the clips of step 2;
+ *   4. masks: y[max(t0, 0) : min(t0 + n, S)] = 0 per span; n <= 0 masks nothing.  The peak of step 3 is taken before the masks.
+ *
+ * MEMORY SAFETY.  The plan is device memory, which the library cannot inspect, so the kernel clamps it: rec_off into
+ * [0, store_len], rec_len into [0, store_len - rec_off], start into [0, Lp - S]; a pad_mode outside 0..3 counts as 0; a recording
+ * of clamped length 0 gives a clip of zeros (its min is 0).  Whatever the plan holds, nothing outside store[0, store_len) is read
+ * and nothing outside out[B][size] is written.
+ *
+ * Clips of up to 32765 samples stay in registers between the peak and the store (the store is read once); longer ones, any
+ * size < 2^31, are gathered twice (the second time from L2 where they fit).  One workgroup works on one clip whatever its
+ * length: a few long clips use a few CUs.
+ *
+ * No workspace.  Alignment: element alignment as everywhere -- store 4 bytes (2 for int16), rec_off 8, every other buffer 4.
+ * Status: LEAF_ERR_UNSUPPORTED for a flag other than LEAF_FLAG_X_PCM16; LEAF_ERR_NULL_POINTER; LEAF_ERR_BAD_SHAPE for B < 1,
+ * size < 1, store_len < 0, M < 0, or M > 0 with masks == NULL (B == 0 is the caller's to skip: there is nothing to write);
+ * LEAF_ERR_ALIGNMENT -- in that order, before any launch.  out must not overlap store. */
+int leaf_assemble_clips_f32(const void* store, long long store_len, int flags, int B, int size, const long long* rec_off,
+                            const int* rec_len, const int* start, const int* pad_mode, const float* gain, int normalize,
+                            const int* masks, int M, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

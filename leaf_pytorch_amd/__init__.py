@@ -6,9 +6,9 @@ from .modules import (ExponentialMovingAverage, GaborConstraint, GaborConv1d, Ga
                       get_padding_value)
 from .initializers import GaborFilter, GaborInit
 from ._native import build, load, LIB_PATH
-from .transforms import CenterCrop, PeakNormalization, RandomCrop
+from .transforms import CenterCrop, ClipSampler, PackedClips, PeakNormalization, RandomCrop
 from .streaming import LeafStream, LeafStreamBank
 
 __all__ = ["Leaf", "SquaredModulus", "get_frontend", "GaborConv1d", "GaborConstraint", "GaussianLowPass",
            "ExponentialMovingAverage", "PCENLayer", "GaborInit", "GaborFilter", "get_padding_value", "build", "load",
-           "PeakNormalization", "CenterCrop", "RandomCrop", "LeafStream", "LeafStreamBank"]
+           "PeakNormalization", "CenterCrop", "RandomCrop", "PackedClips", "ClipSampler", "LeafStream", "LeafStreamBank"]

@@ -94,6 +94,9 @@ _SIGNATURES = {
     "leaf_pcen_backward_f32": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_f32p] * 4
                                + [ctypes.c_float] + [_f32p] * 5 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "leaf_peak_normalize_f32": (ctypes.c_int, [_f32p, ctypes.c_int, ctypes.c_int, _f32p, ctypes.c_void_p]),
+    # batch assembly: store, store_len, flags, B, size, rec_off, rec_len, start, pad_mode, gain, normalize, masks, M, out, stream
+    "leaf_assemble_clips_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+                                + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "leaf_fft_tables_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "leaf_fft_prepare_tables_f32": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_size_t, ctypes.c_void_p]),
@@ -858,6 +861,103 @@ def peak_normalize(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch
     if B:
         _call(x.device, "leaf_peak_normalize_f32", x2, B, T, out)
     return out.reshape(x.shape)
+
+
+PAD_ZERO, PAD_MIN, PAD_REPLICATE, PAD_WRAP = 0, 1, 2, 3     # pad_mode of leaf_assemble_clips_f32
+PAD_MODES = {"zero": PAD_ZERO, "min": PAD_MIN, "replicate": PAD_REPLICATE, "wrap": PAD_WRAP}
+ASSEMBLE_RESIDENT_MAX = 32765    # csrc/leaf_clips.hpp (kClipResidentMax): clips up to this size stay in registers, longer ones are gathered twice
+
+
+def _plan_ints(t, name: str, B: int) -> torch.Tensor:
+    """One integer array of a clip plan, flat, with one entry per clip (ValueError otherwise); it stays on its device."""
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise TypeError(f"{name} must be an integer tensor or sequence, got {t.dtype}")
+    t = t.detach().reshape(-1)
+    if t.numel() != B:
+        raise ValueError(f"{name} has {t.numel()} entries, expected one per clip ({B})")
+    return t
+
+
+def clip_plan(store_len: int, rec_off, rec_len, start, pad_mode, size: int, gain=None, masks=None):
+    """The plan of ``assemble_clips`` as flat tensors on the devices they arrived on, checked as far as the host can see it.  An array
+    that arrives on the CPU is validated here (ValueError, before anything is launched): ``rec_off`` in [0, store_len], ``rec_len`` in
+    [0, store_len - rec_off], ``start`` in [0, max(L, size) - size], ``pad_mode`` in 0..3.  A device-side array is not read back -- that
+    would be a synchronisation per step -- and the kernel clamps it instead (include/leaf_hip.h).  Lengths, and the shape (B, M, 2) of
+    ``masks``, are checked wherever the arrays live.  Returns (B, rec_off, rec_len, start, pad_mode, gain, masks)."""
+    size = int(size)
+    if not 1 <= size < CALL_SAMPLES:
+        raise ValueError(f"size must be in [1, 2^31), got {size}")
+    if not isinstance(rec_off, torch.Tensor):
+        rec_off = torch.as_tensor(rec_off)
+    B = rec_off.numel()
+    rec_off, rec_len, start, pad_mode = (_plan_ints(t, n, B) for t, n in ((rec_off, "rec_off"), (rec_len, "rec_len"), (start, "start"),
+                                                                          (pad_mode, "pad_mode")))
+    on_cpu = lambda t: t.device.type == "cpu" and B > 0
+    if on_cpu(rec_off) and (int(rec_off.min()) < 0 or int(rec_off.max()) > store_len):
+        raise ValueError(f"rec_off holds an offset outside [0, {store_len}] (the store's length)")
+    if on_cpu(rec_len):
+        if int(rec_len.min()) < 0 or int(rec_len.max()) >= CALL_SAMPLES:
+            raise ValueError("rec_len holds a length outside [0, 2^31)")
+        room = store_len - rec_off.long() if on_cpu(rec_off) else store_len
+        if bool((rec_len.long() > room).any()):
+            raise ValueError(f"rec_len holds a recording that ends behind the store ({store_len} samples)")
+    if on_cpu(start):
+        if int(start.min()) < 0:
+            raise ValueError("start holds a negative offset")
+        if on_cpu(rec_len) and bool((start.long() > (rec_len.long() - size).clamp_(min=0)).any()):
+            raise ValueError(f"start holds an offset outside [0, max(rec_len, {size}) - {size}]")
+    if on_cpu(pad_mode) and (int(pad_mode.min()) < PAD_ZERO or int(pad_mode.max()) > PAD_WRAP):
+        raise ValueError("pad_mode holds a value outside 0..3 (zero, min, replicate, wrap)")
+    if gain is not None:
+        if not isinstance(gain, torch.Tensor):
+            gain = torch.as_tensor(gain, dtype=torch.float32)
+        gain = gain.detach().reshape(-1)
+        if gain.numel() != B:
+            raise ValueError(f"gain has {gain.numel()} entries, expected one per clip ({B})")
+        if gain.dtype != torch.float32:
+            raise RuntimeError(f"gain must be float32, got {gain.dtype}")
+    if masks is not None:
+        if not isinstance(masks, torch.Tensor):
+            masks = torch.as_tensor(masks)
+        if masks.dtype.is_floating_point or masks.dtype.is_complex or masks.dtype == torch.bool:
+            raise TypeError(f"masks must be an integer tensor, got {masks.dtype}")
+        if masks.dim() != 3 or masks.shape[0] != B or masks.shape[2] != 2:
+            raise ValueError(f"masks has shape {tuple(masks.shape)}, expected ({B}, M, 2): M spans (t0, n) per clip")
+        masks = None if masks.shape[1] == 0 else masks.detach()
+    return B, rec_off, rec_len, start, pad_mode, gain, masks
+
+
+def assemble_clips(store: torch.Tensor, rec_off, rec_len, start, pad_mode, size: int, gain=None, normalize: bool = True, masks=None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The batch (B, 1, size), float32, from a packed sample store in one launch (leaf_assemble_clips_f32, where the semantics are
+    stated): per clip b the recording ``store[rec_off[b] : rec_off[b] + rec_len[b]]`` is padded to ``size`` if it is shorter
+    (``pad_mode[b]``: PAD_ZERO / PAD_MIN / PAD_REPLICATE / PAD_WRAP, split left = padding // 2), cropped at ``start[b]``, multiplied by
+    ``gain[b]``, peak-normalised (``normalize``: the bits of ``peak_normalize`` on the clip so far) and zeroed inside the ``masks``
+    (B, M, 2) spans (t0, n).  ``store``: 1-D float32 or int16 PCM (a sample v means v / 32768) on a HIP device.  The plan arrays may
+    live on either side: on the CPU they are validated (``clip_plan``) and copied over, on the device they are used as they are and
+    clamped by the kernel."""
+    if not isinstance(store, torch.Tensor) or store.dim() != 1 or store.dtype not in (torch.float32, torch.int16):
+        raise RuntimeError("assemble_clips: store must be a 1-D float32 or int16 tensor")
+    size = int(size)
+    B, rec_off, rec_len, start, pad_mode, gain, masks = clip_plan(store.numel(), rec_off, rec_len, start, pad_mode, size, gain, masks)
+    require_hip(store, "assemble_clips")
+    dev = store.device
+    store = store.detach().contiguous()
+    if out is not None:
+        _check_out(out, (B, 1, size), torch.float32, dev)
+    else:
+        out = torch.empty((B, 1, size), dtype=torch.float32, device=dev)
+    if B == 0:
+        return out
+    rec_off = rec_off.to(device=dev, dtype=torch.int64).contiguous()
+    rec_len, start, pad_mode = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (rec_len, start, pad_mode))
+    gain = None if gain is None else gain.to(device=dev).contiguous()
+    masks = None if masks is None else masks.to(device=dev, dtype=torch.int32).contiguous()
+    _call(dev, "leaf_assemble_clips_f32", store, store.numel(), FLAG_X_PCM16 if store.dtype == torch.int16 else 0, B, size,
+          rec_off, rec_len, start, pad_mode, gain, int(bool(normalize)), masks, 0 if masks is None else masks.shape[1], out)
+    return out
 
 
 def prepare_tables(kernel: torch.Tensor, pool_w: torch.Tensor, K: int, hop: int) -> Optional[torch.Tensor]:

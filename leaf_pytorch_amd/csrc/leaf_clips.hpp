@@ -1,0 +1,261 @@
+// leaf_clips.hpp -- batch assembly from a packed sample store (leaf_assemble_clips_f32): per-clip pad, crop, gain, peak
+// normalisation and time masks in one launch.  Compiled in inst_clips.hip; gfx950 only.
+//
+// Reference arithmetic being replaced (utilities/data/raw_transforms.py, per clip on the CPU there): PadToSize (torch: F.pad
+// 'replicate' / constant signal.min(); numpy: np.pad 'wrap'), RandomCrop / CenterCrop, RandomGain, PeakNormalization
+// (only_too_loud_sounds), TimeMasking -- in the order of get_raw_transforms_v2.  The contract is in include/leaf_hip.h.
+//
+// Shape of the kernel.  One workgroup of 1024 lanes per clip (256 clips fill the 256 CUs); a gather, a max reduction, and a min
+// reduction for the clips that pad with their recording's minimum (the whole recording is then shorter than the clip).  Every
+// decision that selects a path -- the store's sample type (a template argument), the pad mode, whether the min pass runs, resident
+// or re-reading -- is uniform over the workgroup.  No scratch, no atomics, nothing shared between workgroups.
+//
+//   * The output row is walked in 16-byte chunks ALIGNED IN `out`: a row starts 4 * S * b bytes behind `out`, so its first
+//     `shift` = (address / 4) mod 4 elements' worth of the first chunk belong to the row before it.  Chunk q holds the row's
+//     elements 4 q - shift .. 4 q - shift + 3; whole chunks are stored as one float4, the (at most two) partial ones element-wise.
+//   * A chunk whose four source samples are contiguous inside the recording is read with ONE load at element alignment (16 bytes
+//     at 4-byte alignment for a float32 store, 8 bytes at 2-byte alignment for int16: `rec_off`, `start` and the left pad are
+//     arbitrary, so the source cannot be aligned together with the destination; gfx950 global loads take any alignment).  Every
+//     lane issues that load for every chunk of its tile, moved inside the recording where the chunk is not: straight-line code,
+//     so a tile's loads are in flight together.  A chunk that touches the padded margins or the row's ends is then redone element
+//     by element through the pad rule (a few lanes per clip).
+//   * RESIDENT path, S <= kClipResidentMax = 8 * 4 * 1024 - 3 = 32 765 samples (two seconds at 16 kHz): the clip's chunks stay
+//     in registers (eight float4 per lane; the 3 covers the worst `shift`) between the peak reduction and the store, so the store
+//     is read once.  A longer clip takes the RE-READING path: one pass for the peak, a second that gathers again (from L2 where
+//     the clip fits) and stores -- slower, any 1 <= S < 2^31.  Without `normalize` the first pass is skipped.
+//   * One workgroup per clip also for long clips: B = 8 clips of five seconds use 8 CUs.  Splitting a clip over workgroups would
+//     need a second launch for the peak and is not built.
+//
+// Memory safety: the plan is device memory the host never sees, so the kernel clamps it (rec_off into [0, store_len], rec_len
+// into [0, store_len - rec_off], start into [0, max(L, S) - S], an unknown pad mode to 0): no plan reads outside the store or
+// writes outside out[b].
+#pragma once
+#include "leaf_common.hpp"
+
+namespace {
+
+constexpr int kClipThreads = 1024;
+constexpr int kClipChunks = 8;                                            // float4 chunks a lane keeps on the resident path
+constexpr int kClipResidentMax = kClipChunks * 4 * kClipThreads - 3;     // 32 765: the cut-over to the re-reading path
+
+typedef short s16x4u __attribute__((ext_vector_type(4), aligned(2)));    // 8-byte load at 2-byte alignment
+
+struct ClipParams {
+    const void* store;            // float32 or int16 samples
+    long long store_len;
+    const long long* rec_off;     // [B]
+    const int *rec_len, *start, *pad_mode;   // [B]
+    const float* gain;            // [B] or null
+    const int* masks;             // [B][M][2] or null
+    float* out;                   // [B][S]
+    int S, M, normalize;
+};
+
+// One clip's clamped plan (uniform over the workgroup).
+struct ClipView {
+    long long off;                // first sample in the store: of the recording, or of the cropped window when the recording is longer
+    int L, left, mode;            // samples behind `off` (at most S), left pad, pad mode (0 when L == 0)
+    float padv;                   // the constant outside the recording: 0, or min(r) for mode 1
+    float g;
+    bool has_gain;
+};
+
+template <bool PCM> __device__ __forceinline__ float clip_load(const void* store, long long i) {
+    if constexpr (PCM) return pcm16_widen(static_cast<const short*>(store)[i]);
+    else return static_cast<const float*>(store)[i];
+}
+
+// max or min over the workgroup (every lane calls it; `red` is free again on return)
+template <bool MIN> __device__ __forceinline__ float clip_block_reduce(float m, float* red) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = MIN ? fminf(m, __shfl_xor(m, off)) : fmaxf(m, __shfl_xor(m, off));
+    if ((tid & 63) == 0) red[tid >> 6] = m;
+    __syncthreads();
+    float r = red[0];
+#pragma unroll
+    for (int w = 1; w < kClipThreads / 64; ++w) r = MIN ? fminf(r, red[w]) : fmaxf(r, red[w]);
+    __syncthreads();
+    return r;
+}
+
+// element t of the padded, cropped clip (0 <= t < S) before the gain.  I: int on the resident path, long long on the other one.
+template <bool PCM, class I> __device__ __forceinline__ float clip_sample(const void* store, const ClipView& c, I t) {
+    const I j = t - (I)c.left;
+    if (j >= 0 && j < (I)c.L) return clip_load<PCM>(store, c.off + j);
+    if (c.mode == 2) return clip_load<PCM>(store, c.off + (j < 0 ? 0 : c.L - 1));
+    if (c.mode == 3) {
+        int m = (int)(j % (I)c.L);                                        // floor modulus: periodic over any number of periods
+        if (m < 0) m += c.L;
+        return clip_load<PCM>(store, c.off + m);
+    }
+    return c.padv;
+}
+
+// The four source samples of the chunk at row elements t0 .. t0 + 3 in ONE load, issued by every lane whether its chunk can use it or
+// not (straight-line code: the loads of a tile are all in flight before the first is waited for).  The load is moved inside the
+// recording (L >= 4); `exact` says whether it sits where the chunk's samples are, i.e. the chunk is whole and needs no padding.
+template <bool PCM, class I> __device__ __forceinline__ bool clip_chunk_load(const void* store, const ClipView& c, int S, I t0, float (&v)[4]) {
+    const I j0 = t0 - (I)c.left, top = (I)c.L - 4;
+    const I jc = j0 < 0 ? 0 : (j0 > top ? top : j0);
+    if constexpr (PCM) {
+        const s16x4u s = *reinterpret_cast<const s16x4u*>(static_cast<const short*>(store) + (c.off + jc));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = pcm16_widen(s[e]);
+    } else {
+        const f32x4u s = *reinterpret_cast<const f32x4u*>(static_cast<const float*>(store) + (c.off + jc));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = s[e];
+    }
+    return jc == j0 && t0 >= 0 && t0 <= (I)S - 4;
+}
+
+// ... and the chunks that load does not serve (the padded margins, the row's two ends, recordings below four samples): element by
+// element through the pad rule; elements outside [0, S) come back as 0 (they leave the peak alone and are not stored)
+template <bool PCM, class I> __device__ __forceinline__ void clip_chunk_gather(const void* store, const ClipView& c, int S, I t0, float (&v)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const I t = t0 + e;
+        v[e] = (t >= 0 && t < (I)S) ? clip_sample<PCM, I>(store, c, t) : 0.0f;
+    }
+}
+
+__device__ __forceinline__ float clip_chunk_peak(float m, const float (&v)[4]) {
+    return fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+}
+
+// one mask span as the half-open range [lo, hi) of row elements it zeroes (empty when n <= 0)
+__device__ __forceinline__ void clip_mask_span(const int* masks, size_t span, int S, long long& lo, long long& hi) {
+    const long long t0 = masks[2 * span], n = masks[2 * span + 1];
+    lo = t0 > 0 ? t0 : 0;
+    hi = n > 0 ? (t0 + n < S ? t0 + n : S) : lo;
+}
+
+template <class I> __device__ __forceinline__ void clip_chunk_store(float* ob, int S, I t0, const float (&v)[4]) {
+    if (t0 >= 0 && t0 <= (I)S - 4) {
+        *reinterpret_cast<f32x4*>(ob + t0) = f32x4{v[0], v[1], v[2], v[3]};   // 16-byte aligned by the chunk grid
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const I t = t0 + e;
+            if (t >= 0 && t < (I)S) ob[t] = v[e];
+        }
+    }
+}
+
+// A lane's tile: the chunks q0, q0 + 1024, ... (U of them), gathered and multiplied by the gain; the lane's share of the peak comes
+// back.  Chunks behind the row are zeros.
+template <bool PCM, class I, int U>
+__device__ __forceinline__ float clip_tile_load(const void* store, const ClipView& c, int S, int shift, I q0, I nchunks, float (&v)[U][4]) {
+    bool exact[U];
+    if (c.L >= 4) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) exact[u] = clip_chunk_load<PCM, I>(store, c, S, 4 * (q0 + (I)u * kClipThreads) - shift, v[u]);
+    } else {
+#pragma unroll
+        for (int u = 0; u < U; ++u) exact[u] = false;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const I q = q0 + (I)u * kClipThreads;
+        if (q >= nchunks) v[u][0] = v[u][1] = v[u][2] = v[u][3] = 0.0f;
+        else if (!exact[u]) clip_chunk_gather<PCM, I>(store, c, S, 4 * q - shift, v[u]);
+    }
+    float m = 0.0f;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (c.has_gain) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[u][e] = v[u][e] * c.g;
+        }
+        m = clip_chunk_peak(m, v[u]);
+    }
+    return m;
+}
+
+// ... and its second half: the scale of the clip's peak (0 when the call does not normalise), the masks, the stores
+template <class I, int U>
+__device__ __forceinline__ void clip_tile_finish(const ClipParams& p, int b, int shift, I q0, I nchunks, float peak, float (&v)[U][4], float* ob) {
+    const float scale = peak > 1.0f ? 1.0f / peak : 1.0f;                 // the arithmetic of peak_normalize_kernel
+    if (peak > 1.0f) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[u][e] = v[u][e] * scale;
+    }
+    for (int s = 0; s < p.M; ++s) {
+        long long lo, hi;
+        clip_mask_span(p.masks, (size_t)b * p.M + s, p.S, lo, hi);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const I t0 = 4 * (q0 + (I)u * kClipThreads) - shift;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (t0 + e >= lo && t0 + e < hi) v[u][e] = 0.0f;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const I q = q0 + (I)u * kClipThreads;
+        if (q < nchunks) clip_chunk_store<I>(ob, p.S, 4 * q - shift, v[u]);
+    }
+}
+
+template <bool PCM>
+__global__ __launch_bounds__(kClipThreads) void assemble_clips_kernel(const ClipParams p) {
+    __shared__ float red[kClipThreads / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, S = p.S;
+    float* ob = p.out + (size_t)b * S;
+
+    ClipView c;
+    {
+        const long long off = p.rec_off[b], room = p.store_len;
+        c.off = off < 0 ? 0 : (off > room ? room : off);
+        const long long len = p.rec_len[b], most = room - c.off;
+        c.L = (int)(len < 0 ? 0 : (len > most ? most : len));
+        const int st = p.start[b], mode = p.pad_mode[b];
+        if (c.L > S) {                                                    // a crop: the window [start, start + S) of the recording, no padding
+            c.off += st < 0 ? 0 : (st > c.L - S ? c.L - S : st);
+            c.L = S;
+        }                                                                 // (otherwise max(L, S) - S = 0: the only start is 0)
+        c.left = (S - c.L) / 2;
+        c.mode = (c.L > 0 && mode >= 0 && mode <= 3) ? mode : 0;
+        c.padv = 0.0f;
+        c.has_gain = p.gain != nullptr;
+        c.g = c.has_gain ? p.gain[b] : 1.0f;
+    }
+    if (c.mode == 1 && c.L < S) {                                         // PadToSize 'constant': the recording's minimum
+        float mn = INFINITY;
+        for (int i = tid; i < c.L; i += kClipThreads) mn = fminf(mn, clip_load<PCM>(p.store, c.off + i));   // (L < S: i + 1024 fits)
+        c.padv = clip_block_reduce<true>(mn, red);
+    }
+    const int shift = (int)((reinterpret_cast<uintptr_t>(ob) >> 2) & 3);  // row elements the first aligned chunk lacks
+
+    if (S <= kClipResidentMax) {                                          // one tile per lane holds the clip
+        const int nchunks = (S + shift + 3) >> 2;
+        float v[kClipChunks][4];
+        const float m = clip_tile_load<PCM, int, kClipChunks>(p.store, c, S, shift, tid, nchunks, v);
+        const float peak = p.normalize ? clip_block_reduce<false>(m, red) : 0.0f;
+        clip_tile_finish<int, kClipChunks>(p, b, shift, tid, nchunks, peak, v, ob);
+        return;
+    }
+
+    constexpr int kU = 4;                                                 // chunks in flight per lane on the re-reading path
+    const long long nchunks = ((long long)S + shift + 3) >> 2;
+    float peak = 0.0f;
+    if (p.normalize) {
+        float m = 0.0f;
+        for (long long q0 = tid; q0 < nchunks; q0 += kU * kClipThreads) {
+            float v[kU][4];
+            m = fmaxf(m, clip_tile_load<PCM, long long, kU>(p.store, c, S, shift, q0, nchunks, v));
+        }
+        peak = clip_block_reduce<false>(m, red);
+    }
+    for (long long q0 = tid; q0 < nchunks; q0 += kU * kClipThreads) {
+        float v[kU][4];
+        clip_tile_load<PCM, long long, kU>(p.store, c, S, shift, q0, nchunks, v);
+        clip_tile_finish<long long, kU>(p, b, shift, q0, nchunks, peak, v, ob);
+    }
+}
+
+}  // namespace

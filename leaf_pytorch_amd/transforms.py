@@ -72,3 +72,152 @@ class Mixup:
             mixed_y = targets * lam.view(bsize, 1) + targets[perms] * (1 - lam.view(bsize, 1))
             return mixed_x, mixed_y, None, None, perms, lam
         return mixed_x, targets, targets[perms], lam, perms, lam
+
+
+class PackedClips:
+    """A dataset resident on the device: 1-D recordings of any lengths, all int16 PCM or all float32, concatenated once into
+    ``store`` (``offsets`` int64 and ``lengths`` int32 beside it, mirrored on the host as ``offsets_host`` / ``lengths_host``), and
+    the batches made from it by ONE kernel launch (``_native.assemble_clips`` -> leaf_assemble_clips_f32): per clip the reference's
+    PadToSize, RandomCrop / CenterCrop, RandomGain, PeakNormalization and TimeMasking (utilities/data/raw_transforms.py), which
+    run per clip on the CPU there.  The draws are the caller's (``ClipSampler`` makes them as the reference pipelines do); this class
+    applies them.  The result is the float32 ``(B, 1, size)`` batch ``Leaf.forward`` and ``Leaf.forward_mixup`` take.
+
+    One workgroup assembles one clip: a batch of a few very long clips uses a few CUs (splitting a clip over workgroups is not
+    built).  Not built either: bfloat16 stores and outputs in anything but float32."""
+
+    def __init__(self, recordings, device=None):
+        recs = [r if isinstance(r, torch.Tensor) else torch.as_tensor(r) for r in recordings]
+        if not recs:
+            raise ValueError("PackedClips needs at least one recording")
+        if any(r.dim() != 1 for r in recs):
+            raise ValueError("every recording must be 1-D (one channel)")
+        if any(r.dtype != recs[0].dtype for r in recs) or recs[0].dtype not in (torch.int16, torch.float32):
+            raise TypeError("the recordings must be all int16 (PCM) or all float32")
+        lengths = torch.tensor([r.numel() for r in recs], dtype=torch.int64)
+        store = torch.cat([r.detach() for r in recs])
+        self._set(store if device is None else store.to(device), torch.cumsum(lengths, 0) - lengths, lengths)
+
+    @classmethod
+    def from_store(cls, store: torch.Tensor, offsets, lengths) -> "PackedClips":
+        """A store that is packed already (``packed_dataset.py``'s layout): recording i is ``store[offsets[i] : offsets[i] + lengths[i]]``."""
+        self = cls.__new__(cls)
+        offsets, lengths = (torch.as_tensor(t).detach().reshape(-1).cpu().long() for t in (offsets, lengths))
+        if store.dim() != 1 or store.dtype not in (torch.int16, torch.float32):
+            raise TypeError("store must be a 1-D int16 (PCM) or float32 tensor")
+        if offsets.numel() != lengths.numel():
+            raise ValueError(f"{offsets.numel()} offsets for {lengths.numel()} lengths")
+        if offsets.numel() and (int(offsets.min()) < 0 or int(lengths.min()) < 0 or int(lengths.max()) >= 2 ** 31
+                                or int((offsets + lengths).max()) > store.numel()):
+            raise ValueError(f"a recording lies outside the store ({store.numel()} samples)")
+        self._set(store.detach(), offsets, lengths)
+        return self
+
+    def _set(self, store, offsets, lengths):
+        self.store = store.contiguous()
+        self.offsets_host, self.lengths_host = offsets.to(torch.int64), lengths.to(torch.int32)
+        self.offsets, self.lengths = self.offsets_host.to(store.device), self.lengths_host.to(store.device)
+
+    def __len__(self) -> int:
+        return self.lengths_host.numel()
+
+    def _per_clip(self, v, B: int, names=None):
+        """A per-clip plan entry given as one value for the batch, or as a sequence / tensor of B of them."""
+        if isinstance(v, str):
+            v = names[v]
+        elif names is not None and not isinstance(v, torch.Tensor) and not isinstance(v, int):
+            v = [names[m] if isinstance(m, str) else int(m) for m in v]
+        t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v, dtype=torch.int64)
+        return t.reshape(1).expand(B) if t.dim() == 0 else t
+
+    def assemble(self, index, start, size: int, pad_mode="zero", gain=None, normalize: bool = True, masks=None, out=None) -> torch.Tensor:
+        """The batch of the recordings ``index`` (any order, repeats allowed): clip b is recording ``index[b]`` padded by
+        ``pad_mode`` ("zero" / "min" / "replicate" / "wrap" or 0..3; one for the batch or one per clip) when it is shorter than
+        ``size``, cropped at ``start[b]`` in [0, max(L, size) - size], then ``gain``, peak normalisation and ``masks`` as in
+        ``_native.assemble_clips``.  An ``index`` / plan on the CPU is validated (ValueError); on the device it is used unseen and
+        the kernel clamps what it finds."""
+        index = (index if isinstance(index, torch.Tensor) else torch.as_tensor(index, dtype=torch.int64)).reshape(-1)
+        if index.dtype.is_floating_point or index.dtype == torch.bool:
+            raise TypeError(f"index must be an integer tensor or sequence, got {index.dtype}")
+        B = index.numel()
+        if index.device.type == "cpu":
+            if B and (int(index.min()) < 0 or int(index.max()) >= len(self)):
+                raise ValueError(f"index holds a recording outside [0, {len(self)})")
+            rec_off, rec_len = self.offsets_host[index.long()], self.lengths_host[index.long()]
+        else:
+            rec_off, rec_len = self.offsets[index.long()], self.lengths[index.long()]
+        return _native.assemble_clips(self.store, rec_off, rec_len, self._per_clip(start, B), self._per_clip(pad_mode, B, _native.PAD_MODES),
+                                      size, gain, normalize, masks, out)
+
+
+class ClipPlan(tuple):
+    """What ``ClipSampler.plan`` returns: ``(rec_off, rec_len, start, pad_mode, gain, masks)``, CPU tensors in the C ABI's dtypes
+    (``masks`` None without time masking) -- the arguments of ``_native.assemble_clips`` / leaf_assemble_clips_f32 behind the store."""
+    __slots__ = ()
+    rec_off, rec_len, start, pad_mode, gain, masks = (property(lambda self, i=i: self[i]) for i in range(6))
+
+
+class ClipSampler:
+    """The random draws of the reference's training / validation pipelines (raw_transforms.py: get_raw_transforms_v2,
+    simple_supervised_transforms, leaf_supervised_transforms) as a per-clip plan, and the batch ``PackedClips`` makes from it:
+
+    - pad mode: ``pad_modes[0]`` with probability ``wrap_pad_prob``, else ``pad_modes[1]`` -- the reference's
+      ``OneOf([PadToSize('wrap'), PadToSize('constant')])`` under their honest names: its torch 'wrap' is ``F.pad(..., 'replicate')``
+      and its 'constant' pads with ``signal.min()``.  ("wrap", numpy's periodic padding of PadToSize_NP, and "zero" can be named too.)
+    - start: uniform in [0, max(L, size) - size] inclusive when ``train`` (RandomCrop), the centre ``(max(L, size) - size) // 2``
+      otherwise (CenterCrop).
+    - gain: with probability ``gain_prob`` the factor ``10 ** (dB / 20)``, dB uniform in ``gain_db``, else 1.  The default 0.25 is
+      the product of the pipelines' two 0.5s (UseWithProb(RandomGain(prob=0.5), prob=0.5)).  RandomGain wraps the third-party
+      ``torch_audiomentations.Gain``, which is not in this image: its documented behaviour is restated, parity unpinned.
+    - peak normalisation: ``PeakNormalization``'s bits (the same restatement).
+    - time masks, with ``num_masks > 0`` (TimeMasking): ``randint(1, num_masks)`` spans per clip, ``n = int(uniform(0, time_perc) *
+      size)`` samples from ``t0 = int(uniform(0, size - n))``; the unused spans carry ``n = 0``.
+
+    All draws come from a CPU ``torch.Generator`` (``generator``; a fresh default-seeded one otherwise): the same seed gives the same
+    plan.  The reference's own ``random`` / ``numpy.random`` streams are NOT reproduced -- the distributions are, the numbers are not.
+    ``plan(index)`` returns the draws (``ClipPlan``), ``__call__(index)`` the assembled ``(B, 1, size)`` float32 batch.
+
+    Left out: AddGaussianNoise, AddRandomNoise (background noise at an SNR), ClipValue and RandomReverb.  Noise needs a random stream
+    on the device with an oracle of its own; the reference itself has the other two switched off."""
+
+    def __init__(self, clips: PackedClips, size: int, train: bool = True, pad_modes=("replicate", "min"), wrap_pad_prob: float = 0.5,
+                 gain_prob: float = 0.25, gain_db=(-18.0, 6.0), peak_normalize: bool = True, time_perc: float = 0.0, num_masks: int = 0,
+                 generator=None):
+        self.clips, self.size, self.train = clips, int(size), bool(train)
+        self.pad_modes = tuple(_native.PAD_MODES[m] if isinstance(m, str) else int(m) for m in pad_modes)
+        if len(self.pad_modes) != 2 or any(m not in _native.PAD_MODES.values() for m in self.pad_modes):
+            raise ValueError(f"pad_modes must name two of {sorted(_native.PAD_MODES)}")
+        self.wrap_pad_prob, self.gain_prob, self.gain_db = float(wrap_pad_prob), float(gain_prob), (float(gain_db[0]), float(gain_db[1]))
+        self.peak_normalize, self.time_perc, self.num_masks = bool(peak_normalize), float(time_perc), int(num_masks)
+        self.generator = generator if generator is not None else torch.Generator()
+
+    def _uniform(self, *shape) -> torch.Tensor:
+        return torch.rand(*shape, dtype=torch.float64, generator=self.generator)
+
+    def plan(self, index) -> ClipPlan:
+        index = torch.as_tensor(index).reshape(-1).cpu().long()
+        B, S = index.numel(), self.size
+        if B and (int(index.min()) < 0 or int(index.max()) >= len(self.clips)):
+            raise ValueError(f"index holds a recording outside [0, {len(self.clips)})")
+        rec_off, rec_len = self.clips.offsets_host[index], self.clips.lengths_host[index]
+        first = self._uniform(B) < self.wrap_pad_prob
+        pad_mode = torch.where(first, self.pad_modes[0], self.pad_modes[1]).to(torch.int32)
+        span = (rec_len.long() - S).clamp_(min=0)                              # max(L, S) - S
+        if self.train:
+            start = torch.minimum((self._uniform(B) * (span + 1).double()).floor().long(), span)
+        else:
+            start = span // 2
+        apply = self._uniform(B) < self.gain_prob
+        db = self.gain_db[0] + (self.gain_db[1] - self.gain_db[0]) * self._uniform(B)
+        gain = torch.where(apply, torch.pow(10.0, db / 20.0), 1.0).to(torch.float32)
+        masks = None
+        if self.num_masks > 0:
+            used = torch.randint(1, self.num_masks + 1, (B, 1), generator=self.generator)
+            n = (self._uniform(B, self.num_masks) * self.time_perc * S).long()
+            n = torch.where(torch.arange(self.num_masks).reshape(1, -1) < used, n, 0).clamp_(0, S)
+            t0 = (self._uniform(B, self.num_masks) * (S - n).double()).long()
+            masks = torch.stack((t0, n), dim=2).to(torch.int32)
+        return ClipPlan((rec_off.clone(), rec_len.clone(), start.to(torch.int32), pad_mode, gain, masks))
+
+    def __call__(self, index, out=None) -> torch.Tensor:
+        rec_off, rec_len, start, pad_mode, gain, masks = self.plan(index)
+        return _native.assemble_clips(self.clips.store, rec_off, rec_len, start, pad_mode, self.size, gain, self.peak_normalize, masks, out)

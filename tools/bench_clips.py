@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Time of assembling one training batch from a device-resident packed store: ONE leaf_assemble_clips_f32 launch
+(PackedClips / _native.assemble_clips) against the stock-op composition of the same batch -- index gather, .float() / 32768,
+multiply by the gain, transforms.PeakNormalization, one masked_fill per span.
+
+    python tools/bench_clips.py [--rounds 20] [--steps 50] [--out profiles/clip_assembly.txt]
+
+Both sides run in ONE process on the same store and the same plan (already on the device: drawing it is not timed), taking turns
+round after round after a warm-up round, the order alternating.  Every recording is longer than the clip, so the batch is a crop
+and the stock side needs no padding (ragged padding has no batched stock op: that side would be a Python loop over the clips).
+Before anything is timed the two sides' batches are compared bit for bit.  Two figures per side and shape, each the median [min, max]
+over the rounds of (time of `steps` calls) / steps:
+  wall    host clock from the first call to the end of a device synchronisation behind the last: what a training loop sees (the
+          Python layer's checks and the launch included; for a small batch this is the host's time, not the device's)
+  device  HIP events around the same calls, ENQUEUED WHILE THE DEVICE IS KEPT BUSY by a matrix product queued in front, so that the
+          calls run back to back from a full queue: the device's own time per call, launch gaps between kernels included, the
+          host's enqueue time excluded
+and for the kernel the achieved bytes per second: (B * S samples of the store read + 4 * B * S bytes written) / median device time.
+B = 64 / 256 clips of 16 000 and 80 000 samples (80 000 is beyond the resident path: the clip is gathered twice), int16 and float32
+stores.  No assertion on any time; prints the table and, with --out, writes it."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from leaf_pytorch_amd import PeakNormalization, _native  # noqa: E402
+
+DEV = "cuda:0"
+M = 3                                                   # spans per clip, as TimeMasking(num_masks=3)
+
+
+def make_case(B, S, dtype, seed):
+    g = torch.Generator().manual_seed(seed)
+    lengths = torch.randint(S + 1, 3 * S, (B,), generator=g)
+    offsets = torch.cumsum(lengths, 0) - lengths
+    n = int(lengths.sum())
+    store = (torch.randint(-32768, 32768, (n,), generator=g).to(torch.int16) if dtype == torch.int16
+             else torch.rand(n, generator=g) * 2 - 1)
+    start = (torch.rand(B, generator=g, dtype=torch.float64) * (lengths - S + 1).double()).long().clamp_(max=lengths - S)
+    gain = torch.where(torch.rand(B, generator=g) < 0.5, 10.0 ** ((torch.rand(B, generator=g) * 24 - 18) / 20), torch.ones(B))
+    span = (torch.rand(B, M, generator=g) * 0.1 * S).long()
+    t0 = (torch.rand(B, M, generator=g) * (S - span)).long()
+    plan = dict(rec_off=offsets, rec_len=lengths.to(torch.int32), start=start.to(torch.int32), pad_mode=torch.zeros(B, dtype=torch.int32),
+                gain=gain.float(), masks=torch.stack((t0, span), 2).to(torch.int32))
+    return store.to(DEV), {k: v.to(DEV) for k, v in plan.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_clips.py needs the GPU: a time taken anywhere else says nothing about it")
+    pn = PeakNormalization()
+    busy = torch.rand(8192, 8192, device=DEV)
+    busy_out = torch.empty_like(busy)
+    lines = [f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {args.rounds} timed rounds x {args.steps} calls per side after a "
+             "warm-up round; us per call: median [min, max]; device = HIP events, calls queued behind a matrix product; wall = host clock to a synchronise; GB/s = (store bytes read + 4 B S written) / median device time of the kernel",
+             f"{'store':>8} {'B':>4} {'S':>6} {'path':>9} | {'kernel device':>24} {'kernel wall':>12} {'GB/s':>7} | {'stock device':>24} "
+             f"{'stock wall':>11} | {'stock / kernel':>14}"]
+    for dtype in (torch.int16, torch.float32):
+        for B in (64, 256):
+            for S in (16000, 80000):
+                store, p = make_case(B, S, dtype, seed=B + S)
+                out = torch.empty((B, 1, S), dtype=torch.float32, device=DEV)
+                ar = torch.arange(S, device=DEV)
+                lo, hi = p["masks"][..., 0].long(), (p["masks"][..., 0] + p["masks"][..., 1]).long()
+                first = (p["rec_off"] + p["start"])[:, None]
+
+                def kernel():
+                    return _native.assemble_clips(store, p["rec_off"], p["rec_len"], p["start"], p["pad_mode"], S, p["gain"], True, p["masks"], out)
+
+                def stock():
+                    x = store[first + ar]
+                    if dtype == torch.int16:
+                        x = x.float() / 32768
+                    x = pn(x * p["gain"][:, None])
+                    for m in range(M):
+                        x = x.masked_fill((ar >= lo[:, m, None]) & (ar < hi[:, m, None]), 0.0)
+                    return x[:, None]
+
+                a, b = kernel().clone(), stock()
+                torch.cuda.synchronize()
+                if not torch.equal(a.view(torch.int32), b.contiguous().view(torch.int32)):
+                    sys.exit(f"the two sides disagree at {dtype} B={B} S={S}: nothing is timed")
+                sides = {"kernel": kernel, "stock": stock}
+                dev_us, wall_us = {k: [] for k in sides}, {k: [] for k in sides}
+                for rnd in range(args.rounds + 1):
+                    for name in (list(sides) if rnd % 2 == 0 else list(sides)[::-1]):
+                        fn = sides[name]
+                        for _ in range(3):                                    # the side's code and data warm again after the other side
+                            fn()
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        for _ in range(args.steps):
+                            fn()
+                        torch.cuda.synchronize()
+                        t1 = time.perf_counter()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        torch.mm(busy, busy, out=busy_out)                    # the device works on this while the calls below are enqueued
+                        e0.record()
+                        for _ in range(args.steps):
+                            fn()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        if rnd:                                               # round 0 warms up
+                            dev_us[name].append(e0.elapsed_time(e1) * 1e3 / args.steps)
+                            wall_us[name].append((t1 - t0) * 1e6 / args.steps)
+                fmt = lambda v: f"{statistics.median(v):9.1f} [{min(v):6.1f},{max(v):7.1f}]"
+                nbytes = B * S * store.element_size() + 4 * B * S
+                kd, sd = statistics.median(dev_us["kernel"]), statistics.median(dev_us["stock"])
+                lines.append(f"{str(dtype).replace('torch.', ''):>8} {B:>4} {S:>6} {'resident' if S <= _native.ASSEMBLE_RESIDENT_MAX else 'reread':>9} | "
+                             f"{fmt(dev_us['kernel'])} {statistics.median(wall_us['kernel']):12.1f} {nbytes / kd / 1e3:7.1f} | {fmt(dev_us['stock'])} "
+                             f"{statistics.median(wall_us['stock']):11.1f} | {sd / kd:14.2f}")
+                print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(text)
+
+
+if __name__ == "__main__":
+    main()
