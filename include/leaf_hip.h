@@ -640,6 +640,54 @@ int leaf_assemble_clips_f32(const void* store, long long store_len, int flags, i
                             const int* rec_len, const int* start, const int* pad_mode, const float* gain, int normalize,
                             const int* masks, int M, float* out, void* stream);
 
+/* The same launch with the reference's two noise transforms in it (additive: the ABI version stays 6): AddRandomNoise -- a background
+ * recording mixed in at an SNR, get_raw_transforms_v2 -- and AddGaussianNoise (leaf_supervised_transforms, simple_supervised_transforms).
+ * Both sit in front of the peak normalisation, so they cannot be appended behind leaf_assemble_clips_f32.  The arguments of that entry
+ * up to `out` come first and mean what they mean there; `stream` stays last.  Behind `out`:
+ *
+ *   noise_store     [noise_store_len] samples of the background recordings, of the SAME sample type as `store` (flags decides for both)
+ *   noise_off       [B] int64, noise_len [B] int32, noise_start [B] int32, noise_pad_mode [B] int32: clip b's noise recording and how it
+ *                   is padded and cropped to `size` -- the rule of step 1, on its own plan (the reference: PadToSize(size, 'wrap'), which
+ *                   is mode 2 here, then RandomCrop(size))
+ *   noise_coeff     [B][2] float32: c = fp32(coeff) and c' = fp32(1 - coeff), the subtraction in double -- what the reference's
+ *                   `coeff * x + (1.0 - coeff) * noise` multiplies with for a numpy float64 coeff = r / (1 + r), r = 10^(snr / 10)
+ *   gauss_amp       [B] float32 amplitudes            gauss_seed: 64 bits            gauss_stream [B] int64: one stream id per clip
+ *
+ * The noise group (noise_store .. noise_coeff) is given or NULL as a whole, and so is the Gaussian group (gauss_amp, gauss_stream);
+ * with both NULL the call IS leaf_assemble_clips_f32.  The steps, for clip b and t in [0, S):
+ *   1.  pad and crop, as above;
+ *   1a. background noise, for a clip whose clamped noise_len > 0: y = rn(rn(c v) + rn(c' n[t])), n the noise recording through step 1 --
+ *       three separately rounded fp32 operations, no fused multiply-add.  A clip with noise_len <= 0 skips the step (it does not compute
+ *       1 v + 0 n, which would change the sign of a zero);
+ *   2.  gain, as above;
+ *   2a. Gaussian noise, for gauss_amp[b] != 0: y = rn(y + rn(gauss_amp[b] z[b][t])), two separately rounded operations; amplitude 0 skips;
+ *   3., 4. peak normalisation of the result, then the masks, as above.
+ * A clip that skips 1a and 2a has the bits leaf_assemble_clips_f32 gives it.
+ *
+ * THE STREAM is exact by definition: z[b][t] depends on (gauss_seed, gauss_stream[b], t) and on nothing else -- not on B, the clip's
+ * place in the batch, size, the path, or the alignment of out.  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments
+ * 0x9E3779B9 / 0xBB67AE85) with key (lo32(seed), hi32(seed)) and counter (t >> 2, 0, lo32(stream[b]), hi32(stream[b])); its outputs
+ * r0..r3 give the normals of row elements 4 g .. 4 g + 3: u1 = ((r0 >> 8) + 1) 2^-24, u2 = (r1 >> 8) 2^-24, rho = sqrt(-2 ln u1),
+ * z0 = rho cos(2 pi u2), z1 = rho sin(2 pi u2); r2, r3 give z2, z3 the same way.  All fp32, the angle through sincospi(2 u2).  The integer
+ * part is exact; the transcendental part is the device's (within 1e-5 of the formula in double: |z| <= 5.8).
+ * leaf_gaussian_noise_f32 writes z itself, out [B][size] float32, from the same device function: the same bits.
+ *
+ * MEMORY SAFETY: the noise plan is clamped exactly as the clip plan (against noise_store_len): nothing outside either store is read,
+ * nothing outside out[B][size] is written.  Both noises are computed chunk by chunk on the registers of the plain kernel: clips of
+ * up to 32765 samples stay resident here too, longer ones compute the noise twice (the same bits both times).
+ *
+ * Alignment: noise_store as store, noise_off and gauss_stream 8 bytes, every other buffer 4.  Status, in this order, before any
+ * launch: LEAF_ERR_UNSUPPORTED as above; LEAF_ERR_NULL_POINTER (also for a group given in part); LEAF_ERR_BAD_SHAPE (also for
+ * noise_store_len < 0; leaf_gaussian_noise_f32: B < 1, size < 1); LEAF_ERR_ALIGNMENT.  out must not overlap either store. */
+int leaf_assemble_clips_noise_f32(const void* store, long long store_len, int flags, int B, int size, const long long* rec_off,
+                                  const int* rec_len, const int* start, const int* pad_mode, const float* gain, int normalize,
+                                  const int* masks, int M, float* out, const void* noise_store, long long noise_store_len,
+                                  const long long* noise_off, const int* noise_len, const int* noise_start, const int* noise_pad_mode,
+                                  const float* noise_coeff /*[B][2]*/, const float* gauss_amp, unsigned long long gauss_seed,
+                                  const long long* gauss_stream, void* stream);
+int leaf_gaussian_noise_f32(int B, int size, unsigned long long seed, const long long* stream_ids /*[B]*/, float* out /*[B][size]*/,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

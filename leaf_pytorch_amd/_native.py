@@ -97,6 +97,14 @@ _SIGNATURES = {
     # batch assembly: store, store_len, flags, B, size, rec_off, rec_len, start, pad_mode, gain, normalize, masks, M, out, stream
     "leaf_assemble_clips_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
                                 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    # ... with the noise group (noise_store, noise_store_len, noise_off, noise_len, noise_start, noise_pad_mode, noise_coeff) and the
+    # Gaussian group (gauss_amp, gauss_seed, gauss_stream) between out and stream
+    "leaf_assemble_clips_noise_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+                                      + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+                                      + [ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_void_p] * 5
+                                      + [ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_void_p]),
+    # the stream itself: B, size, seed, stream ids, out, stream
+    "leaf_gaussian_noise_f32": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "leaf_fft_tables_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "leaf_fft_prepare_tables_f32": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_size_t, ctypes.c_void_p]),
@@ -866,6 +874,7 @@ def peak_normalize(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch
 PAD_ZERO, PAD_MIN, PAD_REPLICATE, PAD_WRAP = 0, 1, 2, 3     # pad_mode of leaf_assemble_clips_f32
 PAD_MODES = {"zero": PAD_ZERO, "min": PAD_MIN, "replicate": PAD_REPLICATE, "wrap": PAD_WRAP}
 ASSEMBLE_RESIDENT_MAX = 32765    # csrc/leaf_clips.hpp (kClipResidentMax): clips up to this size stay in registers, longer ones are gathered twice
+ASSEMBLE_NOISE_RESIDENT_MAX = 32765   # ... and the cut-over of the instances with noise (kClipNoiseResidentMax): the same eight chunks per lane
 
 
 def _plan_ints(t, name: str, B: int) -> torch.Tensor:
@@ -929,19 +938,122 @@ def clip_plan(store_len: int, rec_off, rec_len, start, pad_mode, size: int, gain
     return B, rec_off, rec_len, start, pad_mode, gain, masks
 
 
+def noise_coefficients(coeff) -> torch.Tensor:
+    """The (B, 2) float32 pairs (c, c') of leaf_assemble_clips_noise_f32 from AddRandomNoise's float64 ``coeff`` = r / (1 + r):
+    c = fp32(coeff), c' = fp32(1 - coeff) with the subtraction in double -- what ``coeff * x + (1.0 - coeff) * noise`` multiplies
+    with.  A (B, 2) float32 tensor is taken as the pairs themselves."""
+    if not isinstance(coeff, torch.Tensor):
+        coeff = torch.as_tensor(coeff, dtype=torch.float64)
+    coeff = coeff.detach()
+    if coeff.dim() == 2:
+        if coeff.shape[1] != 2 or coeff.dtype != torch.float32:
+            raise ValueError(f"noise coefficients given as pairs must be a (B, 2) float32 tensor, got {tuple(coeff.shape)} {coeff.dtype}")
+        return coeff
+    if not coeff.dtype.is_floating_point:
+        raise TypeError(f"noise coefficients must be floating point, got {coeff.dtype}")
+    c = coeff.reshape(-1).double()
+    return torch.stack((c, 1.0 - c), dim=1).to(torch.float32)
+
+
+def snr_coefficients(snr_db) -> torch.Tensor:
+    """AddRandomNoise's float64 coeff = r / (1 + r), r = exp(snr ln 10 / 10), for SNRs in dB."""
+    import math
+    snr = (snr_db if isinstance(snr_db, torch.Tensor) else torch.as_tensor(snr_db, dtype=torch.float64)).detach().double()
+    r = torch.exp(snr * (math.log(10.0) / 10.0))
+    return r / (1.0 + r)
+
+
+def noise_plan(noise_store_len: int, noise_off, noise_len, noise_start, noise_pad_mode, coeff, size: int, B: int):
+    """The noise group of ``assemble_clips`` checked like ``clip_plan`` checks the clips' (ValueError for what the host can see on
+    the CPU; a device-side array is clamped by the kernel) -- except that ``noise_len`` 0 is the way to leave a clip unmixed.
+    Returns (noise_off, noise_len, noise_start, noise_pad_mode, coeff (B, 2) float32)."""
+    noise_len, noise_start = (t if isinstance(t, torch.Tensor) else torch.as_tensor(t) for t in (noise_len, noise_start))
+    if noise_len.device.type == "cpu" and noise_start.device.type == "cpu" and noise_len.numel() == noise_start.numel():
+        noise_start = torch.where(noise_len.reshape(-1) > 0, noise_start.reshape(-1), torch.zeros_like(noise_start.reshape(-1)))   # unmixed: no start to check
+    nB, noise_off, noise_len, noise_start, noise_pad_mode, _, _ = clip_plan(noise_store_len, noise_off, noise_len, noise_start, noise_pad_mode, size)
+    if nB != B:
+        raise ValueError(f"the noise plan has {nB} entries, expected one per clip ({B})")
+    coeff = noise_coefficients(coeff)
+    if coeff.shape[0] != B:
+        raise ValueError(f"the noise coefficients have {coeff.shape[0]} entries, expected one per clip ({B})")
+    if coeff.device.type == "cpu" and B and not bool(((coeff >= 0) & (coeff <= 1)).all()):
+        raise ValueError("a noise coefficient lies outside [0, 1]")
+    return noise_off, noise_len, noise_start, noise_pad_mode, coeff
+
+
+def _gaussian_plan(gaussian, B: int):
+    amp, seed, stream = gaussian
+    if not isinstance(amp, torch.Tensor):
+        amp = torch.as_tensor(amp, dtype=torch.float32)
+    amp = amp.detach().reshape(-1)
+    if amp.numel() != B:
+        raise ValueError(f"the Gaussian amplitudes have {amp.numel()} entries, expected one per clip ({B})")
+    if amp.dtype != torch.float32:
+        raise RuntimeError(f"the Gaussian amplitudes must be float32, got {amp.dtype}")
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"the seed must fit 64 unsigned bits, got {seed}")
+    return amp, seed, _plan_ints(stream, "stream", B)
+
+
+def gaussian_noise(B: int, size: int, seed: int, stream, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """The library's normal stream as a (B, size) float32 tensor (leaf_gaussian_noise_f32): ``out[b][t] = z(seed, stream[b], t)``, the
+    values ``assemble_clips(..., gaussian=(amp, seed, stream))`` scales and adds -- Philox4x32-10 and Box-Muller as include/leaf_hip.h
+    states them; a row depends on nothing but its stream id and the seed.  ``stream``: B int64 ids, on the device or the CPU."""
+    B, size, seed = int(B), int(size), int(seed)
+    if B < 0 or not 1 <= size < CALL_SAMPLES:
+        raise ValueError(f"B must be >= 0 and size in [1, 2^31), got {B}, {size}")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"the seed must fit 64 unsigned bits, got {seed}")
+    stream = _plan_ints(stream, "stream", B)
+    if out is not None:
+        dev = out.device
+    elif device is not None:
+        dev = torch.device(device)
+    else:
+        dev = stream.device if stream.device.type != "cpu" else torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
+    if out is not None:
+        _check_out(out, (B, size), torch.float32, dev)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("gaussian_noise runs only on an AMD GPU (HIP device); there is no CPU fallback")
+    if out is None:
+        out = torch.empty((B, size), dtype=torch.float32, device=dev)
+    if B:
+        _call(dev, "leaf_gaussian_noise_f32", B, size, seed, stream.to(device=dev, dtype=torch.int64).contiguous(), out)
+    return out
+
+
 def assemble_clips(store: torch.Tensor, rec_off, rec_len, start, pad_mode, size: int, gain=None, normalize: bool = True, masks=None,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, noise=None, gaussian=None) -> torch.Tensor:
     """The batch (B, 1, size), float32, from a packed sample store in one launch (leaf_assemble_clips_f32, where the semantics are
     stated): per clip b the recording ``store[rec_off[b] : rec_off[b] + rec_len[b]]`` is padded to ``size`` if it is shorter
     (``pad_mode[b]``: PAD_ZERO / PAD_MIN / PAD_REPLICATE / PAD_WRAP, split left = padding // 2), cropped at ``start[b]``, multiplied by
     ``gain[b]``, peak-normalised (``normalize``: the bits of ``peak_normalize`` on the clip so far) and zeroed inside the ``masks``
     (B, M, 2) spans (t0, n).  ``store``: 1-D float32 or int16 PCM (a sample v means v / 32768) on a HIP device.  The plan arrays may
     live on either side: on the CPU they are validated (``clip_plan``) and copied over, on the device they are used as they are and
-    clamped by the kernel."""
+    clamped by the kernel.
+
+    ``noise`` = (noise_store, noise_off, noise_len, noise_start, noise_pad_mode, coeff) mixes a background recording into every clip
+    whose ``noise_len`` is above 0, in front of the gain: ``coeff * v + (1 - coeff) * n`` in AddRandomNoise's fp32 rounding, ``n`` the
+    noise recording padded and cropped to ``size`` by its own plan (``noise_plan`` / ``noise_coefficients``; the store of the clips'
+    dtype and device).  ``gaussian`` = (amp (B,) float32, seed, stream (B,) int64) adds ``amp[b] * z(seed, stream[b], t)`` behind the
+    gain (``gaussian_noise`` returns z); amplitude 0 leaves a clip alone.  Either makes the call leaf_assemble_clips_noise_f32 -- still
+    one launch; with neither the call is the one it always was."""
     if not isinstance(store, torch.Tensor) or store.dim() != 1 or store.dtype not in (torch.float32, torch.int16):
         raise RuntimeError("assemble_clips: store must be a 1-D float32 or int16 tensor")
     size = int(size)
     B, rec_off, rec_len, start, pad_mode, gain, masks = clip_plan(store.numel(), rec_off, rec_len, start, pad_mode, size, gain, masks)
+    if noise is not None:
+        nstore = noise[0]
+        if not isinstance(nstore, torch.Tensor) or nstore.dim() != 1:
+            raise TypeError("assemble_clips: the noise store must be a 1-D tensor")
+        if nstore.dtype != store.dtype:
+            raise TypeError(f"assemble_clips: the noise store is {nstore.dtype}, the clip store {store.dtype}: both int16 PCM or both float32")
+        if nstore.device != store.device:
+            raise ValueError(f"assemble_clips: the noise store is on {nstore.device}, the clip store on {store.device}")
+        noise = (nstore,) + tuple(noise_plan(nstore.numel(), *noise[1:], size, B))
+    if gaussian is not None:
+        gaussian = _gaussian_plan(gaussian, B)
     require_hip(store, "assemble_clips")
     dev = store.device
     store = store.detach().contiguous()
@@ -955,8 +1067,19 @@ def assemble_clips(store: torch.Tensor, rec_off, rec_len, start, pad_mode, size:
     rec_len, start, pad_mode = (t.to(device=dev, dtype=torch.int32).contiguous() for t in (rec_len, start, pad_mode))
     gain = None if gain is None else gain.to(device=dev).contiguous()
     masks = None if masks is None else masks.to(device=dev, dtype=torch.int32).contiguous()
-    _call(dev, "leaf_assemble_clips_f32", store, store.numel(), FLAG_X_PCM16 if store.dtype == torch.int16 else 0, B, size,
-          rec_off, rec_len, start, pad_mode, gain, int(bool(normalize)), masks, 0 if masks is None else masks.shape[1], out)
+    head = (store, store.numel(), FLAG_X_PCM16 if store.dtype == torch.int16 else 0, B, size,
+            rec_off, rec_len, start, pad_mode, gain, int(bool(normalize)), masks, 0 if masks is None else masks.shape[1], out)
+    if noise is None and gaussian is None:
+        _call(dev, "leaf_assemble_clips_f32", *head)
+        return out
+    ngroup, ggroup = (None, 0, None, None, None, None, None), (None, 0, None)
+    if noise is not None:
+        nstore = noise[0].detach().contiguous()
+        ngroup = (nstore, nstore.numel(), noise[1].to(device=dev, dtype=torch.int64).contiguous()) + tuple(
+            t.to(device=dev, dtype=torch.int32).contiguous() for t in noise[2:5]) + (noise[5].to(device=dev).contiguous(),)
+    if gaussian is not None:
+        ggroup = (gaussian[0].to(device=dev).contiguous(), gaussian[1], gaussian[2].to(device=dev, dtype=torch.int64).contiguous())
+    _call(dev, "leaf_assemble_clips_noise_f32", *head, *ngroup, *ggroup)
     return out
 
 

@@ -1,4 +1,4 @@
-// inst_clips.hip -- batch assembly from a packed sample store: the kernel of leaf_clips.hpp and its C-ABI entry.
+// inst_clips.hip -- batch assembly from a packed sample store: the kernels of leaf_clips.hpp and their C-ABI entries.
 // One of the translation units of libleaf_hip.so; it shares nothing with the others but the header's declarations.
 #define LEAF_INST_TU 1
 #include "leaf_clips.hpp"
@@ -22,6 +22,65 @@ int leaf_assemble_clips_f32(const void* store, long long store_len, int flags, i
     p.S = size; p.M = M; p.normalize = normalize != 0;
     if (pcm) hipLaunchKernelGGL(assemble_clips_kernel<true>, dim3(B), dim3(kClipThreads), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(assemble_clips_kernel<false>, dim3(B), dim3(kClipThreads), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
+    return LEAF_OK;
+}
+
+// ... with background noise at an SNR and / or Gaussian noise in the same launch.  Each group is there or NULL as a whole (a
+// partly given group is LEAF_ERR_NULL_POINTER); without both the call is the entry above.
+int leaf_assemble_clips_noise_f32(const void* store, long long store_len, int flags, int B, int size,
+                                  const long long* rec_off, const int* rec_len, const int* start, const int* pad_mode,
+                                  const float* gain, int normalize, const int* masks, int M, float* out,
+                                  const void* noise_store, long long noise_store_len, const long long* noise_off, const int* noise_len,
+                                  const int* noise_start, const int* noise_pad_mode, const float* noise_coeff,
+                                  const float* gauss_amp, unsigned long long gauss_seed, const long long* gauss_stream, void* stream) {
+    const bool any_noise = noise_store || noise_off || noise_len || noise_start || noise_pad_mode || noise_coeff;
+    const bool any_gauss = gauss_amp || gauss_stream;
+    if (!any_noise && !any_gauss)
+        return leaf_assemble_clips_f32(store, store_len, flags, B, size, rec_off, rec_len, start, pad_mode, gain, normalize, masks, M, out, stream);
+    if (flags & ~LEAF_FLAG_X_PCM16) return LEAF_ERR_UNSUPPORTED;
+    if (!store || !rec_off || !rec_len || !start || !pad_mode || !out) return LEAF_ERR_NULL_POINTER;
+    if (any_noise && !(noise_store && noise_off && noise_len && noise_start && noise_pad_mode && noise_coeff)) return LEAF_ERR_NULL_POINTER;
+    if (any_gauss && !(gauss_amp && gauss_stream)) return LEAF_ERR_NULL_POINTER;
+    if (B < 1 || size < 1 || store_len < 0 || M < 0 || (M > 0 && !masks) || (any_noise && noise_store_len < 0)) return LEAF_ERR_BAD_SHAPE;
+    const bool pcm = (flags & LEAF_FLAG_X_PCM16) != 0;
+    auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (misaligned(store, pcm ? 1u : 3u) || misaligned(rec_off, 7u) || misaligned(rec_len, 3u) || misaligned(start, 3u) ||
+        misaligned(pad_mode, 3u) || misaligned(gain, 3u) || misaligned(masks, 3u) || misaligned(out, 3u) ||
+        misaligned(noise_store, pcm ? 1u : 3u) || misaligned(noise_off, 7u) || misaligned(noise_len, 3u) || misaligned(noise_start, 3u) ||
+        misaligned(noise_pad_mode, 3u) || misaligned(noise_coeff, 3u) || misaligned(gauss_amp, 3u) || misaligned(gauss_stream, 7u))
+        return LEAF_ERR_ALIGNMENT;
+    ClipParams p{};
+    p.store = store; p.store_len = store_len;
+    p.rec_off = rec_off; p.rec_len = rec_len; p.start = start; p.pad_mode = pad_mode;
+    p.gain = gain; p.masks = M > 0 ? masks : nullptr; p.out = out;
+    p.S = size; p.M = M; p.normalize = normalize != 0;
+    ClipNoiseParams np{};
+    np.store = noise_store; np.store_len = noise_store_len;
+    np.rec_off = noise_off; np.rec_len = noise_len; np.start = noise_start; np.pad_mode = noise_pad_mode; np.coeff = noise_coeff;
+    np.amp = gauss_amp; np.stream = gauss_stream; np.seed = gauss_seed;
+    const dim3 grid(B), block(kClipThreads);
+    const hipStream_t st = (hipStream_t)stream;
+    switch ((pcm ? 4 : 0) | (any_noise ? 2 : 0) | (any_gauss ? 1 : 0)) {
+        case 1: hipLaunchKernelGGL((assemble_clips_noise_kernel<false, false, true>), grid, block, 0, st, p, np); break;
+        case 2: hipLaunchKernelGGL((assemble_clips_noise_kernel<false, true, false>), grid, block, 0, st, p, np); break;
+        case 3: hipLaunchKernelGGL((assemble_clips_noise_kernel<false, true, true>), grid, block, 0, st, p, np); break;
+        case 5: hipLaunchKernelGGL((assemble_clips_noise_kernel<true, false, true>), grid, block, 0, st, p, np); break;
+        case 6: hipLaunchKernelGGL((assemble_clips_noise_kernel<true, true, false>), grid, block, 0, st, p, np); break;
+        default: hipLaunchKernelGGL((assemble_clips_noise_kernel<true, true, true>), grid, block, 0, st, p, np); break;
+    }
+    if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
+    return LEAF_OK;
+}
+
+// the stream on its own: z[b][t] for t in [0, size), the values the entry above adds (times gauss_amp[b])
+int leaf_gaussian_noise_f32(int B, int size, unsigned long long seed, const long long* stream_ids, float* out, void* stream) {
+    if (!stream_ids || !out) return LEAF_ERR_NULL_POINTER;
+    if (B < 1 || size < 1) return LEAF_ERR_BAD_SHAPE;
+    const int tiles = (int)((((long long)size + 3) / 4 + 255) / 256);
+    if ((long long)B * tiles > 0x7fffffffll) return LEAF_ERR_BAD_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(stream_ids) & 7u) || (reinterpret_cast<uintptr_t>(out) & 3u)) return LEAF_ERR_ALIGNMENT;
+    hipLaunchKernelGGL(gaussian_noise_kernel, dim3((unsigned)(B * tiles)), dim3(256), 0, (hipStream_t)stream, size, tiles, seed, stream_ids, out);
     if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
     return LEAF_OK;
 }

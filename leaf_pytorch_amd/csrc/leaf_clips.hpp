@@ -29,6 +29,21 @@
 // Memory safety: the plan is device memory the host never sees, so the kernel clamps it (rec_off into [0, store_len], rec_len
 // into [0, store_len - rec_off], start into [0, max(L, S) - S], an unknown pad mode to 0): no plan reads outside the store or
 // writes outside out[b].
+//
+// The noise instances (leaf_assemble_clips_noise_f32: assemble_clips_noise_kernel<PCM, NOISE, GAUSS>).  AddRandomNoise mixes a second recording, taken
+// through the same pad-and-crop rule by a ClipView of its own, in front of the gain: rn(rn(c v) + rn(c' n)); AddGaussianNoise adds
+// rn(a z) behind the gain, z from the counter-based stream below.  Both are per-chunk steps on the registers of the tile: a noise
+// chunk, or a group of normals, is consumed into v[u] before the next one is produced, so the resident path keeps its eight chunks
+// (kClipNoiseResidentMax = kClipResidentMax).  Neither may contract into an fma (clip_mix / clip_add_scaled switch contraction off
+// as mix_load does).  The re-reading path computes both twice, from the same inputs by the same code: the same bits.
+//
+// The stream: z[b][t] is a function of (seed, stream[b], t) alone.  Philox4x32-10, key = the seed's two halves, counter =
+// (t >> 2, 0, stream[b]'s two halves); its four words give the normals of row elements 4 g .. 4 g + 3 by Box-Muller in fp32
+// (gauss_pair).  The chunk grid is aligned in `out`, not in the row: a chunk at shift != 0 straddles the groups q - 1 and q and
+// takes its normals from two Philox calls, evaluating only the pairs it uses (the shift is uniform over the workgroup).
+//
+// The two plain instances keep the kernel text they had (assemble_clips_kernel below, untouched: the same instructions as before the
+// noise instances existed); assemble_clips_noise_kernel restates the body over clip_view / clip_min_pass.
 #pragma once
 #include "leaf_common.hpp"
 
@@ -37,6 +52,9 @@ namespace {
 constexpr int kClipThreads = 1024;
 constexpr int kClipChunks = 8;                                            // float4 chunks a lane keeps on the resident path
 constexpr int kClipResidentMax = kClipChunks * 4 * kClipThreads - 3;     // 32 765: the cut-over to the re-reading path
+
+constexpr int kClipNoiseChunks = 8;                                       // ... and what a noise instance keeps
+constexpr int kClipNoiseResidentMax = kClipNoiseChunks * 4 * kClipThreads - 3;   // 32 765: the noise instances' cut-over
 
 typedef short s16x4u __attribute__((ext_vector_type(4), aligned(2)));    // 8-byte load at 2-byte alignment
 
@@ -58,6 +76,26 @@ struct ClipView {
     float padv;                   // the constant outside the recording: 0, or min(r) for mode 1
     float g;
     bool has_gain;
+};
+
+// The noise transforms of leaf_assemble_clips_noise_f32 (a second kernel argument: the plain instances do not carry it)
+struct ClipNoiseParams {
+    const void* store;            // the noise recordings, of the clip store's sample type; null: no clip is mixed
+    long long store_len;
+    const long long* rec_off;     // [B]
+    const int *rec_len, *start, *pad_mode;   // [B]
+    const float* coeff;           // [B][2]: c, c'
+    const float* amp;             // [B] Gaussian amplitudes, or null
+    const long long* stream;      // [B]
+    unsigned long long seed;
+};
+
+// ... and one clip's share of it (uniform over the workgroup)
+struct ClipNoiseView {
+    ClipView n;                   // the noise recording, clamped as the clip's; L == 0: the clip is not mixed
+    float c, cn;
+    float amp;                    // 0: no Gaussian noise
+    unsigned k0, k1, s0, s1;      // Philox key (the seed) and counter words 2, 3 (the clip's stream)
 };
 
 template <bool PCM> __device__ __forceinline__ float clip_load(const void* store, long long i) {
@@ -143,10 +181,97 @@ template <class I> __device__ __forceinline__ void clip_chunk_store(float* ob, i
     }
 }
 
+// ---- the random stream (include/leaf_hip.h: leaf_gaussian_noise_f32) ---------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped between them
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&r)[4]) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+// Two normals from two words: u1 = ((ra >> 8) + 1) 2^-24 in (0, 1], u2 = (rb >> 8) 2^-24 in [0, 1) -- both exact in fp32 --
+// rho = sqrt(-2 ln u1), (zc, zs) = rho (cos, sin)(2 pi u2).  The angle goes in as 2 u2 (exact) through sincospi: no rounded 2 pi u2.
+// Contraction is off so that every kernel this is inlined into gives the same bits.
+__device__ __forceinline__ void gauss_pair(unsigned ra, unsigned rb, float& zc, float& zs) {
+#pragma clang fp contract(off)
+    const float u1 = (float)((ra >> 8) + 1u) * 0x1p-24f;
+    const float rho = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincospif((float)(rb >> 8) * 0x1p-23f, &sn, &cs);
+    zc = rho * cs;
+    zs = rho * sn;
+}
+
+// the four normals of the row elements 4 g .. 4 g + 3
+__device__ __forceinline__ void gauss_group(unsigned k0, unsigned k1, unsigned s0, unsigned s1, unsigned g, float (&z)[4]) {
+    unsigned r[4];
+    philox4x32_10(g, 0u, s0, s1, k0, k1, r);
+    gauss_pair(r[0], r[1], z[0], z[1]);
+    gauss_pair(r[2], r[3], z[2], z[3]);
+}
+
+// rn(rn(v c) + rn(n cn)): AddRandomNoise's `coeff * x + (1.0 - coeff) * noise`, three separately rounded operations
+__device__ __forceinline__ float clip_mix(float v, float c, float n, float cn) {
+#pragma clang fp contract(off)
+    const float a = v * c;
+    const float b = n * cn;
+    return a + b;
+}
+
+// rn(y + rn(a z)): AddGaussianNoise's `x + amplitude * noise`
+__device__ __forceinline__ float clip_add_scaled(float y, float a, float z) {
+#pragma clang fp contract(off)
+    const float w = a * z;
+    return y + w;
+}
+
+// The noise recording's samples of the chunk at row elements t0 .. t0 + 3, mixed into v.  (Elements outside the row: both sides are 0.)
+template <bool PCM, class I> __device__ __forceinline__ void clip_chunk_mix(const void* nstore, const ClipNoiseView& a, int S, I t0, float (&v)[4]) {
+    float n[4];
+    bool exact = false;
+    if (a.n.L >= 4) exact = clip_chunk_load<PCM, I>(nstore, a.n, S, t0, n);
+    if (!exact) clip_chunk_gather<PCM, I>(nstore, a.n, S, t0, n);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = clip_mix(v[e], a.c, n[e], a.cn);
+}
+
+// The normals of chunk q (row elements 4 q - shift ..), scaled and added to v.  The chunk's elements are the entries 4 - shift ..
+// 7 - shift of the eight normals of the groups q - 1 (words ra) and q (words rb).  An even shift keeps Box-Muller's pairs together
+// (two evaluations); an odd one takes the sine of one pair, a whole pair and the cosine of a third.  The shift is uniform over the
+// workgroup, so the words are picked by scalar conditions and the third evaluation sits in a uniform branch.  Elements outside the
+// row stay as they are: zeros that must leave the peak alone.
+template <class I> __device__ __forceinline__ void clip_chunk_gauss(const ClipNoiseView& a, int S, I q, int shift, float (&v)[4]) {
+    unsigned ra[4] = {0u, 0u, 0u, 0u}, rb[4];
+    philox4x32_10((unsigned)q, 0u, a.s0, a.s1, a.k0, a.k1, rb);
+    if (shift != 0) philox4x32_10((unsigned)(q - 1), 0u, a.s0, a.s1, a.k0, a.k1, ra);   // (q == 0: its elements lie in front of the row)
+    const bool s0 = shift == 0, s3 = shift == 3, odd = (shift & 1) != 0;
+    float c1, n1, c2, n2, z[4];
+    gauss_pair(s0 ? rb[0] : (s3 ? ra[0] : ra[2]), s0 ? rb[1] : (s3 ? ra[1] : ra[3]), c1, n1);
+    gauss_pair(s0 ? rb[2] : (s3 ? ra[2] : rb[0]), s0 ? rb[3] : (s3 ? ra[3] : rb[1]), c2, n2);
+    if (odd) {
+        float c3, n3;
+        gauss_pair(s3 ? rb[0] : rb[2], s3 ? rb[1] : rb[3], c3, n3);
+        z[0] = n1; z[1] = c2; z[2] = n2; z[3] = c3;
+    } else {
+        z[0] = c1; z[1] = n1; z[2] = c2; z[3] = n2;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const I t = 4 * q - shift + e;
+        if (t >= 0 && t < (I)S) v[e] = clip_add_scaled(v[e], a.amp, z[e]);
+    }
+}
+
 // A lane's tile: the chunks q0, q0 + 1024, ... (U of them), gathered and multiplied by the gain; the lane's share of the peak comes
-// back.  Chunks behind the row are zeros.
-template <bool PCM, class I, int U>
-__device__ __forceinline__ float clip_tile_load(const void* store, const ClipView& c, int S, int shift, I q0, I nchunks, float (&v)[U][4]) {
+// back.  Chunks behind the row are zeros.  NOISE / GAUSS: the two noise steps, around the gain, chunk by chunk.
+template <bool PCM, class I, int U, bool NOISE = false, bool GAUSS = false>
+__device__ __forceinline__ float clip_tile_load(const void* store, const ClipView& c, int S, int shift, I q0, I nchunks, float (&v)[U][4],
+                                                const void* nstore = nullptr, const ClipNoiseView* a = nullptr) {
     bool exact[U];
     if (c.L >= 4) {
 #pragma unroll
@@ -164,9 +289,17 @@ __device__ __forceinline__ float clip_tile_load(const void* store, const ClipVie
     float m = 0.0f;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
+        if constexpr (NOISE) {
+            const I q = q0 + (I)u * kClipThreads;
+            if (a->n.L > 0 && q < nchunks) clip_chunk_mix<PCM, I>(nstore, *a, S, 4 * q - shift, v[u]);
+        }
         if (c.has_gain) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[u][e] = v[u][e] * c.g;
+        }
+        if constexpr (GAUSS) {
+            const I q = q0 + (I)u * kClipThreads;
+            if (a->amp != 0.0f && q < nchunks) clip_chunk_gauss<I>(*a, S, q, shift, v[u]);
         }
         m = clip_chunk_peak(m, v[u]);
     }
@@ -256,6 +389,105 @@ __global__ __launch_bounds__(kClipThreads) void assemble_clips_kernel(const Clip
         clip_tile_load<PCM, long long, kU>(p.store, c, S, shift, q0, nchunks, v);
         clip_tile_finish<long long, kU>(p, b, shift, q0, nchunks, peak, v, ob);
     }
+}
+
+// One clip's plan, clamped (the header's MEMORY SAFETY rule; the noise recording's plan goes through the same code)
+__device__ __forceinline__ ClipView clip_view(const long long* rec_off, const int* rec_len, const int* start, const int* pad_mode,
+                                              long long store_len, int b, int S) {
+    ClipView c;
+    const long long off = rec_off[b], room = store_len;
+    c.off = off < 0 ? 0 : (off > room ? room : off);
+    const long long len = rec_len[b], most = room - c.off;
+    c.L = (int)(len < 0 ? 0 : (len > most ? most : len));
+    const int st = start[b], mode = pad_mode[b];
+    if (c.L > S) {                                                        // a crop: the window [start, start + S) of the recording, no padding
+        c.off += st < 0 ? 0 : (st > c.L - S ? c.L - S : st);
+        c.L = S;
+    }                                                                     // (otherwise max(L, S) - S = 0: the only start is 0)
+    c.left = (S - c.L) / 2;
+    c.mode = (c.L > 0 && mode >= 0 && mode <= 3) ? mode : 0;
+    c.padv = 0.0f;
+    c.has_gain = false;
+    c.g = 1.0f;
+    return c;
+}
+
+// PadToSize 'constant': the recording's minimum, for a recording that is padded in that mode
+template <bool PCM> __device__ __forceinline__ void clip_min_pass(const void* store, ClipView& c, int S, float* red) {
+    if (c.mode == 1 && c.L < S) {
+        float mn = INFINITY;
+        for (int i = threadIdx.x; i < c.L; i += kClipThreads) mn = fminf(mn, clip_load<PCM>(store, c.off + i));   // (L < S: i + 1024 fits)
+        c.padv = clip_block_reduce<true>(mn, red);
+    }
+}
+
+// leaf_assemble_clips_noise_f32: the kernel above with one or both noise steps (at least one of NOISE, GAUSS is set)
+template <bool PCM, bool NOISE, bool GAUSS>
+__global__ __launch_bounds__(kClipThreads) void assemble_clips_noise_kernel(const ClipParams p, const ClipNoiseParams np) {
+    __shared__ float red[kClipThreads / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, S = p.S;
+    float* ob = p.out + (size_t)b * S;
+
+    ClipView c = clip_view(p.rec_off, p.rec_len, p.start, p.pad_mode, p.store_len, b, S);
+    c.has_gain = p.gain != nullptr;
+    c.g = c.has_gain ? p.gain[b] : 1.0f;
+    clip_min_pass<PCM>(p.store, c, S, red);
+    ClipNoiseView a{};
+    if constexpr (NOISE) {
+        a.n = clip_view(np.rec_off, np.rec_len, np.start, np.pad_mode, np.store_len, b, S);
+        a.c = np.coeff[2 * b];
+        a.cn = np.coeff[2 * b + 1];
+        clip_min_pass<PCM>(np.store, a.n, S, red);
+    }
+    if constexpr (GAUSS) {
+        const unsigned long long st = (unsigned long long)np.stream[b];
+        a.amp = np.amp[b];
+        a.k0 = (unsigned)np.seed; a.k1 = (unsigned)(np.seed >> 32);
+        a.s0 = (unsigned)st; a.s1 = (unsigned)(st >> 32);
+    }
+    const int shift = (int)((reinterpret_cast<uintptr_t>(ob) >> 2) & 3);  // row elements the first aligned chunk lacks
+
+    constexpr int kResident = kClipNoiseChunks;
+    if (S <= kClipNoiseResidentMax) {                          // one tile per lane holds the clip
+        const int nchunks = (S + shift + 3) >> 2;
+        float v[kResident][4];
+        const float m = clip_tile_load<PCM, int, kResident, NOISE, GAUSS>(p.store, c, S, shift, tid, nchunks, v, np.store, &a);
+        const float peak = p.normalize ? clip_block_reduce<false>(m, red) : 0.0f;
+        clip_tile_finish<int, kResident>(p, b, shift, tid, nchunks, peak, v, ob);
+        return;
+    }
+
+    constexpr int kU = 4;                                                 // chunks in flight per lane on the re-reading path
+    const long long nchunks = ((long long)S + shift + 3) >> 2;
+    float peak = 0.0f;
+    if (p.normalize) {
+        float m = 0.0f;
+        for (long long q0 = tid; q0 < nchunks; q0 += kU * kClipThreads) {
+            float v[kU][4];
+            m = fmaxf(m, clip_tile_load<PCM, long long, kU, NOISE, GAUSS>(p.store, c, S, shift, q0, nchunks, v, np.store, &a));
+        }
+        peak = clip_block_reduce<false>(m, red);
+    }
+    for (long long q0 = tid; q0 < nchunks; q0 += kU * kClipThreads) {
+        float v[kU][4];
+        clip_tile_load<PCM, long long, kU, NOISE, GAUSS>(p.store, c, S, shift, q0, nchunks, v, np.store, &a);
+        clip_tile_finish<long long, kU>(p, b, shift, q0, nchunks, peak, v, ob);
+    }
+}
+
+// leaf_gaussian_noise_f32: z[b][t] as [B][size], one lane per group of four; grid B * tiles, tiles = ceil(ceil(size / 4) / 256)
+__global__ __launch_bounds__(256) void gaussian_noise_kernel(int size, int tiles, unsigned long long seed, const long long* stream, float* out) {
+    const int b = blockIdx.x / tiles;
+    const unsigned g = (unsigned)(blockIdx.x % tiles) * 256u + threadIdx.x;
+    const long long t0 = 4ll * g;
+    if (t0 >= size) return;
+    const unsigned long long st = (unsigned long long)stream[b];
+    float z[4];
+    gauss_group((unsigned)seed, (unsigned)(seed >> 32), (unsigned)st, (unsigned)(st >> 32), g, z);
+    float* o = out + (size_t)b * size + t0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (t0 + e < size) o[e] = z[e];
 }
 
 }  // namespace

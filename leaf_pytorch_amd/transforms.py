@@ -82,8 +82,13 @@ class PackedClips:
     run per clip on the CPU there.  The draws are the caller's (``ClipSampler`` makes them as the reference pipelines do); this class
     applies them.  The result is the float32 ``(B, 1, size)`` batch ``Leaf.forward`` and ``Leaf.forward_mixup`` take.
 
+    The two noise transforms ride in the same launch (``assemble(..., noise=..., gaussian=...)`` -> leaf_assemble_clips_noise_f32):
+    AddRandomNoise, a background recording from a second ``PackedClips`` mixed in at an SNR in front of the gain, and
+    AddGaussianNoise, the library's own counter-based normal stream (``_native.gaussian_noise``) scaled and added behind it -- both
+    in front of the peak normalisation, as in the reference's pipelines.
+
     One workgroup assembles one clip: a batch of a few very long clips uses a few CUs (splitting a clip over workgroups is not
-    built).  Not built either: bfloat16 stores and outputs in anything but float32."""
+    built).  Not built either: bfloat16 stores, outputs in anything but float32, a noise store of another dtype than the clips'."""
 
     def __init__(self, recordings, device=None):
         recs = [r if isinstance(r, torch.Tensor) else torch.as_tensor(r) for r in recordings]
@@ -129,24 +134,62 @@ class PackedClips:
         t = v if isinstance(v, torch.Tensor) else torch.as_tensor(v, dtype=torch.int64)
         return t.reshape(1).expand(B) if t.dim() == 0 else t
 
-    def assemble(self, index, start, size: int, pad_mode="zero", gain=None, normalize: bool = True, masks=None, out=None) -> torch.Tensor:
+    def _records(self, index, what: str = "index"):
+        """(B, rec_off, rec_len) of the recordings ``index`` on the side the index lives on (validated on the CPU)."""
+        index = (index if isinstance(index, torch.Tensor) else torch.as_tensor(index, dtype=torch.int64)).reshape(-1)
+        if index.dtype.is_floating_point or index.dtype == torch.bool:
+            raise TypeError(f"{what} must be an integer tensor or sequence, got {index.dtype}")
+        if index.device.type == "cpu":
+            if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(self)):
+                raise ValueError(f"{what} holds a recording outside [0, {len(self)})")
+            return index.numel(), self.offsets_host[index.long()], self.lengths_host[index.long()]
+        return index.numel(), self.offsets[index.long()], self.lengths[index.long()]
+
+    def _noise(self, noise, B: int):
+        """``assemble``'s noise tuple as the noise group of ``_native.assemble_clips``."""
+        if len(noise) not in (4, 5):
+            raise ValueError("noise must be (noise_clips, noise_index, noise_start, snr_db_or_coeff[, pad_mode])")
+        nclips, nindex, nstart, level = noise[:4]
+        pad_mode = noise[4] if len(noise) == 5 else "replicate"
+        if not isinstance(nclips, PackedClips):
+            raise TypeError("noise_clips must be a PackedClips")
+        if nclips.store.dtype != self.store.dtype:
+            raise TypeError(f"noise_clips holds {nclips.store.dtype} samples, the clips {self.store.dtype}: both int16 PCM or both float32")
+        if nclips.store.device != self.store.device:
+            raise ValueError(f"noise_clips is on {nclips.store.device}, the clips on {self.store.device}")
+        nindex = (nindex if isinstance(nindex, torch.Tensor) else torch.as_tensor(nindex, dtype=torch.int64)).reshape(-1)
+        if nindex.dtype.is_floating_point or nindex.dtype == torch.bool:
+            raise TypeError(f"noise_index must be an integer tensor or sequence, got {nindex.dtype}")
+        if nindex.numel() != B:
+            raise ValueError(f"noise_index has {nindex.numel()} entries, expected one per clip ({B})")
+        mixed = nindex >= 0                                                    # a negative entry: the clip gets no noise
+        _, noff, nlen = nclips._records(nindex.clamp(min=0), "noise_index")
+        nlen = torch.where(mixed.to(nlen.device), nlen, torch.zeros_like(nlen))
+        if not isinstance(level, torch.Tensor):
+            level = torch.as_tensor(level, dtype=torch.float64)
+        if level.dim() == 0:
+            level = level.reshape(1).expand(B)
+        coeff = level if level.dim() == 2 else _native.snr_coefficients(level)
+        return (nclips.store, noff, nlen, self._per_clip(nstart, B), self._per_clip(pad_mode, B, _native.PAD_MODES), coeff)
+
+    def assemble(self, index, start, size: int, pad_mode="zero", gain=None, normalize: bool = True, masks=None, out=None,
+                 noise=None, gaussian=None) -> torch.Tensor:
         """The batch of the recordings ``index`` (any order, repeats allowed): clip b is recording ``index[b]`` padded by
         ``pad_mode`` ("zero" / "min" / "replicate" / "wrap" or 0..3; one for the batch or one per clip) when it is shorter than
         ``size``, cropped at ``start[b]`` in [0, max(L, size) - size], then ``gain``, peak normalisation and ``masks`` as in
         ``_native.assemble_clips``.  An ``index`` / plan on the CPU is validated (ValueError); on the device it is used unseen and
-        the kernel clamps what it finds."""
-        index = (index if isinstance(index, torch.Tensor) else torch.as_tensor(index, dtype=torch.int64)).reshape(-1)
-        if index.dtype.is_floating_point or index.dtype == torch.bool:
-            raise TypeError(f"index must be an integer tensor or sequence, got {index.dtype}")
-        B = index.numel()
-        if index.device.type == "cpu":
-            if B and (int(index.min()) < 0 or int(index.max()) >= len(self)):
-                raise ValueError(f"index holds a recording outside [0, {len(self)})")
-            rec_off, rec_len = self.offsets_host[index.long()], self.lengths_host[index.long()]
-        else:
-            rec_off, rec_len = self.offsets[index.long()], self.lengths[index.long()]
+        the kernel clamps what it finds.
+
+        ``noise`` = (noise_clips, noise_index, noise_start, snr_db_or_coeff, pad_mode="replicate"): clip b is mixed with recording
+        ``noise_index[b]`` of the ``PackedClips`` ``noise_clips`` (same dtype and device; a negative index leaves the clip unmixed),
+        padded by ``pad_mode`` and cropped at ``noise_start[b]`` like a clip.  The level is one SNR in dB per clip (a number or B of
+        them: coeff = r / (1 + r), r = 10^(snr / 10), AddRandomNoise's rule) or, as a (B, 2) float32 tensor, the coefficient pairs
+        (c, c') themselves (``_native.noise_coefficients``).  ``gaussian`` = (amp, seed, stream): amplitudes (B,) float32, a 64-bit
+        seed and one int64 stream id per clip (``_native.gaussian_noise``); amplitude 0 leaves a clip alone."""
+        B, rec_off, rec_len = self._records(index)
         return _native.assemble_clips(self.store, rec_off, rec_len, self._per_clip(start, B), self._per_clip(pad_mode, B, _native.PAD_MODES),
-                                      size, gain, normalize, masks, out)
+                                      size, gain, normalize, masks, out, noise=None if noise is None else self._noise(noise, B),
+                                      gaussian=gaussian)
 
 
 class ClipPlan(tuple):
@@ -154,6 +197,15 @@ class ClipPlan(tuple):
     (``masks`` None without time masking) -- the arguments of ``_native.assemble_clips`` / leaf_assemble_clips_f32 behind the store."""
     __slots__ = ()
     rec_off, rec_len, start, pad_mode, gain, masks = (property(lambda self, i=i: self[i]) for i in range(6))
+
+
+class ClipNoisePlan(ClipPlan):
+    """A ``ClipPlan`` (the same six entries, unpacking as before) that carries the noise draws as attributes: ``noise`` =
+    (noise_off, noise_len, noise_start, noise_pad_mode, coeff) -- ``coeff`` float64, AddRandomNoise's r / (1 + r); ``noise_len`` 0 for
+    a clip without background noise -- or None, and ``gaussian`` = (amp, seed, stream) or None: what ``_native.assemble_clips`` takes
+    as ``noise`` (behind the noise store) and ``gaussian``."""
+    noise = None
+    gaussian = None
 
 
 class ClipSampler:
@@ -172,16 +224,28 @@ class ClipSampler:
     - time masks, with ``num_masks > 0`` (TimeMasking): ``randint(1, num_masks)`` spans per clip, ``n = int(uniform(0, time_perc) *
       size)`` samples from ``t0 = int(uniform(0, size - n))``; the unused spans carry ``n = 0``.
 
+    - background noise, with ``noise_clips`` (a ``PackedClips`` of the clips' dtype and device: AddRandomNoise under
+      UseWithProb(..., noise_prob)): a recording chosen uniformly, padded with 'replicate' (the reference's PadToSize(size, "wrap")) and
+      cropped at a start uniform in [0, max(Ln, size) - size]; ``snr = uniform(lo, hi + 1)`` dB from ``snr_range``,
+      ``coeff = r / (1 + r)``, ``r = exp(snr ln 10 / 10)`` in float64, and the clip becomes ``coeff * x + (1 - coeff) * noise`` in
+      front of the gain.
+    - Gaussian noise, with ``gaussian_prob > 0`` (AddGaussianNoise under UseWithProb): an amplitude uniform in
+      ``gaussian_amplitude``, else 0; ``x + amplitude * z`` behind the gain, in front of the peak normalisation.  ``z`` is the library's
+      stream ``_native.gaussian_noise(seed, stream)``: ``gaussian_seed`` (default: the generator's initial seed) and one stream id per
+      clip from a counter on the sampler (``next_stream``) that advances by B per call, so no two clips ever share a stream.
+
     All draws come from a CPU ``torch.Generator`` (``generator``; a fresh default-seeded one otherwise): the same seed gives the same
-    plan.  The reference's own ``random`` / ``numpy.random`` streams are NOT reproduced -- the distributions are, the numbers are not.
+    plan.  The noise draws come after all the others, so a sampler without noise draws what it always drew.  With noise ``plan``
+    returns a ``ClipNoisePlan``: the same 6-tuple, the noise draws as attributes.
+    The reference's own ``random`` / ``numpy.random`` streams are NOT reproduced -- the distributions are, the numbers are not.
     ``plan(index)`` returns the draws (``ClipPlan``), ``__call__(index)`` the assembled ``(B, 1, size)`` float32 batch.
 
-    Left out: AddGaussianNoise, AddRandomNoise (background noise at an SNR), ClipValue and RandomReverb.  Noise needs a random stream
-    on the device with an oracle of its own; the reference itself has the other two switched off."""
+    Left out: ClipValue and RandomReverb, which the reference itself has switched off."""
 
     def __init__(self, clips: PackedClips, size: int, train: bool = True, pad_modes=("replicate", "min"), wrap_pad_prob: float = 0.5,
                  gain_prob: float = 0.25, gain_db=(-18.0, 6.0), peak_normalize: bool = True, time_perc: float = 0.0, num_masks: int = 0,
-                 generator=None):
+                 generator=None, noise_clips=None, noise_prob: float = 0.5, snr_range=(10, 25), gaussian_prob: float = 0.0,
+                 gaussian_amplitude=(0.001, 0.015), gaussian_seed=None):
         self.clips, self.size, self.train = clips, int(size), bool(train)
         self.pad_modes = tuple(_native.PAD_MODES[m] if isinstance(m, str) else int(m) for m in pad_modes)
         if len(self.pad_modes) != 2 or any(m not in _native.PAD_MODES.values() for m in self.pad_modes):
@@ -189,6 +253,19 @@ class ClipSampler:
         self.wrap_pad_prob, self.gain_prob, self.gain_db = float(wrap_pad_prob), float(gain_prob), (float(gain_db[0]), float(gain_db[1]))
         self.peak_normalize, self.time_perc, self.num_masks = bool(peak_normalize), float(time_perc), int(num_masks)
         self.generator = generator if generator is not None else torch.Generator()
+        if noise_clips is not None:
+            if not isinstance(noise_clips, PackedClips):
+                raise TypeError("noise_clips must be a PackedClips")
+            if noise_clips.store.dtype != clips.store.dtype:
+                raise TypeError(f"noise_clips holds {noise_clips.store.dtype} samples, the clips {clips.store.dtype}")
+            if noise_clips.store.device != clips.store.device:
+                raise ValueError(f"noise_clips is on {noise_clips.store.device}, the clips on {clips.store.device}")
+        self.noise_clips, self.noise_prob = noise_clips, float(noise_prob)
+        self.snr_range = (float(snr_range[0]), float(snr_range[1]))
+        self.gaussian_prob = float(gaussian_prob)
+        self.gaussian_amplitude = (float(gaussian_amplitude[0]), float(gaussian_amplitude[1]))
+        self.gaussian_seed = (self.generator.initial_seed() if gaussian_seed is None else int(gaussian_seed)) % 2 ** 64
+        self.next_stream = 0                                                    # the first stream id of the next batch
 
     def _uniform(self, *shape) -> torch.Tensor:
         return torch.rand(*shape, dtype=torch.float64, generator=self.generator)
@@ -216,8 +293,32 @@ class ClipSampler:
             n = torch.where(torch.arange(self.num_masks).reshape(1, -1) < used, n, 0).clamp_(0, S)
             t0 = (self._uniform(B, self.num_masks) * (S - n).double()).long()
             masks = torch.stack((t0, n), dim=2).to(torch.int32)
-        return ClipPlan((rec_off.clone(), rec_len.clone(), start.to(torch.int32), pad_mode, gain, masks))
+        entries = (rec_off.clone(), rec_len.clone(), start.to(torch.int32), pad_mode, gain, masks)
+        if self.noise_clips is None and self.gaussian_prob <= 0.0:
+            return ClipPlan(entries)
+        plan = ClipNoisePlan(entries)
+        if self.noise_clips is not None:                                        # AddRandomNoise
+            nc = self.noise_clips
+            apply = self._uniform(B) < self.noise_prob
+            snr = self.snr_range[0] + (self.snr_range[1] + 1.0 - self.snr_range[0]) * self._uniform(B)
+            rec = (self._uniform(B) * len(nc)).floor().long().clamp_(max=len(nc) - 1)
+            noff, nlen = nc.offsets_host[rec], nc.lengths_host[rec]
+            nspan = (nlen.long() - S).clamp_(min=0)
+            nstart = torch.minimum((self._uniform(B) * (nspan + 1).double()).floor().long(), nspan)
+            plan.noise = (noff.clone(), torch.where(apply, nlen, torch.zeros_like(nlen)), torch.where(apply, nstart, 0).to(torch.int32),
+                          torch.full((B,), _native.PAD_REPLICATE, dtype=torch.int32), _native.snr_coefficients(snr))
+        if self.gaussian_prob > 0.0:                                            # AddGaussianNoise
+            apply = self._uniform(B) < self.gaussian_prob
+            amp = self.gaussian_amplitude[0] + (self.gaussian_amplitude[1] - self.gaussian_amplitude[0]) * self._uniform(B)
+            stream = torch.arange(self.next_stream, self.next_stream + B, dtype=torch.int64)
+            self.next_stream += B
+            plan.gaussian = (torch.where(apply, amp, 0.0).to(torch.float32), self.gaussian_seed, stream)
+        return plan
 
     def __call__(self, index, out=None) -> torch.Tensor:
-        rec_off, rec_len, start, pad_mode, gain, masks = self.plan(index)
-        return _native.assemble_clips(self.clips.store, rec_off, rec_len, start, pad_mode, self.size, gain, self.peak_normalize, masks, out)
+        plan = self.plan(index)
+        rec_off, rec_len, start, pad_mode, gain, masks = plan
+        noise = getattr(plan, "noise", None)
+        return _native.assemble_clips(self.clips.store, rec_off, rec_len, start, pad_mode, self.size, gain, self.peak_normalize, masks, out,
+                                      noise=None if noise is None else (self.noise_clips.store,) + tuple(noise),
+                                      gaussian=getattr(plan, "gaussian", None))

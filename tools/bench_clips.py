@@ -4,6 +4,7 @@
 multiply by the gain, transforms.PeakNormalization, one masked_fill per span.
 
     python tools/bench_clips.py [--rounds 20] [--steps 50] [--out profiles/clip_assembly.txt]
+    python tools/bench_clips.py --noise [--out profiles/clip_noise.txt]
 
 Both sides run in ONE process on the same store and the same plan (already on the device: drawing it is not timed), taking turns
 round after round after a warm-up round, the order alternating.  Every recording is longer than the clip, so the batch is a crop
@@ -17,7 +18,15 @@ over the rounds of (time of `steps` calls) / steps:
           host's enqueue time excluded
 and for the kernel the achieved bytes per second: (B * S samples of the store read + 4 * B * S bytes written) / median device time.
 B = 64 / 256 clips of 16 000 and 80 000 samples (80 000 is beyond the resident path: the clip is gathered twice), int16 and float32
-stores.  No assertion on any time; prints the table and, with --out, writes it."""
+stores.  No assertion on any time; prints the table and, with --out, writes it.
+
+--noise times the launch with background noise at an SNR and Gaussian noise in it (leaf_assemble_clips_noise_f32) instead: B = 64 /
+256 clips of 16 000 samples, both stores, every clip mixed and every amplitude non-zero.  Its stock side is the composition a user
+would write without the entry: index gather of the clip and of the noise, .float() / 32768, the multiply-add of the mix, multiply by
+the gain, torch.randn scaled and added, transforms.PeakNormalization, one masked_fill per span.  torch.randn is not the library's
+stream, so the two sides are NOT compared bit for bit here (tests/test_gpu_clip_noise.py does that, on the library's own z); the
+stock side is checked against the kernel with the Gaussian amplitude at 0 instead.  A third column times the plain launch
+(leaf_assemble_clips_f32, the same clip plan without noise) in the same rounds: the cost of the augmented launch relative to it."""
 import argparse
 import os
 import statistics
@@ -50,14 +59,108 @@ def make_case(B, S, dtype, seed):
     return store.to(DEV), {k: v.to(DEV) for k, v in plan.items()}
 
 
+def time_sides(sides, rounds, steps, busy, busy_out):
+    """us per call of every side, (device, wall) lists over the rounds: the sides take turns, the order alternating; round 0 warms up."""
+    dev_us, wall_us = {k: [] for k in sides}, {k: [] for k in sides}
+    for rnd in range(rounds + 1):
+        for name in (list(sides) if rnd % 2 == 0 else list(sides)[::-1]):
+            fn = sides[name]
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                fn()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.mm(busy, busy, out=busy_out)
+            e0.record()
+            for _ in range(steps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if rnd:
+                dev_us[name].append(e0.elapsed_time(e1) * 1e3 / steps)
+                wall_us[name].append((t1 - t0) * 1e6 / steps)
+    return dev_us, wall_us
+
+
+def noise_legs(args, busy, busy_out):
+    pn = PeakNormalization()
+    S = 16000
+    lines = [f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {args.rounds} timed rounds x {args.steps} calls per side after a "
+             "warm-up round; us per call: median [min, max]; device = HIP events, calls queued behind a matrix product; wall = host clock to a "
+             "synchronise; noise = leaf_assemble_clips_noise_f32 (background noise + Gaussian noise, every clip), plain = leaf_assemble_clips_f32 "
+             "on the same clip plan, stock = gather x 2 + mix + gain + torch.randn + scaled add + PeakNormalization + masked_fill",
+             f"{'store':>8} {'B':>4} {'S':>6} | {'noise device':>24} {'noise wall':>11} | {'plain device':>24} | {'stock device':>24} {'stock wall':>11} | "
+             f"{'noise / plain':>13} {'stock / noise':>13}"]
+    for dtype in (torch.int16, torch.float32):
+        for B in (64, 256):
+            store, p = make_case(B, S, dtype, seed=B + S)
+            nstore, q = make_case(B, S, dtype, seed=B + S + 1)
+            g = torch.Generator().manual_seed(B)
+            snr = 10.0 + 16.0 * torch.rand(B, generator=g, dtype=torch.float64)
+            coeff = _native.noise_coefficients(_native.snr_coefficients(snr)).to(DEV)
+            amp = (0.001 + 0.014 * torch.rand(B, generator=g)).to(DEV)
+            streams = torch.arange(B, device=DEV)
+            noise = (nstore, q["rec_off"], q["rec_len"], q["start"], torch.full((B,), _native.PAD_REPLICATE, dtype=torch.int32, device=DEV), coeff)
+            out = torch.empty((B, 1, S), dtype=torch.float32, device=DEV)
+            ar = torch.arange(S, device=DEV)
+            lo, hi = p["masks"][..., 0].long(), (p["masks"][..., 0] + p["masks"][..., 1]).long()
+            first, nfirst = (p["rec_off"] + p["start"])[:, None], (q["rec_off"] + q["start"])[:, None]
+            c, cn = coeff[:, :1], coeff[:, 1:]
+
+            def kernel(amp=amp):
+                return _native.assemble_clips(store, p["rec_off"], p["rec_len"], p["start"], p["pad_mode"], S, p["gain"], True, p["masks"], out,
+                                              noise=noise, gaussian=(amp, 1234, streams))
+
+            def plain():
+                return _native.assemble_clips(store, p["rec_off"], p["rec_len"], p["start"], p["pad_mode"], S, p["gain"], True, p["masks"], out)
+
+            def stock(amp=amp):
+                x, n = store[first + ar], nstore[nfirst + ar]
+                if dtype == torch.int16:
+                    x, n = x.float() / 32768, n.float() / 32768
+                x = (c * x + cn * n) * p["gain"][:, None]
+                x = pn(x + amp[:, None] * torch.randn((B, S), device=DEV))
+                for m in range(M):
+                    x = x.masked_fill((ar >= lo[:, m, None]) & (ar < hi[:, m, None]), 0.0)
+                return x[:, None]
+
+            zero = torch.zeros_like(amp)
+            a, b = kernel(zero).clone(), stock(zero)
+            torch.cuda.synchronize()
+            if not torch.equal(a.view(torch.int32), b.contiguous().view(torch.int32)):
+                sys.exit(f"the two sides disagree (Gaussian amplitude 0) at {dtype} B={B}: nothing is timed")
+            dev_us, wall_us = time_sides({"noise": kernel, "plain": plain, "stock": stock}, args.rounds, args.steps, busy, busy_out)
+            fmt = lambda v: f"{statistics.median(v):9.1f} [{min(v):6.1f},{max(v):7.1f}]"
+            med = {k: statistics.median(v) for k, v in dev_us.items()}
+            lines.append(f"{str(dtype).replace('torch.', ''):>8} {B:>4} {S:>6} | {fmt(dev_us['noise'])} {statistics.median(wall_us['noise']):11.1f} | "
+                         f"{fmt(dev_us['plain'])} | {fmt(dev_us['stock'])} {statistics.median(wall_us['stock']):11.1f} | "
+                         f"{med['noise'] / med['plain']:13.2f} {med['stock'] / med['noise']:13.2f}")
+            print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--noise", action="store_true", help="time the launch with background and Gaussian noise (profiles/clip_noise.txt)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_clips.py needs the GPU: a time taken anywhere else says nothing about it")
+    if args.noise:
+        busy = torch.rand(8192, 8192, device=DEV)
+        text = "\n".join(noise_legs(args, busy, torch.empty_like(busy))) + "\n"
+        print(text)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                fh.write(text)
+        return
     pn = PeakNormalization()
     busy = torch.rand(8192, 8192, device=DEV)
     busy_out = torch.empty_like(busy)
