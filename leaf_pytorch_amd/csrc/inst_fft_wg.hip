@@ -4,26 +4,20 @@
 #include "leaf_fft_wg4k.hpp"
 #include "leaf_inst.hpp"
 
-// stream: the variant that finalizes in the kernel (whole clips per workgroup, frame sums in an LDS ring)
-const void* leaf_inst_fft_wg(int sk, int nw, bool stream) {
-    using K = void (*)(const FftParams);
-    K fn = nullptr;
-    if (stream) {
-        if (sk == 401 && nw == 12) fn = leaf_fft_wg_kernel<401, 160, 12, true>;
-        else if (sk == 801 && nw == 10) fn = leaf_fft_wg_kernel<801, 320, 10, true>;
-        else if (sk == 201 && nw == 12) fn = leaf_fft_wg_kernel<201, 80, 12, true>;
-        return reinterpret_cast<const void*>(fn);
-    }
-    if (sk == 401 && nw == 12) fn = leaf_fft_wg_kernel<401, 160, 12>;
-    else if (sk == 801 && nw == 10) fn = leaf_fft_wg_kernel<801, 320, 10>;
-    else if (sk == 201 && nw == 12) fn = leaf_fft_wg_kernel<201, 80, 12>;
+// fp32 waveform, tail finalize (the STREAM variant: inst_fft_wg_streamfin.hip; 16-bit and mixed waveforms: inst_fft_wg_x16.hip,
+// inst_fft_wg_mix.hip, inst_fft_wg_mix16.hip).  tailc: the tile form of the tail, 128 (rows of <= 128 frames) or 64 (longer rows)
+const void* leaf_inst_fft_wg(int sk, int nw, int tailc) {
+    if (const void* fn = wg_tail_instance<kWgXF32>(sk, nw, tailc)) return fn;
+    FftKernelFn fn = nullptr;
+    const bool t128 = tailc == 128, t64 = tailc == 64;
+    (void)t128; (void)t64;
 #ifdef LEAF_WG_NW                   // A/B builds (tools/compare_builds.py name:-DLEAF_WG_NW=8): another workgroup size for 401/160
-    else if (sk == 401 && nw == LEAF_WG_NW) fn = leaf_fft_wg_kernel<401, 160, LEAF_WG_NW>;
+    if (sk == 401 && nw == LEAF_WG_NW) fn = t128 ? wg_tail_kernel<401, 160, LEAF_WG_NW, kWgXF32, 128>() : t64 ? wg_tail_kernel<401, 160, LEAF_WG_NW, kWgXF32, 64>() : nullptr;
 #endif
 #if LEAF_TOOLS                      // LEAF_WG_WAVES=16: the column-half transposition form (A/B measurements)
-    else if (sk == 401 && nw == 16) fn = leaf_fft_wg_kernel<401, 160, 16>;
-    else if (sk == 801 && nw == 14) fn = leaf_fft_wg_kernel<801, 320, 14>;
-    else if (sk == 201 && nw == 16) fn = leaf_fft_wg_kernel<201, 80, 16>;
+    if (sk == 401 && nw == 16) fn = t128 ? wg_tail_kernel<401, 160, 16, kWgXF32, 128>() : t64 ? wg_tail_kernel<401, 160, 16, kWgXF32, 64>() : nullptr;
+    else if (sk == 801 && nw == 14) fn = t128 ? wg_tail_kernel<801, 320, 14, kWgXF32, 128>() : t64 ? wg_tail_kernel<801, 320, 14, kWgXF32, 64>() : nullptr;
+    else if (sk == 201 && nw == 16) fn = t128 ? wg_tail_kernel<201, 80, 16, kWgXF32, 128>() : t64 ? wg_tail_kernel<201, 80, 16, kWgXF32, 64>() : nullptr;
 #endif
     return reinterpret_cast<const void*>(fn);
 }

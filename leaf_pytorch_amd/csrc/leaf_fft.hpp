@@ -1367,14 +1367,19 @@ __global__ void pcen_stream_kernel(const float* __restrict__ p, int BF, int n, F
 // The tail of a workgroup kernel (all its waves call, after their last task): the rows of the clips whose blocks this workgroup
 // ran itself, [b_lo F, b_hi F), finalized with `tile_mem` (the waves' scratch, free by now; >= fin_tile_floats<TR, 64>() floats)
 // as tile memory.  Release (the partial sums have reached L2) - barrier - tiles.  Rows of up to 128 frames go through in one
-// chunk (three dependent stages), longer ones 64 frames at a time, pipelined.
-template <int TR>
+// chunk (three dependent stages), longer ones 64 frames at a time, pipelined.  COLS = 128 / 64: the host knows T' and picked an
+// instance that holds only the tile form its rows take (leaf_fft_wg.hpp: the other one is ~9 KB of code that launch never runs);
+// COLS = 0: both, chosen here.
+template <int TR, int COLS = 0>
 __device__ __forceinline__ void wg_tail_finalize(const FinParams& fin, int b_lo, int b_hi, float* tile_mem, int tid, int nthreads) {
+    static_assert(COLS == 0 || COLS == 64 || COLS == 128, "tile forms of the tail");
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     const int row_end = b_hi * fin.F;
     for (int row = b_lo * fin.F; row < row_end; row += TR) {
-        if (fin.TP <= 128) fft_finalize_tile<true, TR, 128>(fin, row, min(TR, row_end - row), OwnedClips{}, tile_mem, tid, nthreads);
+        if constexpr (COLS == 128) fft_finalize_tile<true, TR, 128>(fin, row, min(TR, row_end - row), OwnedClips{}, tile_mem, tid, nthreads);
+        else if constexpr (COLS == 64) fft_finalize_tile<true, TR, 64>(fin, row, min(TR, row_end - row), OwnedClips{}, tile_mem, tid, nthreads);
+        else if (fin.TP <= 128) fft_finalize_tile<true, TR, 128>(fin, row, min(TR, row_end - row), OwnedClips{}, tile_mem, tid, nthreads);
         else fft_finalize_tile<true, TR, 64>(fin, row, min(TR, row_end - row), OwnedClips{}, tile_mem, tid, nthreads);
     }
 }

@@ -474,8 +474,84 @@ constexpr size_t fft_wg_stream_lds_bytes(int NW, int SK, int ring, int F) {     
                                        (size_t)F * kWgOutRow) * 4;
 }
 
-template <int SK, int SHOP, int NW, bool STREAM = false>
-__global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(const FftParams p) {
+// ---- one loader and one tail tile per instance ------------------------------------------------------------------------------
+// The sample kind of the waveform (XK) and the tile form of the tail (TAILC, wg_tail_finalize) are compile-time: the host knows both
+// (FwdIo::xtype, the call's mix, T') and every launch ran exactly one of the three load loops and one of the two tiles, with the
+// others' code -- ~19 KB of an 80 KB kernel -- around the task loop in a 64 KB instruction cache.  fp32; 16-bit (bfloat16 and PCM16
+// share a loop: a wave-uniform select of the conversion); mixed fp32; mixed PCM16 (leaf_common.hpp; a mixed load is ~3 KB of code
+// and the kernel has two load sites, so the two mixed sample types are an instance each).
+constexpr int kWgXF32 = 0, kWgX16 = 1, kWgXMix = 2, kWgXMix16 = 3;
+// The STREAM instances keep the choice at run time (kWgXAny: the three loops of one load site, as before the split): they do not take the
+// early path, so they have one load site, and with a single loader they measured 0.6-1.3 % slower at the shapes that run them
+// (profiles/early_forward.txt) -- the split stays where the second load site needs it.
+constexpr int kWgXAny = 4;
+// The block gb of the launch, rotated left by padL samples, into the wave's registers: are[r] = sample 64 r + lane of the rotated
+// block, zero outside [0, T) (both partners, mixed); (b, c) = the block's clip and its index in the clip.  The one load site of the
+// forward transforms: the queue's forward task and the two early first blocks (below).
+template <int SK, int SHOP, int XK>
+__device__ __forceinline__ void wg_load_block(const FftParams& p, int gb, int lane, float (&are)[32], int& b, int& c) {
+    constexpr int PADL = SK / 2 + SK % 2 - 1;
+    constexpr int LS = fft_block_len(SK, SHOP, true);
+    // which load loop: compile-time constants in the instances of one kind, the call's own (wave-uniform) for kWgXAny
+    constexpr bool ANY = XK == kWgXAny;
+    b = gb / p.nblk;                                                      // the only division per block
+    c = gb - b * p.nblk;
+    const int n_c = c * LS;
+    const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
+    const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
+    if (ANY ? p.mix_lam != nullptr : (XK == kWgXMix || XK == kWgXMix16)) {
+        // waveform mixup in the load (leaf_common.hpp): the block's clip mixed with its partner, weights and partner row
+        // read once per block; a loop per sample type (fp32 / 16-bit PCM)
+        const MixClip mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
+        const size_t row = (size_t)b * p.T;
+        if constexpr (ANY) {
+            // (one loop for both sample types, a wave-uniform select of the load as in the 16-bit loop below: the instance that keeps
+            // every loader stays inside the size of the kernel it replaces)
+            const int st = p.io_bf16 == kSamplePcm16 ? kSamplePcm16 : kSampleF32;
+#pragma unroll
+            for (int r = 0; r < 32; ++r) {
+                const int i = 64 * r + lane;
+                const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
+                const float w = mix_load(p.x, row, mc.partner, (size_t)min(max(n, 0), p.T - 1), mc.lam, mc.om, st);
+                are[r] = (n >= 0 && n < p.T) ? w : 0.0f;
+            }
+        } else if (XK == kWgXMix16) {
+#pragma unroll
+            for (int r = 0; r < 32; ++r) {
+                const int i = 64 * r + lane;
+                are[r] = mix_sample<kSamplePcm16>(p.x, row, mc, n_c - PADL + ((i + PADL) & (kFftN - 1)), p.T);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 32; ++r) {
+                const int i = 64 * r + lane;
+                are[r] = mix_sample<kSampleF32>(p.x, row, mc, n_c - PADL + ((i + PADL) & (kFftN - 1)), p.T);
+            }
+        }
+    } else if (ANY ? p.io_bf16 != 0 : XK == kWgX16) {
+        const bool pcm = p.io_bf16 == kSamplePcm16;     // 16-bit PCM shares the loop: a wave-uniform select of the conversion
+#pragma unroll
+        for (int r = 0; r < 32; ++r) {
+            const int i = 64 * r + lane;                      // block rotated left by padL samples
+            const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
+            const unsigned v = xh[min(max(n, 0), p.T - 1)];
+            const float w = pcm ? pcm16_widen((short)v) : __uint_as_float(v << 16);
+            are[r] = (n >= 0 && n < p.T) ? w : 0.0f;
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 32; ++r) {
+            const int i = 64 * r + lane;
+            const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
+            are[r] = (n >= 0 && n < p.T) ? xb[n] : 0.0f;
+        }
+    }
+}
+
+// The kernel's body; the two __global__ templates below name its instances (leaf_fft_wg_kernel: fp32 samples, rows of <= 128
+// frames -- what the default forward runs; leaf_fft_wg_kernel_var: every other (sample kind, tail) pair).
+template <int SK, int SHOP, int NW, bool STREAM, int XK, int TAILC>
+__device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
     constexpr bool HALF = NW > 12;                                        // 16 rows of transposition scratch per wave
     constexpr int SCRF = fft_wg_scr_floats(NW);
     extern __shared__ __attribute__((aligned(16))) float wsm[];
@@ -524,10 +600,30 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
 #pragma unroll
         for (int k = 0; k < kWgFwdBins / 64; ++k) sv[k] = src[64 * k + lane0];
     }
+    // Without p.spec0 (the table cache validated and returned; 16-bit PCM; a mixed call; prepared tables) the workgroup's first TWO
+    // blocks are requested here, at the kernel's first instructions: nothing in a forward transform's loads depends on the tables or the
+    // plan, and left to the task queue they started only after the barrier -- 32 loads per lane, cold from HBM, with eleven waves
+    // waiting behind them.  Wave NW - 1 takes block 0, wave NW - 2 block 1 (wave 0 has the plan); both still build twiddles below (the
+    // loads are in flight meanwhile), transform right after the barrier and publish as fwd(0) / fwd(1) do; the queue starts behind them.
+    // The waves that leave the barrier beside them request their first tasks' table rows meanwhile.  Not in the STREAM instances
+    // (whole clips per workgroup, 20+ blocks each at the shapes that run them: the start is amortised, and the second transform's
+    // 9.5 KB of code would put them above the size of the kernel they replace).
+    constexpr bool EARLYK = !HALF && !STREAM;
+    const bool early = EARLYK && p.spec0 == nullptr;
+    const int eset = NW - 1 - wave;                                       // the set an early wave transforms: 0 or 1
+    bool early_me = false;
+    float ex[32];
+    int eb = 0, ec = 0;
+    if constexpr (EARLYK) {
+        const OwnedClips deal0{p.B * p.nblk, (int)gridDim.x, p.nblk};    // (the dealing, as below)
+        early_me = early && eset < 2 && eset < deal0.count((int)blockIdx.x);
+        if (early_me) wg_load_block<SK, SHOP, XK>(p, deal0.start((int)blockIdx.x) + eset, lane0, ex, eb, ec);
+    }
     // (while wave 0 builds the plan -- one global round trip -- the other waves build the twiddle tables)
     if (BANDK && band_on) { if (wave > 0) fft_build_twiddles_wg(twl, twh, tid - 64, (NW - 1) * 64); }
     else fft_build_twiddles_wg(twl, twh, tid, NW * 64);
-    if (tid < kWgQueueInts) q[tid] = (tid == 0 && spec_pre) ? 1 : 0;
+    // (early: tasks 0 and 1 are fwd(0) and fwd(1) -- task 1 the skipped slot when nset == 1)
+    if (tid < kWgQueueInts) q[tid] = (tid == 0 && spec_pre) ? 1 : (tid == 0 && early) ? 2 : 0;
     if constexpr (STREAM) {
         for (int f = tid; f < p.F; f += NW * 64) coefT[f] = fin_coef(p.fin, f);
         if (tid < 8) sq[tid] = 0;
@@ -538,7 +634,11 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
         const int n = (int)((long long)p.B * p.nblk / (int)gridDim.x / p.nblk) * p.F * p.TP;    // clips per workgroup x F x T'
         for (int i = tid; i < n; i += NW * 64) lsum[i] = 0.0f;
         lcoef = reinterpret_cast<FinCoef*>(lsum + (n + 7) / 8 * 8);
-        for (int f = NW * 64 - 1 - tid; f < p.F; f += NW * 64) lcoef[f] = fin_coef(p.fin, f);   // (the last waves: wave 0 builds the plan)
+        // (from wave NW - 3 downwards: wave 0 builds the plan, and the last two hold their first blocks' loads -- memory returns in
+        // order, so a coefficient load behind those would wait for them before the barrier)
+        constexpr int NC = NW > 2 ? (NW - 2) * 64 : NW * 64;
+        if (tid < NC)
+            for (int f = NC - 1 - tid; f < p.F; f += NC) lcoef[f] = fin_coef(p.fin, f);
     }
     __syncthreads();
 #if LEAF_TRACE
@@ -577,6 +677,23 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
         if (lane0 == 0) { q[5] = gb0 / p.nblk; q[6] = gb0 % p.nblk; }
         wg_release();
         if (lane0 == 0) __hip_atomic_fetch_add(&q[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    if (early_me) {
+        // fwd(eset): ring slot eset, generation 0 -- no reader of an earlier occupant to wait for; published as the queue's forward task does
+        WG_STAMP(1);
+        float eim[32];
+#pragma unroll
+        for (int r = 0; r < 32; ++r) eim[r] = 0.0f;
+        fft2048w<HALF>(ex, eim, scr, scr_lds, twl, twh, lane0);           // register i <-> bin 64 brev5(i) + lane
+        float2* A = ring + eset * kWgRingFwdFloat2;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const int k = brev5(i);
+            if (k < kWgFwdBins / 64) A[64 * k + lane0] = make_float2(ex[i], eim[i]);
+        }
+        if (lane0 == 0) { q[5 + 2 * eset] = eb; q[6 + 2 * eset] = ec; }
+        wg_release();
+        if (lane0 == 0) __hip_atomic_fetch_add(&q[1 + eset], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     const int first_gb = deal.start((int)blockIdx.x);
     const int nset = deal.count((int)blockIdx.x);                         // blocks of this workgroup
@@ -734,52 +851,11 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
         if (role == 0) {
             // ---- forward transform of block gb into ring slot `slot` (skipped past the last set)
             if (set < nset) {
-                const int gb = first_gb + set;
-                const int b = gb / p.nblk, c = gb - b * p.nblk;               // the only division per block
-                const int n_c = c * LS;
                 float are[32], aim[32];
-                const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
-                const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
-                if (p.mix_lam) {
-                    // waveform mixup in the load (leaf_common.hpp): the block's clip mixed with its partner, weights and partner row
-                    // read once per block; a loop per sample type (fp32 / 16-bit PCM)
-                    const MixClip mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
-                    const size_t row = (size_t)b * p.T;
-                    if (p.io_bf16 == kSamplePcm16) {
+                int fb, fc;                                               // the block's clip and its index in the clip
+                wg_load_block<SK, SHOP, XK>(p, first_gb + set, lane, are, fb, fc);
 #pragma unroll
-                        for (int r = 0; r < 32; ++r) {
-                            const int i = 64 * r + lane;
-                            are[r] = mix_sample<kSamplePcm16>(p.x, row, mc, n_c - PADL + ((i + PADL) & (kFftN - 1)), p.T);
-                            aim[r] = 0.0f;
-                        }
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 32; ++r) {
-                            const int i = 64 * r + lane;
-                            are[r] = mix_sample<kSampleF32>(p.x, row, mc, n_c - PADL + ((i + PADL) & (kFftN - 1)), p.T);
-                            aim[r] = 0.0f;
-                        }
-                    }
-                } else if (p.io_bf16) {
-                    const bool pcm = p.io_bf16 == kSamplePcm16;     // 16-bit PCM shares the loop: a wave-uniform select of the conversion
-#pragma unroll
-                    for (int r = 0; r < 32; ++r) {
-                        const int i = 64 * r + lane;                      // block rotated left by padL samples
-                        const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
-                        const unsigned v = xh[min(max(n, 0), p.T - 1)];
-                        const float w = pcm ? pcm16_widen((short)v) : __uint_as_float(v << 16);
-                        are[r] = (n >= 0 && n < p.T) ? w : 0.0f;
-                        aim[r] = 0.0f;
-                    }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 32; ++r) {
-                        const int i = 64 * r + lane;
-                        const int n = n_c - PADL + ((i + PADL) & (kFftN - 1));
-                        are[r] = (n >= 0 && n < p.T) ? xb[n] : 0.0f;
-                        aim[r] = 0.0f;
-                    }
-                }
+                for (int r = 0; r < 32; ++r) aim[r] = 0.0f;
                 fft2048w<HALF>(are, aim, scr, scr_lds, twl, twh, lane);        // register i <-> bin 64 brev5(i) + lane
                 wg_wait_ge(&q[3 + slot], gen * NT);                       // the slot's previous readers are done
                 if constexpr (STREAM) {                                   // ... and the frames ours wrap onto in the ring are out
@@ -791,7 +867,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
                     const int k = brev5(i);
                     if (k < kWgFwdBins / 64) A[64 * k + lane] = make_float2(are[i], aim[i]);     // bins 0..1151: 1025.. for band windows that cross Nyquist
                 }
-                if (lane == 0) { q[5 + 2 * slot] = b; q[6 + 2 * slot] = c; }      // the block's coordinates, for its readers
+                if (lane == 0) { q[5 + 2 * slot] = fb; q[6 + 2 * slot] = fc; }    // the block's coordinates, for its readers
                 wg_release();
                 if (lane == 0) __hip_atomic_fetch_add(&q[1 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
@@ -1004,8 +1080,39 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(cons
             fin.lds_row0 = b_lo * p.F;
             fin.lds_coef = lcoef;
         }
-        wg_tail_finalize<TR>(fin, b_lo, b_hi, reinterpret_cast<float*>(q + kWgQueueInts), tid, NW * 64);   // every task is done: the scratch is free
+        wg_tail_finalize<TR, TAILC>(fin, b_lo, b_hi, reinterpret_cast<float*>(q + kWgQueueInts), tid, NW * 64);   // every task is done: the scratch is free
     }
+}
+
+template <int SK, int SHOP, int NW, bool STREAM = false>
+__global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel(const FftParams p) {
+    leaf_fft_wg_body<SK, SHOP, NW, STREAM, STREAM ? kWgXAny : kWgXF32, STREAM ? 0 : 128>(p);
+}
+// the other tail-finalize instances.  XK: kWgXF32 / kWgX16 / kWgXMix / kWgXMix16; TAILC: 128 (T' <= 128) or 64 (longer rows)
+template <int SK, int SHOP, int NW, int XK, int TAILC>
+__global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel_var(const FftParams p) {
+    static_assert(XK != kWgXAny && (XK != kWgXF32 || TAILC != 128) && (TAILC == 64 || TAILC == 128), "that pair is leaf_fft_wg_kernel");
+    leaf_fft_wg_body<SK, SHOP, NW, false, XK, TAILC>(p);
+}
+using FftKernelFn = void (*)(const FftParams);
+// The instance ladder of the translation units (inst_fft_wg*.hip): the tail-finalize kernel of sample kind XK for a geometry and a
+// tail tile, nullptr where there is none.  NWX: a further workgroup size for 401/160, 801/320, 201/80 (tools builds), 0 = none.
+template <int SK, int SHOP, int NW, int XK, int TAILC>
+constexpr FftKernelFn wg_tail_kernel() {
+    if constexpr (XK == kWgXF32 && TAILC == 128) return leaf_fft_wg_kernel<SK, SHOP, NW, false>;
+    else return leaf_fft_wg_kernel_var<SK, SHOP, NW, XK, TAILC>;
+}
+template <int XK, int TAILC>
+inline FftKernelFn wg_tail_instance_of(int sk, int nw) {
+    if (sk == 401 && nw == 12) return wg_tail_kernel<401, 160, 12, XK, TAILC>();
+    if (sk == 801 && nw == 10) return wg_tail_kernel<801, 320, 10, XK, TAILC>();
+    if (sk == 201 && nw == 12) return wg_tail_kernel<201, 80, 12, XK, TAILC>();
+    return nullptr;
+}
+template <int XK>
+inline const void* wg_tail_instance(int sk, int nw, int tailc) {
+    const FftKernelFn fn = tailc == 128 ? wg_tail_instance_of<XK, 128>(sk, nw) : tailc == 64 ? wg_tail_instance_of<XK, 64>(sk, nw) : nullptr;
+    return reinterpret_cast<const void*>(fn);
 }
 
 }  // namespace

@@ -17,7 +17,9 @@
 const void* leaf_inst_fused(int rt, int noff, bool even_k, bool bwd);          // leaf_fused_kernel<RT, NOFF, EVENK, BWD>
 const void* leaf_inst_dtaps(int rt, int tpw, bool even_k);                     // dtaps_mfma_kernel<RT, TPW, EVENK>
 const void* leaf_inst_fft(int sk, int g2, int rs, int bwd);                    // leaf_fft_kernel<SK, SHOP, G2, RS, BWD>; sk = 0 | 201 | 401 | 801
-const void* leaf_inst_fft_wg(int sk, int nw, bool stream);                     // leaf_fft_wg_kernel<SK, SHOP, NW, STREAM>
+const void* leaf_inst_fft_wg(int sk, int nw, int tailc);                       // fp32 waveform: leaf_fft_wg_kernel<SK, SHOP, NW> (tailc = 128), leaf_fft_wg_kernel_var<.., kWgXF32, 64>
+const void* leaf_inst_fft_wg_streamfin(int sk, int nw);                        // leaf_fft_wg_kernel<SK, SHOP, NW, true>: every sample kind
+const void* leaf_inst_fft_wg_x16(int sk, int nw, int tailc);                   // leaf_fft_wg_kernel_var<SK, SHOP, NW, kWgX16, TAILC>: bfloat16 / PCM16 waveform
 const void* leaf_inst_fft_small(int sk, bool split);                          // leaf_fft_small_kernel<SK, SHOP, SPLIT>: sk = 401 | 201
 const void* leaf_inst_fft_stream(int sk);                                      // leaf_fft_stream_kernel<SK, SHOP>: sk = 401 | 201
 const void* leaf_inst_fft_stream_bank(int sk);                                 // leaf_fft_stream_bank_kernel<SK, SHOP>: sk = 401 | 201
@@ -36,6 +38,8 @@ const void* leaf_inst_fft_wg4k_bwd_dx();                                       /
 
 // the instances for a mixed call (waveform mixup in the block load, leaf_common.hpp); nullptr where there is none
 const void* leaf_inst_fft_mix(int sk, int bwd);                                // leaf_fft_kernel<SK, SHOP, 1, 1, BWD, true>: sk = 401 | 801 | 201
+const void* leaf_inst_fft_wg_mix(int sk, int nw, int tailc);                   // leaf_fft_wg_kernel_var<SK, SHOP, NW, kWgXMix, TAILC>: fp32 waveform
+const void* leaf_inst_fft_wg_mix16(int sk, int nw, int tailc);                 // leaf_fft_wg_kernel_var<SK, SHOP, NW, kWgXMix16, TAILC>: PCM16 waveform
 const void* leaf_inst_fft_small_mix(int sk, bool split);                       // leaf_fft_small_kernel<SK, SHOP, SPLIT, true>
 const void* leaf_inst_fft_wg_bwd_mix(int sk);                                  // leaf_fft_wg_bwd_kernel<SK, SHOP, 12, false, true>
 const void* leaf_inst_fft_wgg4k_bwd_mix(int ni2);                              // leaf_fft_wgg4k_bwd_kernel<12, NI2, false, false, true>
@@ -47,6 +51,10 @@ unsigned leaf_layout_fft();
 unsigned leaf_layout_fft_small();
 unsigned leaf_layout_fft_stream();
 unsigned leaf_layout_fft_wg();
+unsigned leaf_layout_fft_wg_streamfin();
+unsigned leaf_layout_fft_wg_x16();
+unsigned leaf_layout_fft_wg_mix();
+unsigned leaf_layout_fft_wg_mix16();
 unsigned leaf_layout_fft_wg_bwd();
 unsigned leaf_layout_fft_wg_bwd_dx();
 unsigned leaf_layout_fft_wgg();

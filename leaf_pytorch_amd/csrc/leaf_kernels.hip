@@ -472,7 +472,12 @@ struct FftWgLaunch {
 // of the 16-wave form (twice the store instructions) costs more than the fourth wave per SIMD brings (cfg1 0.223 vs 0.227 ms,
 // cfg3 0.4215 vs 0.428, cfg4 2.03 vs 2.05: tools/bench_configs.py, interleaved).  LEAF_WG_WAVES=16|12 (environment, tools
 // only) overrides the choice for A/B measurements.
-FftWgLaunch pick_fft_wg_kernel(int K, int hop) {
+// Every instance holds ONE loader and one tile form of the tail (leaf_fft_wg.hpp): xk = the waveform's sample kind
+// (wg_sample_kind), long_rows = T' > 128.
+inline int wg_sample_kind(int xtype, const float* mix_lam) {
+    return mix_lam ? (xtype == kSamplePcm16 ? kWgXMix16 : kWgXMix) : xtype ? kWgX16 : kWgXF32;
+}
+FftWgLaunch pick_fft_wg_kernel(int K, int hop, int xk, bool long_rows) {
     static const int forced = [] { const char* e = tools_env("LEAF_WG_WAVES"); return e ? atoi(e) : 0; }();
     const bool w16 = forced == 16 || forced == 14;
     int nw = 0;
@@ -484,9 +489,14 @@ FftWgLaunch pick_fft_wg_kernel(int K, int hop) {
     else if (K == 801 && hop == 320) nw = w16 ? 14 : 10;               // 16 do not fit the LDS
     else if (K == 201 && hop == 80) nw = w16 ? 16 : 12;
     else return {nullptr, 0, 0};
-    return {as_fft_kernel(leaf_inst_fft_wg(K, nw, false)), nw, fft_wg_lds_bytes(nw, K), true,
-            as_fft_kernel(leaf_inst_fft_wg(K, nw, true)), K, hop, true};
+    const int tailc = long_rows ? 64 : 128;
+    const void* fn = xk == kWgXMix ? leaf_inst_fft_wg_mix(K, nw, tailc) : xk == kWgXMix16 ? leaf_inst_fft_wg_mix16(K, nw, tailc)
+                     : xk == kWgX16 ? leaf_inst_fft_wg_x16(K, nw, tailc) : leaf_inst_fft_wg(K, nw, tailc);
+    const void* fn_stream = leaf_inst_fft_wg_streamfin(K, nw);            // (the loader chosen at run time: one load site)
+    return {as_fft_kernel(fn), nw, fft_wg_lds_bytes(nw, K), true, as_fft_kernel(fn_stream), K, hop, true};
 }
+// is there a static instance for the geometry (every sample kind and tail has one where one has)?  Not for launching.
+inline bool fft_wg_static_exists(int K, int hop) { return pick_fft_wg_kernel(K, hop, kWgXF32, false).fn != nullptr; }
 // Any other window the 2048-sample plan covers -- odd or even -- takes the run-time-geometry workgroup kernel
 // (leaf_fft_wgg.hpp): one instantiation per bucket of taps-per-lane and window parity, as many waves (<= 12: three per
 // SIMD's registers) as the LDS holds energy rows for.
@@ -515,7 +525,7 @@ static_assert(fft_wg_lds_bytes(12, 401) <= (size_t)kMaxLds && fft_wg_lds_bytes(1
 // AUTO takes the workgroup variant when the batch gives every CU at least one block; below that the per-wave kernel
 // (one task per wave, filters-per-task adapted to the batch) has the shorter critical path.
 bool fft_wg_available(const FftPlan& fp, int K, int hop) {
-    return fp.ok && (pick_fft_wg_kernel(K, hop).fn != nullptr || pick_fft_wgg_kernel(fp, K, hop).fn != nullptr);
+    return fp.ok && (fft_wg_static_exists(K, hop) || pick_fft_wgg_kernel(fp, K, hop).fn != nullptr);
 }
 // Blocks from which the workgroup kernels beat the per-wave kernel: a little under half a block per CU (measured crossover,
 // tools/sweep_batch_wg.py: 80 -> 160 blocks at 16 kHz, 60 -> 120 at 22.05 kHz, 80 -> 120 at 8 kHz, 68 -> 136 4096-sample
@@ -666,6 +676,10 @@ bool inst_layouts_ok() {
         leaf_layout_fft_small() == leaf_layout_hash_small() &&
         leaf_layout_fft_stream() == leaf_layout_hash_stream() &&
         leaf_layout_fft_wg() == leaf_layout_hash_fft() &&
+        leaf_layout_fft_wg_streamfin() == leaf_layout_hash_fft() &&
+        leaf_layout_fft_wg_x16() == leaf_layout_hash_fft() &&
+        leaf_layout_fft_wg_mix() == leaf_layout_hash_fft() &&
+        leaf_layout_fft_wg_mix16() == leaf_layout_hash_fft() &&
         leaf_layout_fft_wg_bwd() == leaf_layout_hash_fft() &&
         leaf_layout_fft_wg_bwd_dx() == leaf_layout_hash_fft() &&
         leaf_layout_fft_wgg() == leaf_layout_hash_fft() &&
@@ -1130,7 +1144,7 @@ static int fft_forward_tables(const CallCtx& ctx, const FftPlan& fp, const LeafA
     const auto [B, T, F, K, hop] = a.s;
     const FftTabPtrs tp = fft_tab_ptrs(fp, tables, F);
     if (use_wg && !ctx.band_off && (!tables_ready || band_scratch)) {
-        const FftWgLaunch wl = pick_fft_wg_kernel(K, hop);
+        const FftWgLaunch wl = pick_fft_wg_kernel(K, hop, wg_sample_kind(io.xtype, ctx.mix.lam), fp.TP > 128);
         const BandLayout bl = band_layout(F, K, hop);
         BandTabArgs ba{};
         if (bl.stat && wl.fn && wl.nw <= 12 && !wg_force_generic() && band_env() != 0 && fp.nslot == 2 &&
@@ -1243,7 +1257,7 @@ static int fft_forward(const CallCtx& ctx, const FftPlan& fp, const LeafArgs& a,
     bool all_owned = false;
     if (use_wg) {
         // one persistent workgroup per CU walks its blocks through an LDS task queue (leaf_fft_wg.hpp)
-        FftWgLaunch wl = pick_fft_wg_kernel(K, hop);
+        FftWgLaunch wl = pick_fft_wg_kernel(K, hop, wg_sample_kind(io.xtype, ctx.mix.lam), fp.TP > 128);
         if (!wl.fn || wg_force_generic()) {                   // run-time geometry (any other window, odd or even)
             if (ctx.mix.lam) return LEAF_ERR_BAD_ALGO;        // (these kernels do not mix in their loads: mix_fused_forward sends them a mixed copy)
             wl = pick_fft_wgg_kernel(fp, K, hop);
@@ -1772,7 +1786,7 @@ static bool mix_fused_forward(const Shape& s, int sel, int cus) {
     if (sel == LEAF_ALGO_FFT) return pick_fft_kernel_mix(make_fft_plan(s, cus), s.K, s.hop, false) != nullptr;   // per-wave: static odd windows
     if (sel != LEAF_ALGO_FFT_WG) return false;                            // MFMA, staged: the mixed copy
     if (make_fft4k_plan(s).ok) return true;                               // 4096-sample blocks, static and run-time geometry
-    return pick_fft_wg_kernel(s.K, s.hop).fn != nullptr && !wg_force_generic();   // 2048-sample blocks: the static instances
+    return fft_wg_static_exists(s.K, s.hop) && !wg_force_generic();   // 2048-sample blocks: the static instances
 }
 static size_t mix_copy_offset_floats(size_t base_bytes) { return align_up((base_bytes + 3) / 4, 64); }
 // workspace of the mixed forward behind a RESOLVED selector: the family's own, and the mixed copy where the family needs one
