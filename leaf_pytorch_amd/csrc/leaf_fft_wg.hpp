@@ -479,7 +479,8 @@ constexpr size_t fft_wg_stream_lds_bytes(int NW, int SK, int ring, int F) {     
 // (FwdIo::xtype, the call's mix, T') and every launch ran exactly one of the three load loops and one of the two tiles, with the
 // others' code -- ~19 KB of an 80 KB kernel -- around the task loop in a 64 KB instruction cache.  fp32; 16-bit (bfloat16 and PCM16
 // share a loop: a wave-uniform select of the conversion); mixed fp32; mixed PCM16 (leaf_common.hpp; a mixed load is ~3 KB of code
-// and the kernel has two load sites, so the two mixed sample types are an instance each).
+// and the kernel has two load sites, so the two mixed sample types are an instance each).  Since the row-owned tail (wg_tail_rows,
+// below) TAILC only selects the chunk length of a row, 128 or 64 frames; the instance set and the host's choice by T' are as they were.
 constexpr int kWgXF32 = 0, kWgX16 = 1, kWgXMix = 2, kWgXMix16 = 3;
 // The STREAM instances keep the choice at run time (kWgXAny: the three loops of one load site, as before the split): they do not take the
 // early path, so they have one load site, and with a single loader they measured 0.6-1.3 % slower at the shapes that run them
@@ -548,6 +549,145 @@ __device__ __forceinline__ void wg_load_block(const FftParams& p, int gb, int la
     }
 }
 
+// ---- the tail: every wave finalizes the rows it owns ---------------------------------------------------------------------------
+// After the drain barrier (release fence + __syncthreads at the end of the task loop: every frame sum of the clips this workgroup owns
+// is in its LDS, or in L2) the rows [b_lo F, b_hi F) are dealt to the NW waves -- row counts differ by at most one: 3 or 4 of the
+// default forward's 40 -- and a wave takes its rows end to end in its OWN transposition scratch, kWgTailRows rows at a time, CH frames
+// per chunk.  No barrier and no other wave's data behind the drain barrier: a wave's LDS operations execute in order, so the
+// wavefront-scope fences below (compiler ordering; s_waitcnt lgkmcnt is all the hardware needs) are the only synchronisation.
+//   (1) lane = live frame of the chunk, the rows side by side: the sums (LDS, or `part` past the vector cache with relaxed
+//       agent-scope loads, see fft_finalize_tile; a pass's loads are issued together) -> fin_pooled -> raw_out -> floor -> P;
+//   (2) lane r < rows: the smoother's recurrence of row r down the frames (fin_ema_step, state from p_0, frame 0 through the step
+//       too, the carry in a register between chunks) -> M;
+//   (3) lane = (row, frame of a 16-frame group): the point function and the store.
+// (2) of group g + 1 is issued with (3) of group g: the recurrence's dependent operations on a few lanes beside 64 lanes of log2 /
+// exp2 chains, and beside the two other waves of the SIMD, which are in their own rows.  What the tail costs is instruction issue --
+// 4 cycles per wave instruction, 8 for log2 / exp2 / rcp -- so each stage is written for few instructions per row.  The arithmetic is fin_*'s, in
+// the order fft_finalize_tile and the streaming finalize apply it: the row kernel stays an independent implementation of the same bits.
+// PCEN off and filters with delta <= 0 (the reference's literal powf) take a compact rolled form beside the hot loop.
+constexpr int kWgTailRows = 4, kWgTailGroup = 16;                         // 4 rows x 16 frames: the 64 lanes of the point stage
+constexpr int wg_tail_stride(int CH) { return CH + kWgTailGroup; }        // rows 16 banks apart: a group of the four rows meets every bank once
+constexpr int wg_tail_floats(int CH) { return 2 * kWgTailRows * wg_tail_stride(CH); }
+template <int NW, int CH>
+__device__ __forceinline__ void wg_tail_rows(const FinParams& q, int b_lo, int b_hi, float* scr, int wave, int lane) {
+    static_assert(CH == 64 || CH == 128, "chunk lengths of the tail");
+    constexpr int RB = kWgTailRows, GF = kWgTailGroup, S = wg_tail_stride(CH);
+    float* P = scr;                                                       // [RB][S] floored pooled values of the chunk
+    float* Mt = scr + RB * S;                                             // [RB][S] smoothed values
+    const int TP = q.TP, mode = q.mode;
+    const SlotGeom geo = q.geo;
+    const bool scaled = q.clip_scale2 != nullptr, pcen = (mode & 1) != 0;
+    auto ld = [](const float* a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    auto wave_fence = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); };
+    const int nrows_all = (b_hi - b_lo) * q.F;
+    if (nrows_all <= 0) return;
+    const int per = nrows_all / NW, rem = nrows_all - per * NW;
+    const int my0 = b_lo * q.F + wave * per + min(wave, rem), mycnt = per + (wave < rem ? 1 : 0);
+    for (int r0 = 0; r0 < mycnt; r0 += RB) {
+        const int row0 = my0 + r0, nr = min(RB, mycnt - r0);
+        // lane -> its row of the point stage (lanes past the last row repeat it and store nothing), that row's coefficients and scale
+        const int rl = min(lane >> 4, nr - 1), jl = lane & (GF - 1);
+        const int rowl = row0 + rl, bl = rowl / q.F, fl = rowl - bl * q.F;
+        const FinCoef c = q.lds_coef ? static_cast<const FinCoef*>(q.lds_coef)[fl] : fin_coef(q, fl);
+        const float s2l = scaled ? q.clip_scale2[bl] : 1.0f;
+        const bool mine = (lane >> 4) < nr;
+        // lane -> its row of the recurrence (lanes past the last row repeat it: the same values to the same addresses)
+        const int re = min(lane, nr - 1);
+        FinCoef ce{};
+        ce.w = __shfl(c.w, GF * re);
+        ce.omw = __shfl(c.omw, GF * re);
+        const bool fast = pcen && __all(c.dl > 0.0f);                     // every row on the cancellation-free PCEN form
+        const float* prow = P + re * S;
+        float* mrow = Mt + re * S;
+        auto ema_group = [&](int g, float M) {                            // the GF frames from g GF on, of row `re`
+            float pv[GF];
+#pragma unroll
+            for (int k = 0; k < GF; ++k) pv[k] = prow[g * GF + k];
+#pragma unroll
+            for (int k = 0; k < GF; ++k) {
+                M = fin_ema_step(ce, pv[k], M);
+                mrow[g * GF + k] = M;
+            }
+            return M;
+        };
+        float carry = 0.0f;
+        for (int m0 = 0; m0 < TP; m0 += CH) {
+            const int nfr = min(CH, TP - m0);
+            wave_fence();                                                 // the previous chunk's reads of P and M are issued
+            // ---- (1) lane = frame, the batch's rows side by side: their loads are issued together from clamped, always valid
+            // addresses; a row's base address, bias and scale are wave-uniform (the coefficients sit in lane 16 r)
+            for (int j0 = 0; j0 < nfr; j0 += 64) {
+                const bool on = j0 + lane < nfr;
+                const int j = min(j0 + lane, nfr - 1), m = m0 + j;
+                float a[RB], b2[RB], c3[RB];
+                int ns = 1;
+                if (q.lds_sums) {                                         // the slots were added up in LDS (a + b: the same rounding)
+#pragma unroll
+                    for (int r = 0; r < RB; ++r) {
+                        a[r] = q.lds_sums[(size_t)(row0 + min(r, nr - 1) - q.lds_row0) * TP + m];
+                        b2[r] = c3[r] = 0.0f;
+                    }
+                } else {
+                    ns = fin_slots(geo, m);
+#pragma unroll
+                    for (int r = 0; r < RB; ++r) {
+                        const float* pr = q.part + (size_t)(row0 + min(r, nr - 1)) * geo.nslot * TP + m;
+                        a[r] = ld(pr);
+                        b2[r] = ld(pr + (ns > 1 ? TP : 0));
+                        c3[r] = geo.nslot > 2 ? ld(pr + (ns > 2 ? 2 * TP : 0)) : 0.0f;
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < RB; ++r) {
+                    const float bias = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c.bias), GF * r));
+                    const float s2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s2l), GF * r));
+                    float v = fin_pooled(a[r], b2[r], c3[r], ns, scaled, s2, bias);
+                    if (on && r < nr) {
+                        if (q.raw_out) q.raw_out[(size_t)(row0 + r) * TP + m] = v;
+                        if (!(mode & 8)) v = pooled_floor(v);
+                        P[r * S + j] = v;
+                    }
+                }
+            }
+            wave_fence();                                                 // P is written
+            const int ng = (nfr + GF - 1) / GF;
+            const size_t orow = (size_t)rowl * TP + m0;
+            if (fast) {
+                // ---- (2) + (3): the recurrence runs one group ahead of the point stage.  In the chunk's last group it walks past the
+                // last frame over stale scratch: values nothing reads (a chunk that is cut short is the row's last, so its carry is
+                // not used either).
+                float M = ema_group(0, m0 == 0 ? prow[0] : carry);        // state starts at p_0 (postprocessing.py:15)
+                for (int g = 0; g < ng; ++g) {
+                    wave_fence();                                         // M of group g is written
+                    const int j = g * GF + jl;
+                    const float pv = P[rl * S + j], mv = Mt[rl * S + j];
+                    if (g + 1 < ng) M = ema_group(g + 1, M);
+                    const float o = fin_point_pcen_pos(c, q.floor_, pv, mv);
+                    if (mine && j < nfr) fin_store(q, orow + j, o);
+                }
+                carry = M;
+            } else {
+                if (pcen) {
+                    float M = m0 == 0 ? prow[0] : carry;
+#pragma nounroll
+                    for (int j = 0; j < nfr; ++j) {
+                        M = fin_ema_step(ce, prow[j], M);
+                        mrow[j] = M;
+                    }
+                    carry = M;
+                    wave_fence();
+                }
+#pragma nounroll
+                for (int g = 0; g < ng; ++g) {
+                    const int j = g * GF + jl;
+                    const float o = fin_point(c, mode, q.floor_, P[rl * S + j], pcen ? Mt[rl * S + j] : 0.0f);
+                    if (mine && j < nfr) fin_store(q, orow + j, o);
+                }
+            }
+        }
+    }
+}
+
 // The kernel's body; the two __global__ templates below name its instances (leaf_fft_wg_kernel: fp32 samples, rows of <= 128
 // frames -- what the default forward runs; leaf_fft_wg_kernel_var: every other (sample kind, tail) pair).
 template <int SK, int SHOP, int NW, bool STREAM, int XK, int TAILC>
@@ -561,6 +701,10 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
     int* q = reinterpret_cast<int*>(ring + 2 * kWgRingFwdFloat2);         // q_next | fwd_cnt[2] | inv_cnt[2]
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane0 = tid & 63;
+#if LEAF_TRACE
+    const unsigned long long tr_entry = __builtin_amdgcn_s_memtime();    // kernel entry (written behind the first barrier: WG_STAMP_AT)
+    const unsigned long long tr_entry_rt = __builtin_amdgcn_s_memrealtime();   // ... on the 100 MHz clock too: the shader clock follows from the pair
+#endif
     float* scr = reinterpret_cast<float*>(q + kWgQueueInts) + (size_t)wave * SCRF;
     // STREAM: frame ring [RING][FPS] (one accumulator per frame and filter: the blocks a window meets ADD their sums, the
     // finalize reads it and puts the zero back) and the EMA state [FPS] behind the waves' scratch
@@ -647,12 +791,27 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
 #define WG_STAMP(tag)                                                                                           \
     do {                                                                                                        \
         if (LEAF_TRACE == 2 && (tag) != 1 && (tag) != 2 && (tag) < 8) break;   /* 2: task starts and finalize stamps only */ \
-        if (blockIdx.x == 0 && wave < 16 && lane0 == 0 && tr_n < 64)                                            \
+        if (blockIdx.x == 0 && wave < 16 && lane0 == 0 && tr_n < 56)                                            \
             p.trace[wave * 64 + tr_n] = ((unsigned long long)(tag) << 56) | (__builtin_amdgcn_s_memtime() & 0x00FFFFFFFFFFFFFFull); \
         ++tr_n;                                                                                                 \
     } while (0)
+    // the launch's fixed costs -- start, drain, tail -- at fixed slots behind the 56 running stamps of a wave (every trace level):
+    // slot 56 kernel entry (tag 14), 57 out of the first barrier (15), 58 the workgroup's first spectrum published (16: the wave
+    // that published it), 59 the wave's last task done (17), 60 out of the drain barrier (18), 61 the wave's rows finalized (19)
+    // 62 / 63: the 100 MHz clock (s_memrealtime) at kernel entry and beside slot 61 (tags 20 / 21)
+#define WG_STAMP_AT(slot, tag, when)                                                                            \
+    do {                                                                                                        \
+        if (blockIdx.x == 0 && wave < 16 && lane0 == 0)                                                         \
+            p.trace[wave * 64 + (slot)] = ((unsigned long long)(tag) << 56) | ((when) & 0x00FFFFFFFFFFFFFFull); \
+    } while (0)
+#define WG_STAMP_NOW(slot, tag) WG_STAMP_AT(slot, tag, __builtin_amdgcn_s_memtime())
+    WG_STAMP_NOW(57, 15);
+    WG_STAMP_AT(56, 14, tr_entry);
+    WG_STAMP_AT(62, 20, tr_entry_rt);
 #else
 #define WG_STAMP(tag) do { } while (0)
+#define WG_STAMP_AT(slot, tag, when) do { } while (0)
+#define WG_STAMP_NOW(slot, tag) do { } while (0)
 #endif
 
     constexpr int PADL = SK / 2 + SK % 2 - 1;
@@ -677,6 +836,7 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
         if (lane0 == 0) { q[5] = gb0 / p.nblk; q[6] = gb0 % p.nblk; }
         wg_release();
         if (lane0 == 0) __hip_atomic_fetch_add(&q[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        WG_STAMP_NOW(58, 16);
     }
     if (early_me) {
         // fwd(eset): ring slot eset, generation 0 -- no reader of an earlier occupant to wait for; published as the queue's forward task does
@@ -694,6 +854,7 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
         if (lane0 == 0) { q[5 + 2 * eset] = eb; q[6 + 2 * eset] = ec; }
         wg_release();
         if (lane0 == 0) __hip_atomic_fetch_add(&q[1 + eset], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (eset == 0) WG_STAMP_NOW(58, 16);
     }
     const int first_gb = deal.start((int)blockIdx.x);
     const int nset = deal.count((int)blockIdx.x);                         // blocks of this workgroup
@@ -870,6 +1031,7 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
                 if (lane == 0) { q[5 + 2 * slot] = fb; q[6 + 2 * slot] = fc; }    // the block's coordinates, for its readers
                 wg_release();
                 if (lane == 0) __hip_atomic_fetch_add(&q[1 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (set == 0) WG_STAMP_NOW(58, 16);
             }
             // rq is redefined UNCONDITIONALLY here (row 0 when the next task is not an inverse one), so that the previous
             // row is dead throughout this branch -- carried through the forward transform it would be spilled every task
@@ -1064,23 +1226,28 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
         set = nset_i;
         role = nrole;
     }
+    WG_STAMP_NOW(59, 17);                                                 // this wave's last task is done
     // ---- clip-resident finalize: every partial sum of a clip this workgroup owns outright was written by its own waves.
-    // Release (the stores have reached L2) - barrier - then one wave per pair of (clip, filter) rows: bias, floor, EMA scan,
-    // PCEN (fft_finalize_rows; the partial sums are read past the vector cache).  Clips that straddle two workgroups are
-    // left to fft_finalize_kernel.
-    if (!STREAM && p.fin_fused) {
-        const int b_lo = (first_gb + p.nblk - 1) / p.nblk, b_hi = (first_gb + nset) / p.nblk;
-        // <= 64 filters' rows per tile
-        constexpr int TR = (HALF || NW < 10) ? 32 : 64;                    // (fewer waves -- A/B builds -- hold a smaller tile)
-        static_assert((size_t)NW * SCRF >= (size_t)fin_tile_floats<TR, 64>() && (size_t)NW * SCRF >= (size_t)fin_tile_floats_single<TR, 128>(),
-                      "the transposition scratch of all waves holds a finalize tile");
-        FinParams fin = p.fin;
-        if (lds_sums) {
-            fin.lds_sums = lsum;
-            fin.lds_row0 = b_lo * p.F;
-            fin.lds_coef = lcoef;
+    // Release (the stores have reached L2) - barrier - then every wave finalizes the rows dealt to it in its own scratch
+    // (wg_tail_rows: bias, floor, EMA, PCEN; the partial sums are read past the vector cache); no barrier behind this one.
+    // Clips that straddle two workgroups are left to fft_finalize_kernel.
+    if constexpr (!STREAM) {
+        if (p.fin_fused) {
+            const int b_lo = (first_gb + p.nblk - 1) / p.nblk, b_hi = (first_gb + nset) / p.nblk;
+            static_assert(SCRF >= wg_tail_floats(TAILC), "a wave's transposition scratch holds its rows of a chunk");
+            FinParams fin = p.fin;
+            if (lds_sums) {
+                fin.lds_sums = lsum;
+                fin.lds_row0 = b_lo * p.F;
+                fin.lds_coef = lcoef;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __syncthreads();                                              // every task is done: the scratch is free
+            WG_STAMP_NOW(60, 18);
+            wg_tail_rows<NW, TAILC>(fin, b_lo, b_hi, scr, wave, lane0);
+            WG_STAMP_NOW(61, 19);
+            WG_STAMP_AT(63, 21, __builtin_amdgcn_s_memrealtime());
         }
-        wg_tail_finalize<TR, TAILC>(fin, b_lo, b_hi, reinterpret_cast<float*>(q + kWgQueueInts), tid, NW * 64);   // every task is done: the scratch is free
     }
 }
 
