@@ -762,7 +762,7 @@ struct BandGeom {
 // has in the frame ring / the partial-sum buffer); mlo .. mhi: the frames whose window meets the block.
 template <int A, int SK, int SHOP, bool N4K = false, typename Mid, typename Out, typename Stamp>
 __device__ __forceinline__ void band_task(const FftParams& p, const float (&rq)[32], const float2* Aring, const int* mem, const int* elist,
-                                          const float2* twl, float* scr, unsigned scr_lds, int* inv_cnt, int c, int mlo, int mhi, int lane,
+                                          const float2* twl, float* scr, unsigned scr_lds, int* q, int slot, int c, int mlo, int mhi, int lane,
                                           Mid&& mid, Out&& out, Stamp&& stamp) {
     using GEO = BandGeom<A, SK, SHOP, N4K>;
     constexpr int LPF = band_lpf(A), D = GEO::D, G = band_d(A), RL = GEO::RL;
@@ -804,8 +804,7 @@ __device__ __forceinline__ void band_task(const FftParams& p, const float (&rq)[
         pairs(std::integral_constant<int, 1>{});
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(zre[31]), "v"(zim[31]) : "memory");
-    wg_release();
-    if (lane == 0) __hip_atomic_fetch_add(inv_cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    wg_reader_done(q, slot, lane);                                       // (q, slot: the caller's task queue and the block's ring slot)
     stamp(4);                                                            // spectral multiply done
     band_dit16_stage<2, 0>(zre, zim);
     band_dit16_stage<2, 16>(zre, zim);

@@ -18,13 +18,15 @@
 // inv(i,f) = spectral multiply with filter f + inverse transform + |.|^2 + pooling (the arithmetic of
 // leaf_fft_kernel's static-geometry path; results differ from it only by the rounding of the mirrored upper half-spectrum,
 // ~1e-7 relative, so a clip is bit-identical across batches served by THIS kernel, not across the two kernels).  Dependencies are two monotonic counters per slot:
-//     inv(i,f) waits for  fwd_cnt[slot] >= (i >> 1) + 1          (the spectrum is there)
-//     fwd(i)   waits for  inv_cnt[slot] >= (i >> 1) * F          (every reader of the slot's previous occupant is done)
+//     inv(i,f) waits for  spectrum_cnt[slot] >= (i >> 1) + 1     (the spectrum is there: wg_acquire_block)
+//     fwd(i)   waits for  readers_cnt[slot] >= (i >> 1) * F      (every reader of the slot's previous occupant is done)
+// (the queue's ints, the protocol's operations and the loads every workgroup kernel shares: leaf_wg_queue.hpp)
 // Because fwd(i+1) is queued BEFORE set i's inverse tasks, one wave computes the next spectrum while the other eleven
 // work on the current block, and nobody waits for it.  Deadlock-free: a task only ever waits for tasks queued before it.
 #pragma once
 #include <type_traits>
 #include "leaf_fft.hpp"
+#include "leaf_wg_queue.hpp"        // the task queue, its protocol, the block and spectrum-row loads: shared by all workgroup kernels
 
 namespace {
 
@@ -34,22 +36,6 @@ constexpr int kWgRingFwdFloat2 = kWgFwdBins + 8;   // transform yields all 2048 
                                                // kb .. kb + M - 1 < 1152 as they lie (bins above 1024 are the conjugate mirror of a real block's spectrum).  128 bins
                                                // beyond Nyquist, not 256: with 2 x 2 KB more the streaming-finalize instance would fall from a 64-frame ring to 32
                                                // (lag 6 -> 2, +5 % on BASELINE configs[3] / [4]); the default bank's top filter needs 111
-constexpr int kWgQueueInts = 16;               // q_next, fwd_cnt[2], inv_cnt[2], {clip, block-in-clip} per ring slot, [11..12] blocks
-                                               // finalized per parity (STREAM kernels; their per-block counters live behind their ring)
-
-// The queue protocol between the waves of a workgroup: data (ring slots, block coordinates, shared sums) is written with plain LDS
-// stores, then a counter moves (relaxed atomic add by lane 0) and the readers spin on it (relaxed atomic loads).  The ordering
-// is carried by FENCES restricted to the LDS address space: release before the counter moves, acquire after the spin.  On
-// gfx950 the release fence is the s_waitcnt lgkmcnt(0) these sites issued by hand in round 2 and the acquire fence emits no
-// instruction (a wave's LDS operations execute in order) -- the generated code is unchanged -- but the compiler now KNOWS it
-// may not move LDS accesses across them; the unrestricted fences would also wait for the global loads in flight (table
-// prefetches), which the protocol does not need.
-__device__ __forceinline__ int wg_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void wg_release() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); }
-__device__ __forceinline__ void wg_wait_ge(const int* p, int need) {
-    while (wg_ld(p) < need) __builtin_amdgcn_s_sleep(1);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 // ---- wave-level 2048-point FFT, LDS-lean variant of fft2048 (same arithmetic, same register conventions) ----------
 // At three waves per SIMD the LDS pipe (one per CU) is as busy as the VALUs (profiles/r02), so the transposes and table
@@ -274,8 +260,60 @@ __device__ __forceinline__ void lds_stream16q(unsigned addr, Body body) {
 #include "leaf_band.hpp"           // band-limited filter tasks (uses the LDS helpers above)
 namespace {
 
+// The spectral multiply Z = conj(A' R_f) of a filter task, fused with the first decimation-in-time stage of the transform that follows
+// (pairs of rows (k, k + 16), unit twiddles; the transform is then called with SKIP1).  A = the block's spectrum in the ring, bins
+// 0..1024; rq[k] = R_f[64 k + lane].  Rows 0..15 come straight from the ring, rows 16..31 mirrored (A'[N - e] = conj(A'[e])): two streams
+// of 16 rows, ascending from A[lane], and the mirror A[2048 - 64 k - lane], k = 16..31, read as rows 15..0 of the base A[64 - lane], so
+// row k + 16 is hi[k].  With za = conj(A'[k]) R[k] and zb = the mirrored row's product,
+//     out[k] = za + zb,  out[k + 16] = za - zb   as one product and two FMAs per component -- 6 instructions per pair of rows
+// instead of 4 products + 4 additions.  8-row chunks with counted waits: all 32 ring reads in flight at once would need 64 registers
+// next to rq and Z.  (The counted waits are exact when no older LDS operation of the wave is outstanding; an older one only makes
+// them wait longer.)
+// Called by the backward kernels (wg_bwd_filter).  leaf_fft_wg_body and leaf_fft_wgg_kernel keep their written-out copies: with the call
+// in its place the compiler allocated their registers differently and the STREAM instances and the run-time-geometry forward measured
+// 0.6-0.9 % slower (profiles/wg_shared_protocol.txt).
+__device__ __forceinline__ void wg_multiply_stage1(const float2* A, int lane, const float (&rq)[32], float (&zre)[32], float (&zim)[32]) {
+    const unsigned a_lo = lds_addr(A + lane), a_hi = lds_addr(A + (kFftN - 64 * 31) - lane);
+    v2f lo[16], hi[16];
+    auto rd = [&](auto kk) {
+        constexpr int k = decltype(kk)::value;
+        if constexpr (k < 16) lds_rd8<512 * k>(lo[k], a_lo);
+        else lds_rd8<512 * (31 - k)>(hi[k - 16], a_hi);
+    };
+    // chunk 0: rows 0..7, chunk 1: rows 8..15, chunk 2: rows 16..23, chunk 3: rows 24..31
+#define LEAF_RD8(B) rd(std::integral_constant<int, B + 0>{}); rd(std::integral_constant<int, B + 1>{}); \
+                    rd(std::integral_constant<int, B + 2>{}); rd(std::integral_constant<int, B + 3>{}); \
+                    rd(std::integral_constant<int, B + 4>{}); rd(std::integral_constant<int, B + 5>{}); \
+                    rd(std::integral_constant<int, B + 6>{}); rd(std::integral_constant<int, B + 7>{});
+    v2f(&lo0)[8] = *reinterpret_cast<v2f(*)[8]>(&lo[0]);
+    v2f(&lo1)[8] = *reinterpret_cast<v2f(*)[8]>(&lo[8]);
+    v2f(&hi0)[8] = *reinterpret_cast<v2f(*)[8]>(&hi[0]);
+    v2f(&hi1)[8] = *reinterpret_cast<v2f(*)[8]>(&hi[8]);
+    auto pair = [&](int k) {
+        const float ra = rq[k], rb = rq[k + 16];
+        const float tr_ = lo[k].x * ra, ti_ = -(lo[k].y * ra);
+        zre[k] = fmaf(hi[k].x, rb, tr_);
+        zim[k] = fmaf(hi[k].y, rb, ti_);
+        zre[k + 16] = fmaf(-hi[k].x, rb, tr_);
+        zim[k + 16] = fmaf(-hi[k].y, rb, ti_);
+    };
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // the counted waits below see only these reads
+    LEAF_RD8(0) LEAF_RD8(16) LEAF_RD8(8)
+    lds_wait8<8>(lo0);
+    lds_wait8<8>(hi0);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) pair(k);
+    LEAF_RD8(24)
+    lds_wait8<0>(lo1);
+    lds_wait8<0>(hi1);
+#pragma unroll
+    for (int k = 8; k < 16; ++k) pair(k);
+#undef LEAF_RD8
+}
+
 // SKIP1: the caller has already run the first decimation-in-time stage (registers (k, k + 16), unit twiddles) -- fused with the
-// spectral multiply that produced the input (wg_multiply_stage1)
+// spectral multiply that produced the input (wg_multiply_stage1, above, in the backward kernels; the two forward kernels of the
+// 2048-sample plan carry the same sequence written out in their task loops)
 template <bool HALF, bool SKIP1 = false>
 __device__ __forceinline__ void fft2048w(float (&re)[32], float (&im)[32], float* scr, unsigned scr_lds, const float2* twl,
                                          const float2* twh, int lane) {
@@ -373,31 +411,6 @@ __device__ __forceinline__ void fft2048w(float (&re)[32], float (&im)[32], float
     fft32_dit_stage<16>(re, im);                         // register i <-> k' = brev5(i): element 64 k' + lane
 }
 
-// Task ids over a DENSE grid of F + 1 slots per set: task 0 = fwd(0); task 1 + i (F + 1) + r = slot r of set i, slot 0 being
-// fwd(i + 1) and slots 1..F the set's filters.  u / (F + 1) by multiply-high with M = ceil(2^32 / (F + 1)) -- exact while
-// u (M (F + 1) - 2^32) < 2^32, i.e. u < 2^32 / (F + 1); a plain division beyond that (`exact` = false).  (A power-of-two grid
-// decoded by shifts left 23 of 64 slots empty at F = 40 -- 63 of 128 at F = 64 -- each costing a queue pull and a wasted
-// spectrum-row prefetch: tools/trace_wg.py.)
-struct WgTaskGrid {
-    unsigned n, magic;
-    bool exact;
-};
-__device__ __forceinline__ WgTaskGrid wg_task_grid(int F, int nset) {
-    WgTaskGrid g;
-    g.n = (unsigned)F + 1u;
-    g.magic = (unsigned)((0x100000000ull + g.n - 1u) / g.n);
-    g.exact = (unsigned long long)(nset > 0 ? nset : 1) * g.n * g.n < 0x80000000ull;
-    return g;
-}
-__device__ __forceinline__ void wg_task_decode(const WgTaskGrid& g, int t, int& set, int& role) {
-    if (t == 0) { set = 0; role = 0; return; }
-    const unsigned u = (unsigned)(t - 1);
-    const unsigned qv = g.exact ? __umulhi(u, g.magic) : u / g.n;
-    set = (int)qv;
-    role = (int)(u - qv * g.n);
-    if (role == 0) set += 1;                                              // the NEXT set's spectrum, ahead of this set's filters
-}
-
 // floats of dynamic LDS for NW waves
 constexpr int fft_wg_scr_floats(int NW) { return NW > 12 ? kWgScrHalfFloats : kWgScrFloats; }   // > 12 waves: half buffer
 constexpr size_t fft_wg_lds_bytes(int NW, int SK) {
@@ -481,10 +494,10 @@ constexpr size_t fft_wg_stream_lds_bytes(int NW, int SK, int ring, int F) {     
 // share a loop: a wave-uniform select of the conversion); mixed fp32; mixed PCM16 (leaf_common.hpp; a mixed load is ~3 KB of code
 // and the kernel has two load sites, so the two mixed sample types are an instance each).  Since the row-owned tail (wg_tail_rows,
 // below) TAILC only selects the chunk length of a row, 128 or 64 frames; the instance set and the host's choice by T' are as they were.
-constexpr int kWgXF32 = 0, kWgX16 = 1, kWgXMix = 2, kWgXMix16 = 3;
 // The STREAM instances keep the choice at run time (kWgXAny: the three loops of one load site, as before the split): they do not take the
 // early path, so they have one load site, and with a single loader they measured 0.6-1.3 % slower at the shapes that run them
 // (profiles/early_forward.txt) -- the split stays where the second load site needs it.
+constexpr int kWgXF32 = 0, kWgX16 = 1, kWgXMix = 2, kWgXMix16 = 3;
 constexpr int kWgXAny = 4;
 // The block gb of the launch, rotated left by padL samples, into the wave's registers: are[r] = sample 64 r + lane of the rotated
 // block, zero outside [0, T) (both partners, mixed); (b, c) = the block's clip and its index in the clip.  The one load site of the
@@ -698,7 +711,7 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
     float2* twl = reinterpret_cast<float2*>(wsm);                        // [32][64]
     float2* twh = twl + 32 * 64;                                          // [32][2]
     float2* ring = twh + 64;                                              // [2][kWgRingFwdFloat2]
-    int* q = reinterpret_cast<int*>(ring + 2 * kWgRingFwdFloat2);         // q_next | fwd_cnt[2] | inv_cnt[2]
+    int* q = reinterpret_cast<int*>(ring + 2 * kWgRingFwdFloat2);         // the task queue (leaf_wg_queue.hpp)
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane0 = tid & 63;
 #if LEAF_TRACE
@@ -833,9 +846,7 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
         const int gb0 = deal.start((int)blockIdx.x);
 #pragma unroll
         for (int k = 0; k < kWgFwdBins / 64; ++k) ring[64 * k + lane0] = sv[k];
-        if (lane0 == 0) { q[5] = gb0 / p.nblk; q[6] = gb0 % p.nblk; }
-        wg_release();
-        if (lane0 == 0) __hip_atomic_fetch_add(&q[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        wg_publish(q, 0, gb0 / p.nblk, gb0 % p.nblk, lane0);
         WG_STAMP_NOW(58, 16);
     }
     if (early_me) {
@@ -851,9 +862,7 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
             const int k = brev5(i);
             if (k < kWgFwdBins / 64) A[64 * k + lane0] = make_float2(ex[i], eim[i]);
         }
-        if (lane0 == 0) { q[5 + 2 * eset] = eb; q[6 + 2 * eset] = ec; }
-        wg_release();
-        if (lane0 == 0) __hip_atomic_fetch_add(&q[1 + eset], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        wg_publish(q, eset, eb, ec, lane0);
         if (eset == 0) WG_STAMP_NOW(58, 16);
     }
     const int first_gb = deal.start((int)blockIdx.x);
@@ -862,28 +871,13 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
     const int* tdesc = bl + kBandPlanHead;
     const int* bmem = tdesc + p.F + 4;
     (void)tdesc; (void)bmem;
-    const WgTaskGrid grid = wg_task_grid(NT, nset);                        // NT + 1 slots per set
-    const int ntasks = nset > 0 ? 1 + nset * (NT + 1) : 0;
-    auto pull = [&]() {
-        int v = 0;
-        if (lane0 == 0) v = __hip_atomic_fetch_add(&q[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return __builtin_amdgcn_readfirstlane(v);
-    };
-    // task -> (set, role): role 0 = forward transform of set `set`, role 1..F = filter role - 1 of set `set`
-    auto decode = [&](int t, int& set, int& role) { wg_task_decode(grid, t, set, role); };
+    const WgTaskCursor cur = wg_task_cursor(q, lane0, NT, nset);          // NT + 1 slots per set
     // descriptor of a filter task: class (0: one filter on 2048 points, 1 / 2: band task) | index << 2 (filter / first member)
     auto desc_of = [&](int role) {
         if (role <= 0 || role > NT) return 0;
         return band_on ? __builtin_amdgcn_readfirstlane(tdesc[role - 1]) : (role - 1) << 2;
     };
     float rq[32];                                                         // R_f[64 k + lane], natural row order
-    auto load_real_spectrum = [&](int f, int lane) {
-        const float* src = reinterpret_cast<const float*>(p.H) + (size_t)f * kFftN + lane;
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int k = 0; k < 32; ++k) rq[k] = src[64 * k];
-        asm volatile("" ::: "memory");
-    };
     // the 32 table values the task `role` starts with: a spectrum row, or the bins of a band task's windows (row 0 as a dummy
     // when there is no filter task)
     auto prefetch_task = [&](int role, int lane) {
@@ -892,14 +886,14 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
             if ((d & 3) == 1) { band_load_spectrum<16>(rq, reinterpret_cast<const float*>(p.H), bmem[(d >> 2) + lane / band_lpf(16)], lane); return; }
             if ((d & 3) == 2) { band_load_spectrum<32>(rq, reinterpret_cast<const float*>(p.H), bmem[(d >> 2) + lane / band_lpf(32)], lane); return; }
         }
-        load_real_spectrum(d >> 2, lane);
+        wg_load_real_spectrum(rq, p.H, d >> 2, lane);
     };
 
     // ---- STREAM: finalize the frames that set j's block completed (see the comment above the kernel); one wave, lane = filter
     auto stream_finalize = [&](int j) {
         // called by the wave that completed set j's last filter; blocks go out in order (EMA state, and set j - 1's sums)
         WG_STAMP(10);                                                     // finalize: waiting for the previous block's
-        if (j > 0) wg_wait_ge(&q[11 + ((j - 1) & 1)], ((j - 1) >> 1) + 1);
+        if (j > 0) wg_wait_ge(wgq_stream_out_cnt(q, (j - 1) & 1), ((j - 1) >> 1) + 1);
         WG_STAMP(8);                                                      // finalize: start
         __builtin_amdgcn_s_setprio(3);                                    // (see above: the launch's one dependent chain goes first)
         const int gb = first_gb + j;
@@ -993,17 +987,17 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
         __builtin_amdgcn_s_setprio(0);
         WG_STAMP(9);                                                      // finalize: done
         wg_release();                // ring entries read, EMA state written: block j is out
-        if (lane0 == 0) __hip_atomic_fetch_add(&q[11 + (j & 1)], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        wg_bump(wgq_stream_out_cnt(q, j & 1), lane0);
     };
     (void)stream_finalize;
 
     // Invariant at the loop head: (set, role) is the decoded current task, and when it is an inverse task its filter's
     // spectrum row has already been requested into rq (by the previous task, under its pooling).
     int seen_set = -1, seen_b = 0, seen_c = 0, seen_base = 0, seen_clip = 0;   // block coordinates of the set this wave last worked on
-    int t = pull(), set = 0, role = 0;
-    if (t < ntasks) decode(t, set, role);
+    int set = 0, role = 0;
+    int t = cur.next(set, role);
     prefetch_task(role, lane0);
-    while (t < ntasks) {
+    while (cur.has(t)) {
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         const int slot = set & 1, gen = set >> 1;
@@ -1018,36 +1012,30 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
 #pragma unroll
                 for (int r = 0; r < 32; ++r) aim[r] = 0.0f;
                 fft2048w<HALF>(are, aim, scr, scr_lds, twl, twh, lane);        // register i <-> bin 64 brev5(i) + lane
-                wg_wait_ge(&q[3 + slot], gen * NT);                       // the slot's previous readers are done
+                wg_wait_ge(wgq_readers_cnt(q, slot), gen * NT);           // the slot's previous readers are done
                 if constexpr (STREAM) {                                   // ... and the frames ours wrap onto in the ring are out
                     const int lag = wg_stream_lag(SK, SHOP, RING);        // (block set - lag: same parity, (lag / 2) generations back)
-                    if (set >= lag) wg_wait_ge(&q[11 + slot], gen - lag / 2 + 1);
+                    if (set >= lag) wg_wait_ge(wgq_stream_out_cnt(q, slot), gen - lag / 2 + 1);
                 }
 #pragma unroll
                 for (int i = 0; i < 32; ++i) {
                     const int k = brev5(i);
                     if (k < kWgFwdBins / 64) A[64 * k + lane] = make_float2(are[i], aim[i]);     // bins 0..1151: 1025.. for band windows that cross Nyquist
                 }
-                if (lane == 0) { q[5 + 2 * slot] = fb; q[6 + 2 * slot] = fc; }    // the block's coordinates, for its readers
-                wg_release();
-                if (lane == 0) __hip_atomic_fetch_add(&q[1 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                wg_publish(q, slot, fb, fc, lane);
                 if (set == 0) WG_STAMP_NOW(58, 16);
             }
             // rq is redefined UNCONDITIONALLY here (row 0 when the next task is not an inverse one), so that the previous
             // row is dead throughout this branch -- carried through the forward transform it would be spilled every task
-            t = pull();
-            if (t < ntasks) decode(t, set, role);
-            else role = 0;
+            t = cur.next(set, role);
             prefetch_task(role, lane);
             continue;
         }
         // ---- filter task `role` of the block in ring slot `slot`
         const int tdsc = desc_of(role);
         const int f = tdsc >> 2;
-        if (set != seen_set) {                                            // this wave's first filter of the block: once the
-            wg_wait_ge(&q[1 + slot], gen + 1);                            // spectrum is in the ring it stays until every filter is done
-            seen_b = __builtin_amdgcn_readfirstlane(wg_ld(&q[5 + 2 * slot]));
-            seen_c = __builtin_amdgcn_readfirstlane(wg_ld(&q[6 + 2 * slot]));
+        if (set != seen_set) {                                            // this wave's first filter of the block
+            wg_acquire_block(q, slot, gen, seen_b, seen_c);
             if constexpr (STREAM) seen_base = ((set - seen_c) / p.nblk) * p.TP;   // clip ordinal in this workgroup x T' (aligned dealing)
             seen_clip = lds_sums ? (set - seen_c) / p.nblk : 0;           // clip ordinal in this workgroup (whole clips per workgroup)
             seen_set = set;
@@ -1064,8 +1052,7 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
                 // ---- band task: eight (four) narrow-band filters on 256- (512-) point transforms (leaf_band.hpp)
                 int tn_b = 0, nset_b = 0, nrole_b = 0;
                 auto mid = [&]() {
-                    tn_b = pull();
-                    if (tn_b < ntasks) decode(tn_b, nset_b, nrole_b);
+                    tn_b = cur.next(nset_b, nrole_b);
                     prefetch_task(nrole_b, lane);
                     return std::integral_constant<int, 32>{};             // 32 loads issued
                 };
@@ -1081,13 +1068,11 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
                         p.part[(((size_t)b * p.F + fid) * p.nslot + (c - first_block)) * p.TP + m] = v;
                 };
                 if ((tdsc & 3) == 1)
-                    band_task<16, SK, SHOP>(p, rq, A, bmem + (tdsc >> 2), bl + 4, twl, scr, scr_lds, &q[3 + slot], c, mlo, mhi, lane, mid, bout, stamp);
+                    band_task<16, SK, SHOP>(p, rq, A, bmem + (tdsc >> 2), bl + 4, twl, scr, scr_lds, q, slot, c, mlo, mhi, lane, mid, bout, stamp);
                 else
-                    band_task<32, SK, SHOP>(p, rq, A, bmem + (tdsc >> 2), bl + 4, twl, scr, scr_lds, &q[3 + slot], c, mlo, mhi, lane, mid, bout, stamp);
+                    band_task<32, SK, SHOP>(p, rq, A, bmem + (tdsc >> 2), bl + 4, twl, scr, scr_lds, q, slot, c, mlo, mhi, lane, mid, bout, stamp);
                 if constexpr (STREAM) {                                   // as below: the block's last task sends its frames out
-                    int done = 0;
-                    if (lane == 0) done = __hip_atomic_fetch_add(&sq[set & 7], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    done = __builtin_amdgcn_readfirstlane(done);
+                    const int done = wg_count(&sq[set & 7], lane);
                     if (done + 1 == ((set >> 3) + 1) * NT) stream_finalize(set);
                 }
                 WG_STAMP(7);
@@ -1145,8 +1130,7 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
 #undef LEAF_RD8
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(zre[31]), "v"(zim[31]) : "memory");
-        wg_release();
-        if (lane == 0) __hip_atomic_fetch_add(&q[3 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        wg_reader_done(q, slot, lane);
         WG_STAMP(4);                                                      // spectral multiply done
         fft2048w<HALF, true>(zre, zim, scr, scr_lds, twl, twh, lane);   // register i <-> samples 64 brev5(i) + lane
         WG_STAMP(5);                                                      // inverse transform done
@@ -1171,9 +1155,8 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
             for (int r = 0; r < NROW; ++r) er[r] = 64 * r + lane < Lv ? er[r] : 0.0f;
         }
         // next task: reserved now so that its filter's spectrum row streams in under the pooling
-        const int tn = pull();
         int nset_i = 0, nrole = 0;
-        if (tn < ntasks) decode(tn, nset_i, nrole);
+        const int tn = cur.next(nset_i, nrole);
         asm volatile("" ::"v"(er[0]), "v"(er[NROW - 1]));
         prefetch_task(nrole, lane);                                      // (row 0 as a dummy when there is no next filter)
         asm volatile("s_waitcnt vmcnt(32)" ::: "memory");                 // the pooling weights (issued before the 32 loads) have landed
@@ -1216,9 +1199,7 @@ __device__ __forceinline__ void leaf_fft_wg_body(const FftParams& p) {
             // frames go out NOW, before this wave can block on anything else.  (Looking at the count a task later saves the LDS
             // round trip per task, but a pending finalize on a wave that then waits for a spectrum whose forward task waits
             // for that very finalize is a deadlock -- it happened at F = 3, where a wave's next task is several blocks ahead.)
-            int done = 0;
-            if (lane == 0) done = __hip_atomic_fetch_add(&sq[set & 7], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            done = __builtin_amdgcn_readfirstlane(done);
+            const int done = wg_count(&sq[set & 7], lane);
             if (done + 1 == ((set >> 3) + 1) * NT) stream_finalize(set);
         }
         WG_STAMP(7);                                                      // pooling, reduction and stores issued

@@ -341,6 +341,41 @@ __device__ __forceinline__ T tab_ld(const void* ubase, unsigned voff, int const_
     return *reinterpret_cast<const T*>(static_cast<const char*>(ubase) + (size_t)voff + const_bytes);
 }
 
+// One half of a rotated 4096-sample block, the load of the three kernels of the 4096-sample plan (this one, leaf_fft_wgg4k_kernel,
+// leaf_fft_wgg4k_bwd_kernel): v[r] = sample n = win.start + ((2 (64 r + lane) + odd + win.rot) & 4095) of clip win.b, zero outside
+// [0, T) -- the even (odd = 0) or odd (odd = 1) samples, for the two half transforms.  One loop per sample kind, chosen once per half by
+// wave-uniform branches: mixed with the partner clip (waveform mixup, leaf_common.hpp; mc = mix_clip(..), once per block) as fp32 or
+// PCM16; else 16-bit (bfloat16 and PCM16 share the loop: a wave-uniform select of the conversion) or fp32.
+struct Wg4kWindow {
+    int b;                  // clip
+    int start;              // clip sample under the block's first sample: n_c - padL
+    int rot;                // the block is rotated left by this many samples: padL (static geometry) or K / 2
+};
+template <typename Sample>
+__device__ __forceinline__ void wg4k_half_rows(const Wg4kWindow& win, int odd, int lane, float (&v)[32], Sample sample) {
+#pragma unroll
+    for (int r = 0; r < 32; ++r) v[r] = sample(win.start + ((2 * (64 * r + lane) + odd + win.rot) & (kFft4N - 1)));
+}
+__device__ __forceinline__ void wg4k_load_half(const FftParams& p, bool mixed, const MixClip& mc, const Wg4kWindow& win, int odd, int lane,
+                                               float (&v)[32]) {
+    const size_t row = (size_t)win.b * p.T;
+    if (mixed) {
+        if (p.io_bf16 == kSamplePcm16) wg4k_half_rows(win, odd, lane, v, [&](int n) { return mix_sample<kSamplePcm16>(p.x, row, mc, n, p.T); });
+        else wg4k_half_rows(win, odd, lane, v, [&](int n) { return mix_sample<kSampleF32>(p.x, row, mc, n, p.T); });
+    } else if (p.io_bf16) {
+        const unsigned short* xh = static_cast<const unsigned short*>(p.x) + row;
+        const bool pcm = p.io_bf16 == kSamplePcm16;
+        wg4k_half_rows(win, odd, lane, v, [&](int n) {
+            const unsigned h = xh[min(max(n, 0), p.T - 1)];
+            const float w = pcm ? pcm16_widen((short)h) : __uint_as_float(h << 16);
+            return (n >= 0 && n < p.T) ? w : 0.0f;
+        });
+    } else {
+        const float* xb = static_cast<const float*>(p.x) + row;
+        wg4k_half_rows(win, odd, lane, v, [&](int n) { return (n >= 0 && n < p.T) ? xb[n] : 0.0f; });
+    }
+}
+
 template <int SK, int SHOP, int NW>
 __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(const FftParams p) {
     static_assert(SK == 801 && SHOP == 320, "the 4096-sample plan is instantiated for the 32 kHz LEAF geometry");
@@ -396,19 +431,12 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
     const int NT = band_on ? __builtin_amdgcn_readfirstlane(bl[0]) : p.F;
     const int* tdesc = bl + kBandPlanHead;
     const int* bmem = tdesc + p.F + 4;
-    const WgTaskGrid grid = wg_task_grid(NT, nset);                        // NT + 1 slots per set
-    const int ntasks = nset > 0 ? 1 + nset * (NT + 1) : 0;
-    auto pull = [&]() {
-        int v = 0;
-        if (lane0 == 0) v = __hip_atomic_fetch_add(&q[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return __builtin_amdgcn_readfirstlane(v);
-    };
-    auto decode = [&](int t, int& set, int& role) { wg_task_decode(grid, t, set, role); };
+    const WgTaskCursor cur = wg_task_cursor(q, lane0, NT, nset);          // NT + 1 slots per set
 
     int seen_set = -1, seen_b = 0, seen_c = 0;                            // block coordinates of the set this wave last worked on
-    int t = pull(), set = 0, role = 0;
-    if (t < ntasks) decode(t, set, role);
-    while (t < ntasks) {
+    int set = 0, role = 0;
+    int t = cur.next(set, role);
+    while (cur.has(t)) {
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         const int slot = set & 1, gen = set >> 1;
@@ -420,44 +448,17 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
                 const int gb = first_gb + set;
                 const int b = gb / p.nblk, c = gb - b * p.nblk;
                 const int n_c = c * LS;
-                const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
-                const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
-                const bool pcm = p.io_bf16 == kSamplePcm16;                // 16-bit PCM: the bf16 load, another conversion (wave-uniform select)
-                auto sample = [&](int i) -> float {                       // rotated block a'[i] = xz[n_c - padL + ((i + padL) mod 4096)]
-                    const int n = n_c - PADL + ((i + PADL) & (kFft4N - 1));
-                    if (p.io_bf16) {
-                        const unsigned v = xh[min(max(n, 0), p.T - 1)];
-                        const float w = pcm ? pcm16_widen((short)v) : __uint_as_float(v << 16);
-                        return (n >= 0 && n < p.T) ? w : 0.0f;
-                    }
-                    return (n >= 0 && n < p.T) ? xb[n] : 0.0f;
-                };
-                // waveform mixup in the load (leaf_common.hpp): the block's clip mixed with its partner, weights and partner row read
-                // once per block; ST: the compile-time sample type of the loop (fp32 / 16-bit PCM)
+                // the block's two halves (wg4k_load_half, leaf_fft_wg4k.hpp); mixed: the partner clip and the weights, read once per block
                 MixClip mc{};
                 if (p.mix_lam) mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
-                auto load_mixed = [&](float (&v)[32], int odd, auto st) {
-#pragma unroll
-                    for (int r = 0; r < 32; ++r) {
-                        const int i = 2 * (64 * r + lane) + odd;
-                        v[r] = mix_sample<decltype(st)::value>(p.x, (size_t)b * p.T, mc, n_c - PADL + ((i + PADL) & (kFft4N - 1)), p.T);
-                    }
-                };
-                auto load_half = [&](float (&v)[32], int odd) {
-                    if (p.mix_lam) {
-                        if (p.io_bf16 == kSamplePcm16) load_mixed(v, odd, std::integral_constant<int, kSamplePcm16>{});
-                        else load_mixed(v, odd, std::integral_constant<int, kSampleF32>{});
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 32; ++r) v[r] = sample(2 * (64 * r + lane) + odd);
-                    }
-                };
+                const Wg4kWindow win{b, n_c - PADL, PADL};
+                auto load_half = [&](float (&v)[32], int odd) { wg4k_load_half(p, p.mix_lam != nullptr, mc, win, odd, lane, v); };
                 float xre[32], xim[32];
                 load_half(xre, 0);
 #pragma unroll
                 for (int r = 0; r < 32; ++r) xim[r] = 0.0f;
                 fft2048w<false>(xre, xim, scr, scr_lds, twl, twh, lane);
-                wg_wait_ge(&q[3 + slot], gen * NT);                       // the slot's previous readers are done
+                wg_wait_ge(wgq_readers_cnt(q, slot), gen * NT);           // the slot's previous readers are done
 #pragma unroll
                 for (int i = 0; i < 32; ++i) A[64 * brev5(i) + lane] = make_float2(xre[i], xim[i]);
                 load_half(xre, 1);
@@ -475,12 +476,9 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
                     A[64 * k + lane] = make_float2(xe.x + tr, xe.y + ti);
                     if (k == 0 && lane == 0) A[2048] = make_float2(xe.x - tr, xe.y - ti);
                 }
-                if (lane == 0) { q[5 + 2 * slot] = b; q[6 + 2 * slot] = c; }
-                wg_release();
-                if (lane == 0) __hip_atomic_fetch_add(&q[1 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                wg_publish(q, slot, b, c, lane);
             }
-            t = pull();
-            if (t < ntasks) decode(t, set, role);
+            t = cur.next(set, role);
             continue;
         }
         // ---- filter task of the block in ring slot `slot`.  Odd sets walk the tasks backwards: the per-filter tables (16 KB each
@@ -489,10 +487,8 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
         const int ti = (set & 1) ? NT - role : role - 1;
         const int tdsc = band_on ? __builtin_amdgcn_readfirstlane(tdesc[ti]) : ti << 2;   // class (0: one filter, two 2048-point halves; 2: band task) | index << 2
         const int f = tdsc >> 2;
-        if (set != seen_set) {                                            // this wave's first filter of the block: once the
-            wg_wait_ge(&q[1 + slot], gen + 1);                            // spectrum is in the ring it stays until every filter is done
-            seen_b = __builtin_amdgcn_readfirstlane(wg_ld(&q[5 + 2 * slot]));
-            seen_c = __builtin_amdgcn_readfirstlane(wg_ld(&q[6 + 2 * slot]));
+        if (set != seen_set) {                                            // this wave's first filter of the block
+            wg_acquire_block(q, slot, gen, seen_b, seen_c);
             seen_set = set;
         }
         const int b = seen_b, c = seen_c;
@@ -517,8 +513,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
             }
             int tn_b = 0, nset_b = 0, nrole_b = 0;
             auto mid = [&]() {
-                tn_b = pull();
-                if (tn_b < ntasks) decode(tn_b, nset_b, nrole_b);
+                tn_b = cur.next(nset_b, nrole_b);
                 return 0;                                                 // no table loads for the next task
             };
             auto stamp = [&](int) {};
@@ -526,7 +521,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
                 const int first_block = max(0, m * SHOP - PADL) / LS;
                 p.part[(((size_t)b * p.F + fid) * p.nslot + (c - first_block)) * p.TP + m] = v;
             };
-            band_task<32, SK, SHOP, true>(p, rq, A, mem, bl + 4, twl, scr, scr_lds, &q[3 + slot], c, mlo, mhi, lane, mid, bout, stamp);
+            band_task<32, SK, SHOP, true>(p, rq, A, mem, bl + 4, twl, scr, scr_lds, q, slot, c, mlo, mhi, lane, mid, bout, stamp);
             t = tn_b;
             set = nset_b;
             role = nrole_b;
@@ -660,15 +655,13 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg4k_kernel(co
             step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
             step(std::integral_constant<int, 6>{}); step(std::integral_constant<int, 7>{});
         }
-        wg_release();
-        if (lane == 0) __hip_atomic_fetch_add(&q[3 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ring reads done
+        wg_reader_done(q, slot, lane);                                    // ring reads done
         load_weights(1);                                                  // the odd taps' weights, under the second transform
         fft2048w<false>(zre, zim, scr, scr_lds, twl, twh, lane);
         pin32(zre);
         pin32(zim);
-        const int tn = pull();                                            // next task reserved under the pooling
         int nset_i = 0, nrole = 0;
-        if (tn < ntasks) decode(tn, nset_i, nrole);
+        const int tn = cur.next(nset_i, nrole);                                      // next task reserved under the pooling
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the weights have landed
         const float v_odd = pool_half(std::integral_constant<int, 1>{}, pw);
         {

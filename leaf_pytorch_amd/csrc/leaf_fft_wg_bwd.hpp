@@ -128,10 +128,10 @@ __device__ __forceinline__ void wg_dx_accumulate(const FftParams& p, int f, int 
             float rv[8];
             // one chunk's loads at a time (registers): the chunk's POINTER is made opaque, in the global address space, so that
             // its eight loads differ by an immediate offset (an opaque index costs ~3 VALU per load in 64-bit address arithmetic)
-            const __attribute__((address_space(1))) float* q = (const __attribute__((address_space(1))) float*)rr + 64 * k0;
-            asm volatile("" : "+v"(q) : : "memory");
+            const __attribute__((address_space(1))) float* rk = (const __attribute__((address_space(1))) float*)rr + 64 * k0;
+            asm volatile("" : "+v"(rk) : : "memory");
 #pragma unroll
-            for (int j = 0; j < 8; ++j) rv[j] = q[64 * j];
+            for (int j = 0; j < 8; ++j) rv[j] = rk[64 * j];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 vre[brev5(k0 + j)] *= rv[j];
@@ -210,50 +210,6 @@ __device__ __forceinline__ void wg_dx_finish(const FftParams& p, const float2* g
         dst[n] = tS ? xre[i] + tS[n] : xre[i];
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                    // the slot's arrays are read before the slot can be released
-}
-
-// The recomputed forward of a backward task as the forward kernel does it (leaf_fft_wg_kernel): the spectral multiply
-// Z = conj(A' R_f) fused with the first decimation-in-time stage of the transform that follows (rows (k, k + 16), unit
-// twiddles): out[k] = za + zb, out[k + 16] = za - zb as one product and two FMAs per component -- 6 instructions per pair of
-// rows instead of 4 products + 4 additions; the transform is then called with SKIP1.
-__device__ __forceinline__ void wg_multiply_stage1(const float2* A, int lane, const float (&rq)[32], float (&zre)[32], float (&zim)[32]) {
-    // two streams of 16 rows: ascending from A[lane], and the mirror A[2048 - 64 k - lane], k = 16..31, read as rows 15..0 of the
-    // base A[64 - lane]: row k + 16 is hi[k]
-    const unsigned a_lo = lds_addr(A + lane), a_hi = lds_addr(A + (kFftN - 64 * 31) - lane);
-    v2f lo[16], hi[16];
-    auto rd = [&](auto kk) {
-        constexpr int k = decltype(kk)::value;
-        if constexpr (k < 16) lds_rd8<512 * k>(lo[k], a_lo);
-        else lds_rd8<512 * (31 - k)>(hi[k - 16], a_hi);
-    };
-#define LEAF_RD8(B) rd(std::integral_constant<int, B + 0>{}); rd(std::integral_constant<int, B + 1>{}); \
-                    rd(std::integral_constant<int, B + 2>{}); rd(std::integral_constant<int, B + 3>{}); \
-                    rd(std::integral_constant<int, B + 4>{}); rd(std::integral_constant<int, B + 5>{}); \
-                    rd(std::integral_constant<int, B + 6>{}); rd(std::integral_constant<int, B + 7>{});
-    v2f(&lo0)[8] = *reinterpret_cast<v2f(*)[8]>(&lo[0]);
-    v2f(&lo1)[8] = *reinterpret_cast<v2f(*)[8]>(&lo[8]);
-    v2f(&hi0)[8] = *reinterpret_cast<v2f(*)[8]>(&hi[0]);
-    v2f(&hi1)[8] = *reinterpret_cast<v2f(*)[8]>(&hi[8]);
-    auto pair = [&](int k) {
-        const float ra = rq[k], rb = rq[k + 16];
-        const float tr_ = lo[k].x * ra, ti_ = -(lo[k].y * ra);
-        zre[k] = fmaf(hi[k].x, rb, tr_);
-        zim[k] = fmaf(hi[k].y, rb, ti_);
-        zre[k + 16] = fmaf(-hi[k].x, rb, tr_);
-        zim[k + 16] = fmaf(-hi[k].y, rb, ti_);
-    };
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // the counted waits below see only these reads
-    LEAF_RD8(0) LEAF_RD8(16) LEAF_RD8(8)
-    lds_wait8<8>(lo0);
-    lds_wait8<8>(hi0);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) pair(k);
-    LEAF_RD8(24)
-    lds_wait8<0>(lo1);
-    lds_wait8<0>(hi1);
-#pragma unroll
-    for (int k = 8; k < 16; ++k) pair(k);
-#undef LEAF_RD8
 }
 
 // Backward of ONE filter on ONE block whose spectrum A' (bins 0..1024) sits in LDS at A; rq = R_f[64 k + lane].
@@ -406,9 +362,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
     float2* twh = twl + 32 * 64;
     float2* ring = twh + 64;                                              // A': [2][kWgRingFloat2]
     [[maybe_unused]] float2* gsum = ring + 2 * kWgRingFloat2;            // DX: G, Hermitian-folded: [2][kWgRingFloat2]
-    int* q = reinterpret_cast<int*>(ring + (DX ? 4 : 2) * kWgRingFloat2);
-    // q: 0 next task | 1,2 spectra stored per slot | 3,4 inverse tasks finished per slot | 5..8 (clip, block) per slot |
-    //    9,10 generations released per slot (all readers done) | 11,12 (DX) filters added to the slot's G, ever
+    int* q = reinterpret_cast<int*>(ring + (DX ? 4 : 2) * kWgRingFloat2);   // the task queue (leaf_wg_queue.hpp)
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane0 = tid & 63;
     float* scr = reinterpret_cast<float*>(q + kWgQueueInts) + (size_t)wave * SCRF;
@@ -439,14 +393,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
     const int* tdesc = bl + kBandPlanHead;
     const int* bmem = tdesc + p.F + 4;
     (void)tdesc; (void)bmem;
-    const WgTaskGrid grid = wg_task_grid(NT, nset);                        // NT + 1 slots per set
-    const int ntasks = nset > 0 ? 1 + nset * (NT + 1) : 0;
-    auto pull = [&]() {
-        int v = 0;
-        if (lane0 == 0) v = __hip_atomic_fetch_add(&q[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return __builtin_amdgcn_readfirstlane(v);
-    };
-    auto decode = [&](int t, int& set, int& role) { wg_task_decode(grid, t, set, role); };
+    const WgTaskCursor cur = wg_task_cursor(q, lane0, NT, nset);          // NT + 1 slots per set
     // descriptor of a filter task: class (0: one filter on 2048 points, 1 / 2: band task) | index << 2 (filter / first member)
     auto desc_of = [&](int role) {
         if (role <= 0 || role > NT) return 0;
@@ -455,23 +402,19 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
     auto row_of = [&](int role) { return desc_of(role); };
     float rq[32];
     // the 32 table values the task starts with: a spectrum row, or the bins of a band task's windows
-    auto load_real_spectrum = [&](int d, int lane) {
+    auto prefetch_task = [&](int d, int lane) {
         if constexpr (BANDK) {
             if ((d & 3) == 1) { band_load_spectrum<16>(rq, reinterpret_cast<const float*>(p.H), bmem[(d >> 2) + lane / band_lpf(16)], lane); return; }
             if ((d & 3) == 2) { band_load_spectrum<32>(rq, reinterpret_cast<const float*>(p.H), bmem[(d >> 2) + lane / band_lpf(32)], lane); return; }
         }
-        const float* src = reinterpret_cast<const float*>(p.H) + (size_t)(d >> 2) * kFftN + lane;
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int k = 0; k < 32; ++k) rq[k] = src[64 * k];
-        asm volatile("" ::: "memory");
+        wg_load_real_spectrum(rq, p.H, d >> 2, lane);
     };
 
     int seen_set = -1, seen_b = 0, seen_c = 0;                            // block coordinates of the set this wave last worked on
-    int t = pull(), set = 0, role = 0;
-    if (t < ntasks) decode(t, set, role);
-    load_real_spectrum(row_of(role), lane0);
-    while (t < ntasks) {
+    int set = 0, role = 0;
+    int t = cur.next(set, role);
+    prefetch_task(row_of(role), lane0);
+    while (cur.has(t)) {
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         const int slot = set & 1, gen = set >> 1;
@@ -526,7 +469,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
                     }
                 }
                 fft2048w<HALF>(are, aim, scr, scr_lds, twl, twh, lane);
-                wg_wait_ge(&q[9 + slot], gen);                            // the slot's previous occupant has been released
+                wg_wait_ge(wgq_released_cnt(q, slot), gen);                          // the slot's previous occupant has been released
 #pragma unroll
                 for (int i = 0; i < 32; ++i) {
                     const int k = brev5(i);
@@ -537,23 +480,17 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
                     float2* gS = gsum + slot * kWgRingFloat2;
                     for (int i = lane; i < kWgRingFloat2; i += 64) gS[i] = make_float2(0.0f, 0.0f);
                 }
-                if (lane == 0) { q[5 + 2 * slot] = b; q[6 + 2 * slot] = c; }
-                wg_release();
-                if (lane == 0) __hip_atomic_fetch_add(&q[1 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                wg_publish(q, slot, b, c, lane);
             }
-            t = pull();
-            if (t < ntasks) decode(t, set, role);
-            else role = 0;
-            load_real_spectrum(row_of(role), lane);
+            t = cur.next(set, role);
+            prefetch_task(row_of(role), lane);
             continue;
         }
         // ---- backward of filter f on the block in ring slot `slot`
         const int tdsc = desc_of(role);
         const int f = tdsc >> 2;
-        if (set != seen_set) {                                            // this wave's first filter of the block: once the
-            wg_wait_ge(&q[1 + slot], gen + 1);                            // spectrum is in the ring it stays until every filter is done
-            seen_b = __builtin_amdgcn_readfirstlane(wg_ld(&q[5 + 2 * slot]));
-            seen_c = __builtin_amdgcn_readfirstlane(wg_ld(&q[6 + 2 * slot]));
+        if (set != seen_set) {                                            // this wave's first filter of the block
+            wg_acquire_block(q, slot, gen, seen_b, seen_c);
             seen_set = set;
         }
         const int b = seen_b, c = seen_c;
@@ -568,23 +505,22 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
                 const int mhi = min(p.TP - 1, (n_c + Lv - 1 + PADL) / SHOP);
                 if ((tdsc & 3) == 1)
                     band_bwd_task<16, SK, SHOP, false, DX>(p, rq, A, bmem + (tdsc >> 2), bl + 4, twl, scr, scr_lds, b, c, gb, mlo, mhi, lane,
-                                                           gsum + slot * kWgRingFloat2, &q[11 + slot], gen * NT + role - 1);
+                                                           gsum + slot * kWgRingFloat2, wgq_dx_ticket(q, slot), gen * NT + role - 1);
                 else
                     band_bwd_task<32, SK, SHOP, false, DX>(p, rq, A, bmem + (tdsc >> 2), bl + 4, twl, scr, scr_lds, b, c, gb, mlo, mhi, lane,
-                                                           gsum + slot * kWgRingFloat2, &q[11 + slot], gen * NT + role - 1);
+                                                           gsum + slot * kWgRingFloat2, wgq_dx_ticket(q, slot), gen * NT + role - 1);
                 if constexpr (DX) {
                     if (role == NT) wg_dx_finish<HALF>(p, gsum + slot * kWgRingFloat2, nullptr, gb, PADL, lane, scr, scr_lds, twl, twh);
                 }
-                const int tn_b = pull();
                 int nset_b = 0, nrole_b = 0;
-                if (tn_b < ntasks) decode(tn_b, nset_b, nrole_b);
-                load_real_spectrum(row_of(nrole_b), lane);
+                const int tn_b = cur.next(nset_b, nrole_b);
+                prefetch_task(row_of(nrole_b), lane);
                 wg_release();
                 int old_b = 0;
-                if (lane == 0) old_b = __hip_atomic_fetch_add(&q[3 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (lane == 0) old_b = __hip_atomic_fetch_add(wgq_readers_cnt(q, slot), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 old_b = __builtin_amdgcn_readfirstlane(old_b);
                 if (old_b == gen * NT + NT - 1) {
-                    if (lane == 0) __hip_atomic_fetch_add(&q[9 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (lane == 0) __hip_atomic_fetch_add(wgq_released_cnt(q, slot), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
                 t = tn_b;
                 set = nset_b;
@@ -596,16 +532,15 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
         {
             float dummy_re[32], dummy_im[32];
             wg_bwd_filter<SK, SHOP, DX ? 2 : 0, HALF>(p, A, lane, f, b, c, rq, scr, scr_lds, twl, twh, dummy_re, dummy_im, amu, asg,
-                                                      dpw, gsum + slot * kWgRingFloat2, &q[11 + slot], gen * NT + role - 1);
+                                                      dpw, gsum + slot * kWgRingFloat2, wgq_dx_ticket(q, slot), gen * NT + role - 1);
         }
         if constexpr (DX) {
             if (role == NT) wg_dx_finish<HALF>(p, gsum + slot * kWgRingFloat2, nullptr, gb, PADL, lane, scr, scr_lds, twl, twh);
         }
         // next task: reserved now, its spectrum row requested before the reductions (rq is free from here)
-        const int tn = pull();
         int nset_i = 0, nrole = 0;
-        if (tn < ntasks) decode(tn, nset_i, nrole);
-        load_real_spectrum(row_of(nrole), lane);
+        const int tn = cur.next(nset_i, nrole);
+        prefetch_task(row_of(nrole), lane);
         amu = wave_sum(amu);
         asg = wave_sum(asg);
         dpw = wave_sum(dpw);
@@ -618,10 +553,10 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_bwd_kernel(
         // ---- this task is done with the slot; the wave that finishes the block's last filter releases it
         wg_release();
         int old = 0;
-        if (lane == 0) old = __hip_atomic_fetch_add(&q[3 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (lane == 0) old = __hip_atomic_fetch_add(wgq_readers_cnt(q, slot), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         old = __builtin_amdgcn_readfirstlane(old);
         if (old == gen * NT + NT - 1) {
-            if (lane == 0) __hip_atomic_fetch_add(&q[9 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (lane == 0) __hip_atomic_fetch_add(wgq_released_cnt(q, slot), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         t = tn;
         set = nset_i;

@@ -46,7 +46,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_kernel(con
     float2* twl = reinterpret_cast<float2*>(wsm);                        // [32][64]
     float2* twh = twl + 32 * 64;                                          // [32][2]
     float2* ring = twh + 64;                                              // [2][kWgRingFloat2]
-    int* q = reinterpret_cast<int*>(ring + 2 * kWgRingFloat2);            // q_next | fwd_cnt[2] | inv_cnt[2]
+    int* q = reinterpret_cast<int*>(ring + 2 * kWgRingFloat2);            // the task queue (leaf_wg_queue.hpp)
     const int PF = fft_wgg_front_floats(p.K), BP = HALF ? fft_wgg_back_floats(p.K) : fft_wgg_back_floats_full(p.K);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane0 = tid & 63;
@@ -71,32 +71,17 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_kernel(con
     const OwnedClips deal{p.B * p.nblk, (int)gridDim.x, p.nblk};
     const int first_gb = deal.start((int)blockIdx.x);
     const int nset = deal.count((int)blockIdx.x);      // blocks of this workgroup
-    const WgTaskGrid grid = wg_task_grid(p.F, nset);                       // F + 1 slots per set
-    const int ntasks = nset > 0 ? 1 + nset * (p.F + 1) : 0;
-    auto pull = [&]() {
-        int v = 0;
-        if (lane0 == 0) v = __hip_atomic_fetch_add(&q[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return __builtin_amdgcn_readfirstlane(v);
-    };
-    // task -> (set, role): role 0 = forward transform of set `set`, role 1..F = filter role - 1 of set `set`
-    auto decode = [&](int t, int& set, int& role) { wg_task_decode(grid, t, set, role); };
+    const WgTaskCursor cur = wg_task_cursor(q, lane0, p.F, nset);         // F + 1 slots per set
     auto row_of = [&](int role) { return role > 0 && role <= p.F ? role - 1 : 0; };   // spectrum row to prefetch
     float rq[32];                                                         // R_f[64 k + lane], natural row order
-    auto load_real_spectrum = [&](int f, int lane) {
-        const float* src = reinterpret_cast<const float*>(p.H) + (size_t)f * kFftN + lane;
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int k = 0; k < 32; ++k) rq[k] = src[64 * k];
-        asm volatile("" ::: "memory");
-    };
 
     // Invariant at the loop head: (set, role) is the decoded current task, and when it is an inverse task its filter's
     // spectrum row has already been requested into rq (by the previous task, under its pooling).
     int seen_set = -1, seen_b = 0, seen_c = 0;                            // block coordinates of the set this wave last worked on
-    int t = pull(), set = 0, role = 0;
-    if (t < ntasks) decode(t, set, role);
-    load_real_spectrum(row_of(role), lane0);
-    while (t < ntasks) {
+    int set = 0, role = 0;
+    int t = cur.next(set, role);
+    wg_load_real_spectrum(rq, p.H, row_of(role), lane0);
+    while (cur.has(t)) {
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         const int slot = set & 1, gen = set >> 1;
@@ -131,31 +116,25 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_kernel(con
                     }
                 }
                 fft2048w<HALF>(are, aim, scr, scr_lds, twl, twh, lane);        // register i <-> bin 64 brev5(i) + lane
-                wg_wait_ge(&q[3 + slot], gen * p.F);                      // the slot's previous readers are done
+                wg_wait_ge(wgq_readers_cnt(q, slot), gen * p.F);          // the slot's previous readers are done
 #pragma unroll
                 for (int i = 0; i < 32; ++i) {
                     const int k = brev5(i);
                     if (k < 16) A[64 * k + lane] = make_float2(are[i], aim[i]);
                     else if (k == 16 && lane == 0) A[1024] = make_float2(are[i], aim[i]);
                 }
-                if (lane == 0) { q[5 + 2 * slot] = b; q[6 + 2 * slot] = c; }      // the block's coordinates, for its readers
-                wg_release();
-                if (lane == 0) __hip_atomic_fetch_add(&q[1 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                wg_publish(q, slot, b, c, lane);
             }
             // rq is redefined UNCONDITIONALLY here (row 0 when the next task is not an inverse one), so that the previous
             // row is dead throughout this branch -- carried through the forward transform it would be spilled every task
-            t = pull();
-            if (t < ntasks) decode(t, set, role);
-            else role = 0;
-            load_real_spectrum(row_of(role), lane);
+            t = cur.next(set, role);
+            wg_load_real_spectrum(rq, p.H, row_of(role), lane);
             continue;
         }
         // ---- filter f of the block in ring slot `slot`
         const int f = role - 1;
-        if (set != seen_set) {                                            // this wave's first filter of the block: once the
-            wg_wait_ge(&q[1 + slot], gen + 1);                            // spectrum is in the ring it stays until every filter is done
-            seen_b = __builtin_amdgcn_readfirstlane(wg_ld(&q[5 + 2 * slot]));
-            seen_c = __builtin_amdgcn_readfirstlane(wg_ld(&q[6 + 2 * slot]));
+        if (set != seen_set) {                                            // this wave's first filter of the block
+            wg_acquire_block(q, slot, gen, seen_b, seen_c);
             seen_set = set;
         }
         const int b = seen_b, c = seen_c;
@@ -212,8 +191,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_kernel(con
 #undef LEAF_RD8
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(zre[31]), "v"(zim[31]) : "memory");
-        wg_release();
-        if (lane == 0) __hip_atomic_fetch_add(&q[3 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        wg_reader_done(q, slot, lane);
         fft2048w<HALF, true>(zre, zim, scr, scr_lds, twl, twh, lane);   // register i <-> samples 64 brev5(i) + lane
         if (even) {
             // the unpaired tap t = -K/2: y[cL + r] += w[-K/2] x[cL - padL + r]; with u = conj(y) in registers (register i <->
@@ -271,10 +249,9 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_kernel(con
             }
         }
         // next task: reserved now so that its filter's spectrum row streams in under the pooling
-        const int tn = pull();
         int nset_i = 0, nrole = 0;
-        if (tn < ntasks) decode(tn, nset_i, nrole);
-        load_real_spectrum(row_of(nrole), lane);
+        const int tn = cur.next(nset_i, nrole);
+        wg_load_real_spectrum(rq, p.H, row_of(nrole), lane);
         asm volatile("s_waitcnt vmcnt(32)" ::: "memory");                 // the taps (issued before the 32 loads) have landed
         // ---- Gaussian pooling: frame m = sum_j g_f[j] e[is_m + j], is_m = m hop - padL - n_c (window start relative to the
         // block; the zeros in front of and behind the energies stand for the parts of the window outside it).  Four frames

@@ -68,19 +68,12 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_kernel(c
     const OwnedClips deal{p.B * p.nblk, (int)gridDim.x, p.nblk};
     const int first_gb = deal.start((int)blockIdx.x);
     const int nset = deal.count((int)blockIdx.x);
-    const WgTaskGrid grid = wg_task_grid(p.F, nset);                       // F + 1 slots per set
-    const int ntasks = nset > 0 ? 1 + nset * (p.F + 1) : 0;
-    auto pull = [&]() {
-        int v = 0;
-        if (lane0 == 0) v = __hip_atomic_fetch_add(&q[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return __builtin_amdgcn_readfirstlane(v);
-    };
-    auto decode = [&](int t, int& set, int& role) { wg_task_decode(grid, t, set, role); };
+    const WgTaskCursor cur = wg_task_cursor(q, lane0, p.F, nset);         // F + 1 slots per set
 
     int seen_set = -1, seen_b = 0, seen_c = 0;                            // block coordinates of the set this wave last worked on
-    int t = pull(), set = 0, role = 0;
-    if (t < ntasks) decode(t, set, role);
-    while (t < ntasks) {
+    int set = 0, role = 0;
+    int t = cur.next(set, role);
+    while (cur.has(t)) {
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         const int slot = set & 1, gen = set >> 1;
@@ -92,44 +85,17 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_kernel(c
                 const int gb = first_gb + set;
                 const int b = gb / p.nblk, c = gb - b * p.nblk;
                 const int n_c = c * LS;
-                const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
-                const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
-                const bool pcm = p.io_bf16 == kSamplePcm16;                // 16-bit PCM: the bf16 load, another conversion (wave-uniform select)
-                auto sample = [&](int i) -> float {                       // rotated block a'[i] = xz[n_c - padL + ((i + padL) mod 4096)]
-                    const int n = n_c - PADL + ((i + ROT) & (kFft4N - 1));
-                    if (p.io_bf16) {
-                        const unsigned v = xh[min(max(n, 0), p.T - 1)];
-                        const float w = pcm ? pcm16_widen((short)v) : __uint_as_float(v << 16);
-                        return (n >= 0 && n < p.T) ? w : 0.0f;
-                    }
-                    return (n >= 0 && n < p.T) ? xb[n] : 0.0f;
-                };
-                // waveform mixup in the load (leaf_common.hpp): the block's clip mixed with its partner, weights and partner row read
-                // once per block; ST: the compile-time sample type of the loop (fp32 / 16-bit PCM)
+                // the block's two halves (wg4k_load_half, leaf_fft_wg4k.hpp); mixed: the partner clip and the weights, read once per block
                 MixClip mc{};
                 if (p.mix_lam) mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
-                auto load_mixed = [&](float (&v)[32], int odd, auto st) {
-#pragma unroll
-                    for (int r = 0; r < 32; ++r) {
-                        const int i = 2 * (64 * r + lane) + odd;
-                        v[r] = mix_sample<decltype(st)::value>(p.x, (size_t)b * p.T, mc, n_c - PADL + ((i + ROT) & (kFft4N - 1)), p.T);
-                    }
-                };
-                auto load_half = [&](float (&v)[32], int odd) {
-                    if (p.mix_lam) {
-                        if (p.io_bf16 == kSamplePcm16) load_mixed(v, odd, std::integral_constant<int, kSamplePcm16>{});
-                        else load_mixed(v, odd, std::integral_constant<int, kSampleF32>{});
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 32; ++r) v[r] = sample(2 * (64 * r + lane) + odd);
-                    }
-                };
+                const Wg4kWindow win{b, n_c - PADL, ROT};
+                auto load_half = [&](float (&v)[32], int odd) { wg4k_load_half(p, p.mix_lam != nullptr, mc, win, odd, lane, v); };
                 float xre[32], xim[32];
                 load_half(xre, 0);
 #pragma unroll
                 for (int r = 0; r < 32; ++r) xim[r] = 0.0f;
                 fft2048w<true>(xre, xim, scr, scr_lds, twl, twh, lane);
-                wg_wait_ge(&q[3 + slot], gen * p.F);                      // the slot's previous readers are done
+                wg_wait_ge(wgq_readers_cnt(q, slot), gen * p.F);          // the slot's previous readers are done
 #pragma unroll
                 for (int i = 0; i < 32; ++i) A[64 * brev5(i) + lane] = make_float2(xre[i], xim[i]);
                 load_half(xre, 1);
@@ -147,22 +113,17 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_kernel(c
                     A[64 * k + lane] = make_float2(xe.x + tr, xe.y + ti);
                     if (k == 0 && lane == 0) A[2048] = make_float2(xe.x - tr, xe.y - ti);
                 }
-                if (lane == 0) { q[5 + 2 * slot] = b; q[6 + 2 * slot] = c; }
-                wg_release();
-                if (lane == 0) __hip_atomic_fetch_add(&q[1 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                wg_publish(q, slot, b, c, lane);
             }
-            t = pull();
-            if (t < ntasks) decode(t, set, role);
+            t = cur.next(set, role);
             continue;
         }
         // ---- filter f of the block in ring slot `slot`
         const int f = role - 1;
         const float* Rtab = reinterpret_cast<const float*>(p.H) + (size_t)f * kFft4TabFloats;   // (R_lo, R_hi)[2048] f2 | (D_lo, D_hi)[2048] f4
         const unsigned lane4 = 4u * (unsigned)lane;
-        if (set != seen_set) {                                            // this wave's first filter of the block: once the
-            wg_wait_ge(&q[1 + slot], gen + 1);                            // spectrum is in the ring it stays until every filter is done
-            seen_b = __builtin_amdgcn_readfirstlane(wg_ld(&q[5 + 2 * slot]));
-            seen_c = __builtin_amdgcn_readfirstlane(wg_ld(&q[6 + 2 * slot]));
+        if (set != seen_set) {                                            // this wave's first filter of the block
+            wg_acquire_block(q, slot, gen, seen_b, seen_c);
             seen_set = set;
         }
         const int b = seen_b, c = seen_c;
@@ -316,14 +277,12 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_kernel(c
             step(std::integral_constant<int, 4>{}); step(std::integral_constant<int, 5>{});
             step(std::integral_constant<int, 6>{}); step(std::integral_constant<int, 7>{});
         }
-        wg_release();
-        if (lane == 0) __hip_atomic_fetch_add(&q[3 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // ring reads done
+        wg_reader_done(q, slot, lane);                                    // ring reads done
         fft2048w<true>(zre, zim, scr, scr_lds, twl, twh, lane);
         pin32(zre);
         pin32(zim);
-        const int tn = pull();                                            // next task reserved under the pooling
         int nset_i = 0, nrole = 0;
-        if (tn < ntasks) decode(tn, nset_i, nrole);
+        const int tn = cur.next(nset_i, nrole);                                      // next task reserved under the pooling
         pool_half(std::integral_constant<int, 1>{});
         t = tn;
         set = nset_i;

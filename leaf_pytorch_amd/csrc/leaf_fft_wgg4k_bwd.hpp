@@ -225,19 +225,12 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
     const int* tdesc = bl + kBandPlanHead;
     const int* bmem = tdesc + p.F + 4;
     (void)tdesc; (void)bmem;
-    const WgTaskGrid grid = wg_task_grid(NT, nset);                        // NT + 1 slots per set
-    const int ntasks = nset > 0 ? 1 + nset * (NT + 1) : 0;
-    auto pull = [&]() {
-        int v = 0;
-        if (lane0 == 0) v = __hip_atomic_fetch_add(&q[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return __builtin_amdgcn_readfirstlane(v);
-    };
-    auto decode = [&](int t, int& set, int& role) { wg_task_decode(grid, t, set, role); };
+    const WgTaskCursor cur = wg_task_cursor(q, lane0, NT, nset);          // NT + 1 slots per set
 
     int seen_set = -1, seen_b = 0, seen_c = 0;                            // block coordinates of the set this wave last worked on
-    int t = pull(), set = 0, role = 0;
-    if (t < ntasks) decode(t, set, role);
-    while (t < ntasks) {
+    int set = 0, role = 0;
+    int t = cur.next(set, role);
+    while (cur.has(t)) {
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         const int slot = set & 1, gen = set >> 1;
@@ -249,52 +242,22 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
                 const int gb = (int)blockIdx.x + set * (int)gridDim.x;
                 const int b = gb / p.nblk, c = gb - b * p.nblk;
                 const int n_c = c * LS;
-                const float* xb = static_cast<const float*>(p.x) + (size_t)b * p.T;
-                const unsigned short* xh = static_cast<const unsigned short*>(p.x) + (size_t)b * p.T;
-                const bool pcm = p.io_bf16 == kSamplePcm16;                // 16-bit PCM: the bf16 load, another conversion (wave-uniform select)
-                auto sample = [&](int i) -> float {                       // rotated block a'[i] = xz[n_c - padL + ((i + padL) mod 4096)]
-                    const int n = n_c - PADL + ((i + ROT) & (kFft4N - 1));
-                    if (p.io_bf16) {
-                        const unsigned v = xh[min(max(n, 0), p.T - 1)];
-                        const float w = pcm ? pcm16_widen((short)v) : __uint_as_float(v << 16);
-                        return (n >= 0 && n < p.T) ? w : 0.0f;
-                    }
-                    return (n >= 0 && n < p.T) ? xb[n] : 0.0f;
-                };
-                // waveform mixup in the load (leaf_common.hpp): the block's clip mixed with its partner, weights and partner row read
-                // once per block; ST: the compile-time sample type of the loop (fp32 / 16-bit PCM)
+                // the block's two halves (wg4k_load_half, leaf_fft_wg4k.hpp); mixed: the partner clip and the weights, read once per block
                 MixClip mc{};
                 if constexpr (MIX) mc = mix_clip(p.mix_perm, p.mix_lam, b, p.B, p.T);
-                auto load_mixed = [&](float (&v)[32], int odd, auto st) {
-#pragma unroll
-                    for (int r = 0; r < 32; ++r) {
-                        const int i = 2 * (64 * r + lane) + odd;
-                        v[r] = mix_sample<decltype(st)::value>(p.x, (size_t)b * p.T, mc, n_c - PADL + ((i + ROT) & (kFft4N - 1)), p.T);
-                    }
-                };
-                auto load_half = [&](float (&v)[32], float (&vi)[32], int odd) {      // (MIX instances only)
-                    if (p.io_bf16 == kSamplePcm16) load_mixed(v, odd, std::integral_constant<int, kSamplePcm16>{});
-                    else load_mixed(v, odd, std::integral_constant<int, kSampleF32>{});
+                const Wg4kWindow win{b, n_c - PADL, ROT};
+                auto load_half = [&](float (&v)[32], float (&vi)[32], int odd) {
+                    wg4k_load_half(p, MIX, mc, win, odd, lane, v);
 #pragma unroll
                     for (int r = 0; r < 32; ++r) vi[r] = 0.0f;
                 };
                 float xre[32], xim[32];
-                if constexpr (MIX) {
-                    load_half(xre, xim, 0);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 32; ++r) { xre[r] = sample(2 * (64 * r + lane)); xim[r] = 0.0f; }
-                }
+                load_half(xre, xim, 0);
                 fft2048w<HS>(xre, xim, scr, scr_lds, twl, twh, lane);
-                wg_wait_ge(&q[9 + slot], gen);                            // the slot's previous occupant has been released
+                wg_wait_ge(wgq_released_cnt(q, slot), gen);                          // the slot's previous occupant has been released
 #pragma unroll
                 for (int i = 0; i < 32; ++i) A[64 * brev5(i) + lane] = make_float2(xre[i], xim[i]);
-                if constexpr (MIX) {
-                    load_half(xre, xim, 1);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 32; ++r) { xre[r] = sample(2 * (64 * r + lane) + 1); xim[r] = 0.0f; }
-                }
+                load_half(xre, xim, 1);
                 fft2048w<HS>(xre, xim, scr, scr_lds, twl, twh, lane);
                 const float2 wl = tw4b[lane];
 #pragma unroll
@@ -307,12 +270,9 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
                     A[64 * k + lane] = make_float2(xe.x + tr, xe.y + ti);
                     if (k == 0 && lane == 0) A[2048] = make_float2(xe.x - tr, xe.y - ti);
                 }
-                if (lane == 0) { q[5 + 2 * slot] = b; q[6 + 2 * slot] = c; }
-                wg_release();
-                if (lane == 0) __hip_atomic_fetch_add(&q[1 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                wg_publish(q, slot, b, c, lane);
             }
-            t = pull();
-            if (t < ntasks) decode(t, set, role);
+            t = cur.next(set, role);
             continue;
         }
         // ---- backward of filter f on the block in ring slot `slot` (odd sets walk the tasks backwards: leaf_fft_wg4k.hpp)
@@ -325,10 +285,8 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
         const float* Mtab = reinterpret_cast<const float*>(p.H) + ((size_t)p.F + f) * kFft4TabFloats;
         const float* Stab = reinterpret_cast<const float*>(p.H) + ((size_t)2 * p.F + f) * kFft4TabFloats;
         const unsigned lane4 = 4u * (unsigned)lane;
-        if (set != seen_set) {                                            // this wave's first filter of the block: once the
-            wg_wait_ge(&q[1 + slot], gen + 1);                            // spectrum is in the ring it stays until every filter is done
-            seen_b = __builtin_amdgcn_readfirstlane(wg_ld(&q[5 + 2 * slot]));
-            seen_c = __builtin_amdgcn_readfirstlane(wg_ld(&q[6 + 2 * slot]));
+        if (set != seen_set) {                                            // this wave's first filter of the block
+            wg_acquire_block(q, slot, gen, seen_b, seen_c);
             seen_set = set;
         }
         const int b = seen_b, c = seen_c;
@@ -354,15 +312,14 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
                     asm volatile("" ::: "memory");
                 }
                 band_bwd_task<32, 801, 320, true>(p, rq, A, mem, bl + 4, twl, scr, scr_lds, b, c, gb, mlo, mhi, lane);
-                const int tn_b = pull();
                 int nset_b = 0, nrole_b = 0;
-                if (tn_b < ntasks) decode(tn_b, nset_b, nrole_b);
+                const int tn_b = cur.next(nset_b, nrole_b);
                 wg_release();
                 int old_b = 0;
-                if (lane == 0) old_b = __hip_atomic_fetch_add(&q[3 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (lane == 0) old_b = __hip_atomic_fetch_add(wgq_readers_cnt(q, slot), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 old_b = __builtin_amdgcn_readfirstlane(old_b);
                 if (old_b == gen * NT + NT - 1) {
-                    if (lane == 0) __hip_atomic_fetch_add(&q[9 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (lane == 0) __hip_atomic_fetch_add(wgq_released_cnt(q, slot), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
                 t = tn_b;
                 set = nset_b;
@@ -486,10 +443,10 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
             const int rho_lo = (mlo * SHOPr - PADL - n_c - h) & 1;        // tap parity of frame mlo in this half
             // taps of parity rho: lane l holds g[2 (64 i + l) + rho]
             auto load_taps = [&](int rho, float (&w)[NI2]) {
-                gfp q = (gfp)(p.Gz + (size_t)f * 2 * p.GZ + kGPad + (rho ? p.GZ : 0)) + lane;
-                asm volatile("" : "+v"(q) : : "memory");
+                gfp gq = (gfp)(p.Gz + (size_t)f * 2 * p.GZ + kGPad + (rho ? p.GZ : 0)) + lane;
+                asm volatile("" : "+v"(gq) : : "memory");
 #pragma unroll
-                for (int i = 0; i < NI2; ++i) w[i] = q[64 * i];
+                for (int i = 0; i < NI2; ++i) w[i] = gq[64 * i];
             };
             // frames of one parity class: m_first, m_first + step, ...
             auto first_of = [&](int rho) { return step == 1 ? (rho == rho_lo ? mlo : mhi + 1) : mlo + (rho == rho_lo ? 0 : 1); };
@@ -689,9 +646,8 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
         half_bwd(std::integral_constant<int, 1>{});
         float dpw = qacc / (half * half);
         // next task: reserved before the reductions
-        const int tn = pull();
         int nset_i = 0, nrole = 0;
-        if (tn < ntasks) decode(tn, nset_i, nrole);
+        const int tn = cur.next(nset_i, nrole);
         amu = wave_sum(amu);
         asg = wave_sum(asg);
         dpw = wave_sum(dpw);
@@ -716,10 +672,10 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg4k_bwd_kern
         // ---- this task is done with the slot; the wave that finishes the block's last filter releases it
         wg_release();
         int old = 0;
-        if (lane == 0) old = __hip_atomic_fetch_add(&q[3 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (lane == 0) old = __hip_atomic_fetch_add(wgq_readers_cnt(q, slot), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         old = __builtin_amdgcn_readfirstlane(old);
         if (old == gen * NT + NT - 1) {
-            if (lane == 0) __hip_atomic_fetch_add(&q[9 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (lane == 0) __hip_atomic_fetch_add(wgq_released_cnt(q, slot), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         t = tn;
         set = nset_i;

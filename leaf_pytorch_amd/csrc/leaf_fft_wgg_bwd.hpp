@@ -253,10 +253,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_bwd_kernel
     float2* twh = twl + 32 * 64;
     float2* ring = twh + 64;                                              // A': [2][kWgRingFloat2]
     [[maybe_unused]] float2* gsum = ring + 2 * kWgRingFloat2;            // DX: G, Hermitian-folded: [2][kWgRingFloat2]
-    int* q = reinterpret_cast<int*>(ring + (DX ? 4 : 2) * kWgRingFloat2);
-    // q: 0 next task | 1,2 spectra stored per slot | 3,4 inverse tasks finished per slot | 5..8 (clip, block) per slot |
-    //    9,10 generations released per slot (all readers done) | 11,12 (DX) filters added to the slot's G, ever
-    //    | 13,14 (DX, even windows) filters added to the slot's unpaired-tap array, ever
+    int* q = reinterpret_cast<int*>(ring + (DX ? 4 : 2) * kWgRingFloat2);   // the task queue (leaf_wg_queue.hpp)
     const int PF = fft_wgg_front_floats(p.K), BP = HALF ? fft_wgg_back_floats(p.K) : fft_wgg_back_floats_full(p.K);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane0 = tid & 63;
@@ -273,28 +270,14 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_bwd_kernel
     const int PADL = p.padL, ROT = p.K / 2, LS = p.L, SKr = p.K;
     const int nblocks = p.B * p.nblk;
     const int nset = (nblocks - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    const WgTaskGrid grid = wg_task_grid(p.F, nset);                       // F + 1 slots per set
-    const int ntasks = nset > 0 ? 1 + nset * (p.F + 1) : 0;
-    auto pull = [&]() {
-        int v = 0;
-        if (lane0 == 0) v = __hip_atomic_fetch_add(&q[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return __builtin_amdgcn_readfirstlane(v);
-    };
-    auto decode = [&](int t, int& set, int& role) { wg_task_decode(grid, t, set, role); };
+    const WgTaskCursor cur = wg_task_cursor(q, lane0, p.F, nset);         // F + 1 slots per set
     auto row_of = [&](int role) { return role > 0 && role <= p.F ? role - 1 : 0; };
     float rq[32];
-    auto load_real_spectrum = [&](int f, int lane) {
-        const float* src = reinterpret_cast<const float*>(p.H) + (size_t)f * kFftN + lane;
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int k = 0; k < 32; ++k) rq[k] = src[64 * k];
-        asm volatile("" ::: "memory");
-    };
     int seen_set = -1, seen_b = 0, seen_c = 0;                            // block coordinates of the set this wave last worked on
-    int t = pull(), set = 0, role = 0;
-    if (t < ntasks) decode(t, set, role);
-    load_real_spectrum(row_of(role), lane0);
-    while (t < ntasks) {
+    int set = 0, role = 0;
+    int t = cur.next(set, role);
+    wg_load_real_spectrum(rq, p.H, row_of(role), lane0);
+    while (cur.has(t)) {
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         const int slot = set & 1, gen = set >> 1;
@@ -315,7 +298,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_bwd_kernel
                     aim[r] = 0.0f;
                 }
                 fft2048w<HALF>(are, aim, scr, scr_lds, twl, twh, lane);
-                wg_wait_ge(&q[9 + slot], gen);                            // the slot's previous occupant has been released
+                wg_wait_ge(wgq_released_cnt(q, slot), gen);                          // the slot's previous occupant has been released
 #pragma unroll
                 for (int i = 0; i < 32; ++i) {
                     const int k = brev5(i);
@@ -328,22 +311,16 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_bwd_kernel
                     if (even)
                         for (int i = lane; i < kFftN; i += 64) tsum[slot * kFftN + i] = 0.0f;
                 }
-                if (lane == 0) { q[5 + 2 * slot] = b; q[6 + 2 * slot] = c; }
-                wg_release();
-                if (lane == 0) __hip_atomic_fetch_add(&q[1 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                wg_publish(q, slot, b, c, lane);
             }
-            t = pull();
-            if (t < ntasks) decode(t, set, role);
-            else role = 0;
-            load_real_spectrum(row_of(role), lane);
+            t = cur.next(set, role);
+            wg_load_real_spectrum(rq, p.H, row_of(role), lane);
             continue;
         }
         // ---- backward of filter f on the block in ring slot `slot`
         const int f = role - 1;
-        if (set != seen_set) {                                            // this wave's first filter of the block: once the
-            wg_wait_ge(&q[1 + slot], gen + 1);                            // spectrum is in the ring it stays until every filter is done
-            seen_b = __builtin_amdgcn_readfirstlane(wg_ld(&q[5 + 2 * slot]));
-            seen_c = __builtin_amdgcn_readfirstlane(wg_ld(&q[6 + 2 * slot]));
+        if (set != seen_set) {                                            // this wave's first filter of the block
+            wg_acquire_block(q, slot, gen, seen_b, seen_c);
             seen_set = set;
         }
         const int b = seen_b, c = seen_c;
@@ -352,8 +329,8 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_bwd_kernel
         {
             float dummy_re[32], dummy_im[32];
             wgg_bwd_filter<NI, DX ? 2 : 0, HALF>(p, A, lane, f, b, c, even, rq, wbase, scr, scr_lds, twl, twh, dummy_re, dummy_im, amu,
-                                                 asg, dpw, gsum + slot * kWgRingFloat2, &q[11 + slot], gen * p.F + f,
-                                                 tsum + slot * kFftN, &q[13 + slot]);
+                                                 asg, dpw, gsum + slot * kWgRingFloat2, wgq_dx_ticket(q, slot), gen * p.F + f,
+                                                 tsum + slot * kFftN, wgq_tap_ticket(q, slot));
         }
         if constexpr (DX) {
             if (f == p.F - 1) {
@@ -361,10 +338,9 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_bwd_kernel
             }
         }
         // next task: reserved now, its spectrum row requested before the reductions (rq is free from here)
-        const int tn = pull();
         int nset_i = 0, nrole = 0;
-        if (tn < ntasks) decode(tn, nset_i, nrole);
-        load_real_spectrum(row_of(nrole), lane);
+        const int tn = cur.next(nset_i, nrole);
+        wg_load_real_spectrum(rq, p.H, row_of(nrole), lane);
         amu = wave_sum(amu);
         asg = wave_sum(asg);
         dpw = wave_sum(dpw);
@@ -377,10 +353,10 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wgg_bwd_kernel
         // ---- this task is done with the slot; the wave that finishes the block's last filter releases it
         wg_release();
         int old = 0;
-        if (lane == 0) old = __hip_atomic_fetch_add(&q[3 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (lane == 0) old = __hip_atomic_fetch_add(wgq_readers_cnt(q, slot), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         old = __builtin_amdgcn_readfirstlane(old);
         if (old == gen * p.F + p.F - 1) {
-            if (lane == 0) __hip_atomic_fetch_add(&q[9 + slot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (lane == 0) __hip_atomic_fetch_add(wgq_released_cnt(q, slot), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         t = tn;
         set = nset_i;

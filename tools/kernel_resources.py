@@ -38,8 +38,6 @@ ALLOWED_SCRATCH = {
                                                        "per (block, filter) task of ~3 000 instructions, the rest in wg_dx_finish (once per block)",
     r"leaf_fft_blk_bwd_dx_kernel": "dL/dx at the static LEAF geometries (small batches; K = 801 at every batch): 32-64 B/lane outside the filter loop (the extra transform's "
                                    "temporaries); 0.15 ms of the 0.88 ms training step with dL/dx",
-    r"leaf_fft_wgg4k_bwd_kernelILi12ELi7ELb1E": "static 32 kHz instance of the 4096-sample backward: 12 B/lane = two launch-invariant values "
-                                                "stored once, reloaded three times per (block, filter) task of ~8 000 instructions",
     r"leaf_fft_wgg4k_bwd_kernel": "parameter gradients at 44.1 / 48 kHz (4096-sample plan): 76-84 B/lane around the half-transform "
                                   "hand-over = 11 spill stores + ~20 reloads per (block, filter) task of ~14 000 instructions (< 0.3 %)",
     r"leaf_fft_wg_kernel.*Lb1": "streaming finalize (what AUTO runs at BASELINE configs[3] / [4], and LEAF_ALGO_STREAM_FINALIZE elsewhere): 48 B/lane = the "
