@@ -173,6 +173,7 @@ __global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restr
         const float Mend = fmaf(A, carry, Bv);
         const float Mprev = __shfl_up(Mend, 1);
         M0 = fmaf(A0, lane ? Mprev : carry, B0);
+        if (c == 0 && lane == 0) M0 = q0;                                  // M_0 = w p_0 + (1-w) p_0 = p_0 exactly, not to a rounding
         M1 = fmaf(A1, M0, B1);
         carry = __shfl(Mend, 63);
     };
@@ -200,15 +201,19 @@ __global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restr
     float s_a = 0.f, s_d = 0.f, s_rho = 0.f, s_w = 0.f, s_g = 0.f;
     float gnext = 0.0f;                                                   // gM of the first frame of the following chunk
     // Mv0 / Mv1: M at the lane's frames j0, j0 + 1; Mb: M at j0 - 1 (p_0 in front of the row)
+    // dL/dp_m = dpd_m + wm gM_m with gM_m = cm_m + (1-w) gM_{m+1}, cm_m = -dpd_m t_m, t_m = alpha p_m / (floor + M_m), wm = w (m = 0:
+    // 1, the recurrence starts from p_0).  The frame's own share is taken in factored form, dpd_m (1 - wm t_m): at the first frame
+    // M_0 = p_0 makes t_0 = alpha and the two terms agree to 1 - alpha (0.04 at the default) -- as a difference of two rounded products
+    // a clip of ONE frame lost 25x .. 125x their rounding (tests/test_gpu_backward_edges.py); 1 - alpha (p / (floor + M)) is exact there.
     auto bwd_chunk = [&](int c, float Mv0, float Mv1, float Mb) {
         const int j0 = 128 * c + 2 * lane;
-        float cm[2], dpd[2], pv[2], Mp[2];
+        float cm[2], dpd[2], pv[2], Mp[2], own[2];
         bool ok[2], above[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int m = j0 + k;
             ok[k] = m < TP;
-            cm[k] = dpd[k] = pv[k] = Mp[k] = 0.0f;
+            cm[k] = dpd[k] = pv[k] = Mp[k] = own[k] = 0.0f;
             above[k] = false;
             if (ok[k]) {
                 const float rv = r[m];
@@ -240,9 +245,10 @@ __global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restr
                 s_d += dv - rho * d_rho / d * g;
                 s_rho += (vr * (l2v * 0.6931471805599453f) - d_rho * ln_d) * g;
                 dpd[k] = dv / u;
-                const float du = -dv * p / (u * u);
-                s_a += du * u * (l2M * 0.6931471805599453f);
-                cm[k] = du * a * u / Mf;
+                const float t = a * (p / Mf);
+                s_a -= dpd[k] * p * (l2M * 0.6931471805599453f);          // d/d alpha: du u ln M with du = -dv p / u^2
+                cm[k] = -dpd[k] * t;                                      // du alpha u / (floor + M)
+                own[k] = dpd[k] * (1.0f - (m == 0 ? t : w * t));
                 pv[k] = p;
                 Mp[k] = k ? Mv0 : Mb;
             }
@@ -260,16 +266,16 @@ __global__ __launch_bounds__(256) void pcen_bwd_scan_kernel(const float* __restr
         }
         const float g0 = fmaf(A, gnext, Bv);                              // gM of this lane's first frame
         const float gn = __shfl_down(g0, 1);
-        const float g1 = fmaf(b1, lane < 63 ? gn : gnext, cm[1]);         // gM of this lane's second frame
+        const float g2 = lane < 63 ? gn : gnext;                          // gM of the frame after this lane's second
+        const float g1 = fmaf(b1, g2, cm[1]);                             // gM of this lane's second frame
         gnext = __shfl(g0, 0);
-        const float gM[2] = {g0, g1};
+        const float gM[2] = {g0, g1}, gMnext[2] = {g1, g2};              // (past the row's end: 0)
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int m = j0 + k;
             if (ok[k]) {
-                float dp = dpd[k] + w * gM[k];
+                const float dp = fmaf(m == 0 ? omw : w * omw, gMnext[k], own[k]);
                 s_w += gM[k] * (pv[k] - Mp[k]);
-                if (m == 0) dp += omw * gM[k];                            // the recurrence starts from p_0
                 const float gv = above[k] ? dp : 0.0f;
                 gp[m] = gv;
                 s_g += gv;

@@ -173,6 +173,13 @@ TRAIN_CASES = [("16k-workgroup", 40, 401, 160, 15900, 2048 - 401 + 1, 6, 20, Tru
                ("k833-runtime-4096", 6, 833, 333, 7000, (4096 - 833 + 1) & ~1, 8, 8, True),
                ("16k-per-wave", 40, 401, 160, 4001, 2048 - 401 + 1, 0, 0, True),
                ("22k-runtime-workgroup", 12, 552, 220, 9000, 2048 - 552 + 1, 10, 10, False)]
+# ... and at the clip lengths where a block load ends ragged (tests/test_gpu_backward_edges.py): one sample, one hop h, h + 1, and
+# L - 1, L, L + 1 of the plan's block length L; the batch follows each case's length (one or two blocks per clip)
+EDGE_LENGTHS = lambda hop, L: (1, hop, hop + 1, L - 1, L, L + 1)
+TRAIN_CASES += [(f"16k-workgroup-edge-T{T}", 40, 401, 160, T, 1600, 6, 20, True) for T in EDGE_LENGTHS(160, 1600)]
+TRAIN_CASES += [(f"32k-4096-edge-T{T}", 12, 801, 320, T, 3200, 8, 8, True) for T in EDGE_LENGTHS(320, 3200)]
+TRAIN_CASES += [(f"16k-per-wave-edge-T{T}", 40, 401, 160, T, 1600, 0, 0, True) for T in EDGE_LENGTHS(160, 1600)]
+TRAIN_CASES += [(f"k833-runtime-4096-edge-T{T}", 6, 833, 333, T, (4096 - 833 + 1) & ~1, 8, 8, True) for T in EDGE_LENGTHS(333, (4096 - 833 + 1) & ~1)]
 
 
 @pytest.mark.parametrize("int16", [False, True], ids=["fp32", "int16"])
@@ -213,7 +220,9 @@ def test_parameter_gradients_equal_those_through_forward_of_the_mixed_batch(case
     assert all(torch.equal(u, v) for u, v in zip(a, b)), "the float32 backward is not reproducible run to run"
     assert len(got) == 7
     for (n, _), u, v in zip(sorted(m.named_parameters()), got, a):
-        assert float(v.abs().max()) > 0, n
+        # (a clip of one frame has no smoother step, a clip of one sample meets the pooling window at its centre alone: those
+        # gradients are exact zeros, in fp64 as here)
+        assert float(v.abs().max()) > 0 or (T <= hop and n == "_compression.ema._weights") or (T == 1 and n == "_pooling.weights"), n
         assert torch.equal(u, v), f"{name}: {n} differs by {float((u - v).abs().max()):.3e}"
 
 

@@ -217,6 +217,13 @@ BWD = [("16k-band", 40, 401, 160, 3, 4000, "pcen", {}),
        ("16k-staged", 8, 401, 160, 3, 801, "pcen", {"staged": True}),
        ("16k-log1p", 40, 401, 160, 3, 4000, "log1p", {}),
        ("16k-off", 40, 401, 160, 1, 801, "off", {})]
+# ... and at the clip lengths where a block load ends ragged (tests/test_gpu_backward_edges.py): one sample, one hop h, h + 1, and
+# L - 1, L, L + 1 of the plan's block length L, on the per-wave kernel (three clips) and on the workgroup kernels (B = ("cus", s): one clip
+# more than s/16 of a block per CU asks for)
+EDGE_LENGTHS = lambda hop, L: (1, hop, hop + 1, L - 1, L, L + 1)
+BWD += [(f"16k-per-wave-edge-T{T}", 40, 401, 160, 3, T, "pcen", {}) for T in EDGE_LENGTHS(160, 1600)]
+BWD += [(f"16k-workgroup-edge-T{T}", 40, 401, 160, ("cus", 6), T, "pcen", {}) for T in EDGE_LENGTHS(160, 1600)]
+BWD += [(f"32k-4096-edge-T{T}", 12, 801, 320, ("cus", 8), T, "pcen", {}) for T in EDGE_LENGTHS(320, 3200)]
 
 
 def grad_out_bf16(shape, seed):
@@ -233,6 +240,8 @@ def assert_same_grads(got, want, n, what):
 @pytest.mark.parametrize("case", BWD, ids=[c[0] for c in BWD])
 def test_backward_equals_the_float32_backward_on_the_widened_gradient(case, xtype):
     name, F, K, hop, B, T, mode, kw = case
+    if isinstance(B, tuple):
+        B = n_cus() * B[1] // 16 + 1
     m = module(F, K, hop, mode, seed=3)
     prm = args_of(m)
     pcen, log1p = mode == "pcen", mode == "log1p"

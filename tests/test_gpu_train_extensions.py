@@ -369,6 +369,25 @@ def test_bf16_training_static_16k_geometry(mode, need_dx):
 
 @pytest.mark.parametrize("need_dx", [False, True])
 @pytest.mark.parametrize("mode", ["pcen", "off", "log1p"])
+@pytest.mark.parametrize("T", [1, 160, 161, 1599, 1600, 1601])
+def test_bf16_training_static_16k_geometry_at_clip_edges(T, mode, need_dx):
+    """(7) at the clip lengths where a block load ends ragged (tests/test_gpu_backward_edges.py): one sample, one hop, one more, and
+    L - 1, L, L + 1 of the 1600-sample block -- at odd T a clip's 16-bit row does not start on a 4-byte boundary.  Two clips (one wave
+    per block) and one clip more than 6/16 of a block per CU asks for (the workgroup kernel)."""
+    bf16_case(40, 401, 160, T, 2, mode, need_dx, seed=3)
+    bf16_case(40, 401, 160, T, torch.cuda.get_device_properties(DEV).multi_processor_count * 6 // 16 + 1, mode, need_dx, seed=4)
+
+
+@pytest.mark.parametrize("need_dx", [False, True])
+@pytest.mark.parametrize("mode", ["pcen", "off", "log1p"])
+@pytest.mark.parametrize("T", [1, 320, 321, 3199, 3200, 3201])
+def test_bf16_training_static_32k_geometry_at_clip_edges(T, mode, need_dx):
+    """The same on the 4096-sample blocks of the 32 kHz geometry (L = 3200): one clip more than 8/16 of a block per CU asks for."""
+    bf16_case(3, 801, 320, T, torch.cuda.get_device_properties(DEV).multi_processor_count * 8 // 16 + 1, mode, need_dx, seed=82)
+
+
+@pytest.mark.parametrize("need_dx", [False, True])
+@pytest.mark.parametrize("mode", ["pcen", "off", "log1p"])
 def test_bf16_training_other_families(mode, need_dx):
     """(7) 32 kHz geometry on 4096-sample blocks (direct loads), a run-time geometry (K = 552, even; the workgroup kernel and the one wave
     per block kernel) and a short window (MFMA backward without dL/dx, staged with it): the last two through one widening pass, then
