@@ -1,6 +1,5 @@
 // inst_clips.hip -- batch assembly from a packed sample store: the kernels of leaf_clips.hpp and their C-ABI entries.
 // One of the translation units of libleaf_hip.so; it shares nothing with the others but the header's declarations.
-#define LEAF_INST_TU 1
 #include "leaf_clips.hpp"
 
 // include/leaf_hip.h: the argument checks come first (status only, nothing launched), one launch of B workgroups follows

@@ -1,9 +1,8 @@
 // inst_fft_wg_mix16.hip -- the tail-finalize instances of the static workgroup forward kernel (leaf_fft_wg.hpp) for mixed calls on a 16-bit PCM waveform (waveform mixup in the block load).
 // One of the translation units of libleaf_hip.so; see leaf_inst.hpp.
-#define LEAF_INST_TU 1
 #include "leaf_fft_wg.hpp"
 #include "leaf_inst.hpp"
 
-const void* leaf_inst_fft_wg_mix16(int sk, int nw, int tailc) { return wg_tail_instance<kWgXMix16>(sk, nw, tailc); }
+FftKernel leaf_inst_fft_wg_mix16(int sk, int nw, int tailc) { return wg_tail_instance<kWgXMix16>(sk, nw, tailc); }
 
-unsigned leaf_layout_fft_wg_mix16() { return leaf_layout_hash_fft(); }      // parameter-struct layout this unit was compiled with (leaf_inst.hpp)
+unsigned leaf_layout_fft_wg_mix16() { return leaf_params_layout(); }      // the launch structs' layout this unit was compiled with (leaf_inst.hpp)

@@ -1,9 +1,8 @@
 // inst_fft_wg_x16.hip -- the tail-finalize instances of the static workgroup forward kernel (leaf_fft_wg.hpp) for 16-bit waveforms (bfloat16 and PCM16 share the load loop).
 // One of the translation units of libleaf_hip.so; see leaf_inst.hpp.
-#define LEAF_INST_TU 1
 #include "leaf_fft_wg.hpp"
 #include "leaf_inst.hpp"
 
-const void* leaf_inst_fft_wg_x16(int sk, int nw, int tailc) { return wg_tail_instance<kWgX16>(sk, nw, tailc); }
+FftKernel leaf_inst_fft_wg_x16(int sk, int nw, int tailc) { return wg_tail_instance<kWgX16>(sk, nw, tailc); }
 
-unsigned leaf_layout_fft_wg_x16() { return leaf_layout_hash_fft(); }      // parameter-struct layout this unit was compiled with (leaf_inst.hpp)
+unsigned leaf_layout_fft_wg_x16() { return leaf_params_layout(); }      // the launch structs' layout this unit was compiled with (leaf_inst.hpp)

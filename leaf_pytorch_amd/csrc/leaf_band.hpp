@@ -1,5 +1,5 @@
 // leaf_band.hpp -- band-limited filter tasks of the static workgroup forward kernel (leaf_fft_wg.hpp), round 5
-// Part of libleaf_hip.so (gfx950 only); included by leaf_fft_wg.hpp.
+// Included by every unit (through leaf_fft_wg.hpp): templates, device functions, constexpr sizes (gfx950 only).
 //
 // Why.  The workgroup kernel runs one 2048-point inverse transform per (block, filter).  Most Gabor filters occupy a narrow
 // band: the spectrum R_f of the K-tap filter (impulse_responses.py:5-16) is a Gaussian of sigma_k = N / (2 pi sigma_f) bins
@@ -209,354 +209,6 @@ template <bool HALF, bool SKIP1>
 __device__ __forceinline__ void fft2048w(float (&re)[32], float (&im)[32], float* scr, unsigned scr_lds, const float2* twl,
                                          const float2* twh, int lane);   // leaf_fft_wg.hpp (which includes this header above it)
 __device__ __forceinline__ void fft_build_twiddles_wg(float2* twl, float2* twp, int tid, int nthreads);
-
-#ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
-#include "leaf_band_phi.inc"
-static_assert(kBandPhiLh == kBandLh, "leaf_band_phi.inc was generated for another filter length");
-
-struct BandTabArgs {
-    int T, L, hop, padL;
-    float eps2, eta;
-    int force;             // tests / tools: 0 decide, 1 / 2 every filter in the 256- / 512-point class, 3 none
-    int edge_only;         // frozen-parameter tables (leaf_forward_prepared_f32): grid (F, n_edge), only the edge tables of this clip length
-    int* rec;
-    float* gz;
-    float* edge;
-    float* gz2;            // (backward) the same two tables for the window g_f[j] (j - c)^2, c = (K - 1) / 2: d pool_w at the decimated
-    float* edge2;          // rate (impulse_responses.py:74-80: d g / d s = g (j - c)^2 / (c^2 s^3)); NULL: not built
-    int* elist;
-    int* classes;          // leaf_band_classes_f32: [F] the transform length each filter gets (NULL: not asked for)
-    const float* cls_bias; // ... for these pooling biases (round 6: the energy bound follows the bias; NULL: the strict decision)
-    int n_edge;
-    BandEdge e[kBandMaxEdge];
-    // the main kernel's first blocks (round 5): waves 1..7 of the workgroups (f, 0) -- idle while wave 0 transforms the filter's
-    // taps -- transform the first block of main-kernel workgroups w = 7 f + wave - 1 (+ 7 F, ...) < G into spec0[w]: the one
-    // forward transform nothing in the main kernel can overlap with.  Their transposition scratch is the launch's dynamic LDS.
-    const void* x;
-    int io_bf16, B, nblk, G;
-    float2* spec0;
-    int cross;             // != 0 (forward launches of the 2048-sample plan, round 6): windows may reach bin kWgFwdBins - 1 (beyond Nyquist)
-    unsigned* stamps;      // the table cache's stamps, [2 + n_edge][F][kStampWords] (leaf_fft.hpp); NULL everywhere else
-    int strict;            // (stamped launches) LEAF_ALGO_STRICT_BAND_CLASSES, part of the stamp
-    int bwd_slabs;         // (backward) != 0: the class decision also asks band_deriv_fits; 1 (2048-sample plan): two more grid rows, (f, 2 + n_edge) and (f, 3 + n_edge), build the spectra of d w / d mu and
-                           // d w / d sigma into slabs 1 and 2 of H (what fft_prep_kernel's grid (F, 3) does): one table launch
-};
-
-// sum over a 16-lane row (every lane of the row gets it)
-__device__ __forceinline__ float band_row_sum(float v) {
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, false));    // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, false));    // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));   // row_ror:4
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));   // row_ror:8
-    return v;
-}
-
-// fft_prep_kernel (real-spectrum form, forward tables) + the tables of the band tasks.  Grid (F, 2 + n_edge):
-//   workgroup (f, 0): the tables of fft_prep_kernel (wave 0 runs the filter's 2048-point transform), then all waves take the
-//                     seven sums of the class decision from the spectrum wave 0 left in LDS;
-//   workgroup (f, 1 + s): the edge table of edge entry s, both classes   } on CUs the F transform workgroups leave idle,
-//   workgroup (f, 1 + n_edge): the decimated pooling windows G~ of both classes } and done before wave 0's transform is
-// Sixteen lanes per table entry: the sum over the window samples within lphi of the entry's position.
-// (Workgroup (0, 0) also copies the edge list to device memory for the main kernel.)
-__device__ __forceinline__ void fft_prep_band_body(const float* __restrict__ kernel, const float* __restrict__ pool_w,
-                                                   int F, int K, int GZ, const GaborBounds& bd, float2* __restrict__ H,
-                                                   float* __restrict__ Gz, int* __restrict__ col_of, const BandTabArgs& a) {
-    __shared__ float2 s_twl[32 * 64];
-    __shared__ float2 s_twh[64];
-    __shared__ float2 s_twp[64];
-    __shared__ float s_scr[32 * 65];
-    __shared__ float2 s_taps[kFftN / 2 + 64];
-    __shared__ float Rs[kFftN];
-    __shared__ float gs[64 * kPoolRowsMax];
-    __shared__ float phis[2][kBandLh * 8 + 1];               // phi_8 | phi_4 (one half each)
-    __shared__ float red[8][14];
-    __shared__ int es[kBandMaxEdge][4];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, f = blockIdx.x;
-    const int l16 = lane & 15;
-    // one table entry per 16-lane row: value = sum over pp = lo .. hi of gs[pp + goff] phi[|p0 - pp|]
-    auto entry = [&](const float* phi, int p0, int lo, int hi, int goff, const float* win) {
-        float acc = 0.0f;
-#pragma unroll 4
-        for (int pp = lo + l16; pp <= hi; pp += 16) {
-            const int u = p0 - pp;
-            acc = fmaf(win[pp + goff], phi[u < 0 ? -u : u], acc);
-        }
-        return band_row_sum(acc);
-    };
-    float* gs2 = gs + 64 * kPoolRowsMax / 2;                              // (backward tables) g_f[j] (j - c)^2; K <= 640 here
-    // both windows in one pass (the backward's tables: the same taps, the same phi)
-    auto entry2 = [&](const float* phi, int p0, int lo, int hi, int goff, float& v2) {
-        float acc = 0.0f, acc2 = 0.0f;
-#pragma unroll 4
-        for (int pp = lo + l16; pp <= hi; pp += 16) {
-            const int u = p0 - pp;
-            const float ph = phi[u < 0 ? -u : u];
-            acc = fmaf(gs[pp + goff], ph, acc);
-            acc2 = fmaf(gs2[pp + goff], ph, acc2);
-        }
-        v2 = band_row_sum(acc2);
-        return band_row_sum(acc);
-    };
-    if (tid <= kBandLh * 8) phis[0][tid] = kBandPhi8[tid];
-    else if (tid >= 128 && tid - 128 <= kBandLh * 4) phis[1][tid - 128] = kBandPhi4[tid - 128];
-#pragma unroll
-    for (int s = 0; s < kBandMaxEdge; ++s)
-        if (tid == 256 + s) { es[s][0] = a.e[s].c; es[s][1] = a.e[s].m; es[s][2] = a.e[s].lo; es[s][3] = a.e[s].hi; }
-    if (a.bwd_slabs && (int)blockIdx.y >= 2 + a.n_edge) {
-        // ---- (backward) the spectrum of d w / d mu or d w / d sigma: fft_prep_kernel's workgroup (f, which)
-        const int which = (int)blockIdx.y - (1 + a.n_edge);
-        fft_prep_front(kernel, pool_w, F, K, GZ, bd, Gz, f, which, s_twl, s_twh, s_taps, nullptr, tid);
-        __syncthreads();
-        if (wave == 0) fft_prep_transform(F, K, 1, H, col_of, nullptr, f, which, s_twl, s_twh, s_scr, s_taps, nullptr, lane);
-        return;
-    }
-    if ((LEAF_PREP_ABLATE & 1) && blockIdx.y > 0 && (int)blockIdx.y < 1 + a.n_edge) return;
-    if ((LEAF_PREP_ABLATE & 2) && (int)blockIdx.y == 1 + a.n_edge) return;
-    if (blockIdx.y > 0 || a.edge_only) {
-        // ---- edge table W~[m] of entry s, both classes, in the register order of the class (band_task: the lane reads entry
-        // k LPF + l2 of its register k): the window's samples [pa, pb) relative to the block, and the image of m D within lphi of them
-        const float half = 0.5f * (float)(K - 1);
-        for (int j = tid; j < K; j += kPrepWaves * 64) {                   // the pooling window: as fft_prep_front evaluates it, or
-            if (a.edge_only) {                                             // (frozen-parameter tables) as it left it in the pooling row
-                gs[j] = Gz[(size_t)f * GZ + kGPad + j];
-            } else {
-                const float q = ((float)j - half) / (pool_sigma(pool_w[f], K) * half);
-                gs[j] = expf(-0.5f * (q * q));
-            }
-            const float tj = (float)j - half;
-            gs2[j] = gs[j] * (tj * tj);
-        }
-        __syncthreads();
-        const int grp = tid >> 4;
-        if (!a.edge_only && (int)blockIdx.y == 1 + a.n_edge) {
-            // ---- decimated pooling windows G~(tau) = D sum_u g[tau - u] phi_D[|u|], tau = c0min + D j, of both classes
-            const int len16 = band_gz_len(K, a.hop, 16), len32 = band_gz_len(K, a.hop, 32);
-            const int gzs = band_gz_floats(K, a.hop);                       // (run-time gcd loops: evaluated ONCE, not per table entry)
-            float* gzf = a.gz + (size_t)f * gzs;
-            float* gz2f = a.gz2 ? a.gz2 + (size_t)f * gzs : nullptr;
-#pragma unroll
-            for (int cls = 0; cls < 2; ++cls) {
-                const int A = 16 << cls, D = band_d(A), lphi = band_lphi(A), c0 = band_c0min(K, a.hop, A), len = cls ? len32 : len16;
-                for (int j = grp; j < len; j += kPrepWaves * 4) {
-                    const int tau = c0 + D * j;
-                    if (a.gz2) {
-                        float v2;
-                        const float v = entry2(phis[cls], tau, max(0, tau - lphi), min(K - 1, tau + lphi), 0, v2);
-                        if (l16 == 0) {
-                            gzf[(cls ? len16 : 0) + j] = (float)D * v;
-                            gz2f[(cls ? len16 : 0) + j] = (float)D * v2;
-                        }
-                    } else {
-                        const float v = entry(phis[cls], tau, max(0, tau - lphi), min(K - 1, tau + lphi), 0, gs);
-                        if (l16 == 0) gzf[(cls ? len16 : 0) + j] = (float)D * v;
-                    }
-                }
-            }
-            return;
-        }
-        const int s = a.edge_only ? blockIdx.y : blockIdx.y - 1;
-        if (f == 0 && s == 0 && tid < 4 * kBandMaxEdge) a.elist[tid] = es[tid >> 2][tid & 3];   // (edge_only: nobody else does)
-        const int c = es[s][0], goff = c * a.L - (es[s][1] * a.hop - a.padL);
-        const int pa = es[s][2] - c * a.L, pb = es[s][3] - c * a.L;
-#pragma unroll
-        for (int cls = 0; cls < 2; ++cls) {
-            const int A = 16 << cls, D = band_d(A), lphi = band_lphi(A), M = band_m(A);
-            float* tab = a.edge + (((size_t)f * 2 + cls) * kBandMaxEdge + s) * 512;
-            for (int m = grp; m < M; m += kPrepWaves * 4) {
-                int p0 = m * D;
-                if (p0 - kFftN + lphi >= pa) p0 -= kFftN;
-                else if (p0 + kFftN - lphi < pb) p0 += kFftN;
-                const int m1 = m >> 4, m2 = m & 15;
-                const int idx = cls ? brev5(m1) * 16 + m2 : (16 * (m2 >> 3) + brev4(m1)) * 8 + (m2 & 7);
-                if (a.edge2) {
-                    float v2;
-                    const float v = entry2(phis[cls], p0, max(pa, p0 - lphi), min(pb - 1, p0 + lphi), goff, v2);
-                    if (l16 == 0) { tab[idx] = (float)D * v; a.edge2[(tab - a.edge) + idx] = (float)D * v2; }
-                } else {
-                    const float v = entry(phis[cls], p0, max(pa, p0 - lphi), min(pb - 1, p0 + lphi), goff, gs);
-                    if (l16 == 0) tab[idx] = (float)D * v;
-                }
-            }
-        }
-        return;
-    }
-    fft_prep_front(kernel, pool_w, F, K, GZ, bd, Gz, f, 0, s_twl, s_twh, s_taps, gs, tid);
-    if (a.spec0 && tid < 64) {                                             // the half-wave twiddles in fft2048w's layout (fft_build_twiddles_wg)
-        const int h = tid >> 5, e = tid & 31, j = (e >> 1) + 16 * (e & 1);
-        float sn, cs;
-        sincospif(2.0f * (float)j / 64.0f, &sn, &cs);
-        s_twp[tid] = h ? make_float2(cs, -sn) : make_float2(1.0f, 0.0f);
-    }
-    __syncthreads();
-    if (a.elist && f == 0 && tid >= 64 && tid < 64 + 4 * kBandMaxEdge) a.elist[tid - 64] = es[(tid - 64) >> 2][(tid - 64) & 3];
-    if (wave == 0) fft_prep_transform(F, K, 1, H, col_of, nullptr, f, 0, s_twl, s_twh, s_scr, s_taps, Rs, lane);
-    else if (a.spec0 && !(LEAF_PREP_ABLATE & 8)) {
-        // ---- first blocks of the main kernel's workgroups, with the main kernel's own transform (fft2048w: the bits it would
-        // compute itself; s_twl is the table both transforms share)
-        extern __shared__ __attribute__((aligned(16))) float dyn_scr[];
-        float* scr = dyn_scr + (size_t)(wave - 1) * kWgScrFloats;
-        const unsigned scr_lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) float*)scr);
-        const OwnedClips deal{a.B * a.nblk, a.G, a.nblk};
-        for (int w = f * (kPrepWaves - 1) + wave - 1; w < a.G; w += F * (kPrepWaves - 1)) {
-            if (deal.count(w) <= 0) continue;
-            const int gb = deal.start(w), b = gb / a.nblk, c = gb - b * a.nblk, n_c = c * a.L;
-            const float* xb = static_cast<const float*>(a.x) + (size_t)b * a.T;
-            const unsigned short* xh = static_cast<const unsigned short*>(a.x) + (size_t)b * a.T;
-            float are[32], aim[32];
-#pragma unroll
-            for (int r = 0; r < 32; ++r) {
-                const int i = 64 * r + lane;                              // block rotated left by padL samples (leaf_fft_wg_kernel)
-                const int n = n_c - a.padL + ((i + a.padL) & (kFftN - 1));
-                const int nc = min(max(n, 0), a.T - 1);
-                const float v = a.io_bf16 ? __uint_as_float((unsigned)xh[nc] << 16) : xb[nc];
-                are[r] = (n >= 0 && n < a.T) ? v : 0.0f;
-                aim[r] = 0.0f;
-            }
-            fft2048w<false, false>(are, aim, scr, scr_lds, s_twl, s_twp, lane);
-            float2* dst = a.spec0 + (size_t)w * kWgRingFwdFloat2;
-#pragma unroll
-            for (int i = 0; i < 32; ++i) {
-                const int k = brev5(i);
-                if (k < kWgFwdBins / 64) dst[64 * k + lane] = make_float2(are[i], aim[i]);   // bins 0..1151 (kWgFwdBins)
-            }
-        }
-    }
-    __syncthreads();
-    if (LEAF_PREP_ABLATE & 4) return;
-    // ---- the seven sums of the decision
-    const float mu = fminf(fmaxf(kernel[2 * f], 0.0f), 3.14159274101257324f);
-    const int k0 = (int)rintf(mu * (float)(kFftN / 6.283185307179586));
-    float sums[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // tot | out2, ac(M/2), ac(3M/4) of class 1 | of class 2
-    float dcs = 0.0f, mxdc = 0.0f;                                 // what every window drops at DC: bins 0, -1 .. -63 are entries 0 .. 63 (kBandAdjacentDC)
-    float pmir[2] = {0.0f, 0.0f};                                  // mirrored pairs |R_k R_(2048-k)| inside a window that crosses Nyquist, 2 (k - 1024) >= 5 M / 16
-    float mxo[2] = {0.0f, 0.0f};                                   // the largest dropped R^2 per class (round 6: the bias bound)
-    int kbv[2];
-#pragma unroll
-    for (int cls = 0; cls < 2; ++cls) {
-        const int M = 256 << cls;
-        // bins kb .. kb + M - 1, centred on the filter.  Backward launches and LEAF_ALGO_STRICT_BAND_CLASSES keep the window inside the half
-        // spectrum 1..1024 (a.cross = 0); the forward's ring holds bins 0..1151 (kWgFwdBins), so its windows may cross Nyquist -- a filter whose pass band
-        // reaches beyond pi (the top one or two of the default mel bank) is then centred in its window instead of cut by it (round 6)
-        const int kb = min(max(k0 - M / 2, 1), (a.cross ? kWgFwdBins : kFftN / 2 + 1) - M);
-        kbv[cls] = kb;
-        const int rlo = kFftN - kb - M + 1;                                // ... are entries rlo .. rlo + M - 1 of R (descending bins)
-#pragma unroll
-        for (int i0 = 0; i0 < kFftN; i0 += kPrepWaves * 64) {
-            const int i = i0 + tid;
-            const float v = Rs[i];
-            if (cls == 0) {
-                sums[0] += v * v;
-                dcs += i < 64 ? v * v : 0.0f;
-                mxdc = fmaxf(mxdc, i < 64 ? v * v : 0.0f);
-            }
-            const int j = i - rlo;
-            const bool in = j >= 0 && j < M;
-            sums[1 + 3 * cls] += in ? 0.0f : v * v;
-            mxo[cls] = fmaxf(mxo[cls], in ? 0.0f : v * v);
-            sums[2 + 3 * cls] += in && j + M / 2 < M ? v * Rs[min(i + M / 2, kFftN - 1)] : 0.0f;
-            sums[3 + 3 * cls] += in && j + 3 * M / 4 < M ? v * Rs[min(i + 3 * M / 4, kFftN - 1)] : 0.0f;
-            // entry i is bin 2048 - i: above Nyquist for i < 1024, its mirror image (bin i) is entry 2048 - i
-            const int jm = kFftN - i - rlo;
-            pmir[cls] += in && i < kFftN / 2 && kFftN / 2 - i >= 5 * M / 32 && jm >= 0 && jm < M ? fabsf(v * Rs[(kFftN - i) & (kFftN - 1)]) : 0.0f;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        const float w = wave_sum(sums[k]);
-        if (lane == 0) red[wave][k] = w;
-    }
-#pragma unroll
-    for (int cls = 0; cls < 2; ++cls) {
-        const float w = wave_sum(pmir[cls]);
-        if (lane == 0) red[wave][10 + cls] = w;
-    }
-    {
-        const float w = wave_sum(dcs);
-        float m = mxdc;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        if (lane == 0) { red[wave][12] = w; red[wave][13] = m; }
-    }
-#pragma unroll
-    for (int cls = 0; cls < 2; ++cls) {
-        float m = mxo[cls];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        if (lane == 0) red[wave][8 + cls] = m;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int flags = 0, need = 0;
-#pragma unroll
-        for (int cls = 0; cls < 2; ++cls) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int col = k == 0 ? 0 : k + 3 * cls;
-                float s = 0.0f;
-#pragma unroll
-                for (int w = 0; w < kPrepWaves; ++w) s += red[w][col];
-                v[k] = s;
-            }
-            float pm = 0.0f;
-#pragma unroll
-            for (int w = 0; w < kPrepWaves; ++w) pm += red[w][10 + cls];
-            float odc = 0.0f, mdc = 0.0f;
-#pragma unroll
-            for (int w = 0; w < kPrepWaves; ++w) { odc += red[w][12]; mdc = fmaxf(mdc, red[w][13]); }
-            // (the bias-free energy bound counts what is dropped at DC kBandAdjacentDC / kBandAdjacent times too; not under round 5's rule, a.eta = kBandEta)
-            const float o2 = a.eta < kBandEta ? v[1] + (kBandAdjacentDC / kBandAdjacent - 1.0f) * odc : v[1];
-            bool ok = o2 <= a.eps2 * v[0] && v[2] <= a.eta * v[0] && v[3] <= a.eta * v[0] && pm <= a.eta * v[0];
-            // the smallest bias that admits the class beyond the strict rule (band_need): the filter's core is 2 sigma_k around the centre bin
-            const int Mc = 256 << cls;
-            const float sgc = fminf(fmaxf(kernel[2 * f + 1], bd.sigma_lo), bd.sigma_hi), sk = (float)kFftN / (6.2831853f * sgc);
-            const float dmin = (float)min(k0 - (kbv[cls] - 1), kbv[cls] + Mc - k0) - 2.0f * sk;
-            const float spw = pool_sigma(pool_w[f], K);
-            float mx = 0.0f;
-#pragma unroll
-            for (int w = 0; w < kPrepWaves; ++w) mx = fmaxf(mx, red[w][8 + cls]);
-            int nd = band_need(v[1], mx, v[2], v[3], v[0], a.eta, fabsf(Rs[(kFftN - k0) & (kFftN - 1)]),
-                               band_pool_gamma(spw, K, dmin, kFftN), spw, K, kFftN, pm, Mc, odc, mdc);
-            if (a.bwd_slabs && !band_deriv_fits(k0, kbv[cls], Mc, sk)) { ok = false; nd = kBandNever; }   // (backward: see kBandDerivCore)
-            if (a.force) { ok = a.force == cls + 1; nd = kBandNever; }
-            flags |= ok ? 1 << cls : 0;
-            need |= nd << (16 * cls);
-        }
-        if (a.classes) {
-            const bool c1 = (flags & 1) || band_bias_admits(a.cls_bias, f, true, need), c2 = (flags & 2) || band_bias_admits(a.cls_bias, f, true, need >> 16);
-            a.classes[f] = c1 ? 256 : c2 ? 512 : kFftN;
-        }
-        a.rec[4 * f] = flags;
-        a.rec[4 * f + 1] = kbv[0];
-        a.rec[4 * f + 2] = kbv[1];
-        a.rec[4 * f + 3] = need;          // bmin(256) | bmin(512) << 16, fp16 codes
-    }
-}
-// a.stamps != NULL (the table cache, leaf_forward_cached_f32; forward launches with grid (F, 2 + n_edge) only): every workgroup
-// validates its stamp (leaf_fft.hpp) and returns, or builds what it builds without one and stamps it
-__global__ __launch_bounds__(kPrepWaves * 64) void fft_prep_band_kernel(const float* __restrict__ kernel, const float* __restrict__ pool_w,
-                                                                        int F, int K, int GZ, GaborBounds bd, float2* __restrict__ H,
-                                                                        float* __restrict__ Gz, int* __restrict__ col_of, const BandTabArgs a) {
-    const int tid = threadIdx.x, f = blockIdx.x, y = blockIdx.y;
-    unsigned* slot = nullptr;
-    unsigned word = 0u;
-    if (a.stamps) {
-        // role 0: workgroup (f, 0); role 1: the decimated pooling windows (f, 1 + n_edge); role 2 + s: the edge table (f, 1 + s)
-        const int s = y - 1, role = y == 0 ? 0 : y == 1 + a.n_edge ? 1 : 2 + s;
-        StampKey key{};
-        key.kind = 2; key.F = F; key.K = K; key.hop = a.hop; key.T = a.T; key.role = role; key.n_edge = a.n_edge;
-#pragma unroll
-        for (int i = 0; i < kBandMaxEdge; ++i)
-            if (role == 2 + i) { key.e[0] = a.e[i].c; key.e[1] = a.e[i].m; key.e[2] = a.e[i].lo; key.e[3] = a.e[i].hi; }
-        key.eps2 = a.eps2; key.eta = a.eta; key.cross = a.cross; key.force = a.force; key.strict = a.strict;
-        slot = a.stamps + ((size_t)role * F + f) * kStampWords;
-        if (tid < kStampWords) word = stamp_word(tid, key, kernel, pool_w, f);
-        if (stamp_check(slot, word, tid)) return;
-    }
-    fft_prep_band_body(kernel, pool_w, F, K, GZ, bd, H, Gz, col_of, a);
-    if (slot) stamp_publish(slot, word, tid);
-}
-#endif
 
 // ---- device side of the main kernel -------------------------------------------------------------------------------------
 // Every workgroup builds the same plan from the per-filter records (wave 0, before the first barrier): lists of the filters

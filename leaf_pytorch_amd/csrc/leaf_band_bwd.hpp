@@ -1,5 +1,5 @@
 // leaf_band_bwd.hpp -- band-limited filter tasks of the static workgroup BACKWARD kernel (leaf_fft_wg_bwd.hpp), round 5
-// Part of libleaf_hip.so (gfx950 only); included by leaf_fft_wg_bwd.hpp.
+// Included by every unit (through leaf_fft_wg_bwd.hpp): templates, device functions, constexpr sizes (gfx950 only).
 //
 // The parameter gradients of the filters the forward runs on 256- / 512-point transforms (leaf_band.hpp), at the same decimated
 // rate.  With Zb[j] = conj(A'[kb + j]) R[j] the window's bins, z = F_M Zb (the band task's network: a plain M-point DFT matrix

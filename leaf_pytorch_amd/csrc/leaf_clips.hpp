@@ -1,5 +1,5 @@
 // leaf_clips.hpp -- batch assembly from a packed sample store (leaf_assemble_clips_f32): per-clip pad, crop, gain, peak
-// normalisation and time masks in one launch.  Compiled in inst_clips.hip; gfx950 only.
+// normalisation and time masks in one launch.  Included by inst_clips.hip only: kernels and their parameter structs (gfx950 only).
 //
 // Reference arithmetic being replaced (utilities/data/raw_transforms.py, per clip on the CPU there): PadToSize (torch: F.pad
 // 'replicate' / constant signal.min(); numpy: np.pad 'wrap'), RandomCrop / CenterCrop, RandomGain, PeakNormalization

@@ -1,5 +1,5 @@
-// leaf_common.hpp -- tuning knobs, vector types, Gabor tap / pooling-window formulas and their table kernels
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// leaf_common.hpp -- tuning knobs, vector types, sample loads (bfloat16 / PCM16 / mixup), Gabor tap / pooling-window formulas
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "leaf_fastmath.hpp"
@@ -8,8 +8,11 @@
 #include <algorithm>
 #include <type_traits>
 #include "leaf_hip.h"
+#include "leaf_params.hpp"
 
 namespace {
+
+using namespace leaf;                    // the launch structs (leaf_params.hpp); every csrc header reopens this one unnamed namespace
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte load at 4-byte alignment
@@ -71,23 +74,6 @@ __device__ __forceinline__ float mix_sample(const void* x, size_t clip, const Mi
     const float w = mix_load(x, clip, mc.partner, (size_t)min(max(n, 0), T - 1), mc.lam, mc.om, ST);
     return (n >= 0 && n < T) ? w : 0.0f;
 }
-#ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
-// The stand-alone mix (leaf_mixup_f32): out[b][n] = the mixed sample, fp32, read two rows / write one.  Grid B * tiles, tiles = ceil(T / 1024):
-// a workgroup mixes 1024 samples of one clip.
-__global__ __launch_bounds__(256) void mixup_kernel(const void* __restrict__ x, int st, int B, int T, int tiles, const int* __restrict__ perm,
-                                                    const float* __restrict__ lam, float* __restrict__ out) {
-    const int b = blockIdx.x / tiles;
-    const MixClip mc = mix_clip(perm, lam, b, B, T);
-    const size_t row = (size_t)b * T;
-    const int n0 = (blockIdx.x - b * tiles) * 1024 + threadIdx.x;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int n = n0 + 256 * j;
-        if (n < T) out[row + n] = st == kSamplePcm16 ? mix_load(x, row, mc.partner, n, mc.lam, mc.om, kSamplePcm16)
-                                                     : mix_load(x, row, mc.partner, n, mc.lam, mc.om, kSampleF32);
-    }
-}
-#endif
 __device__ __forceinline__ void io_store(void* p, size_t i, int bf16, float v) {
     if (bf16) static_cast<unsigned short*>(p)[i] = bf16_round(v);
     else static_cast<float*>(p)[i] = v;
@@ -109,8 +95,6 @@ constexpr int kAblate = LEAF_ABLATE;
 constexpr int kWavesPerWG = LEAF_WAVES_PER_WG;   // 8 -> 512 threads: 2 waves per SIMD
 constexpr int kUB = 5;                   // 16-sample n-blocks per unit (register tile = RT x kUB MFMA tiles x2)
 constexpr int kMaxLds = 160 * 1024;
-
-struct GaborBounds { float sigma_lo, sigma_hi; };
 
 // convolution.py:15-22 -- bounds are built from float32 tensors in the reference.
 inline GaborBounds gabor_bounds(int K) {
@@ -135,37 +119,7 @@ __device__ __forceinline__ void gabor_tap(float mu_raw, float sg_raw, GaborBound
     im = (norm * s) * env;
 }
 
-// ---------------------------------------------------------------------------------------------
-// tap tables
-// ---------------------------------------------------------------------------------------------
-
-// Direct table, the layout convolution.py:88-90 hands to conv1d: taps[2f][j] = Re, taps[2f+1][j] = Im,
-// t_j = j - K/2.
-#ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
-__global__ void taps_direct_kernel(const float* __restrict__ kernel, int F, int K, GaborBounds bd,
-                                   float* __restrict__ taps) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= F * K) return;
-    const int f = idx / K, j = idx - f * K;
-    float re, im;
-    gabor_tap(kernel[2 * f], kernel[2 * f + 1], bd, (float)(j - K / 2), re, im);
-    taps[(size_t)(2 * f) * K + j] = re;
-    taps[(size_t)(2 * f + 1) * K + j] = im;
-}
-#endif
-
 // impulse_responses.py:74-80
 __device__ __forceinline__ float pool_sigma(float w_raw, int K) { return fminf(fmaxf(w_raw, 2.0f / (float)K), 0.5f); }
-
-#ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
-__global__ void lowpass_window_kernel(const float* __restrict__ pool_w, int F, int K, float* __restrict__ g) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= F * K) return;
-    const int f = idx / K, j = idx - f * K;
-    const float half = 0.5f * (float)(K - 1);
-    const float q = ((float)j - half) / (pool_sigma(pool_w[f], K) * half);
-    g[idx] = expf(-0.5f * (q * q));
-}
-#endif
 
 }  // namespace

@@ -2,7 +2,7 @@
 // used by the PCEN epilogue:  (q + d)^(1/r) - d^(1/r) = d^(1/r) * expm1(log1p(q/d) / r)  for d > 0.
 // Both use Kahan's correction (evaluate the function at the ROUNDED intermediate u and rescale by the ratio of the
 // exact argument to the one u stands for), so the relative accuracy holds for arbitrarily small arguments; measured
-// against double precision by tools/check_fast_math.hip.
+// against double precision by tools/check_fast_math.hip.  Included by every unit: device functions.
 //
 // `#pragma clang fp contract(off)` in every function: whether the compiler fuses `1.0f + q * inv_d` into one FMA depends on
 // the code AROUND the inlined call, and the same frame finalized by two kernels (the row kernel, the workgroup kernels'

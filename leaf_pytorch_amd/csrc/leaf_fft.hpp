@@ -1,5 +1,5 @@
 // leaf_fft.hpp -- FFT (overlap-save) formulation of the fused forward: one wave = one 2048-sample block
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only).
 //
 // Why: the filterbank is a length-K cross-correlation per filter.  In direct (MFMA) form it costs ~2*K flops per
 // filter-sample even after the Hermitian halving; by the convolution theorem a block of N = 2048 input samples costs
@@ -354,15 +354,7 @@ constexpr int kPrepWaves = 8;
 // invalidates the stamp, builds exactly what it builds without one and writes the stamp last, so that a build cut short never reads
 // as valid.  Slots are laid out by role, [role][F]: role 0 the workgroup (f, 0) (spectra, pooling row, col_of, the band record and,
 // for f = 0, the edge list), role 1 the decimated pooling windows, role 2 + s the edge table of edge entry s.  A zeroed slot is invalid.
-constexpr int kStampWords = 32;                          // 128 bytes per slot
-constexpr unsigned kStampMagic = 0x4c454146u;
-struct StampKey {
-    int kind;              // 1: fft_prep_kernel, 2: fft_prep_band_kernel
-    int F, K, hop, T, role, n_edge;
-    int e[4];              // the role's edge entry (c, m, lo, hi); zeros for the other roles
-    float eps2, eta;
-    int cross, force, strict;
-};
+// (kStampWords words per slot, the key a table kernel builds: StampKey -- leaf_params.hpp)
 // word i of filter f's stamp for this call
 __device__ __forceinline__ unsigned stamp_word(int i, const StampKey& k, const float* __restrict__ kernel, const float* __restrict__ pool_w, int f) {
     switch (i) {
@@ -492,144 +484,9 @@ __device__ __forceinline__ void fft_prep_transform(int F, int K, int real_spec, 
     }
     if (lane == 0 && which == 0) col_of[f] = f;
 }
-#ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
-__global__ __launch_bounds__(kPrepWaves * 64) void fft_prep_kernel(const float* __restrict__ kernel,
-                                                                   const float* __restrict__ pool_w, int F, int K, int GZ,
-                                                                   GaborBounds bd, int real_spec, float2* __restrict__ H,
-                                                                   float* __restrict__ Gz, int* __restrict__ col_of,
-                                                                   float* __restrict__ lone, unsigned* __restrict__ stamps,
-                                                                   int hop, int T) {
-    __shared__ float2 s_twl[32 * 64];
-    __shared__ float2 s_twh[64];
-    __shared__ float s_scr[32 * 65];
-    __shared__ float2 s_taps[kFftN / 2 + 64];            // conj(w_f), K <= N/2 + 1
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int f = blockIdx.x;
-    // stamps != NULL (the table cache; grid (F, 1) only): validate or build, role 0
-    unsigned* slot = stamps ? stamps + (size_t)f * kStampWords : nullptr;
-    unsigned word = 0u;
-    if (slot) {
-        StampKey key{};
-        key.kind = 1; key.F = F; key.K = K; key.hop = hop; key.T = T; key.cross = real_spec;
-        if (tid < kStampWords) word = stamp_word(tid, key, kernel, pool_w, f);
-        if (stamp_check(slot, word, tid)) return;
-    }
-    // blockIdx.y (backward tables, real-spectrum form only): 0 the taps w, 1 d w/d mu = i t w, 2 d w/d sigma =
-    // (t^2/s^3 - 1/s) w (impulse_responses.py:5-16 differentiated; both stay Hermitian, so their spectra are real too)
-    const int which = blockIdx.y;
-    fft_prep_front(kernel, pool_w, F, K, GZ, bd, Gz, f, which, s_twl, s_twh, s_taps, nullptr, tid);
-    __syncthreads();
-    if (wave == 0) fft_prep_transform(F, K, real_spec, H, col_of, lone, f, which, s_twl, s_twh, s_scr, s_taps, nullptr, lane);
-    if (slot) stamp_publish(slot, word, tid);
-}
-#endif
 
-// Contiguous dealing of the nblocks = B * nblk blocks to G workgroups (the first `rem` get one more): workgroup w walks
-// blocks [start(w), start(w) + count(w)).  A clip whose nblk blocks all fall to one workgroup is OWNED by it: its partial
-// sums never leave that CU's reach and the workgroup finalizes it in its tail.  nblocks = 0: nothing is owned (kernels that
-// do not finalize).
-struct OwnedClips {
-    int nblocks, G, nblk;
-    __host__ __device__ int per() const { return nblocks / G; }
-    __host__ __device__ int rem() const { return nblocks % G; }
-    __host__ __device__ int start(int w) const { return w * per() + (w < rem() ? w : rem()); }
-    __host__ __device__ int count(int w) const { return per() + (w < rem() ? 1 : 0); }
-    __host__ __device__ int wg_of(int gb) const {
-        const int q = per(), r = rem(), cut = r * (q + 1);
-        return gb < cut ? gb / (q + 1) : r + (gb - cut) / (q > 0 ? q : 1);
-    }
-    __host__ __device__ bool owned(int b) const {
-        return nblocks > 0 && wg_of(b * nblk) == wg_of(b * nblk + nblk - 1);
-    }
-};
-// what the row arithmetic of the finalize step needs (fft_finalize_rows below)
-struct FinParams {
-    const float* part;     // [B][F][nslot][T']
-    int F, TP;
-    SlotGeom geo;
-    const float *bias, *alpha, *delta, *root, *ema_w;
-    float floor_;
-    int mode;              // bit0 PCEN, bit1 log1p, bit2 bf16 output, bit3 no floor (the backward's raw pooled tensor)
-    void* out;
-    float* raw_out;
-    const float* clip_scale2;   // LEAF_FLAG_PEAKNORM: [B] s_b^2 multiplying the pooled energies of clip b (NULL: none)
-    // set by a workgroup kernel for its own tail only: the per-frame sums of the clips it owns sit in its LDS, already added
-    // up ([rows from lds_row0][T']), instead of in `part`
-    const float* lds_sums = nullptr;
-    int lds_row0 = 0;
-    const void* lds_coef = nullptr;   // (the same kernels) FinCoef[F] in its LDS, evaluated at the kernel's start: the tail does not wait for the parameters
-};
-
-// ---- band-limited filter tasks (leaf_band.hpp; static workgroup kernels, frame sums in LDS) ---------------------------------
-// A frame whose window -- widened by the tails of the decimated pooling window -- is cut by the clip's ends (or would reach
-// past them) is an EDGE frame: its sum over block `c` comes from a dense per-(filter, block) table; [lo, hi) is the part of
-// the (cut) window that block owns, in absolute samples.
-constexpr int kBandMaxEdge = 12;
-struct BandEdge { int c, m, lo, hi; };
-struct BandParams {
-    const int* rec;        // [F][4]: bit 0 / 1 = the filter passes the 256- / 512-point criteria, first bin of its 256- / 512-point window (NULL: every filter on 2048 points)
-    const float* gz;       // [F][kBandGzFloats]: decimated pooling windows of both classes
-    const float* edge;     // [F][2][kBandMaxEdge][512]: edge-frame tables, register order of the class
-    const float* gz2;      // (backward kernels) gz and edge built from the window g[j] (j - c)^2: d pool_w at the decimated rate
-    const float* edge2;
-    const int* elist;      // [kBandMaxEdge][4]: the edge list (c, m, lo, hi) in device memory
-    int lds_off;           // float offset of the band area (plan, twiddle tables) in dynamic LDS
-    int reg_lo, reg_hi;    // frames reg_lo .. reg_hi take the shift-invariant window, the others are edge frames
-    int n_edge;
-    const float* bias;     // (forward kernels) the pooling biases of THIS call, [F]: the energy bound of the class decision follows them
-    float smax;            // > 1: the class decision may take them into account (leaf_band.hpp: band_bias_admits); NULL / <= 1: the strict decision alone (backward kernels, LEAF_ALGO_STRICT_BAND_CLASSES)
-};
-
-struct FftParams {
-    const void* x;         // [B][T] fp32, bf16 or 16-bit PCM by io_bf16
-    int io_bf16;           // sample type of x: kSampleF32 / kSampleBf16 / kSamplePcm16 (leaf_common.hpp)
-    const float2* H;       // [F][2048] complex spectra, or (real-spectrum kernels, odd K) [F][2048] floats
-    const float* Gz;       // [F][GZ]
-    float* part;           // [B][F][nslot][TP]: slot s = s-th block the frame's window meets (2, or 3 when K - 1 > L)
-    int nslot;
-    int B, T, TP, F, K, hop, padL;
-    int L;                 // valid outputs per block
-    int nblk;              // blocks per clip
-    int GZ;                // row length of Gz (multiple of 4)
-    int g_bufs;            // wave-private LDS pooling-row buffers: 2 (next row prefetched) when LDS allows, else 1
-    int NT;                // 64-sample rows a pooling window can touch: ceil((K+63)/64)
-    int scr_floats;        // wave-private LDS floats for transposes / energy rows
-    int fq;                // filters per task: kFftFQ when the batch fills the chip, fewer (more, shorter tasks) when not
-    int nfq;               // filter groups of fq
-    int total_tasks;       // B * nblk * nfq  (one wave per task)
-    // backward instantiation only (BWD = 1; real-spectrum tables R | R_mu | R_sigma stacked in H as [3][F][2048] floats)
-    const float* gpre;     // [B][F][TP] dL/d(pooled pre-floor)
-    const float* pool_w;   // [F] raw pooling widths
-    float* dkpart;         // [B*nblk][F][2] per-block partial (d mu, d sigma), before the clamp sub-gradient
-    float* dwpart;         // [B*nblk][F]    per-block partial d pool_w, before the clamp sub-gradient
-    const float* lone;     // even K, real-spectrum form: [F][2] the unpaired tap w_f[t = -K/2] (backward: [3][F][2] with d/dmu, d/dsigma)
-    int rot;               // rotation of the block for the real-spectrum form: K / 2 (= padL for odd K)
-    unsigned long long* trace;   // LEAF_TRACE builds only
-    // Clip-resident finalize (workgroup kernels): blocks are dealt contiguously, and with fin_fused != 0 a workgroup runs the
-    // row arithmetic (bias, floor, EMA, PCEN) itself for every clip it owns outright; fft_finalize_kernel then handles only
-    // the clips that straddle two workgroups.
-    FinParams fin;
-    int fin_fused;
-    int stream_ring;       // STREAM kernels: frames of the LDS ring of per-frame partial sums (a power of two)
-    BandParams band;       // band-limited filter tasks (rec == NULL: off)
-    const float2* spec0;   // [workgroups][kWgRingFloat2]: the half spectrum of every workgroup's FIRST block, computed by the table
-                           // launch on CUs it leaves idle (fft_prep_band_kernel); NULL: the kernel transforms it itself
-    // Waveform mixup in the load (leaf_common.hpp: mix_load), the kernels with a fused mix only; mix_lam == NULL: off
-    const int* mix_perm;   // [B] partner clip of every clip (clamped into [0, B) on the device)
-    const float* mix_lam;  // [B] weight of the clip itself; its partner gets 1 - lam
-};
-
-constexpr unsigned leaf_layout_hash_fft() {                              // see leaf_layout_hash_fused (leaf_fused.hpp)
-    unsigned h = leaf_layout_hash_fused();
-    h = leaf_mix(h, sizeof(FftParams)); h = leaf_mix(h, offsetof(FftParams, part)); h = leaf_mix(h, offsetof(FftParams, lone));
-    h = leaf_mix(h, offsetof(FftParams, trace)); h = leaf_mix(h, offsetof(FftParams, fin)); h = leaf_mix(h, offsetof(FftParams, stream_ring));
-    h = leaf_mix(h, sizeof(FinParams)); h = leaf_mix(h, offsetof(FinParams, geo)); h = leaf_mix(h, offsetof(FinParams, out));
-    h = leaf_mix(h, offsetof(FinParams, lds_row0)); h = leaf_mix(h, sizeof(OwnedClips)); h = leaf_mix(h, sizeof(SlotGeom));
-    h = leaf_mix(h, offsetof(FftParams, band)); h = leaf_mix(h, sizeof(BandParams)); h = leaf_mix(h, offsetof(BandParams, n_edge));
-    h = leaf_mix(h, offsetof(FftParams, mix_perm)); h = leaf_mix(h, offsetof(FftParams, mix_lam));
-    return h;
-}
-
+// (The kernels' arguments -- FftParams with its FinParams, BandParams and the dealing of blocks, OwnedClips -- are leaf_params.hpp's.)
+//
 // SK/SHOP > 0: window and hop known at compile time (the reference's default 401/160): every frame/window offset of
 // the pooling becomes an immediate, the energies never leave registers and no guard rows are needed.
 // SK = 0: generic geometry, energies go through wave-private LDS rows.
@@ -1344,26 +1201,6 @@ __device__ __forceinline__ void fft_finalize_tile(const FinParams& q, int row0, 
     }
 }
 
-// the row kernel: 16 rows x 128 frames per chunk by 1024 threads (a 1 s clip's T' = 100 frames is one chunk: three
-// dependent stages, each one pass per thread)
-// leaf_pcen_stream_f32: one lane per (stream, filter) row, the chunk's frames in order, smoother state in and out
-#ifndef LEAF_INST_TU
-__global__ void pcen_stream_kernel(const float* __restrict__ p, int BF, int n, FinParams q, const float* __restrict__ ema_in,
-                                   float* __restrict__ ema_out) {
-    const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    if (row >= BF) return;
-    const FinCoef c = fin_coef(q, row % q.F);
-    const float* pr = p + (size_t)row * n;
-    float M = ema_in ? ema_in[row] : pr[0];                     // a stream starts at its first frame (postprocessing.py:15)
-    for (int m = 0; m < n; ++m) {
-        const float v = pr[m];
-        if (q.mode & 1) M = fin_ema_step(c, v, M);
-        fin_store(q, (size_t)row * n + m, fin_point(c, q.mode, q.floor_, v, M));
-    }
-    if (ema_out && (q.mode & 1)) ema_out[row] = M;
-}
-#endif
-
 // The tail of a workgroup kernel (all its waves call, after their last task): the rows of the clips whose blocks this workgroup
 // ran itself, [b_lo F, b_hi F), finalized with `tile_mem` (the waves' scratch, free by now; >= fin_tile_floats<TR, 64>() floats)
 // as tile memory.  Release (the partial sums have reached L2) - barrier - tiles.  Rows of up to 128 frames go through in one
@@ -1384,6 +1221,8 @@ __device__ __forceinline__ void wg_tail_finalize(const FinParams& fin, int b_lo,
     }
 }
 
+// the row kernel: 16 rows x 128 frames per chunk by 1024 threads (a 1 s clip's T' = 100 frames is one chunk: three
+// dependent stages, each one pass per thread)
 constexpr int kFinKernelRows = 16, kFinKernelCols = 128;
 // NT = 512 when there are many tiles (four workgroups share a CU: throughput), 1024 when there are few (every stage one pass
 // per thread: latency -- small batches, long rows)

@@ -1,5 +1,5 @@
 // leaf_fft_small.hpp -- the whole forward of a SMALL batch in ONE launch (LEAF_ALGO_FFT_SMALL)
-// One of the kernel families of libleaf_hip.so (gfx950 only); instantiated in inst_fft_small.hip, see leaf_inst.hpp.
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only); instantiated in inst_fft_small.hip, see leaf_inst.hpp.
 //
 // Why: inference in the reference is a handful of 1 s chunks per call (test.py:57-71,125-128: pad_input -> (n_sec,1,sr) ->
 // mean over chunks).  At B = 4 the overlap-save path is 40 blocks of work on 256 CUs and three DEPENDENT launches -- tables
@@ -40,29 +40,6 @@ constexpr int kSmallSplitWaves = 7;              // SPLIT: 6 block waves + the t
 constexpr int kSmallSplitRing = kSmallSplitWaves - 1;
 constexpr int kSmallRing = 10;                   // most block spectra resident at once (one pass = up to this many blocks)
 constexpr int kSmallMaxBlocks = 2 * kSmallRing;  // clips up to two passes long take this kernel
-
-struct SmallParams {
-    const void* x;          // [B][T] fp32, bf16 or 16-bit PCM by io_bf16
-    int io_bf16;            // sample type of x: kSampleF32 / kSampleBf16 / kSamplePcm16 (leaf_common.hpp)
-    const float* kernel;    // [F][2] (mu, sigma), unclamped
-    const float* pool_w;    // [F]
-    GaborBounds bd;
-    int B, T, TP, F, nblk;
-    int ring;               // block spectra held in LDS per pass (<= kSmallRing)
-    FinParams fin;          // part unused: the sums stay in LDS
-    // SPLIT variant (two workgroups per (clip, filter), grid (F, B, 2)): the EMA state the first half hands to the second,
-    // [B][F] pairs (epoch, value bits) in the workspace; `epoch` is this launch's 64-bit ticket (host counter from a random seed)
-    unsigned long long epoch;
-    unsigned long long* carry;
-    // Waveform mixup in the load (leaf_common.hpp: mix_load); mix_lam == NULL: off
-    const int* mix_perm;    // [B]
-    const float* mix_lam;   // [B]
-};
-
-constexpr unsigned leaf_layout_hash_small() {
-    return leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_layout_hash_fft(), sizeof(SmallParams)), offsetof(SmallParams, fin)), offsetof(SmallParams, ring)),
-                             offsetof(SmallParams, carry)), offsetof(SmallParams, mix_lam));
-}
 
 // dynamic LDS: twiddles | R (the taps first) | full transposition scratch of every wave | frame sums | finalize coefficients |
 // pooling-weight vectors.  (Round 5: no spectrum ring -- a wave keeps its block's spectrum in registers between the phases.)

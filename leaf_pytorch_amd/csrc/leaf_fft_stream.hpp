@@ -1,5 +1,5 @@
 // leaf_fft_stream.hpp -- one step of a running stream in ONE launch (leaf_stream_step_f32)
-// One of the kernel families of libleaf_hip.so (gfx950 only); instantiated in inst_fft_stream.hip, see leaf_inst.hpp.
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only); instantiated in inst_fft_stream.hip, see leaf_inst.hpp.
 //
 // Why: chunked real-time inference (LeafStream) ran torch.cat -> the whole fused forward over [history | chunk] -> slice ->
 // leaf_pcen_stream_f32 -> slice: two product launches and four stock ones per 10..100 ms of audio, host-bound.  The one-launch
@@ -49,57 +49,6 @@
 #include "leaf_fft_small.hpp"
 
 namespace {
-
-struct StreamParams {
-    const void* chunk;        // [B][chunk_stride], the first Tc samples of a row; fp32 or 16-bit PCM by `pcm`
-    const void* hist_in;      // [B][H]: the history half this step reads, hist_len samples of a row (the bank: half 0)
-    void* hist_out;           // [B][H]: the other half, receives the next step's history (the bank: half 1)
-    float* ema_state;         // [B][F]
-    long long chunk_stride;   // samples
-    int pcm;                  // sample type of chunk and history: kSampleF32 / kSamplePcm16 (leaf_common.hpp)
-    const float* kernel;      // [F][2] (mu, sigma), unclamped
-    const float* pool_w;      // [F]
-    GaborBounds bd;
-    int B, F, H;
-    int hist_len, Tc, drop;   // the virtual buffer is hist_len + Tc samples; [drop, hist_len + Tc) is the next step's history
-    int first, n, started;    // frames emitted; has a frame been emitted before (the smoother has a state)
-    int c_lo, nb;             // blocks the emitted frames' windows meet
-    FinParams fin;            // part unused: the sums stay in LDS; fin.out is [B][F][n]
-};
-
-// where ONE stream stands in one pass of the body (wave-uniform: from the kernel arguments alone)
-struct StreamPos {
-    const void* hist_in;      // the history half the stream reads ...
-    void* hist_out;           // ... and the one it hands over to
-    int hist_len, Tc, drop, first, n, started, c_lo, nb;   // as in StreamParams
-    int hist_off, chunk_off;  // samples skipped in front of the history row / the chunk row (the bank's ending pass; else 0)
-    int n_lds;                // frame sums the launch's LDS holds (>= n)
-    int n_row, o_lo, o_end;   // out rows are n_row long; this pass's frames start at column o_lo and zeros follow them up to o_end
-};
-
-// the bank: up to kBankSlots slots per launch and as many PASS records of 6 words; a slot has one record, or two when its stream
-// ends on a chunk that also completes frames (header comment), consecutive, the last one marked
-constexpr int kBankSlots = 128;
-struct StreamPassRec {
-    // w[0] = hist_len | Tc << 16          w[1] = drop | first << 16       w[2] = n | c_lo << 16 | nb << 24
-    // w[3] = hist_off | chunk_off << 16   w[4] = o_lo | o_end << 16       (StreamPos)
-    // w[5] = started | parity << 1 | idle << 2 | last << 3
-    unsigned w[6];
-};
-struct StreamBankParams {
-    StreamParams c;                   // what the slots share; its position fields are unused; fin.out is [B][F][n_max]
-    int b0;                           // the launch's first slot: workgroup (f, y) serves row b0 + y
-    int n_lds, n_max;
-    unsigned first[kBankSlots / 4];   // byte y: slot y's first record
-    StreamPassRec rec[kBankSlots];
-};
-static_assert(sizeof(StreamBankParams) <= 4096, "the records travel in the kernel argument segment");
-
-constexpr unsigned leaf_layout_hash_stream() {
-    return leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_mix(leaf_layout_hash_fft(), sizeof(StreamParams)), offsetof(StreamParams, fin)),
-                                               offsetof(StreamParams, bd)), offsetof(StreamParams, c_lo)),
-                             sizeof(StreamBankParams)), offsetof(StreamBankParams, rec));
-}
 
 // one pass of stream b at position s; dynamic LDS: the small kernel's layout with s.n_lds frame sums.  BANK: out rows are longer
 // than the pass's frames and get their zeros here (the uniform step has no such columns and carries no code for them)
@@ -348,7 +297,6 @@ __device__ __forceinline__ void leaf_fft_stream_body(const StreamParams& p, cons
         if (f == 0) move_history(tid - 64, (NW - 1) * 64);
     }
 }
-
 
 // the uniform step: every stream stands where StreamParams says; dynamic LDS fft_small_lds_bytes(kSmallWaves, n)
 template <int SK, int SHOP>

@@ -1,5 +1,5 @@
 // leaf_fft_wg.hpp -- overlap-save forward, second generation: one WORKGROUP per block, spectrum shared through LDS
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only).
 //
 // Why (round-1 profile of leaf_fft_kernel, profiles/r01): the kernel is fp32-VALU-issue-bound but issues only ~0.49 of
 // the SIMD's slots: a wave issues at most one VALU instruction per ~4.6 cycles, so two waves per SIMD cannot fill a
@@ -26,7 +26,8 @@
 #pragma once
 #include <type_traits>
 #include "leaf_fft.hpp"
-#include "leaf_wg_queue.hpp"        // the task queue, its protocol, the block and spectrum-row loads: shared by all workgroup kernels
+#include "leaf_inst.hpp"            // leaf::FftKernel: what the instance ladder at the end of this header hands out
+#include "leaf_wg_queue.hpp"       // the task queue, its protocol, the block and spectrum-row loads: shared by all workgroup kernels
 
 namespace {
 
@@ -1242,25 +1243,23 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void leaf_fft_wg_kernel_var(
     static_assert(XK != kWgXAny && (XK != kWgXF32 || TAILC != 128) && (TAILC == 64 || TAILC == 128), "that pair is leaf_fft_wg_kernel");
     leaf_fft_wg_body<SK, SHOP, NW, false, XK, TAILC>(p);
 }
-using FftKernelFn = void (*)(const FftParams);
 // The instance ladder of the translation units (inst_fft_wg*.hip): the tail-finalize kernel of sample kind XK for a geometry and a
 // tail tile, nullptr where there is none.  NWX: a further workgroup size for 401/160, 801/320, 201/80 (tools builds), 0 = none.
 template <int SK, int SHOP, int NW, int XK, int TAILC>
-constexpr FftKernelFn wg_tail_kernel() {
+constexpr FftKernel wg_tail_kernel() {
     if constexpr (XK == kWgXF32 && TAILC == 128) return leaf_fft_wg_kernel<SK, SHOP, NW, false>;
     else return leaf_fft_wg_kernel_var<SK, SHOP, NW, XK, TAILC>;
 }
 template <int XK, int TAILC>
-inline FftKernelFn wg_tail_instance_of(int sk, int nw) {
+inline FftKernel wg_tail_instance_of(int sk, int nw) {
     if (sk == 401 && nw == 12) return wg_tail_kernel<401, 160, 12, XK, TAILC>();
     if (sk == 801 && nw == 10) return wg_tail_kernel<801, 320, 10, XK, TAILC>();
     if (sk == 201 && nw == 12) return wg_tail_kernel<201, 80, 12, XK, TAILC>();
     return nullptr;
 }
 template <int XK>
-inline const void* wg_tail_instance(int sk, int nw, int tailc) {
-    const FftKernelFn fn = tailc == 128 ? wg_tail_instance_of<XK, 128>(sk, nw) : tailc == 64 ? wg_tail_instance_of<XK, 64>(sk, nw) : nullptr;
-    return reinterpret_cast<const void*>(fn);
+inline FftKernel wg_tail_instance(int sk, int nw, int tailc) {
+    return tailc == 128 ? wg_tail_instance_of<XK, 128>(sk, nw) : tailc == 64 ? wg_tail_instance_of<XK, 64>(sk, nw) : nullptr;
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // leaf_fft_wg4k.hpp -- overlap-save forward with 4096-sample blocks for the long 32 kHz window (K = 801, hop = 320)
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only).
 //
 // Why: with 2048-sample blocks a K = 801 window leaves L = 960 valid outputs per transform (47 %); a 4096-sample block
 // leaves 3200 (78 %).  A wave cannot hold a 4096-point transform (128 data registers), but it does not have to: one
@@ -64,256 +64,6 @@ constexpr size_t kFft4WtFloats = 2 * 2048;
 // per-filter tables of the 4096-point plan (floats): (R_lo, R_hi)[2048] f2 | (D_lo, D_hi)[2048] f4   (derivative slabs: the second part
 // holds (d/dmu lo, d/dmu hi, d/dsigma lo, d/dsigma hi)[2048] in the mu slab; fft4k_prep_kernel)
 constexpr size_t kFft4TabFloats = 2048 * 6;
-
-// ---- tables: one workgroup per filter.  z = conj(taps) in zero-phase layout over 4096 points; its spectrum through two
-// 2048-point transforms (even / odd samples) and the decimation-in-time butterfly; real by the Hermitian symmetry of the
-// taps about the centre (impulse_responses.py:5-16), 1 / 4096 folded in.
-#ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
-__global__ __launch_bounds__(kPrepWaves * 64) void fft4k_prep_kernel(const float* __restrict__ kernel, const float* __restrict__ pool_w,
-                                                                     int F, int K, GaborBounds bd, float* __restrict__ tab,
-                                                                     float* __restrict__ Grow, int RG, float2* __restrict__ Wt = nullptr,
-                                                                     const BandTabArgs a = BandTabArgs{}) {
-    __shared__ float2 s_twl[32 * 64];
-    __shared__ float2 s_twh[64];
-    __shared__ float s_scr[32 * 65];
-    __shared__ float2 s_taps[2048 + 64];                                  // conj(w_f), K <= 2049; afterwards the spectrum R[4096] (band decision)
-    __shared__ float red[kPrepWaves][7];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int f = blockIdx.x;
-    // blockIdx.y (backward tables): 0 the taps w, 1 d w / d mu = i t w, 2 d w / d sigma = (t^2 / s^3 - 1 / s) w -- as
-    // fft_prep_kernel; slab `which` of the table holds their spectra (the D tables matter for the taps only)
-    const int which = blockIdx.y;
-    tab += (size_t)which * F * kFft4TabFloats;
-    const float mu = kernel[2 * f], sg = kernel[2 * f + 1];
-    const float sgc = fminf(fmaxf(sg, bd.sigma_lo), bd.sigma_hi);
-    for (int j = tid; j < K; j += kPrepWaves * 64) {
-        float a_, b_;
-        const float t = (float)(j - K / 2);
-        gabor_tap(mu, sg, bd, t, a_, b_);
-        if (which == 1) {
-            const float a0 = a_;
-            a_ = -t * b_;
-            b_ = t * a0;
-        } else if (which == 2) {
-            const float c = t * t / (sgc * sgc * sgc) - 1.0f / sgc;
-            a_ *= c;
-            b_ *= c;
-        }
-        s_taps[j] = make_float2(a_, -b_);
-    }
-    if (which == 0) {   // de-interleaved pooling rows: Ge[64 + i] = g[2 i], Go[64 + i] = g[2 i + 1]  (impulse_responses.py:74-80)
-        const float half = 0.5f * (float)(K - 1);
-        const float sp = pool_sigma(pool_w[f], K);
-        for (int jj = tid; jj < 2 * RG; jj += kPrepWaves * 64) {             // RG floats per parity row (kWg4RowFloats for K = 801)
-            const int h = jj / RG, i = jj - h * RG - kGPad, j = 2 * i + h;
-            float v = 0.0f;
-            if (i >= 0 && j < K) {
-                const float q = ((float)j - half) / (sp * half);
-                v = expf(-0.5f * (q * q));
-            }
-            Grow[(size_t)f * 2 * RG + jj] = v;
-        }
-    }
-    if (which == 0 && f == 0 && Wt) {                                     // w^e, e < 2048: shared by every filter (round 4)
-        for (int e = tid; e < 2048; e += kPrepWaves * 64) {
-            float sn, cs;
-            sincospif(2.0f * (float)e / (float)kFft4N, &sn, &cs);          // the expression the D tables are built from, below
-            Wt[e] = make_float2(cs, -sn);
-        }
-    }
-    fft_build_twiddles(s_twl, s_twh, tid, kPrepWaves * 64);
-    __syncthreads();
-    // band-limited filter tasks of the static forward kernel (leaf_band.hpp): the class decision is taken here, from the spectrum
-    const bool decide = which == 0 && a.rec != nullptr;                   // (uniform over the workgroup)
-    if (wave != 0 && !decide) return;
-    float* Rs = reinterpret_cast<float*>(s_taps);                         // [4096]: entry i <-> R[i] (the filter lives at entries 4096 - bin)
-    if (wave == 0) {
-        auto tap_at = [&](int i) {                                        // zero-phase layout: index i <-> t = i (i < 2048) or i - 4096
-            const int j = (i < kFft4N / 2 ? i : i - kFft4N) + K / 2;
-            return (j >= 0 && j < K) ? s_taps[j] : make_float2(0.0f, 0.0f);
-        };
-        // the even samples' transform first, then the odd ones' (round 5: both sets loaded up front were 128 live registers next
-        // to a transform's temporaries -- 244 B of scratch per lane)
-        float ere[32], eim[32];
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            const float2 te = tap_at(2 * (64 * r + lane));
-            ere[r] = te.x; eim[r] = te.y;
-        }
-        fft2048(ere, eim, s_scr, s_twl, s_twh, lane);
-        asm volatile("" : "+v"(ere[0]), "+v"(ere[31]) : : "memory");        // (the odd samples are read after it)
-        float ore[32], oim[32];
-#pragma unroll
-        for (int r = 0; r < 32; ++r) {
-            const float2 to = tap_at(2 * (64 * r + lane) + 1);
-            ore[r] = to.x; oim[r] = to.y;
-        }
-        fft2048(ore, oim, s_scr, s_twl, s_twh, lane);
-        // slab layout (kFft4TabFloats floats per filter): R2[2048] float2 = (R_lo[e], R_hi[e]) | D4[2048] float4 = (D_lo[e], D_hi[e]):
-        // the values a bin needs together sit together, one 8- / 16-byte load per bin instead of two (round 4: a load instruction
-        // costs these kernels more than four VALU instructions)
-        float2* R2 = reinterpret_cast<float2*>(tab + (size_t)f * kFft4TabFloats);
-        float4* D4 = reinterpret_cast<float4*>(tab + (size_t)f * kFft4TabFloats + 4096);
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-            const int e = 64 * brev5(i) + lane;
-            float s, c;
-            sincospif(2.0f * (float)e / (float)kFft4N, &s, &c);              // w^e = (c, -s)
-            const float tr = ore[i] * c + oim[i] * s;                         // Re(w^e Xo[e])
-            const float rlo = (ere[i] + tr) * (1.0f / kFft4N), rhi = (ere[i] - tr) * (1.0f / kFft4N);
-            if (which == 0) {
-                R2[e] = make_float2(rlo, rhi);
-                D4[e] = make_float4(rlo * c, -rlo * s, rhi * c, -rhi * s);
-                if (decide) { Rs[e] = rlo; Rs[e + 2048] = rhi; }          // (this wave was the taps' only reader)
-            } else {
-                // the derivative tables' D slots carry (d/dmu lo, d/dmu hi, d/dsigma lo, d/dsigma hi) of bin e as ONE 16-byte entry
-                // (in the mu slab: which = 1 writes the first half of each entry, which = 2 the second): the backward's dot products
-                // take one load per bin and half instead of four (-1.4 .. -2.1 % of the backward: profiles/r04/ab_table_addressing.txt)
-                float2* ms = reinterpret_cast<float2*>(tab - (size_t)(which - 1) * F * kFft4TabFloats + (size_t)f * kFft4TabFloats + 4096);
-                ms[2 * e + (which - 1)] = make_float2(rlo, rhi);
-            }
-        }
-    }
-    if (!decide) return;
-    __syncthreads();
-    // ---- class decision (leaf_band.hpp; one class here: a 512-bin window of the 4096-point spectrum, decimation 8): the window
-    // [kb, kb + 512) around the centre bin inside bins 1..2048 are entries rlo .. rlo + 511 of R (descending bins)
-    constexpr int M = 512;
-    const float muc = fminf(fmaxf(mu, 0.0f), 3.14159274101257324f);
-    const int k0 = (int)rintf(muc * (float)(kFft4N / 6.283185307179586));
-    const int kb = min(max(k0 - M / 2, 1), kFft4N / 2 + 1 - M);
-    const int rlo = kFft4N - kb - M + 1;
-    float sums[4] = {0.0f, 0.0f, 0.0f, 0.0f};                            // total | outside the window | |autocorrelation| at M/2, 3M/4
-    float mxo = 0.0f;                                                    // the largest dropped R^2 (round 6: the bias bound, leaf_band.hpp)
-    float dcs = 0.0f, mxdc = 0.0f;                                       // ... and what is dropped at DC: bins 0, -1 .. -63 = entries 0 .. 63 (kBandAdjacentDC)
-#pragma unroll
-    for (int i0 = 0; i0 < kFft4N; i0 += kPrepWaves * 64) {
-        const int i = i0 + tid;
-        const float v = Rs[i];
-        const int j = i - rlo;
-        const bool in = j >= 0 && j < M;
-        sums[0] += v * v;
-        sums[1] += in ? 0.0f : v * v;
-        mxo = fmaxf(mxo, in ? 0.0f : v * v);
-        dcs += i < 64 ? v * v : 0.0f;
-        mxdc = fmaxf(mxdc, i < 64 ? v * v : 0.0f);
-        sums[2] += in && j + M / 2 < M ? fabsf(v * Rs[min(i + M / 2, kFft4N - 1)]) : 0.0f;
-        sums[3] += in && j + 3 * M / 4 < M ? fabsf(v * Rs[min(i + 3 * M / 4, kFft4N - 1)]) : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float w = wave_sum(sums[k]);
-        if (lane == 0) red[wave][k] = w;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mxo = fmaxf(mxo, __shfl_xor(mxo, o));
-    if (lane == 0) red[wave][4] = mxo;
-    {
-        const float w = wave_sum(dcs);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mxdc = fmaxf(mxdc, __shfl_xor(mxdc, o));
-        if (lane == 0) { red[wave][5] = w; red[wave][6] = mxdc; }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float s = 0.0f;
-#pragma unroll
-            for (int w = 0; w < kPrepWaves; ++w) s += red[w][k];
-            v[k] = s;
-        }
-        float odc = 0.0f, mdc = 0.0f;
-#pragma unroll
-        for (int w = 0; w < kPrepWaves; ++w) { odc += red[w][5]; mdc = fmaxf(mdc, red[w][6]); }
-        const float o2 = a.eta < kBandEta ? v[1] + (kBandAdjacentDC / kBandAdjacent - 1.0f) * odc : v[1];   // (leaf_band.hpp: what is dropped at DC)
-        bool ok = o2 <= a.eps2 * v[0] && v[2] <= a.eta * v[0] && v[3] <= a.eta * v[0];
-        // the smallest bias that admits the class beyond the strict rule (leaf_band.hpp: band_need, band_pool_gamma)
-        const float sk = (float)kFft4N / (6.2831853f * sgc), spw = pool_sigma(pool_w[f], K);
-        const float dmin = (float)min(k0 - (kb - 1), kb + M - k0) - 2.0f * sk;
-        float mx = 0.0f;
-#pragma unroll
-        for (int w = 0; w < kPrepWaves; ++w) mx = fmaxf(mx, red[w][4]);
-        int nd = band_need(v[1], mx, v[2], v[3], v[0], a.eta, fabsf(Rs[(kFft4N - k0) & (kFft4N - 1)]),
-                           band_pool_gamma(spw, K, dmin, kFft4N), spw, K, kFft4N, 0.0f, M, odc, mdc);
-        if (a.bwd_slabs && !band_deriv_fits(k0, kb, M, sk)) { ok = false; nd = kBandNever; }          // (backward: leaf_band.hpp, kBandDerivCore)
-        if (a.force) { ok = a.force == 2; nd = kBandNever; }
-        if (a.classes) a.classes[f] = (ok || band_bias_admits(a.cls_bias, f, true, nd)) ? M : kFft4N;
-        a.rec[4 * f] = ok ? 2 : 0;                                        // (bit 1: the four-filters-per-task class of band_build_plan)
-        a.rec[4 * f + 1] = kb;
-        a.rec[4 * f + 2] = kb;
-        a.rec[4 * f + 3] = kBandNever | (nd << 16);                       // bmin (fp16 codes): never the eight-per-task class | the 512-bin class
-    }
-}
-
-// The tables of the band tasks on 4096-sample blocks (K = 801 / hop = 320; as the blockIdx.y > 0 workgroups of
-// fft_prep_band_kernel, one class).  Grid (F, 1 + n_edge): workgroup (f, 0) the decimated pooling window G~(tau) =
-// 8 sum_u g[tau - u] phi_8[|u|], tau = c0min + 8 j; workgroup (f, 1 + s) the dense table of edge entry s over the block's 512
-// decimated samples, in the register order of the task (the lane reads entry 16 k + l2 of its register k).
-__global__ __launch_bounds__(kPrepWaves * 64) void fft4k_band_tab_kernel(const float* __restrict__ pool_w, int F, int K, const BandTabArgs a) {
-    __shared__ float gs[64 * kPoolRowsMax];
-    __shared__ float gs2[64 * kPoolRowsMax];
-    __shared__ float phis[kBandLh * 8 + 1];
-    __shared__ int es[kBandMaxEdge][4];
-    constexpr int D = 8, LPHI = kBandLh * D;
-    const int tid = threadIdx.x, f = blockIdx.x, l16 = tid & 15, grp = tid >> 4;
-    if (tid <= LPHI) phis[tid] = kBandPhi8[tid];
-#pragma unroll
-    for (int s = 0; s < kBandMaxEdge; ++s)
-        if (tid == 256 + s) { es[s][0] = a.e[s].c; es[s][1] = a.e[s].m; es[s][2] = a.e[s].lo; es[s][3] = a.e[s].hi; }
-    {
-        const float half = 0.5f * (float)(K - 1), sp = pool_sigma(pool_w[f], K);
-        for (int j = tid; j < K; j += kPrepWaves * 64) {                   // the pooling window, as fft4k_prep_kernel evaluates it
-            const float q = ((float)j - half) / (sp * half);
-            gs[j] = expf(-0.5f * (q * q));
-            gs2[j] = gs[j] * (((float)j - half) * ((float)j - half));     // (backward tables: d pool_w, leaf_band_bwd.hpp)
-        }
-    }
-    __syncthreads();
-    auto entry = [&](int p0, int lo, int hi, int goff, const float* win) {   // sixteen lanes per table entry
-        float acc = 0.0f;
-#pragma unroll 4
-        for (int pp = lo + l16; pp <= hi; pp += 16) {
-            const int u = p0 - pp;
-            acc = fmaf(win[pp + goff], phis[u < 0 ? -u : u], acc);
-        }
-        return band_row_sum(acc);
-    };
-    if (blockIdx.y == 0) {
-        const int len = band_gz_len_d(K, a.hop, 32, D), c0 = band_c0min_d(K, a.hop, 32, D);
-        const int gzs = band4k_gz_floats(K, a.hop);                        // (run-time gcd loops: once, not per entry)
-        float* gzf = a.gz + (size_t)f * gzs;
-        float* gz2f = a.gz2 ? a.gz2 + (size_t)f * gzs : nullptr;
-        for (int j = grp; j < len; j += kPrepWaves * 4) {
-            const int tau = c0 + D * j;
-            const float v = entry(tau, max(0, tau - LPHI), min(K - 1, tau + LPHI), 0, gs);
-            if (l16 == 0) gzf[j] = (float)D * v;
-            if (a.gz2) {
-                const float v2 = entry(tau, max(0, tau - LPHI), min(K - 1, tau + LPHI), 0, gs2);
-                if (l16 == 0) gz2f[j] = (float)D * v2;
-            }
-        }
-        if (f == 0 && tid < 4 * kBandMaxEdge) a.elist[tid] = es[tid >> 2][tid & 3];
-        return;
-    }
-    const int s = blockIdx.y - 1;
-    const int c = es[s][0], goff = c * a.L - (es[s][1] * a.hop - a.padL);
-    const int pa = es[s][2] - c * a.L, pb = es[s][3] - c * a.L;
-    float* tabe = a.edge + ((size_t)f * kBandMaxEdge + s) * 512;
-    for (int m = grp; m < 512; m += kPrepWaves * 4) {
-        int p0 = m * D;
-        if (p0 - kFft4N + LPHI >= pa) p0 -= kFft4N;
-        else if (p0 + kFft4N - LPHI < pb) p0 += kFft4N;
-        const float v = entry(p0, max(pa, p0 - LPHI), min(pb - 1, p0 + LPHI), goff, gs);
-        if (l16 == 0) tabe[brev5(m >> 4) * 16 + (m & 15)] = (float)D * v;
-        if (a.edge2) {
-            const float v2 = entry(p0, max(pa, p0 - LPHI), min(pb - 1, p0 + LPHI), goff, gs2);
-            if (l16 == 0) a.edge2[(tabe - a.edge) + brev5(m >> 4) * 16 + (m & 15)] = (float)D * v2;
-        }
-    }
-}
-#endif
 
 // Rows k = 0..31 of the two ring streams a 4096-point multiply needs, eight rows at a time:
 //   a[j] = A'[64 k + lane],  m[j] = A'[2048 - 64 k - lane],  k = 8 C + j.

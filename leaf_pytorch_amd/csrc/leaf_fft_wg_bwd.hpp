@@ -1,5 +1,5 @@
 // leaf_fft_wg_bwd.hpp -- overlap-save BACKWARD on the workgroup-per-block structure of leaf_fft_wg.hpp, with dL/dx
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only).
 //
 // Same task queue, same LDS ring for the block spectrum A' as the forward kernel; an inverse task (block, filter f) is the
 // backward epilogue of leaf_fft_kernel<.., BWD = 1> (leaf_fft.hpp), i.e. with u = conj(y) = FFT(conj(A' R_f)) in registers:

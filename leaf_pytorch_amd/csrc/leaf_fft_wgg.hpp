@@ -1,6 +1,6 @@
 // leaf_fft_wgg.hpp -- the workgroup-per-block overlap-save forward (leaf_fft_wg.hpp) for ANY window the 2048-sample plan
 // covers: window, hop and block length at run time, odd and even windows.
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only).
 //
 // Same task queue, spectrum ring and LDS-lean transform as leaf_fft_wg_kernel; what differs is the pooling, which cannot
 // unroll over compile-time frame offsets.  Round 1's generic pooling (leaf_fft.hpp: per frame, a switch on the window's

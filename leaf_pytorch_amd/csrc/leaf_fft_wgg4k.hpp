@@ -1,6 +1,6 @@
 // leaf_fft_wgg4k.hpp -- the 4096-sample overlap-save forward (leaf_fft_wg4k.hpp) for ANY odd window 833 <= K <= 2049:
 // window, hop and block length at run time.
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only).
 //
 // With 2048-sample blocks a window of K = 1103 / 1201 (44.1 / 48 kHz) leaves 44 / 41 % valid outputs per transform, and
 // K > 1217 does not fit at all; 4096-sample blocks leave 73 / 71 % and reach K = 2049.  Queue, ring, the decimation-in-time

@@ -1,6 +1,6 @@
 // leaf_fft_wgg4k_bwd.hpp -- overlap-save BACKWARD on 4096-sample blocks with run-time geometry (odd windows 833..2049):
 // the parameter gradients of leaf_fft_wgg_bwd.hpp on the plan of leaf_fft_wgg4k.hpp.
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only).
 //
 // Per (block, filter), half by half (h = 0: even outputs, h = 1: odd):
 //   u_h = the half inverse transform of the forward (zs / zd multiply, 2048 points);
@@ -26,15 +26,6 @@
 #include "leaf_band_bwd.hpp"
 
 namespace {
-
-// identity filter -> column map for param_reduce_kernel (the 2048-sample tables get theirs from fft_prep_kernel)
-#ifndef LEAF_INST_TU               // non-template kernel: compiled once, in leaf_kernels.hip
-__global__ void iota_kernel(int* __restrict__ v, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) v[i] = i;
-}
-#endif
-
 
 // ---- dL/dx on 4096-sample blocks (DX = true; the static 32 kHz instance).  dL/dA'[k] = sum_f R_f[k] g_f[k] =: G[k], k < 4096,
 // Hermitian-folded as in leaf_fft_wg_bwd.hpp: S[e] = G[e] + conj(G[4096 - e]), e = 0..2048 (S[0] = G[0], S[2048] = conj(G[2048])).

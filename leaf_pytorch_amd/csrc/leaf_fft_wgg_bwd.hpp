@@ -1,6 +1,6 @@
 // leaf_fft_wgg_bwd.hpp -- the workgroup-per-block overlap-save BACKWARD (leaf_fft_wg_bwd.hpp) for ANY window the
 // 2048-sample plan covers: window, hop and block length at run time, odd and even windows.
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// Included by every unit: templates, device functions, constexpr sizes (gfx950 only).
 //
 // Same queue, ring, transforms and spectral tail as leaf_fft_wg_bwd_kernel; the pooling backward cannot unroll over
 // compile-time frame offsets, so it uses the layout of the run-time-geometry forward (leaf_fft_wgg.hpp): a wave-private LDS

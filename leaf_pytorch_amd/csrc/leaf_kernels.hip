@@ -2,6 +2,11 @@
 // C ABI declared in include/leaf_hip.h.  Written for gfx950 only: 64-lane wavefronts, fp32 MFMA
 // (v_mfma_f32_16x16x4_f32), 160 KiB LDS per CU.  No torch types anywhere in this file.
 //
+// One of the translation units of libleaf_hip.so: the C ABI, the host logic and every plain (non-template) kernel -- the headers
+// this unit alone includes (leaf_kernels_*.hpp, leaf_staged.hpp, leaf_stage_backward.hpp).  The big kernel templates are
+// instantiated in the inst_*.hip units and reached through the typed getters of leaf_inst.hpp; what a launch passes is defined
+// once, in leaf_params.hpp.  Every other header is safe in any unit: templates, device functions, constexpr sizes.
+//
 // Reference arithmetic being replaced (file:line under the reference repository):
 //   leaf_pytorch/frontend.py:78-89        Leaf.forward
 //   leaf_pytorch/convolution.py:15-22     GaborConstraint            -> constrain() below
@@ -51,12 +56,14 @@
 #include "leaf_fft_wgg_bwd.hpp"
 #include "leaf_fft_wgg4k.hpp"
 #include "leaf_fft_wgg4k_bwd.hpp"
-#include "leaf_inst.hpp"
+#include "leaf_inst.hpp"            // the big kernel templates are instantiated in the inst_*.hip units: typed handles
+// the plain kernels, compiled in this unit alone
+#include "leaf_kernels_tables.hpp"
+#include "leaf_kernels_rows.hpp"
+#include "leaf_kernels_misc.hpp"
+#include "leaf_kernels_backward.hpp"
 namespace {
 
-// The big kernel templates are instantiated in the inst_*.hip translation units (leaf_inst.hpp); here they are opaque handles.
-using FftKernel = void (*)(const FftParams);
-inline FftKernel as_fft_kernel(const void* h) { return reinterpret_cast<FftKernel>(const_cast<void*>(h)); }
 // Tools-only environment switches (A/B measurements of tools/*.py): compiled in only with -DLEAF_TOOLS=1
 // (LEAF_HIPCC_EXTRA="-DLEAF_TOOLS=1"); the product library reads no environment variable except LEAF_NO_4K.
 inline const char* tools_env(const char* name) { return LEAF_TOOLS ? getenv(name) : nullptr; }
@@ -199,10 +206,9 @@ FusedPlan make_plan(const Shape& s, int cus) {
 }
 
 hipError_t launch_fused(const FusedParams& prm, int rt, int noff_t, int groups, size_t lds, int grid_x, hipStream_t st) {
-    const void* h = leaf_inst_fused(rt, noff_t, (prm.K % 2) == 0, prm.dY != nullptr);
-    if (!h) return hipErrorInvalidValue;
-    auto kfn = reinterpret_cast<void (*)(const FusedParams)>(const_cast<void*>(h));
-    (void)hipFuncSetAttribute(h, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const FusedKernel kfn = leaf_inst_fused(rt, noff_t, (prm.K % 2) == 0, prm.dY != nullptr);
+    if (!kfn) return hipErrorInvalidValue;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kfn, dim3(grid_x, groups), dim3(kWavesPerWG * 64), lds, st, prm);
     return hipGetLastError();
 }
@@ -235,10 +241,9 @@ BwdPlan make_bwd_plan(const FusedPlan& pl, int T) {
 }
 
 hipError_t launch_dtaps(const DtapsParams& prm, int rt, int tpw, int groups, size_t lds, int grid_x, hipStream_t st) {
-    const void* h = leaf_inst_dtaps(rt, tpw, (prm.K % 2) == 0);
-    if (!h) return hipErrorInvalidValue;
-    auto kfn = reinterpret_cast<void (*)(const DtapsParams)>(const_cast<void*>(h));
-    (void)hipFuncSetAttribute(h, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const DtapsKernel kfn = leaf_inst_dtaps(rt, tpw, (prm.K % 2) == 0);
+    if (!kfn) return hipErrorInvalidValue;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kfn, dim3(grid_x, groups), dim3(prm.NW * 64), lds, st, prm);
     return hipGetLastError();
 }
@@ -414,7 +419,7 @@ inline bool fft4k_disabled() {
     static const bool off = [] { const char* e = getenv("LEAF_NO_4K"); return e && atoi(e) != 0; }();
     return off;
 }
-FftKernel pick_fft_wgg4k_kernel(int K) { return as_fft_kernel(leaf_inst_fft_wgg4k(fft_wgg4k_taps_per_lane(K))); }
+FftKernel pick_fft_wgg4k_kernel(int K) { return leaf_inst_fft_wgg4k(fft_wgg4k_taps_per_lane(K)); }
 Fft4kPlan make_fft4k_plan(const Shape& s) {
     const auto [B, T, F, K, hop] = s;
     Fft4kPlan fp{};
@@ -490,10 +495,10 @@ FftWgLaunch pick_fft_wg_kernel(int K, int hop, int xk, bool long_rows) {
     else if (K == 201 && hop == 80) nw = w16 ? 16 : 12;
     else return {nullptr, 0, 0};
     const int tailc = long_rows ? 64 : 128;
-    const void* fn = xk == kWgXMix ? leaf_inst_fft_wg_mix(K, nw, tailc) : xk == kWgXMix16 ? leaf_inst_fft_wg_mix16(K, nw, tailc)
-                     : xk == kWgX16 ? leaf_inst_fft_wg_x16(K, nw, tailc) : leaf_inst_fft_wg(K, nw, tailc);
-    const void* fn_stream = leaf_inst_fft_wg_streamfin(K, nw);            // (the loader chosen at run time: one load site)
-    return {as_fft_kernel(fn), nw, fft_wg_lds_bytes(nw, K), true, as_fft_kernel(fn_stream), K, hop, true};
+    const FftKernel fn = xk == kWgXMix ? leaf_inst_fft_wg_mix(K, nw, tailc) : xk == kWgXMix16 ? leaf_inst_fft_wg_mix16(K, nw, tailc)
+                         : xk == kWgX16 ? leaf_inst_fft_wg_x16(K, nw, tailc) : leaf_inst_fft_wg(K, nw, tailc);
+    const FftKernel fn_stream = leaf_inst_fft_wg_streamfin(K, nw);        // (the loader chosen at run time: one load site)
+    return {fn, nw, fft_wg_lds_bytes(nw, K), true, fn_stream, K, hop, true};
 }
 // is there a static instance for the geometry (every sample kind and tail has one where one has)?  Not for launching.
 inline bool fft_wg_static_exists(int K, int hop) { return pick_fft_wg_kernel(K, hop, kWgXF32, false).fn != nullptr; }
@@ -512,13 +517,13 @@ FftWgLaunch pick_fft_wgg_kernel(const FftPlan& fp, int K, int hop) {
         int nwf = 12;
         while (nwf > full_min && fft_wgg_lds_bytes_full(nwf, K) > (size_t)kMaxLds) --nwf;
         if (fft_wgg_lds_bytes_full(nwf, K) <= (size_t)kMaxLds)
-            return {as_fft_kernel(leaf_inst_fft_wgg(ni, false)), nwf, fft_wgg_lds_bytes_full(nwf, K), true};
+            return {leaf_inst_fft_wgg(ni, false), nwf, fft_wgg_lds_bytes_full(nwf, K), true};
     }
     int nw = 12;
     while (nw > 6 && fft_wgg_lds_bytes(nw, K) > (size_t)kMaxLds) --nw;
     const size_t lds = fft_wgg_lds_bytes(nw, K);
     if (lds > (size_t)kMaxLds) return {nullptr, 0, 0};
-    return {as_fft_kernel(leaf_inst_fft_wgg(ni, true)), nw, lds, true};
+    return {leaf_inst_fft_wgg(ni, true), nw, lds, true};
 }
 static_assert(fft_wg_lds_bytes(12, 401) <= (size_t)kMaxLds && fft_wg_lds_bytes(10, 801) <= (size_t)kMaxLds &&
               fft_wg_lds_bytes(16, 401) <= (size_t)kMaxLds && fft_wg_lds_bytes(14, 801) <= (size_t)kMaxLds, "LDS budget");
@@ -546,14 +551,14 @@ bool fft_wg_auto(const FftPlan& fp, int B, int K, int hop, int cus) {
 FftKernel pick_fft_kernel(const FftPlan& fp, int K, int hop, bool bwd) {
     const bool stat = fft_static_geometry(K, hop) && fp.g_bufs == 2;
     // odd and even windows alike: real-spectrum kernels (even K: Hermitian K - 1 taps + the unpaired tap in the time domain)
-    if (stat && (K & 1)) return as_fft_kernel(leaf_inst_fft(K, 1, 1, bwd ? 1 : 0));
-    return as_fft_kernel(leaf_inst_fft(0, fp.g_bufs == 2 ? 1 : 0, (K & 1) ? 1 : 2, bwd ? 1 : 0));
+    if (stat && (K & 1)) return (leaf_inst_fft(K, 1, 1, bwd ? 1 : 0));
+    return (leaf_inst_fft(0, fp.g_bufs == 2 ? 1 : 0, (K & 1) ? 1 : 2, bwd ? 1 : 0));
 }
 
 // the MIX instances (waveform mixup in the block load): the static odd windows only; nullptr elsewhere
 FftKernel pick_fft_kernel_mix(const FftPlan& fp, int K, int hop, bool bwd) {
     const bool stat = fp.ok && fft_static_geometry(K, hop) && fp.g_bufs == 2;
-    return stat && (K & 1) ? as_fft_kernel(leaf_inst_fft_mix(K, bwd ? 1 : 0)) : nullptr;
+    return stat && (K & 1) ? (leaf_inst_fft_mix(K, bwd ? 1 : 0)) : nullptr;
 }
 
 // Even K (real-spectrum form): the unpaired taps live behind the real spectra, in the second half of the float2 slab that
@@ -667,26 +672,17 @@ inline int x_sample_type(int flags) {
     return (flags & LEAF_FLAG_IO_BF16) ? kSampleBf16 : (flags & LEAF_FLAG_X_PCM16) ? kSamplePcm16 : kSampleF32;
 }
 
-// Every inst_*.hip was compiled with the parameter-struct layouts this unit has (the handles are opaque, a per-unit
-// macro divergence would otherwise be a silent parameter mismatch at launch).  Checked once; a mismatch fails every entry
-// point with LEAF_ERR_LAUNCH.
+// Every inst_*.hip was compiled with the launch structs' layout this unit has (leaf_params.hpp: the types are shared, the object
+// files of an incremental build are not).  Checked once; a mismatch fails every entry point with LEAF_ERR_LAUNCH.
 bool inst_layouts_ok() {
-    static const bool ok =
-        leaf_layout_fft() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_small() == leaf_layout_hash_small() &&
-        leaf_layout_fft_stream() == leaf_layout_hash_stream() &&
-        leaf_layout_fft_wg() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_wg_streamfin() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_wg_x16() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_wg_mix() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_wg_mix16() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_wg_bwd() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_wg_bwd_dx() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_wgg() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_wgg4k_bwd() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_wgg_bwd() == leaf_layout_hash_fft() &&
-        leaf_layout_fft_wgg_bwd_dx() == leaf_layout_hash_fft() &&
-        leaf_layout_fused() == leaf_layout_hash_bwd();
+    static const bool ok = [] {
+        for (unsigned (*unit)() : {leaf_layout_fft, leaf_layout_fft_small, leaf_layout_fft_stream, leaf_layout_fft_wg, leaf_layout_fft_wg_streamfin,
+                                   leaf_layout_fft_wg_x16, leaf_layout_fft_wg_mix, leaf_layout_fft_wg_mix16, leaf_layout_fft_wg_bwd,
+                                   leaf_layout_fft_wg_bwd_dx, leaf_layout_fft_wgg, leaf_layout_fft_wgg4k_bwd, leaf_layout_fft_wgg_bwd,
+                                   leaf_layout_fft_wgg_bwd_dx, leaf_layout_fused})
+            if (unit() != leaf_params_layout()) return false;
+        return true;
+    }();
     return ok;
 }
 
@@ -1301,8 +1297,7 @@ static int forward_small(const CallCtx& ctx, const LeafArgs& a, const FwdIo& io,
     const auto [B, T, F, K, hop] = a.s;
     const SmallPlan sp = make_small_plan(a.s, ctx.cus);
     if (!sp.ok) return LEAF_ERR_BAD_ALGO;
-    using SmallKernel = void (*)(const SmallParams);
-    const SmallKernel kfn = reinterpret_cast<SmallKernel>(const_cast<void*>(ctx.mix.lam ? leaf_inst_fft_small_mix(K, sp.split) : leaf_inst_fft_small(K, sp.split)));
+    const SmallKernel kfn = ctx.mix.lam ? leaf_inst_fft_small_mix(K, sp.split) : leaf_inst_fft_small(K, sp.split);
     if (!kfn) return LEAF_ERR_BAD_ALGO;
     SmallParams q{};
     q.x = io.x; q.io_bf16 = io.xtype; q.kernel = a.kernel; q.pool_w = a.pool_w; q.bd = gabor_bounds(K);
@@ -1377,8 +1372,7 @@ struct StreamIo {
 // (stream, filter) whatever the CU count.)
 static int stream_step(const CallCtx&, const LeafArgs& a, const StreamIo& io) {
     const auto [B, T, F, K, hop] = a.s;                       // T: the virtual buffer [history | chunk]
-    using StreamKernel = void (*)(const StreamParams);
-    const StreamKernel kfn = reinterpret_cast<StreamKernel>(const_cast<void*>(leaf_inst_fft_stream(K)));
+    const StreamKernel kfn = leaf_inst_fft_stream(K);
     if (!kfn) return LEAF_ERR_UNSUPPORTED;
     const StreamLayout L = stream_layout(B, F, K, hop, io.pcm == kSamplePcm16);
     const int LS = fft_block_len(K, hop, true), padL = K / 2 + K % 2 - 1;
@@ -1499,8 +1493,7 @@ int leaf_stream_bank_step_f32(const void* chunk, long long chunk_stride, int B, 
     }
     if (state_bytes < L.total) return LEAF_ERR_WORKSPACE;
     if (!work) return LEAF_OK;                                            // no slot emits anything or keeps anything
-    using BankKernel = void (*)(const StreamBankParams);
-    const BankKernel kfn = reinterpret_cast<BankKernel>(const_cast<void*>(leaf_inst_fft_stream_bank(K)));
+    const StreamBankKernel kfn = leaf_inst_fft_stream_bank(K);
     if (!kfn) return LEAF_ERR_UNSUPPORTED;
     const int mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (out_bf16 ? 4 : 0);
     char* base = static_cast<char*>(state);
@@ -1585,7 +1578,7 @@ static int forward_4k(const CallCtx& ctx, const Fft4kPlan& f4, const LeafArgs& a
         q.fin = fin;
         q.fin_fused = 1;
     }
-    const int rc = launch_lds(f4.generic ? pick_fft_wgg4k_kernel(K) : as_fft_kernel(leaf_inst_fft_wg4k()), dim3(grid), f4.nw, f4.lds + band_lds, a.st, q);
+    const int rc = launch_lds(f4.generic ? pick_fft_wgg4k_kernel(K) : leaf_inst_fft_wg4k(), dim3(grid), f4.nw, f4.lds + band_lds, a.st, q);
     if (rc != LEAF_OK) return rc;
     record(io.ev, 2, a.st);
     if (fin_fused_off() || !all_clips_owned(own)) launch_fft_finalize(fin, B, own, ctx.cus, a.st);
@@ -2048,11 +2041,11 @@ FftWgBwdLaunch pick_fft_wg_bwd_kernel(int K, int hop, bool dx, int cus, bool ban
         // (not K = 801: there the block-per-wave kernel measures 5 % faster, 1.89 vs 1.99 ms at 256 x 1 s)
         if (wg_block_dx_enabled() && K != 801 && blocks >= fft_wg_bwd_min_blocks(cus, wg_bwd_sixteenths(K, hop, true, band_possible)) &&
             fft_wg_bwd_dx_lds_bytes(12, K) <= (size_t)kMaxLds)
-            return {as_fft_kernel(leaf_inst_fft_wg_bwd_dx(K)), 12, fft_wg_bwd_dx_lds_bytes(12, K), true};
+            return {leaf_inst_fft_wg_bwd_dx(K), 12, fft_wg_bwd_dx_lds_bytes(12, K), true};
         // below that: one wave per block, G in registers (leaf_fft_blk_bwd_dx_kernel)
-        return {as_fft_kernel(io_bf16 ? leaf_inst_fft_blk_bwd_dx_bf16(K) : leaf_inst_fft_blk_bwd_dx(K)), kBlkBwdWaves, fft_blk_bwd_lds_bytes(K)};
+        return {(io_bf16 ? leaf_inst_fft_blk_bwd_dx_bf16(K) : leaf_inst_fft_blk_bwd_dx(K)), kBlkBwdWaves, fft_blk_bwd_lds_bytes(K)};
     }
-    if (fft_static_geometry(K, hop) && (K & 1)) return {as_fft_kernel(leaf_inst_fft_wg_bwd(K)), 12, fft_wg_bwd_lds_bytes(12, K)};
+    if (fft_static_geometry(K, hop) && (K & 1)) return {leaf_inst_fft_wg_bwd(K), 12, fft_wg_bwd_lds_bytes(12, K)};
     return {nullptr, 0, 0};
 }
 // any other window of the 2048-sample plan, odd or even: the run-time-geometry kernel (leaf_fft_wgg_bwd.hpp); parameter
@@ -2066,13 +2059,13 @@ FftWgBwdLaunch pick_fft_wgg_bwd_kernel(const FftPlan& fp, int K, int hop) {
         int nwf = 12;
         while (nwf > full_min && fft_wgg_lds_bytes_full(nwf, K) > (size_t)kMaxLds) --nwf;
         if (fft_wgg_lds_bytes_full(nwf, K) <= (size_t)kMaxLds)
-            return {as_fft_kernel(leaf_inst_fft_wgg_bwd(ni, false)), nwf, fft_wgg_lds_bytes_full(nwf, K)};
+            return {leaf_inst_fft_wgg_bwd(ni, false), nwf, fft_wgg_lds_bytes_full(nwf, K)};
     }
     int nw = 12;                                                          // the forward's row layout with the half-size scratch
     while (nw > 6 && fft_wgg_lds_bytes(nw, K) > (size_t)kMaxLds) --nw;
     if (fft_wgg_lds_bytes(nw, K) > (size_t)kMaxLds) return {nullptr, 0, 0};
     const FftWgLaunch fwd{nullptr, nw, fft_wgg_lds_bytes(nw, K)};
-    return {as_fft_kernel(leaf_inst_fft_wgg_bwd(ni, true)), fwd.nw, fwd.lds};
+    return {leaf_inst_fft_wgg_bwd(ni, true), fwd.nw, fwd.lds};
 }
 static_assert(fft_wg_bwd_lds_bytes(12, 801) <= (size_t)kMaxLds && fft_blk_bwd_lds_bytes(801) <= (size_t)kMaxLds, "LDS budget");
 // used for dL/dx always (nothing else fused yields it), and for the parameter gradients once every CU gets a block
@@ -2091,7 +2084,7 @@ FftWgBwdLaunch pick_fft_wgg_bwd_dx_kernel(const FftPlan& fp, int K, int hop, int
     while (nw > 6 && fft_wgg_bwd_dx_lds_bytes(nw, K) > (size_t)kMaxLds) --nw;
     const size_t lds = fft_wgg_bwd_dx_lds_bytes(nw, K);
     if (lds > (size_t)kMaxLds) return {nullptr, 0, 0};
-    return {as_fft_kernel(leaf_inst_fft_wgg_bwd_dx(fft_wgg_taps_per_lane(K))), nw, lds};
+    return {leaf_inst_fft_wgg_bwd_dx(fft_wgg_taps_per_lane(K)), nw, lds};
 }
 // the run-time-geometry kernel: parameter gradients, once every CU gets a block
 bool fft_wgg_bwd_use(const FftPlan& fp, int B, int K, int hop, bool need_dx, int cus) {
@@ -2140,7 +2133,7 @@ struct Fft4kBwdPlan {
     int L, nblk, TP, padL, RG, nw;
     size_t lds;
 };
-FftKernel pick_fft_wgg4k_bwd_kernel(int K) { return as_fft_kernel(leaf_inst_fft_wgg4k_bwd(fft_wgg4k_taps_per_lane(K))); }
+FftKernel pick_fft_wgg4k_bwd_kernel(int K) { return leaf_inst_fft_wgg4k_bwd(fft_wgg4k_taps_per_lane(K)); }
 Fft4kBwdPlan make_fft4k_bwd_plan(const Shape& s, bool need_dx, int cus) {
     const auto [B, T, F, K, hop] = s;
     Fft4kBwdPlan bp{};
@@ -2360,7 +2353,7 @@ static int backward_4k(const CallCtx& ctx, const LeafArgs& a, const BwdIo& io, f
         const size_t flds = bp.stat ? fft_wg4k_lds_bytes(LEAF_4K_FWD_NW) : fft_wgg4k_lds_bytes(fnw, K, fbn);
         if (flds > (size_t)kMaxLds) return LEAF_ERR_BAD_ALGO;
         q.NT = fbn;
-        rc = launch_lds(bp.stat ? as_fft_kernel(leaf_inst_fft_wg4k()) : pick_fft_wgg4k_kernel(K), grid, fnw, flds, a.st, q);
+        rc = launch_lds(bp.stat ? leaf_inst_fft_wg4k() : pick_fft_wgg4k_kernel(K), grid, fnw, flds, a.st, q);
         if (rc != LEAF_OK) return rc;
         q.NT = 0;
         finalize_pooled_raw(a, part, SlotGeom{bp.L, bp.padL, K, hop, T, 2}, raw, ctx.cus);
@@ -2373,9 +2366,9 @@ static int backward_4k(const CallCtx& ctx, const LeafArgs& a, const BwdIo& io, f
     // 3. per-(block, filter) partial gradients
     q.gpre = gpre; q.pool_w = a.pool_w; q.dkpart = ws + L.dkpart; q.dwpart = ws + L.dwpart; q.part = nullptr;
     const bool mixed = ctx.mix.lam != nullptr;
-    FftKernel kb = bp.dx ? as_fft_kernel(leaf_inst_fft_wg4k_bwd_dx())
-                         : bp.stat ? as_fft_kernel(mixed ? leaf_inst_fft_wg4k_bwd_mix() : leaf_inst_fft_wg4k_bwd())
-                                   : mixed ? as_fft_kernel(leaf_inst_fft_wgg4k_bwd_mix(fft_wgg4k_taps_per_lane(K))) : pick_fft_wgg4k_bwd_kernel(K);
+    FftKernel kb = bp.dx ? leaf_inst_fft_wg4k_bwd_dx()
+                         : bp.stat ? (mixed ? leaf_inst_fft_wg4k_bwd_mix() : leaf_inst_fft_wg4k_bwd())
+                                   : mixed ? leaf_inst_fft_wgg4k_bwd_mix(fft_wgg4k_taps_per_lane(K)) : pick_fft_wgg4k_bwd_kernel(K);
     if (!kb) return LEAF_ERR_BAD_ALGO;
     if (bp.dx) q.part = ws + L.dxblk;                                 // [block][4096] input gradients, un-rotated
     size_t blds = bp.lds;
@@ -2455,7 +2448,7 @@ static int backward_fft(const CallCtx& ctx, const LeafArgs& a, const BwdIo& io, 
         // workgroup-per-block backward; with g_x the per-block input gradients go to dxblk and are gathered below
         FftWgBwdLaunch wl = pick_fft_wg_bwd_kernel(K, hop, need_dx, ctx.cus, band_possible, (long long)B * fp.nblk, io.xtype == kSampleBf16);
         q.part = need_dx ? ws + L.dxblk : nullptr;
-        if (mixed) wl.fn = as_fft_kernel(leaf_inst_fft_wg_bwd_mix(K));
+        if (mixed) wl.fn = leaf_inst_fft_wg_bwd_mix(K);
         if (!wl.fn) return LEAF_ERR_BAD_ALGO;
         if (band_bwd) {
             band.lds_off = (int)(wl.lds / 4);

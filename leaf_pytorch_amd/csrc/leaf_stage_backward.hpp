@@ -1,5 +1,5 @@
 // leaf_stage_backward.hpp -- backward kernels of the stand-alone stage entry points (one reference module each)
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// Included by leaf_kernels.hip only: kernels (gfx950 only).
 //
 // The reference's sub-modules are ordinary differentiable nn.Modules (convolution.py:71-99, frontend.py:15-19,
 // pooling.py:31-42, postprocessing.py:13-28,62-69).  Leaf.forward has its own fused backward (leaf_backward_f32); these

@@ -1,5 +1,5 @@
 // leaf_staged.hpp -- staged (one kernel per reference module) forward kernels
-// Part of the single translation unit leaf_kernels.hip (gfx950 only); see that file's header comment.
+// Included by leaf_kernels.hip only: kernels (gfx950 only).
 #pragma once
 #include "leaf_common.hpp"
 
@@ -102,7 +102,6 @@ __global__ __launch_bounds__(1024) void peak_normalize_kernel(const float* __res
 
 // LEAF_FLAG_PEAKNORM: the per-clip scale of the transform above without the copy -- scale2[b] = s_b^2, s_b = 1 / peak when
 // the clip's peak |x| exceeds 1, else 1 (what the overlap-save finalize multiplies the pooled energies by).  x fp32, bf16 or 16-bit PCM (io_bf16: the sample type).
-#ifndef LEAF_INST_TU
 __global__ __launch_bounds__(1024) void peak_scale2_kernel(const void* __restrict__ x_, int io_bf16, int T, float* __restrict__ scale2) {
     __shared__ float red[16];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -129,6 +128,5 @@ __global__ __launch_bounds__(1024) void peak_scale2_kernel(const void* __restric
         scale2[b] = s * s;
     }
 }
-#endif
 
 }  // namespace

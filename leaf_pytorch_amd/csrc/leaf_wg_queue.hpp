@@ -1,4 +1,5 @@
-// leaf_wg_queue.hpp -- what the seven workgroup-per-block kernels share: the task queue in LDS, its protocol and the spectrum-row load.  Included by leaf_fft_wg.hpp; part of the translation units that include that header (gfx950 only).
+// leaf_wg_queue.hpp -- what the seven workgroup-per-block kernels share: the task queue in LDS, its protocol and the spectrum-row load.
+// Included by every unit (through leaf_fft_wg.hpp): templates, device functions, constexpr sizes (gfx950 only).
 //
 // The kernels (forward: leaf_fft_wg, _wg4k, _wgg, _wgg4k; backward: leaf_fft_wg_bwd, _wgg_bwd, _wgg4k_bwd) give a workgroup a list of
 // blocks ("sets"), keep the spectra of two of them in a ring in LDS and hand (block, filter) tasks to their waves through one queue,

@@ -84,6 +84,30 @@ def test_the_16_khz_instances_are_no_larger_than_before_and_keep_their_registers
         assert r["scratch"] <= (STREAM_SCRATCH if stream else 0), (name, r)
 
 
+@pytest.mark.skipif(not os.path.exists(READELF), reason="needs llvm-readelf of the ROCm toolchain (no GPU)")
+def test_every_kernel_is_compiled_in_exactly_one_translation_unit():
+    """A csrc header is either safe in every unit (templates, device functions, sizes) or leaf_kernels.hip's alone (the plain
+    kernels: leaf_kernels_*.hpp, leaf_staged.hpp, leaf_stage_backward.hpp).  What that buys, counted in the BUILT library: over all
+    gfx950 code objects (one per translation unit), every kernel -- a FUNC symbol with a `.kd` kernel descriptor beside it -- occurs
+    in exactly one."""
+    _native.load()
+    seen = {}
+    blobs = list(device_code_objects(_native.LIB_PATH))
+    for unit, blob in enumerate(blobs):
+        with tempfile.NamedTemporaryFile(suffix=".elf") as fh:
+            fh.write(blob)
+            fh.flush()
+            syms = subprocess.run([READELF, "-sW", fh.name], capture_output=True, text=True, check=True).stdout
+        rows = [line.split() for line in syms.splitlines()]
+        rows = [c for c in rows if len(c) >= 8]
+        descriptors = {c[7][:-3] for c in rows if c[3] == "OBJECT" and c[7].endswith(".kd")}
+        for name in {c[7] for c in rows if c[3] == "FUNC"} & descriptors:
+            seen.setdefault(name, []).append(unit)
+    assert len(blobs) == len(_native._translation_units(os.path.dirname(_native.SRC_PATH))) and len(seen) > 100, (len(blobs), len(seen))
+    twice = {name: units for name, units in seen.items() if len(units) != 1}
+    assert not twice, f"kernels compiled in more than one translation unit: {twice}"
+
+
 def getters():
     """The instance getters of csrc/leaf_inst.hpp by their plain names (C++ linkage: looked up in the dynamic symbol table)."""
     out = subprocess.run(["nm", "-D", "--defined-only", _native.LIB_PATH], capture_output=True, text=True, check=True).stdout

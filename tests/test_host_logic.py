@@ -371,9 +371,9 @@ def test_notes_switch_table_is_current():
     assert r.stdout.strip() in notes, "NOTES.md: regenerate the switches table (python tools/list_switches.py --markdown)"
 
 
-# `#ifdef`-style handles of the HIP sources: defined only by a tool's -D or by an instantiation unit, so list_switches.py (which
-# reads `#ifndef X / #define X default`) does not report them
-SWITCH_HANDLES = {"LEAF_TOOLS", "LEAF_INST_TU", "LEAF_WG_NW", "LEAF_SMALL_STAMP", "LEAF_DX_NOWAIT", "LEAF_4K_DX_NOACC"}
+# `#ifdef`-style handles of the HIP sources: defined only by a tool's -D, so list_switches.py (which reads
+# `#ifndef X / #define X default`) does not report them
+SWITCH_HANDLES = {"LEAF_TOOLS", "LEAF_WG_NW", "LEAF_SMALL_STAMP", "LEAF_DX_NOWAIT", "LEAF_4K_DX_NOACC"}
 
 
 def leaf_identifiers_outside_the_switch_list(handles=SWITCH_HANDLES):
@@ -418,10 +418,10 @@ def leaf_identifiers_outside_the_switch_list(handles=SWITCH_HANDLES):
 def test_every_leaf_identifier_is_a_listed_switch():
     """A retired switch left behind in a condition (`#if LEAF_WG_PK`) would select the `#else` side silently: every LEAF_* name
     that csrc/ tests or uses as a constant is one tools/list_switches.py reports, or a handle of SWITCH_HANDLES.  The scan sees
-    what it should: without its allowance for LEAF_INST_TU it reports that handle."""
+    what it should: without its allowance for LEAF_SMALL_STAMP it reports that handle."""
     assert leaf_identifiers_outside_the_switch_list() == []
-    missed = leaf_identifiers_outside_the_switch_list(SWITCH_HANDLES - {"LEAF_INST_TU"})
-    assert missed and {n for _, n in missed} == {"LEAF_INST_TU"}
+    missed = leaf_identifiers_outside_the_switch_list(SWITCH_HANDLES - {"LEAF_SMALL_STAMP"})
+    assert missed and {n for _, n in missed} == {"LEAF_SMALL_STAMP"}
 
 
 def test_gradient_metric_rejects_a_wrong_sigma_derivative():

@@ -8,7 +8,6 @@
 // Priority schemes by the wave's slot on its SIMD (slot = wave / 4: waves w, w + 4, w + 8 share SIMD w):
 //     equal      0 0 0          ladder   2 1 0         two-high   1 1 0        one-high   1 0 0
 //   hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -I leaf_pytorch_amd/csrc -I include tools/ubench_prio.hip -o /tmp/ubench_prio && /tmp/ubench_prio
-#define LEAF_INST_TU 1
 #include "leaf_fft.hpp"
 #include <hip/hip_runtime.h>
 #include <cstdio>

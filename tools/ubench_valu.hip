@@ -12,8 +12,7 @@
 //       Printed as tasks/s for the chip, as executed TFLOP/s (the same flop count per task bench.py uses) and as a fraction
 //       of the 157.3 TF issue peak; the last line is JSON for profiles/valu_roof.json.
 //   hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -I leaf_pytorch_amd/csrc -I include tools/ubench_valu.hip -o /tmp/ubench_valu && /tmp/ubench_valu
-#define LEAF_INST_TU 1             // templates and device functions only: none of the library's kernels is compiled here
-#include "leaf_fft.hpp"
+#include "leaf_fft.hpp"            // templates and device functions only: a header every unit may include holds no kernel
 #include <hip/hip_runtime.h>
 #include <cstdio>
 typedef float f32x2 __attribute__((ext_vector_type(2)));
