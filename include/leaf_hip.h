@@ -367,6 +367,35 @@ int leaf_backward_f32(const float* x, int B, int T,
                       float* g_x, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Head-only backward (additive: the ABI version stays 6): the gradients of pool_b and of the four PCEN vectors alone, for a
+ * frontend whose Gabor kernel and pooling width are frozen and whose input needs no gradient.  They depend on nothing but
+ *   pooled_raw [B][F][T'] float32  the pre-floor pooled tensor, bias included, exactly what leaf_forward_save_f32 writes, and
+ *   grad_out   [B][F][T']          float32, or bfloat16 behind the float pointer with LEAF_FLAG_OUT_BF16 / LEAF_FLAG_IO_BF16
+ *                                  (here both mean "grad_out is bfloat16"; widened where it is read, 2-byte aligned),
+ * so the call takes no waveform, builds no tables and runs no transform.  alpha, delta, root, ema_w [F] and g_alpha .. g_ema_w [F]
+ * are required with LEAF_FLAG_PCEN and ignored (may be NULL) without it; then g_pool_b [F] is the sum of grad_out over the entries
+ * above the 1e-5 floor, each divided by 1 + pooled_raw with LEAF_FLAG_LOG1P (ignored with LEAF_FLAG_PCEN, as everywhere).  The
+ * values agree with those leaf_backward_f32 gives for the same five gradients to float32 rounding (the rows' arithmetic is the same
+ * code; the sum over the batch is taken in another fixed order), with the same clamp sub-gradients.
+ * One hipMemsetAsync (the ticket words at the workspace's start) and ONE kernel launch per call, both on `stream`: the sum over the
+ * batch happens inside the launch, in a fixed order and without floating-point atomics, so the result is bit-identical from call
+ * to call.  Nothing is allocated and nothing synchronises: the call can be captured into a HIP graph (while `stream` is being
+ * captured the tickets are zeroed by a one-workgroup kernel node in place of the memset node, whose replays were seen to write
+ * other bytes than zeros: two kernel nodes, replayed with the eager call's bits).  Nothing is assumed about the workspace's
+ * contents; its size depends on B, T', F, the flags and the device's CU count.
+ * Status, in this order and before anything is launched: a flag other than the four above: LEAF_ERR_UNSUPPORTED; B == 0 (the
+ * empty batch): the outputs are zero-filled with memsets, nothing else runs (the inputs and the workspace may be NULL);
+ * LEAF_ERR_NULL_POINTER; B < 0, T' < 1, F < 1 or B * F * T' >= 2^31 (slice the batch and add): LEAF_ERR_BAD_SHAPE; buffers below
+ * 4-byte (bfloat16 grad_out: 2-byte; workspace: 16-byte) alignment: LEAF_ERR_ALIGNMENT; a workspace that is NULL or below the
+ * size query for the same B, T', F and flags: LEAF_ERR_WORKSPACE.  The size query answers 0 for arguments the call refuses.
+ */
+size_t leaf_backward_head_workspace_bytes(int B, int TP, int F, int flags);
+int leaf_backward_head_f32(const float* pooled_raw, const float* grad_out, int B, int TP, int F,
+                           const float* alpha, const float* delta, const float* root, const float* ema_w,
+                           int flags, float* g_pool_b, float* g_alpha, float* g_delta, float* g_root,
+                           float* g_ema_w, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Waveform mixup in front of the frontend (the reference's training loop, utilities/data/mixup.py:17-24 with train.py:237-243),
  * additive to ABI 6.  Per clip b, with the partner clip p = mix_perm[b] and the weight lam = mix_lam[b], a mixed sample is
  *     om = 1 - lam;   x'[b][n] = (x[b][n] * lam) + (x[p][n] * om)

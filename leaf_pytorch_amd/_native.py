@@ -38,6 +38,8 @@ ALGO_FULL_TRANSFORMS = 1 << 26   # LEAF_ALGO_FULL_TRANSFORMS: no band-limited fi
 ALGO_STRICT_BAND_CLASSES = 1 << 27   # LEAF_ALGO_STRICT_BAND_CLASSES: the band classes' energy bound does not follow the pooling bias (round 5's decision)
 ALGO_NO_TABLE_CACHE = 1 << 28   # LEAF_ALGO_NO_TABLE_CACHE: the forward rebuilds its tables on every call (no self-validating table cache)
 OPT_PEAKNORM = 1 << 24          # torch.ops.leaf_amd.forward: option bit in `algo` that sets LEAF_FLAG_PEAKNORM (torch_binding.cpp)
+OPT_FULL_BACKWARD = 1 << 29     # torch.ops.leaf_amd.forward_train / _LeafFn: option bit in `algo` -- the autograd formula takes the full backward
+                                # (leaf_amd::backward) also where the head-only one would do (Leaf.full_backward(); never reaches the C ABI)
 STAGE_GABOR_CONV, STAGE_LOWPASS, STAGE_EMA, STAGE_PCEN = 1, 2, 3, 4
 
 _lock = threading.Lock()
@@ -67,6 +69,10 @@ _SIGNATURES = {
                           + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "leaf_forward_save_f32": (ctypes.c_int, [_f32p, ctypes.c_int, ctypes.c_int] + [_f32p] * 7 + [ctypes.c_int] * 5
                               + [_f32p, _f32p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # head-only backward: pooled_raw, grad_out, B, TP, F, the PCEN four, flags, g_pool_b and the four PCEN gradients, workspace, stream
+    "leaf_backward_head_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 4),
+    "leaf_backward_head_f32": (ctypes.c_int, [_f32p] * 2 + [ctypes.c_int] * 3 + [_f32p] * 4 + [ctypes.c_int] + [_f32p] * 5
+                               + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "leaf_gabor_taps_f32": (ctypes.c_int, [_f32p, ctypes.c_int, ctypes.c_int, _f32p, ctypes.c_void_p]),
     "leaf_lowpass_window_f32": (ctypes.c_int, [_f32p, ctypes.c_int, ctypes.c_int, _f32p, ctypes.c_void_p]),
     "leaf_gabor_conv_f32": (ctypes.c_int, [_f32p, ctypes.c_int, ctypes.c_int, _f32p, ctypes.c_int, ctypes.c_int,
@@ -553,6 +559,63 @@ def leaf_backward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: int, 
     bit for bit; ``x`` stays float32 (dL/dx float32) or int16."""
     return _backward("leaf_backward", x, None, (kernel, pool_w, pool_b, alpha, delta, root, ema_w), K, hop, grad_out,
                      backward_flags(pcen, staged, mfma, full_transforms, strict_band_classes, log1p), need_dx, pooled_raw, out_bf16)
+
+
+CALL_ELEMENTS = 1 << 31          # leaf_backward_head_f32 indexes pooled_raw with 32 bits: B * F * T' of a call stays below this
+
+
+def leaf_backward_head(pooled_raw: torch.Tensor, grad_out: torch.Tensor, pool_b: torch.Tensor, alpha, delta, root, ema_w,
+                       pcen: bool = True, log1p: bool = False, out_bf16: bool = False):
+    """The head-only backward (leaf_backward_head_f32): ``(g_pool_b, g_alpha, g_delta, g_root, g_ema_w)`` from the saved pre-floor
+    pooled tensor ``pooled_raw`` (B, F, T') and ``grad_out`` alone, one launch -- the gradients a ``Leaf`` with a frozen Gabor kernel and
+    pooling width needs; the PCEN four are None with ``pcen=False``.  ``pool_b`` is taken only for its shape and device.  ``log1p``:
+    the backward of the log1p-compressed forward (PCEN off; ignored with PCEN on).  ``out_bf16``: ``grad_out`` is bfloat16, widened
+    where the kernel reads it -- the gradients are those of the call on ``grad_out.float()`` bit for bit."""
+    # shapes and dtypes first, then the devices: every error is raised here, before the library is loaded
+    if pooled_raw.dim() != 3 or pooled_raw.shape[1] < 1 or pooled_raw.shape[2] < 1:
+        raise RuntimeError(f"pooled_raw must be (B, F, T') with F, T' >= 1, got {tuple(pooled_raw.shape)}")
+    B, F, TP = pooled_raw.shape
+    if pooled_raw.dtype != torch.float32:
+        raise RuntimeError(f"pooled_raw must be float32, got {pooled_raw.dtype}")
+    want = torch.bfloat16 if out_bf16 else torch.float32
+    if grad_out.dtype != want:
+        raise RuntimeError(f"grad_out must be {want} with out_bf16={bool(out_bf16)}, got {grad_out.dtype}")
+    if tuple(grad_out.shape) != (B, F, TP):
+        raise RuntimeError(f"grad_out has shape {tuple(grad_out.shape)}, expected {(B, F, TP)}")
+    if pool_b.numel() != F:
+        raise RuntimeError(f"pool_b must hold one bias per filter ({F}), got {tuple(pool_b.shape)}")
+    names = ("alpha", "delta", "root", "ema_w")
+    pc = (alpha, delta, root, ema_w) if pcen else ()
+    for t, name in zip(pc, names):
+        if t is None or t.numel() != F:
+            raise RuntimeError(f"{name} must hold one entry per filter ({F}) with pcen=True")
+    require_hip(pooled_raw, "leaf_backward_head")
+    dev = pooled_raw.device
+    raw = _dev_f32(pooled_raw, "pooled_raw", dev)
+    if grad_out.device != dev or pool_b.device != dev:
+        raise RuntimeError(f"grad_out and pool_b must be on {dev}, got {grad_out.device} and {pool_b.device}")
+    go = grad_out.detach().contiguous()
+    pc = [_dev_f32(t, name, dev) for t, name in zip(pc, names)] if pcen else [None] * 4
+    flags = (FLAG_PCEN if pcen else (FLAG_LOG1P if log1p else 0)) | (FLAG_OUT_BF16 if out_bf16 else 0)
+    grads = [torch.empty(pool_b.shape, dtype=torch.float32, device=dev)] + [torch.empty(F, dtype=torch.float32, device=dev) if pcen else None
+                                                                            for _ in range(4)]
+    if B == 0:                                     # the sum over no clips: zero gradients, nothing launched
+        for g in grads:
+            if g is not None:
+                g.zero_()
+    elif B * F * TP >= CALL_ELEMENTS:
+        # slices over B, the gradients added in slice order (fixed: bit-reproducible), like _backward
+        if F * TP >= CALL_ELEMENTS:
+            raise RuntimeError(f"a clip of {F} x {TP} pooled values is beyond the C ABI's 32-bit index")
+        total = None
+        for b0, b1 in batch_slices(B, F * TP):
+            g = leaf_backward_head(raw[b0:b1], go[b0:b1], pool_b, *pc, pcen=pcen, log1p=log1p, out_bf16=out_bf16)
+            total = list(g) if total is None else [None if a is None else a.add_(b) for a, b in zip(total, g)]
+        return tuple(total)
+    else:
+        _call(dev, "leaf_backward_head_f32", raw, go, B, TP, F, *[_ptr(t) for t in pc], flags, *[_ptr(g) for g in grads],
+              ws=lambda lib: lib.leaf_backward_head_workspace_bytes(B, TP, F, flags))
+    return tuple(grads)
 
 
 def mix_args(perm, lam, B: int, device: torch.device):

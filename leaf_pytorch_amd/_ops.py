@@ -1,6 +1,7 @@
-"""Dispatcher ops ``torch.ops.leaf_amd.{forward, forward_train, backward}`` (csrc/torch_binding.cpp: a thin torch
+"""Dispatcher ops ``torch.ops.leaf_amd.{forward, forward_train, backward, backward_head}`` (csrc/torch_binding.cpp: a thin torch
 extension over the C ABI of include/leaf_hip.h) plus what only Python can attach to them: the fake (meta) kernels
-``torch.compile`` / ``torch.export`` need to propagate shapes, and the autograd formula of the training forward.
+``torch.compile`` / ``torch.export`` need to propagate shapes, and the autograd formula of the training forward, which picks the
+full or the head-only backward by what needs a gradient (``backward_route``).
 
 ``Leaf.forward`` goes through these ops, so a model containing the frontend compiles without a graph break and an eager
 call costs one dispatcher hop.  There is no fallback: the ops exist only for HIP tensors and fail loudly otherwise.
@@ -76,6 +77,16 @@ def _out_dtype(x: torch.Tensor, out_bf16: bool = False) -> torch.dtype:
     return torch.bfloat16 if x.dtype == torch.bfloat16 or out_bf16 else torch.float32
 
 
+def backward_route(need_kernel: bool, need_pool_w: bool, need_x: bool, create_graph: bool) -> str:
+    """Which backward a training forward gets: ``"head"`` -- leaf_amd::backward_head, the gradients of the pooling bias and the PCEN
+    vectors from the saved pre-floor pooled tensor alone, one launch -- exactly when neither the Gabor kernel, nor the pooling width,
+    nor the waveform needs a gradient and no graph of the backward is asked for; ``"full"`` (leaf_amd::backward) otherwise.
+
+    The forward decides what it saves from the three needs (``create_graph`` is not known before the backward runs): on the head
+    route that is the pooled tensor and the PCEN vectors -- no waveform, no ``perm`` / ``lam``, no kernel, no pooling width."""
+    return "full" if (need_kernel or need_pool_w or need_x or create_graph) else "head"
+
+
 def _register_family(mixed: bool) -> None:
     """Fake kernels and the autograd formula of one family of three ops: forward / forward_train / backward, or (``mixed``) the
     same three with (perm, lam) behind x -- waveform mixup, parameter gradients only."""
@@ -116,9 +127,26 @@ def _register_family(mixed: bool) -> None:
         ctx.geom = (K, hop)
         ctx.full = bool(algo & _native.ALGO_FULL_TRANSFORMS)     # Leaf.full_transforms(): no band tasks in the backward either
         ctx.strict = bool(algo & _native.ALGO_STRICT_BAND_CLASSES)
+        need = ctx.needs_input_grad
+        ctx.route = "full" if algo & _native.OPT_FULL_BACKWARD else backward_route(need[lead], need[lead + 1], need[0] or (mixed and need[2]), False)
+        if ctx.route == "head":
+            # nothing of the waveform side reaches the backward: not x, not (perm, lam), not the filterbank
+            ctx.grad_bf16 = ctx.out_bf16 or inputs[0].dtype == torch.bfloat16     # (a bfloat16 waveform: bfloat16 features)
+            ctx.save_for_backward(pool_b, raw, *([alpha, delta, root, ema_w] if ctx.pcen else []))
+            return
         ctx.save_for_backward(*inputs[:lead], kernel, pool_w, pool_b, raw, *([alpha, delta, root, ema_w] if ctx.pcen else []))
 
+    def backward_head(ctx, grad_out):
+        pool_b, raw, *pc = ctx.saved_tensors
+        # Under create_graph=True (grad mode is on in here) the same op runs: its own autograd formula (_second_order.py) gives the
+        # gradients of these gradients from the pooled tensor, which is all they depend on with the filterbank and x constant.
+        gpb, *gpc = torch.ops.leaf_amd.backward_head(raw, grad_out.contiguous(), pool_b, *(pc or (None,) * 4),
+                                                     _native.FLAG_LOG1P if ctx.log1p else 0, out_bf16=ctx.grad_bf16)
+        return (*(None,) * (lead + 2), gpb, *(gpc if ctx.pcen else (None,) * 4), None, None, None, None)   # (one per positional input)
+
     def backward(ctx, grad_out, grad_raw):
+        if ctx.route == "head":
+            return backward_head(ctx, grad_out)
         K, hop = ctx.geom
         saved = ctx.saved_tensors
         kernel, pool_w, pool_b, raw = saved[lead:lead + 4]
@@ -141,7 +169,16 @@ def _register_family(mixed: bool) -> None:
     torch.library.register_autograd(f"leaf_amd::forward_train{sfx}", backward, setup_context=setup_context)
 
 
+def _register_head() -> None:
+    @torch.library.register_fake("leaf_amd::backward_head")
+    def _(pooled_raw, grad_out, pool_b, alpha, delta, root, ema_w, flags, out_bf16=False):
+        pc = pooled_raw.shape[1] if alpha is not None else 0
+        e = lambda *s: pooled_raw.new_empty(s, dtype=torch.float32)
+        return [e(*pool_b.shape), e(pc), e(pc), e(pc), e(pc)]
+
+
 def _register_python_side() -> None:
+    _register_head()
     _register_family(mixed=False)
     _register_family(mixed=True)
     from . import _second_order

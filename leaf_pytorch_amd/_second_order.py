@@ -56,6 +56,12 @@ def composite_forward(x, kernel, pool_w, pool_b, alpha, delta, root, ema_w, K: i
     g = torch.exp(-0.5 * ((j - half) / (s * half)) ** 2)                        # (F, K)
     frames = torch.nn.functional.pad(e, (pad_l, pad_r)).unfold(-1, K, hop)      # (B, F, T', K)
     pooled = (frames * g.unsqueeze(0).unsqueeze(2)).sum(-1) + pool_b.reshape(1, -1, 1)
+    return composite_head(pooled, alpha, delta, root, ema_w)
+
+
+def composite_head(pooled, alpha, delta, root, ema_w) -> torch.Tensor:
+    """The floor and PCEN on the pre-floor pooled tensor (B, F, T'): frontend.py:84-89, the part of ``composite_forward`` behind the
+    pooling -- all that the gradients of the pooling bias and the PCEN vectors depend on."""
     pooled = pooled.clamp(min=FLOOR_POOLED)
     if alpha is None:
         return pooled
@@ -135,6 +141,45 @@ def _backward_mix(ctx, *grads):
                        "itself (create_graph=True: mix with transforms.Mixup / _native.mixup and call forward on the result)")
 
 
+def _setup_context_head(ctx, inputs, output, keyword_only_inputs=None):
+    pooled_raw, grad_out, pool_b, alpha, delta, root, ema_w, flags = inputs
+    ctx.out_bf16 = bool((keyword_only_inputs or {}).get("out_bf16", False))
+    ctx.pcen = alpha is not None
+    ctx.log1p = bool(flags & FLAG_LOG1P) and not ctx.pcen
+    ctx.save_for_backward(pooled_raw, grad_out, pool_b, *([alpha, delta, root, ema_w] if ctx.pcen else []))
+
+
+def _backward_head(ctx, grads):
+    """``leaf_amd::backward_head``: cotangents on (g_pool_b, g_alpha, g_delta, g_root, g_ema_w) -> gradients on the op's inputs.  With the
+    filterbank and the waveform constant, G depends on the bias only through pooled = pooled_raw + (a shift of the bias), so the
+    composite starts at the saved pooled tensor: the same formula as ``backward`` above without the filterbank in front."""
+    if getattr(ctx, "out_bf16", False):
+        raise RuntimeError("gradients of gradients through Leaf are float32 only: second order with bfloat16 features or bfloat16 I/O "
+                           "is not supported (leave the waveform and the features float32 for create_graph=True)")
+    pooled_raw, grad_out, pool_b = ctx.saved_tensors[:3]
+    with torch.enable_grad():
+        shift = torch.zeros_like(pool_b, dtype=pooled_raw.dtype).requires_grad_(True)     # d/d pool_b = d/d shift
+        pc = [t.detach().requires_grad_(True) for t in ctx.saved_tensors[3:]] if ctx.pcen else [None] * 4
+        go = grad_out.detach().requires_grad_(True)
+        out = composite_head(pooled_raw.detach() + shift.reshape(1, -1, 1), *pc)
+        if ctx.log1p:
+            out = torch.log1p(out)
+        wrt = [shift] + (pc if ctx.pcen else [])
+        G = torch.autograd.grad(out, wrt, go, create_graph=True, allow_unused=True)
+        s = None
+        for v, g in zip(grads[:len(wrt)], G):
+            if v is None or g is None:
+                continue
+            term = (v.detach().reshape(g.shape) * g).sum()
+            s = term if s is None else s + term
+        res = [None] * (len(wrt) + 1) if s is None else torch.autograd.grad(s, [*wrt, go], allow_unused=True)
+    gpb = None if res[0] is None else res[0].reshape(pool_b.shape)
+    gpc = list(res[1:5]) if ctx.pcen else [None] * 4
+    # inputs: pooled_raw, grad_out, pool_b, alpha, delta, root, ema_w, flags
+    return None, res[-1], gpb, *gpc, None
+
+
 def register() -> None:
+    torch.library.register_autograd("leaf_amd::backward_head", _backward_head, setup_context=_setup_context_head)
     torch.library.register_autograd("leaf_amd::backward", backward, setup_context=setup_context)
     torch.library.register_autograd("leaf_amd::backward_mix", _backward_mix, setup_context=_setup_context_mix)

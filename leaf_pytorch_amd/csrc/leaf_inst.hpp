@@ -23,6 +23,7 @@ using FftKernel = void (*)(const FftParams);
 using SmallKernel = void (*)(const SmallParams);
 using StreamKernel = void (*)(const StreamParams);
 using StreamBankKernel = void (*)(const StreamBankParams);
+using HeadBwdKernel = void (*)(const HeadBwdParams);
 }  // namespace leaf
 
 leaf::FusedKernel leaf_inst_fused(int rt, int noff, bool even_k, bool bwd);          // leaf_fused_kernel<RT, NOFF, EVENK, BWD>
@@ -46,6 +47,10 @@ leaf::FftKernel leaf_inst_fft_wgg_bwd_dx(int ni);                               
 leaf::FftKernel leaf_inst_fft_wgg4k_bwd(int ni2);                                    // leaf_fft_wgg4k_bwd_kernel<12, NI2>
 leaf::FftKernel leaf_inst_fft_wg4k_bwd();                                            // leaf_fft_wgg4k_bwd_kernel<12, 7, true>: K = 801, hop = 320
 leaf::FftKernel leaf_inst_fft_wg4k_bwd_dx();                                         // leaf_fft_wgg4k_bwd_kernel<9, 7, true, true>: the same with dL/dx
+leaf::HeadBwdKernel leaf_inst_head_bwd();                                            // leaf_head_bwd_kernel: pool_b and PCEN gradients from pooled_raw, one launch
+// the split of the batch that kernel's grid (F, S) follows -- slices of L rows, a function of B, F and the CU count alone
+// (leaf_head_bwd.hpp: head_plan)
+void leaf_head_bwd_plan(int B, int F, int cus, int* S, int* L);
 
 // the instances for a mixed call (waveform mixup in the block load, leaf_common.hpp); nullptr where there is none
 leaf::FftKernel leaf_inst_fft_mix(int sk, int bwd);                                  // leaf_fft_kernel<SK, SHOP, 1, 1, BWD, true>: sk = 401 | 801 | 201
@@ -73,3 +78,4 @@ unsigned leaf_layout_fft_wgg4k_bwd();
 unsigned leaf_layout_fft_wgg_bwd();
 unsigned leaf_layout_fft_wgg_bwd_dx();
 unsigned leaf_layout_fused();
+unsigned leaf_layout_head_bwd();

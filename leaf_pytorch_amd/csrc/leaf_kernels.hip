@@ -679,7 +679,7 @@ bool inst_layouts_ok() {
         for (unsigned (*unit)() : {leaf_layout_fft, leaf_layout_fft_small, leaf_layout_fft_stream, leaf_layout_fft_wg, leaf_layout_fft_wg_streamfin,
                                    leaf_layout_fft_wg_x16, leaf_layout_fft_wg_mix, leaf_layout_fft_wg_mix16, leaf_layout_fft_wg_bwd,
                                    leaf_layout_fft_wg_bwd_dx, leaf_layout_fft_wgg, leaf_layout_fft_wgg4k_bwd, leaf_layout_fft_wgg_bwd,
-                                   leaf_layout_fft_wgg_bwd_dx, leaf_layout_fused})
+                                   leaf_layout_fft_wgg_bwd_dx, leaf_layout_fused, leaf_layout_head_bwd})
             if (unit() != leaf_params_layout()) return false;
         return true;
     }();
@@ -2683,6 +2683,87 @@ int leaf_backward_mix_f32(const void* x, const int* mix_perm, const float* mix_l
                          LeafArgs{{B, T, F, K, hop}, kernel, pool_w, pool_b, alpha, delta, root, ema_w, (hipStream_t)stream}, flags,
                          BwdIo{static_cast<const float*>(x), 0, grad_out, pooled_raw, g_kernel, g_pool_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w, g_x, 0, false},
                          workspace, workspace_bytes);
+}
+
+// ---- head-only backward (leaf_head_bwd.hpp): d pool_b and the PCEN gradients from pooled_raw, one memset and one launch ----------
+// workspace: [tickets: F words, padded to 16 bytes][records: F S kHeadRecFloats floats][ema: F S kHeadWaves rows of TP floats, only
+// for rows beyond the scan's register form]
+struct HeadLayout {
+    int S, L;
+    size_t ticket_bytes, rec_floats, ema_floats;
+    size_t bytes() const { return ticket_bytes + (rec_floats + ema_floats) * 4; }
+};
+static HeadLayout head_layout(int B, int TP, int F, int flags) {
+    HeadLayout h{};
+    leaf_head_bwd_plan(B, F, device_cus(), &h.S, &h.L);
+    h.ticket_bytes = align_up((size_t)F * 4, 16);
+    h.rec_floats = (size_t)F * h.S * kHeadRecFloats;
+    const bool scan_mem = (flags & LEAF_FLAG_PCEN) && TP > kScanRegChunks * 128;
+    h.ema_floats = scan_mem ? (size_t)F * h.S * kHeadWaves * TP : 0;
+    return h;
+}
+constexpr int kHeadFlags = LEAF_FLAG_PCEN | LEAF_FLAG_LOG1P | LEAF_FLAG_IO_BF16 | LEAF_FLAG_OUT_BF16;
+
+size_t leaf_backward_head_workspace_bytes(int B, int TP, int F, int flags) {
+    if (B < 1 || TP < 1 || F < 1 || (flags & ~kHeadFlags) || (long long)B * F * TP >= (1ll << 31)) return 0;
+    return head_layout(B, TP, F, flags).bytes();
+}
+
+int leaf_backward_head_f32(const float* pooled_raw, const float* grad_out, int B, int TP, int F, const float* alpha,
+                           const float* delta, const float* root, const float* ema_w, int flags, float* g_pool_b, float* g_alpha,
+                           float* g_delta, float* g_root, float* g_ema_w, void* workspace, size_t workspace_bytes, void* stream) {
+    if (flags & ~kHeadFlags) return LEAF_ERR_UNSUPPORTED;
+    const hipStream_t st = (hipStream_t)stream;
+    const bool use_pcen = (flags & LEAF_FLAG_PCEN) != 0;
+    if (B == 0 && TP >= 1 && F >= 1) {
+        // the sum over zero clips (leaf_backward_f32): zero gradients, nothing launched
+        if (!g_pool_b || (use_pcen && (!g_alpha || !g_delta || !g_root || !g_ema_w))) return LEAF_ERR_NULL_POINTER;
+        if (!inst_layouts_ok()) return LEAF_ERR_LAUNCH;
+        bool ok = hipMemsetAsync(g_pool_b, 0, (size_t)F * 4, st) == hipSuccess;
+        if (use_pcen)
+            for (float* g : {g_alpha, g_delta, g_root, g_ema_w}) ok = ok && hipMemsetAsync(g, 0, (size_t)F * 4, st) == hipSuccess;
+        return ok ? LEAF_OK : LEAF_ERR_LAUNCH;
+    }
+    if (!pooled_raw || !grad_out || !g_pool_b) return LEAF_ERR_NULL_POINTER;
+    if (use_pcen && (!alpha || !delta || !root || !ema_w || !g_alpha || !g_delta || !g_root || !g_ema_w)) return LEAF_ERR_NULL_POINTER;
+    if (B < 1 || TP < 1 || F < 1) return LEAF_ERR_BAD_SHAPE;
+    if ((long long)B * F * TP >= (1ll << 31)) return LEAF_ERR_BAD_SHAPE;          // (the caller slices the batch)
+    if (!inst_layouts_ok()) return LEAF_ERR_LAUNCH;
+    const bool go_bf16 = feat_bf16(flags);
+    if ((reinterpret_cast<uintptr_t>(grad_out) & (go_bf16 ? 1u : 3u)) || misaligned16(workspace) ||
+        any_misaligned(pooled_raw, alpha, delta, root, ema_w, g_pool_b, g_alpha, g_delta, g_root, g_ema_w))
+        return LEAF_ERR_ALIGNMENT;
+    const HeadLayout h = head_layout(B, TP, F, flags);
+    if (h.S < 1 || h.S > 65535) return LEAF_ERR_BAD_SHAPE;
+    if (!workspace || workspace_bytes < h.bytes()) return LEAF_ERR_WORKSPACE;
+    HeadBwdParams p{};
+    p.raw = pooled_raw; p.gout = grad_out;
+    p.alpha = alpha; p.delta = delta; p.root = root; p.ema_w = ema_w;
+    p.floor_ = 1e-12f;
+    p.mode = (use_pcen ? 1 : 0) | ((flags & LEAF_FLAG_LOG1P) && !use_pcen ? 2 : 0) | (go_bf16 ? 4 : 0);
+    p.B = B; p.F = F; p.TP = TP; p.S = h.S; p.L = h.L;
+    p.tickets = static_cast<unsigned*>(workspace);
+    p.rec = reinterpret_cast<float*>(static_cast<char*>(workspace) + h.ticket_bytes);
+    p.ema = h.ema_floats ? p.rec + h.rec_floats : nullptr;
+    p.g_pool_b = g_pool_b; p.g_alpha = g_alpha; p.g_delta = g_delta; p.g_root = g_root; p.g_ema_w = g_ema_w;
+    // the tickets: one memset in front of the launch.  While the stream is being captured a kernel node zeroes them instead: on this
+    // runtime a captured memset node writes zeros on the first replay of its graph and other bytes on the later ones (a stand-alone
+    // probe showed it; the tickets then never reach S - 1), and a kernel node replays as it was captured
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &capture) != hipSuccess) {
+        (void)hipGetLastError();
+        capture = hipStreamCaptureStatusNone;
+    }
+    if (capture == hipStreamCaptureStatusActive) {
+        const int words = (int)(h.ticket_bytes / 4);
+        hipLaunchKernelGGL(zero_words_kernel, dim3(ceil_div(words, 256)), dim3(256), 0, st, p.tickets, words);
+        LEAF_LAUNCH_CHECK();
+    } else if (hipMemsetAsync(p.tickets, 0, h.ticket_bytes, st) != hipSuccess) {
+        return LEAF_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(leaf_inst_head_bwd(), dim3(F, h.S), dim3(64 * kHeadWaves), 0, st, p);
+    LEAF_LAUNCH_CHECK();
+    return LEAF_OK;
 }
 
 }  // extern "C"

@@ -28,4 +28,11 @@ __global__ void x16_widen_kernel(const unsigned short* __restrict__ src, int st,
     if (i < n) dst[i] = st == kSamplePcm16 ? pcm16_widen((short)src[i]) : bf16_widen(src[i]);
 }
 
+// n words <- 0: what leaf_backward_head_f32 launches in place of its hipMemsetAsync while the stream is being captured (a captured
+// memset node was seen to write other bytes than zeros from the second replay of its graph on)
+__global__ void zero_words_kernel(unsigned* __restrict__ dst, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = 0u;
+}
+
 }  // namespace

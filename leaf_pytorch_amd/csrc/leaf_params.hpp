@@ -271,6 +271,23 @@ struct StreamBankParams {
 };
 static_assert(sizeof(StreamBankParams) <= 4096, "the records travel in the kernel argument segment");
 
+// ---- head-only backward: pool_b and PCEN gradients from pooled_raw in one launch (leaf_head_bwd.hpp) ----------------------------
+constexpr int kHeadWaves = 4;            // waves per workgroup, one (b, f) row each at a time
+constexpr int kHeadRecFloats = 8;        // a workgroup's record: (s_a, s_d, s_rho, s_w, s_g), padded to 32 bytes
+struct HeadBwdParams {
+    const float* raw;         // [B][F][TP] pooled_raw: pre-floor, bias included (leaf_forward_save_f32)
+    const void* gout;         // [B][F][TP] grad_out, float32 or bfloat16 by bit 2 of mode
+    const float *alpha, *delta, *root, *ema_w;   // [F] (PCEN only)
+    float floor_;             // the PCEN floor
+    int mode;                 // bit0 PCEN, bit1 log1p behind the floor (PCEN off only), bit2 bfloat16 grad_out
+    int B, F, TP;
+    int S, L;                 // grid (F, S): workgroup (f, s) walks rows b in [s L, min(B, (s + 1) L)) of filter f
+    unsigned* tickets;        // [F], zeroed by the host in front of every launch
+    float* rec;               // [F][S][kHeadRecFloats]: one partial record per workgroup
+    float* ema;               // [F * S * waves][TP] smoother values of rows beyond the register form; NULL when every row fits
+    float *g_pool_b, *g_alpha, *g_delta, *g_root, *g_ema_w;   // [F] out (the PCEN four with bit0 only)
+};
+
 // Layout fingerprint of the structs above.  The types are shared, but the OBJECT FILES of an incremental build are not: a unit
 // compiled before a field was added, or with a macro that changes a layout, would read its arguments at the wrong offsets.  Every
 // unit exports the value it was compiled with (leaf_layout_* of leaf_inst.hpp) and leaf_kernels.hip compares them all with its
@@ -299,6 +316,8 @@ constexpr unsigned leaf_params_layout() {
     h = layout_mix(h, sizeof(StreamParams), offsetof(StreamParams, bd), offsetof(StreamParams, c_lo), offsetof(StreamParams, fin));
     h = layout_mix(h, sizeof(StreamPos), sizeof(StreamPassRec), sizeof(StreamBankParams), offsetof(StreamBankParams, first),
                    offsetof(StreamBankParams, rec), (size_t)kBankSlots);
+    h = layout_mix(h, sizeof(HeadBwdParams), offsetof(HeadBwdParams, floor_), offsetof(HeadBwdParams, S), offsetof(HeadBwdParams, tickets),
+                   offsetof(HeadBwdParams, g_pool_b), (size_t)kHeadWaves, (size_t)kHeadRecFloats);
     return h;
 }
 

@@ -182,6 +182,7 @@ Tensor forward_impl(const Tensor& x, const Mix* mix, const Params& p, int64_t K,
     // call options travelling in the upper bits of the op's `algo` argument (the schema stays as it is): bit 24 = the
     // PeakNormalization prologue folded into the forward (LEAF_FLAG_PEAKNORM; inference only, the plain ops only)
     constexpr int64_t kOptPeakNorm = int64_t(1) << 24;
+    algo &= ~(int64_t(1) << 29);                               // OPT_FULL_BACKWARD: read by the autograd formula (_ops.py) alone
     if (!c.mixed && (algo & kOptPeakNorm)) {
         TORCH_CHECK(!raw, "the fused PeakNormalization prologue is forward-only");
         if (!c.pcm16) flags |= LEAF_FLAG_PEAKNORM;              // (|v / 32768| <= 1: nothing to normalise, nothing launched)
@@ -340,6 +341,73 @@ std::vector<Tensor> backward_impl(const Tensor& x, const Mix* mix, const Params&
     return result();
 }
 
+// The head-only backward (leaf_hip.h: leaf_backward_head_f32): (g_pool_b, g_alpha, g_delta, g_root, g_ema_w) from the saved pre-floor
+// pooled tensor and grad_out alone -- what a Leaf whose Gabor kernel and pooling width are frozen needs.  pool_b gives the shape and
+// the device of its gradient, nothing else; the PCEN entries are empty tensors without PCEN.  `flags`: LEAF_FLAG_LOG1P (PCEN off);
+// LEAF_FLAG_PCEN follows from the tensors.  out_bf16: grad_out is bfloat16 (bfloat16 features, from whatever waveform).
+// B * F * T' >= 2^31: slices over B, the gradients of the slices added in slice order.
+std::vector<Tensor> op_backward_head(const Tensor& pooled_raw, const Tensor& grad_out, const Tensor& pool_b, const OptTensor& alpha,
+                                     const OptTensor& delta, const OptTensor& root, const OptTensor& ema_w, int64_t flags, bool out_bf16) {
+    TORCH_CHECK(pooled_raw.is_cuda(), "leaf_amd::backward_head: pooled_raw is on '", pooled_raw.device(),
+                "'. leaf_pytorch_amd runs only on an AMD GPU through its HIP kernels; there is no CPU path in the product");
+    const auto dev = pooled_raw.device();
+    TORCH_CHECK(pooled_raw.dim() == 3, "pooled_raw must be (B, F, T'), got ", pooled_raw.sizes());
+    const Tensor raw = dev_f32(pooled_raw, "pooled_raw", dev);
+    const int64_t B = raw.size(0), F = raw.size(1), TP = raw.size(2);
+    TORCH_CHECK(F >= 1 && TP >= 1 && F * TP < (int64_t(1) << 31), "bad shape B=", B, " F=", F, " T'=", TP);
+    Tensor go;
+    if (out_bf16) {
+        TORCH_CHECK(grad_out.device() == dev, "grad_out is on ", grad_out.device(), ", expected ", dev);
+        TORCH_CHECK(grad_out.scalar_type() == at::kBFloat16, "grad_out must be bfloat16 with out_bf16=True, got ", grad_out.scalar_type());
+        go = grad_out.contiguous();
+    } else {
+        go = dev_f32(grad_out, "grad_out", dev);
+    }
+    TORCH_CHECK(go.sizes() == raw.sizes(), "grad_out has shape ", go.sizes(), ", expected ", raw.sizes());
+    TORCH_CHECK(pool_b.device() == dev && pool_b.numel() == F, "pool_b must hold one bias per filter on ", dev);
+    const bool pcen = alpha.has_value() && alpha->defined();
+    OptTensor a, d, r, w;
+    if (pcen) {
+        a = dev_f32(alpha, "alpha", dev); d = dev_f32(delta, "delta", dev); r = dev_f32(root, "root", dev); w = dev_f32(ema_w, "ema_w", dev);
+        TORCH_CHECK(d && r && w, "PCEN needs alpha, delta, root and ema_w");
+        TORCH_CHECK(a->numel() == F && d->numel() == F && r->numel() == F && w->numel() == F, "the PCEN vectors must hold one entry per filter");
+    }
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index());
+    auto opt = raw.options();
+    const int64_t np = pcen ? F : 0;
+    Tensor gb = at::empty(pool_b.sizes(), opt), ga = at::empty({np}, opt), gd = at::empty({np}, opt), gr = at::empty({np}, opt),
+           gw = at::empty({np}, opt);
+    if (B == 0) {
+        for (Tensor* g : {&gb, &ga, &gd, &gr, &gw}) g->zero_();
+        return {gb, ga, gd, gr, gw};
+    }
+    const int fl = (pcen ? LEAF_FLAG_PCEN : ((int)flags & LEAF_FLAG_LOG1P)) | (out_bf16 ? LEAF_FLAG_OUT_BF16 : 0);
+    const BatchSlices sl = batch_slices(B, F * TP);
+    const int last = (int)(B - (sl.calls - 1) * sl.per_call);
+    auto ws_bytes = [&](int nb) { return leaf_backward_head_workspace_bytes(nb, (int)TP, (int)F, fl); };
+    Tensor ws = at::empty({(int64_t)std::max<size_t>({ws_bytes((int)sl.per_call), ws_bytes(last), size_t(4)})}, opt.dtype(at::kByte));
+    Tensor tb, ta, td, tr, tw;
+    if (sl.calls > 1) {
+        tb = at::empty_like(gb); ta = at::empty_like(ga); td = at::empty_like(gd); tr = at::empty_like(gr); tw = at::empty_like(gw);
+    }
+    for (int64_t b0 = 0; b0 < B; b0 += sl.per_call) {
+        const int nb = (int)std::min<int64_t>(sl.per_call, B - b0);
+        const bool first = b0 == 0;
+        Tensor &b_ = first ? gb : tb, &a_ = first ? ga : ta, &d_ = first ? gd : td, &r_ = first ? gr : tr, &w_ = first ? gw : tw;
+        check_status(leaf_backward_head_f32(fptr(raw) + (size_t)b0 * F * TP, io_at(go, (size_t)b0 * F * TP), nb, (int)TP, (int)F, fptr(a),
+                                            fptr(d), fptr(r), fptr(w), fl, b_.data_ptr<float>(), pcen ? a_.data_ptr<float>() : nullptr,
+                                            pcen ? d_.data_ptr<float>() : nullptr, pcen ? r_.data_ptr<float>() : nullptr,
+                                            pcen ? w_.data_ptr<float>() : nullptr, ws.data_ptr(), (size_t)ws.numel(), stream.stream()),
+                     "leaf_backward_head_f32");
+        if (!first) {
+            gb.add_(tb);
+            if (pcen) { ga.add_(ta); gd.add_(td); gr.add_(tr); gw.add_(tw); }
+        }
+    }
+    return {gb, ga, gd, gr, gw};
+}
+
 // ---- the six ops: leaf_amd::forward -- frontend.py:78-89 (inference / no-grad); forward_train -- the same, additionally returning
 // the pre-floor pooled tensor the backward consumes; backward; and the three on the mixed batch (forward_mix, forward_train_mix,
 // backward_mix: the seven parameter gradients, no dL/dx)
@@ -393,6 +461,8 @@ TORCH_LIBRARY(leaf_amd, m) {
           "Tensor? delta, Tensor? root, Tensor? ema_w, int K, int hop, int algo, bool log1p=False, *, bool out_bf16=False) -> (Tensor, Tensor)");
     m.def("backward_mix(Tensor x, Tensor perm, Tensor lam, Tensor kernel, Tensor pool_w, Tensor pool_b, Tensor? alpha, Tensor? delta, "
           "Tensor? root, Tensor? ema_w, int K, int hop, Tensor grad_out, Tensor? pooled_raw, int flags, *, bool out_bf16=False) -> Tensor[]");
+    m.def("backward_head(Tensor pooled_raw, Tensor grad_out, Tensor pool_b, Tensor? alpha, Tensor? delta, Tensor? root, Tensor? ema_w, "
+          "int flags, *, bool out_bf16=False) -> Tensor[]");
     m.def("table_cache_info() -> int[]", &op_table_cache_info);
 }
 
@@ -404,4 +474,5 @@ TORCH_LIBRARY_IMPL(leaf_amd, CUDA, m) {
     m.impl("forward_mix", &op_forward_mix);
     m.impl("forward_train_mix", &op_forward_train_mix);
     m.impl("backward_mix", &op_backward_mix);
+    m.impl("backward_head", &op_backward_head);
 }

@@ -27,8 +27,9 @@ class SquaredModulus(nn.Module):
 
 class _LeafFn(torch.autograd.Function):
     """The path without the dispatcher ops.  Forward = fused HIP path (leaf_forward_save_f32); backward = leaf_backward_f32 (recomputes
-    on device).  ``lead`` inputs stand in front of the seven parameters: x alone, or x, perm, lam for the mixed batch
-    x * lam + x[perm] * (1 - lam) (leaf_forward_save_mix_f32 / leaf_backward_mix_f32: parameter gradients only)."""
+    on device), or leaf_backward_head_f32 where ``_ops.backward_route`` says the head is all that is asked for.  ``lead`` inputs stand
+    in front of the seven parameters: x alone, or x, perm, lam for the mixed batch x * lam + x[perm] * (1 - lam)
+    (leaf_forward_save_mix_f32 / leaf_backward_mix_f32: parameter gradients only)."""
 
     @staticmethod
     def forward(ctx, lead, *args):
@@ -36,9 +37,17 @@ class _LeafFn(torch.autograd.Function):
         if algo & _native.OPT_PEAKNORM:
             # leaf_forward_save_f32 would hand the backward a pooled tensor of the NORMALISED clips next to the raw x
             raise RuntimeError("the folded PeakNormalization prologue is forward-only (no backward through it)")
+        need = ctx.needs_input_grad[1:]                               # (behind `lead`)
+        ctx.route = "full" if algo & _native.OPT_FULL_BACKWARD else _ops.backward_route(need[lead], need[lead + 1], need[0] or (lead == 3 and need[2]), False)
+        algo &= ~_native.OPT_FULL_BACKWARD
         fwd = _native.leaf_forward if lead == 1 else _native.leaf_forward_mix
         out, raw = fwd(*head, *params, K, hop, pcen=pcen, log1p=log1p, algo=algo, save_raw=True, out_bf16=out_bf16)
         ctx.lead, ctx.geom = lead, (K, hop)
+        if ctx.route == "head":
+            # the gradients of the pooling bias and the PCEN vectors: nothing of the waveform side is saved
+            ctx.how = dict(pcen=pcen, log1p=bool(log1p) and not pcen, out_bf16=out.dtype == torch.bfloat16)
+            ctx.save_for_backward(params[2], raw, *(params[3:] if pcen else ()))
+            return out
         ctx.how = dict(pcen=pcen, log1p=bool(log1p) and not pcen,
                        out_bf16=bool(out_bf16),                   # bfloat16 features: their gradient arrives in bfloat16 and goes straight in
                        full_transforms=bool(algo & _native.ALGO_FULL_TRANSFORMS),   # Leaf.full_transforms(): the backward keeps them too
@@ -50,6 +59,10 @@ class _LeafFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable      # (gradients of gradients: the dispatcher-op path, _second_order.py; here they raise)
     def backward(ctx, grad_out):
         lead, saved = ctx.lead, ctx.saved_tensors
+        if ctx.route == "head":
+            pool_b, raw, *pc = saved
+            gpb, *gpc = _native.leaf_backward_head(raw, grad_out, pool_b, *(pc or (None,) * 4), **ctx.how)
+            return (None, *(None,) * (lead + 2), gpb, *gpc, *(None,) * 6)      # (one per input of forward)
         head, (kernel, pool_w, pool_b, raw), pc = saved[:lead], saved[lead:lead + 4], saved[lead + 4:] or (None,) * 4
         if lead == 1:
             *grads, gx = _native.leaf_backward(*head, kernel, pool_w, pool_b, *pc, *ctx.geom, grad_out, need_dx=ctx.needs_input_grad[1],
@@ -95,6 +108,7 @@ class Leaf(nn.Module):
         self._fuse_peaknorm = False          # not part of the reference surface: see fuse_peak_normalization()
         self._log1p = False                  # not part of the reference surface: see log_compression()
         self._out_dtype = None               # not part of the reference surface: see output_dtype()
+        self._full_backward = False          # not part of the reference surface: see full_backward()
 
     def full_transforms(self, enable: bool = True) -> "Leaf":
         """Not part of the reference surface: switch the band-limited filter tasks off for this module -- every filter on the
@@ -103,6 +117,16 @@ class Leaf(nn.Module):
         oracle in the forward and ~1e-5 of the full-transform gradients; this is the opt-out for a caller who wants the
         formulation without the approximation, at ~1.8x the time of the 16 kHz forward."""
         self._algo = (self._algo | _native.ALGO_FULL_TRANSFORMS) if enable else (self._algo & ~_native.ALGO_FULL_TRANSFORMS)
+        return self
+
+    def full_backward(self, enable: bool = True) -> "Leaf":
+        """Not part of the reference surface: keep the full backward (leaf_backward_f32: every forward intermediate recomputed, all
+        seven parameter gradients) also where the head-only backward would do.  By default a training forward whose Gabor kernel
+        and pooling width are frozen (``requires_grad_(False)``) and whose input needs no gradient saves the pre-floor pooled
+        tensor and the PCEN vectors alone -- no waveform -- and its backward is one launch over them (leaf_backward_head_f32) for
+        the gradients of the pooling bias and the PCEN vectors.  This switch is what ``tools/bench_backward.py --frozen-filters``
+        measures that route against; the gradients of the two routes agree to float32 rounding."""
+        self._full_backward = bool(enable)
         return self
 
     def log_compression(self, enable: bool = True) -> "Leaf":
@@ -219,13 +243,14 @@ class Leaf(nn.Module):
         log1p = self._log1p and c is None
         bf16 = self._features_bf16(x)                             # output_dtype(): bfloat16 features of the mixed batch
         needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params)
+        train_algo = self._algo | (_native.OPT_FULL_BACKWARD if self._full_backward else 0)
         if _ops.available():
             _ops.load()
             if needs_grad:
-                return _ops.forward_train_mix(x, perm, lam, *params, K, hop, algo=self._algo, log1p=log1p, out_bf16=bf16)
+                return _ops.forward_train_mix(x, perm, lam, *params, K, hop, algo=train_algo, log1p=log1p, out_bf16=bf16)
             return _ops.forward_mix(x, perm, lam, *params, K, hop, log1p=log1p, algo=self._algo, out_bf16=bf16)
         if needs_grad:
-            return _LeafFn.apply(3, x, perm, lam, *params, K, hop, c is not None, self._algo, log1p, bf16)
+            return _LeafFn.apply(3, x, perm, lam, *params, K, hop, c is not None, train_algo, log1p, bf16)
         return _native.leaf_forward_mix(x, perm, lam, *params, K, hop, pcen=c is not None, log1p=log1p, algo=self._algo, out_bf16=bf16)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -243,6 +268,7 @@ class Leaf(nn.Module):
         # from the tensors actually handed to the kernel, not self.parameters(): nn.DataParallel replicas hold plain
         # (non-leaf) tensors, for which parameters() is empty
         params_need_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in params)
+        train_full = self._full_backward
         # an int16 waveform (16-bit PCM: a sample v means v / 32768) lies in [-1, 1) by construction: nothing to normalise
         if self._fuse_peaknorm and x.dtype != torch.int16:
             # the folded prologue is forward-only: the same condition that sends the call to the training path below
@@ -259,6 +285,7 @@ class Leaf(nn.Module):
             else:
                 from .transforms import PeakNormalization
                 x = PeakNormalization()(x)
+                train_full = True                                 # (under autograd: the backward stays the full one, as before)
         if c is not None and c._floor != 1e-12:
             raise NotImplementedError("fused path is specialised for the PCEN floor Leaf constructs (1e-12)")
         pcen = c is not None
@@ -270,11 +297,12 @@ class Leaf(nn.Module):
             # dispatcher ops (csrc/torch_binding.cpp): traceable by torch.compile / export, one hop per eager call
             _ops.load()
             if needs_grad:
-                return _ops.forward_train(x, *params, K, hop, algo=algo, log1p=log1p, out_bf16=bf16)
+                return _ops.forward_train(x, *params, K, hop, algo=algo | (_native.OPT_FULL_BACKWARD if train_full else 0), log1p=log1p,
+                                          out_bf16=bf16)
             if not (self._cache_tables and not torch.compiler.is_compiling()):
                 return _ops.forward(x, *params, K, hop, log1p=log1p, algo=algo, out_bf16=bf16)
         if needs_grad:
-            return _LeafFn.apply(1, x, *params, K, hop, pcen, algo, log1p, bf16)
+            return _LeafFn.apply(1, x, *params, K, hop, pcen, algo | (_native.OPT_FULL_BACKWARD if train_full else 0), log1p, bf16)
         if self._cache_tables and self._algo in (_native.ALGO_AUTO, _native.ALGO_FFT):
             B, T = x.shape[0], x.shape[-1]
             with torch.cuda.device(x.device):            # the plan is sized for the CU count of the device the call runs on
