@@ -717,6 +717,61 @@ int leaf_assemble_clips_noise_f32(const void* store, long long store_len, int fl
 int leaf_gaussian_noise_f32(int B, int size, unsigned long long seed, const long long* stream_ids /*[B]*/, float* out /*[B][size]*/,
                             void* stream);
 
+/* Whole-recording evaluation batches from the same packed store (additive: the ABI version stays 6).  The reference's test.py
+ * evaluates a recording r of L samples as a whole: PeakNormalization over the recording (ONE peak per recording), pad_input --
+ * n = ceil(L / S) rows of S = sample_rate samples, P = n S, left = (P - L) / 2, F.pad(r, (left, P - L - left), 'replicate'),
+ * reshape(-1, 1, S) -- the model on the n rows, and the mean of its outputs.  Two entries restate the data side: the recordings'
+ * peaks, once per dataset, and the rows of any number of recordings in one launch.
+ *
+ * leaf_clip_peaks_f32: peaks[i] = max |r_i[j]| over recording i, r_i[j] = store[rec_off[i] + j], 0 <= j < rec_len[i]; a recording
+ * of no samples gives 0.  The result is exact (max does not depend on the order); a NaN sample is ignored, as fmaxf ignores it in
+ * leaf_peak_normalize_f32; an int16 store (LEAF_FLAG_X_PCM16, v / 32768) has no peak above 1.  The work is split by tiles of 1024
+ * samples, one wave each, not by recording: one long recording spreads over the chip, a short one costs one wave.  Two launches:
+ * the tile prefix of the clamped plan into the workspace, then the tiles, folded into peaks[] by an integer max on the bit pattern
+ * of the non-negative floats (no float atomics).
+ *
+ *   store, store_len, flags: as in leaf_assemble_clips_f32          R: the number of recordings
+ *   rec_off  [R] int64, rec_len [R] int32: the recordings           peaks [R] float32, out
+ *   workspace: leaf_clip_peaks_workspace_bytes(R) = 8 (R + 1) bytes (0 for R < 1), overwritten
+ *
+ * MEMORY SAFETY: rec_off and rec_len are device memory and are clamped exactly as in leaf_assemble_clips_f32 (rec_off into
+ * [0, store_len], rec_len into [0, store_len - rec_off]): nothing outside store[0, store_len) is read, nothing outside peaks[0, R)
+ * and the workspace is written.  Alignment: store 4 bytes (2 for int16), rec_off 8, rec_len and peaks 4, workspace 16.  Status, in
+ * this order, before any launch: LEAF_ERR_UNSUPPORTED for a flag other than LEAF_FLAG_X_PCM16; LEAF_ERR_NULL_POINTER (store, rec_off,
+ * rec_len, peaks); LEAF_ERR_BAD_SHAPE for R < 1 or store_len < 0; LEAF_ERR_ALIGNMENT; LEAF_ERR_WORKSPACE for a workspace that is NULL
+ * or below the size query.  peaks and the workspace must not overlap the store or the plan. */
+size_t leaf_clip_peaks_workspace_bytes(int R);
+int leaf_clip_peaks_f32(const void* store, long long store_len, int flags, int R, const long long* rec_off /*[R]*/,
+                        const int* rec_len /*[R]*/, float* peaks /*[R]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* leaf_assemble_segments_f32: `rows` rows of `size` samples, each a window of one recording.
+ *
+ *   rec_off  [rows] int64, rec_len [rows] int32: the row's recording (repeated for each of its rows)
+ *   win      [rows] int64: the recording's sample the row starts at; it may lie before the recording or behind it.  test.py's
+ *            row k of a recording is win = k S - left
+ *   peaks    [R] float32 (leaf_clip_peaks_f32) or NULL; rec [rows] int32: the row's entry of peaks (read only with peaks != NULL)
+ *   out      [rows][size] float32
+ *
+ * With r[j] = store[rec_off[b] + j] and L = rec_len[b], for row b and t in [0, size):
+ *   1. v = r[clamp(win[b] + t, 0, L - 1)] -- F.pad 'replicate' on either side; L == 0 gives zeros;
+ *   2. peaks != NULL: p = peaks[clamp(rec[b], 0, R - 1)]; p > 1 gives v * (1 / p), else v unchanged -- the arithmetic of
+ *      leaf_peak_normalize_f32 with the recording's peak in place of the row's.  Padding a scaled recording by replication equals
+ *      scaling the padded one, so the rows have the bits of test.py's order of operations.
+ *
+ * Nothing is reduced: a row longer than one tile of 32768 samples is split over workgroups (grid = rows x tiles), on the 16-byte
+ * chunk grid aligned in `out` and with the element-aligned source loads of leaf_assemble_clips_f32.  No workspace.
+ *
+ * MEMORY SAFETY: the plan is clamped by the kernel -- rec_off and rec_len as in leaf_assemble_clips_f32, win into [-size, L] (a
+ * window further out reads the same samples), rec into [0, R - 1]; win + t is formed in 64 bits from the clamped win.  Whatever
+ * the plan holds, nothing outside store[0, store_len) or peaks[0, R) is read and nothing outside out[rows][size] is written.
+ * Alignment: store 4 bytes (2 for int16), rec_off and win 8, every other buffer 4.  Status, in this order, before any launch:
+ * LEAF_ERR_UNSUPPORTED for a flag other than LEAF_FLAG_X_PCM16; LEAF_ERR_NULL_POINTER (store, rec_off, rec_len, win, out; rec with
+ * peaks != NULL); LEAF_ERR_BAD_SHAPE for rows < 1, size < 1, store_len < 0, R < 1 with peaks != NULL, or rows x tiles >= 2^31;
+ * LEAF_ERR_ALIGNMENT.  out must not overlap the store. */
+int leaf_assemble_segments_f32(const void* store, long long store_len, int flags, int rows, int size, const long long* rec_off,
+                               const int* rec_len, const long long* win, const float* peaks /*[R] or NULL*/, const int* rec, int R,
+                               float* out /*[rows][size]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

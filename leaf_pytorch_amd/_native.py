@@ -111,6 +111,13 @@ _SIGNATURES = {
                                       + [ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_void_p]),
     # the stream itself: B, size, seed, stream ids, out, stream
     "leaf_gaussian_noise_f32": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # whole-recording evaluation.  The peaks: store, store_len, flags, R, rec_off, rec_len, peaks, workspace, workspace_bytes, stream
+    "leaf_clip_peaks_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "leaf_clip_peaks_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4
+                            + [ctypes.c_size_t, ctypes.c_void_p]),
+    # ... and the rows: store, store_len, flags, rows, size, rec_off, rec_len, win, peaks, rec, R, out, stream
+    "leaf_assemble_segments_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+                                   + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "leaf_fft_tables_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "leaf_fft_prepare_tables_f32": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_size_t, ctypes.c_void_p]),
@@ -1143,6 +1150,69 @@ def assemble_clips(store: torch.Tensor, rec_off, rec_len, start, pad_mode, size:
     if gaussian is not None:
         ggroup = (gaussian[0].to(device=dev).contiguous(), gaussian[1], gaussian[2].to(device=dev, dtype=torch.int64).contiguous())
     _call(dev, "leaf_assemble_clips_noise_f32", *head, *ngroup, *ggroup)
+    return out
+
+
+def _recordings(store: torch.Tensor, rec_off, rec_len, who: str, size: int = 1):
+    """``store`` and the two arrays that name recordings in it, checked as ``clip_plan`` checks them: (B, rec_off, rec_len)."""
+    if not isinstance(store, torch.Tensor) or store.dim() != 1 or store.dtype not in (torch.float32, torch.int16):
+        raise RuntimeError(f"{who}: store must be a 1-D float32 or int16 tensor")
+    if not isinstance(rec_off, torch.Tensor):
+        rec_off = torch.as_tensor(rec_off)
+    zeros = torch.zeros(rec_off.numel(), dtype=torch.int64)
+    B, rec_off, rec_len, _, _, _, _ = clip_plan(store.numel(), rec_off, rec_len, zeros, zeros, size)
+    return B, rec_off, rec_len
+
+
+def clip_peaks(store: torch.Tensor, rec_off, rec_len) -> torch.Tensor:
+    """``max |r_i|`` of every recording ``store[rec_off[i] : rec_off[i] + rec_len[i]]`` as an (R,) float32 tensor on the store's device
+    (leaf_clip_peaks_f32): exact; 0 for a recording of no samples; NaN samples are ignored; an int16 store (v / 32768) has no peak
+    above 1.  One call for all recordings, split by tiles of samples and not by recording.  The two arrays are validated on the CPU
+    and clamped by the kernel on the device, as the plan of ``assemble_clips``."""
+    R, rec_off, rec_len = _recordings(store, rec_off, rec_len, "clip_peaks")
+    require_hip(store, "clip_peaks")
+    dev = store.device
+    peaks = torch.empty(R, dtype=torch.float32, device=dev)
+    if R:
+        _call(dev, "leaf_clip_peaks_f32", store.detach().contiguous(), store.numel(), FLAG_X_PCM16 if store.dtype == torch.int16 else 0, R,
+              rec_off.to(device=dev, dtype=torch.int64).contiguous(), rec_len.to(device=dev, dtype=torch.int32).contiguous(), peaks,
+              ws=lambda lib: lib.leaf_clip_peaks_workspace_bytes(R))
+    return peaks
+
+
+def assemble_segments(store: torch.Tensor, rec_off, rec_len, win, size: int, peaks: Optional[torch.Tensor] = None, rec=None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rows (rows, 1, size), float32, cut from whole recordings in one launch (leaf_assemble_segments_f32): row b is the window of
+    ``size`` samples that starts at sample ``win[b]`` of the recording ``store[rec_off[b] : rec_off[b] + rec_len[b]]`` -- before it,
+    inside it or behind it -- filled by replication outside the recording (F.pad 'replicate'); a recording of no samples gives zeros.
+    With ``peaks`` ((R,) float32 on the store's device, ``clip_peaks``) and ``rec`` (the row's entry of it) a row is divided by its
+    RECORDING's peak where that exceeds 1 -- ``peak_normalize`` on the whole recording, then the cut.  Arrays on the CPU are validated
+    and copied over; on the device they are used as they are and clamped by the kernel."""
+    size = int(size)
+    rows, rec_off, rec_len = _recordings(store, rec_off, rec_len, "assemble_segments", size)
+    win = _plan_ints(win, "win", rows)                                          # (any start is a valid window)
+    if peaks is not None:
+        if rec is None:
+            raise ValueError("assemble_segments: peaks needs rec, the entry of peaks each row scales by")
+        rec = _plan_ints(rec, "rec", rows)
+        if peaks.dim() != 1 or peaks.numel() < 1:
+            raise ValueError(f"peaks must be a 1-D tensor of at least one entry, got {tuple(peaks.shape)}")
+        if rec.device.type == "cpu" and rows and (int(rec.min()) < 0 or int(rec.max()) >= peaks.numel()):
+            raise ValueError(f"rec holds an entry outside [0, {peaks.numel()})")
+    require_hip(store, "assemble_segments")
+    dev = store.device
+    if peaks is not None:
+        peaks = _dev_f32(peaks, "peaks", dev)
+    if out is not None:
+        _check_out(out, (rows, 1, size), torch.float32, dev)
+    else:
+        out = torch.empty((rows, 1, size), dtype=torch.float32, device=dev)
+    if rows == 0:
+        return out
+    _call(dev, "leaf_assemble_segments_f32", store.detach().contiguous(), store.numel(), FLAG_X_PCM16 if store.dtype == torch.int16 else 0,
+          rows, size, rec_off.to(device=dev, dtype=torch.int64).contiguous(), rec_len.to(device=dev, dtype=torch.int32).contiguous(),
+          win.to(device=dev, dtype=torch.int64).contiguous(), _ptr(peaks),
+          None if peaks is None else rec.to(device=dev, dtype=torch.int32).contiguous(), 0 if peaks is None else peaks.numel(), out)
     return out
 
 

@@ -83,3 +83,56 @@ int leaf_gaussian_noise_f32(int B, int size, unsigned long long seed, const long
     if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
     return LEAF_OK;
 }
+
+// max |r_i| per recording: the tile prefix (one workgroup), then the tiles (two launches, one call per dataset)
+size_t leaf_clip_peaks_workspace_bytes(int R) { return R < 1 ? 0 : sizeof(long long) * ((size_t)R + 1); }
+
+int leaf_clip_peaks_f32(const void* store, long long store_len, int flags, int R, const long long* rec_off, const int* rec_len,
+                        float* peaks, void* workspace, size_t workspace_bytes, void* stream) {
+    if (flags & ~LEAF_FLAG_X_PCM16) return LEAF_ERR_UNSUPPORTED;
+    if (!store || !rec_off || !rec_len || !peaks) return LEAF_ERR_NULL_POINTER;
+    if (R < 1 || store_len < 0) return LEAF_ERR_BAD_SHAPE;
+    const bool pcm = (flags & LEAF_FLAG_X_PCM16) != 0;
+    auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (misaligned(store, pcm ? 1u : 3u) || misaligned(rec_off, 7u) || misaligned(rec_len, 3u) || misaligned(peaks, 3u) || misaligned(workspace, 15u))
+        return LEAF_ERR_ALIGNMENT;
+    if (!workspace || workspace_bytes < leaf_clip_peaks_workspace_bytes(R)) return LEAF_ERR_WORKSPACE;
+    PeakParams p{};
+    p.store = store; p.store_len = store_len; p.rec_off = rec_off; p.rec_len = rec_len; p.peaks = peaks;
+    p.tile_start = static_cast<long long*>(workspace); p.R = R;
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(clip_peaks_plan_kernel, dim3(1), dim3(kClipThreads), 0, st, p);
+    // the host does not see the plan: recordings that do not overlap have at most R + store_len / tile tiles, and a plan with more
+    // is walked by the same waves
+    const long long tiles = (long long)R + store_len / kPeakTile, per_block = kPeakThreads / 64;
+    const long long blocks = std::min<long long>((tiles + per_block - 1) / per_block, kPeakMaxBlocks);
+    if (pcm) hipLaunchKernelGGL(clip_peaks_kernel<true>, dim3((unsigned)blocks), dim3(kPeakThreads), 0, st, p);
+    else hipLaunchKernelGGL(clip_peaks_kernel<false>, dim3((unsigned)blocks), dim3(kPeakThreads), 0, st, p);
+    if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
+    return LEAF_OK;
+}
+
+// the rows of whole recordings, test.py's pad_input: one launch of rows x tiles workgroups
+int leaf_assemble_segments_f32(const void* store, long long store_len, int flags, int rows, int size, const long long* rec_off,
+                               const int* rec_len, const long long* win, const float* peaks, const int* rec, int R, float* out,
+                               void* stream) {
+    if (flags & ~LEAF_FLAG_X_PCM16) return LEAF_ERR_UNSUPPORTED;
+    if (!store || !rec_off || !rec_len || !win || !out || (peaks && !rec)) return LEAF_ERR_NULL_POINTER;
+    if (rows < 1 || size < 1 || store_len < 0 || (peaks && R < 1)) return LEAF_ERR_BAD_SHAPE;
+    const long long chunks = ((long long)size + 3 + 3) >> 2;              // at the worst row shift
+    const long long tiles = (chunks + kClipChunks * kClipThreads - 1) / (kClipChunks * kClipThreads);
+    if ((long long)rows * tiles > 0x7fffffffll) return LEAF_ERR_BAD_SHAPE;
+    const bool pcm = (flags & LEAF_FLAG_X_PCM16) != 0;
+    auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (misaligned(store, pcm ? 1u : 3u) || misaligned(rec_off, 7u) || misaligned(rec_len, 3u) || misaligned(win, 7u) ||
+        misaligned(peaks, 3u) || misaligned(rec, 3u) || misaligned(out, 3u))
+        return LEAF_ERR_ALIGNMENT;
+    SegmentParams p{};
+    p.store = store; p.store_len = store_len; p.rec_off = rec_off; p.rec_len = rec_len; p.win = win;
+    p.peaks = peaks; p.rec = rec; p.out = out; p.R = R; p.S = size; p.tiles = (int)tiles;
+    const dim3 grid((unsigned)(rows * tiles)), block(kClipThreads);
+    if (pcm) hipLaunchKernelGGL(assemble_segments_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(assemble_segments_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
+    return LEAF_OK;
+}

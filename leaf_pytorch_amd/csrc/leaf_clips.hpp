@@ -44,8 +44,13 @@
 //
 // The two plain instances keep the kernel text they had (assemble_clips_kernel below, untouched: the same instructions as before the
 // noise instances existed); assemble_clips_noise_kernel restates the body over clip_view / clip_min_pass.
+//
+// Whole-recording evaluation (leaf_clip_peaks_f32, leaf_assemble_segments_f32) is at the end of the file: the recordings' peaks in
+// wave-sized tiles, and rows cut from a recording by a window that may begin before it or end behind it, split over workgroups.
+// Their clamped plan is leaf_segments_view.hpp (host and device).
 #pragma once
 #include "leaf_common.hpp"
+#include "leaf_segments_view.hpp"
 
 namespace {
 
@@ -488,6 +493,150 @@ __global__ __launch_bounds__(256) void gaussian_noise_kernel(int size, int tiles
 #pragma unroll
     for (int e = 0; e < 4; ++e)
         if (t0 + e < size) o[e] = z[e];
+}
+
+// ---- whole-recording evaluation (include/leaf_hip.h: leaf_clip_peaks_f32, leaf_assemble_segments_f32) -------------------------------
+// test.py cuts every recording into ceil(L / S) rows of S samples after ONE peak normalisation over the whole recording and a
+// 'replicate' padding split left = (P - L) / 2.  Two pieces: the recordings' peaks, once per dataset, and the rows themselves.
+
+// leaf_clip_peaks_f32.  The work unit is a wave and a tile of kPeakTile samples of one recording: a long recording is many tiles
+// (spread over the chip), a short one is one wave's reduction of 64 lanes.  Stage 1 (one workgroup) counts each clamped recording's
+// tiles into the exclusive prefix `tile_start` and zeroes the peaks; stage 2 gives every wave a contiguous run of tiles -- one
+// binary search, then a walk -- and folds a recording's share into peaks[i] with an INTEGER max on the bit pattern, which orders
+// non-negative floats as the floats themselves (no float atomic; max is exact in any order).
+constexpr int kPeakThreads = 256;
+constexpr int kPeakChunks = 4;                                            // loads of four samples a lane has in flight
+constexpr int kPeakTile = kPeakChunks * 4 * 64;                           // 1024 samples
+constexpr int kPeakMaxBlocks = 2048;                                      // 8 workgroups per CU; the tiles beyond are walked
+
+struct PeakParams {
+    const void* store;
+    long long store_len;
+    const long long* rec_off;     // [R]
+    const int* rec_len;           // [R]
+    float* peaks;                 // [R]
+    long long* tile_start;        // [R + 1] workspace
+    int R;
+};
+
+__global__ __launch_bounds__(kClipThreads) void clip_peaks_plan_kernel(const PeakParams p) {
+    __shared__ long long wsum[kClipThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    long long carry = 0;                                                  // tiles of the recordings before this round's
+    for (long long base = 0; base < p.R; base += kClipThreads) {
+        const long long i = base + tid;
+        long long n = 0;
+        if (i < p.R) {
+            n = ((long long)recording_view(p.rec_off[i], p.rec_len[i], p.store_len).L + kPeakTile - 1) / kPeakTile;
+            p.peaks[i] = 0.0f;
+        }
+        long long s = n;                                                  // inclusive scan over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const long long o = __shfl_up(s, d);
+            if (lane >= d) s += o;
+        }
+        if (lane == 63) wsum[wave] = s;
+        __syncthreads();
+        long long before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kClipThreads / 64; ++w) {
+            const long long x = wsum[w];
+            if (w < wave) before += x;
+            total += x;
+        }
+        if (i < p.R) p.tile_start[i] = carry + before + s - n;
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) p.tile_start[p.R] = carry;
+}
+
+template <bool PCM>
+__global__ __launch_bounds__(kPeakThreads) void clip_peaks_kernel(const PeakParams p) {
+    const int lane = threadIdx.x & 63;
+    const long long total = p.tile_start[p.R];
+    const long long waves = (long long)gridDim.x * (kPeakThreads / 64), w = (long long)blockIdx.x * (kPeakThreads / 64) + (threadIdx.x >> 6);
+    const long long per = (total + waves - 1) / waves;
+    long long t = w * per;                                                // this wave's tiles: [t, end)
+    const long long end = t + per < total ? t + per : total;
+    if (t >= end) return;
+    int i = 0;                                                            // the LAST i with tile_start[i] <= t: the recording tile t belongs to
+    for (int hi = p.R; hi - i > 1;) {                                     // tile_start[i] <= t < tile_start[hi]
+        const int mid = i + (hi - i) / 2;
+        if (p.tile_start[mid] <= t) i = mid; else hi = mid;
+    }
+    while (t < end) {
+        const long long first = p.tile_start[i], next = p.tile_start[i + 1];   // first <= t < next
+        const long long stop = next < end ? next : end;
+        const SegmentView r = recording_view(p.rec_off[i], p.rec_len[i], p.store_len);
+        float m = 0.0f;
+        for (; t < stop; ++t) {
+            const long long j0 = (t - first) * kPeakTile + 4 * lane;
+            float v[kPeakChunks][4];
+#pragma unroll
+            for (int u = 0; u < kPeakChunks; ++u) {
+                const long long j = j0 + u * (4 * 64);
+                if (j + 4 <= r.L) {                                      // one load at element alignment, as clip_chunk_load
+                    if constexpr (PCM) {
+                        const s16x4u s = *reinterpret_cast<const s16x4u*>(static_cast<const short*>(p.store) + (r.off + j));
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[u][e] = pcm16_widen(s[e]);
+                    } else {
+                        const f32x4u s = *reinterpret_cast<const f32x4u*>(static_cast<const float*>(p.store) + (r.off + j));
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[u][e] = s[e];
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[u][e] = j + e < r.L ? clip_load<PCM>(p.store, r.off + j + e) : 0.0f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kPeakChunks; ++u) m = clip_chunk_peak(m, v[u]);   // (fmaxf: a NaN sample is ignored)
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+        if (lane == 0 && m > 0.0f) atomicMax(reinterpret_cast<unsigned*>(p.peaks + i), __float_as_uint(m));
+        if (t < end)                                                      // t == next: the following recording that has a tile
+            do ++i; while (p.tile_start[i + 1] <= t);
+    }
+}
+
+// leaf_assemble_segments_f32.  Nothing is reduced, so a row is split freely: grid = rows x tiles, a tile the eight chunks per lane
+// of the resident path above, on the same chunk grid aligned in `out` and through the same loads.  The row is a ClipView in
+// 'replicate' mode whose `left` is minus the (clamped) window start; all row indices are 64-bit.
+struct SegmentParams {
+    const void* store;
+    long long store_len;
+    const long long* rec_off;     // [rows]
+    const int* rec_len;           // [rows]
+    const long long* win;         // [rows]
+    const float* peaks;           // [R] or null
+    const int* rec;               // [rows]
+    float* out;                   // [rows][S]
+    int R, S, tiles;
+};
+
+template <bool PCM>
+__global__ __launch_bounds__(kClipThreads) void assemble_segments_kernel(const SegmentParams p) {
+    const int b = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles, S = p.S;
+    float* ob = p.out + (size_t)b * S;
+    const SegmentView sv = segment_view(p.rec_off[b], p.rec_len[b], p.win[b], p.store_len, S);
+    ClipView c;
+    c.off = sv.off; c.L = sv.L; c.left = sv.left;
+    c.mode = sv.L > 0 ? 2 : 0;                                            // no samples: zeros
+    c.padv = 0.0f; c.has_gain = false; c.g = 1.0f;
+    const float peak = p.peaks ? p.peaks[segment_peak_index(p.rec[b], p.R)] : 0.0f;   // the RECORDING's peak, not the row's
+    const int shift = (int)((reinterpret_cast<uintptr_t>(ob) >> 2) & 3);  // row elements the first aligned chunk lacks
+    const long long nchunks = ((long long)S + shift + 3) >> 2;
+    const long long q0 = (long long)tile * (kClipChunks * kClipThreads) + threadIdx.x;
+    if (q0 >= nchunks) return;                                            // (no barrier in this kernel)
+    ClipParams cp{};                                                      // what clip_tile_finish reads: the row size, no masks
+    cp.S = S;
+    float v[kClipChunks][4];
+    clip_tile_load<PCM, long long, kClipChunks>(p.store, c, S, shift, q0, nchunks, v);
+    clip_tile_finish<long long, kClipChunks>(cp, b, shift, q0, nchunks, peak, v, ob);
 }
 
 }  // namespace

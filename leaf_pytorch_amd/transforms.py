@@ -87,8 +87,13 @@ class PackedClips:
     AddGaussianNoise, the library's own counter-based normal stream (``_native.gaussian_noise``) scaled and added behind it -- both
     in front of the peak normalisation, as in the reference's pipelines.
 
+    Evaluation as the reference's test.py does it -- whole recordings, one peak per recording, cut into rows -- is ``segments``
+    (leaf_assemble_segments_f32) with ``peaks`` (leaf_clip_peaks_f32) behind it; ``segment_mean`` and ``evaluate_recordings`` finish
+    the loop.
+
     One workgroup assembles one clip: a batch of a few very long clips uses a few CUs (splitting a clip over workgroups is not
-    built).  Not built either: bfloat16 stores, outputs in anything but float32, a noise store of another dtype than the clips'."""
+    built; the rows of ``segments`` are split).  Not built either: bfloat16 stores, outputs in anything but float32, a noise store
+    of another dtype than the clips'."""
 
     def __init__(self, recordings, device=None):
         recs = [r if isinstance(r, torch.Tensor) else torch.as_tensor(r) for r in recordings]
@@ -121,6 +126,7 @@ class PackedClips:
         self.store = store.contiguous()
         self.offsets_host, self.lengths_host = offsets.to(torch.int64), lengths.to(torch.int32)
         self.offsets, self.lengths = self.offsets_host.to(store.device), self.lengths_host.to(store.device)
+        self._peaks = None                                                      # peaks(): computed on the first call, then kept
 
     def __len__(self) -> int:
         return self.lengths_host.numel()
@@ -190,6 +196,122 @@ class PackedClips:
         return _native.assemble_clips(self.store, rec_off, rec_len, self._per_clip(start, B), self._per_clip(pad_mode, B, _native.PAD_MODES),
                                       size, gain, normalize, masks, out, noise=None if noise is None else self._noise(noise, B),
                                       gaussian=gaussian)
+
+    # ---- whole recordings, the way the reference's test.py evaluates them -----------------------------------------------------------
+
+    def peaks(self) -> torch.Tensor:
+        """``max |r_i|`` of every recording, ``(len(self),)`` float32 on the store's device (``_native.clip_peaks`` ->
+        leaf_clip_peaks_f32: exact, one call over all recordings, split by tiles of samples so that one long recording fills the
+        chip and many short ones cost a wave each).  Computed on the first call and kept: the store is taken as immutable after
+        construction (``refresh_peaks`` after writing into it)."""
+        if self._peaks is None:
+            self._peaks = _native.clip_peaks(self.store, self.offsets, self.lengths)
+        return self._peaks
+
+    def refresh_peaks(self) -> None:
+        """Drop the kept peaks; the next ``peaks()`` computes them again.  The store is taken as immutable after construction: a
+        caller that writes into ``store`` all the same calls this afterwards."""
+        self._peaks = None
+
+    def segment_plan(self, index, size: int):
+        """The integers of ``segments``, all on the CPU from ``lengths_host``: ``(counts, rec, win, left)``.  Recording
+        ``index[i]`` of L samples becomes ``counts[i] = ceil(L / size)`` rows; with ``P = counts[i] * size`` the reference's
+        pad_input pads ``left[i] = (P - L) // 2`` samples in front (and ``P - L - left[i]`` behind), so its row k starts at the
+        recording's sample ``win = k * size - left[i]``.  ``rec`` and ``win`` have one entry per row, recording after recording in
+        ``index`` order.  ``index`` is a sequence or a CPU tensor (the number of rows follows from it, and nothing is read back from
+        the device for it); a recording outside the store or an empty one raises ValueError."""
+        size = int(size)
+        if not 1 <= size < _native.CALL_SAMPLES:
+            raise ValueError(f"size must be in [1, 2^31), got {size}")
+        index = (index if isinstance(index, torch.Tensor) else torch.as_tensor(index, dtype=torch.int64)).reshape(-1)
+        if index.dtype.is_floating_point or index.dtype == torch.bool:
+            raise TypeError(f"index must be an integer tensor or sequence, got {index.dtype}")
+        if index.device.type != "cpu":
+            raise TypeError("segments takes its index on the CPU: the number of rows is host work on lengths_host")
+        if index.numel() and (int(index.min()) < 0 or int(index.max()) >= len(self)):
+            raise ValueError(f"index holds a recording outside [0, {len(self)})")
+        index = index.long()
+        L = self.lengths_host[index].long()
+        if bool((L == 0).any()):
+            raise ValueError("index names an empty recording: it has no rows (the reference's pad_input cannot pad it either)")
+        counts = (L + size - 1) // size
+        left = (counts * size - L) // 2
+        first = torch.cumsum(counts, 0) - counts
+        k = torch.arange(int(counts.sum())) - torch.repeat_interleave(first, counts)
+        return counts, torch.repeat_interleave(index, counts), k * size - torch.repeat_interleave(left, counts), left
+
+    def _segment_rows(self, rec: torch.Tensor, win: torch.Tensor, size: int, normalize: bool, out=None) -> torch.Tensor:
+        """The rows ``(rec, win)`` of a ``segment_plan`` in one launch.  An int16 store has no peak above 1: like
+        ``Leaf.fuse_peak_normalization`` for int16, nothing is scaled and ``peaks()`` is not launched."""
+        scaled = bool(normalize) and self.store.dtype == torch.float32 and rec.numel() > 0
+        # the four row arrays cross in ONE copy (they come from this object's own validated tables: nothing to check again)
+        plan = torch.stack((self.offsets_host[rec], self.lengths_host[rec].long(), win, rec)).to(self.store.device)
+        return _native.assemble_segments(self.store, plan[0], plan[1].to(torch.int32), plan[2], size,
+                                         self.peaks() if scaled else None, plan[3].to(torch.int32) if scaled else None, out)
+
+    def segments(self, index, size: int, normalize: bool = True, out=None):
+        """The evaluation batch of the reference's test.py for the recordings ``index`` (any order, repeats allowed), in ONE launch
+        (``_native.assemble_segments`` -> leaf_assemble_segments_f32): ``(batch, counts)``.  Per recording r of L samples test.py runs
+        ``PeakNormalization`` over the WHOLE recording (``normalize``; the peak comes from ``peaks()``), then ``pad_input`` --
+        ``n = ceil(L / size)``, ``F.pad(r, (left, n * size - L - left), 'replicate')`` with ``left = (n * size - L) // 2``,
+        ``reshape(-1, 1, size)``.  ``batch`` is the rows of all recordings behind one another, ``(sum n_i, 1, size)`` float32 as
+        ``Leaf.forward`` takes it, bit for bit what those stock ops give; ``counts`` the CPU int64 tensor of the ``n_i``
+        (``segment_mean(model(batch), counts)`` is test.py's ``torch.mean(preds, dim=0)`` per recording).  An empty ``index`` returns
+        ``(0, 1, size)`` and launches nothing; an empty recording raises ValueError."""
+        counts, rec, win, _ = self.segment_plan(index, size)
+        return self._segment_rows(rec, win, int(size), normalize, out), counts
+
+
+def _segment_sums(preds: torch.Tensor, counts) -> torch.Tensor:
+    """Sums over runs of ``counts[i]`` consecutive rows of ``preds``, in float64 (stock ops: one ``index_add_``).  float64 puts the
+    order of the additions far below a float32 ulp of the result, and a NaN or infinity stays in its own recording."""
+    counts = torch.as_tensor(counts).reshape(-1).cpu().long()
+    if counts.numel() and int(counts.min()) < 1:
+        raise ValueError("every recording needs at least one row")
+    if int(counts.sum()) != preds.shape[0]:
+        raise ValueError(f"counts names {int(counts.sum())} rows, preds has {preds.shape[0]}")
+    sums = torch.zeros((counts.numel(),) + tuple(preds.shape[1:]), dtype=torch.float64, device=preds.device)
+    return sums.index_add_(0, torch.repeat_interleave(torch.arange(counts.numel()), counts).to(preds.device), preds.double())
+
+
+def _per_row(counts: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    return counts.to(like.device).double().reshape((-1,) + (1,) * (like.dim() - 1))
+
+
+def segment_mean(preds: torch.Tensor, counts) -> torch.Tensor:
+    """``(len(counts), ...)``: the mean over each recording's ``counts[i]`` consecutive rows of ``preds`` ``(sum counts, ...)`` --
+    test.py's ``torch.mean(preds, dim=0)`` for a batch of recordings (``PackedClips.segments``), in stock ops on the device ``preds``
+    is on, in its dtype.  The caller applies sigmoid / argmax to the mean, as test.py does."""
+    counts = torch.as_tensor(counts).reshape(-1).cpu().long()
+    sums = _segment_sums(preds, counts)
+    return (sums / _per_row(counts, sums)).to(preds.dtype)
+
+
+def evaluate_recordings(model, clips: PackedClips, size: int, index=None, max_rows: int = 512, normalize: bool = True) -> torch.Tensor:
+    """The evaluation loop of the reference's test.py over the recordings ``index`` of ``clips`` (default: all of them): ``(N, C)``,
+    per recording the mean of ``model``'s outputs over its rows, in ``index`` order; sigmoid / argmax are the caller's, as there.
+    Runs under ``torch.no_grad()`` (``model.eval()`` is the caller's).  Instead of test.py's one recording per forward, the rows of
+    consecutive recordings are packed into forwards of at most ``max_rows`` rows -- one ``segments`` launch and one ``model`` call
+    each; a recording that does not fit the rest of a forward, or has more rows than ``max_rows``, continues in the next one and its
+    sum is carried (in float64, as ``segment_mean`` sums)."""
+    max_rows = int(max_rows)
+    if max_rows < 1:
+        raise ValueError(f"max_rows must be at least 1, got {max_rows}")
+    counts, rec, win, _ = clips.segment_plan(torch.arange(len(clips)) if index is None else index, size)
+    if counts.numel() == 0:
+        raise ValueError("evaluate_recordings needs at least one recording")
+    place = torch.repeat_interleave(torch.arange(counts.numel()), counts)      # the row's recording, as its place in index
+    sums, dtype = None, None
+    with torch.no_grad():
+        for a in range(0, rec.numel(), max_rows):
+            b = min(rec.numel(), a + max_rows)
+            preds = model(clips._segment_rows(rec[a:b], win[a:b], int(size), normalize))
+            first, last = int(place[a]), int(place[b - 1])
+            part = _segment_sums(preds, torch.bincount(place[a:b] - first, minlength=last - first + 1))
+            if sums is None:
+                sums, dtype = torch.zeros((counts.numel(),) + tuple(part.shape[1:]), dtype=torch.float64, device=part.device), preds.dtype
+            sums[first:last + 1] += part
+        return (sums / _per_row(counts, sums)).to(dtype)
 
 
 class ClipPlan(tuple):

@@ -5,6 +5,7 @@ multiply by the gain, transforms.PeakNormalization, one masked_fill per span.
 
     python tools/bench_clips.py [--rounds 20] [--steps 50] [--out profiles/clip_assembly.txt]
     python tools/bench_clips.py --noise [--out profiles/clip_noise.txt]
+    python tools/bench_clips.py --segments [--out profiles/eval_segments.txt]
 
 Both sides run in ONE process on the same store and the same plan (already on the device: drawing it is not timed), taking turns
 round after round after a warm-up round, the order alternating.  Every recording is longer than the clip, so the batch is a crop
@@ -26,7 +27,15 @@ would write without the entry: index gather of the clip and of the noise, .float
 the gain, torch.randn scaled and added, transforms.PeakNormalization, one masked_fill per span.  torch.randn is not the library's
 stream, so the two sides are NOT compared bit for bit here (tests/test_gpu_clip_noise.py does that, on the library's own z); the
 stock side is checked against the kernel with the Gaussian amplitude at 0 instead.  A third column times the plain launch
-(leaf_assemble_clips_f32, the same clip plan without noise) in the same rounds: the cost of the augmented launch relative to it."""
+(leaf_assemble_clips_f32, the same clip plan without noise) in the same rounds: the cost of the augmented launch relative to it.
+
+--segments times the evaluation batch of whole recordings (leaf_assemble_segments_f32): 16 and 64 recordings of 1 - 10.3 s at 16 kHz cut
+into one-second rows the way the reference's test.py cuts them, both stores.  Three sides take turns: `kernel`, the one launch with its
+row plan already on the device; `segments`, PackedClips.segments as a user calls it (the plan made on the host from lengths_host and
+copied over: wall time only, its copies wait for the device); and `stock`, the reference loop restated in stock ops on the device --
+per recording transforms.PeakNormalization over the whole recording, F.pad(..., 'replicate'), reshape; then torch.cat.  The two
+batches are compared bit for bit before anything is timed.  The one-time PackedClips.peaks() launch (leaf_clip_peaks_f32 over the
+whole store; float32 stores only use it) is timed on its own, in rounds of its own, and reported in its own column."""
 import argparse
 import os
 import statistics
@@ -34,10 +43,11 @@ import sys
 import time
 
 import torch
+import torch.nn.functional as F
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-from leaf_pytorch_amd import PeakNormalization, _native  # noqa: E402
+from leaf_pytorch_amd import PackedClips, PeakNormalization, _native  # noqa: E402
 
 DEV = "cuda:0"
 M = 3                                                   # spans per clip, as TimeMasking(num_masks=3)
@@ -143,18 +153,83 @@ def noise_legs(args, busy, busy_out):
     return lines
 
 
+def segment_legs(args, busy, busy_out):
+    pn = PeakNormalization()
+    S = 16000
+    lines = [f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {args.rounds} timed rounds x {args.steps} calls per side after a "
+             "warm-up round; us per call: median [min, max]; device = HIP events, calls queued behind a matrix product; wall = host clock to a "
+             "synchronise; kernel = leaf_assemble_segments_f32 with the row plan on the device, segments = PackedClips.segments (plan made on the "
+             "host and copied), stock = per recording PeakNormalization + F.pad replicate + reshape, then cat; GB/s = (row samples read + 4 bytes "
+             "per row sample written) / median device time of the kernel; peaks = the one-time leaf_clip_peaks_f32 call over the whole store",
+             f"{'store':>8} {'N':>4} {'rows':>5} | {'kernel device':>24} {'kernel wall':>12} {'GB/s':>7} | {'segments wall':>13} | {'stock device':>26} "
+             f"{'stock wall':>11} | {'stock / kernel':>14} | {'peaks device':>24} {'peaks wall':>11}"]
+    for dtype in (torch.int16, torch.float32):
+        for N in (16, 64):
+            g = torch.Generator().manual_seed(N)
+            lengths = torch.randint(S, 164801, (N,), generator=g).tolist()                  # 1 s .. 10.3 s
+            recs = [(torch.rand(n, generator=g) * 2 - 1) * (1.5 if i % 2 else 0.5) for i, n in enumerate(lengths)]
+            if dtype == torch.int16:
+                recs = [(r.clamp(-1, 1) * 32767).to(torch.int16) for r in recs]
+            pc = PackedClips(recs, device=DEV)
+            index = list(range(N))
+            counts, rec, win, _ = pc.segment_plan(index, S)
+            rows = int(counts.sum())
+            out = torch.empty((rows, 1, S), dtype=torch.float32, device=DEV)
+            peaks = pc.peaks() if dtype == torch.float32 else None
+            d_off, d_len = pc.offsets[rec.to(DEV)], pc.lengths[rec.to(DEV)]
+            d_win, d_rec = win.to(DEV), rec.to(device=DEV, dtype=torch.int32)
+            bounds = [(int(o), int(o) + int(n)) for o, n in zip(pc.offsets_host, pc.lengths_host)]
+
+            def kernel():
+                return _native.assemble_segments(pc.store, d_off, d_len, d_win, S, peaks, None if peaks is None else d_rec, out)
+
+            def segments():
+                return pc.segments(index, S, out=out)[0]
+
+            def stock():
+                parts = []
+                for (a, b), n in zip(bounds, counts.tolist()):
+                    r = pc.store[a:b]
+                    if dtype == torch.int16:
+                        r = r.float() / 32768
+                    r = pn(r[None])
+                    left = (n * S - (b - a)) // 2
+                    parts.append(F.pad(r[None], (left, n * S - (b - a) - left), "replicate").reshape(-1, 1, S))
+                return torch.cat(parts)
+
+            def whole_store_peaks():
+                pc.refresh_peaks()
+                return pc.peaks()
+
+            a, b, c = kernel().clone(), stock(), segments().clone()
+            torch.cuda.synchronize()
+            if not (torch.equal(a.view(torch.int32), b.view(torch.int32)) and torch.equal(a.view(torch.int32), c.view(torch.int32))):
+                sys.exit(f"the sides disagree at {dtype} N={N}: nothing is timed")
+            dev_us, wall_us = time_sides({"kernel": kernel, "segments": segments, "stock": stock}, args.rounds, args.steps, busy, busy_out)
+            pdev, pwall = time_sides({"peaks": whole_store_peaks}, args.rounds, args.steps, busy, busy_out)
+            fmt = lambda v: f"{statistics.median(v):9.1f} [{min(v):6.1f},{max(v):7.1f}]"
+            kd, sd = statistics.median(dev_us["kernel"]), statistics.median(dev_us["stock"])
+            nbytes = rows * S * (pc.store.element_size() + 4)
+            lines.append(f"{str(dtype).replace('torch.', ''):>8} {N:>4} {rows:>5} | {fmt(dev_us['kernel'])} {statistics.median(wall_us['kernel']):12.1f} "
+                         f"{nbytes / kd / 1e3:7.1f} | {statistics.median(wall_us['segments']):13.1f} | {fmt(dev_us['stock']):>26} "
+                         f"{statistics.median(wall_us['stock']):11.1f} | {sd / kd:14.2f} | {fmt(pdev['peaks'])} {statistics.median(pwall['peaks']):11.1f}")
+            print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--out", default=None)
     ap.add_argument("--noise", action="store_true", help="time the launch with background and Gaussian noise (profiles/clip_noise.txt)")
+    ap.add_argument("--segments", action="store_true", help="time the whole-recording evaluation batch (profiles/eval_segments.txt)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_clips.py needs the GPU: a time taken anywhere else says nothing about it")
-    if args.noise:
+    if args.noise or args.segments:
         busy = torch.rand(8192, 8192, device=DEV)
-        text = "\n".join(noise_legs(args, busy, torch.empty_like(busy))) + "\n"
+        text = "\n".join((segment_legs if args.segments else noise_legs)(args, busy, torch.empty_like(busy))) + "\n"
         print(text)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
