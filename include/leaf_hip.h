@@ -772,6 +772,90 @@ int leaf_assemble_segments_f32(const void* store, long long store_len, int flags
                                const int* rec_len, const long long* win, const float* peaks /*[R] or NULL*/, const int* rec, int R,
                                float* out /*[rows][size]*/, void* stream);
 
+/* Waveform standardisation in the assembly launches (additive: the ABI version stays 6).  The reference's RawAudioParser with
+ * audio_config.normalize (utilities/data/raw_waveform_parser.py:16-23) maps the WHOLE recording r of L samples, as loaded and in
+ * front of every other transform, to (r - mean) / (std + 1e-9), std torch's unbiased one.  A clip cut from such a recording depends
+ * on samples outside the clip, so the step cannot be appended by the caller: the recordings' moments are computed once per dataset
+ * (leaf_clip_moments_f32), and two entries apply the map inside the launches of the entries above.  "Recording" always means the
+ * recording as packed in the store.
+ *
+ * leaf_clip_moments_f32: moments[i] = (mean_i, std_i, min_i, max_i), four float32 per recording, for all R recordings in one call.
+ *   mean_i = fp32(sum r / L), the sum in float64;
+ *   std_i  = fp32(sqrt(sum (r - m)^2 / (L - 1))), evaluated in float64, m the float64 mean BEFORE its rounding: two passes over the
+ *            samples, not sum r^2 - (sum r)^2 / L;
+ *   min_i, max_i: exact.  An int16 sample v means v / 32768, as everywhere.
+ *   L == 1: std = NaN (0 / 0, as torch);  L == 0: (0, NaN, 0, 0).  A NaN sample makes the mean and the std NaN -- nothing is ignored,
+ *   the recording standardises to NaN as in the reference; min and max skip NaN samples (fminf / fmaxf; a recording of NaNs alone
+ *   gives +inf, -inf), which no result depends on behind a NaN mean.
+ * THE ORDER OF THE ADDITIONS is fixed by L alone: the recording's tiles of 1024 samples are dealt to 32 spans of
+ * ceil(ceil(L / 1024) / 32) consecutive tiles; one wave sums one span -- every lane its samples 4 lane + 256 u + 1024 t + e in
+ * index order, then a butterfly over the 64 lanes -- into the span's slot of the workspace, and one lane folds the 32 slots in slot
+ * order.  No atomics: the result does not depend on the grid, on the store's alignment, on the other recordings or on the run.
+ * Four launches (partials and fold, for the sum and for the squared deviations); the float64 means are kept in the workspace between
+ * them.
+ *
+ *   store, store_len, flags, R, rec_off, rec_len: as in leaf_clip_peaks_f32          moments [R][4] float32, out
+ *   workspace: leaf_clip_moments_workspace_bytes(R) = 520 R bytes (32 slots of 16 bytes and one float64 per recording; 0 for
+ *   R < 1), overwritten
+ *
+ * MEMORY SAFETY: rec_off and rec_len are clamped exactly as in leaf_clip_peaks_f32: nothing outside store[0, store_len) is read,
+ * nothing outside moments[R][4] and the workspace is written.  Alignment: store 4 bytes (2 for int16), rec_off 8, rec_len and
+ * moments 4, workspace 16.  Status, in this order, before any launch: LEAF_ERR_UNSUPPORTED for a flag other than LEAF_FLAG_X_PCM16;
+ * LEAF_ERR_NULL_POINTER (store, rec_off, rec_len, moments); LEAF_ERR_BAD_SHAPE for R < 1 or store_len < 0; LEAF_ERR_ALIGNMENT;
+ * LEAF_ERR_WORKSPACE for a workspace that is NULL or below the size query. */
+size_t leaf_clip_moments_workspace_bytes(int R);
+int leaf_clip_moments_f32(const void* store, long long store_len, int flags, int R, const long long* rec_off /*[R]*/,
+                          const int* rec_len /*[R]*/, float* moments /*[R][4]*/, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
+/* leaf_assemble_clips_std_f32: leaf_assemble_clips_noise_f32 on the standardised recording.  The arguments of that entry up to
+ * gauss_stream come first and mean what they mean there; `stream` stays last.  Between them the standardisation group:
+ *
+ *   moments      [R][4] float32 (leaf_clip_moments_f32)
+ *   moments_rec  [B] int32: clip b's row of moments, i.e. the recording its rec_off / rec_len name          R: rows of moments
+ *
+ * The group is given or NULL as a whole (in part: LEAF_ERR_NULL_POINTER); with it NULL the call IS leaf_assemble_clips_noise_f32
+ * (and without that entry's groups, leaf_assemble_clips_f32).  With i = clamp(moments_rec[b], 0, R - 1):
+ *   0.  d = rn(std_i + 1e-9f), one fp32 add per clip; every sample v of the clip's recording becomes y = rn(rn(v - mean_i) / d): one
+ *       fp32 subtraction and one CORRECTLY ROUNDED fp32 division per sample -- no reciprocal multiply, no contraction.  This is bit
+ *       for bit (r - mean) / (std + 1e-9) evaluated by torch in float32 on 0-d float32 tensors holding moments[i];
+ *   1.  pad and crop, on the standardised samples.  Mode 1 ('min') pads with rn(rn(min_i - mean_i) / d), the minimum of the
+ *       standardised recording exactly (the map is monotone in fp32); mode 0 still pads with 0; modes 2 and 3 are index rules;
+ *   1a. .. 4. as in leaf_assemble_clips_noise_f32.  The NOISE recording is not standardised (the reference builds its noise generator
+ *       with normalize_waveform=False).  The peak normalisation of step 3 is live for an int16 store too: standardised samples
+ *       leave [-1, 1].
+ * The map is applied where a sample is loaded, on the resident and on the re-reading path alike (the same bits on both).  A clip
+ * whose std is NaN (L == 1) or whose recording holds a NaN is NaN throughout, as in the reference.
+ *
+ * MEMORY SAFETY: as leaf_assemble_clips_noise_f32, and moments_rec is clamped into [0, R - 1]: nothing outside moments[R][4] is read.
+ * Alignment: moments and moments_rec 4 bytes.  Status, in that entry's order (moments / moments_rec among the pointers, R < 1 among
+ * the shapes), before any launch. */
+int leaf_assemble_clips_std_f32(const void* store, long long store_len, int flags, int B, int size, const long long* rec_off,
+                                const int* rec_len, const int* start, const int* pad_mode, const float* gain, int normalize,
+                                const int* masks, int M, float* out, const void* noise_store, long long noise_store_len,
+                                const long long* noise_off, const int* noise_len, const int* noise_start, const int* noise_pad_mode,
+                                const float* noise_coeff /*[B][2]*/, const float* gauss_amp, unsigned long long gauss_seed,
+                                const long long* gauss_stream, const float* moments /*[R][4]*/, const int* moments_rec /*[B]*/, int R,
+                                void* stream);
+
+/* leaf_assemble_segments_std_f32: leaf_assemble_segments_f32 on the standardised recording -- the parser in front of test.py's
+ * PeakNormalization and pad_input.  The arguments of that entry up to `out` come first; behind `out`:
+ *
+ *   moments   [R][4] float32 or NULL; NULL: the call IS leaf_assemble_segments_f32 (normalize is not read)
+ *   normalize 0 / 1: PeakNormalization over the whole standardised recording
+ *
+ * With moments, `rec` [rows] and R name the rows' entries of MOMENTS (rec is required), and peaks must be NULL
+ * (LEAF_ERR_UNSUPPORTED: the raw recording's peak has no place behind the map).  For row b, i = clamp(rec[b], 0, R - 1):
+ *   1. v = r[clamp(win[b] + t, 0, L - 1)], y = rn(rn(v - mean_i) / d), d = rn(std_i + 1e-9f) (replication commutes with the map);
+ *      L == 0 gives zeros;
+ *   2. normalize != 0: p = max(|rn(rn(min_i - mean_i) / d)|, |rn(rn(max_i - mean_i) / d)|), the peak of the standardised recording
+ *      exactly (monotone map); p > 1 gives y * (1 / p), the arithmetic of leaf_peak_normalize_f32.  An int16 store is scaled too.
+ * MEMORY SAFETY, alignment (moments 4 bytes) and status as leaf_assemble_segments_f32, with LEAF_ERR_UNSUPPORTED also for
+ * peaks != NULL, rec among the required pointers and R < 1 among the shapes. */
+int leaf_assemble_segments_std_f32(const void* store, long long store_len, int flags, int rows, int size, const long long* rec_off,
+                                   const int* rec_len, const long long* win, const float* peaks /*NULL*/, const int* rec, int R,
+                                   float* out /*[rows][size]*/, const float* moments /*[R][4] or NULL*/, int normalize, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,19 @@ _SIGNATURES = {
     # ... and the rows: store, store_len, flags, rows, size, rec_off, rec_len, win, peaks, rec, R, out, stream
     "leaf_assemble_segments_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int]
                                    + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    # waveform standardisation.  The moments: store, store_len, flags, R, rec_off, rec_len, moments, workspace, workspace_bytes, stream
+    "leaf_clip_moments_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "leaf_clip_moments_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4
+                              + [ctypes.c_size_t, ctypes.c_void_p]),
+    # ... the noise entry with the group (moments, moments_rec, R) between gauss_stream and stream
+    "leaf_assemble_clips_std_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
+                                    + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+                                    + [ctypes.c_void_p, ctypes.c_longlong] + [ctypes.c_void_p] * 5
+                                    + [ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_void_p]
+                                    + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    # ... and the rows entry with (moments, normalize) between out and stream
+    "leaf_assemble_segments_std_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+                                       + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "leaf_fft_tables_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "leaf_fft_prepare_tables_f32": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_size_t, ctypes.c_void_p]),
@@ -1093,8 +1106,26 @@ def gaussian_noise(B: int, size: int, seed: int, stream, out: Optional[torch.Ten
     return out
 
 
+def _moments_group(standardize, B: int, store: torch.Tensor, who: str):
+    """The standardisation group (moments (R, 4) float32 on the store's device, rec: one row of it per clip) checked as the host can
+    see it: shapes and dtypes wherever the arrays live, the range of a ``rec`` that arrives on the CPU (ValueError)."""
+    if len(standardize) != 2:
+        raise ValueError(f"{who}: standardize must be (moments, rec)")
+    moments, rec = standardize
+    if not isinstance(moments, torch.Tensor) or moments.dim() != 2 or moments.shape[1] != 4 or moments.shape[0] < 1:
+        raise ValueError(f"{who}: moments must be an (R, 4) tensor of at least one row (clip_moments)")
+    if moments.dtype != torch.float32:
+        raise TypeError(f"{who}: moments must be float32, got {moments.dtype}")
+    if moments.device != store.device:
+        raise ValueError(f"{who}: moments is on {moments.device}, the store on {store.device}")
+    rec = _plan_ints(rec, "rec", B)
+    if rec.device.type == "cpu" and B and (int(rec.min()) < 0 or int(rec.max()) >= moments.shape[0]):
+        raise ValueError(f"rec holds an entry outside [0, {moments.shape[0]})")
+    return moments.detach().contiguous(), rec
+
+
 def assemble_clips(store: torch.Tensor, rec_off, rec_len, start, pad_mode, size: int, gain=None, normalize: bool = True, masks=None,
-                   out: Optional[torch.Tensor] = None, noise=None, gaussian=None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, noise=None, gaussian=None, standardize=None) -> torch.Tensor:
     """The batch (B, 1, size), float32, from a packed sample store in one launch (leaf_assemble_clips_f32, where the semantics are
     stated): per clip b the recording ``store[rec_off[b] : rec_off[b] + rec_len[b]]`` is padded to ``size`` if it is shorter
     (``pad_mode[b]``: PAD_ZERO / PAD_MIN / PAD_REPLICATE / PAD_WRAP, split left = padding // 2), cropped at ``start[b]``, multiplied by
@@ -1108,7 +1139,12 @@ def assemble_clips(store: torch.Tensor, rec_off, rec_len, start, pad_mode, size:
     noise recording padded and cropped to ``size`` by its own plan (``noise_plan`` / ``noise_coefficients``; the store of the clips'
     dtype and device).  ``gaussian`` = (amp (B,) float32, seed, stream (B,) int64) adds ``amp[b] * z(seed, stream[b], t)`` behind the
     gain (``gaussian_noise`` returns z); amplitude 0 leaves a clip alone.  Either makes the call leaf_assemble_clips_noise_f32 -- still
-    one launch; with neither the call is the one it always was."""
+    one launch; with neither the call is the one it always was.
+
+    ``standardize`` = (moments (R, 4) float32 from ``clip_moments``, rec: clip b's row of it) puts the reference's waveform
+    standardisation (RawAudioParser, ``audio_config.normalize``) in front of everything: every sample of the clip's recording becomes
+    ``(v - mean) / (std + 1e-9)`` in torch's float32 rounding, the 'min' padding is the standardised recording's minimum, the noise
+    recording stays as it is (leaf_assemble_clips_std_f32, one launch).  None: the call is the one above."""
     if not isinstance(store, torch.Tensor) or store.dim() != 1 or store.dtype not in (torch.float32, torch.int16):
         raise RuntimeError("assemble_clips: store must be a 1-D float32 or int16 tensor")
     size = int(size)
@@ -1124,6 +1160,8 @@ def assemble_clips(store: torch.Tensor, rec_off, rec_len, start, pad_mode, size:
         noise = (nstore,) + tuple(noise_plan(nstore.numel(), *noise[1:], size, B))
     if gaussian is not None:
         gaussian = _gaussian_plan(gaussian, B)
+    if standardize is not None:
+        standardize = _moments_group(standardize, B, store, "assemble_clips")
     require_hip(store, "assemble_clips")
     dev = store.device
     store = store.detach().contiguous()
@@ -1139,7 +1177,7 @@ def assemble_clips(store: torch.Tensor, rec_off, rec_len, start, pad_mode, size:
     masks = None if masks is None else masks.to(device=dev, dtype=torch.int32).contiguous()
     head = (store, store.numel(), FLAG_X_PCM16 if store.dtype == torch.int16 else 0, B, size,
             rec_off, rec_len, start, pad_mode, gain, int(bool(normalize)), masks, 0 if masks is None else masks.shape[1], out)
-    if noise is None and gaussian is None:
+    if noise is None and gaussian is None and standardize is None:
         _call(dev, "leaf_assemble_clips_f32", *head)
         return out
     ngroup, ggroup = (None, 0, None, None, None, None, None), (None, 0, None)
@@ -1149,7 +1187,11 @@ def assemble_clips(store: torch.Tensor, rec_off, rec_len, start, pad_mode, size:
             t.to(device=dev, dtype=torch.int32).contiguous() for t in noise[2:5]) + (noise[5].to(device=dev).contiguous(),)
     if gaussian is not None:
         ggroup = (gaussian[0].to(device=dev).contiguous(), gaussian[1], gaussian[2].to(device=dev, dtype=torch.int64).contiguous())
-    _call(dev, "leaf_assemble_clips_noise_f32", *head, *ngroup, *ggroup)
+    if standardize is None:
+        _call(dev, "leaf_assemble_clips_noise_f32", *head, *ngroup, *ggroup)
+        return out
+    moments, rec = standardize
+    _call(dev, "leaf_assemble_clips_std_f32", *head, *ngroup, *ggroup, moments, rec.to(device=dev, dtype=torch.int32).contiguous(), moments.shape[0])
     return out
 
 
@@ -1180,17 +1222,46 @@ def clip_peaks(store: torch.Tensor, rec_off, rec_len) -> torch.Tensor:
     return peaks
 
 
+def clip_moments(store: torch.Tensor, rec_off, rec_len) -> torch.Tensor:
+    """(mean, std, min, max) of every recording ``store[rec_off[i] : rec_off[i] + rec_len[i]]`` as an (R, 4) float32 tensor on the
+    store's device (leaf_clip_moments_f32): the mean and torch's unbiased std accumulated in float64 (two passes: the deviations are
+    taken from the float64 mean) and rounded once, min and max exact; an int16 sample v means v / 32768.  One sample gives std NaN, no
+    samples (0, NaN, 0, 0), a NaN sample a NaN mean and std.  The order of the additions depends on a recording's length alone: the
+    same bits on every call, whatever else the store holds.  The two arrays are validated on the CPU and clamped by the kernel on
+    the device, as in ``clip_peaks``."""
+    R, rec_off, rec_len = _recordings(store, rec_off, rec_len, "clip_moments")
+    require_hip(store, "clip_moments")
+    dev = store.device
+    moments = torch.empty((R, 4), dtype=torch.float32, device=dev)
+    if R:
+        _call(dev, "leaf_clip_moments_f32", store.detach().contiguous(), store.numel(), FLAG_X_PCM16 if store.dtype == torch.int16 else 0, R,
+              rec_off.to(device=dev, dtype=torch.int64).contiguous(), rec_len.to(device=dev, dtype=torch.int32).contiguous(), moments,
+              ws=lambda lib: lib.leaf_clip_moments_workspace_bytes(R))
+    return moments
+
+
 def assemble_segments(store: torch.Tensor, rec_off, rec_len, win, size: int, peaks: Optional[torch.Tensor] = None, rec=None,
-                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      out: Optional[torch.Tensor] = None, moments: Optional[torch.Tensor] = None, normalize: bool = True) -> torch.Tensor:
     """Rows (rows, 1, size), float32, cut from whole recordings in one launch (leaf_assemble_segments_f32): row b is the window of
     ``size`` samples that starts at sample ``win[b]`` of the recording ``store[rec_off[b] : rec_off[b] + rec_len[b]]`` -- before it,
     inside it or behind it -- filled by replication outside the recording (F.pad 'replicate'); a recording of no samples gives zeros.
     With ``peaks`` ((R,) float32 on the store's device, ``clip_peaks``) and ``rec`` (the row's entry of it) a row is divided by its
     RECORDING's peak where that exceeds 1 -- ``peak_normalize`` on the whole recording, then the cut.  Arrays on the CPU are validated
-    and copied over; on the device they are used as they are and clamped by the kernel."""
+    and copied over; on the device they are used as they are and clamped by the kernel.
+
+    With ``moments`` ((R, 4) float32, ``clip_moments``; ``rec`` is then the row's entry of IT and ``peaks`` must be None) the rows are
+    cut from the standardised recording ``(r - mean) / (std + 1e-9)`` (leaf_assemble_segments_std_f32), and ``normalize`` divides
+    them by the standardised recording's peak where that exceeds 1 -- the peak follows from min and max, nothing else is launched.
+    ``normalize`` is read only with ``moments``."""
     size = int(size)
     rows, rec_off, rec_len = _recordings(store, rec_off, rec_len, "assemble_segments", size)
     win = _plan_ints(win, "win", rows)                                          # (any start is a valid window)
+    if moments is not None:
+        if peaks is not None:
+            raise ValueError("assemble_segments: peaks and moments exclude each other (the standardised recording's peak comes from moments)")
+        if rec is None:
+            raise ValueError("assemble_segments: moments needs rec, the entry of moments each row is standardised by")
+        moments, rec = _moments_group((moments, rec), rows, store, "assemble_segments")
     if peaks is not None:
         if rec is None:
             raise ValueError("assemble_segments: peaks needs rec, the entry of peaks each row scales by")
@@ -1208,6 +1279,12 @@ def assemble_segments(store: torch.Tensor, rec_off, rec_len, win, size: int, pea
     else:
         out = torch.empty((rows, 1, size), dtype=torch.float32, device=dev)
     if rows == 0:
+        return out
+    if moments is not None:
+        _call(dev, "leaf_assemble_segments_std_f32", store.detach().contiguous(), store.numel(), FLAG_X_PCM16 if store.dtype == torch.int16 else 0,
+              rows, size, rec_off.to(device=dev, dtype=torch.int64).contiguous(), rec_len.to(device=dev, dtype=torch.int32).contiguous(),
+              win.to(device=dev, dtype=torch.int64).contiguous(), None, rec.to(device=dev, dtype=torch.int32).contiguous(), moments.shape[0], out,
+              moments, int(bool(normalize)))
         return out
     _call(dev, "leaf_assemble_segments_f32", store.detach().contiguous(), store.numel(), FLAG_X_PCM16 if store.dtype == torch.int16 else 0,
           rows, size, rec_off.to(device=dev, dtype=torch.int64).contiguous(), rec_len.to(device=dev, dtype=torch.int32).contiguous(),

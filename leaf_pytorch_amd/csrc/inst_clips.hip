@@ -72,6 +72,62 @@ int leaf_assemble_clips_noise_f32(const void* store, long long store_len, int fl
     return LEAF_OK;
 }
 
+// ... on the standardised recording.  The group (moments, moments_rec) is there or NULL as a whole; without it the call is the
+// entry above (which, without its own groups, is the plain one).
+int leaf_assemble_clips_std_f32(const void* store, long long store_len, int flags, int B, int size,
+                                const long long* rec_off, const int* rec_len, const int* start, const int* pad_mode,
+                                const float* gain, int normalize, const int* masks, int M, float* out,
+                                const void* noise_store, long long noise_store_len, const long long* noise_off, const int* noise_len,
+                                const int* noise_start, const int* noise_pad_mode, const float* noise_coeff,
+                                const float* gauss_amp, unsigned long long gauss_seed, const long long* gauss_stream,
+                                const float* moments, const int* moments_rec, int R, void* stream) {
+    if (!moments && !moments_rec)
+        return leaf_assemble_clips_noise_f32(store, store_len, flags, B, size, rec_off, rec_len, start, pad_mode, gain, normalize, masks, M, out,
+                                             noise_store, noise_store_len, noise_off, noise_len, noise_start, noise_pad_mode, noise_coeff,
+                                             gauss_amp, gauss_seed, gauss_stream, stream);
+    const bool any_noise = noise_store || noise_off || noise_len || noise_start || noise_pad_mode || noise_coeff;
+    const bool any_gauss = gauss_amp || gauss_stream;
+    if (flags & ~LEAF_FLAG_X_PCM16) return LEAF_ERR_UNSUPPORTED;
+    if (!store || !rec_off || !rec_len || !start || !pad_mode || !out) return LEAF_ERR_NULL_POINTER;
+    if (any_noise && !(noise_store && noise_off && noise_len && noise_start && noise_pad_mode && noise_coeff)) return LEAF_ERR_NULL_POINTER;
+    if (any_gauss && !(gauss_amp && gauss_stream)) return LEAF_ERR_NULL_POINTER;
+    if (!moments || !moments_rec) return LEAF_ERR_NULL_POINTER;
+    if (B < 1 || size < 1 || store_len < 0 || M < 0 || (M > 0 && !masks) || (any_noise && noise_store_len < 0) || R < 1) return LEAF_ERR_BAD_SHAPE;
+    const bool pcm = (flags & LEAF_FLAG_X_PCM16) != 0;
+    auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (misaligned(store, pcm ? 1u : 3u) || misaligned(rec_off, 7u) || misaligned(rec_len, 3u) || misaligned(start, 3u) ||
+        misaligned(pad_mode, 3u) || misaligned(gain, 3u) || misaligned(masks, 3u) || misaligned(out, 3u) ||
+        misaligned(noise_store, pcm ? 1u : 3u) || misaligned(noise_off, 7u) || misaligned(noise_len, 3u) || misaligned(noise_start, 3u) ||
+        misaligned(noise_pad_mode, 3u) || misaligned(noise_coeff, 3u) || misaligned(gauss_amp, 3u) || misaligned(gauss_stream, 7u) ||
+        misaligned(moments, 3u) || misaligned(moments_rec, 3u))
+        return LEAF_ERR_ALIGNMENT;
+    ClipParams p{};
+    p.store = store; p.store_len = store_len;
+    p.rec_off = rec_off; p.rec_len = rec_len; p.start = start; p.pad_mode = pad_mode;
+    p.gain = gain; p.masks = M > 0 ? masks : nullptr; p.out = out;
+    p.S = size; p.M = M; p.normalize = normalize != 0;
+    ClipNoiseParams np{};
+    np.store = noise_store; np.store_len = noise_store_len;
+    np.rec_off = noise_off; np.rec_len = noise_len; np.start = noise_start; np.pad_mode = noise_pad_mode; np.coeff = noise_coeff;
+    np.amp = gauss_amp; np.stream = gauss_stream; np.seed = gauss_seed;
+    ClipStdParams sp{};
+    sp.moments = moments; sp.rec = moments_rec; sp.R = R;
+    const dim3 grid(B), block(kClipThreads);
+    const hipStream_t st = (hipStream_t)stream;
+    switch ((pcm ? 4 : 0) | (any_noise ? 2 : 0) | (any_gauss ? 1 : 0)) {
+        case 0: hipLaunchKernelGGL((assemble_clips_std_kernel<false, false, false>), grid, block, 0, st, p, np, sp); break;
+        case 1: hipLaunchKernelGGL((assemble_clips_std_kernel<false, false, true>), grid, block, 0, st, p, np, sp); break;
+        case 2: hipLaunchKernelGGL((assemble_clips_std_kernel<false, true, false>), grid, block, 0, st, p, np, sp); break;
+        case 3: hipLaunchKernelGGL((assemble_clips_std_kernel<false, true, true>), grid, block, 0, st, p, np, sp); break;
+        case 4: hipLaunchKernelGGL((assemble_clips_std_kernel<true, false, false>), grid, block, 0, st, p, np, sp); break;
+        case 5: hipLaunchKernelGGL((assemble_clips_std_kernel<true, false, true>), grid, block, 0, st, p, np, sp); break;
+        case 6: hipLaunchKernelGGL((assemble_clips_std_kernel<true, true, false>), grid, block, 0, st, p, np, sp); break;
+        default: hipLaunchKernelGGL((assemble_clips_std_kernel<true, true, true>), grid, block, 0, st, p, np, sp); break;
+    }
+    if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
+    return LEAF_OK;
+}
+
 // the stream on its own: z[b][t] for t in [0, size), the values the entry above adds (times gauss_amp[b])
 int leaf_gaussian_noise_f32(int B, int size, unsigned long long seed, const long long* stream_ids, float* out, void* stream) {
     if (!stream_ids || !out) return LEAF_ERR_NULL_POINTER;
@@ -133,6 +189,73 @@ int leaf_assemble_segments_f32(const void* store, long long store_len, int flags
     const dim3 grid((unsigned)(rows * tiles)), block(kClipThreads);
     if (pcm) hipLaunchKernelGGL(assemble_segments_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(assemble_segments_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
+    return LEAF_OK;
+}
+
+// ... of the standardised recordings.  moments == NULL: the call is the entry above.
+int leaf_assemble_segments_std_f32(const void* store, long long store_len, int flags, int rows, int size, const long long* rec_off,
+                                   const int* rec_len, const long long* win, const float* peaks, const int* rec, int R, float* out,
+                                   const float* moments, int normalize, void* stream) {
+    if (!moments) return leaf_assemble_segments_f32(store, store_len, flags, rows, size, rec_off, rec_len, win, peaks, rec, R, out, stream);
+    if (flags & ~LEAF_FLAG_X_PCM16) return LEAF_ERR_UNSUPPORTED;
+    if (peaks) return LEAF_ERR_UNSUPPORTED;                               // the raw recording's peak has no place behind the map
+    if (!store || !rec_off || !rec_len || !win || !out || !rec) return LEAF_ERR_NULL_POINTER;
+    if (rows < 1 || size < 1 || store_len < 0 || R < 1) return LEAF_ERR_BAD_SHAPE;
+    const long long chunks = ((long long)size + 3 + 3) >> 2;              // at the worst row shift
+    const long long tiles = (chunks + kClipChunks * kClipThreads - 1) / (kClipChunks * kClipThreads);
+    if ((long long)rows * tiles > 0x7fffffffll) return LEAF_ERR_BAD_SHAPE;
+    const bool pcm = (flags & LEAF_FLAG_X_PCM16) != 0;
+    auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (misaligned(store, pcm ? 1u : 3u) || misaligned(rec_off, 7u) || misaligned(rec_len, 3u) || misaligned(win, 7u) ||
+        misaligned(rec, 3u) || misaligned(out, 3u) || misaligned(moments, 3u))
+        return LEAF_ERR_ALIGNMENT;
+    SegmentParams p{};
+    p.store = store; p.store_len = store_len; p.rec_off = rec_off; p.rec_len = rec_len; p.win = win;
+    p.peaks = nullptr; p.rec = rec; p.out = out; p.R = R; p.S = size; p.tiles = (int)tiles;
+    ClipStdParams sp{};
+    sp.moments = moments; sp.rec = rec; sp.R = R; sp.normalize = normalize != 0;
+    const dim3 grid((unsigned)(rows * tiles)), block(kClipThreads);
+    if (pcm) hipLaunchKernelGGL(assemble_segments_std_kernel<true>, grid, block, 0, (hipStream_t)stream, p, sp);
+    else hipLaunchKernelGGL(assemble_segments_std_kernel<false>, grid, block, 0, (hipStream_t)stream, p, sp);
+    if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
+    return LEAF_OK;
+}
+
+// mean, std, min, max per recording: two passes over the samples (sum; squared deviations from the float64 mean), each a launch of
+// span partials and a launch that folds them -- four launches, one call per dataset
+size_t leaf_clip_moments_workspace_bytes(int R) {
+    return R < 1 ? 0 : (sizeof(MomentPartial) * kMomentSpans + sizeof(double)) * (size_t)R;
+}
+
+int leaf_clip_moments_f32(const void* store, long long store_len, int flags, int R, const long long* rec_off, const int* rec_len,
+                          float* moments, void* workspace, size_t workspace_bytes, void* stream) {
+    if (flags & ~LEAF_FLAG_X_PCM16) return LEAF_ERR_UNSUPPORTED;
+    if (!store || !rec_off || !rec_len || !moments) return LEAF_ERR_NULL_POINTER;
+    if (R < 1 || store_len < 0) return LEAF_ERR_BAD_SHAPE;
+    const bool pcm = (flags & LEAF_FLAG_X_PCM16) != 0;
+    auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (misaligned(store, pcm ? 1u : 3u) || misaligned(rec_off, 7u) || misaligned(rec_len, 3u) || misaligned(moments, 3u) || misaligned(workspace, 15u))
+        return LEAF_ERR_ALIGNMENT;
+    if (!workspace || workspace_bytes < leaf_clip_moments_workspace_bytes(R)) return LEAF_ERR_WORKSPACE;
+    static_assert(sizeof(MomentPartial) == 16, "the workspace layout of include/leaf_hip.h");
+    MomentParams p{};
+    p.store = store; p.store_len = store_len; p.rec_off = rec_off; p.rec_len = rec_len; p.moments = moments;
+    p.part = static_cast<MomentPartial*>(workspace);
+    p.mean = reinterpret_cast<double*>(p.part + (size_t)R * kMomentSpans);
+    p.R = R;
+    const hipStream_t st = (hipStream_t)stream;
+    // a unit (one span of one recording) is one wave's; the units beyond the grid are walked by the same waves, and which wave takes
+    // a unit does not enter its partial
+    const long long units = (long long)R * kMomentSpans, per_block = kPeakThreads / 64;
+    const dim3 pass((unsigned)std::min<long long>((units + per_block - 1) / per_block, kPeakMaxBlocks)), block(kPeakThreads);
+    const dim3 fold((unsigned)(((long long)R + kPeakThreads - 1) / kPeakThreads));
+    if (pcm) hipLaunchKernelGGL((clip_moments_pass_kernel<true, false>), pass, block, 0, st, p);
+    else hipLaunchKernelGGL((clip_moments_pass_kernel<false, false>), pass, block, 0, st, p);
+    hipLaunchKernelGGL(clip_moments_fold_kernel<false>, fold, block, 0, st, p);
+    if (pcm) hipLaunchKernelGGL((clip_moments_pass_kernel<true, true>), pass, block, 0, st, p);
+    else hipLaunchKernelGGL((clip_moments_pass_kernel<false, true>), pass, block, 0, st, p);
+    hipLaunchKernelGGL(clip_moments_fold_kernel<true>, fold, block, 0, st, p);
     if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
     return LEAF_OK;
 }

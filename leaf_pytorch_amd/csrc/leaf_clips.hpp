@@ -48,6 +48,12 @@
 // Whole-recording evaluation (leaf_clip_peaks_f32, leaf_assemble_segments_f32) is at the end of the file: the recordings' peaks in
 // wave-sized tiles, and rows cut from a recording by a window that may begin before it or end behind it, split over workgroups.
 // Their clamped plan is leaf_segments_view.hpp (host and device).
+//
+// Waveform standardisation (leaf_clip_moments_f32, leaf_assemble_clips_std_f32, leaf_assemble_segments_std_f32): the recordings'
+// mean / std / min / max, reduced in float64 in an order the recording's length fixes (at the end of the file), and instances of the
+// assembly kernels that map every sample of the clip's recording to (v - mean) / (std + 1e-9f) where it leaves its load
+// (clip_standardize: a subtraction and a true division, STD = true in clip_sample / clip_chunk_gather / clip_tile_load).  The plain
+// and the noise instances are the STD = false instantiations of the same functions: their instructions are what they were.
 #pragma once
 #include "leaf_common.hpp"
 #include "leaf_segments_view.hpp"
@@ -108,6 +114,24 @@ template <bool PCM> __device__ __forceinline__ float clip_load(const void* store
     else return static_cast<const float*>(store)[i];
 }
 
+// The standardising instances (leaf_assemble_clips_std_f32, leaf_assemble_segments_std_f32): one clip's or row's share of
+// moments[R][4] (uniform over the workgroup) and the map y = (v - mean) / d, d = std + 1e-9f, applied where a sample of the
+// recording leaves a load.  Two correctly rounded fp32 operations, a true division: no reciprocal, no contraction, nothing of
+// leaf_fastmath.hpp -- the bits of torch's (r - mean) / (std + 1e-9) in float32.
+struct ClipStd {
+    float mean, d;
+};
+
+__device__ __forceinline__ float clip_standardize(float v, const ClipStd& s) {
+#pragma clang fp contract(off)
+    return __fdiv_rn(__fsub_rn(v, s.mean), s.d);
+}
+
+template <bool PCM, bool STD> __device__ __forceinline__ float clip_load_std(const void* store, long long i, const ClipStd* sd) {
+    if constexpr (STD) return clip_standardize(clip_load<PCM>(store, i), *sd);
+    else return clip_load<PCM>(store, i);
+}
+
 // max or min over the workgroup (every lane calls it; `red` is free again on return)
 template <bool MIN> __device__ __forceinline__ float clip_block_reduce(float m, float* red) {
     const int tid = threadIdx.x;
@@ -123,14 +147,16 @@ template <bool MIN> __device__ __forceinline__ float clip_block_reduce(float m, 
 }
 
 // element t of the padded, cropped clip (0 <= t < S) before the gain.  I: int on the resident path, long long on the other one.
-template <bool PCM, class I> __device__ __forceinline__ float clip_sample(const void* store, const ClipView& c, I t) {
+// STD: the recording's samples are standardised (`padv` is not: the caller sets it in the standardised scale).
+template <bool PCM, class I, bool STD = false>
+__device__ __forceinline__ float clip_sample(const void* store, const ClipView& c, I t, const ClipStd* sd = nullptr) {
     const I j = t - (I)c.left;
-    if (j >= 0 && j < (I)c.L) return clip_load<PCM>(store, c.off + j);
-    if (c.mode == 2) return clip_load<PCM>(store, c.off + (j < 0 ? 0 : c.L - 1));
+    if (j >= 0 && j < (I)c.L) return clip_load_std<PCM, STD>(store, c.off + j, sd);
+    if (c.mode == 2) return clip_load_std<PCM, STD>(store, c.off + (j < 0 ? 0 : c.L - 1), sd);
     if (c.mode == 3) {
         int m = (int)(j % (I)c.L);                                        // floor modulus: periodic over any number of periods
         if (m < 0) m += c.L;
-        return clip_load<PCM>(store, c.off + m);
+        return clip_load_std<PCM, STD>(store, c.off + m, sd);
     }
     return c.padv;
 }
@@ -155,11 +181,12 @@ template <bool PCM, class I> __device__ __forceinline__ bool clip_chunk_load(con
 
 // ... and the chunks that load does not serve (the padded margins, the row's two ends, recordings below four samples): element by
 // element through the pad rule; elements outside [0, S) come back as 0 (they leave the peak alone and are not stored)
-template <bool PCM, class I> __device__ __forceinline__ void clip_chunk_gather(const void* store, const ClipView& c, int S, I t0, float (&v)[4]) {
+template <bool PCM, class I, bool STD = false>
+__device__ __forceinline__ void clip_chunk_gather(const void* store, const ClipView& c, int S, I t0, float (&v)[4], const ClipStd* sd = nullptr) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const I t = t0 + e;
-        v[e] = (t >= 0 && t < (I)S) ? clip_sample<PCM, I>(store, c, t) : 0.0f;
+        v[e] = (t >= 0 && t < (I)S) ? clip_sample<PCM, I, STD>(store, c, t, sd) : 0.0f;
     }
 }
 
@@ -273,10 +300,11 @@ template <class I> __device__ __forceinline__ void clip_chunk_gauss(const ClipNo
 }
 
 // A lane's tile: the chunks q0, q0 + 1024, ... (U of them), gathered and multiplied by the gain; the lane's share of the peak comes
-// back.  Chunks behind the row are zeros.  NOISE / GAUSS: the two noise steps, around the gain, chunk by chunk.
-template <bool PCM, class I, int U, bool NOISE = false, bool GAUSS = false>
+// back.  Chunks behind the row are zeros.  NOISE / GAUSS: the two noise steps, around the gain, chunk by chunk.  STD: the clip's
+// samples are standardised as they arrive -- a whole chunk here, the others inside the pad rule; the noise recording is not.
+template <bool PCM, class I, int U, bool NOISE = false, bool GAUSS = false, bool STD = false>
 __device__ __forceinline__ float clip_tile_load(const void* store, const ClipView& c, int S, int shift, I q0, I nchunks, float (&v)[U][4],
-                                                const void* nstore = nullptr, const ClipNoiseView* a = nullptr) {
+                                                const void* nstore = nullptr, const ClipNoiseView* a = nullptr, const ClipStd* sd = nullptr) {
     bool exact[U];
     if (c.L >= 4) {
 #pragma unroll
@@ -289,7 +317,11 @@ __device__ __forceinline__ float clip_tile_load(const void* store, const ClipVie
     for (int u = 0; u < U; ++u) {
         const I q = q0 + (I)u * kClipThreads;
         if (q >= nchunks) v[u][0] = v[u][1] = v[u][2] = v[u][3] = 0.0f;
-        else if (!exact[u]) clip_chunk_gather<PCM, I>(store, c, S, 4 * q - shift, v[u]);
+        else if (!exact[u]) clip_chunk_gather<PCM, I, STD>(store, c, S, 4 * q - shift, v[u], sd);
+        else if constexpr (STD) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[u][e] = clip_standardize(v[u][e], *sd);
+        }
     }
     float m = 0.0f;
 #pragma unroll
@@ -480,6 +512,81 @@ __global__ __launch_bounds__(kClipThreads) void assemble_clips_noise_kernel(cons
     }
 }
 
+// The standardising instances (a third kernel argument: neither the plain nor the noise instances carry it)
+struct ClipStdParams {
+    const float* moments;         // [R][4]: mean, std, min, max of every recording of the store (leaf_clip_moments_f32)
+    const int* rec;               // [B] (segments: [rows]): the clip's entry of moments, clamped into [0, R - 1]
+    int R;
+    int normalize;                // segments only: scale by the standardised recording's peak
+};
+
+// the clip's moments: mean and d = std + 1e-9f (one fp32 add per clip); `mo` comes back as the clip's row of moments
+__device__ __forceinline__ ClipStd clip_std_view(const ClipStdParams& sp, int b, const float*& mo) {
+    mo = sp.moments + 4 * (size_t)segment_peak_index(sp.rec[b], sp.R);
+    ClipStd sd;
+    sd.mean = mo[0];
+    sd.d = __fadd_rn(mo[1], 1e-9f);
+    return sd;
+}
+
+// leaf_assemble_clips_std_f32: assemble_clips_noise_kernel (any of NOISE, GAUSS, or neither) on the STANDARDISED recording:
+// (v - mean_i) / d_i on every sample of the clip's recording as it is loaded, on either path; the 'min' pad value is the
+// standardised minimum of the whole recording, from moments (no min pass: the map is monotone); the noise recording stays as it is.
+template <bool PCM, bool NOISE, bool GAUSS>
+__global__ __launch_bounds__(kClipThreads) void assemble_clips_std_kernel(const ClipParams p, const ClipNoiseParams np, const ClipStdParams sp) {
+    __shared__ float red[kClipThreads / 64];
+    const int b = blockIdx.x, tid = threadIdx.x, S = p.S;
+    float* ob = p.out + (size_t)b * S;
+
+    ClipView c = clip_view(p.rec_off, p.rec_len, p.start, p.pad_mode, p.store_len, b, S);
+    c.has_gain = p.gain != nullptr;
+    c.g = c.has_gain ? p.gain[b] : 1.0f;
+    const float* mo;
+    const ClipStd sd = clip_std_view(sp, b, mo);
+    if (c.mode == 1 && c.L < S) c.padv = clip_standardize(mo[2], sd);
+    ClipNoiseView a{};
+    if constexpr (NOISE) {
+        a.n = clip_view(np.rec_off, np.rec_len, np.start, np.pad_mode, np.store_len, b, S);
+        a.c = np.coeff[2 * b];
+        a.cn = np.coeff[2 * b + 1];
+        clip_min_pass<PCM>(np.store, a.n, S, red);
+    }
+    if constexpr (GAUSS) {
+        const unsigned long long st = (unsigned long long)np.stream[b];
+        a.amp = np.amp[b];
+        a.k0 = (unsigned)np.seed; a.k1 = (unsigned)(np.seed >> 32);
+        a.s0 = (unsigned)st; a.s1 = (unsigned)(st >> 32);
+    }
+    const int shift = (int)((reinterpret_cast<uintptr_t>(ob) >> 2) & 3);  // row elements the first aligned chunk lacks
+
+    constexpr int kResident = kClipNoiseChunks;
+    if (S <= kClipNoiseResidentMax) {                                     // one tile per lane holds the clip
+        const int nchunks = (S + shift + 3) >> 2;
+        float v[kResident][4];
+        const float m = clip_tile_load<PCM, int, kResident, NOISE, GAUSS, true>(p.store, c, S, shift, tid, nchunks, v, np.store, &a, &sd);
+        const float peak = p.normalize ? clip_block_reduce<false>(m, red) : 0.0f;
+        clip_tile_finish<int, kResident>(p, b, shift, tid, nchunks, peak, v, ob);
+        return;
+    }
+
+    constexpr int kU = 4;                                                 // chunks in flight per lane on the re-reading path
+    const long long nchunks = ((long long)S + shift + 3) >> 2;
+    float peak = 0.0f;
+    if (p.normalize) {
+        float m = 0.0f;
+        for (long long q0 = tid; q0 < nchunks; q0 += kU * kClipThreads) {
+            float v[kU][4];
+            m = fmaxf(m, clip_tile_load<PCM, long long, kU, NOISE, GAUSS, true>(p.store, c, S, shift, q0, nchunks, v, np.store, &a, &sd));
+        }
+        peak = clip_block_reduce<false>(m, red);
+    }
+    for (long long q0 = tid; q0 < nchunks; q0 += kU * kClipThreads) {
+        float v[kU][4];
+        clip_tile_load<PCM, long long, kU, NOISE, GAUSS, true>(p.store, c, S, shift, q0, nchunks, v, np.store, &a, &sd);
+        clip_tile_finish<long long, kU>(p, b, shift, q0, nchunks, peak, v, ob);
+    }
+}
+
 // leaf_gaussian_noise_f32: z[b][t] as [B][size], one lane per group of four; grid B * tiles, tiles = ceil(ceil(size / 4) / 256)
 __global__ __launch_bounds__(256) void gaussian_noise_kernel(int size, int tiles, unsigned long long seed, const long long* stream, float* out) {
     const int b = blockIdx.x / tiles;
@@ -637,6 +744,149 @@ __global__ __launch_bounds__(kClipThreads) void assemble_segments_kernel(const S
     float v[kClipChunks][4];
     clip_tile_load<PCM, long long, kClipChunks>(p.store, c, S, shift, q0, nchunks, v);
     clip_tile_finish<long long, kClipChunks>(cp, b, shift, q0, nchunks, peak, v, ob);
+}
+
+// leaf_assemble_segments_std_f32: the rows of the STANDARDISED recording.  The recording's peak needs no pass over it: the map is
+// monotone in fp32 (a correctly rounded subtraction, a correctly rounded division by d > 0), so max |y| is taken at min or at max.
+template <bool PCM>
+__global__ __launch_bounds__(kClipThreads) void assemble_segments_std_kernel(const SegmentParams p, const ClipStdParams sp) {
+    const int b = blockIdx.x / p.tiles, tile = blockIdx.x % p.tiles, S = p.S;
+    float* ob = p.out + (size_t)b * S;
+    const SegmentView sv = segment_view(p.rec_off[b], p.rec_len[b], p.win[b], p.store_len, S);
+    ClipView c;
+    c.off = sv.off; c.L = sv.L; c.left = sv.left;
+    c.mode = sv.L > 0 ? 2 : 0;                                            // no samples: zeros
+    c.padv = 0.0f; c.has_gain = false; c.g = 1.0f;
+    const float* mo;
+    const ClipStd sd = clip_std_view(sp, b, mo);
+    const float peak = sp.normalize ? fmaxf(fabsf(clip_standardize(mo[2], sd)), fabsf(clip_standardize(mo[3], sd))) : 0.0f;
+    const int shift = (int)((reinterpret_cast<uintptr_t>(ob) >> 2) & 3);  // row elements the first aligned chunk lacks
+    const long long nchunks = ((long long)S + shift + 3) >> 2;
+    const long long q0 = (long long)tile * (kClipChunks * kClipThreads) + threadIdx.x;
+    if (q0 >= nchunks) return;                                            // (no barrier in this kernel)
+    ClipParams cp{};                                                      // what clip_tile_finish reads: the row size, no masks
+    cp.S = S;
+    float v[kClipChunks][4];
+    clip_tile_load<PCM, long long, kClipChunks, false, false, true>(p.store, c, S, shift, q0, nchunks, v, nullptr, nullptr, &sd);
+    clip_tile_finish<long long, kClipChunks>(cp, b, shift, q0, nchunks, peak, v, ob);
+}
+
+// ---- the recordings' moments (include/leaf_hip.h: leaf_clip_moments_f32) -------------------------------------------------------------
+// mean, std (unbiased), min and max of every recording, the reductions in float64 and in an order that the recording's length
+// alone fixes.  The work unit is a wave and one SPAN of one recording (leaf_segments_view.hpp: moment_span -- up to kMomentSpans
+// spans of whole 1024-sample tiles): a long recording is 32 waves' work, a short one a single tile's.  A lane adds its samples in
+// index order (the tile layout of clip_peaks_kernel: four chunks of four per lane and tile), the 64 lanes are folded by a butterfly
+// (a + b on both sides: the same bits in every lane), and the span's partial goes to its own slot of the workspace.  A second kernel
+// folds a recording's 32 slots in slot order.  Two such passes: sum -> mean (kept in the workspace in float64), then the squared
+// deviations from that mean.  No atomics; which wave takes which unit does not enter the result.
+struct MomentPartial {
+    double sum;                   // of the samples (pass 1), of the squared deviations (pass 2)
+    float mn, mx;                 // pass 1 (NaN samples are ignored by fminf / fmaxf; the mean and the std carry them)
+};
+
+struct MomentParams {
+    const void* store;
+    long long store_len;
+    const long long* rec_off;     // [R]
+    const int* rec_len;           // [R]
+    float* moments;               // [R][4]
+    MomentPartial* part;          // [R][kMomentSpans] workspace
+    double* mean;                 // [R] workspace: the float64 mean before its rounding
+    int R;
+};
+
+template <bool PCM, bool SQ>
+__global__ __launch_bounds__(kPeakThreads) void clip_moments_pass_kernel(const MomentParams p) {
+    const int lane = threadIdx.x & 63;
+    const long long waves = (long long)gridDim.x * (kPeakThreads / 64), units = (long long)p.R * kMomentSpans;
+    for (long long unit = (long long)blockIdx.x * (kPeakThreads / 64) + (threadIdx.x >> 6); unit < units; unit += waves) {
+        const int i = (int)(unit / kMomentSpans), k = (int)(unit % kMomentSpans);
+        const SegmentView r = recording_view(p.rec_off[i], p.rec_len[i], p.store_len);
+        const MomentSpan s = moment_span(r.L, k);
+        const double m = SQ ? p.mean[i] : 0.0;
+        double acc = 0.0;
+        float mn = INFINITY, mx = -INFINITY;
+        for (long long t0 = s.begin; t0 < s.end; t0 += kMomentTile) {
+            float v[kPeakChunks][4];
+            int n[kPeakChunks];                                           // the chunk's samples inside the span
+#pragma unroll
+            for (int u = 0; u < kPeakChunks; ++u) {
+                const long long j = t0 + u * (4 * 64) + 4 * lane;
+                if (j + 4 <= s.end) {                                     // one load at element alignment, as clip_chunk_load
+                    n[u] = 4;
+                    if constexpr (PCM) {
+                        const s16x4u q = *reinterpret_cast<const s16x4u*>(static_cast<const short*>(p.store) + (r.off + j));
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[u][e] = pcm16_widen(q[e]);
+                    } else {
+                        const f32x4u q = *reinterpret_cast<const f32x4u*>(static_cast<const float*>(p.store) + (r.off + j));
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[u][e] = q[e];
+                    }
+                } else {
+                    n[u] = j < s.end ? (int)(s.end - j) : 0;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[u][e] = e < n[u] ? clip_load<PCM>(p.store, r.off + j + e) : 0.0f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kPeakChunks; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (e < n[u]) {
+                        if constexpr (SQ) {
+                            const double dv = (double)v[u][e] - m;
+                            acc += dv * dv;                               // (contraction would only drop a float64 rounding; the order stays)
+                        } else {
+                            acc += (double)v[u][e];
+                            mn = fminf(mn, v[u][e]);
+                            mx = fmaxf(mx, v[u][e]);
+                        }
+                    }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            acc += __shfl_xor(acc, off);
+            if constexpr (!SQ) {
+                mn = fminf(mn, __shfl_xor(mn, off));
+                mx = fmaxf(mx, __shfl_xor(mx, off));
+            }
+        }
+        if (lane == 0) {
+            p.part[unit].sum = acc;
+            if constexpr (!SQ) { p.part[unit].mn = mn; p.part[unit].mx = mx; }
+        }
+    }
+}
+
+// ... and the fold of a recording's slots, one lane per recording.  SQ = false: mean (float64 to the workspace, rounded once to
+// moments[i][0]), min, max; SQ = true: std = sqrt(sum / (L - 1)) in float64, rounded once.  L == 1: 0 / 0 = NaN, as torch's unbiased
+// std; L == 0: (0, NaN, 0, 0).
+template <bool SQ>
+__global__ __launch_bounds__(kPeakThreads) void clip_moments_fold_kernel(const MomentParams p) {
+    const long long i = (long long)blockIdx.x * kPeakThreads + threadIdx.x;
+    if (i >= p.R) return;
+    const int L = recording_view(p.rec_off[i], p.rec_len[i], p.store_len).L;
+    const MomentPartial* part = p.part + i * kMomentSpans;
+    double sum = 0.0;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int k = 0; k < kMomentSpans; ++k) {
+        sum += part[k].sum;
+        if constexpr (!SQ) {
+            mn = fminf(mn, part[k].mn);
+            mx = fmaxf(mx, part[k].mx);
+        }
+    }
+    float* mo = p.moments + 4 * i;
+    if constexpr (SQ) {
+        mo[1] = L > 0 ? (float)sqrt(sum / (double)(L - 1)) : __builtin_nanf("");
+    } else {
+        const double mean = L > 0 ? sum / (double)L : 0.0;
+        p.mean[i] = mean;
+        mo[0] = (float)mean;
+        mo[2] = L > 0 ? mn : 0.0f;
+        mo[3] = L > 0 ? mx : 0.0f;
+    }
 }
 
 }  // namespace

@@ -43,7 +43,30 @@ LEAF_HOST_DEVICE inline long long segment_source(const SegmentView& v, long long
     return j < 0 ? 0 : (j > last ? last : j);
 }
 
-// the entry of peaks[0, R) a row scales by; R >= 1
+// the entry of peaks[0, R) a row scales by (and of moments[0, R) a clip or a row is standardised by); R >= 1
 LEAF_HOST_DEVICE inline int segment_peak_index(int rec, int R) {
     return rec < 0 ? 0 : (rec > R - 1 ? R - 1 : rec);
+}
+
+// leaf_clip_moments_f32: the fixed split of a recording's reductions.  A recording of L samples is ceil(L / 1024) tiles; its tiles
+// are dealt to kMomentSpans spans of `per` = ceil(tiles / kMomentSpans) consecutive tiles each (the last ones may be empty).  The
+// split depends on L alone -- not on the grid, the store or the other recordings -- so the order of every addition is fixed by it.
+constexpr int kMomentTile = 1024;
+constexpr int kMomentSpans = 32;
+
+struct MomentSpan {
+    long long begin, end;         // the recording's samples [begin, end), 0 <= begin, end <= L; begin >= end: an empty span
+};
+
+// span k, 0 <= k < kMomentSpans, of a recording of L >= 0 samples (k and L outside are clamped)
+LEAF_HOST_DEVICE inline MomentSpan moment_span(int L, int k) {
+    const long long len = L < 0 ? 0 : L, kk = k < 0 ? 0 : (k > kMomentSpans - 1 ? kMomentSpans - 1 : k);
+    const long long tiles = (len + kMomentTile - 1) / kMomentTile;        // <= 2^21
+    const long long per = (tiles + kMomentSpans - 1) / kMomentSpans;      // <= 2^16
+    MomentSpan s;
+    s.begin = kk * per * kMomentTile;                                     // <= 2^31: 64 bits hold it
+    s.end = s.begin + per * kMomentTile;
+    if (s.begin > len) s.begin = len;
+    if (s.end > len) s.end = len;
+    return s;
 }

@@ -91,9 +91,17 @@ class PackedClips:
     (leaf_assemble_segments_f32) with ``peaks`` (leaf_clip_peaks_f32) behind it; ``segment_mean`` and ``evaluate_recordings`` finish
     the loop.
 
+    The reference's waveform standardisation (RawAudioParser with ``audio_config.normalize``: the WHOLE recording, as loaded and in
+    front of every other transform, becomes ``(r - mean) / (std + 1e-9)``) is the keyword ``standardize`` of ``assemble`` and
+    ``segments``: the recordings' ``moments()`` (leaf_clip_moments_f32, once per dataset) are looked up by the kernel and the map is
+    applied as the samples are loaded (leaf_assemble_clips_std_f32 / leaf_assemble_segments_std_f32) -- still one launch per batch,
+    the int16 store stays int16.
+
     One workgroup assembles one clip: a batch of a few very long clips uses a few CUs (splitting a clip over workgroups is not
     built; the rows of ``segments`` are split).  Not built either: bfloat16 stores, outputs in anything but float32, a noise store
-    of another dtype than the clips'."""
+    of another dtype than the clips', a standardised noise store (the reference does not standardise its noise either), and the
+    statistics of the reference's ``--cropped_read`` (there the parser sees only the frames that were read, tiled by ``load_audio``:
+    another padding convention)."""
 
     def __init__(self, recordings, device=None):
         recs = [r if isinstance(r, torch.Tensor) else torch.as_tensor(r) for r in recordings]
@@ -127,6 +135,7 @@ class PackedClips:
         self.offsets_host, self.lengths_host = offsets.to(torch.int64), lengths.to(torch.int32)
         self.offsets, self.lengths = self.offsets_host.to(store.device), self.lengths_host.to(store.device)
         self._peaks = None                                                      # peaks(): computed on the first call, then kept
+        self._moments = None                                                    # ... and moments()
 
     def __len__(self) -> int:
         return self.lengths_host.numel()
@@ -179,7 +188,7 @@ class PackedClips:
         return (nclips.store, noff, nlen, self._per_clip(nstart, B), self._per_clip(pad_mode, B, _native.PAD_MODES), coeff)
 
     def assemble(self, index, start, size: int, pad_mode="zero", gain=None, normalize: bool = True, masks=None, out=None,
-                 noise=None, gaussian=None) -> torch.Tensor:
+                 noise=None, gaussian=None, standardize: bool = False) -> torch.Tensor:
         """The batch of the recordings ``index`` (any order, repeats allowed): clip b is recording ``index[b]`` padded by
         ``pad_mode`` ("zero" / "min" / "replicate" / "wrap" or 0..3; one for the batch or one per clip) when it is shorter than
         ``size``, cropped at ``start[b]`` in [0, max(L, size) - size], then ``gain``, peak normalisation and ``masks`` as in
@@ -191,11 +200,19 @@ class PackedClips:
         padded by ``pad_mode`` and cropped at ``noise_start[b]`` like a clip.  The level is one SNR in dB per clip (a number or B of
         them: coeff = r / (1 + r), r = 10^(snr / 10), AddRandomNoise's rule) or, as a (B, 2) float32 tensor, the coefficient pairs
         (c, c') themselves (``_native.noise_coefficients``).  ``gaussian`` = (amp, seed, stream): amplitudes (B,) float32, a 64-bit
-        seed and one int64 stream id per clip (``_native.gaussian_noise``); amplitude 0 leaves a clip alone."""
+        seed and one int64 stream id per clip (``_native.gaussian_noise``); amplitude 0 leaves a clip alone.
+
+        ``standardize``: the reference's ``audio_config.normalize`` -- recording ``index[b]`` as a whole becomes
+        ``(r - mean) / (std + 1e-9)`` (``moments()``; torch's float32 rounding) in front of the padding, so "min" pads with the
+        standardised recording's minimum and the peak normalisation sees the standardised clip (it is live for an int16 store too).
+        The noise recordings are not standardised, as in the reference.  False: the call, and its bits, are what they were."""
         B, rec_off, rec_len = self._records(index)
+        std = None
+        if standardize:
+            std = (self.moments(), (index if isinstance(index, torch.Tensor) else torch.as_tensor(index, dtype=torch.int64)).reshape(-1))
         return _native.assemble_clips(self.store, rec_off, rec_len, self._per_clip(start, B), self._per_clip(pad_mode, B, _native.PAD_MODES),
                                       size, gain, normalize, masks, out, noise=None if noise is None else self._noise(noise, B),
-                                      gaussian=gaussian)
+                                      gaussian=gaussian, standardize=std)
 
     # ---- whole recordings, the way the reference's test.py evaluates them -----------------------------------------------------------
 
@@ -212,6 +229,20 @@ class PackedClips:
         """Drop the kept peaks; the next ``peaks()`` computes them again.  The store is taken as immutable after construction: a
         caller that writes into ``store`` all the same calls this afterwards."""
         self._peaks = None
+
+    def moments(self) -> torch.Tensor:
+        """``(mean, std, min, max)`` of every recording, ``(len(self), 4)`` float32 on the store's device (``_native.clip_moments``
+        -> leaf_clip_moments_f32: float64 accumulation in an order the recording's length fixes, torch's unbiased std, exact min and
+        max) -- what ``standardize`` maps the samples with.  Computed on the first call and kept, like ``peaks()``: the store is
+        taken as immutable after construction (``refresh_moments`` after writing into it)."""
+        if self._moments is None:
+            self._moments = _native.clip_moments(self.store, self.offsets, self.lengths)
+        return self._moments
+
+    def refresh_moments(self) -> None:
+        """Drop the kept moments; the next ``moments()`` computes them again.  The store is taken as immutable after construction: a
+        caller that writes into ``store`` all the same calls this afterwards."""
+        self._moments = None
 
     def segment_plan(self, index, size: int):
         """The integers of ``segments``, all on the CPU from ``lengths_host``: ``(counts, rec, win, left)``.  Recording
@@ -240,16 +271,22 @@ class PackedClips:
         k = torch.arange(int(counts.sum())) - torch.repeat_interleave(first, counts)
         return counts, torch.repeat_interleave(index, counts), k * size - torch.repeat_interleave(left, counts), left
 
-    def _segment_rows(self, rec: torch.Tensor, win: torch.Tensor, size: int, normalize: bool, out=None) -> torch.Tensor:
+    def _segment_rows(self, rec: torch.Tensor, win: torch.Tensor, size: int, normalize: bool, out=None, standardize: bool = False) -> torch.Tensor:
         """The rows ``(rec, win)`` of a ``segment_plan`` in one launch.  An int16 store has no peak above 1: like
-        ``Leaf.fuse_peak_normalization`` for int16, nothing is scaled and ``peaks()`` is not launched."""
+        ``Leaf.fuse_peak_normalization`` for int16, nothing is scaled and ``peaks()`` is not launched.  ``standardize``: the rows of
+        the standardised recordings; their peak comes from ``moments()``, for either store."""
+        if standardize:
+            plan = torch.stack((self.offsets_host[rec], self.lengths_host[rec].long(), win, rec)).to(self.store.device)
+            return _native.assemble_segments(self.store, plan[0], plan[1].to(torch.int32), plan[2], size, None, plan[3].to(torch.int32), out,
+                                             moments=self.moments() if rec.numel() else torch.zeros((1, 4), device=self.store.device),
+                                             normalize=normalize)
         scaled = bool(normalize) and self.store.dtype == torch.float32 and rec.numel() > 0
         # the four row arrays cross in ONE copy (they come from this object's own validated tables: nothing to check again)
         plan = torch.stack((self.offsets_host[rec], self.lengths_host[rec].long(), win, rec)).to(self.store.device)
         return _native.assemble_segments(self.store, plan[0], plan[1].to(torch.int32), plan[2], size,
                                          self.peaks() if scaled else None, plan[3].to(torch.int32) if scaled else None, out)
 
-    def segments(self, index, size: int, normalize: bool = True, out=None):
+    def segments(self, index, size: int, normalize: bool = True, out=None, standardize: bool = False):
         """The evaluation batch of the reference's test.py for the recordings ``index`` (any order, repeats allowed), in ONE launch
         (``_native.assemble_segments`` -> leaf_assemble_segments_f32): ``(batch, counts)``.  Per recording r of L samples test.py runs
         ``PeakNormalization`` over the WHOLE recording (``normalize``; the peak comes from ``peaks()``), then ``pad_input`` --
@@ -257,8 +294,14 @@ class PackedClips:
         ``reshape(-1, 1, size)``.  ``batch`` is the rows of all recordings behind one another, ``(sum n_i, 1, size)`` float32 as
         ``Leaf.forward`` takes it, bit for bit what those stock ops give; ``counts`` the CPU int64 tensor of the ``n_i``
         (``segment_mean(model(batch), counts)`` is test.py's ``torch.mean(preds, dim=0)`` per recording).  An empty ``index`` returns
-        ``(0, 1, size)`` and launches nothing; an empty recording raises ValueError."""
+        ``(0, 1, size)`` and launches nothing; an empty recording raises ValueError.
+
+        ``standardize``: the reference's ``audio_config.normalize`` in front of it all -- the parser's ``(r - mean) / (std + 1e-9)``
+        on the whole recording (``moments()``), THEN ``PeakNormalization`` over the whole standardised recording (its peak is
+        ``max(|y(min)|, |y(max)|)``, exact: the map is monotone), then ``pad_input``.  An int16 store is scaled too."""
         counts, rec, win, _ = self.segment_plan(index, size)
+        if standardize:
+            return self._segment_rows(rec, win, int(size), normalize, out, standardize=True), counts
         return self._segment_rows(rec, win, int(size), normalize, out), counts
 
 
@@ -287,13 +330,15 @@ def segment_mean(preds: torch.Tensor, counts) -> torch.Tensor:
     return (sums / _per_row(counts, sums)).to(preds.dtype)
 
 
-def evaluate_recordings(model, clips: PackedClips, size: int, index=None, max_rows: int = 512, normalize: bool = True) -> torch.Tensor:
+def evaluate_recordings(model, clips: PackedClips, size: int, index=None, max_rows: int = 512, normalize: bool = True,
+                        standardize: bool = False) -> torch.Tensor:
     """The evaluation loop of the reference's test.py over the recordings ``index`` of ``clips`` (default: all of them): ``(N, C)``,
     per recording the mean of ``model``'s outputs over its rows, in ``index`` order; sigmoid / argmax are the caller's, as there.
     Runs under ``torch.no_grad()`` (``model.eval()`` is the caller's).  Instead of test.py's one recording per forward, the rows of
     consecutive recordings are packed into forwards of at most ``max_rows`` rows -- one ``segments`` launch and one ``model`` call
     each; a recording that does not fit the rest of a forward, or has more rows than ``max_rows``, continues in the next one and its
-    sum is carried (in float64, as ``segment_mean`` sums)."""
+    sum is carried (in float64, as ``segment_mean`` sums).  ``standardize``: the rows of ``clips.segments(..., standardize=True)``,
+    the reference's ``audio_config.normalize``."""
     max_rows = int(max_rows)
     if max_rows < 1:
         raise ValueError(f"max_rows must be at least 1, got {max_rows}")
@@ -305,7 +350,8 @@ def evaluate_recordings(model, clips: PackedClips, size: int, index=None, max_ro
     with torch.no_grad():
         for a in range(0, rec.numel(), max_rows):
             b = min(rec.numel(), a + max_rows)
-            preds = model(clips._segment_rows(rec[a:b], win[a:b], int(size), normalize))
+            extra = {"standardize": True} if standardize else {}
+            preds = model(clips._segment_rows(rec[a:b], win[a:b], int(size), normalize, **extra))
             first, last = int(place[a]), int(place[b - 1])
             part = _segment_sums(preds, torch.bincount(place[a:b] - first, minlength=last - first + 1))
             if sums is None:
@@ -325,9 +371,11 @@ class ClipNoisePlan(ClipPlan):
     """A ``ClipPlan`` (the same six entries, unpacking as before) that carries the noise draws as attributes: ``noise`` =
     (noise_off, noise_len, noise_start, noise_pad_mode, coeff) -- ``coeff`` float64, AddRandomNoise's r / (1 + r); ``noise_len`` 0 for
     a clip without background noise -- or None, and ``gaussian`` = (amp, seed, stream) or None: what ``_native.assemble_clips`` takes
-    as ``noise`` (behind the noise store) and ``gaussian``."""
+    as ``noise`` (behind the noise store) and ``gaussian``.  A standardising sampler adds ``rec``, the clips' recordings (int32: their
+    rows of ``PackedClips.moments()``), or None."""
     noise = None
     gaussian = None
+    rec = None
 
 
 class ClipSampler:
@@ -362,13 +410,18 @@ class ClipSampler:
     The reference's own ``random`` / ``numpy.random`` streams are NOT reproduced -- the distributions are, the numbers are not.
     ``plan(index)`` returns the draws (``ClipPlan``), ``__call__(index)`` the assembled ``(B, 1, size)`` float32 batch.
 
+    - ``standardize`` (``audio_config.normalize``): no draw -- the plan carries the clips' recordings (``plan.rec``, a
+      ``ClipNoisePlan`` then) and the batch is assembled from the standardised recordings (``PackedClips.assemble(...,
+      standardize=True)``).  A sampler without it draws and returns what it always did.
+
     Left out: ClipValue and RandomReverb, which the reference itself has switched off."""
 
     def __init__(self, clips: PackedClips, size: int, train: bool = True, pad_modes=("replicate", "min"), wrap_pad_prob: float = 0.5,
                  gain_prob: float = 0.25, gain_db=(-18.0, 6.0), peak_normalize: bool = True, time_perc: float = 0.0, num_masks: int = 0,
                  generator=None, noise_clips=None, noise_prob: float = 0.5, snr_range=(10, 25), gaussian_prob: float = 0.0,
-                 gaussian_amplitude=(0.001, 0.015), gaussian_seed=None):
+                 gaussian_amplitude=(0.001, 0.015), gaussian_seed=None, standardize: bool = False):
         self.clips, self.size, self.train = clips, int(size), bool(train)
+        self.standardize = bool(standardize)
         self.pad_modes = tuple(_native.PAD_MODES[m] if isinstance(m, str) else int(m) for m in pad_modes)
         if len(self.pad_modes) != 2 or any(m not in _native.PAD_MODES.values() for m in self.pad_modes):
             raise ValueError(f"pad_modes must name two of {sorted(_native.PAD_MODES)}")
@@ -416,9 +469,11 @@ class ClipSampler:
             t0 = (self._uniform(B, self.num_masks) * (S - n).double()).long()
             masks = torch.stack((t0, n), dim=2).to(torch.int32)
         entries = (rec_off.clone(), rec_len.clone(), start.to(torch.int32), pad_mode, gain, masks)
-        if self.noise_clips is None and self.gaussian_prob <= 0.0:
+        if self.noise_clips is None and self.gaussian_prob <= 0.0 and not self.standardize:
             return ClipPlan(entries)
         plan = ClipNoisePlan(entries)
+        if self.standardize:
+            plan.rec = index.to(torch.int32)
         if self.noise_clips is not None:                                        # AddRandomNoise
             nc = self.noise_clips
             apply = self._uniform(B) < self.noise_prob
@@ -440,7 +495,8 @@ class ClipSampler:
     def __call__(self, index, out=None) -> torch.Tensor:
         plan = self.plan(index)
         rec_off, rec_len, start, pad_mode, gain, masks = plan
-        noise = getattr(plan, "noise", None)
+        noise, rec = getattr(plan, "noise", None), getattr(plan, "rec", None)
         return _native.assemble_clips(self.clips.store, rec_off, rec_len, start, pad_mode, self.size, gain, self.peak_normalize, masks, out,
                                       noise=None if noise is None else (self.noise_clips.store,) + tuple(noise),
-                                      gaussian=getattr(plan, "gaussian", None))
+                                      gaussian=getattr(plan, "gaussian", None),
+                                      standardize=None if rec is None else (self.clips.moments(), rec))

@@ -6,6 +6,7 @@ multiply by the gain, transforms.PeakNormalization, one masked_fill per span.
     python tools/bench_clips.py [--rounds 20] [--steps 50] [--out profiles/clip_assembly.txt]
     python tools/bench_clips.py --noise [--out profiles/clip_noise.txt]
     python tools/bench_clips.py --segments [--out profiles/eval_segments.txt]
+    python tools/bench_clips.py --standardize [--out profiles/clip_standardize.txt]
 
 Both sides run in ONE process on the same store and the same plan (already on the device: drawing it is not timed), taking turns
 round after round after a warm-up round, the order alternating.  Every recording is longer than the clip, so the batch is a crop
@@ -35,7 +36,14 @@ row plan already on the device; `segments`, PackedClips.segments as a user calls
 copied over: wall time only, its copies wait for the device); and `stock`, the reference loop restated in stock ops on the device --
 per recording transforms.PeakNormalization over the whole recording, F.pad(..., 'replicate'), reshape; then torch.cat.  The two
 batches are compared bit for bit before anything is timed.  The one-time PackedClips.peaks() launch (leaf_clip_peaks_f32 over the
-whole store; float32 stores only use it) is timed on its own, in rounds of its own, and reported in its own column."""
+whole store; float32 stores only use it) is timed on its own, in rounds of its own, and reported in its own column.
+
+--standardize times the launch on the standardised recordings (leaf_assemble_clips_std_f32: audio_config.normalize in the launch): B =
+64 / 256 clips of 16 000 and B = 256 of 80 000 samples, both stores.  Three sides take turns: `std`, the standardising launch; `plain`,
+leaf_assemble_clips_f32 on the same plan (what the keyword costs, and whether the plain launch is what it was); `stock`, what a user
+without the entry keeps -- a float32 copy of the whole store standardised per recording by the reference's expression (made once on
+the CPU from the library's moments, not timed) -- through the stock chain of the first table.  The std and stock batches are compared
+bit for bit before anything is timed.  The one-time PackedClips.moments() call (leaf_clip_moments_f32) is timed in rounds of its own."""
 import argparse
 import os
 import statistics
@@ -217,6 +225,61 @@ def segment_legs(args, busy, busy_out):
     return lines
 
 
+def standardize_legs(args, busy, busy_out):
+    pn = PeakNormalization()
+    lines = [f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {args.rounds} timed rounds x {args.steps} calls per side after a "
+             "warm-up round; us per call: median [min, max]; device = HIP events, calls queued behind a matrix product; wall = host clock to a "
+             "synchronise; std = leaf_assemble_clips_std_f32 (standardize=(moments, rec)), plain = leaf_assemble_clips_f32 on the same plan, "
+             "stock = gather from a float32 copy of the store standardised per recording (made once, not timed) + gain + PeakNormalization + "
+             "masked_fill; moments = the one-time leaf_clip_moments_f32 call over the store, rounds of its own",
+             f"{'store':>8} {'B':>4} {'S':>6} | {'std device':>24} {'std wall':>9} | {'plain device':>24} | {'stock device':>24} {'stock wall':>11} | "
+             f"{'std / plain':>11} {'stock / std':>11} | {'moments device':>24}"]
+    for dtype in (torch.int16, torch.float32):
+        for B, S in ((64, 16000), (256, 16000), (256, 80000)):
+            store, p = make_case(B, S, dtype, seed=B + S)
+            rec = torch.arange(B, dtype=torch.int32, device=DEV)
+            moments = _native.clip_moments(store, p["rec_off"], p["rec_len"])
+            # the copy a user without the entry would keep: every recording through the reference's expression, on the CPU, once
+            wide, mo = (store.cpu().float() / 32768 if dtype == torch.int16 else store.cpu().clone()), moments.cpu()
+            for i, (o, n) in enumerate(zip(p["rec_off"].tolist(), p["rec_len"].tolist())):
+                wide[o:o + n] = (wide[o:o + n] - mo[i, 0]) / (mo[i, 1] + 1e-9)
+            wide = wide.to(DEV)
+            out = torch.empty((B, 1, S), dtype=torch.float32, device=DEV)
+            ar = torch.arange(S, device=DEV)
+            lo, hi = p["masks"][..., 0].long(), (p["masks"][..., 0] + p["masks"][..., 1]).long()
+            first = (p["rec_off"] + p["start"])[:, None]
+
+            def kernel():
+                return _native.assemble_clips(store, p["rec_off"], p["rec_len"], p["start"], p["pad_mode"], S, p["gain"], True, p["masks"], out,
+                                              standardize=(moments, rec))
+
+            def plain():
+                return _native.assemble_clips(store, p["rec_off"], p["rec_len"], p["start"], p["pad_mode"], S, p["gain"], True, p["masks"], out)
+
+            def stock():
+                x = pn(wide[first + ar] * p["gain"][:, None])
+                for m in range(M):
+                    x = x.masked_fill((ar >= lo[:, m, None]) & (ar < hi[:, m, None]), 0.0)
+                return x[:, None]
+
+            def once():
+                return _native.clip_moments(store, p["rec_off"], p["rec_len"])
+
+            a, b = kernel().clone(), stock()
+            torch.cuda.synchronize()
+            if not torch.equal(a.view(torch.int32), b.contiguous().view(torch.int32)):
+                sys.exit(f"the two sides disagree at {dtype} B={B} S={S}: nothing is timed")
+            dev_us, wall_us = time_sides({"std": kernel, "plain": plain, "stock": stock}, args.rounds, args.steps, busy, busy_out)
+            mom_us, _ = time_sides({"moments": once}, args.rounds, args.steps, busy, busy_out)
+            fmt = lambda v: f"{statistics.median(v):9.1f} [{min(v):6.1f},{max(v):7.1f}]"
+            med = {k: statistics.median(v) for k, v in dev_us.items()}
+            lines.append(f"{str(dtype).replace('torch.', ''):>8} {B:>4} {S:>6} | {fmt(dev_us['std'])} {statistics.median(wall_us['std']):9.1f} | "
+                         f"{fmt(dev_us['plain'])} | {fmt(dev_us['stock'])} {statistics.median(wall_us['stock']):11.1f} | "
+                         f"{med['std'] / med['plain']:11.2f} {med['stock'] / med['std']:11.2f} | {fmt(mom_us['moments'])}")
+            print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=20)
@@ -224,12 +287,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--noise", action="store_true", help="time the launch with background and Gaussian noise (profiles/clip_noise.txt)")
     ap.add_argument("--segments", action="store_true", help="time the whole-recording evaluation batch (profiles/eval_segments.txt)")
+    ap.add_argument("--standardize", action="store_true", help="time the standardising launch (profiles/clip_standardize.txt)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_clips.py needs the GPU: a time taken anywhere else says nothing about it")
-    if args.noise or args.segments:
+    if args.noise or args.segments or args.standardize:
         busy = torch.rand(8192, 8192, device=DEV)
-        text = "\n".join((segment_legs if args.segments else noise_legs)(args, busy, torch.empty_like(busy))) + "\n"
+        legs = standardize_legs if args.standardize else (segment_legs if args.segments else noise_legs)
+        text = "\n".join(legs(args, busy, torch.empty_like(busy))) + "\n"
         print(text)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -7,7 +7,9 @@
 //
 // Every combination of the values below goes through segment_view / segment_source / segment_peak_index, and what comes back is
 // checked against the contract of include/leaf_hip.h: the recording inside store[0, store_len), every source index inside the
-// recording, the peak index inside peaks[0, R), and the value the closed form clamp(win + t, 0, L - 1) gives in wide arithmetic.
+// recording, the peak index inside peaks[0, R) (the same clamp picks a clip's row of moments[0, R)), and the value the closed form
+// clamp(win + t, 0, L - 1) gives in wide arithmetic.  The spans of leaf_clip_moments_f32 (moment_span) go through it too: for any
+// length they follow each other, begin at whole tiles and cover [0, L) exactly.
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -61,6 +63,26 @@ int main() {
             const int i = segment_peak_index(rec, R);
             expect(i >= 0 && i < R && (rec < 0 || rec >= R || i == rec), "peak index outside [0, R)", rec, R, 0, 0, 0);
         }
+    // leaf_clip_moments_f32: the spans of a recording of any length tile [0, L) in order, in whole tiles, for any (clamped) k
+    const int Ls[] = {INT_MIN, -1, 0, 1, 2, 1023, 1024, 1025, 32 * 1024 - 1, 32 * 1024, 32 * 1024 + 1, 300001, INT_MAX - 1024, INT_MAX - 1, INT_MAX};
+    for (int L : Ls) {
+        const long long len = L < 0 ? 0 : L;
+        long long at = 0;
+        for (int k = 0; k < kMomentSpans; ++k) {
+            ++cases;
+            const MomentSpan s = moment_span(L, k);
+            expect(s.begin == at && s.end >= s.begin && s.end <= len, "spans do not follow each other inside [0, L)", L, k, s.begin, s.end, 0);
+            expect(s.begin == s.end || s.begin % kMomentTile == 0, "a span does not begin at a tile", L, k, s.begin, s.end, 0);
+            at = s.end;
+        }
+        expect(at == len, "the spans do not cover the recording", L, at, 0, 0, 0);
+        const int ks[] = {INT_MIN, -1, kMomentSpans, INT_MAX};
+        for (int k : ks) {
+            ++cases;
+            const MomentSpan s = moment_span(L, k), edge = moment_span(L, k < 0 ? 0 : kMomentSpans - 1);
+            expect(s.begin == edge.begin && s.end == edge.end, "a span index outside is not clamped", L, k, s.begin, s.end, 0);
+        }
+    }
     std::printf("%lld cases, %lld failures\n", cases, fails);
     return fails ? EXIT_FAILURE : EXIT_SUCCESS;
 }
