@@ -856,6 +856,64 @@ int leaf_assemble_segments_std_f32(const void* store, long long store_len, int f
                                    const int* rec_len, const long long* win, const float* peaks /*NULL*/, const int* rec, int R,
                                    float* out /*[rows][size]*/, const float* moments /*[R][4] or NULL*/, int normalize, void* stream);
 
+/* leaf_draw_clip_plan: the plan of the three assemble_clips entries drawn ON THE DEVICE (additive: the ABI version stays 6) -- the
+ * random draws of the reference's training pipelines (pad mode, crop, gain, time masks, background noise, Gaussian amplitude) from a
+ * counter-based generator and a step counter that lives in device memory, so that a training step that begins with its batch can be
+ * captured into a graph and every replay draws a fresh plan.  One launch of ONE workgroup of 256 lanes that stride over the B clips;
+ * no workspace, nothing read back, nothing reduced.
+ *
+ *   offsets [R] int64, lengths [R] int32: the clip store's recordings (device)
+ *   noise_offsets [Rn] int64, noise_lengths [Rn] int32: the noise store's, or both NULL (then the noise outputs must be NULL too)
+ *   index [B] int64: clip b's recording -- or NULL and order [N] int64, N >= 1: clip b is order[(step B + b) mod N] (unsigned 64-bit,
+ *         wrapping).  Exactly one of index and order is given.  An entry is clamped into [0, R - 1], never trusted.
+ *   state: ONE uint64 in device memory, the step counter.  Every lane reads step = state[0]; a workgroup barrier follows; then lane 0
+ *         stores step + 1 (a plain store: one workgroup, nothing else to order).  advance == 0 leaves the counter alone.
+ *   seed, stream_base: 64 bits each, by value.  size = S in [1, 2^31), train, the two pad modes (0..3), M <= 32 spans, and the
+ *         probabilities and ranges below: by value, doubles.
+ *
+ * Outputs, in the dtypes the assemble entries take: rec_off int64, rec_len / start / pad_mode int32 (required); gain float32; masks
+ * int32 [B][M][2] (required for M > 0); rec int32 (the clip's row of moments); the noise group noise_off int64, noise_len /
+ * noise_start / noise_pad_mode int32, noise_coeff float32 [B][2] (given or NULL as a whole, together with noise_offsets /
+ * noise_lengths); the Gaussian group gauss_amp float32, gauss_stream int64 (as a whole); index_out int64 [B], the recordings chosen
+ * (the caller gathers its labels with it).  A NULL output or group is not drawn and not written.
+ *
+ * THE DRAWS are exact by definition.  Per clip b: id = stream_base + step B + b (unsigned 64-bit, wrapping).  P(q) is Philox4x32-10
+ * (the rounds of THE STREAM above) with key (lo32(seed), hi32(seed)) and counter (q, 1, lo32(id), hi32(id)) -- counter word 1 is 1
+ * here and 0 in the Gaussian stream, so id also serves as the clip's gauss_stream without the two domains meeting; r0..r3 are its
+ * four words.  u(r) = r 2^-32 in double; a uniform integer in [0, n) is (uint64(r) n) >> 32, integers only.  With i the clip's
+ * (clamped) recording, L = lengths[i] and span = max(L - S, 0):
+ *   P(0):     pad_mode = u(r0) < wrap_pad_prob ? pad_mode_a : pad_mode_b;  start = train ? (r1 (span + 1)) >> 32 : span / 2;
+ *             gain = u(r2) < gain_prob ? f32(exp((gain_db_lo + (gain_db_hi - gain_db_lo) u(r3)) (ln10 / 20))) : 1
+ *   P(1):     used = 1 + ((r0 M) >> 32)
+ *   P(2 + m): m < M: n_m = m < used ? min(S, floor((u(r0) time_perc) S)) : 0 (not below 0);  t0_m = floor(u(r1) double(S - n_m))
+ *   P(64):    applied when u(r0) < noise_prob;  snr = snr_lo + (snr_hi + 1 - snr_lo) u(r1);  noise recording j = (r2 Rn) >> 32;
+ *             noise_start = (r3 (nspan + 1)) >> 32, nspan = max(noise_lengths[j] - S, 0);  noise_len and noise_start are 0 where not
+ *             applied;  noise_pad_mode = 2;  c = r / (1 + r), r = exp(snr (ln10 / 10));  noise_coeff = (f32(c), f32(1 - c))
+ *   P(65):    gauss_amp = u(r0) < gauss_prob ? f32(gauss_amp_lo + (gauss_amp_hi - gauss_amp_lo) u(r1)) : 0;  gauss_stream = id
+ * All floating point is IEEE double in the association written, no contraction, ln10 = 2.302585092994045684, each result rounded
+ * once to float32.  The only inexact operations are the two exp: gain and noise_coeff are within one float32 ulp of the formula,
+ * everything else is bit-exact.  csrc/leaf_clip_draws.hpp is this definition as host-and-device code.
+ *
+ * These are the distributions ClipSampler draws on the host, with 32-bit uniforms in place of 53-bit ones; neither its numbers nor
+ * the reference's are reproduced.
+ *
+ * MEMORY SAFETY: index / order entries are clamped into [0, R - 1]; the noise recording is in [0, Rn - 1] by construction; nothing
+ * outside the arrays above is read, nothing outside the outputs' B entries (masks: B M 2) and state[0] is written.  The lengths go out
+ * as they are read: the assemble entries clamp them.  Alignment: 8 bytes for the int64 arrays and state, 4 for the others.
+ * Status, in this order, before the launch: LEAF_ERR_NULL_POINTER (a required pointer; neither or both of index and order; a group
+ * given in part); LEAF_ERR_BAD_SHAPE (B < 1, size < 1, R < 1, M < 0 or M > 32, M > 0 without masks, order with N < 1, the noise group
+ * with Rn < 1, a pad mode outside 0..3); LEAF_ERR_ALIGNMENT. */
+int leaf_draw_clip_plan(int B, int size, int train, const long long* offsets /*[R]*/, const int* lengths /*[R]*/, int R,
+                        const long long* noise_offsets /*[Rn] or NULL*/, const int* noise_lengths, int Rn,
+                        const long long* index /*[B] or NULL*/, const long long* order /*[N] or NULL*/, long long N,
+                        unsigned long long* state, int advance, unsigned long long seed, unsigned long long stream_base,
+                        int pad_mode_a, int pad_mode_b, double wrap_pad_prob, double gain_prob, double gain_db_lo, double gain_db_hi,
+                        int M, double time_perc, double noise_prob, double snr_lo, double snr_hi,
+                        double gauss_prob, double gauss_amp_lo, double gauss_amp_hi,
+                        long long* rec_off, int* rec_len, int* start, int* pad_mode, float* gain, int* masks /*[B][M][2]*/, int* rec,
+                        long long* noise_off, int* noise_len, int* noise_start, int* noise_pad_mode, float* noise_coeff /*[B][2]*/,
+                        float* gauss_amp, long long* gauss_stream, long long* index_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,13 @@ _SIGNATURES = {
     # ... and the rows entry with (moments, normalize) between out and stream
     "leaf_assemble_segments_std_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int]
                                        + [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    # the plan drawn on the device: B, size, train, offsets, lengths, R, noise_offsets, noise_lengths, Rn, index, order, N, state, advance,
+    # seed, stream_base, the two pad modes, wrap_pad_prob, gain_prob, gain_db (2), M, time_perc, noise_prob, snr (2), gauss_prob,
+    # gauss_amp (2), the fifteen outputs, stream
+    "leaf_draw_clip_plan": (ctypes.c_int, [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4
+                            + [ctypes.c_int] + [ctypes.c_double] * 7 + [ctypes.c_void_p] * 15 + [ctypes.c_void_p]),
     "leaf_fft_tables_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "leaf_fft_prepare_tables_f32": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_size_t, ctypes.c_void_p]),
@@ -1193,6 +1200,58 @@ def assemble_clips(store: torch.Tensor, rec_off, rec_len, start, pad_mode, size:
     moments, rec = standardize
     _call(dev, "leaf_assemble_clips_std_f32", *head, *ngroup, *ggroup, moments, rec.to(device=dev, dtype=torch.int32).contiguous(), moments.shape[0])
     return out
+
+
+DRAW_MAX_MASKS = 32             # csrc/leaf_clip_draws.hpp (kDrawMaxMasks)
+
+
+def draw_clip_plan(B: int, size: int, train: bool, offsets: torch.Tensor, lengths: torch.Tensor, state: torch.Tensor, seed: int,
+                   stream_base: int, consts: dict, out: dict, index: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None,
+                   noise_offsets: Optional[torch.Tensor] = None, noise_lengths: Optional[torch.Tensor] = None, advance: bool = True) -> None:
+    """One ``leaf_draw_clip_plan`` launch on the current stream: the plan of ``assemble_clips`` for ``B`` clips of ``size`` samples,
+    drawn on the device into the tensors of ``out`` (include/leaf_hip.h states the draws bit for bit).  Everything is device memory
+    the caller owns -- ``offsets`` int64 / ``lengths`` int32 of the clip store (and of the noise store), ``index`` (B,) int64 or
+    ``order`` (N,) int64, ``state`` one int64 holding the step counter's 64 bits -- so nothing is copied to the device, nothing is
+    read back and the call can be captured into a graph.  ``consts``: pad_modes (two of 0..3), wrap_pad_prob, gain_prob, gain_db,
+    num_masks, time_perc, noise_prob, snr_range, gaussian_prob, gaussian_amplitude.  ``out``: rec_off, rec_len, start, pad_mode
+    (required) and any of gain, masks (B, M, 2), rec, the noise group (noise_off, noise_len, noise_start, noise_pad_mode, coeff
+    (B, 2)), the Gaussian group (gauss_amp, gauss_stream), index; an absent entry is not drawn."""
+    dev = state.device
+    require_hip(state, "draw_clip_plan")
+    want = {"rec_off": (torch.int64, (B,)), "rec_len": (torch.int32, (B,)), "start": (torch.int32, (B,)), "pad_mode": (torch.int32, (B,)),
+            "gain": (torch.float32, (B,)), "masks": (torch.int32, (B, int(consts["num_masks"]), 2)), "rec": (torch.int32, (B,)),
+            "noise_off": (torch.int64, (B,)), "noise_len": (torch.int32, (B,)), "noise_start": (torch.int32, (B,)),
+            "noise_pad_mode": (torch.int32, (B,)), "coeff": (torch.float32, (B, 2)), "gauss_amp": (torch.float32, (B,)),
+            "gauss_stream": (torch.int64, (B,)), "index": (torch.int64, (B,))}
+    unknown = set(out) - set(want)
+    if unknown:
+        raise ValueError(f"draw_clip_plan: unknown outputs {sorted(unknown)}")
+    for name, t in out.items():
+        if t is not None:
+            _check_out(t, want[name][1], want[name][0], dev)
+    ins = (("offsets", offsets, torch.int64), ("lengths", lengths, torch.int32), ("noise_offsets", noise_offsets, torch.int64),
+           ("noise_lengths", noise_lengths, torch.int32), ("index", index, torch.int64), ("order", order, torch.int64), ("state", state, torch.int64))
+    for name, t, dtype in ins:
+        if t is not None and (t.dtype != dtype or t.device != dev or t.dim() != 1 or not t.is_contiguous()):
+            raise RuntimeError(f"draw_clip_plan: {name} must be a contiguous 1-D {dtype} tensor on {dev}")
+    if offsets.numel() != lengths.numel() or state.numel() != 1 or (index is not None and index.numel() != B):
+        raise ValueError("draw_clip_plan: offsets and lengths name the same recordings, state is one counter, index has one entry per clip")
+    if noise_offsets is not None and (noise_lengths is None or noise_offsets.numel() != noise_lengths.numel()):
+        raise ValueError("draw_clip_plan: noise_offsets and noise_lengths name the same recordings")
+    seed, stream_base = int(seed), int(stream_base)
+    if not (0 <= seed < 2 ** 64 and 0 <= stream_base < 2 ** 64):
+        raise ValueError("draw_clip_plan: seed and stream_base must fit 64 unsigned bits")
+    M = int(consts["num_masks"])
+    o = lambda name: out.get(name)
+    _call(dev, "leaf_draw_clip_plan", int(B), int(size), int(bool(train)), offsets, lengths, offsets.numel(),
+          noise_offsets, noise_lengths, 0 if noise_offsets is None else noise_offsets.numel(),
+          index, order, 0 if order is None else order.numel(), state, int(bool(advance)), seed, stream_base,
+          int(consts["pad_modes"][0]), int(consts["pad_modes"][1]), float(consts["wrap_pad_prob"]), float(consts["gain_prob"]),
+          float(consts["gain_db"][0]), float(consts["gain_db"][1]), M, float(consts["time_perc"]), float(consts["noise_prob"]),
+          float(consts["snr_range"][0]), float(consts["snr_range"][1]), float(consts["gaussian_prob"]),
+          float(consts["gaussian_amplitude"][0]), float(consts["gaussian_amplitude"][1]),
+          o("rec_off"), o("rec_len"), o("start"), o("pad_mode"), o("gain"), o("masks") if M > 0 else None, o("rec"),
+          o("noise_off"), o("noise_len"), o("noise_start"), o("noise_pad_mode"), o("coeff"), o("gauss_amp"), o("gauss_stream"), o("index"))
 
 
 def _recordings(store: torch.Tensor, rec_off, rec_len, who: str, size: int = 1):

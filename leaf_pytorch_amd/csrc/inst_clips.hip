@@ -259,3 +259,48 @@ int leaf_clip_moments_f32(const void* store, long long store_len, int flags, int
     if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
     return LEAF_OK;
 }
+
+// the plan of the entries above, drawn on the device: one launch of one workgroup, no workspace, nothing read back.  Each output group
+// is there or NULL as a whole; the noise group brings the noise store's two arrays with it.
+int leaf_draw_clip_plan(int B, int size, int train, const long long* offsets, const int* lengths, int R,
+                        const long long* noise_offsets, const int* noise_lengths, int Rn,
+                        const long long* index, const long long* order, long long N,
+                        unsigned long long* state, int advance, unsigned long long seed, unsigned long long stream_base,
+                        int pad_mode_a, int pad_mode_b, double wrap_pad_prob, double gain_prob, double gain_db_lo, double gain_db_hi,
+                        int M, double time_perc, double noise_prob, double snr_lo, double snr_hi,
+                        double gauss_prob, double gauss_amp_lo, double gauss_amp_hi,
+                        long long* rec_off, int* rec_len, int* start, int* pad_mode, float* gain, int* masks, int* rec,
+                        long long* noise_off, int* noise_len, int* noise_start, int* noise_pad_mode, float* noise_coeff,
+                        float* gauss_amp, long long* gauss_stream, long long* index_out, void* stream) {
+    const bool any_noise = noise_offsets || noise_lengths || noise_off || noise_len || noise_start || noise_pad_mode || noise_coeff;
+    const bool any_gauss = gauss_amp || gauss_stream;
+    if (!offsets || !lengths || !state || !rec_off || !rec_len || !start || !pad_mode) return LEAF_ERR_NULL_POINTER;
+    if (!index == !order) return LEAF_ERR_NULL_POINTER;                   // exactly one names the recordings
+    if (any_noise && !(noise_offsets && noise_lengths && noise_off && noise_len && noise_start && noise_pad_mode && noise_coeff))
+        return LEAF_ERR_NULL_POINTER;
+    if (any_gauss && !(gauss_amp && gauss_stream)) return LEAF_ERR_NULL_POINTER;
+    if (B < 1 || size < 1 || R < 1 || M < 0 || M > kDrawMaxMasks || (M > 0 && !masks) || (order && N < 1) || (any_noise && Rn < 1) ||
+        pad_mode_a < 0 || pad_mode_a > 3 || pad_mode_b < 0 || pad_mode_b > 3)
+        return LEAF_ERR_BAD_SHAPE;
+    auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (misaligned(offsets, 7u) || misaligned(lengths, 3u) || misaligned(noise_offsets, 7u) || misaligned(noise_lengths, 3u) ||
+        misaligned(index, 7u) || misaligned(order, 7u) || misaligned(state, 7u) || misaligned(rec_off, 7u) || misaligned(rec_len, 3u) ||
+        misaligned(start, 3u) || misaligned(pad_mode, 3u) || misaligned(gain, 3u) || misaligned(masks, 3u) || misaligned(rec, 3u) ||
+        misaligned(noise_off, 7u) || misaligned(noise_len, 3u) || misaligned(noise_start, 3u) || misaligned(noise_pad_mode, 3u) ||
+        misaligned(noise_coeff, 3u) || misaligned(gauss_amp, 3u) || misaligned(gauss_stream, 7u) || misaligned(index_out, 7u))
+        return LEAF_ERR_ALIGNMENT;
+    DrawParams p{};
+    p.offsets = offsets; p.lengths = lengths; p.noise_offsets = noise_offsets; p.noise_lengths = noise_lengths;
+    p.index = index; p.order = order; p.N = N; p.state = state; p.seed = seed; p.stream_base = stream_base;
+    p.k.S = size; p.k.train = train != 0; p.k.mode0 = pad_mode_a; p.k.mode1 = pad_mode_b; p.k.M = M;
+    p.k.wrap_pad_prob = wrap_pad_prob; p.k.gain_prob = gain_prob; p.k.gain_lo = gain_db_lo; p.k.gain_hi = gain_db_hi; p.k.time_perc = time_perc;
+    p.k.noise_prob = noise_prob; p.k.snr_lo = snr_lo; p.k.snr_hi = snr_hi;
+    p.k.gauss_prob = gauss_prob; p.k.amp_lo = gauss_amp_lo; p.k.amp_hi = gauss_amp_hi;
+    p.B = B; p.R = R; p.Rn = Rn; p.advance = advance != 0;
+    p.rec_off = rec_off; p.rec_len = rec_len; p.start = start; p.pad_mode = pad_mode; p.gain = gain; p.masks = M > 0 ? masks : nullptr; p.rec = rec;
+    p.noise_off = noise_off; p.noise_len = noise_len; p.noise_start = noise_start; p.noise_pad_mode = noise_pad_mode; p.noise_coeff = noise_coeff;
+    p.gauss_amp = gauss_amp; p.gauss_stream = gauss_stream; p.index_out = index_out;
+    hipLaunchKernelGGL(draw_clip_plan_kernel, dim3(1), dim3(kDrawThreads), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
+    return LEAF_OK;
+}

@@ -54,9 +54,13 @@
 // assembly kernels that map every sample of the clip's recording to (v - mean) / (std + 1e-9f) where it leaves its load
 // (clip_standardize: a subtraction and a true division, STD = true in clip_sample / clip_chunk_gather / clip_tile_load).  The plain
 // and the noise instances are the STD = false instantiations of the same functions: their instructions are what they were.
+//
+// The plan itself (leaf_draw_clip_plan) is drawn by draw_clip_plan_kernel at the end of the file: one workgroup, a clip per lane, the
+// per-clip arithmetic of leaf_clip_draws.hpp (host and device) from a counter the kernel keeps in device memory.
 #pragma once
 #include "leaf_common.hpp"
 #include "leaf_segments_view.hpp"
+#include "leaf_clip_draws.hpp"
 
 namespace {
 
@@ -887,6 +891,22 @@ __global__ __launch_bounds__(kPeakThreads) void clip_moments_fold_kernel(const M
         mo[2] = L > 0 ? mn : 0.0f;
         mo[3] = L > 0 ? mx : 0.0f;
     }
+}
+
+// ---- the plan (include/leaf_hip.h: leaf_draw_clip_plan) -------------------------------------------------------------------------------
+// ClipSampler's draws on the device: what the assembly kernels above take as their plan, written by ONE workgroup whose lanes stride
+// over the clips.  Nothing is reduced and nothing is shared but the step counter: every lane reads it, a barrier follows, and lane 0
+// alone stores step + 1 behind it (one workgroup: no other reader exists).  A draw is a function of (seed, id, counter word) --
+// leaf_clip_draws.hpp -- so which lane takes which clip does not enter it.  What the kernel cannot see it clamps: index / order
+// entries into [0, R); the lengths it reads go out as they are (the assembly kernels clamp them) and only count as max(L - S, 0).
+// The arguments (DrawParams) and one clip's reads, draws and stores (draw_plan_clip) are in leaf_clip_draws.hpp, for the host too.
+constexpr int kDrawThreads = 256;
+
+__global__ __launch_bounds__(kDrawThreads) void draw_clip_plan_kernel(const DrawParams p) {
+    const unsigned long long step = p.state[0];
+    __syncthreads();
+    if (threadIdx.x == 0 && p.advance) p.state[0] = step + 1ull;
+    for (int b = threadIdx.x; b < p.B; b += kDrawThreads) draw_plan_clip(p, step, b);
 }
 
 }  // namespace

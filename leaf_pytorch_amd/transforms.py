@@ -376,6 +376,7 @@ class ClipNoisePlan(ClipPlan):
     noise = None
     gaussian = None
     rec = None
+    index = None                                                                # DeviceClipSampler: the recordings chosen, int64 on the device
 
 
 class ClipSampler:
@@ -500,3 +501,144 @@ class ClipSampler:
                                       noise=None if noise is None else (self.noise_clips.store,) + tuple(noise),
                                       gaussian=getattr(plan, "gaussian", None),
                                       standardize=None if rec is None else (self.clips.moments(), rec))
+
+
+class DeviceClipSampler:
+    """``ClipSampler`` with the draws made ON THE DEVICE (``_native.draw_clip_plan`` -> leaf_draw_clip_plan, one launch of one
+    workgroup): the same distributions -- pad mode, crop start, gain, time masks, background noise, Gaussian amplitude; the keywords and
+    defaults are ``ClipSampler``'s -- from a counter-based generator (Philox4x32-10 keyed by ``seed``) and a step counter that lives in
+    device memory.  Nothing crosses from the host per step, so ``sampler(out=static)`` captures into a graph
+    (``torch.cuda.graph``) and every replay draws a fresh plan; include/leaf_hip.h states the draws bit for bit.
+
+    - The uniforms are 32-bit (``r * 2**-32``) where ``ClipSampler``'s are 53-bit: a spacing far below anything the pipelines can
+      see.  Neither ``ClipSampler``'s numbers nor the reference's are reproduced -- the distributions are.
+    - Clip b of step s has the id ``stream_base + s * B + b`` (64-bit, wrapping): its draws depend on (seed, id) alone, and the id is
+      also its Gaussian stream.  Samplers that share a seed (data-parallel ranks) take disjoint ``stream_base`` ranges.
+    - ``plan(index=None)`` launches the draw and returns a ``ClipNoisePlan`` of DEVICE tensors -- the sampler's static buffers, the
+      same objects on every call, overwritten by the next one -- with ``.noise`` / ``.gaussian`` / ``.rec`` as ``ClipSampler`` fills
+      them (``coeff`` as the (B, 2) float32 pairs) and ``.index``, the recordings chosen (int64: gather the labels with it; also
+      ``sampler.index`` after the call).  It advances the counter.  ``__call__(index=None, out=None)`` is ``plan`` followed by ``_native.assemble_clips`` on those tensors:
+      two launches, nothing from the host between them.
+    - ``index``: a device tensor is used as it is (a static buffer under capture; entries outside the store are clamped by the
+      kernel); a CPU tensor or sequence is validated (ValueError) and copied.  Without it clip b is ``order[(s * B + b) % len(order)]``
+      -- ``order`` an int64 device tensor the caller reshuffles in place between epochs (default: 0 .. len(clips) - 1) -- for
+      ``batch_size`` clips.
+    - ``step`` / ``set_step(n)`` read and write the counter; they are eager and the only calls that synchronise.
+    - ``standardize=True`` computes ``clips.moments()`` in the constructor, so nothing is computed under a capture.  The buffers of
+      ``batch_size`` are allocated there too; another batch size allocates its own on first use (do that before capturing).
+
+    Not built: mixup's ``perm`` / ``lam`` (a Beta sampler on the device), bfloat16."""
+
+    def __init__(self, clips: PackedClips, size: int, train: bool = True, pad_modes=("replicate", "min"), wrap_pad_prob: float = 0.5,
+                 gain_prob: float = 0.25, gain_db=(-18.0, 6.0), peak_normalize: bool = True, time_perc: float = 0.0, num_masks: int = 0,
+                 *, noise_clips=None, noise_prob: float = 0.5, snr_range=(10, 25), gaussian_prob: float = 0.0,
+                 gaussian_amplitude=(0.001, 0.015), gaussian_seed=None, standardize: bool = False, seed: int = 0, stream_base: int = 0,
+                 order=None, batch_size=None):
+        self.clips, self.size, self.train = clips, int(size), bool(train)
+        if not 1 <= self.size < _native.CALL_SAMPLES:
+            raise ValueError(f"size must be in [1, 2^31), got {self.size}")
+        self.standardize, self.peak_normalize = bool(standardize), bool(peak_normalize)
+        modes = tuple(_native.PAD_MODES[m] if isinstance(m, str) else int(m) for m in pad_modes)
+        if len(modes) != 2 or any(m not in _native.PAD_MODES.values() for m in modes):
+            raise ValueError(f"pad_modes must name two of {sorted(_native.PAD_MODES)}")
+        if not 0 <= int(num_masks) <= _native.DRAW_MAX_MASKS:
+            raise ValueError(f"num_masks must be in [0, {_native.DRAW_MAX_MASKS}], got {num_masks}")
+        if noise_clips is not None:
+            if not isinstance(noise_clips, PackedClips):
+                raise TypeError("noise_clips must be a PackedClips")
+            if noise_clips.store.dtype != clips.store.dtype:
+                raise TypeError(f"noise_clips holds {noise_clips.store.dtype} samples, the clips {clips.store.dtype}")
+            if noise_clips.store.device != clips.store.device:
+                raise ValueError(f"noise_clips is on {noise_clips.store.device}, the clips on {clips.store.device}")
+        self.noise_clips = noise_clips
+        self.consts = dict(pad_modes=modes, wrap_pad_prob=float(wrap_pad_prob), gain_prob=float(gain_prob),
+                           gain_db=(float(gain_db[0]), float(gain_db[1])), num_masks=int(num_masks), time_perc=float(time_perc),
+                           noise_prob=float(noise_prob), snr_range=(float(snr_range[0]), float(snr_range[1])),
+                           gaussian_prob=float(gaussian_prob), gaussian_amplitude=(float(gaussian_amplitude[0]), float(gaussian_amplitude[1])))
+        self.seed, self.stream_base = int(seed) % 2 ** 64, int(stream_base) % 2 ** 64
+        self.gaussian_seed = self.seed if gaussian_seed is None else int(gaussian_seed) % 2 ** 64
+        _native.require_hip(clips.store, "DeviceClipSampler")
+        dev = clips.store.device
+        self._state = torch.zeros(1, dtype=torch.int64, device=dev)             # the step counter's 64 bits
+        if order is None:
+            order = torch.arange(len(clips), dtype=torch.int64, device=dev)
+        if not isinstance(order, torch.Tensor) or order.dtype != torch.int64 or order.device != dev or order.dim() != 1 or order.numel() < 1:
+            raise ValueError(f"order must be a 1-D int64 tensor of at least one entry on {dev}")
+        self.order = order.contiguous()
+        self.moments = clips.moments() if self.standardize else None
+        self.batch_size = None if batch_size is None else int(batch_size)
+        self._plans = {}                                                        # batch size -> (plan, out dict, index buffer)
+        self.index = None                                                       # the last plan's recordings (its static buffer)
+        if self.batch_size is not None:
+            self._buffers(self.batch_size)
+
+    def _buffers(self, B: int):
+        if B not in self._plans:
+            if B < 1:
+                raise ValueError(f"a batch needs at least one clip, got {B}")
+            dev, M = self.clips.store.device, self.consts["num_masks"]
+            new = lambda dtype, *shape: torch.zeros(shape, dtype=dtype, device=dev)
+            out = dict(rec_off=new(torch.int64, B), rec_len=new(torch.int32, B), start=new(torch.int32, B), pad_mode=new(torch.int32, B),
+                       gain=new(torch.float32, B), index=new(torch.int64, B))
+            if M > 0:
+                out["masks"] = new(torch.int32, B, M, 2)
+            if self.standardize:
+                out["rec"] = new(torch.int32, B)
+            if self.noise_clips is not None:
+                out.update(noise_off=new(torch.int64, B), noise_len=new(torch.int32, B), noise_start=new(torch.int32, B),
+                           noise_pad_mode=new(torch.int32, B), coeff=new(torch.float32, B, 2))
+            if self.consts["gaussian_prob"] > 0.0:
+                out.update(gauss_amp=new(torch.float32, B), gauss_stream=new(torch.int64, B))
+            plan = ClipNoisePlan((out["rec_off"], out["rec_len"], out["start"], out["pad_mode"], out["gain"], out.get("masks")))
+            plan.index, plan.rec = out["index"], out.get("rec")
+            if self.noise_clips is not None:
+                plan.noise = (out["noise_off"], out["noise_len"], out["noise_start"], out["noise_pad_mode"], out["coeff"])
+            if "gauss_amp" in out:
+                plan.gaussian = (out["gauss_amp"], self.gaussian_seed, out["gauss_stream"])
+            self._plans[B] = (plan, out, new(torch.int64, B))
+        return self._plans[B]
+
+    @property
+    def step(self) -> int:
+        """The counter: the step the next ``plan`` draws (synchronises)."""
+        return int(self._state.item()) % 2 ** 64
+
+    def set_step(self, n: int) -> None:
+        """Position the counter: the next ``plan`` draws step ``n`` (mod 2^64)."""
+        n = int(n) % 2 ** 64
+        self._state.fill_(n - 2 ** 64 if n >= 2 ** 63 else n)
+
+    def plan(self, index=None, advance: bool = True) -> ClipNoisePlan:
+        if index is None:
+            if self.batch_size is None:
+                raise ValueError("without an index the sampler walks `order`: construct it with batch_size")
+            B, dindex = self.batch_size, None
+        else:
+            if not isinstance(index, torch.Tensor):
+                index = torch.as_tensor(index, dtype=torch.int64)
+            if index.dtype.is_floating_point or index.dtype == torch.bool:
+                raise TypeError(f"index must be an integer tensor or sequence, got {index.dtype}")
+            index = index.reshape(-1)
+            B = index.numel()
+        plan, out, ibuf = self._buffers(B)
+        if index is not None:
+            if index.device.type == "cpu":
+                if int(index.min()) < 0 or int(index.max()) >= len(self.clips):
+                    raise ValueError(f"index holds a recording outside [0, {len(self.clips)})")
+                dindex = ibuf.copy_(index)
+            else:
+                dindex = index.to(torch.int64).contiguous()
+        nc = self.noise_clips
+        _native.draw_clip_plan(B, self.size, self.train, self.clips.offsets, self.clips.lengths, self._state, self.seed, self.stream_base,
+                               self.consts, out, index=dindex, order=None if dindex is not None else self.order,
+                               noise_offsets=None if nc is None else nc.offsets, noise_lengths=None if nc is None else nc.lengths,
+                               advance=advance)
+        self.index = plan.index
+        return plan
+
+    def __call__(self, index=None, out=None) -> torch.Tensor:
+        plan = self.plan(index)
+        rec_off, rec_len, start, pad_mode, gain, masks = plan
+        return _native.assemble_clips(self.clips.store, rec_off, rec_len, start, pad_mode, self.size, gain, self.peak_normalize, masks, out,
+                                      noise=None if plan.noise is None else (self.noise_clips.store,) + plan.noise,
+                                      gaussian=plan.gaussian, standardize=None if plan.rec is None else (self.moments, plan.rec))

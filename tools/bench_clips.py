@@ -7,6 +7,7 @@ multiply by the gain, transforms.PeakNormalization, one masked_fill per span.
     python tools/bench_clips.py --noise [--out profiles/clip_noise.txt]
     python tools/bench_clips.py --segments [--out profiles/eval_segments.txt]
     python tools/bench_clips.py --standardize [--out profiles/clip_standardize.txt]
+    python tools/bench_clips.py --device-draws [--out profiles/clip_device_draws.txt]
 
 Both sides run in ONE process on the same store and the same plan (already on the device: drawing it is not timed), taking turns
 round after round after a warm-up round, the order alternating.  Every recording is longer than the clip, so the batch is a crop
@@ -43,7 +44,17 @@ whole store; float32 stores only use it) is timed on its own, in rounds of its o
 leaf_assemble_clips_f32 on the same plan (what the keyword costs, and whether the plain launch is what it was); `stock`, what a user
 without the entry keeps -- a float32 copy of the whole store standardised per recording by the reference's expression (made once on
 the CPU from the library's moments, not timed) -- through the stock chain of the first table.  The std and stock batches are compared
-bit for bit before anything is timed.  The one-time PackedClips.moments() call (leaf_clip_moments_f32) is timed in rounds of its own."""
+bit for bit before anything is timed.  The one-time PackedClips.moments() call (leaf_clip_moments_f32) is timed in rounds of its own.
+
+--device-draws times a training step's batch INCLUDING its random draws: B = 64 / 256 clips of 16 000 samples, both stores, three time
+masks and background noise on.  Five sides take turns: `host`, ClipSampler.__call__ with a CPU index (the draws on the CPU from a
+torch.Generator, the plan uploaded: the path as it was, the baseline); `device`, DeviceClipSampler.__call__ (leaf_draw_clip_plan, then
+the assembling launch on its static buffers); `graph`, the replay of that pair captured with torch.cuda.graph; and, for the device
+time of each launch on its own, `plan` (DeviceClipSampler.plan alone) and `assemble` (_native.assemble_clips on the static plan).  A
+round is --steps calls (default here: 40) and one synchronisation, so `wall` is the host time per call of a loop that synchronises
+every 40 calls.  Before anything is timed the replayed batch is compared bit for bit with the eager batch of a second sampler of the
+same seed at the same step.  The last column is the verdict the comparison is made for: `device` wall must not exceed `host` wall by
+more than the run-to-run spread of `host` (max - min of its rounds' wall times, measured here, not fixed)."""
 import argparse
 import os
 import statistics
@@ -280,6 +291,64 @@ def standardize_legs(args, busy, busy_out):
     return lines
 
 
+def device_draw_legs(args, busy, busy_out):
+    from leaf_pytorch_amd import ClipSampler, DeviceClipSampler
+    S = 16000
+    steps = args.steps if args.steps_given else 40
+    lines = [f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {args.rounds} timed rounds x {steps} calls per side after a "
+             "warm-up round, one synchronisation per round; us per call: median [min, max]; device = HIP events, calls queued behind a matrix "
+             "product; wall = host clock to the synchronise; host = ClipSampler.__call__ (draws on the CPU, plan uploaded), device = "
+             "DeviceClipSampler.__call__ (leaf_draw_clip_plan + the assembling launch), graph = replay of that pair captured, plan / assemble = "
+             "each launch alone; 3 masks and background noise on; spread = max - min of host's wall over the rounds",
+             f"{'store':>8} {'B':>4} | {'host wall':>26} {'host device':>11} | {'device wall':>26} {'device device':>13} | {'graph wall':>26} "
+             f"{'graph device':>12} | {'plan device':>24} {'assemble device':>24} | {'spread':>7} {'device <= host + spread':>23}"]
+    for dtype in (torch.int16, torch.float32):
+        for B in (64, 256):
+            g = torch.Generator().manual_seed(B)
+
+            def packed(n_rec, seed):
+                gg = torch.Generator().manual_seed(seed)
+                lengths = torch.randint(S + 1, 3 * S, (n_rec,), generator=gg).tolist()
+                recs = [(torch.randint(-32768, 32768, (n,), generator=gg).to(torch.int16) if dtype == torch.int16
+                         else torch.rand(n, generator=gg) * 2 - 1) for n in lengths]
+                return PackedClips(recs, device=DEV)
+
+            clips, nclips = packed(B, B + S), packed(32, B + S + 1)
+            kw = dict(num_masks=M, time_perc=0.1, noise_clips=nclips)
+            host = ClipSampler(clips, S, generator=g, **kw)
+            dev, twin = (DeviceClipSampler(clips, S, seed=1234, batch_size=B, **kw) for _ in range(2))
+            index = torch.arange(B)
+            out = torch.empty((B, 1, S), dtype=torch.float32, device=DEV)
+            static = torch.empty((B, 1, S), dtype=torch.float32, device=DEV)
+            dev(out=static)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                dev(out=static)
+            twin.set_step(dev.step)
+            for _ in range(2):
+                graph.replay()
+                want = twin()
+                torch.cuda.synchronize()
+                if not torch.equal(static.view(torch.int32), want.view(torch.int32)):
+                    sys.exit(f"the replayed batch is not the eager one at {dtype} B={B}: nothing is timed")
+            plan = dev.plan()
+            rec_off, rec_len, start, pad_mode, gain, masks = plan
+            noise = (nclips.store,) + plan.noise
+            sides = {"host": lambda: host(index, out=out), "device": lambda: dev(out=out), "graph": graph.replay, "plan": dev.plan,
+                     "assemble": lambda: _native.assemble_clips(clips.store, rec_off, rec_len, start, pad_mode, S, gain, True, masks, out, noise=noise)}
+            dev_us, wall_us = time_sides(sides, args.rounds, steps, busy, busy_out)
+            fmt = lambda v: f"{statistics.median(v):9.1f} [{min(v):6.1f},{max(v):7.1f}]"
+            med = lambda v: statistics.median(v)
+            spread = max(wall_us["host"]) - min(wall_us["host"])
+            ok = med(wall_us["device"]) <= med(wall_us["host"]) + spread
+            lines.append(f"{str(dtype).replace('torch.', ''):>8} {B:>4} | {fmt(wall_us['host']):>26} {med(dev_us['host']):11.1f} | {fmt(wall_us['device']):>26} "
+                         f"{med(dev_us['device']):13.1f} | {fmt(wall_us['graph']):>26} {med(dev_us['graph']):12.1f} | {fmt(dev_us['plan'])} "
+                         f"{fmt(dev_us['assemble'])} | {spread:7.1f} {'PASS' if ok else 'FAIL':>23}")
+            print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=20)
@@ -288,12 +357,15 @@ def main():
     ap.add_argument("--noise", action="store_true", help="time the launch with background and Gaussian noise (profiles/clip_noise.txt)")
     ap.add_argument("--segments", action="store_true", help="time the whole-recording evaluation batch (profiles/eval_segments.txt)")
     ap.add_argument("--standardize", action="store_true", help="time the standardising launch (profiles/clip_standardize.txt)")
+    ap.add_argument("--device-draws", action="store_true", help="time the batch with its draws: ClipSampler, DeviceClipSampler, the captured graph "
+                                                                "(profiles/clip_device_draws.txt)")
     args = ap.parse_args()
+    args.steps_given = any(a == "--steps" or a.startswith("--steps=") for a in sys.argv[1:])
     if not torch.cuda.is_available():
         sys.exit("bench_clips.py needs the GPU: a time taken anywhere else says nothing about it")
-    if args.noise or args.segments or args.standardize:
+    if args.noise or args.segments or args.standardize or args.device_draws:
         busy = torch.rand(8192, 8192, device=DEV)
-        legs = standardize_legs if args.standardize else (segment_legs if args.segments else noise_legs)
+        legs = device_draw_legs if args.device_draws else (standardize_legs if args.standardize else (segment_legs if args.segments else noise_legs))
         text = "\n".join(legs(args, busy, torch.empty_like(busy))) + "\n"
         print(text)
         if args.out:
