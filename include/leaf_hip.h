@@ -141,6 +141,9 @@ typedef enum leaf_status {
                                   LEAF_FLAG_IO_BF16 it is redundant and accepted.  LEAF_ALGO_STAGED, explicit or what AUTO
                                   resolves to, answers LEAF_ERR_UNSUPPORTED before the workspace check and before any launch,
                                   as for bfloat16 I/O. */
+#define LEAF_FLAG_OUT_PCM16 0x400 /* extension (additive: the ABI version stays 6), leaf_resample_f32 only: `out` is an int16_t buffer
+                                  (2-byte aligned) and each output is q = rintf(y * 32768.0f), round half to even, clamped to
+                                  [-32768, 32767] (saturating, never wrapping), NaN -> 0.  No other entry names this bit. */
 
 /* algorithm selector for the fused path */
 #define LEAF_ALGO_AUTO   0     /* _FFT_SMALL for a handful of clips of a LEAF geometry; else the FFT kernels when their plan fits and K >= 224 or the geometry has a static instance, else MFMA, else staged */
@@ -913,6 +916,82 @@ int leaf_draw_clip_plan(int B, int size, int train, const long long* offsets /*[
                         long long* rec_off, int* rec_len, int* start, int* pad_mode, float* gain, int* masks /*[B][M][2]*/, int* rec,
                         long long* noise_off, int* noise_len, int* noise_start, int* noise_pad_mode, float* noise_coeff /*[B][2]*/,
                         float* gauss_amp, long long* gauss_stream, long long* index_out, void* stream);
+
+/* Resampling of a packed store on the device (additive: the ABI version stays 6).  The reference's loaders stop at
+ * `assert clip_sr == sr` (utilities/data/utils.py:109,159): they expect a data set that was resampled on disk.  The entries below bring
+ * every recording of a packed store from orig_freq to new_freq in one call, int16 in and int16 out where asked, without a float32
+ * copy and without a sample of one recording reaching its neighbour.
+ *
+ * THE DEFINITION is the band-limited interpolation torchaudio.functional.resample documents (Hann-windowed sinc, polyphase), stated
+ * here exactly; csrc/leaf_resample.hpp is this statement as host-and-device code.  Inputs: integers orig_freq > 0, new_freq > 0,
+ * W = lowpass_width >= 1 (torchaudio's default 6), rho = rolloff in (0, 1] (0.99).
+ *   g = gcd(orig_freq, new_freq), o = orig_freq / g, n = new_freq / g;  base = (double)min(o, n) * rho;  width = ceil(W * o / base).
+ *   For phase p in [0, n) and tap k in [0, 2 width + o): num = (k - width) * n - p * o in int64, t = (double)num * base / (double)(o * n).
+ *   The tap belongs to the phase's SPAN iff |t| < W.  The span is contiguous: k0[p] is its first tap, cnt[p] its size (12 - 13 taps at
+ *   44.1 -> 48 kHz, 33 - 34 at 44.1 -> 16 kHz, 37 at 48 -> 16 kHz).  Inside it
+ *       h[p][k] = fp32( sinc(t) * cos^2(pi t / (2 W)) * base / o ),   sinc(0) = 1, sinc(t) = sin(pi t) / (pi t),
+ *   evaluated in double and rounded once.  Taps outside the span are exactly 0 and are never applied (torchaudio evaluates its window
+ *   there and is left with ~1e-33; this library has nothing there).
+ *   o == n is special: one phase whose only tap is 1 (width = 0).  Resampling to the same rate is then the identity on every bit
+ *   pattern but two: -0 comes back as +0 and a signalling NaN as its quiet twin (payload kept), because the sample still passes
+ *   through the chain below, fmaf(1, x, +0).  It also serves as the int16 <-> float32 conversion.
+ * For a recording x[0, L), zeros outside it: out_len = ceil(n L / o) = (n L + o - 1) / o in 64 bits, and for j = i n + p
+ *       y[j] = sum over the span, k ascending, of h[p][k] * x[i o + k - width],
+ * accumulated in float32 as ONE chain acc = fmaf(h, x, acc) from acc = +0.0f: every tap of the span is applied, a sample outside
+ * [0, L) enters as +0.0f, an int16 sample v means v * 2^-15 as everywhere.  The fixed order makes y a pure function of the recording:
+ * it does not depend on the neighbours in the store, the offsets, the alignment, the number of recordings, the tile or the path, and
+ * a CPU build of the same function (tools/resample_check.cpp) has the kernel's bits.  Against the formula in real numbers,
+ * |y - y*| <= (cnt + 2) 2^-24 sum |h| |x| + 2^-149.
+ * Output: float32, or int16 with LEAF_FLAG_OUT_PCM16: q = rintf(y * 32768.0f), round half to even, clamped to [-32768, 32767] --
+ * the Gibbs overshoot of a full-scale signal saturates, it never wraps -- and NaN gives 0.
+ *
+ * The length, the table and the workspace:
+ *   The length entry answers out_len for any L (L <= 0: 0; saturating at 2^63 - 1) and 0 for a frequency <= 0, as a size_t like the
+ *   other size queries.  Host only.
+ *   The table, host only, no GPU: the size query answers the bytes of the library's own compact layout for these parameters (0 for
+ *   parameters the call would refuse), and the builder writes it to HOST memory: eight int32 header words (a magic number, o, n,
+ *   width, stride, taps_in_lds, 0, 0), k0[n] and cnt[n] int32, then n rows of `stride` float32 taps -- row p holds h[p][k0 .. k0 + cnt)
+ *   and zeros behind; stride is the largest cnt made odd.  The caller uploads it once per (orig_freq, new_freq, W, rho) and hands the
+ *   device copy to every call.  The call recomputes o, n, width and stride on the host and reads none of them from the
+ *   device; taps_in_lds is the one word the kernel reads: what the library would choose, and a caller may clear it to keep the taps
+ *   in global memory where they would fit LDS (the same bits: the plan's switch between the two tap paths, which the tests use;
+ *   setting it where the host finds no room changes nothing).  The builder's status: LEAF_ERR_UNSUPPORTED, LEAF_ERR_NULL_POINTER, LEAF_ERR_BAD_SHAPE (also for
+ *   table_bytes other than the size query), LEAF_ERR_ALIGNMENT (4 bytes).
+ *   The workspace: 8 (R + 1) bytes (0 for R < 1), overwritten.
+ *
+ * The call:
+ *   store, store_len, flags: as in leaf_assemble_clips_f32, flags also LEAF_FLAG_OUT_PCM16            R: the number of recordings
+ *   in_off [R] int64, in_len [R] int32: the recordings          out_off [R] int64: where each recording's output begins in `out`
+ *   table, table_bytes: the device copy of the table for the SAME four parameters
+ *   out: out_total samples, float32 or int16
+ * The work is split by TILES of 1024 output samples, not by recording: a first launch of one workgroup writes the tile prefix of the
+ * clamped plan into the workspace, a second runs the tiles, one workgroup of 256 lanes each -- one long recording spreads over the
+ * chip, a short one costs one workgroup, a tile never spans two recordings.  A tile stages its input window (about 1024 o / n +
+ * 2 width + o samples) into LDS as float32, converting int16 in the load and ZERO-FILLING everything outside [0, L): that zero fill is
+ * the padding rule and what keeps the neighbouring recording out.  Taps come from LDS when table and window fit 64 KB per workgroup,
+ * otherwise from global memory (4096 -> 4099 has a 213 KB table); a window beyond the budget (from o / n of about 15: 16 -> 1, 44100 -> 2000) is read from
+ * global memory too.  Stores are 16-byte chunks where out's alignment allows, element stores at a tile's two ends.
+ *
+ * MEMORY SAFETY: what the library cannot inspect is clamped by the kernel.  in_off / in_len as in leaf_assemble_clips_f32; out_off
+ * into [0, out_total]; a record's output length is min(out_len of the clamped L, out_total - out_off); every k0 / cnt read from the
+ * table is clamped against the staged window (cnt into [0, stride], k0 into [0, 2 width + o - cnt]); o, n, width and stride are
+ * recomputed on the host, never read from the table.  Whatever plan or table the caller hands in, nothing outside store[0, store_len)
+ * and table[0, table_bytes) is read, nothing outside out[0, out_total) and the workspace is written.  Records whose outputs overlap
+ * leave the overlap to whichever tile stores last.
+ * Alignment: store and out 4 bytes (2 for int16), in_off and out_off 8, in_len and table 4, workspace 16.  Status, in this order, before
+ * any launch: LEAF_ERR_UNSUPPORTED for a flag other than LEAF_FLAG_X_PCM16 / LEAF_FLAG_OUT_PCM16, for a reduced o or n above 65535 and
+ * for a table above 2^26 bytes; LEAF_ERR_NULL_POINTER (store, in_off, in_len, table, out, out_off); LEAF_ERR_BAD_SHAPE for R < 1, a
+ * negative store_len or out_total, a frequency <= 0, lowpass_width < 1, rolloff outside (0, 1], or table_bytes other than the size
+ * query; LEAF_ERR_ALIGNMENT; LEAF_ERR_WORKSPACE.  out must not overlap the store.
+ * Not built: the Kaiser window, a streaming resampler with carried state, gradients, bfloat16. */
+size_t leaf_resample_length(long long L, int orig_freq, int new_freq);
+size_t leaf_resample_table_bytes(int orig_freq, int new_freq, int lowpass_width, double rolloff);
+int leaf_resample_table_f32(int orig_freq, int new_freq, int lowpass_width, double rolloff, void* table_host, size_t table_bytes);
+size_t leaf_resample_workspace_bytes(int R);
+int leaf_resample_f32(const void* store, long long store_len, int flags, int R, const long long* in_off /*[R]*/,
+                      const int* in_len /*[R]*/, int orig_freq, int new_freq, int lowpass_width, double rolloff,
+                      const void* table /*device*/, size_t table_bytes, void* out, long long out_total,
+                      const long long* out_off /*[R]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

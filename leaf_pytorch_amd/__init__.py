@@ -7,10 +7,10 @@ from .modules import (ExponentialMovingAverage, GaborConstraint, GaborConv1d, Ga
 from .initializers import GaborFilter, GaborInit
 from ._native import build, load, LIB_PATH
 from .transforms import (CenterCrop, ClipSampler, DeviceClipSampler, PackedClips, PeakNormalization, RandomCrop, evaluate_recordings,
-                         segment_mean)
+                         resample, segment_mean)
 from .streaming import LeafStream, LeafStreamBank
 
 __all__ = ["Leaf", "SquaredModulus", "get_frontend", "GaborConv1d", "GaborConstraint", "GaussianLowPass",
            "ExponentialMovingAverage", "PCENLayer", "GaborInit", "GaborFilter", "get_padding_value", "build", "load",
            "PeakNormalization", "CenterCrop", "RandomCrop", "PackedClips", "ClipSampler", "DeviceClipSampler", "LeafStream", "LeafStreamBank",
-           "segment_mean", "evaluate_recordings"]
+           "segment_mean", "evaluate_recordings", "resample"]

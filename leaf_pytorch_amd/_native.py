@@ -32,6 +32,7 @@ def algo_reserve_cus(k: int) -> int:
 FLAG_PCEN, FLAG_LOG1P, FLAG_IO_BF16, FLAG_BWD_STAGED, FLAG_BWD_MFMA, FLAG_PEAKNORM, FLAG_BWD_FULL_TRANSFORMS = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
 FLAG_X_PCM16 = 0x100           # x is int16 PCM (a sample v means v / 32768); everything else stays float32
 FLAG_OUT_BF16 = 0x200          # the feature side alone is bfloat16: out of the forward, grad_out of the backward; x as its own flags say
+FLAG_OUT_PCM16 = 0x400         # leaf_resample_f32: the output is int16 PCM, rint(y * 32768) saturated
 FLAG_BWD_STRICT_BAND_CLASSES = 0x80   # leaf_backward_f32: the backward's band classes by round 5's rule alone (default: the forward's bias-aware decision)
 ALGO_STREAM_FINALIZE = 1 << 25   # LEAF_ALGO_STREAM_FINALIZE: per-frame sums in an LDS ring, finalized as the blocks complete
 ALGO_FULL_TRANSFORMS = 1 << 26   # LEAF_ALGO_FULL_TRANSFORMS: no band-limited filter tasks (every filter on 2048-point transforms)
@@ -138,6 +139,16 @@ _SIGNATURES = {
                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
                                            ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4
                             + [ctypes.c_int] + [ctypes.c_double] * 7 + [ctypes.c_void_p] * 15 + [ctypes.c_void_p]),
+    # resampling: the output length (L, orig_freq, new_freq); the table's bytes and the table itself, on the host (orig_freq, new_freq,
+    # lowpass_width, rolloff[, table, table_bytes]); the workspace (R); the call -- store, store_len, flags, R, in_off, in_len, the four
+    # parameters, table, table_bytes, out, out_total, out_off, workspace, workspace_bytes, stream
+    "leaf_resample_length": (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
+    "leaf_resample_table_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double]),
+    "leaf_resample_table_f32": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t]),
+    "leaf_resample_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "leaf_resample_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t,
+                                         ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "leaf_fft_tables_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "leaf_fft_prepare_tables_f32": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_size_t, ctypes.c_void_p]),
@@ -1349,6 +1360,130 @@ def assemble_segments(store: torch.Tensor, rec_off, rec_len, win, size: int, pea
           rows, size, rec_off.to(device=dev, dtype=torch.int64).contiguous(), rec_len.to(device=dev, dtype=torch.int32).contiguous(),
           win.to(device=dev, dtype=torch.int64).contiguous(), _ptr(peaks),
           None if peaks is None else rec.to(device=dev, dtype=torch.int32).contiguous(), 0 if peaks is None else peaks.numel(), out)
+    return out
+
+
+RESAMPLE_TILE = 1024             # csrc/leaf_resample.hpp (kResampleTile): output samples per tile, one workgroup each
+RESAMPLE_LDS_BUDGET = 64 * 1024  # ... (kResampleLdsBudget): bytes of LDS a workgroup may take for outputs, window and table
+RESAMPLE_HEADER_INTS = 8         # ... (kResampleHeaderInts): magic, o, n, width, stride, taps_in_lds, 0, 0
+_resample_tables: dict = {}
+
+
+def _resample_params(orig_freq, new_freq, lowpass_filter_width, rolloff):
+    """The four parameters as the C ABI takes them; ValueError for what it would answer with LEAF_ERR_BAD_SHAPE."""
+    for name, v in (("orig_freq", orig_freq), ("new_freq", new_freq), ("lowpass_filter_width", lowpass_filter_width)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    orig_freq, new_freq, W, rolloff = int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff)
+    if not (0 < orig_freq < 2 ** 31 and 0 < new_freq < 2 ** 31):
+        raise ValueError(f"orig_freq and new_freq must be in [1, 2^31), got {orig_freq} and {new_freq}")
+    if not 1 <= W < 2 ** 31:
+        raise ValueError(f"lowpass_filter_width must be at least 1, got {W}")
+    if not 0.0 < rolloff <= 1.0:
+        raise ValueError(f"rolloff must be in (0, 1], got {rolloff}")
+    return orig_freq, new_freq, W, rolloff
+
+
+class ResampleTable:
+    """The plan and the taps of one (orig_freq, new_freq, lowpass_filter_width, rolloff), on the CPU: ``o, n, width`` (the reduced
+    ratio and the half width in input samples), ``k0`` / ``cnt`` (int32 (n,): every phase's span), ``taps`` (float32 (n, stride):
+    row p holds the span's taps and zeros behind them), ``taps_in_lds`` / ``window_in_lds`` (the path the tiles take) and ``words``,
+    the table as leaf_resample_table_f32 wrote it (int32).  ``on(device)`` is the device copy, uploaded on first use and kept.
+
+    Tables and their device copies live as long as the process (``resample_table`` keeps one per key, this object one copy per
+    device): a few hundred bytes to a few hundred KB for audio ratios, up to 64 MB at the library's limit.  That suits a handful
+    of ratios; ``drop_resample_tables()`` releases them all."""
+
+    def __init__(self, key, words: torch.Tensor):
+        self.key, self.words = key, words
+        _, self.o, self.n, self.width, self.stride, lds = (int(v) for v in words[:6])
+        n, h = self.n, RESAMPLE_HEADER_INTS
+        self.k0, self.cnt = words[h: h + n], words[h + n: h + 2 * n]
+        self.taps = words[h + 2 * n:].view(torch.float32).reshape(n, self.stride)
+        window = ((RESAMPLE_TILE - 1) // n + 2) * self.o + 2 * self.width
+        self.window_in_lds = 4 * (window + RESAMPLE_TILE) <= RESAMPLE_LDS_BUDGET
+        self.taps_in_lds = bool(lds)
+        self._device = {}
+
+    def on(self, device) -> torch.Tensor:
+        device = torch.device(device)
+        if device not in self._device:
+            self._device[device] = self.words.to(device)
+        return self._device[device]
+
+    def with_global_taps(self) -> "ResampleTable":
+        """The same table with ``taps_in_lds`` cleared: the tiles read their taps from global memory (the same bits; a test switch).
+        The copy is the caller's: ``resample_table`` does not keep it."""
+        words = self.words.clone()
+        words[5] = 0
+        return ResampleTable(self.key, words)
+
+
+def drop_resample_tables() -> None:
+    """Forget every kept table and its device copies; the next ``resample_table`` builds and uploads again."""
+    with _lock:
+        _resample_tables.clear()
+
+
+def resample_table(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> ResampleTable:
+    """The table of leaf_resample_f32 for these parameters (leaf_resample_table_f32: host only, evaluated in double and rounded once;
+    no GPU is needed), kept per key.  ValueError for parameters outside the definition or beyond what the library takes (a reduced
+    ratio above 65535, a table above 2^26 bytes)."""
+    key = _resample_params(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    with _lock:
+        table = _resample_tables.get(key)
+    if table is None:
+        lib = load()
+        nbytes = lib.leaf_resample_table_bytes(*key)
+        if nbytes == 0:
+            raise ValueError(f"resampling {key[0]} -> {key[1]} (width {key[2]}, rolloff {key[3]}) is beyond the library: the reduced "
+                             "ratio's terms stay at or below 65535 and the table below 2^26 bytes")
+        words = torch.empty(nbytes // 4, dtype=torch.int32)
+        check(lib.leaf_resample_table_f32(*key, ctypes.c_void_p(words.data_ptr()), nbytes), "leaf_resample_table_f32")
+        table = ResampleTable(key, words)
+        with _lock:
+            table = _resample_tables.setdefault(key, table)
+    return table
+
+
+def resample_length(L: int, orig_freq: int, new_freq: int) -> int:
+    """``ceil(L * n / o)`` for the reduced ratio (leaf_resample_length): the samples a recording of ``L`` samples becomes."""
+    if int(orig_freq) <= 0 or int(new_freq) <= 0 or int(orig_freq) >= 2 ** 31 or int(new_freq) >= 2 ** 31:
+        raise ValueError(f"orig_freq and new_freq must be in [1, 2^31), got {orig_freq} and {new_freq}")
+    return int(load().leaf_resample_length(int(L), int(orig_freq), int(new_freq)))
+
+
+def resample_records(store: torch.Tensor, in_off: torch.Tensor, in_len: torch.Tensor, orig_freq: int, new_freq: int, out: torch.Tensor,
+                     out_off: torch.Tensor, lowpass_filter_width: int = 6, rolloff: float = 0.99, table: Optional[ResampleTable] = None,
+                     ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """leaf_resample_f32 as it is: the recordings ``store[in_off[i] : in_off[i] + in_len[i]]`` (1-D float32 or int16 on the device;
+    ``in_off`` int64 and ``in_len`` int32 on the device) resampled into ``out`` (1-D float32 or int16) from ``out_off[i]`` (int64 on
+    the device) on, in one call.  The plan is used unseen: the kernel clamps it.  ``table``: another table of the same parameters
+    (``ResampleTable.with_global_taps``); ``ws``: a workspace of the caller's (uint8, at
+    least the size query)."""
+    require_hip(store, "resample_records")
+    dev = store.device
+    if store.dim() != 1 or store.dtype not in (torch.float32, torch.int16) or not store.is_contiguous():
+        raise TypeError("store must be a contiguous 1-D float32 or int16 tensor")
+    if out.dim() != 1 or out.dtype not in (torch.float32, torch.int16) or not out.is_contiguous() or out.device != dev:
+        raise TypeError("out must be a contiguous 1-D float32 or int16 tensor on the store's device")
+    R = in_off.numel()
+    for name, t, dt in (("in_off", in_off, torch.int64), ("in_len", in_len, torch.int32), ("out_off", out_off, torch.int64)):
+        if t.dtype != dt or t.device != dev or t.numel() != R or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous {dt} tensor of {R} entries on {dev}")
+    key = _resample_params(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    table = resample_table(*key) if table is None else table
+    if table.key != key:
+        raise ValueError(f"the table was built for {table.key}, the call is {key}")
+    if R == 0:
+        return out
+    words = table.on(dev)
+    flags = (FLAG_X_PCM16 if store.dtype == torch.int16 else 0) | (FLAG_OUT_PCM16 if out.dtype == torch.int16 else 0)
+    args = (store, store.numel(), flags, R, in_off, in_len, *key, words, words.numel() * 4, out, out.numel(), out_off)
+    if ws is None:
+        _call(dev, "leaf_resample_f32", *args, ws=lambda lib: lib.leaf_resample_workspace_bytes(R))
+    else:
+        _call(dev, "leaf_resample_f32", *args, ws, ws.numel())
     return out
 
 

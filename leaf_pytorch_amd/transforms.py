@@ -304,6 +304,71 @@ class PackedClips:
             return self._segment_rows(rec, win, int(size), normalize, out, standardize=True), counts
         return self._segment_rows(rec, win, int(size), normalize, out), counts
 
+    def resampled(self, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99, out_dtype=None) -> "PackedClips":
+        """Every recording brought from ``orig_freq`` to ``new_freq`` (``resample``'s definition) in ONE leaf_resample_f32 call for the
+        whole data set: a new ``PackedClips`` on the same device whose recording i has ``ceil(L_i n / o)`` samples, packed back to back
+        in the order of this one.  ``lengths_host`` / ``offsets_host`` are integer work on the host; the samples never leave the device,
+        and an int16 store stays int16 unless ``out_dtype`` says otherwise.  The zero fill outside a recording is the kernel's, so no
+        sample of a neighbour enters a result; kept ``peaks()`` and ``moments()`` are not carried over."""
+        out_dtype = _resample_out_dtype(self.store.dtype, out_dtype)
+        key = _native._resample_params(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        table = _native.resample_table(*key)
+        L = self.lengths_host.to(torch.int64)
+        lengths = (L * table.n + (table.o - 1)) // table.o                       # L < 2^31, n <= 65535: 64 bits hold it
+        if lengths.numel() and int(lengths.max()) >= 2 ** 31:
+            raise ValueError(f"a recording would have {int(lengths.max())} samples at {new_freq} Hz: beyond the 32-bit length of a recording")
+        offsets = torch.cumsum(lengths, 0) - lengths
+        dev = self.store.device
+        out = torch.empty(int(lengths.sum()), dtype=out_dtype, device=dev)
+        if out.numel():
+            _native.resample_records(self.store, self.offsets, self.lengths, key[0], key[1], out, offsets.to(dev), key[2], key[3])
+        return PackedClips.from_store(out, offsets, lengths)
+
+
+def _resample_out_dtype(dtype: torch.dtype, out_dtype) -> torch.dtype:
+    out_dtype = dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.int16):
+        raise TypeError(f"out_dtype must be torch.float32 or torch.int16, got {out_dtype}")
+    return out_dtype
+
+
+def resample(x: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
+             out_dtype=None) -> torch.Tensor:
+    """``x`` ``(..., T)``, float32 or int16 PCM on the device, from ``orig_freq`` to ``new_freq``: ``(..., ceil(T n / o))`` for the
+    reduced ratio ``o : n``, every row a recording of its own (leaf_resample_f32, one call).  The band-limited interpolation
+    ``torchaudio.functional.resample`` documents -- a Hann-windowed sinc of ``lowpass_filter_width`` zero crossings, cut off at
+    ``rolloff`` of the lower Nyquist frequency, zeros outside the row -- as include/leaf_hip.h states it: each output is one float32
+    fma chain over its phase's taps in ascending order, so a row's bits depend on the row alone.  ``out_dtype=None`` keeps ``x``'s
+    dtype: an int16 batch stays int16 (``rint(y * 32768)``, saturated); ``orig_freq == new_freq`` is the identity and, with
+    ``out_dtype``, the int16 <-> float32 conversion.  No gradient flows through it."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a tensor")
+    if x.dtype not in (torch.float32, torch.int16):
+        raise TypeError(f"x must be float32 or int16 (PCM), got {x.dtype}")
+    if x.requires_grad:
+        raise RuntimeError("resample: no gradient is built (detach x first)")
+    out_dtype = _resample_out_dtype(x.dtype, out_dtype)
+    key = _native._resample_params(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    if x.dim() < 1:
+        raise ValueError("x must have at least one dimension (..., T)")
+    _native.resample_table(*key)                                                # (ValueError for a ratio beyond the library)
+    _native.require_hip(x, "resample")
+    T = x.shape[-1]
+    if T >= 2 ** 31:
+        raise ValueError(f"a row of {T} samples is beyond the 32-bit length of a recording")
+    rows = x.numel() // T if T else 0
+    out_len = _native.resample_length(T, key[0], key[1])
+    if out_len >= 2 ** 31:
+        raise ValueError(f"a result of {out_len} samples per row is beyond the 32-bit length of a recording")
+    out = torch.empty(x.shape[:-1] + (out_len,), dtype=out_dtype, device=x.device)
+    if rows == 0 or out_len == 0:
+        return out
+    store = x.detach().contiguous().reshape(-1)
+    r = torch.arange(rows, dtype=torch.int64)
+    plan = torch.stack((r * T, torch.full_like(r, T), r * out_len)).to(x.device)
+    _native.resample_records(store, plan[0], plan[1].to(torch.int32), key[0], key[1], out.reshape(-1), plan[2], key[2], key[3])
+    return out
+
 
 def _segment_sums(preds: torch.Tensor, counts) -> torch.Tensor:
     """Sums over runs of ``counts[i]`` consecutive rows of ``preds``, in float64 (stock ops: one ``index_add_``).  float64 puts the
