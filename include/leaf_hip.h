@@ -917,6 +917,47 @@ int leaf_draw_clip_plan(int B, int size, int train, const long long* offsets /*[
                         long long* noise_off, int* noise_len, int* noise_start, int* noise_pad_mode, float* noise_coeff /*[B][2]*/,
                         float* gauss_amp, long long* gauss_stream, long long* index_out, void* stream);
 
+/* leaf_draw_mixup: mixup's permutation and weights drawn ON THE DEVICE (additive: the ABI version stays 6) -- what mix_perm and
+ * mix_lam of the *_mix_f32 entries and leaf_mixup_f32 take, from the generator and the counter protocol of leaf_draw_clip_plan, so
+ * that a step of sample, draw the mix, forward, backward captures into one graph and every replay mixes other pairs with other
+ * weights.  One launch of ONE workgroup, as wide as its sort (64 to 1024 lanes); no workspace, nothing read back.
+ *
+ *   B in [1, 4096]; alpha finite and > 0: the weights are Beta(alpha, alpha), one per clip (the reference's do_mixup)
+ *   state: ONE uint64 in device memory, the step counter, read and advanced exactly as by leaf_draw_clip_plan (every lane reads
+ *         step = state[0]; a workgroup barrier; lane 0 stores step + 1 unless advance == 0).  A mixer keeps a counter of its own.
+ *   seed, stream_base: 64 bits each, by value
+ *   perm [B] int32, lam [B] float32: the outputs
+ *
+ * THE DRAWS.  Per clip b: id = stream_base + step B + b (unsigned 64-bit, wrapping); r0..r3 are the words of Philox4x32-10 with key
+ * (lo32(seed), hi32(seed)) on the counter (0, 2, lo32(id), hi32(id)).  Counter word 1 is 2 here, 1 in leaf_draw_clip_plan and 0 in the
+ * Gaussian stream: a mixer may share seed and ids with a sampler without sharing numbers.  r3 is not used.
+ *
+ * lam is Beta(alpha, alpha) without rejection, so a draw costs a fixed number of words.  If T is Student-t with 2 alpha degrees of
+ * freedom, 1/2 + T / (2 sqrt(2 alpha + T^2)) is Beta(alpha, alpha), and Bailey's polar form gives
+ * T = sqrt(2 alpha (U^(-1/alpha) - 1)) cos(2 pi V).  Multiplied through by U^(1/alpha), so that nothing overflows for a small alpha,
+ * in IEEE double in exactly this association, no contraction:
+ *       U = (r0 + 1) 2^-32   in (0, 1]             V = r1 2^-32
+ *       w = pow(U, 1 / alpha)                      may underflow to 0, never above 1
+ *       c = (r1 & 0x7FFFFFFF) == 0x40000000 ? 0.0 : cos(6.283185307179586 V)         V = 1/4 and 3/4: exactly 0
+ *       n = (1 - w) (c c);   d = w + n;   s = d > 0 ? sqrt(n / d) : 0
+ *       lam = f32(0.5 + 0.5 copysign(s, c))        rounded once to float32, in [0, 1]
+ * The exception at V = 1/4 and 3/4 is there because the cos of the double next to pi / 2 is about 6e-17 with a sign that is the
+ * library's own, and where w underflows that sign would decide between 0 and 1.  The inexact operations are the pow and the cos;
+ * every quantity lies in [0, 1], so two conforming implementations differ by about 1e-15 in front of the rounding: lam is bit-equal
+ * except where the double sits on a rounding boundary, and then off by one float32 ulp (at most 2^-24).
+ *
+ * perm is defined by its result, not by a sorting method: key_b = (uint64(r2) << 32) | b, and perm[k] is the b with the k-th smallest
+ * key.  The low word is b, so keys never tie: perm is the stable argsort of r2, exactly, on every implementation.  (The kernel orders
+ * the keys in LDS with a bitonic network over the power of two at or above B, padded with all-ones keys.)
+ * csrc/leaf_mix_draws.hpp is this definition as host-and-device code.  Neither numpy's nor torch's numbers are reproduced.
+ *
+ * MEMORY SAFETY: nothing but state[0] is read; nothing outside perm[0, B), lam[0, B) and state[0] is written; perm holds each of
+ * 0 .. B - 1 once.  Alignment: 8 bytes for state, 4 for perm and lam.  Status, in this order, before the launch (the counter is not
+ * touched): LEAF_ERR_NULL_POINTER (state, perm, lam); LEAF_ERR_BAD_SHAPE (B < 1, B > 4096, alpha NaN, infinite, 0 or negative);
+ * LEAF_ERR_ALIGNMENT. */
+int leaf_draw_mixup(int B, double alpha, unsigned long long* state, int advance, unsigned long long seed,
+                    unsigned long long stream_base, int* perm /*[B]*/, float* lam /*[B]*/, void* stream);
+
 /* Resampling of a packed store on the device (additive: the ABI version stays 6).  The reference's loaders stop at
  * `assert clip_sr == sr` (utilities/data/utils.py:109,159): they expect a data set that was resampled on disk.  The entries below bring
  * every recording of a packed store from orig_freq to new_freq in one call, int16 in and int16 out where asked, without a float32

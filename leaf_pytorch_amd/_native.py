@@ -7,6 +7,7 @@ buffers, the caching allocator provides the scratch workspace) and for the curre
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import subprocess
 import threading
@@ -139,6 +140,9 @@ _SIGNATURES = {
                                            ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
                                            ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int] + [ctypes.c_double] * 4
                             + [ctypes.c_int] + [ctypes.c_double] * 7 + [ctypes.c_void_p] * 15 + [ctypes.c_void_p]),
+    # mixup's draws on the device: B, alpha, state, advance, seed, stream_base, perm, lam, stream
+    "leaf_draw_mixup": (ctypes.c_int, [ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_ulonglong,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     # resampling: the output length (L, orig_freq, new_freq); the table's bytes and the table itself, on the host (orig_freq, new_freq,
     # lowpass_width, rolloff[, table, table_bytes]); the workspace (R); the call -- store, store_len, flags, R, in_off, in_len, the four
     # parameters, table, table_bytes, out, out_total, out_off, workspace, workspace_bytes, stream
@@ -1263,6 +1267,39 @@ def draw_clip_plan(B: int, size: int, train: bool, offsets: torch.Tensor, length
           float(consts["gaussian_amplitude"][0]), float(consts["gaussian_amplitude"][1]),
           o("rec_off"), o("rec_len"), o("start"), o("pad_mode"), o("gain"), o("masks") if M > 0 else None, o("rec"),
           o("noise_off"), o("noise_len"), o("noise_start"), o("noise_pad_mode"), o("coeff"), o("gauss_amp"), o("gauss_stream"), o("index"))
+
+
+MIX_MAX_BATCH = 4096            # csrc/leaf_mix_draws.hpp (kMixMaxBatch)
+
+
+def mix_alpha(alpha) -> float:
+    """``alpha`` of Beta(alpha, alpha) as the C ABI takes it: a finite double above 0, anything else is a ValueError."""
+    alpha = float(alpha)
+    if not (math.isfinite(alpha) and alpha > 0.0):
+        raise ValueError(f"alpha must be finite and > 0, got {alpha}")
+    return alpha
+
+
+def draw_mixup(B: int, alpha: float, state: torch.Tensor, seed: int, stream_base: int, perm: torch.Tensor, lam: torch.Tensor,
+               advance: bool = True) -> None:
+    """One ``leaf_draw_mixup`` launch on the current stream: mixup's permutation (``perm``, (B,) int32) and Beta(alpha, alpha) weights
+    (``lam``, (B,) float32) of the step that ``state`` (one int64 holding the counter's 64 bits) stands at, drawn on the device into
+    the caller's tensors (include/leaf_hip.h states the draws).  Nothing is copied to the device and nothing is read back, so the call
+    can be captured into a graph.  What the host can see is checked here: ``B`` in [1, 4096], ``alpha`` finite and > 0 (ValueError)."""
+    dev = state.device
+    require_hip(state, "draw_mixup")
+    B = int(B)
+    if not 1 <= B <= MIX_MAX_BATCH:
+        raise ValueError(f"draw_mixup: B must be in [1, {MIX_MAX_BATCH}], got {B}")
+    alpha = mix_alpha(alpha)
+    _check_out(perm, (B,), torch.int32, dev)
+    _check_out(lam, (B,), torch.float32, dev)
+    if state.dtype != torch.int64 or state.numel() != 1 or not state.is_contiguous():
+        raise RuntimeError(f"draw_mixup: state must be one int64 on {dev}")
+    seed, stream_base = int(seed), int(stream_base)
+    if not (0 <= seed < 2 ** 64 and 0 <= stream_base < 2 ** 64):
+        raise ValueError("draw_mixup: seed and stream_base must fit 64 unsigned bits")
+    _call(dev, "leaf_draw_mixup", B, alpha, state, int(bool(advance)), seed, stream_base, perm, lam)
 
 
 def _recordings(store: torch.Tensor, rec_off, rec_len, who: str, size: int = 1):

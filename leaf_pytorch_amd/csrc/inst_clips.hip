@@ -304,3 +304,20 @@ int leaf_draw_clip_plan(int B, int size, int train, const long long* offsets, co
     if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
     return LEAF_OK;
 }
+
+// mixup's permutation and weights, drawn on the device: one launch of one workgroup, no workspace, nothing read back
+int leaf_draw_mixup(int B, double alpha, unsigned long long* state, int advance, unsigned long long seed, unsigned long long stream_base,
+                    int* perm, float* lam, void* stream) {
+    if (!state || !perm || !lam) return LEAF_ERR_NULL_POINTER;
+    if (B < 1 || B > kMixMaxBatch || !(alpha > 0.0 && std::isfinite(alpha))) return LEAF_ERR_BAD_SHAPE;   // a NaN is not > 0
+    auto misaligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+    if (misaligned(state, 7u) || misaligned(perm, 3u) || misaligned(lam, 3u)) return LEAF_ERR_ALIGNMENT;
+    MixDrawParams p{};
+    p.state = state; p.seed = seed; p.stream_base = stream_base; p.alpha = alpha; p.perm = perm; p.lam = lam;
+    p.B = B; p.advance = advance != 0;
+    p.N = 1;
+    while (p.N < B) p.N <<= 1;                                            // the sort's size: the power of two at or above B
+    hipLaunchKernelGGL(draw_mixup_kernel, dim3(1), dim3(mix_draw_threads(p.N)), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return LEAF_ERR_LAUNCH;
+    return LEAF_OK;
+}

@@ -56,11 +56,13 @@
 // and the noise instances are the STD = false instantiations of the same functions: their instructions are what they were.
 //
 // The plan itself (leaf_draw_clip_plan) is drawn by draw_clip_plan_kernel at the end of the file: one workgroup, a clip per lane, the
-// per-clip arithmetic of leaf_clip_draws.hpp (host and device) from a counter the kernel keeps in device memory.
+// per-clip arithmetic of leaf_clip_draws.hpp (host and device) from a counter the kernel keeps in device memory.  Mixup's permutation
+// and weights (leaf_draw_mixup) are drawn the same way by draw_mixup_kernel behind it, on the arithmetic of leaf_mix_draws.hpp.
 #pragma once
 #include "leaf_common.hpp"
 #include "leaf_segments_view.hpp"
 #include "leaf_clip_draws.hpp"
+#include "leaf_mix_draws.hpp"
 
 namespace {
 
@@ -907,6 +909,61 @@ __global__ __launch_bounds__(kDrawThreads) void draw_clip_plan_kernel(const Draw
     __syncthreads();
     if (threadIdx.x == 0 && p.advance) p.state[0] = step + 1ull;
     for (int b = threadIdx.x; b < p.B; b += kDrawThreads) draw_plan_clip(p, step, b);
+}
+
+// ---- mixup's draws (include/leaf_hip.h: leaf_draw_mixup) -------------------------------------------------------------------------------
+// The permutation and the weights of a step's mixup, by ONE workgroup and the same counter protocol.  Lanes stride over the clips:
+// each computes lam[b] (leaf_mix_draws.hpp: one pow and one cos in double) and puts the clip's key into LDS.  perm is the order of the
+// keys, so the workgroup sorts them: a bitonic network over N, the power of two at or above B (the host passes it), with all-ones keys
+// behind the real ones -- a real key's low word is b < B, so the padding sorts last and the first B keys' low words are perm.  Every
+// stage is N / 2 compare-exchanges on disjoint pairs, a barrier between stages; log2(N) (log2(N) + 1) / 2 stages, 78 at the cap.
+// The workgroup is as wide as the sort, N lanes between one wave and kMixMaxThreads (mix_draw_threads): up to 64 clips are one wave's,
+// and at the cap sixteen waves share the double-precision draws, four clips a lane, and hide each other's LDS round trips, two pairs
+// a lane and stage (measured: 48 us at B = 4096 against 89 us with 256 lanes, 5.9 us at B = 64 either way;
+// profiles/clip_device_mixup.txt).  The kernel strides by blockDim.x, so any width gives the same result.
+struct MixDrawParams {
+    unsigned long long* state;    // the step counter
+    unsigned long long seed, stream_base;
+    double alpha;
+    int* perm;                    // [B]
+    float* lam;                   // [B]
+    int B, N, advance;            // 1 <= B <= N <= kMixMaxBatch, N a power of two
+};
+
+constexpr int kMixMaxThreads = 1024;
+
+inline int mix_draw_threads(int N) { return N < 64 ? 64 : (N > kMixMaxThreads ? kMixMaxThreads : N); }
+
+__global__ __launch_bounds__(kMixMaxThreads) void draw_mixup_kernel(const MixDrawParams p) {
+    __shared__ unsigned long long keys[kMixMaxBatch];
+    const int lane = (int)threadIdx.x, width = (int)blockDim.x;
+    const unsigned long long step = p.state[0];
+    __syncthreads();
+    if (lane == 0 && p.advance) p.state[0] = step + 1ull;
+    for (int b = lane; b < p.N; b += width) {
+        unsigned long long key = ~0ull;
+        if (b < p.B) {
+            const MixDraw d = draw_mix_clip(p.seed, p.stream_base, step, p.B, b, p.alpha);
+            p.lam[b] = d.lam;
+            key = d.key;
+        }
+        keys[b] = key;
+    }
+    __syncthreads();
+    for (int k = 2; k <= p.N; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = lane; i < (p.N >> 1); i += width) {
+                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;      // pair i of the stage: lo < hi < N
+                const unsigned long long a = keys[lo], c = keys[hi];
+                if ((a > c) == ((lo & k) == 0)) {
+                    keys[lo] = c;
+                    keys[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int b = lane; b < p.B; b += width) p.perm[b] = (int)(unsigned)keys[b];
 }
 
 }  // namespace

@@ -592,7 +592,7 @@ class DeviceClipSampler:
     - ``standardize=True`` computes ``clips.moments()`` in the constructor, so nothing is computed under a capture.  The buffers of
       ``batch_size`` are allocated there too; another batch size allocates its own on first use (do that before capturing).
 
-    Not built: mixup's ``perm`` / ``lam`` (a Beta sampler on the device), bfloat16."""
+    Mixup's ``perm`` / ``lam`` are ``DeviceMixup``'s, a launch and a counter of their own.  Not built: bfloat16."""
 
     def __init__(self, clips: PackedClips, size: int, train: bool = True, pad_modes=("replicate", "min"), wrap_pad_prob: float = 0.5,
                  gain_prob: float = 0.25, gain_db=(-18.0, 6.0), peak_normalize: bool = True, time_perc: float = 0.0, num_masks: int = 0,
@@ -707,3 +707,59 @@ class DeviceClipSampler:
         return _native.assemble_clips(self.clips.store, rec_off, rec_len, start, pad_mode, self.size, gain, self.peak_normalize, masks, out,
                                       noise=None if plan.noise is None else (self.noise_clips.store,) + plan.noise,
                                       gaussian=plan.gaussian, standardize=None if plan.rec is None else (self.moments, plan.rec))
+
+
+class DeviceMixup:
+    """``Mixup``'s draws made ON THE DEVICE (``_native.draw_mixup`` -> leaf_draw_mixup, one launch of one workgroup): one permutation
+    of the batch and one weight per clip from Beta(alpha, alpha), from the counter-based generator of ``DeviceClipSampler`` (Philox4x32-10
+    keyed by ``seed``) and a step counter of its own in device memory.  Nothing crosses from the host per step, so ``mix()`` captures into
+    a graph (``torch.cuda.graph``) and every replay mixes other pairs with other weights -- with any ``alpha``, 0.3 as well as 1;
+    include/leaf_hip.h states the draws.
+
+    - ``perm, lam = mix()``: int32 ``(B,)`` and float32 ``(B,)``, the mixer's static buffers -- the same tensors on every call,
+      overwritten by the next one -- in the form ``Leaf.forward_mixup(x, perm, lam)`` and ``_native.mixup`` take without a copy.  The
+      call validates nothing on the device and allocates nothing.  ``mix(advance=False)`` draws the step without advancing.
+    - Clip b of step s has the id ``stream_base + s * B + b`` (64-bit, wrapping); its draws depend on (seed, id) alone and lie in a
+      domain of their own (counter word 1 is 2): a mixer may share seed and ids with a ``DeviceClipSampler`` without sharing numbers.
+    - ``targets(t)`` mixes the labels with the pair drawn last, returning the last four values of the reference's ``do_mixup``.  Mode
+      "multilabel": ``(mixed_y, None, None, None)`` with ``mixed_y = t * lam + t[perm] * (1 - lam)`` per clip -- float32 ``t`` of
+      ``B`` rows through ``_native.mixup`` (one launch, bit for bit that separately rounded expression).  Any other mode:
+      ``(t, t[perm], lam, None)`` by stock indexing.
+    - ``step`` / ``set_step(n)`` read and write the counter; they are eager and the only calls that synchronise.
+
+    Neither numpy's nor torch's numbers are reproduced (``Mixup`` keeps the reference's): the distributions are."""
+
+    def __init__(self, batch_size: int, alpha: float = 1.0, seed: int = 1234, stream_base: int = 0, mode: str = "multilabel", device="cuda"):
+        self.batch_size = int(batch_size)
+        if not 1 <= self.batch_size <= _native.MIX_MAX_BATCH:
+            raise ValueError(f"batch_size must be in [1, {_native.MIX_MAX_BATCH}], got {batch_size}")
+        self.alpha = _native.mix_alpha(alpha)
+        self.seed, self.stream_base = int(seed) % 2 ** 64, int(stream_base) % 2 ** 64
+        self.mode = mode
+        self._state = torch.zeros(1, dtype=torch.int64, device=device)          # the step counter's 64 bits
+        _native.require_hip(self._state, "DeviceMixup")
+        self.perm = torch.arange(self.batch_size, dtype=torch.int32, device=device)
+        self.lam = torch.ones(self.batch_size, dtype=torch.float32, device=device)
+
+    @property
+    def step(self) -> int:
+        """The counter: the step the next call draws (synchronises)."""
+        return int(self._state.item()) % 2 ** 64
+
+    def set_step(self, n: int) -> None:
+        """Position the counter: the next call draws step ``n`` (mod 2^64)."""
+        n = int(n) % 2 ** 64
+        self._state.fill_(n - 2 ** 64 if n >= 2 ** 63 else n)
+
+    def __call__(self, advance: bool = True):
+        _native.draw_mixup(self.batch_size, self.alpha, self._state, self.seed, self.stream_base, self.perm, self.lam, advance=advance)
+        return self.perm, self.lam
+
+    def targets(self, t: torch.Tensor):
+        if t.dim() < 1 or t.shape[0] != self.batch_size:
+            raise ValueError(f"targets of shape {tuple(t.shape)} for a mixer of {self.batch_size} clips")
+        if self.mode != "multilabel":
+            return t, t[self.perm], self.lam, None
+        if t.dtype != torch.float32:
+            raise TypeError(f"multilabel targets are mixed in float32, got {t.dtype}")
+        return _native.mixup(t.reshape(self.batch_size, -1), self.perm, self.lam).reshape(t.shape), None, None, None

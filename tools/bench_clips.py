@@ -8,6 +8,7 @@ multiply by the gain, transforms.PeakNormalization, one masked_fill per span.
     python tools/bench_clips.py --segments [--out profiles/eval_segments.txt]
     python tools/bench_clips.py --standardize [--out profiles/clip_standardize.txt]
     python tools/bench_clips.py --device-draws [--out profiles/clip_device_draws.txt]
+    python tools/bench_clips.py --device-mixup [--out profiles/clip_device_mixup.txt]
 
 Both sides run in ONE process on the same store and the same plan (already on the device: drawing it is not timed), taking turns
 round after round after a warm-up round, the order alternating.  Every recording is longer than the clip, so the batch is a crop
@@ -54,7 +55,15 @@ time of each launch on its own, `plan` (DeviceClipSampler.plan alone) and `assem
 round is --steps calls (default here: 40) and one synchronisation, so `wall` is the host time per call of a loop that synchronises
 every 40 calls.  Before anything is timed the replayed batch is compared bit for bit with the eager batch of a second sampler of the
 same seed at the same step.  The last column is the verdict the comparison is made for: `device` wall must not exceed `host` wall by
-more than the run-to-run spread of `host` (max - min of its rounds' wall times, measured here, not fixed)."""
+more than the run-to-run spread of `host` (max - min of its rounds' wall times, measured here, not fixed).
+
+--device-mixup times mixup's draws: B = 64 / 256 / 4096 clips, alpha = 0.3 and 1.  Four sides take turns: `host`, the draws of
+transforms.Mixup.__call__ with their upload (numpy's RandomState.beta, torch.randperm on the CPU, two copies to the device: the path as
+it was); `device`, DeviceMixup.__call__ (leaf_draw_mixup into the mixer's static buffers); `graph`, the replay of that launch captured
+with torch.cuda.graph; and `argsort`, torch.argsort of B 64-bit keys on the device, the stock form of the kernel's sort alone (device
+time).  Rounds as for --device-draws.  Before anything is timed the replayed draw is compared bit for bit with the eager draw of a second
+mixer of the same seed at the same step, and checked to be a permutation with weights in [0, 1].  No verdict column: the file records
+what was measured."""
 import argparse
 import os
 import statistics
@@ -349,6 +358,51 @@ def device_draw_legs(args, busy, busy_out):
     return lines
 
 
+def device_mixup_legs(args, busy, busy_out):
+    import numpy as np
+    from leaf_pytorch_amd import DeviceMixup
+    steps = args.steps if args.steps_given else 40
+    lines = [f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {args.rounds} timed rounds x {steps} calls per side after a "
+             "warm-up round, one synchronisation per round; us per call: median [min, max]; device = HIP events, calls queued behind a matrix "
+             "product; wall = host clock to the synchronise; host = the draws of transforms.Mixup.__call__ and their upload (numpy RandomState "
+             "beta, torch.randperm on the CPU, two copies to the device), device = DeviceMixup.__call__ (leaf_draw_mixup), graph = replay of that "
+             "launch captured, argsort = torch.argsort of B 64-bit keys on the device (the stock form of the kernel's sort alone)",
+             f"{'B':>5} {'alpha':>5} | {'host wall':>26} {'host device':>11} | {'device wall':>26} {'device device':>24} | {'graph wall':>26} "
+             f"{'graph device':>12} | {'argsort device':>24}"]
+    for B in (64, 256, 4096):
+        for alpha in (0.3, 1.0):
+            mix, twin = (DeviceMixup(B, alpha=alpha, seed=1234, device=DEV) for _ in range(2))
+            mix()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                mix()
+            twin.set_step(mix.step)
+            for _ in range(2):
+                graph.replay()
+                perm, lam = twin()
+                torch.cuda.synchronize()
+                if not (torch.equal(mix.perm, perm) and torch.equal(mix.lam.view(torch.int32), lam.view(torch.int32))):
+                    sys.exit(f"the replayed draw is not the eager one at B={B} alpha={alpha}: nothing is timed")
+                if sorted(perm.tolist()) != list(range(B)) or not bool(((lam >= 0) & (lam <= 1)).all()):
+                    sys.exit(f"not a permutation, or a weight outside [0, 1], at B={B} alpha={alpha}: nothing is timed")
+            keys = ((torch.randint(0, 2 ** 31, (B,), generator=torch.Generator().manual_seed(B)) << 32) | torch.arange(B)).to(DEV)
+
+            def host():                                                           # transforms.Mixup.__call__, its first three lines
+                random_state = np.random.RandomState(1233)
+                lam = torch.from_numpy(random_state.beta(alpha, alpha, B)).to(DEV).float()
+                return lam, torch.randperm(B).to(DEV)
+
+            sides = {"host": host, "device": mix, "graph": graph.replay, "argsort": lambda: torch.argsort(keys)}
+            dev_us, wall_us = time_sides(sides, args.rounds, steps, busy, busy_out)
+            fmt = lambda v: f"{statistics.median(v):9.1f} [{min(v):6.1f},{max(v):7.1f}]"
+            med = lambda v: statistics.median(v)
+            lines.append(f"{B:>5} {alpha:>5} | {fmt(wall_us['host']):>26} {med(dev_us['host']):11.1f} | {fmt(wall_us['device']):>26} "
+                         f"{fmt(dev_us['device'])} | {fmt(wall_us['graph']):>26} {med(dev_us['graph']):12.1f} | {fmt(dev_us['argsort'])}")
+            print(lines[-1], flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=20)
@@ -359,13 +413,15 @@ def main():
     ap.add_argument("--standardize", action="store_true", help="time the standardising launch (profiles/clip_standardize.txt)")
     ap.add_argument("--device-draws", action="store_true", help="time the batch with its draws: ClipSampler, DeviceClipSampler, the captured graph "
                                                                 "(profiles/clip_device_draws.txt)")
+    ap.add_argument("--device-mixup", action="store_true", help="time mixup's draws: Mixup's on the host, DeviceMixup, the captured graph, "
+                                                                "torch.argsort (profiles/clip_device_mixup.txt)")
     args = ap.parse_args()
     args.steps_given = any(a == "--steps" or a.startswith("--steps=") for a in sys.argv[1:])
     if not torch.cuda.is_available():
         sys.exit("bench_clips.py needs the GPU: a time taken anywhere else says nothing about it")
-    if args.noise or args.segments or args.standardize or args.device_draws:
+    if args.noise or args.segments or args.standardize or args.device_draws or args.device_mixup:
         busy = torch.rand(8192, 8192, device=DEV)
-        legs = device_draw_legs if args.device_draws else (standardize_legs if args.standardize else (segment_legs if args.segments else noise_legs))
+        legs = device_mixup_legs if args.device_mixup else device_draw_legs if args.device_draws else (standardize_legs if args.standardize else (segment_legs if args.segments else noise_legs))
         text = "\n".join(legs(args, busy, torch.empty_like(busy))) + "\n"
         print(text)
         if args.out:
