@@ -1024,7 +1024,7 @@ int leaf_draw_mixup(int B, double alpha, unsigned long long* state, int advance,
  * for a table above 2^26 bytes; LEAF_ERR_NULL_POINTER (store, in_off, in_len, table, out, out_off); LEAF_ERR_BAD_SHAPE for R < 1, a
  * negative store_len or out_total, a frequency <= 0, lowpass_width < 1, rolloff outside (0, 1], or table_bytes other than the size
  * query; LEAF_ERR_ALIGNMENT; LEAF_ERR_WORKSPACE.  out must not overlap the store.
- * Not built: the Kaiser window, a streaming resampler with carried state, gradients, bfloat16. */
+ * Not built: the Kaiser window, gradients, bfloat16.  (Chunked resampling with carried state: the next section.) */
 size_t leaf_resample_length(long long L, int orig_freq, int new_freq);
 size_t leaf_resample_table_bytes(int orig_freq, int new_freq, int lowpass_width, double rolloff);
 int leaf_resample_table_f32(int orig_freq, int new_freq, int lowpass_width, double rolloff, void* table_host, size_t table_bytes);
@@ -1033,6 +1033,86 @@ int leaf_resample_f32(const void* store, long long store_len, int flags, int R, 
                       const int* in_len /*[R]*/, int orig_freq, int new_freq, int lowpass_width, double rolloff,
                       const void* table /*device*/, size_t table_bytes, void* out, long long out_total,
                       const long long* out_off /*[R]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Chunked resampling with carried state (additive: the ABI version stays 6): B INDEPENDENT streams at a device rate (44.1 or 48 kHz
+ * from a capture device or the network) are brought to the rate leaf_stream_bank_step_f32 serves, chunk by chunk, in ONE launch per
+ * step and 128 slots.  The history the next outputs still need stays ON THE DEVICE in a `state` buffer the caller owns; WHERE a stream
+ * stands stays on the host, in a leaf_resample_pos per slot (nothing is read back, nothing synchronises, there is no workspace).
+ *
+ * THE CONTRACT: an output of leaf_resample_f32 is one fmaf chain over its span, a pure function of the recording.  The outputs a
+ * stream emits over its life, concatenated, are therefore BIT FOR BIT those of leaf_resample_f32 on the concatenated chunks, for
+ * any chunking (chunks of 0 and 1 samples included), float32 and int16, on both tap paths.
+ *
+ * The position (csrc/leaf_resample_stream.hpp is this paragraph as code).  With the reduced ratio o : n, width, K = 2 width + o and
+ * the spans k0[p], cnt[p] of the definition above, klast[p] = k0[p] + cnt[p] - 1 (non-decreasing in p).  A stream's signal in a step
+ * is the virtual buffer V = [history (hist_len samples) | chunk (Tc samples)], Lv = hist_len + Tc.  Window coordinate c means "tap c
+ * of group 0", group 0 being the group of the next output to emit.  `shift` virtual +0.0f samples stand in front of V[0]: width of
+ * them when a stream begins (the recording starts at its first sample), 0 once the stream has moved width samples in.
+ * E = shift + Lv is one past the last sample that has arrived; `phase` is the phase of the next output.
+ *   While the stream runs, a step emits, in order from (g, p) = (0, phase), every output whose whole span has arrived:
+ *     g o + klast[p] <= E - 1 -- per output, not per group: an output leaves as soon as its last sample is there.
+ *   At the end of the stream (end = 1) it emits every remaining output of the recording: (g n + p) o < n (E - width), samples at or
+ *     behind E counting as +0.0f.  This is out_len = ceil(n T / o) in relative terms; no absolute position is kept, so a stream may
+ *     run for ever.
+ *   Hand-over: the next output being (G, p'), the new origin is window coordinate G o: drop_samples = max(0, G o - shift),
+ *     shift' = max(0, shift - G o), hist_len' = Lv - drop_samples, phase' = p'.  hist_len' never exceeds H = K - 1, the history
+ *     capacity (474 samples at 44.1 -> 16 kHz, 40 at 48 -> 16 kHz, 0 at o == n).  At the end nothing is kept.
+ *
+ * The history query answers H (0 for parameters the step refuses).  The state query sizes `state`: two history halves of [B][H]
+ * samples in the sample type `flags` names (float32, or int16 with LEAF_FLAG_X_PCM16), each region a multiple of 256 bytes and at
+ * least 256; 0 for B < 1 and for what the step refuses.  The buffer may hold anything when a stream begins.
+ *
+ * A slot's record (leaf_resample_slot):
+ *   idle = 1: the slot takes no part.  Nothing of its state is read or written, no other field is looked at, its row of out is zeros.
+ *   idle = 0: the signal is [history (hist_len samples of row b of half `parity`) | chunk[b * chunk_stride .. + Tc)]; outputs
+ *     phase, phase + 1, ... (n of them) of group 0 on are written to out[b][0 .. n); unless end = 1, samples [drop_samples, Lv) go to
+ *     row b of the OTHER half, and the caller flips the slot's parity.  Only the first Tc samples of a chunk row are read.
+ *
+ * The plan entry is the host side of a step for the whole bank, on integers alone (no table, no GPU): from each slot's carried
+ * position pos[b] (running, hist_len, shift, phase, parity), its Tc[b] (0 .. 2^20 samples) and its end[b] (NULL: no stream ends) it
+ * fills slots[b] and counts[b] (= slots[b].n) and advances pos[b].  Tc = 0 without end leaves a slot idle; a slot that is not running
+ * begins a new stream with its first samples (hist_len = 0, shift = width, phase = 0); end on a slot that is not running does
+ * nothing; a stream that ends stops running.  All positions move or none: LEAF_ERR_UNSUPPORTED, LEAF_ERR_NULL_POINTER (pos, Tc,
+ * slots, counts), LEAF_ERR_BAD_SHAPE (B < 0, bad parameters, a Tc outside its range, a position outside its ranges, a count beyond
+ * 2^31 - 1); B = 0: LEAF_OK.
+ *
+ * The step:
+ *   chunk, chunk_stride: float32 or int16 (LEAF_FLAG_X_PCM16: the history is then int16 too); row b starts at b * chunk_stride; may
+ *     be NULL when no slot has samples              slots: a HOST array of B records, read before the call returns (they travel to
+ *     the kernel by value)              state, state_bytes: as the state query sizes it
+ *   the four parameters, table, table_bytes: as in leaf_resample_f32 (the device copy of the same table)
+ *   out: [B][n_max], float32 or int16 (LEAF_FLAG_OUT_PCM16): a slot's n outputs, then zeros; EVERY element is written.  n_max = 0:
+ *     out is not touched and may be NULL (the launch still moves the history).
+ * Grid: (tiles of 1024 outputs over n_max, at least 1) x slots, 256 lanes.  A workgroup stages its tile's window into LDS as float32
+ * from the two sources (+0.0f below `shift`, the history below hist_len, the chunk below Lv, +0.0f behind), runs the tile function
+ * of leaf_resample_f32 from phase `phase` on and stores with the same aligned store; the workgroup of tile 0 hands the history over.
+ * Every workgroup reads only the old half and the chunk: nothing races.  Taps come from LDS or global memory as the table's word 5
+ * says.  No atomics, no scratch, no workspace, no readback.  A call in which no slot emits or keeps anything launches nothing.
+ * A ratio whose tile window does not fit LDS (16 -> 1, 44100 -> 2000) is NOT served: LEAF_ERR_UNSUPPORTED, and the size queries
+ * answer 0.  Steps on one `state` must execute in order (one HIP stream, or events).
+ * Checks, all on the host before anything is launched, in this order: a flag other than LEAF_FLAG_X_PCM16 / LEAF_FLAG_OUT_PCM16, or
+ * a ratio the library or this entry does not take: LEAF_ERR_UNSUPPORTED; B = 0: LEAF_OK; NULL (slots, state, table; out when n_max >
+ * 0; chunk when a slot has Tc > 0); shape (B < 1, n_max < 0, bad parameters, table_bytes, a slot's idle or Tc, chunk_stride below the
+ * longest Tc when B > 1): LEAF_ERR_BAD_SHAPE; alignment (state 16 bytes, table 4, chunk and out by element); then per slot, one bad
+ * slot refusing the whole call with LEAF_ERR_BAD_SHAPE: hist_len <= H, shift <= width, phase < n, parity and end 0 or 1,
+ * drop_samples <= Lv and (end = 0) Lv - drop_samples <= H, n <= n_max, n equal to what the rule gives; state_bytes:
+ * LEAF_ERR_WORKSPACE.  Whatever the records say, nothing outside state, table, out and the first Tc samples of a chunk row is touched.
+ * Not built: resampling inside the fused streaming kernel, ratios whose window does not fit LDS, a device-resident position. */
+typedef struct leaf_resample_slot {
+    int idle;
+    int hist_len, Tc, parity, shift, phase, n, drop_samples, end;
+} leaf_resample_slot;
+typedef struct leaf_resample_pos {
+    int running, hist_len, shift, phase, parity;
+} leaf_resample_pos;
+int leaf_resample_stream_history_samples(int orig_freq, int new_freq, int lowpass_width, double rolloff);
+size_t leaf_resample_stream_state_bytes(int B, int orig_freq, int new_freq, int lowpass_width, double rolloff, int flags);
+int leaf_resample_stream_plan(int B, int orig_freq, int new_freq, int lowpass_width, double rolloff, leaf_resample_pos* pos /*[B] in and out*/,
+                              const int* Tc /*[B]*/, const int* end /*[B] or NULL*/, leaf_resample_slot* slots /*[B] out*/,
+                              int* counts /*[B] out*/);
+int leaf_resample_stream_step_f32(const void* chunk, long long chunk_stride, int B, const leaf_resample_slot* slots /*host*/, int n_max,
+                                  void* state, size_t state_bytes, int flags, int orig_freq, int new_freq, int lowpass_width,
+                                  double rolloff, const void* table /*device*/, size_t table_bytes, void* out, void* stream);
 
 #ifdef __cplusplus
 }

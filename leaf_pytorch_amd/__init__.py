@@ -8,9 +8,9 @@ from .initializers import GaborFilter, GaborInit
 from ._native import build, load, LIB_PATH
 from .transforms import (CenterCrop, ClipSampler, DeviceClipSampler, DeviceMixup, PackedClips, PeakNormalization, RandomCrop,
                          evaluate_recordings, resample, segment_mean)
-from .streaming import LeafStream, LeafStreamBank
+from .streaming import LeafStream, LeafStreamBank, ResampleStream, ResampleStreamBank
 
 __all__ = ["Leaf", "SquaredModulus", "get_frontend", "GaborConv1d", "GaborConstraint", "GaussianLowPass",
            "ExponentialMovingAverage", "PCENLayer", "GaborInit", "GaborFilter", "get_padding_value", "build", "load",
-           "PeakNormalization", "CenterCrop", "RandomCrop", "PackedClips", "ClipSampler", "DeviceClipSampler", "DeviceMixup", "LeafStream", "LeafStreamBank",
+           "PeakNormalization", "CenterCrop", "RandomCrop", "PackedClips", "ClipSampler", "DeviceClipSampler", "DeviceMixup", "LeafStream", "LeafStreamBank", "ResampleStream", "ResampleStreamBank",
            "segment_mean", "evaluate_recordings", "resample"]

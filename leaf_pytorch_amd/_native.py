@@ -153,6 +153,16 @@ _SIGNATURES = {
     "leaf_resample_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t,
                                          ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    # chunked resampling with carried state: the history capacity and the state's bytes (the four parameters[, flags]); the host plan --
+    # B, the four parameters, pos (leaf_resample_pos[B]), Tc, end, slots (leaf_resample_slot[B]), counts; the step -- chunk,
+    # chunk_stride, B, slots, n_max, state, state_bytes, flags, the four parameters, table, table_bytes, out, stream
+    "leaf_resample_stream_history_samples": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double]),
+    "leaf_resample_stream_state_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int]),
+    "leaf_resample_stream_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "leaf_resample_stream_step_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                     ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                                     ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     "leaf_fft_tables_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "leaf_fft_prepare_tables_f32": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_size_t, ctypes.c_void_p]),
@@ -1522,6 +1532,58 @@ def resample_records(store: torch.Tensor, in_off: torch.Tensor, in_len: torch.Te
     else:
         _call(dev, "leaf_resample_f32", *args, ws, ws.numel())
     return out
+
+
+RESAMPLE_STREAM_MAX_CHUNK = 1 << 20   # csrc/leaf_resample_stream.hpp (kResampleStreamMaxChunk): samples one slot takes in one step
+
+
+class ResampleSlot(ctypes.Structure):
+    """leaf_resample_slot (include/leaf_hip.h): one slot of a chunked resampler in one step."""
+    _fields_ = [(name, ctypes.c_int) for name in ("idle", "hist_len", "Tc", "parity", "shift", "phase", "n", "drop_samples", "end")]
+
+
+class ResamplePos(ctypes.Structure):
+    """leaf_resample_pos (include/leaf_hip.h): where one slot's stream stands between two steps."""
+    _fields_ = [(name, ctypes.c_int) for name in ("running", "hist_len", "shift", "phase", "parity")]
+
+
+def resample_stream_history(key) -> int:
+    """H = K - 1 of the four parameters ``key`` (leaf_resample_stream_history_samples); 0 for what the step refuses."""
+    return int(load().leaf_resample_stream_history_samples(*key))
+
+
+def resample_stream_state(B: int, key, flags: int, device: torch.device) -> torch.Tensor:
+    """The device-resident state of ``B`` chunked resamplers (leaf_resample_stream_state_bytes: two history halves), uninitialised --
+    a stream's first step reads none of it."""
+    nbytes = load().leaf_resample_stream_state_bytes(B, *key, flags)
+    if nbytes == 0:
+        raise RuntimeError(f"leaf_resample_stream_state_bytes: no chunked resampler for {key[0]} -> {key[1]}")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def resample_stream_plan(key, pos, lengths, end):
+    """leaf_resample_stream_plan: the host side of a step.  ``pos``: a ctypes array of ``ResamplePos``, advanced in place (all slots
+    or none); ``lengths`` / ``end``: host integers per slot.  Returns (the slots' ``ResampleSlot`` records, the counts as a list);
+    ValueError for what the entry refuses."""
+    B = len(pos)
+    Tc = (ctypes.c_int * B)(*lengths)
+    ends = (ctypes.c_int * B)(*[int(bool(v)) for v in end])
+    slots, counts = (ResampleSlot * B)(), (ctypes.c_int * B)()
+    vp = ctypes.c_void_p
+    rc = load().leaf_resample_stream_plan(B, *key, ctypes.cast(pos, vp), ctypes.cast(Tc, vp), ctypes.cast(ends, vp), ctypes.cast(slots, vp),
+                                          ctypes.cast(counts, vp))
+    if rc != 0:
+        raise ValueError(f"leaf_resample_stream_plan refused the step: {load().leaf_status_string(rc).decode()} (status {rc})")
+    return slots, list(counts)
+
+
+def resample_stream_step(chunk_ptr: int, chunk_stride: int, slots, n_max: int, state: torch.Tensor, flags: int, key, table: ResampleTable,
+                         out_ptr: int, device: torch.device) -> None:
+    """leaf_resample_stream_step_f32 on the current stream of ``device``.  ``slots``: a ctypes array of ``ResampleSlot`` (host memory,
+    read before the call returns); ``chunk_ptr`` / ``out_ptr``: device addresses (0 where no slot has samples / n_max is 0)."""
+    words = table.on(device)
+    _call(device, "leaf_resample_stream_step_f32", ctypes.c_void_p(chunk_ptr), chunk_stride, len(slots), ctypes.cast(slots, ctypes.c_void_p),
+          n_max, state, state.numel(), flags, *key, words, words.numel() * 4, ctypes.c_void_p(out_ptr))
 
 
 def prepare_tables(kernel: torch.Tensor, pool_w: torch.Tensor, K: int, hop: int) -> Optional[torch.Tensor]:

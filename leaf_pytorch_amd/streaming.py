@@ -362,3 +362,172 @@ class LeafStreamBank:
         for b in ending:
             end[b] = True
         return self.step(None, [0] * self.slots, end)
+
+
+_SAMPLE_DTYPES = (torch.float32, torch.int16)
+
+
+class ResampleStreamBank:
+    """``slots`` INDEPENDENT streams at a device rate (44.1 or 48 kHz) brought to ``new_freq`` chunk by chunk, one
+    ``leaf_resample_stream_step_f32`` call per step for the whole bank: what stands between a microphone and ``LeafStreamBank``.
+    Streams begin and end at different steps, take chunks of different lengths, or take nothing in a step.
+
+    Every output of ``resample()`` is one fma chain over its span, a pure function of the recording; so what a slot emits over its
+    stream's life, concatenated, is BIT FOR BIT ``resample()`` of the concatenated chunks, for any chunking.  An output leaves in the
+    step that brings its last sample.  The host keeps where each slot stands (``pos``: ``_native.ResamplePos``, moved by
+    ``leaf_resample_stream_plan``, integers alone); the history the next outputs need (at most ``history`` = K - 1 samples per slot:
+    474 at 44.1 -> 16 kHz, 40 at 48 -> 16 kHz) lives in ``state_buf``, allocated by the first step and never cleared.
+
+    ``max_chunk`` (2^20 samples) is the most one slot takes in one step.  Ratios whose tile window does not fit LDS (16 -> 1,
+    44100 -> 2000) are not served: ``ValueError``."""
+
+    def __init__(self, orig_freq: int, new_freq: int, slots: int, sample_dtype=torch.float32, out_dtype=None,
+                 lowpass_filter_width: int = 6, rolloff: float = 0.99, device=None):
+        if sample_dtype not in _SAMPLE_DTYPES:
+            raise ValueError(f"ResampleStreamBank: sample_dtype must be torch.float32 or torch.int16 (16-bit PCM), got {sample_dtype!r}")
+        if out_dtype not in (None,) + _SAMPLE_DTYPES:
+            raise ValueError(f"ResampleStreamBank: out_dtype must be None, torch.float32 or torch.int16, got {out_dtype!r}")
+        if isinstance(slots, bool) or int(slots) != slots or int(slots) < 1:
+            raise ValueError(f"ResampleStreamBank: slots must be an integer of at least 1, got {slots!r}")
+        self.key = _native._resample_params(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        self.table = _native.resample_table(*self.key)                    # (ValueError for a ratio beyond the library)
+        self.slots = int(slots)
+        self.sample_dtype = sample_dtype
+        self.out_dtype = sample_dtype if out_dtype is None else out_dtype
+        self.flags = (_native.FLAG_X_PCM16 if sample_dtype is torch.int16 else 0) | (_native.FLAG_OUT_PCM16 if self.out_dtype is torch.int16 else 0)
+        if _native.load().leaf_resample_stream_state_bytes(self.slots, *self.key, self.flags) == 0:
+            raise ValueError(f"ResampleStreamBank: {self.key[0]} -> {self.key[1]} is not served in chunks: a tile's input window "
+                             "does not fit LDS (resample() takes whole recordings at this ratio)")
+        self.history = _native.resample_stream_history(self.key)
+        self.max_chunk = _native.RESAMPLE_STREAM_MAX_CHUNK
+        self.device = None if device is None else torch.device(device)
+        self.state_buf: Optional[torch.Tensor] = None                     # [history half 0 | history half 1], never cleared
+        self.pos = (_native.ResamplePos * self.slots)()
+
+    @property
+    def running(self):
+        return [bool(p.running) for p in self.pos]
+
+    @torch.no_grad()
+    def step(self, chunk: Optional[torch.Tensor], lengths, end=None):
+        """One step of every slot.  ``chunk``: (slots,1,Tmax) or (slots,Tmax) on the device, ``sample_dtype`` samples; a strided view
+        is read in place, and only ``chunk[b, :lengths[b]]`` is ever read (None: no slot has samples).  ``lengths``: per slot, host
+        integers in 0 .. min(Tmax, max_chunk).  ``end``: per slot, host booleans -- the slot's stream ends with this chunk, every
+        remaining output of its recording comes out in this step (zeros behind the last sample) and the slot is free.  A slot that is
+        not running begins a new stream with its first samples; no samples and no ``end`` leaves a slot idle (its state is not
+        touched); ``end`` on a slot that is not running does nothing.  Returns ``(y, counts)``: ``y`` is (slots, max(counts)) in
+        ``out_dtype``, row b holding ``counts[b]`` samples and zeros behind them; ``counts`` are host integers, nothing synchronises.
+        ``ValueError`` for bad lengths or a chunk of another type or shape: nothing is launched and no position moves."""
+        B = self.slots
+        lengths = [int(v) for v in lengths]
+        end = [False] * B if end is None else [bool(v) for v in end]
+        if len(lengths) != B or len(end) != B:
+            raise ValueError(f"ResampleStreamBank.step: lengths and end must have one entry per slot ({B})")
+        for b, Tc in enumerate(lengths):
+            if not 0 <= Tc <= self.max_chunk:
+                raise ValueError(f"ResampleStreamBank.step: lengths[{b}] = {Tc} is outside 0 .. max_chunk = {self.max_chunk}")
+        x2 = None
+        if chunk is not None:
+            if chunk.dtype != self.sample_dtype:
+                raise ValueError(f"ResampleStreamBank.step: this bank takes {self.sample_dtype} samples and got a {chunk.dtype} chunk")
+            x2 = chunk[:, 0, :] if chunk.dim() == 3 and chunk.shape[1] == 1 else chunk
+            if x2.dim() != 2 or x2.shape[0] != B:
+                raise ValueError(f"ResampleStreamBank.step: chunk must be ({B},1,Tmax) or ({B},Tmax), got {tuple(chunk.shape)}")
+            _native.require_hip(chunk, "ResampleStreamBank.step")
+            if self.device is not None and x2.device != self.device:
+                raise ValueError(f"ResampleStreamBank.step: this bank lives on {self.device} and got a chunk on {x2.device}")
+        Tmax = 0 if x2 is None else x2.shape[1]
+        for b, Tc in enumerate(lengths):
+            if Tc > Tmax:
+                raise ValueError(f"ResampleStreamBank.step: lengths[{b}] = {Tc} exceeds the chunk's {Tmax} samples")
+        if self.device is None:
+            if x2 is None:
+                return torch.empty((B, 0), dtype=self.out_dtype), [0] * B   # (nothing has ever run)
+            self.device = x2.device
+        if x2 is not None and ((Tmax > 1 and x2.stride(1) != 1) or (B > 1 and x2.stride(0) < Tmax)):    # (an expanded view: rows overlap)
+            x2 = x2.contiguous()
+        pos = (_native.ResamplePos * B).from_buffer_copy(self.pos)        # the plan moves a copy: a refusal leaves the bank as it was
+        recs, counts = _native.resample_stream_plan(self.key, pos, lengths, end)
+        dev, n_max = self.device, max(counts)
+        if self.state_buf is None:
+            self.state_buf = _native.resample_stream_state(B, self.key, self.flags, dev)
+        out = torch.empty((B, n_max), dtype=self.out_dtype, device=dev)
+        _native.resample_stream_step(x2.data_ptr() if Tmax else 0, x2.stride(0) if Tmax else 0, recs, n_max, self.state_buf, self.flags,
+                                     self.key, self.table, out.data_ptr() if n_max else 0, dev)
+        self.pos = pos
+        return out, counts
+
+    def flush(self, slots=None):
+        """A step without samples that ends the named slots (all running slots by default): ``(y, counts)`` as ``step``."""
+        ending = range(self.slots) if slots is None else [int(b) for b in slots]
+        end = [False] * self.slots
+        for b in ending:
+            end[b] = True
+        return self.step(None, [0] * self.slots, end)
+
+
+class ResampleStream:
+    """``ResampleStream(orig_freq, new_freq)``: B waveforms in lock-step through ``ResampleStreamBank``'s machinery.  ``step(chunk)``
+    returns the outputs that became final, ``flush()`` ends the stream with the rest: concatenated they are ``resample()`` of the
+    concatenated chunks, bit for bit.  The sample dtype (float32 or int16) and the batch are those of the first chunk; ``out_dtype=None``
+    keeps the sample dtype.  A chunk beyond ``max_chunk`` samples (2^20) goes in pieces."""
+
+    def __init__(self, orig_freq: int, new_freq: int, out_dtype=None, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+        if out_dtype not in (None,) + _SAMPLE_DTYPES:
+            raise ValueError(f"ResampleStream: out_dtype must be None, torch.float32 or torch.int16, got {out_dtype!r}")
+        self.key = _native._resample_params(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        self.out_dtype = out_dtype
+        self.table = _native.resample_table(*self.key)
+        if _native.load().leaf_resample_stream_state_bytes(1, *self.key, 0) == 0:
+            raise ValueError(f"ResampleStream: {self.key[0]} -> {self.key[1]} is not served in chunks: a tile's input window does not "
+                             "fit LDS (resample() takes whole recordings at this ratio)")
+        self.max_chunk = _native.RESAMPLE_STREAM_MAX_CHUNK
+        self.bank: Optional[ResampleStreamBank] = None                    # made by the first chunk, kept for the next stream
+        self.open = False                                                 # a stream is running
+
+    def _rows(self, chunk: torch.Tensor) -> torch.Tensor:
+        if not isinstance(chunk, torch.Tensor) or chunk.dtype not in _SAMPLE_DTYPES:
+            raise ValueError(f"ResampleStream.step: chunks are float32 or int16 (PCM) tensors, got {getattr(chunk, 'dtype', type(chunk))!r}")
+        x2 = chunk[:, 0, :] if chunk.dim() == 3 and chunk.shape[1] == 1 else chunk
+        if x2.dim() != 2 or x2.shape[0] < 1:
+            raise ValueError(f"ResampleStream.step: chunk must be (B,1,Tc) or (B,Tc) with B >= 1, got {tuple(chunk.shape)}")
+        return x2
+
+    @torch.no_grad()
+    def step(self, chunk: torch.Tensor) -> torch.Tensor:
+        """chunk (B,1,Tc) or (B,Tc) on the device, float32 or int16; a strided view is read in place -> (B, n), n >= 0."""
+        x2 = self._rows(chunk)
+        _native.require_hip(chunk, "ResampleStream.step")
+        B, Tc = x2.shape
+        bank = self.bank
+        if self.open:
+            if x2.dtype != bank.sample_dtype:
+                raise RuntimeError(f"ResampleStream.step: this stream holds {bank.sample_dtype} samples and got a {x2.dtype} chunk: "
+                                   "one sample type per stream (flush() ends it)")
+            if (B, x2.device) != (bank.slots, bank.device):
+                raise RuntimeError(f"ResampleStream.step: this stream runs {bank.slots} waveforms on {bank.device} and got {B} on "
+                                   f"{x2.device} (flush() ends it)")
+        elif bank is None or (bank.slots, bank.sample_dtype, bank.device) != (B, x2.dtype, x2.device):
+            bank = self.bank = ResampleStreamBank(self.key[0], self.key[1], B, x2.dtype, self.out_dtype, self.key[2], self.key[3], x2.device)
+            bank.table = self.table                                       # (a test switch: ResampleTable.with_global_taps)
+        outs, at = [], 0
+        while at < Tc:                                                    # one piece unless the chunk exceeds max_chunk
+            take = min(Tc - at, self.max_chunk)
+            y, _ = bank.step(x2[:, at:at + take], [take] * B)
+            self.open = True
+            outs.append(y)
+            at += take
+        if not outs:
+            return x2.new_empty((B, 0), dtype=bank.out_dtype)
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+
+    @torch.no_grad()
+    def flush(self) -> torch.Tensor:
+        """End of the stream: the outputs still owed, with zeros behind the last sample.  The state buffer is kept."""
+        if not self.open:
+            if self.bank is None:
+                return torch.empty((0, 0), dtype=self.out_dtype or torch.float32)
+            return torch.empty((self.bank.slots, 0), dtype=self.bank.out_dtype, device=self.bank.device)
+        y, _ = self.bank.flush()
+        self.open = False
+        return y
