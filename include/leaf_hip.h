@@ -1114,6 +1114,69 @@ int leaf_resample_stream_step_f32(const void* chunk, long long chunk_stride, int
                                   void* state, size_t state_bytes, int flags, int orig_freq, int new_freq, int lowpass_width,
                                   double rolloff, const void* table /*device*/, size_t table_bytes, void* out, void* stream);
 
+/* ClipValue and a sox-style reverb on an assembled batch (additive: the ABI version stays 6).  In the reference's training pipeline
+ * (utilities/data/raw_transforms.py, get_raw_transforms_v2) both transforms sit between AddRandomNoise and RandomGain, switched
+ * off: ClipValue "needs work", RandomReverb -- sox's `reverb` effect per clip on the CPU -- is "TOO SLOW".  One launch maps a
+ * float32 batch x [B][S] to y [B][S]; clips are independent, each takes two optional steps in the reference's order.
+ *
+ * CLIPVALUE.  clip_factor [B] float32 or NULL (no clip takes the step); a negative factor skips the clip's step.  Otherwise, with the
+ * exact minimum and maximum of the clip's S samples (a zero of either sign counting as +0),
+ *       lo = fp32(min * factor)      hi = fp32(max * factor)      x' = min(max(x, lo), hi)   i.e.  m = x < lo ? lo : x;  hi < m ? hi : m
+ * which is torch.clamp(x, min=lo, max=hi) for finite input.  NaN input is unspecified.
+ *
+ * REVERB.  sox's `reverb` (Freeverb: eight feedback combs with a damping one-pole in the loop, summed, then four all-passes in
+ * series) for one channel, stereo depth 0, pre-delay 0, wet gain 0 dB, the dry signal kept.  feedback [B], damp [B] float32 and
+ * comb [B][8] int32 delay lengths -- all three or all NULL (no clip takes the step); comb[b][0] <= 0 skips the clip's step.  The four
+ * all-pass lengths follow from sample_rate alone (below).  All arithmetic is IEEE float32 and EVERY operation is rounded on its own:
+ * no fused multiply-add, no contraction; subnormals are kept.  State per clip, all zero at sample 0: the lines cb[i][comb[i]] and
+ * ap[j][allpass[j]], store[i], and one write index per line that wraps at the line's length.  Per sample n = 0 .. S - 1, x' being
+ * the sample behind ClipValue:
+ *       in = x'[n];  out = 0.0f;
+ *       for (i = 7; i >= 0; --i) {                  combs, in this order; out is summed in this order
+ *           o = cb[i][p_i];
+ *           store[i] = o + (store[i] - o) * damp;   subtract, multiply, add: three roundings
+ *           cb[i][p_i] = in + store[i] * feedback;  multiply, add
+ *           advance p_i;  out = out + o;
+ *       }
+ *       for (j = 3; j >= 0; --j) {                  all-passes in series, in this order
+ *           o = ap[j][q_j];
+ *           ap[j][q_j] = out + o * 0.5f;
+ *           advance q_j;  out = o - out;
+ *       }
+ *       y[n] = in + out * wet;                      multiply, add
+ * y has S samples: the tail behind the clip's end is dropped.  A clip that takes neither step is copied bit for bit.
+ *
+ * THE PLAN is host arithmetic in IEEE double, rounded once where a float32 is stored, from sample_rate and the integer percentages
+ * reverberance, damping and room_scale (sox's parameters):
+ *       r = sample_rate / 44100            scale = room_scale / 100 * 0.9 + 0.1
+ *       comb[i] = (int)(scale * r * C[i] + 0.5),   C = {1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617}
+ *       allpass[j] = (int)(r * A[j] + 0.5),        A = {225, 341, 441, 556}
+ *       a = -1 / ln(1 - 0.3);   b = 100 / (ln(1 - 0.98) * a + 1);   feedback = 1 - exp((reverberance - b) / (a * b))
+ *       damp = damping / 100 * 0.3 + 0.2
+ * (feedback is 0.30 at 0 %, about 0.88 at 50 %, 0.98 at 100 %.)  Every length must be at least 1.  This restates sox's algorithm from
+ * its published form; sox is not part of this library's tests, so parity with sox itself is UNPINNED.  Left out: the two one-pole
+ * tone filters newer sox versions put behind the all-passes, stereo depth, pre-delay, wet-only mode and sox's drain tail.
+ *
+ * HOSTILE PLANS.  The plan arrays are device memory that the entry cannot see.  The kernel clamps each comb length into
+ * [1, cap_i], cap_i being the length at room_scale = 100 for the call's sample_rate; its LDS is laid out by those caps and the
+ * all-pass lengths, so whatever the plan holds it indexes nothing outside its own LDS, reads nothing outside x and the plan arrays'
+ * B (or 8 B) entries, and writes nothing outside y.  A sample_rate whose lines do not fit a workgroup's LDS budget (64 KB; 48 kHz
+ * takes about 55 KB) is refused with LEAF_ERR_UNSUPPORTED.
+ *
+ * The kernel (csrc/inst_clip_effects.hip; the arithmetic is csrc/leaf_clip_effects.hpp, host and device) walks a clip in chunks no
+ * longer than its shortest line: within a chunk the comb sum and the all-passes are elementwise over all lanes, and only the eight
+ * store[i] chains run in order, one lane each, several clips side by side in one wave.  The result is bit for bit the sequential
+ * definition above (no parallel scan: that would change the rounding).  No workspace, nothing read back, no host synchronisation:
+ * the launch captures into a graph.  tools/clip_effects_check.cpp runs the definition on the CPU.
+ *
+ * Alignment: 4 bytes for every array.  Status, in this order, before the launch: LEAF_ERR_NULL_POINTER (x, y; a reverb group given
+ * in part); LEAF_ERR_BAD_SHAPE (B < 1, S < 1, B * S >= 2^31, y overlapping x, or, with the reverb group, a sample_rate below 1 or one
+ * that makes a length 0); LEAF_ERR_ALIGNMENT; LEAF_ERR_UNSUPPORTED (the lines do not fit).  Without the reverb group sample_rate and
+ * wet are not looked at. */
+int leaf_clip_effects_f32(const float* x /*[B][S]*/, float* y /*[B][S]*/, int B, int S, const float* clip_factor /*[B] or NULL*/,
+                          const float* feedback /*[B] or NULL*/, const float* damp /*[B] or NULL*/, const int* comb /*[B][8] or NULL*/,
+                          int sample_rate, float wet, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

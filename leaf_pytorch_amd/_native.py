@@ -163,6 +163,9 @@ _SIGNATURES = {
     "leaf_resample_stream_step_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                                      ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    # ClipValue and the reverb: x, y, B, S, clip_factor, feedback, damp, comb, sample_rate, wet, stream
+    "leaf_clip_effects_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 4
+                              + [ctypes.c_int, ctypes.c_float, ctypes.c_void_p]),
     "leaf_fft_tables_bytes": (ctypes.c_size_t, [ctypes.c_int] * 3),
     "leaf_fft_prepare_tables_f32": (ctypes.c_int, [_f32p, _f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                                    ctypes.c_size_t, ctypes.c_void_p]),
@@ -1584,6 +1587,159 @@ def resample_stream_step(chunk_ptr: int, chunk_stride: int, slots, n_max: int, s
     words = table.on(device)
     _call(device, "leaf_resample_stream_step_f32", ctypes.c_void_p(chunk_ptr), chunk_stride, len(slots), ctypes.cast(slots, ctypes.c_void_p),
           n_max, state, state.numel(), flags, *key, words, words.numel() * 4, ctypes.c_void_p(out_ptr))
+
+
+REVERB_COMB_TUNING = (1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617)   # csrc/leaf_clip_effects.hpp (kFxCombTuning): Freeverb at 44.1 kHz
+REVERB_ALLPASS_TUNING = (225, 341, 441, 556)                              # ... (kFxAllpassTuning)
+REVERB_LDS_BUDGET = 64 * 1024                                             # ... (kFxLdsBudget): bytes of LDS a workgroup may take
+
+
+def reverb_lengths(sample_rate: int, room_scale=100):
+    """``(comb, allpass)``: the eight comb and four all-pass delay lengths of leaf_clip_effects_f32 at ``sample_rate`` for
+    ``room_scale`` percent, in double as include/leaf_hip.h states them (``room_scale=100`` gives the caps the kernel clamps a plan
+    into).  A length below 1 is a ValueError."""
+    sample_rate = int(sample_rate)
+    if sample_rate < 1:
+        raise ValueError(f"sample_rate must be at least 1, got {sample_rate}")
+    r = sample_rate / 44100
+    scale = float(room_scale) / 100 * 0.9 + 0.1
+    comb = [int(scale * r * c + 0.5) if scale * r * c + 0.5 >= 1 else 0 for c in REVERB_COMB_TUNING]
+    allpass = [int(r * a + 0.5) for a in REVERB_ALLPASS_TUNING]
+    if min(comb + allpass) < 1:
+        raise ValueError(f"sample_rate {sample_rate} with room_scale {room_scale} makes a delay line shorter than one sample")
+    if max(comb + allpass) >= 1 << 24:
+        raise ValueError(f"sample_rate {sample_rate} is beyond the reverb's delay lines")
+    return comb, allpass
+
+
+def _reverb_caps(sample_rate: int):
+    """The caps and all-pass lengths of a call, refused (ValueError) where the entry would refuse the rate."""
+    caps, allpass = reverb_lengths(sample_rate, 100)
+    if 4 * (sum(caps) + sum(allpass) + allpass[0]) > REVERB_LDS_BUDGET:
+        raise ValueError(f"sample_rate {sample_rate}: the reverb's delay lines do not fit a workgroup's LDS ({REVERB_LDS_BUDGET} bytes)")
+    return caps, allpass
+
+
+def _percentages(v, name: str):
+    if isinstance(v, torch.Tensor):
+        v = v.detach().reshape(-1).cpu().tolist()
+    elif not isinstance(v, (list, tuple)):
+        v = [v]
+    out = [float(e) for e in v]
+    if any(not (0.0 <= e <= 100.0) for e in out):
+        raise ValueError(f"{name} is a percentage in [0, 100]")
+    return out
+
+
+def reverb_plan(reverberance, damping, room_scale, sample_rate: int):
+    """The reverb plan of ``clip_effects`` from sox's parameters: ``(feedback (B,) float32, damp (B,) float32, comb (B, 8) int32)``,
+    CPU tensors.  ``reverberance``, ``damping`` and ``room_scale`` are percentages in [0, 100], tensors or sequences of B entries (or
+    single numbers); the arithmetic is host work in double, rounded once where float32 is stored (include/leaf_hip.h):
+    ``feedback = 1 - exp((reverberance - b) / (a b))`` with ``a = -1 / ln 0.7``, ``b = 100 / (ln 0.02 a + 1)``;
+    ``damp = damping / 100 * 0.3 + 0.2``; ``comb[i] = int(scale r C[i] + 0.5)``, ``scale = room_scale / 100 * 0.9 + 0.1``,
+    ``r = sample_rate / 44100``.  A length below 1 is a ValueError."""
+    rev, dmp, room = _percentages(reverberance, "reverberance"), _percentages(damping, "damping"), _percentages(room_scale, "room_scale")
+    if not len(rev) == len(dmp) == len(room):
+        raise ValueError(f"reverberance, damping and room_scale have {len(rev)}, {len(dmp)} and {len(room)} entries")
+    a = -1 / math.log(1 - 0.3)
+    b = 100 / (math.log(1 - 0.98) * a + 1)
+    fb_of, comb_of = {}, {}
+    for v in set(rev):
+        fb_of[v] = 1 - math.exp((v - b) / (a * b))
+    for v in set(room):
+        comb_of[v] = reverb_lengths(sample_rate, v)[0]
+    reverb_lengths(sample_rate, 100)                                            # (the all-pass lengths, also without a clip)
+    feedback = torch.tensor([fb_of[v] for v in rev], dtype=torch.float64).to(torch.float32)
+    damp = torch.tensor([v / 100 * 0.3 + 0.2 for v in dmp], dtype=torch.float64).to(torch.float32)
+    comb = torch.tensor([comb_of[v] for v in room], dtype=torch.int32).reshape(len(room), 8)
+    return feedback, damp, comb
+
+
+def _effects_f32(t, name: str, B: int) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t, dtype=torch.float32)
+    t = t.detach().reshape(-1)
+    if t.numel() != B:
+        raise ValueError(f"{name} has {t.numel()} entries, expected one per clip ({B})")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name} must be float32, got {t.dtype}")
+    return t
+
+
+def clip_effects_plan(B: int, clip_factor=None, reverb=None, sample_rate: int = 16000):
+    """The plan of ``clip_effects`` as flat tensors on the devices they arrived on: ``(clip_factor, feedback, damp, comb)``, None
+    for a step nobody takes.  Shapes and dtypes are checked wherever the arrays live.  An array that arrives on the CPU is validated
+    (ValueError, before anything is launched): ``clip_factor`` finite (negative: the clip skips ClipValue); ``comb`` rows either
+    skipped (``comb[b][0] <= 0``) or with every length in [1, cap_i], the lengths at ``room_scale = 100``; ``feedback`` in [0, 1) and
+    ``damp`` in [0, 1] for the rows that are not skipped (when ``comb`` is on the CPU too: all rows otherwise).  A device-side array
+    is not read back and the kernel clamps its lengths.  With ``reverb``, a ``sample_rate`` whose lines are shorter than one sample or
+    do not fit LDS is a ValueError."""
+    if clip_factor is not None:
+        clip_factor = _effects_f32(clip_factor, "clip_factor", B)
+        if clip_factor.device.type == "cpu" and B and not bool(torch.isfinite(clip_factor).all()):
+            raise ValueError("clip_factor holds a value that is not finite")
+    if reverb is None:
+        return clip_factor, None, None, None
+    if len(reverb) != 3:
+        raise ValueError("reverb must be (feedback, damp, comb)")
+    caps, _ = _reverb_caps(sample_rate)
+    feedback, damp = _effects_f32(reverb[0], "feedback", B), _effects_f32(reverb[1], "damp", B)
+    comb = reverb[2] if isinstance(reverb[2], torch.Tensor) else torch.as_tensor(reverb[2], dtype=torch.int32)
+    if comb.dtype.is_floating_point or comb.dtype.is_complex or comb.dtype == torch.bool:
+        raise TypeError(f"comb must be an integer tensor, got {comb.dtype}")
+    if tuple(comb.shape) != (B, 8):
+        raise ValueError(f"comb has shape {tuple(comb.shape)}, expected ({B}, 8): eight delay lengths per clip")
+    comb = comb.detach()
+    live = None
+    if comb.device.type == "cpu" and B:
+        live = comb[:, 0] > 0
+        rows = comb[live].long()
+        if bool(((rows < 1) | (rows > torch.tensor(caps))).any()):
+            raise ValueError(f"comb holds a delay length outside [1, cap] (the caps at {sample_rate} Hz: {caps})")
+    for t, name, hi_ok in ((feedback, "feedback", False), (damp, "damp", True)):
+        if t.device.type == "cpu" and B:
+            v = t if live is None else t[live]
+            if not bool(((v >= 0) & ((v <= 1) if hi_ok else (v < 1))).all()):
+                raise ValueError(f"{name} holds a value outside [0, 1{']' if hi_ok else ')'}")
+    return clip_factor, feedback, damp, comb
+
+
+def clip_effects(x: torch.Tensor, clip_factor=None, reverb=None, sample_rate: int = 16000, wet: float = 0.015,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ClipValue and the sox-style reverb on a batch, one launch (leaf_clip_effects_f32, where both are stated bit for bit).  ``x``:
+    contiguous float32 ``(B, 1, S)`` or ``(B, S)`` on a HIP device; the result has its shape (``out``, distinct from ``x``, is
+    written when given).  ``clip_factor``: B float32 factors -- the clip is clamped into ``[min(x) * factor, max(x) * factor]``, a
+    negative factor leaves it alone.  ``reverb`` = (feedback (B,) float32, damp (B,) float32, comb (B, 8) int32), what ``reverb_plan``
+    returns; ``comb[b][0] <= 0`` leaves clip b alone.  The all-pass lengths follow from ``sample_rate``; ``wet`` scales the
+    reverberated signal that is added to the dry one.  The plan arrays may live on either side: on the CPU they are validated
+    (``clip_effects_plan``) and copied over, on the device they are used as they are and the kernel clamps the lengths -- nothing is
+    read back, so the call captures into a graph.  Parity with sox itself is unpinned (sox is not in this image)."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous() or not (
+            x.dim() == 2 or (x.dim() == 3 and x.shape[1] == 1)):
+        raise RuntimeError("clip_effects: x must be a contiguous float32 (B, 1, S) or (B, S) tensor")
+    B, S = x.shape[0], x.shape[-1]
+    if S < 1 or B * S >= CALL_SAMPLES:
+        raise ValueError(f"clip_effects: S must be at least 1 and B * S below 2^31, got B = {B}, S = {S}")
+    wet = float(wet)
+    if not math.isfinite(wet):
+        raise ValueError(f"wet must be finite, got {wet}")
+    clip_factor, feedback, damp, comb = clip_effects_plan(B, clip_factor, reverb, sample_rate)
+    require_hip(x, "clip_effects")
+    dev = x.device
+    x = x.detach()
+    if out is not None:
+        _check_out(out, tuple(x.shape), torch.float32, dev)
+        lo, hi = out.data_ptr(), x.data_ptr()
+        if lo < hi + 4 * B * S and hi < lo + 4 * B * S:
+            raise ValueError("clip_effects: out must not overlap x")
+    else:
+        out = torch.empty_like(x)
+    if B == 0:
+        return out
+    on = lambda t, dtype: None if t is None else t.to(device=dev, dtype=dtype).contiguous()
+    _call(dev, "leaf_clip_effects_f32", x, out, B, S, on(clip_factor, torch.float32), on(feedback, torch.float32), on(damp, torch.float32),
+          on(comb, torch.int32), int(sample_rate), wet)
+    return out
 
 
 def prepare_tables(kernel: torch.Tensor, pool_w: torch.Tensor, K: int, hop: int) -> Optional[torch.Tensor]:

@@ -480,7 +480,8 @@ class ClipSampler:
       ``ClipNoisePlan`` then) and the batch is assembled from the standardised recordings (``PackedClips.assemble(...,
       standardize=True)``).  A sampler without it draws and returns what it always did.
 
-    Left out: ClipValue and RandomReverb, which the reference itself has switched off."""
+    ClipValue and RandomReverb, which the reference itself has switched off, are ``EffectsClipSampler``'s: a launch of their own
+    between two launches of this sampler's kernel."""
 
     def __init__(self, clips: PackedClips, size: int, train: bool = True, pad_modes=("replicate", "min"), wrap_pad_prob: float = 0.5,
                  gain_prob: float = 0.25, gain_db=(-18.0, 6.0), peak_normalize: bool = True, time_perc: float = 0.0, num_masks: int = 0,
@@ -566,6 +567,89 @@ class ClipSampler:
                                       noise=None if noise is None else (self.noise_clips.store,) + tuple(noise),
                                       gaussian=getattr(plan, "gaussian", None),
                                       standardize=None if rec is None else (self.clips.moments(), rec))
+
+
+clip_effects = _native.clip_effects
+reverb_plan = _native.reverb_plan
+
+
+class ClipEffectsPlan(ClipNoisePlan):
+    """A ``ClipNoisePlan`` (the same six entries, ``noise`` / ``gaussian`` / ``rec`` as the parent sampler fills them) that carries
+    the effect draws: ``clip_factor`` (B,) float32, negative for a clip without ClipValue, and ``reverb`` = (feedback (B,) float32,
+    damp (B,) float32, comb (B, 8) int32), all zero for a clip without reverb -- the arguments of ``clip_effects``."""
+    clip_factor = None
+    reverb = None
+
+
+class EffectsClipSampler(ClipSampler):
+    """``ClipSampler`` with the two transforms the reference's get_raw_transforms_v2 holds between AddRandomNoise and RandomGain and
+    has switched off -- ClipValue ("needs work") and RandomReverb ("TOO SLOW": sox's reverb per clip on the CPU) -- run on the device
+    by ``clip_effects`` (leaf_clip_effects_f32, where both are stated bit for bit).  Keywords and defaults beyond ``ClipSampler``'s are
+    the reference's:
+
+    - ClipValue under ``clip_prob``: the clip is clamped into ``[min(x) * f, max(x) * f]``, ``f = uniform(0, max_clip_val)``.
+    - RandomReverb under ``reverb_prob``: three inclusive integer draws, reverberance from ``reverb_range``, damping from
+      ``damping_range`` and room scale from ``room_scale_range`` (percent), turned into the kernel's plan by ``reverb_plan`` at
+      ``sample_rate``.  This restates sox's published algorithm; neither sox nor ``augment`` is in this image, so parity with sox is
+      unpinned (as RandomGain's and PeakNormalization's is).  Left out: sox's tone filters, stereo depth, pre-delay, wet-only mode
+      and the drain tail -- the batch keeps ``size`` samples.
+
+    ``plan(index)`` makes ``ClipSampler``'s draws first and unchanged, then the effects' (ClipValue: apply flag, factor; reverb: apply
+    flag, the three integers): from one generator state the parent's part of the plan is what ``ClipSampler`` draws.  It returns a
+    ``ClipEffectsPlan``.  ``__call__`` is three launches in the reference's order: the assemble with pad / crop, background noise and
+    standardisation only; ``clip_effects``; and the assemble again over that batch viewed as a packed store, which carries the gain,
+    the Gaussian noise, the peak normalisation and the masks.  With both probabilities 0 the batch is bit for bit ``ClipSampler``'s."""
+
+    def __init__(self, clips: PackedClips, size: int, *args, clip_prob: float = 0.0, max_clip_val: float = 0.2, reverb_prob: float = 0.0,
+                 reverb_range=(10, 50), damping_range=(10, 50), room_scale_range=(0, 100), sample_rate: int = 16000, **kwargs):
+        super().__init__(clips, size, *args, **kwargs)
+        self.clip_prob, self.max_clip_val, self.reverb_prob = float(clip_prob), float(max_clip_val), float(reverb_prob)
+        if not (self.max_clip_val >= 0.0 and self.max_clip_val < float("inf")):
+            raise ValueError(f"max_clip_val must be finite and at least 0, got {max_clip_val}")
+        ranges = []
+        for name, r in (("reverb_range", reverb_range), ("damping_range", damping_range), ("room_scale_range", room_scale_range)):
+            lo, hi = int(r[0]), int(r[1])
+            if not 0 <= lo <= hi <= 100:
+                raise ValueError(f"{name} must be two integer percentages 0 <= lo <= hi <= 100, got {tuple(r)}")
+            ranges.append((lo, hi))
+        self.reverb_range, self.damping_range, self.room_scale_range = ranges
+        self.sample_rate = int(sample_rate)
+        _native._reverb_caps(self.sample_rate)                                  # (ValueError for a rate the launch would refuse)
+        _native.reverb_lengths(self.sample_rate, self.room_scale_range[0])
+
+    def _integers(self, B: int, lo: int, hi: int) -> torch.Tensor:
+        return torch.randint(lo, hi + 1, (B,), generator=self.generator)
+
+    def plan(self, index) -> ClipEffectsPlan:
+        base = super().plan(index)
+        plan = ClipEffectsPlan(tuple(base))
+        plan.noise, plan.gaussian, plan.rec = getattr(base, "noise", None), getattr(base, "gaussian", None), getattr(base, "rec", None)
+        B = base.rec_off.numel()
+        apply = self._uniform(B) < self.clip_prob                               # ClipValue
+        factor = self._uniform(B) * self.max_clip_val
+        plan.clip_factor = torch.where(apply, factor, -1.0).to(torch.float32)
+        apply = self._uniform(B) < self.reverb_prob                             # RandomReverb
+        rev, dmp, room = (self._integers(B, *r) for r in (self.reverb_range, self.damping_range, self.room_scale_range))
+        feedback, damp, comb = _native.reverb_plan(rev, dmp, room, self.sample_rate)
+        zero = torch.zeros((), dtype=torch.float32)
+        plan.reverb = (torch.where(apply, feedback, zero), torch.where(apply, damp, zero), torch.where(apply.reshape(-1, 1), comb, 0).to(torch.int32))
+        return plan
+
+    def __call__(self, index, out=None) -> torch.Tensor:
+        plan = self.plan(index)
+        rec_off, rec_len, start, pad_mode, gain, masks = plan
+        B, S = rec_off.numel(), self.size
+        # 1. pad / crop, background noise, standardisation: gain 1, no Gaussian noise, no peak normalisation, no masks
+        raw = _native.assemble_clips(self.clips.store, rec_off, rec_len, start, pad_mode, S, None, False, None, None,
+                                     noise=None if plan.noise is None else (self.noise_clips.store,) + tuple(plan.noise),
+                                     standardize=None if plan.rec is None else (self.clips.moments(), plan.rec))
+        # 2. ClipValue and the reverb
+        wet = _native.clip_effects(raw, plan.clip_factor, plan.reverb, self.sample_rate)
+        # 3. gain, Gaussian noise, peak normalisation, masks: the batch as a packed store of B recordings of S samples
+        rows = torch.arange(B, dtype=torch.int64)
+        whole, zeros = torch.full((B,), S, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)
+        return _native.assemble_clips(wet.reshape(-1), rows * S, whole, zeros, zeros, S, gain, self.peak_normalize, masks, out,
+                                      gaussian=plan.gaussian)
 
 
 class DeviceClipSampler:

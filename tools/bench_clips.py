@@ -9,6 +9,7 @@ multiply by the gain, transforms.PeakNormalization, one masked_fill per span.
     python tools/bench_clips.py --standardize [--out profiles/clip_standardize.txt]
     python tools/bench_clips.py --device-draws [--out profiles/clip_device_draws.txt]
     python tools/bench_clips.py --device-mixup [--out profiles/clip_device_mixup.txt]
+    python tools/bench_clips.py --effects [--out profiles/clip_effects.txt]
 
 Both sides run in ONE process on the same store and the same plan (already on the device: drawing it is not timed), taking turns
 round after round after a warm-up round, the order alternating.  Every recording is longer than the clip, so the batch is a crop
@@ -63,7 +64,15 @@ it was); `device`, DeviceMixup.__call__ (leaf_draw_mixup into the mixer's static
 with torch.cuda.graph; and `argsort`, torch.argsort of B 64-bit keys on the device, the stock form of the kernel's sort alone (device
 time).  Rounds as for --device-draws.  Before anything is timed the replayed draw is compared bit for bit with the eager draw of a second
 mixer of the same seed at the same step, and checked to be a permutation with weights in [0, 1].  No verdict column: the file records
-what was measured."""
+what was measured.
+
+--effects times ClipValue and the reverb (leaf_clip_effects_f32): B = 64 / 256 clips of 16 000 samples at 16 kHz, both stores.  Three
+sides take turns: `effects`, EffectsClipSampler.__call__ with a CPU index and every clip clipped and reverberated (its draws on the
+host, then assemble, effects, assemble: three launches); `plain`, ClipSampler.__call__ with the same keywords otherwise (one launch);
+and `launch`, _native.clip_effects alone on a batch and a plan that are on the device already (its device time is the kernel's).
+A round is --steps calls (default here: 20).  Before anything is timed the launch is checked to change every clip and to leave a
+batch with an all-skip plan bit for bit alone.  The last line is the sequential definition on the CPU (tools/clip_effects_check.cpp
+built with g++ -O2, one core): the per-clip time the reference's "TOO SLOW" is about, for context.  No verdict column."""
 import argparse
 import os
 import statistics
@@ -403,6 +412,61 @@ def device_mixup_legs(args, busy, busy_out):
     return lines
 
 
+def effects_legs(args, busy, busy_out):
+    import shutil
+    import subprocess
+    import tempfile
+    from leaf_pytorch_amd import ClipSampler, EffectsClipSampler
+    S, rate = 16000, 16000
+    steps = args.steps if args.steps_given else 20
+    lines = [f"# {torch.cuda.get_device_name(0)}; torch {torch.__version__}; {args.rounds} timed rounds x {steps} calls per side after a "
+             "warm-up round; us per call: median [min, max]; device = HIP events, calls queued behind a matrix product; wall = host clock to a "
+             "synchronise every round; effects = EffectsClipSampler.__call__ (clip_prob = reverb_prob = 1), plain = ClipSampler.__call__, "
+             "launch = _native.clip_effects alone on device-resident plan and batch",
+             f"{'store':>8} {'B':>4} {'S':>6} | {'effects wall':>26} {'effects device':>26} | {'plain wall':>26} {'plain device':>26} | "
+             f"{'launch device':>26} {'launch wall':>12} {'us/clip':>8}"]
+    for dtype in (torch.int16, torch.float32):
+        for B in (64, 256):
+            g = torch.Generator().manual_seed(B)
+            lengths = torch.randint(S + 1, 3 * S, (B,), generator=g)
+            n = int(lengths.sum())
+            store = (torch.randint(-32768, 32768, (n,), generator=g).to(torch.int16) if dtype == torch.int16 else torch.rand(n, generator=g) * 2 - 1)
+            clips = PackedClips.from_store(store.to(DEV), torch.cumsum(lengths, 0) - lengths, lengths)
+            index = torch.arange(B)
+            kw = dict(num_masks=M, time_perc=0.1, gain_prob=0.5)
+            fx = EffectsClipSampler(clips, S, generator=torch.Generator().manual_seed(1), clip_prob=1.0, reverb_prob=1.0, sample_rate=rate, **kw)
+            plain = ClipSampler(clips, S, generator=torch.Generator().manual_seed(1), **kw)
+            out_fx, out_plain = (torch.empty((B, 1, S), dtype=torch.float32, device=DEV) for _ in range(2))
+            plan = fx.plan(index)
+            batch = plain(index).clone()
+            factor, reverb = plan.clip_factor.to(DEV), tuple(t.to(DEV) for t in plan.reverb)
+            out_launch = torch.empty_like(batch)
+            wet = _native.clip_effects(batch, factor, reverb, rate, out=out_launch)
+            skip = _native.clip_effects(batch, torch.full((B,), -1.0, device=DEV), tuple(torch.zeros_like(t) for t in reverb), rate)
+            torch.cuda.synchronize()
+            if not torch.equal(skip.view(torch.int32), batch.view(torch.int32)) or bool((wet == batch).flatten(1).all(1).any()):
+                sys.exit(f"the launch does not do what it is timed for at {dtype} B={B}: nothing is timed")
+            sides = {"effects": lambda: fx(index, out=out_fx), "plain": lambda: plain(index, out=out_plain),
+                     "launch": lambda: _native.clip_effects(batch, factor, reverb, rate, out=out_launch)}
+            dev_us, wall_us = time_sides(sides, args.rounds, steps, busy, busy_out)
+            fmt = lambda v: f"{statistics.median(v):9.1f} [{min(v):6.1f},{max(v):7.1f}]"
+            lines.append(f"{str(dtype).replace('torch.', ''):>8} {B:>4} {S:>6} | {fmt(wall_us['effects']):>26} {fmt(dev_us['effects']):>26} | "
+                         f"{fmt(wall_us['plain']):>26} {fmt(dev_us['plain']):>26} | {fmt(dev_us['launch']):>26} "
+                         f"{statistics.median(wall_us['launch']):12.1f} {statistics.median(dev_us['launch']) / B:8.2f}")
+            print(lines[-1], flush=True)
+    cxx = shutil.which("g++")
+    if cxx is None:
+        lines.append("# CPU: NOT MEASURED (no g++ on this machine)")
+    else:
+        with tempfile.TemporaryDirectory() as tmp:
+            exe = os.path.join(tmp, "clip_effects_check")
+            subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-I", os.path.join(REPO, "leaf_pytorch_amd", "csrc"),
+                            os.path.join(REPO, "tools", "clip_effects_check.cpp"), "-o", exe], check=True)
+            run = subprocess.run([exe, "time", str(S), "64"], capture_output=True, text=True, check=True)
+        lines.append("# CPU, the sequential definition (tools/clip_effects_check.cpp, g++ -O2 -ffp-contract=off, one core): " + run.stdout.strip())
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=20)
@@ -415,13 +479,15 @@ def main():
                                                                 "(profiles/clip_device_draws.txt)")
     ap.add_argument("--device-mixup", action="store_true", help="time mixup's draws: Mixup's on the host, DeviceMixup, the captured graph, "
                                                                 "torch.argsort (profiles/clip_device_mixup.txt)")
+    ap.add_argument("--effects", action="store_true", help="time ClipValue and the reverb: EffectsClipSampler, ClipSampler, the launch alone, "
+                                                           "the CPU program (profiles/clip_effects.txt)")
     args = ap.parse_args()
     args.steps_given = any(a == "--steps" or a.startswith("--steps=") for a in sys.argv[1:])
     if not torch.cuda.is_available():
         sys.exit("bench_clips.py needs the GPU: a time taken anywhere else says nothing about it")
-    if args.noise or args.segments or args.standardize or args.device_draws or args.device_mixup:
+    if args.noise or args.segments or args.standardize or args.device_draws or args.device_mixup or args.effects:
         busy = torch.rand(8192, 8192, device=DEV)
-        legs = device_mixup_legs if args.device_mixup else device_draw_legs if args.device_draws else (standardize_legs if args.standardize else (segment_legs if args.segments else noise_legs))
+        legs = effects_legs if args.effects else device_mixup_legs if args.device_mixup else device_draw_legs if args.device_draws else (standardize_legs if args.standardize else (segment_legs if args.segments else noise_legs))
         text = "\n".join(legs(args, busy, torch.empty_like(busy))) + "\n"
         print(text)
         if args.out:
